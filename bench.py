@@ -16,6 +16,10 @@ one-shot exchange kernel, or as RCCL's all-reduce - whichever verifies, in that 
 Total work is fixed (26 000 evals per step): strong scaling.  (`--weak`: 40 pieces per rank instead.)
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 via torch.distributed.run (one rank per GPU).
+A plain run sets up, warms up, times the K steps and prints the headline line (`--dump-outputs DIR`: also the last timed step's
+[cost | gradT | gradC] as DIR/{cost,grad_T,grad_C}.npy).  `--full` adds everything else - the kernel-duration pass, the
+steady-state run, the roofline, the other configurations, the host-API boundary, L-BFGS, the CPU baseline and parity, the N > 1
+comparisons - and prints the compact record of all of it.
 """
 import argparse
 import hashlib
@@ -58,7 +62,11 @@ def main():
     ap.add_argument("--lbfgs-iters", type=int, default=40, help="iterations of the L-BFGS driver timed after the sweep (0: skip)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--steady-steps", type=int, default=3000, help="steps of the extra steady-state measurement `value_steady` (0: skip)")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline (the options above that tune those extras apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -175,15 +183,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return int(t.item()) != 0
 
-    # ---- duration of the dominant kernel, in a SEPARATE pass (events attached to every dispatch cost the stream 1-3 us each),
-    # BEFORE the timed region: the process has spent seconds building the map on the CPU, and the pass doubles as the first GPU
-    # activity of the run (the timed region below is still exactly W warm-up + K timed steps of the plain step)
-    eng.profile_enable(1)
-    for _ in range(40):
-        eval_only()
-    torch.cuda.synchronize()
-    n_launch, kern_ms_dispatch = eng.profile_read()
-    eng.profile_enable(0)
+    # ---- --full: duration of the dominant kernel, in a SEPARATE pass (events attached to every dispatch cost the stream 1-3 us
+    # each), BEFORE the timed region: the process has spent seconds building the map on the CPU, and the pass doubles as the first
+    # GPU activity of the run (the timed region below is still exactly W warm-up + K timed steps of the plain step)
+    if args.full:
+        eng.profile_enable(1)
+        for _ in range(40):
+            eval_only()
+        torch.cuda.synchronize()
+        n_launch, kern_ms_dispatch = eng.profile_read()
+        eng.profile_enable(0)
 
     mode = "none" if world == 1 else ("fused" if in_kernel else ("xchg" if xchg else "rccl"))
     names = {"none": "none", "fused": "in-kernel peer-to-peer exchange over xGMI (rows stored into the peers' outputs by the owning workgroups of the step's launches), verified against RCCL at start-up",
@@ -208,8 +217,28 @@ def main():
     evals_per_step = N * (K + 1)
     value = evals_per_step * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    out_gpu = d_out.cpu().numpy().copy()        # the last timed step's [cost | gradT | gradC] (every rank holds the sum)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("cost", out_gpu[:1]), ("grad_T", out_gpu[1:1 + N]), ("grad_C", out_gpu[1 + N:1 + 19 * N])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    headline = {
+        "metric": "SDF cost+grad point-evals/sec", "value": round(value, 1), "unit": "point-evals/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"V3 ESDF-tile sweep: 1 trajectory x {N} pieces x {K + 1} samples/piece, {args.grid}^3 fp32 ESDF "
+                               f"@ {res:g} m, kernel_size {args.kernel_size}, box robot (1.6,0.3,0.3) central-diff grad, "
+                               f"occ_thresh = 0, cull {'on' if args.cull else 'off'}"
+                               + (" = BASELINE configs[1]" if (world == 1 and N == 40) else "")
+                               + ("" if world == 1 else (f" = BASELINE configs[3], {N // world}-{-(-N // world)} pieces per rank" if N == 400 else ""))
+                               + ("" if world == 1 else "; the --gpus 1 line is configs[1] (another workload): read `speedup`, not value(N)/value(1)"),
+                   "pieces": N, "samples_per_piece": K + 1, "grid": args.grid, "kernel_size": args.kernel_size,
+                   "sharding": ("none" if world == 1 else ("pieces contiguous by rank; each piece's 19 rows + cost stored by its owner into every peer's output inside the step's launches" if mode == "fused" else "pieces contiguous by rank + all_reduce(sum) of 1+19N doubles")),
+                   "collective": collective}}
+    if not args.full:
+        finish(json.dumps(headline) if rank == 0 else None, world)
+        return
     stats = eng.stats()
-    out_gpu = d_out.cpu().numpy().copy()
     # the driver's 20-step region lasts half a millisecond, right after start-up (clocks still ramping): the same step over a
     # region long enough to be in steady state, as an EXTRA key - `value` stays what the K steps measured
     value_steady = None
@@ -473,27 +502,15 @@ def main():
                       "v3mesh_issue_frac": _frac(lambda n: "MESH robot (blob, 720" in n, "roofline"),
                       "v1_issue_frac": _frac(lambda n: n.startswith("V1 swept-volume sweep") and "rounded cone" in n, "roofline_issue"),
                       "v1mesh_issue_frac": _frac(lambda n: n.startswith("C5 (configs[4]) shape") and "720" in n, "roofline_issue")}
-        result = {
-            "metric": "SDF cost+grad point-evals/sec", "value": round(value, 1), "unit": "point-evals/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"V3 ESDF-tile sweep: 1 trajectory x {N} pieces x {K + 1} samples/piece, {args.grid}^3 fp32 ESDF "
-                                   f"@ {res:g} m, kernel_size {args.kernel_size}, box robot (1.6,0.3,0.3) central-diff grad, "
-                                   f"occ_thresh = 0, cull {'on' if args.cull else 'off'}"
-                                   + (" = BASELINE configs[1]" if (world == 1 and N == 40) else "")
-                                   + ("" if world == 1 else (f" = BASELINE configs[3], {N // world}-{-(-N // world)} pieces per rank" if N == 400 else ""))
-                                   + ("" if world == 1 else "; the --gpus 1 line is configs[1] (another workload): read `speedup`, not value(N)/value(1)"),
-                       "pieces": N, "samples_per_piece": K + 1, "grid": args.grid, "kernel_size": args.kernel_size,
-                       "sharding": ("none" if world == 1 else ("pieces contiguous by rank; each piece's 19 rows + cost stored by its owner into every peer's output inside the step's launches" if mode == "fused" else "pieces contiguous by rank + all_reduce(sum) of 1+19N doubles")),
-                       "collective": collective,
-                       "rccl_all_reduce_ms_per_step": None if rccl_ms is None else round(rccl_ms, 5),
-                       "group": rccl_seen},
+        result = dict(headline)
+        result["config"] = dict(headline["config"], rccl_all_reduce_ms_per_step=None if rccl_ms is None else round(rccl_ms, 5), group=rccl_seen)
+        result.update({
             "roofline": roofline, "roofline_issue": issue, "cpu_baseline": cpu, "configs": extra,
             "one_gpu_same_workload": one_gpu, "speedup": None if one_gpu is None else round(value / one_gpu["evals_per_s"], 3),
             "value_steady": value_steady, "parity_rel_err_vs_oracle": parity, "host_api_ms": None if host_ms is None else round(host_ms, 4), "host_api_timer": host_timer,
             "host_api_ms_two_shards_one_gpu": host_ms_multi, "host_api_ms_eight_shards_one_gpu": host_ms_multi8, "host_queue_ms_eight_shards_one_gpu": host_queue_multi8,
             "stats_last_step_rank0": stats, "lbfgs": lbfgs, "hbm_copy_gbs_measured": hbm_copy,
-        }
+        })
         result.update(issue_keys)
         # the long form (every entry with its prose) goes to a file; the ONE printed line is the compact record (< 4 KB: the driver
         # keeps an 8 KB tail of stdout - round 5's 21 KB line could not be parsed)
@@ -508,8 +525,15 @@ def main():
             result["detail_file"] = None
         line = json.dumps(compact_line(result))
         assert len(line) < MAX_LINE, len(line)
+    finish(line if rank == 0 else None, world)
+
+
+def finish(line, world):
+    """Prints the ONE result line (rank 0 passes it, the other ranks None) and leaves the process group."""
+    if line is not None:
         print(line, flush=True)
     if world > 1:
+        import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
 

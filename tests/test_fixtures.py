@@ -1,7 +1,10 @@
 """The library's readers for the reference's OWN input files (csrc/fixtures.hip: ASCII .pcd, Wavefront .obj through the
-Generalshape constructor's transform, the flat yaml configs) against independent numpy parsing of the files under
-/root/reference/src/plan_manager, and the committed demo fixtures (tests/golden/ref_demo_inputs.npz, made by
-tests/golden/make_golden_demo.py from those files) - CPU only, no device needed."""
+Generalshape constructor's transform, the flat yaml configs) against independent numpy parsing of the files of the reference's
+src/plan_manager, and the committed demo fixtures (tests/golden/ref_demo_inputs.npz, made by tests/golden/make_golden_demo.py
+from those files) - CPU only, no device needed.  The files themselves are rebuilt from tests/golden/ref_demo_files.npz (each
+.pcd byte for byte: its sha256 is checked), so the tests need nothing outside the repository."""
+import hashlib
+import lzma
 import math
 import os
 
@@ -9,9 +12,31 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PM = "/root/reference/src/plan_manager"
 GOLD = os.path.join(ROOT, "tests", "golden", "ref_demo_inputs.npz")
-need_ref = pytest.mark.skipif(not os.path.isdir(PM), reason="/root/reference not present (GPU box): the golden fixtures cover it")
+FILES = os.path.join(ROOT, "tests", "golden", "ref_demo_files.npz")
+PCD_STEP = 0.00025      # grid of the maps stored as indices (tests/golden/make_golden_demo.py)
+
+
+@pytest.fixture(scope="session")
+def PM(tmp_path_factory):
+    """The reference's src/plan_manager files these tests read (map_pcds/, shapes/, config/), rebuilt from the golden data."""
+    pm = tmp_path_factory.mktemp("plan_manager")
+    g, gold = np.load(FILES), np.load(GOLD)
+    for key in g.files:
+        if not key.startswith("pcd/"):
+            os.makedirs(pm / os.path.dirname(key), exist_ok=True)
+            (pm / key).write_bytes(g[key].tobytes())
+    os.makedirs(pm / "map_pcds")
+    for name in sorted({k.split("/")[1] for k in g.files if k.startswith("pcd/")}):
+        if name == "CappedCone":
+            xyz = gold["CappedCone_xyz"]
+        else:
+            dk = np.frombuffer(lzma.decompress(g[f"pcd/{name}/dk"].tobytes()), dtype=np.int32).reshape(3, -1).T
+            xyz = (np.cumsum(dk, axis=0, dtype=np.int64) * PCD_STEP).astype(np.float32)
+        raw = g[f"pcd/{name}/header"].tobytes() + "".join(" ".join("%.8g" % v for v in r) + "\n" for r in xyz.astype(np.float64)).encode()
+        assert hashlib.sha256(raw).hexdigest() == str(g[f"pcd/{name}/sha256"]), name
+        (pm / "map_pcds" / (name + ".pcd")).write_bytes(raw)
+    return str(pm)
 
 
 def _eigen_rotate(pp):
@@ -31,8 +56,7 @@ def _eigen_rotate(pp):
     return aa(pp[5] * PI / 180.0, 2) @ aa(pp[4] * PI / 180.0, 1) @ aa(pp[3] * PI / 180.0, 0)
 
 
-@need_ref
-def test_pcd_reader_vs_numpy_and_the_voxel_grid_of_demo1(pkg, orc, product_lib):
+def test_pcd_reader_vs_numpy_and_the_voxel_grid_of_demo1(pkg, orc, product_lib, PM):
     fx = pkg.fixtures
     path = os.path.join(PM, "map_pcds", "CappedCone.pcd")
     xyz = fx.read_pcd(path)
@@ -50,9 +74,8 @@ def test_pcd_reader_vs_numpy_and_the_voxel_grid_of_demo1(pkg, orc, product_lib):
         assert a.shape[0] == int(hdr.split()[1])
 
 
-@need_ref
 @pytest.mark.parametrize("name,nv,nf", [("Lthick", 60, 20), ("mybox", 8, 12), ("RoundedCone", None, None)])
-def test_obj_reader_and_body_transform(pkg, product_lib, name, nv, nf):
+def test_obj_reader_and_body_transform(pkg, product_lib, name, nv, nf, PM):
     fx = pkg.fixtures
     path = os.path.join(PM, "shapes", name + ".obj")
     V, F = fx.read_obj(path)
@@ -76,8 +99,7 @@ def test_obj_reader_and_body_transform(pkg, product_lib, name, nv, nf):
     assert np.array_equal(W0, V) and np.array_equal(R0, np.eye(3))
 
 
-@need_ref
-def test_yaml_configs(pkg, product_lib):
+def test_yaml_configs(pkg, product_lib, PM):
     fx, capi = pkg.fixtures, pkg.capi
     p = fx.load_yaml_config(os.path.join(PM, "config", "config_CappedCone.yaml"))      # demo1.launch:22
     s = p.sweep
@@ -105,8 +127,8 @@ def test_yaml_configs(pkg, product_lib):
 
 
 def test_golden_demo_fixtures_are_self_consistent(pkg, orc):
-    """What travels to the GPU box: the point cloud of demo1's map, the transformed vertices of demo6's robot and the yaml
-    values - readable without /root/reference."""
+    """What the GPU tests use: the point cloud of demo1's map, the transformed vertices of demo6's robot and the yaml
+    values - readable without the reference."""
     g = np.load(GOLD)
     assert g["CappedCone_xyz"].dtype == np.float32 and g["CappedCone_xyz"].shape == (80107, 3)
     occ, bmin, bmax = orc.pointcloud_to_occupancy(g["CappedCone_xyz"], 1.0, 1)

@@ -7,9 +7,10 @@ cd $REPO
 bash tools/profile_round.sh $TAG > gpurun_out/${TAG}_profile_round.log 2>&1
 for c in c3 v1 v1mesh v3mesh; do bash tools/profile_cfg.sh $TAG $c > gpurun_out/${TAG}_profile_cfg_$c.log 2>&1; done
 cd $REPO
+OUT=$REPO/$(sed -n 's|^OUT=\$REPO/||p' tools/profile_round.sh)       # the output directory of tools/profile_round.sh
 for n in 2 8; do
-  ISDF_BENCH_SINGLE_DEVICE=1 ISDF_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29510 + n)) bench.py --gpus $n --steps 200 --warmup 20 > gpurun_out/${TAG}_bench_${n}ranks_one_gpu.log 2>&1
-  grep '^{' gpurun_out/${TAG}_bench_${n}ranks_one_gpu.log | tail -1 > gpurun_out/${TAG}_bench_${n}ranks_one_gpu.json
+  ISDF_BENCH_SINGLE_DEVICE=1 ISDF_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29510 + n)) bench.py --full --gpus $n --steps 200 --warmup 20 > $OUT/${TAG}_bench_${n}ranks_one_gpu.log 2>&1
+  grep '^{' $OUT/${TAG}_bench_${n}ranks_one_gpu.log | tail -1 > $OUT/${TAG}_bench_${n}ranks_one_gpu.json
 done
 # the ESDF point sampler: measured HBM bytes (separate FETCH_SIZE / WRITE_SIZE passes) next to its algorithmic 88 B per point
 ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/pe_f /tmp/pe_w

@@ -8,8 +8,8 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --steps 200 --warmup 20 --no-cpu-baseline --lbfgs-iters 0 --no-extra-configs --no-host-api"
-BENCHS="python $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --lbfgs-iters 0 --no-extra-configs --no-host-api"
+BENCH="python $REPO/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --lbfgs-iters 0 --no-extra-configs --no-host-api"
+BENCHS="python $REPO/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --lbfgs-iters 0 --no-extra-configs --no-host-api"
 finddb() { find "$1" -name "*results.db" | head -1; }
 rm -rf /tmp/prof_kt /tmp/prof_f /tmp/prof_w /tmp/prof_sq /tmp/prof_sq2 /tmp/prof_sq3
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -- $BENCH > $OUT/${TAG}_bench_under_rocprof.log 2>&1
@@ -27,7 +27,7 @@ python $REPO/tools/pmc_sq.py "$(finddb /tmp/prof_sq3)" $OUT/${TAG}_pmc_sq3.txt "
 python $REPO/tools/pmc_collect.py $OUT/${TAG}_pmc_counters.json "$(finddb /tmp/prof_kt)" "$(finddb /tmp/prof_f)" "$(finddb /tmp/prof_w)" "$(finddb /tmp/prof_sq)" "$(finddb /tmp/prof_sq2)" "$(finddb /tmp/prof_sq3)" > $OUT/${TAG}_pmc_collect.log 2>&1
 cd $REPO
 cp $OUT/${TAG}_pmc_counters.json $REPO/profiles/pmc_counters.json     # (on the box: so that the bench line below carries them)
-python bench.py > $OUT/${TAG}_bench.log 2>&1
+python bench.py --full > $OUT/${TAG}_bench.log 2>&1
 tail -1 $OUT/${TAG}_bench.log > $OUT/${TAG}_bench.json
 python tools/configs_bench.py > $OUT/${TAG}_configs.txt 2>&1
 ls -la $OUT | tail -12
