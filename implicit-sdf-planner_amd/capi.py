@@ -90,6 +90,20 @@ class IsdfLbfgsResult(C.Structure):
                 ("evaluations", C.c_int32), ("reserved", C.c_int32)]
 
 
+SWEPT_FIELD_PLANNER, SWEPT_FIELD_CLOSED = 0, 1
+
+
+class IsdfSweptMeshParams(C.Structure):
+    _fields_ = [("eps", C.c_double), ("iso", C.c_double), ("mode", C.c_int32), ("band", C.c_int32), ("lipschitz", C.c_double),
+                ("use_bbox", C.c_int32), ("reserved", C.c_int32), ("bmin", C.c_double * 3), ("bmax", C.c_double * 3)]
+
+
+class IsdfSweptMeshInfo(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("reserved", C.c_int32), ("origin", C.c_double * 3), ("eps", C.c_double),
+                ("coarse_points", C.c_int64), ("fine_points", C.c_int64), ("band_cells", C.c_int64), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("unqualified_edges", C.c_int64), ("field_ms", C.c_double), ("mesh_ms", C.c_double)]
+
+
 EVALUATE_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int)
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_int)   # isdf_progress_fn
 
@@ -113,6 +127,8 @@ EXPORTED_SYMBOLS = [
     "isdf_host_path", "isdf_mesh_atan2f", "isdf_create_multi", "isdf_multi_info", "isdf_set_shape_grid", "isdf_set_shape_sampled",
     "isdf_xchg_create", "isdf_xchg_connect", "isdf_xchg_allreduce", "isdf_xchg_fuse", "isdf_xchg_status", "isdf_xchg_destroy",
     "isdf_xchg_timeout_ms", "isdf_xchg_set_timeout_ms", "isdf_lbfgs_minimize_progress", "isdf_set_progress", "isdf_mesh_info",
+    "isdf_swept_sdf", "isdf_swept_sdf_device", "isdf_swept_mesh_params_default", "isdf_swept_mesh_build", "isdf_swept_mesh_get",
+    "isdf_swept_mesh_release", "isdf_write_obj",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -223,6 +239,15 @@ def load_library(path=None):
     lib.isdf_plan_config_default.restype = None
     lib.isdf_load_yaml_config.argtypes = [C.c_char_p, C.POINTER(IsdfPlanConfig)]
     lib.isdf_shape_from_config.argtypes = [C.POINTER(IsdfShape), C.POINTER(IsdfPlanConfig), C.c_char_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
+    lib.isdf_swept_sdf.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, C.c_longlong, C.c_int, dp, dp]
+    lib.isdf_swept_sdf_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+    lib.isdf_swept_mesh_params_default.argtypes = [C.POINTER(IsdfSweptMeshParams)]
+    lib.isdf_swept_mesh_params_default.restype = None
+    lib.isdf_swept_mesh_build.argtypes = [C.c_void_p, C.c_int, dp, dp, C.POINTER(IsdfSweptMeshParams), C.POINTER(IsdfSweptMeshInfo)]
+    lib.isdf_swept_mesh_get.argtypes = [C.c_void_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
+    lib.isdf_swept_mesh_release.argtypes = [C.c_void_p]
+    lib.isdf_write_obj.argtypes = [C.c_char_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
     if path is None:
         _lib = lib
     return lib

@@ -149,8 +149,12 @@ struct SweptParams {
     unsigned long long *dbg;    // developer timing buffer (ISDF_DEBUG_TIMING=1): 4 words per point, null on the product path
     unsigned long long *stats;  // [0]=units [2]=intervals [3]=active points [4]=overflow [5]=descent iterations [6]=reduce ticket [7]=passes
 };
-void launch_swept_prepare(const SweptParams &P, hipStream_t stream);
-void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// closed: the field query's closed form (isdf_swept_sdf, ISDF_SWEPT_FIELD_CLOSED) - a coarse sample at the trajectory's end, runs
+// still in range there kept; the optimizer step never sets it
+void launch_swept_prepare(const SweptParams &P, hipStream_t stream, bool closed = false);
+void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, bool closed = false);
+// the field query: the interval slots of every point -> (value, t*) (10 / -1: no interval)
+void launch_swept_field_reduce(const SweptParams &P, double *value_out, double *tstar_out, hipStream_t stream);
 void launch_swept_reduce(const SweptParams &P, double *out, hipStream_t stream);      // back-prop + sums (writes every entry of `out`)
 void launch_swept_fixed(const SweptParams &P, const double *tstar_in, hipStream_t stream);   // minimisers given: replaces prepare + sweep
 

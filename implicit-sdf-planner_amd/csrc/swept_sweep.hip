@@ -104,7 +104,9 @@ __device__ __forceinline__ double rlane(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 
-template <bool LDS>
+// CLOSED (the field query's closed form, isdf_swept_sdf): one more coarse sample at t = duration, and the scan keeps a run still in
+// range after it (see scan_body).  The optimizer step instantiates CLOSED = false only.
+template <bool LDS, bool CLOSED = false>
 __global__ __launch_bounds__(1024) void swept_prepare_kernel(const SweptParams P) {
     extern __shared__ double s_dyn[];
     __shared__ int s_n;
@@ -119,6 +121,7 @@ __global__ __launch_bounds__(1024) void swept_prepare_kernel(const SweptParams P
         if (td < 3 * 1e2) { D = td; *P.traj_duration = D; }    // updateTraj, sw_manager.hpp:287-296
         int n = 0;
         for (double t = 0; t < D && n < P.max_coarse; t += 0.2) P.coarse_t[n++] = t;   // choiceTInit :392
+        if constexpr (CLOSED) if (n < P.max_coarse) P.coarse_t[n++] = D;               // the trajectory's end (the loop stops short of it)
         s_n = n;
         *P.n_coarse = n;
         for (int k = 0; k < 8; k++) if (k != 4) P.stats[k] = 0ull;      // [4] = overflow: sticky until the host reads it
@@ -344,7 +347,7 @@ __device__ __forceinline__ void eval_lane(const SweptParams &P, const TrajL<LDS>
 // intervals and per interval (lb, ub, seed) in the point's task slots.  The workgroup that finishes last turns the interval
 // counts into the task list of the descent kernel (exclusive scan in point order: deterministic).
 // (WGM: at least 4 wavefronts per SIMD - without the cap the compiler spends 450 registers, one workgroup per CU)
-template <int KIND, bool LDS, int WGM>
+template <int KIND, bool LDS, int WGM, bool CLOSED>
 __device__ __forceinline__ void scan_body(const SweptParams &P, double *s_dyn, const int block) {
     constexpr bool COOP = WGM != 0;      // the evaluating lanes' mesh queries go through mesh_eval_wg (compacted, 4 lanes per query)
     constexpr bool FLAT = WGM == 3;      // ... small meshes: the flat evaluation instead of the walks; one point per WAVEFRONT like the analytic kinds
@@ -515,6 +518,19 @@ __device__ __forceinline__ void scan_body(const SweptParams &P, double *s_dyn, c
         const unsigned long long in_mask = __ballot((k < n_coarse) && (dis < inf));
         walk_window(base, in_mask, dis, ct);
     }
+    if constexpr (CLOSED) {
+        // the field query's closed form: the last coarse sample is t = D (prepare kernel), and a run still in range after it ends
+        // there instead of being dropped (quirk q2) - the runs that closed before are the planner's, bit for bit
+        if (in_range) {
+            if (n_ranges < SW_MAX_RANGES) {
+                if (lane == 0) { s_rl[wave][n_ranges] = tou_lb; s_rr[wave][n_ranges] = D; }
+            } else if (writer) {
+                atomicOr((unsigned int *)&P.stats[4], 1u);
+            }
+            n_ranges++;
+            in_range = false;
+        }
+    }
     n_ranges = min(n_ranges, SW_MAX_RANGES);
     if (dbg && writer) dbg[2] = wall_clock64();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -629,10 +645,10 @@ __device__ __forceinline__ void scan_body(const SweptParams &P, double *s_dyn, c
         }
     }
 }
-template <int KIND, bool LDS, int WGM = 0>
+template <int KIND, bool LDS, int WGM = 0, bool CLOSED = false>
 __global__ __launch_bounds__(64 * SW_WAVES, WGM ? ISDF_MESH_WPE : 1) void swept_scan_kernel(const SweptParams P) {
     extern __shared__ double s_dyn[];
-    scan_body<KIND, LDS, WGM>(P, s_dyn, (int)blockIdx.x);
+    scan_body<KIND, LDS, WGM, CLOSED>(P, s_dyn, (int)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1176,13 +1192,34 @@ __global__ __launch_bounds__(128) void swept_backprop_kernel(const SweptParams P
 __global__ __launch_bounds__(256) void swept_reduce_kernel(const SweptParams P, double *out, double *hist) {
     reduce_body(P, out, hist, (int)blockIdx.x);
 }
+// The field query (isdf_swept_sdf): one thread per point reduces its interval slots to (value, t*) with the selection of the step's
+// record - interval order, strict '<', starting from 10 (getSDFofSweptVolume :729-745); no interval below 10: (10, -1).
+__global__ __launch_bounds__(256) void swept_field_reduce_kernel(const SweptParams P, double *value_out, double *tstar_out) {
+    const int pt = P.point_begin + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (pt >= P.point_end) return;
+    const int nr = P.point_nr[pt] & 0xFF;
+    const double *slots = P.task_buf + (size_t)(pt - P.point_begin) * SW_MAX_RANGES * TASK_STRIDE;
+    double best = 1e1, ts = -1.0;
+    for (int r = 0; r < nr; r++) {
+        const double f_r = slots[(size_t)r * TASK_STRIDE + 1];
+        if (f_r < best) { best = f_r; ts = slots[(size_t)r * TASK_STRIDE]; }
+    }
+    value_out[pt] = best;
+    if (tstar_out) tstar_out[pt] = ts;
+}
 
-void launch_swept_prepare(const SweptParams &P, hipStream_t stream) {
+void launch_swept_prepare(const SweptParams &P, hipStream_t stream, bool closed) {
     const size_t lds = traj_lds_bytes(P.N);
+    if (closed) {
+        if (lds <= TRAJ_LDS_MAX) hipLaunchKernelGGL((swept_prepare_kernel<true, true>), dim3(1), dim3(1024), lds, stream, P);
+        else hipLaunchKernelGGL((swept_prepare_kernel<false, true>), dim3(1), dim3(1024), 0, stream, P);
+        return;
+    }
     if (lds <= TRAJ_LDS_MAX) hipLaunchKernelGGL(swept_prepare_kernel<true>, dim3(1), dim3(1024), lds, stream, P);
     else hipLaunchKernelGGL(swept_prepare_kernel<false>, dim3(1), dim3(1024), 0, stream, P);
 }
-void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
+template <bool CLOSED>
+static void launch_swept_sweep_impl(const SweptParams &P, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
     const int n = P.point_end - P.point_begin;
     if (n <= 0) return;
     // (larger mesh robots: one point / task per workgroup)
@@ -1192,9 +1229,9 @@ void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_
     const bool in_lds = lds <= TRAJ_LDS_MAX;
     // scan, then descent (one wavefront per task while there are no more tasks than points, which is the rule); the start
     // event rides on the first dispatch, the stop event on the second
-#define ISDF_SWEPT_CASE(K) case K: if (in_lds) { hipExtLaunchKernelGGL((swept_scan_kernel<K, true>), grid, block, lds, stream, ev_start, nullptr, 0, P); \
+#define ISDF_SWEPT_CASE(K) case K: if (in_lds) { hipExtLaunchKernelGGL((swept_scan_kernel<K, true, 0, CLOSED>), grid, block, lds, stream, ev_start, nullptr, 0, P); \
                                                  hipExtLaunchKernelGGL((swept_descent_kernel<K, true>), grid, block, lds, stream, nullptr, ev_stop, 0, P); } \
-                                   else { hipExtLaunchKernelGGL((swept_scan_kernel<K, false>), grid, block, 0, stream, ev_start, nullptr, 0, P); \
+                                   else { hipExtLaunchKernelGGL((swept_scan_kernel<K, false, 0, CLOSED>), grid, block, 0, stream, ev_start, nullptr, 0, P); \
                                           hipExtLaunchKernelGGL((swept_descent_kernel<K, false>), grid, block, 0, stream, nullptr, ev_stop, 0, P); } break;
     if (P.shape.kind == ISDF_SHAPE_MESH && P.shape.mesh_flat) {
         // small meshes: one point / task per WAVEFRONT (four to a workgroup, like the analytic kinds), the flat evaluation; dynamic LDS = the
@@ -1205,10 +1242,10 @@ void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_
         static const int tl_env = []{ const char *e = getenv("ISDF_FLAT_TRAJ_LDS"); return e ? atoi(e) : -1; }();
         const bool traj_in_lds = tl_env >= 0 ? tl_env != 0 : lds_traj <= 12 * 1024;
         if (traj_in_lds && lds_traj + lds_flat <= 40 * 1024) {
-            hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, true, 3>), grid, block, lds_traj + lds_flat, stream, ev_start, nullptr, 0, P);
+            hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, true, 3, CLOSED>), grid, block, lds_traj + lds_flat, stream, ev_start, nullptr, 0, P);
             hipExtLaunchKernelGGL((swept_descent_kernel<ISDF_SHAPE_MESH, true, 3>), grid, block, lds_traj + lds_flat, stream, nullptr, ev_stop, 0, P);
         } else {
-            hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, false, 3>), grid, block, lds_flat, stream, ev_start, nullptr, 0, P);
+            hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, false, 3, CLOSED>), grid, block, lds_flat, stream, ev_start, nullptr, 0, P);
             hipExtLaunchKernelGGL((swept_descent_kernel<ISDF_SHAPE_MESH, false, 3>), grid, block, lds_flat, stream, nullptr, ev_stop, 0, P);
         }
         return;
@@ -1231,9 +1268,9 @@ void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_
         // ISDF_MESH_SCAN_WAVES = 1 / 2 forces a form.
         static const int sw_env = []{ const char *e = getenv("ISDF_MESH_SCAN_WAVES"); return e ? atoi(e) : 0; }();
         const int sw = (sw_env == 1 || sw_env == 2) ? sw_env : (n >= 3 * 4096 ? 1 : 2);
-        if (sw == 1) hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, false, 1>), grid, dim3(64), fr2 / 2, stream, ev_start, nullptr, 0, P);
+        if (sw == 1) hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, false, 1, CLOSED>), grid, dim3(64), fr2 / 2, stream, ev_start, nullptr, 0, P);
         else
-        hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, false, 2>), grid, block2, fr2, stream, ev_start, nullptr, 0, P);
+        hipExtLaunchKernelGGL((swept_scan_kernel<ISDF_SHAPE_MESH, false, 2, CLOSED>), grid, block2, fr2, stream, ev_start, nullptr, 0, P);
         // The descent's passes are directed (descent_body): at most 14 queries = one quad round on ONE wavefront - one-wavefront
         // workgroups, twice the tasks in flight.  Measured against two wavefronts per task (the second one idle but for a first pass
         // without a usable seed): 16 611 points, blob 9.63 -> 7.78 ms, Trefoil.obj 6.62 -> 5.68; an eighth of them (a rank's shard of
@@ -1253,6 +1290,14 @@ void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_
     default: ISDF_SWEPT_CASE(-1)      // Ball
     }
 #undef ISDF_SWEPT_CASE
+}
+void launch_swept_sweep(const SweptParams &P, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, bool closed) {
+    if (closed) launch_swept_sweep_impl<true>(P, stream, ev_start, ev_stop);
+    else launch_swept_sweep_impl<false>(P, stream, ev_start, ev_stop);
+}
+void launch_swept_field_reduce(const SweptParams &P, double *value_out, double *tstar_out, hipStream_t stream) {
+    const int n = P.point_end - P.point_begin;
+    if (n > 0) hipLaunchKernelGGL(swept_field_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, P, value_out, tstar_out);
 }
 // the minimisers are given: replaces prepare + sweep (isdf_eval_swept_at_tstar)
 void launch_swept_fixed(const SweptParams &P, const double *tstar_in, hipStream_t stream) {

@@ -8,6 +8,8 @@ with the same ACCUMULATE semantics.  All arithmetic happens in libisdf_accel.so 
 marshals numpy arrays / device pointers.  No CPU fallback exists: errors raise IsdfError.
 """
 import ctypes as C
+import os
+
 import numpy as np
 
 from . import capi
@@ -60,6 +62,16 @@ def lbfgs_minimize(fun, x0, lib=None, progress=None, **params):
     if rc != capi.ISDF_OK:
         raise IsdfError(rc, "isdf_lbfgs_minimize")
     return x, {"f": r.f, "status": r.status, "iterations": r.iterations, "evaluations": r.evaluations, "wall_ms": r.wall_ms}
+
+
+def write_obj(path, V, F, lib=None):
+    """Writes a triangle mesh as Wavefront .obj (isdf_write_obj: isdf_read_obj reads the same doubles back)."""
+    lib = lib or capi.load_library()
+    V = np.ascontiguousarray(V, dtype=np.float64).reshape(-1, 3)
+    F = np.ascontiguousarray(F, dtype=np.int32).reshape(-1, 3)
+    rc = lib.isdf_write_obj(os.fsencode(path), _p(V), V.shape[0], F.ctypes.data_as(C.POINTER(C.c_int32)), F.shape[0])
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, f"isdf_write_obj {path}")
 
 
 class Engine:
@@ -352,6 +364,47 @@ class Engine:
 
     def out_stride(self, N):
         return int(self.lib.isdf_out_stride(N))
+
+    # ---- swept-volume field and mesh (isdf_swept_sdf, isdf_swept_mesh_*)
+    def swept_sdf(self, T, coeffs_colmajor, xyz, mode=capi.SWEPT_FIELD_PLANNER):
+        """The swept-volume SDF of the trajectory at the points xyz (n x 3): (value, t*); no qualifying interval: (10, -1)."""
+        T = np.ascontiguousarray(T, dtype=np.float64); N = T.size
+        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(-1)
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        n = xyz.shape[0]
+        val = np.zeros(n); ts = np.zeros(n)
+        self._check(self.lib.isdf_swept_sdf(self.h, N, _p(T), _p(Cc), _p(xyz), n, int(mode), _p(val), _p(ts)))
+        return val, ts
+
+    def swept_sdf_device(self, N, d_T, d_coeffs, d_xyz, n, d_value, d_tstar=0, mode=capi.SWEPT_FIELD_PLANNER, stream=0):
+        self._check(self.lib.isdf_swept_sdf_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), C.c_void_p(d_xyz), n, int(mode),
+                                                   C.c_void_p(d_value), C.c_void_p(d_tstar), C.c_void_p(stream)))
+
+    def swept_mesh(self, T, coeffs_colmajor, eps, iso=0.0, mode=capi.SWEPT_FIELD_CLOSED, band=4, bbox=None, lipschitz=1.0):
+        """Surface mesh of the swept volume: (V (nV x 3), F (nF x 3, int32, zero based), info dict).  bbox: ((x, y, z), (x, y, z))."""
+        T = np.ascontiguousarray(T, dtype=np.float64); N = T.size
+        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(-1)
+        p = capi.IsdfSweptMeshParams()
+        self.lib.isdf_swept_mesh_params_default(C.byref(p))
+        p.eps, p.iso, p.mode, p.band, p.lipschitz = float(eps), float(iso), int(mode), int(band), float(lipschitz)
+        if bbox is not None:
+            p.use_bbox = 1
+            for a in range(3):
+                p.bmin[a], p.bmax[a] = float(bbox[0][a]), float(bbox[1][a])
+        info = capi.IsdfSweptMeshInfo()
+        self._check(self.lib.isdf_swept_mesh_build(self.h, N, _p(T), _p(Cc), C.byref(p), C.byref(info)))
+        nV, nF = int(info.n_vertices), int(info.n_triangles)
+        V = np.zeros((nV, 3)); F = np.zeros((nF, 3), dtype=np.int32)
+        self._check(self.lib.isdf_swept_mesh_get(self.h, _p(V), nV, F.ctypes.data_as(C.POINTER(C.c_int32)), nF))
+        d = {name: (list(getattr(info, name)) if name in ("dims", "origin") else getattr(info, name))
+             for name, _ in capi.IsdfSweptMeshInfo._fields_ if name != "reserved"}
+        return V, F, d
+
+    def swept_mesh_release(self):
+        self._check(self.lib.isdf_swept_mesh_release(self.h))
+
+    def write_obj(self, path, V, F):
+        return write_obj(path, V, F, self.lib)
 
     # ---- full objective callback (TrajOptimizer::costFunctionLmbm)
     def set_trajectory(self, N, head_pva, tail_pva, rho):

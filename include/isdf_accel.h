@@ -337,6 +337,67 @@ int isdf_eval_swept_at_tstar(isdf_ctx *ctx, int N, const double *d_T, const doub
 int isdf_eval_swept_at_tstar_host(isdf_ctx *ctx, int N, const double *T, const double *coeffs, const double *tstar,
                                   double *cost_inout, double *gradT_inout, double *gradC_inout);
 
+/* ---- swept-volume field and mesh ------------------------------------------------------------------------------ */
+/* The swept-volume SDF of a trajectory at arbitrary points: getSDFofSweptVolume (sw_manager.hpp:710-747) per point, the
+ * query the V1 collision term binds, with the ctx's shape (any kind) and config (safety_hor, flatness constants), on any
+ * single-device ctx whatever cfg.variant is (a multi-device ctx: ISDF_ERR_UNSUPPORTED).  The trajectory is passed as
+ * isdf_eval takes it: N durations, 6N x 3 column-major coefficients; a total of 300 s or more is ISDF_ERR_INVALID_ARG.
+ *   PLANNER  exactly the collision term's query: coarse 0.2 s table, qualification sdf < 2 safety_hor + 0.1, quirks q1-q3,
+ *            the 0.02 s fine scan and the sign descent.  A point with no qualifying interval reads value 10, t* = -1.
+ *   CLOSED   the same with the trajectory's end included: one more coarse sample at t = duration, and a run still in range
+ *            after it is kept (upper bound = duration) instead of dropped.  Where all of a point's in-range runs close before
+ *            the end it equals PLANNER bit for bit; elsewhere it is <= PLANNER.  The mesh needs it (end cap, short trajectories).
+ * The query has scratch of its own: the V1 step's points, lastTstar, duration state, dispatch records and overflow word are
+ * not touched.  Points go through in chunks (1.5 KB of interval slots each), so millions can be queried.  A point with more
+ * than 32 intervals: ISDF_ERR_OVERFLOW.  tstar_out may be NULL.  The device form synchronises `stream` before it returns. */
+#define ISDF_SWEPT_FIELD_PLANNER 0
+#define ISDF_SWEPT_FIELD_CLOSED  1
+int isdf_swept_sdf(isdf_ctx *ctx, int N, const double *T, const double *coeffs, const double *xyz, long long n,
+                   int mode, double *value_out, double *tstar_out);
+int isdf_swept_sdf_device(isdf_ctx *ctx, int N, const double *d_T, const double *d_coeffs, const double *d_xyz,
+                          long long n, int mode, double *d_value_out, double *d_tstar_out, void *stream);
+/* The surface mesh of the swept volume (sw_calculate::calculation / getmesh, reached from calculateSwept sw_manager.hpp:225-237):
+ * the field above on a lattice of spacing eps, marching tetrahedra on the Kuhn split (six tetrahedra per cell around its main
+ * diagonal).  Inside is f < iso; a vertex lies on a lattice edge (7 per node: +x +y +z +xy +xz +yz +xyz), placed by linear
+ * interpolation; triangles face towards larger f (outwards).  Vertices are numbered by ascending edge id (node * 7 + dir, node
+ * = (i * ny + j) * nz + k), triangles come in cell order (z fastest), then tetrahedron order: the output is bitwise
+ * reproducible, and the narrow band gives the dense mesh.
+ * Box: use_bbox, or the trajectory's positions grown by R + iso + 2 eps (R: bound_radius of the shape; mesh robots: their
+ * largest vertex norm; none known: ISDF_ERR_INVALID_ARG), snapped to multiples of eps; more than 2^27 lattice nodes:
+ * ISDF_ERR_INVALID_ARG.  Narrow band (band = B > 0): the field on every B-th node, then on the nodes of the coarse cells whose
+ * corners change sign about iso or all lie within lipschitz * sqrt(3) * B * eps of it - a corner farther away proves the cell's
+ * side of iso (exact for a field with that Lipschitz bound); band = 0 evaluates every node. */
+typedef struct isdf_swept_mesh_params {
+    double eps;          /* lattice spacing (m), > 0 (the reference's yaml eps: 0.05-0.15); default 0.1                */
+    double iso;          /* level to extract, >= 0 (0 = the swept volume, > 0 = an inflated one); default 0           */
+    int32_t mode;        /* ISDF_SWEPT_FIELD_CLOSED (default) or ISDF_SWEPT_FIELD_PLANNER                              */
+    int32_t band;        /* coarse factor B of the narrow band (default 4); 0 = evaluate every lattice node            */
+    double lipschitz;    /* bound L on the field's Lipschitz constant, > 0, used to cull coarse cells (default 1)      */
+    int32_t use_bbox;    /* nonzero: the lattice covers [bmin, bmax] (snapped outwards to eps) instead of the derived box */
+    int32_t reserved;
+    double bmin[3], bmax[3];
+} isdf_swept_mesh_params;
+typedef struct isdf_swept_mesh_info {
+    int32_t dims[3];             /* lattice nodes per axis                                                              */
+    int32_t reserved;
+    double origin[3];            /* position of node (0, 0, 0)                                                          */
+    double eps;
+    int64_t coarse_points;       /* field queries on the coarse lattice (0 without a band)                              */
+    int64_t fine_points;         /* field queries of the fine batch (every node without a band)                         */
+    int64_t band_cells;          /* lattice cells with all eight corners evaluated (the cells the extraction visits)     */
+    int64_t n_vertices, n_triangles;
+    int64_t unqualified_edges;   /* sign-changing edges with an end that found no qualifying interval (value 10): nonzero
+                                    means the qualification radius 2 safety_hor + 0.1 was too small for this iso         */
+    double field_ms, mesh_ms;    /* device time of the field queries / of the extraction (events on the ctx's stream)    */
+} isdf_swept_mesh_info;
+void isdf_swept_mesh_params_default(isdf_swept_mesh_params *p);
+/* builds the mesh on the device and keeps it in the ctx (replacing the previous one); T / coeffs are host arrays */
+int isdf_swept_mesh_build(isdf_ctx *ctx, int N, const double *T, const double *coeffs,
+                          const isdf_swept_mesh_params *p, isdf_swept_mesh_info *info_out);
+/* copies the last mesh out: V_out capV x 3, F_out capF x 3 (zero based); ISDF_ERR_OVERFLOW (nothing written) if too small */
+int isdf_swept_mesh_get(isdf_ctx *ctx, double *V_out, int capV, int32_t *F_out, int capF);
+int isdf_swept_mesh_release(isdf_ctx *ctx);      /* frees the kept mesh */
+
 /* ---- full objective callback ------------------------------------------------------------------------------ */
 /* TrajOptimizer::costFunctionLmbm (back_end_optimizer.hpp:358-430): x = [tau(N) | inner waypoints 3(N-1)] ->
  * cost, g.  MINCO (minco.hpp:397-655: setParameters, energy and its partials, propogateGrad) and the sweeps: for
@@ -537,6 +598,9 @@ long long isdf_read_pcd(const char *path, float *xyz_out, long long capacity);
 /* Wavefront .obj as igl::read_triangle_mesh reads it (src/utils/src/Shape.cpp:36): vertices V_out (capV x 3), triangles F_out
  * (capF x 3, zero based; polygons fanned from their first vertex).  nV_out / nF_out always receive the counts in the file. */
 int isdf_read_obj(const char *path, double *V_out, int capV, int32_t *F_out, int capF, int *nV_out, int *nF_out);
+/* Writes V (nV x 3) and F (nF x 3, zero based) as a Wavefront .obj ("v x y z" with 17 significant digits, "f a b c" one based):
+ * isdf_read_obj reads the same doubles and indices back. */
+int isdf_write_obj(const char *path, const double *V, int nV, const int32_t *F, int nF);
 /* yaml poly_params [x, y, z, roll, pitch, yaw (degrees)] -> Rotate = yaw * pitch * roll with Eigen's AngleAxis matrices and
  * PI = 3.14159265358979323846 (Shape.cpp:23,38-43), row-major. */
 int isdf_poly_rotation(const double poly_params[6], double rotate_out[9]);
