@@ -104,6 +104,17 @@ class IsdfSweptMeshInfo(C.Structure):
                 ("n_triangles", C.c_int64), ("unqualified_edges", C.c_int64), ("field_ms", C.c_double), ("mesh_ms", C.c_double)]
 
 
+class IsdfTrajCheckParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IsdfTrajCheckInfo(C.Structure):
+    _fields_ = [("occupied_in_box", C.c_int64), ("candidates", C.c_int64), ("qualified", C.c_int64), ("n_below_margin", C.c_int64),
+                ("n_penetrating", C.c_int64), ("min_clearance", C.c_double), ("min_tstar", C.c_double), ("min_point", C.c_double * 3),
+                ("min_voxel", C.c_int64), ("min_piece", C.c_int32), ("culled", C.c_int32), ("margin", C.c_double), ("far_r", C.c_double),
+                ("select_ms", C.c_double), ("field_ms", C.c_double), ("reduce_ms", C.c_double)]
+
+
 EVALUATE_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int)
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_int)   # isdf_progress_fn
 
@@ -128,7 +139,8 @@ EXPORTED_SYMBOLS = [
     "isdf_xchg_create", "isdf_xchg_connect", "isdf_xchg_allreduce", "isdf_xchg_fuse", "isdf_xchg_status", "isdf_xchg_destroy",
     "isdf_xchg_timeout_ms", "isdf_xchg_set_timeout_ms", "isdf_lbfgs_minimize_progress", "isdf_set_progress", "isdf_mesh_info",
     "isdf_swept_sdf", "isdf_swept_sdf_device", "isdf_swept_mesh_params_default", "isdf_swept_mesh_build", "isdf_swept_mesh_get",
-    "isdf_swept_mesh_release", "isdf_write_obj",
+    "isdf_swept_mesh_release", "isdf_write_obj", "isdf_traj_check_params_default", "isdf_traj_check", "isdf_traj_check_device",
+    "isdf_traj_check_get", "isdf_traj_check_release", "isdf_traj_collide",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -248,6 +260,14 @@ def load_library(path=None):
     lib.isdf_swept_mesh_get.argtypes = [C.c_void_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
     lib.isdf_swept_mesh_release.argtypes = [C.c_void_p]
     lib.isdf_write_obj.argtypes = [C.c_char_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
+    lib.isdf_traj_check_params_default.argtypes = [C.POINTER(IsdfTrajCheckParams)]
+    lib.isdf_traj_check_params_default.restype = None
+    lib.isdf_traj_check.argtypes = [C.c_void_p, C.c_int, dp, dp, C.POINTER(IsdfTrajCheckParams), C.POINTER(IsdfTrajCheckInfo), dp]
+    lib.isdf_traj_check_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(IsdfTrajCheckParams),
+                                           C.POINTER(IsdfTrajCheckInfo), C.c_void_p, C.c_void_p]
+    lib.isdf_traj_check_get.argtypes = [C.c_void_p, dp, C.c_longlong]
+    lib.isdf_traj_check_release.argtypes = [C.c_void_p]
+    lib.isdf_traj_collide.argtypes = [C.c_void_p, C.c_int, dp, dp]
     if path is None:
         _lib = lib
     return lib

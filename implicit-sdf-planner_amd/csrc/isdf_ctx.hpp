@@ -10,6 +10,7 @@ using namespace isdf;
 struct ProfEvent { hipEvent_t a, b, c, d; };   // start/stop of the dominant kernel, start/stop of the one after it
 struct isdf_xchg;
 struct SweptMeshState;          // swept_mesh.hip: scratch of the swept-volume field query and the last mesh
+struct TrajCheckState;          // traj_check.hip: the last clearance check's points below the margin
 struct isdf_ctx {
     isdf_config cfg;
     int device = 0;
@@ -20,6 +21,7 @@ struct isdf_ctx {
     int mesh_info[16] = {0};                    // isdf_mesh_info: what isdf_set_shape found and decided about the installed mesh
     double mesh_rmax = 0.0;                     // mesh robots: largest body-frame vertex norm (the swept mesh's box margin)
     SweptMeshState *swm = nullptr;              // isdf_swept_sdf / isdf_swept_mesh_*: own scratch, never the V1 step's
+    TrajCheckState *tck = nullptr;              // isdf_traj_check*: the kept report rows
     const double *v1_tstar_stage = nullptr;     // set by the host-direct V1 step for ONE eval_device_impl call (SweptParams::tstar_stage)
     double *d_esdf_stage = nullptr; size_t esdf_stage_cap = 0;        // isdf_esdf_sample's staging (points | values | gradients): grows only, no allocation per call
     float *d_esdf_bricks = nullptr; size_t bricks_cap = 0; bool bricks_stale = true;     // the ESDF as 2 x 2 x 2-cell bricks with apron, one 128-byte line each (map_build.hip: scattered points)
@@ -163,6 +165,7 @@ int isdf_reset_result_slots(isdf_ctx *c); // isdf_host.hip: drains the device an
 void isdf_xchg_release(isdf_ctx *c);          // xchg.hip: closes the peer mappings, frees the mailbox (isdf_destroy)
 void isdf_frontend_release(isdf_ctx *c);      // frontend.hip: frees the tables (isdf_destroy)
 void isdf_swept_release_all(isdf_ctx *c);     // swept_mesh.hip: frees the field scratch and the mesh (isdf_destroy)
+void isdf_traj_check_release_all(isdf_ctx *c);        // traj_check.hip: frees the kept clearance report (isdf_destroy)
 int isdf_mesh_lattice_build(isdf_ctx *c, isdf::DevMesh *hm, const double lo[3], const double hi[3], int n, float s_range_out[2]);
 int isdf_mesh_surface_valid(isdf_ctx *c, const double *d_tri, int nF, double extent, double tau_limit, int *valid_out, float defect_out[2]);      // shape_eval.hip: exact winding number 0 / 1 on both sides of every face      // shape_eval.hip: the mesh kind's distance lattice (DevMesh::dl)
 

@@ -18,8 +18,7 @@
 //                on every run, and the narrow-band mesh is the dense one.
 // The reference continues its field along a flood fill (descents of +-0.1 s seeded by a neighbour's t*, sw_manager.hpp:1173-1193):
 // its values depend on the flood order and are deliberately not reproduced - every node here is an independent query.
-#include "isdf_ctx.hpp"
-#include <hipcub/hipcub.hpp>
+#include "swept_field.hpp"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -27,28 +26,7 @@
 
 namespace {
 
-constexpr int FIELD_CHUNK = 65536;                        // points per field launch: 65 536 x 1.5 KB of interval slots = 96 MiB
 constexpr long long MESH_MAX_NODES = 1ll << 27;           // fine lattice nodes of one mesh build (~20 B of scratch per node)
-constexpr double MAX_DURATION = 300.0;                    // the reference's stale-duration rule (sw_manager.hpp:287-296)
-
-}  // namespace
-
-// scratch of the field query and the last mesh (never shared with the optimizer step's state)
-struct SweptMeshState {
-    // field
-    double *d_traj_duration = nullptr, *d_coarse_t = nullptr, *d_coarse_pose = nullptr;
-    int *d_n_coarse = nullptr;
-    int *d_point_nr = nullptr; double *d_task_buf = nullptr; unsigned *d_task_map = nullptr, *d_point_lmask = nullptr, *d_words = nullptr;
-    unsigned long long *d_stats = nullptr;
-    unsigned long long *h_overflow = nullptr;
-    // mesh build inputs (T | coeffs) and the last mesh
-    double *d_traj = nullptr; size_t traj_cap = 0;
-    double *d_V = nullptr; int32_t *d_F = nullptr;
-    long long nV = 0, nF = 0;
-    bool have_mesh = false;
-};
-
-namespace {
 
 void free_field_scratch(SweptMeshState *s) {
     void *ptrs[] = {s->d_traj_duration, s->d_coarse_t, s->d_coarse_pose, s->d_n_coarse, s->d_point_nr, s->d_task_buf, s->d_task_map,
@@ -64,14 +42,16 @@ void free_mesh_result(SweptMeshState *s) {
 
 int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
 
-int field_scratch(isdf_ctx *c, SweptMeshState **out) {
+}  // namespace
+
+int swept_field_scratch(isdf_ctx *c, SweptMeshState **out) {
     if (!c->swm) c->swm = new SweptMeshState();
     SweptMeshState *s = c->swm;
     *out = s;
     if (s->d_task_buf) return ISDF_OK;
     HIPCHK(c, hipMalloc(&s->d_traj_duration, sizeof(double)));
-    HIPCHK(c, hipMalloc(&s->d_coarse_t, 1536 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&s->d_coarse_pose, 1536 * 12 * sizeof(double)));
+    HIPCHK(c, hipMalloc(&s->d_coarse_t, SWEPT_MAX_COARSE * sizeof(double)));
+    HIPCHK(c, hipMalloc(&s->d_coarse_pose, SWEPT_MAX_COARSE * 12 * sizeof(double)));
     HIPCHK(c, hipMalloc(&s->d_n_coarse, sizeof(int)));
     HIPCHK(c, hipMalloc(&s->d_point_nr, (size_t)FIELD_CHUNK * sizeof(int)));
     HIPCHK(c, hipMalloc(&s->d_task_map, (size_t)FIELD_CHUNK * 32 * sizeof(unsigned)));
@@ -86,7 +66,7 @@ int field_scratch(isdf_ctx *c, SweptMeshState **out) {
 }
 
 // host-side checks shared by both field entry points and the mesh build
-int check_traj(isdf_ctx *c, int N, const double *T) {
+int swept_check_traj(isdf_ctx *c, int N, const double *T) {
     double td = 0.0;
     for (int i = 0; i < N; i++) {
         if (!(T[i] > 0.0) || !std::isfinite(T[i])) return fail(c, ISDF_ERR_INVALID_ARG, "piece durations must be finite and > 0");
@@ -95,19 +75,14 @@ int check_traj(isdf_ctx *c, int N, const double *T) {
     if (!(td < MAX_DURATION)) return fail(c, ISDF_ERR_INVALID_ARG, "swept-volume field: trajectory of 300 s or longer (the reference's duration rule)");
     return ISDF_OK;
 }
-int check_ctx(isdf_ctx *c) {
+int swept_check_ctx(isdf_ctx *c) {
     if (!c->peers.empty() || c->is_peer || c->rccl_comm) return fail(c, ISDF_ERR_UNSUPPORTED, "swept-volume field on a multi-device ctx");
     if (!c->have_shape) return fail(c, ISDF_ERR_STATE, "shape not set");
     return ISDF_OK;
 }
 
-// the field at n points (device arrays), synchronous on `st` at the end (the overflow word is read back)
-int field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
-              double *d_value, double *d_tstar, hipStream_t st) {
-    SweptMeshState *s;
-    { const int rc = field_scratch(c, &s); if (rc) return rc; }
-    if (n <= 0) return ISDF_OK;
-    const bool closed = mode == ISDF_SWEPT_FIELD_CLOSED;
+// the field launches' parameters on the query's own scratch
+static SweptParams field_params(isdf_ctx *c, SweptMeshState *s, int N, const double *d_T, const double *d_coeffs) {
     SweptParams P{};
     P.shape = c->shape;
     P.flat.mass = c->cfg.vehicle_mass; P.flat.grav = c->cfg.grav_acc; P.flat.dh = c->cfg.horiz_drag; P.flat.dv = c->cfg.vert_drag;
@@ -116,9 +91,32 @@ int field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, con
     P.safety_hor = c->cfg.safety_hor; P.weight_p = c->cfg.weight_p;
     P.T = d_T; P.coeffs = d_coeffs;
     P.traj_duration = s->d_traj_duration;
-    P.coarse_t = s->d_coarse_t; P.coarse_pose = s->d_coarse_pose; P.n_coarse = s->d_n_coarse; P.max_coarse = 1536;
+    P.coarse_t = s->d_coarse_t; P.coarse_pose = s->d_coarse_pose; P.n_coarse = s->d_n_coarse; P.max_coarse = SWEPT_MAX_COARSE;
     P.point_nr = s->d_point_nr; P.task_buf = s->d_task_buf; P.task_map = s->d_task_map;
     P.point_lmask = s->d_point_lmask; P.words = s->d_words; P.stats = s->d_stats;
+    return P;
+}
+
+// the coarse table of a trajectory alone (prepare kernel; asynchronous on `st`): n_coarse and the component-major poses in the
+// query's scratch, the doubles swept_field_run builds again for the same trajectory and mode
+int swept_field_coarse_table(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, int mode, hipStream_t st) {
+    SweptMeshState *s;
+    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    SweptParams P = field_params(c, s, N, d_T, d_coeffs);
+    P.points = nullptr; P.point_begin = 0; P.point_end = 0; P.M = 0;
+    launch_swept_prepare(P, st, mode == ISDF_SWEPT_FIELD_CLOSED);
+    HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+
+// the field at n points (device arrays), synchronous on `st` at the end (the overflow word is read back)
+int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
+                    double *d_value, double *d_tstar, hipStream_t st) {
+    SweptMeshState *s;
+    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    if (n <= 0) return ISDF_OK;
+    const bool closed = mode == ISDF_SWEPT_FIELD_CLOSED;
+    SweptParams P = field_params(c, s, N, d_T, d_coeffs);
     HIPCHK(c, hipMemsetAsync(s->d_stats, 0, 8 * sizeof(unsigned long long), st));
     // the coarse table once (it depends on the trajectory alone): the prepare kernel reads no point
     P.points = d_xyz; P.point_begin = 0; P.point_end = 0; P.M = 0;
@@ -136,6 +134,8 @@ int field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, con
     if (*s->h_overflow) return fail(c, ISDF_ERR_OVERFLOW, "swept-volume field: a point has more than 32 in-range intervals (results not valid)");
     return ISDF_OK;
 }
+
+namespace {
 
 // ---- mesh kernels ---------------------------------------------------------------------------------------------------
 struct Lattice {
@@ -397,15 +397,6 @@ __global__ void tri_emit_kernel(Lattice L, const double *f, double iso, const un
 }
 
 // ---- host helpers ---------------------------------------------------------------------------------------------------
-inline unsigned blocks(long long n, int b = 256) { return (unsigned)((n + b - 1) / b); }
-
-// a device buffer that frees itself
-template <typename T> struct DBuf {
-    T *p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
-};
-
 // the field at the nodes [0, n) of a list (ids) or of the lattice (ids == null) into f[node]
 int field_nodes(isdf_ctx *c, int N, const double *d_T, const double *d_C, const Lattice &L, const int *ids, long long n, int mode,
                 double *f, hipStream_t st) {
@@ -416,20 +407,11 @@ int field_nodes(isdf_ctx *c, int N, const double *d_T, const double *d_C, const 
     for (long long b = 0; b < n; b += chunk) {
         const int m = (int)std::min(chunk, n - b);
         hipLaunchKernelGGL(node_xyz_kernel, dim3(blocks(m)), dim3(256), 0, st, L, ids, b, m, xyz.p);
-        const int rc = field_run(c, N, d_T, d_C, xyz.p, m, mode, val.p, nullptr, st);
+        const int rc = swept_field_run(c, N, d_T, d_C, xyz.p, m, mode, val.p, nullptr, st);
         if (rc) return rc;
         hipLaunchKernelGGL(node_scatter_kernel, dim3(blocks(m)), dim3(256), 0, st, ids, b, m, val.p, f);
     }
     HIPCHK(c, hipGetLastError());
-    return ISDF_OK;
-}
-
-template <typename In, typename Out> int exclusive_sum(isdf_ctx *c, In in, Out out, long long n, hipStream_t st) {
-    size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
-    DBuf<unsigned char> tmp;
-    HIPCHK(c, tmp.alloc(bytes));
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, in, out, (int)n, st));
     return ISDF_OK;
 }
 
@@ -485,15 +467,15 @@ extern "C" int isdf_swept_sdf_device(isdf_ctx *c, int N, const double *d_T, cons
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (N < 1 || !d_T || !d_coeffs || n < 0 || (n > 0 && (!d_xyz || !d_value_out))) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: bad arguments");
     if (mode != ISDF_SWEPT_FIELD_PLANNER && mode != ISDF_SWEPT_FIELD_CLOSED) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: unknown mode");
-    { const int rc = check_ctx(c); if (rc) return rc; }
+    { const int rc = swept_check_ctx(c); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     // the 300 s rule needs the durations on the host
     std::vector<double> hT(N);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(c, hipMemcpyAsync(hT.data(), d_T, N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    { const int rc = check_traj(c, N, hT.data()); if (rc) return rc; }
-    return field_run(c, N, d_T, d_coeffs, d_xyz, n, mode, d_value_out, d_tstar_out, st);
+    { const int rc = swept_check_traj(c, N, hT.data()); if (rc) return rc; }
+    return swept_field_run(c, N, d_T, d_coeffs, d_xyz, n, mode, d_value_out, d_tstar_out, st);
 }
 
 extern "C" int isdf_swept_sdf(isdf_ctx *c, int N, const double *T, const double *coeffs, const double *xyz, long long n, int mode,
@@ -501,8 +483,8 @@ extern "C" int isdf_swept_sdf(isdf_ctx *c, int N, const double *T, const double 
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (N < 1 || !T || !coeffs || n < 0 || (n > 0 && (!xyz || !value_out))) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: bad arguments");
     if (mode != ISDF_SWEPT_FIELD_PLANNER && mode != ISDF_SWEPT_FIELD_CLOSED) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: unknown mode");
-    { const int rc = check_ctx(c); if (rc) return rc; }
-    { const int rc = check_traj(c, N, T); if (rc) return rc; }
+    { const int rc = swept_check_ctx(c); if (rc) return rc; }
+    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DBuf<double> d_in, d_xyz, d_out;
@@ -512,7 +494,7 @@ extern "C" int isdf_swept_sdf(isdf_ctx *c, int N, const double *T, const double 
     HIPCHK(c, hipMemcpyAsync(d_in.p, T, N * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_in.p + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
     if (n > 0) HIPCHK(c, hipMemcpyAsync(d_xyz.p, xyz, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-    const int rc = field_run(c, N, d_in.p, d_in.p + N, d_xyz.p, n, mode, d_out.p, d_out.p + n, st);
+    const int rc = swept_field_run(c, N, d_in.p, d_in.p + N, d_xyz.p, n, mode, d_out.p, d_out.p + n, st);
     if (rc) return rc;
     if (n > 0) {
         HIPCHK(c, hipMemcpyAsync(value_out, d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -539,12 +521,12 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     if (N < 1 || !T || !coeffs) return fail(c, ISDF_ERR_INVALID_ARG, "swept mesh: null trajectory");
     { const int rc = check_mesh_params(c, p); if (rc) return rc; }
     if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "swept mesh: null ctx");
-    { const int rc = check_ctx(c); if (rc) return rc; }
-    { const int rc = check_traj(c, N, T); if (rc) return rc; }
+    { const int rc = swept_check_ctx(c); if (rc) return rc; }
+    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
     for (int k = 0; k < 18 * N; k++) if (!std::isfinite(coeffs[k])) return fail(c, ISDF_ERR_INVALID_ARG, "swept mesh: non-finite coefficient");
     HIPCHK(c, hipSetDevice(c->device));
     SweptMeshState *s;
-    { const int rc = field_scratch(c, &s); if (rc) return rc; }
+    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
     free_mesh_result(s);
     hipStream_t st = c->stream;
 

@@ -1,0 +1,510 @@
+// Trajectory clearance check on the device (isdf_traj_check*, isdf_traj_collide): what the reference's
+// SweptVolumeManager::isTrajCollide (sw_manager.hpp:764, a stub that returns false) is called for at the end of generateTraj
+// (plan_manager.cpp) - how close the swept volume of a trajectory comes to any occupied voxel centre of the WHOLE map.
+//
+//   select   the occupied voxels that can matter.  The field query skips a coarse sample whose position is farther from the point
+//            than far_r = R + (2 safety_hor + 0.1) (mesh robots: band x 1.05) - swept_sweep.hip, scan_body - so a point that far
+//            from EVERY coarse sample has no in-range run and reads 10 / -1.  Dropping it changes no result: the selection only
+//            has to be a superset of the points inside some sample's sphere.  The samples are the table the query's own prepare
+//            kernel builds (same doubles, the CLOSED sample included).  Box of the samples grown by far_r -> 8 x 8 x 8 bricks
+//            against the samples (radius grown by the brick's half-diagonal; each live brick keeps the range of sample indices
+//            that reach it) -> the occupied voxels of live bricks singly, one wavefront per z-row, d_occ read 64 consecutive bytes
+//            at a time.  Ballot masks per row, row counts, one exclusive scan, emit: candidates come out by ascending voxel index.
+//            A shape with no bound radius: every occupied voxel of the grid (culled = 0).
+//   field    the candidates through swept_field_run (swept_mesh.hip), PLANNER or CLOSED.
+//   reduce   (value, t*) of the candidates -> minimum with its point (ties: lowest voxel index - the candidates are in voxel
+//            order, so the lowest list position), counts below the margin / below 0, per piece of the trajectory the smallest value
+//            among the points whose t* lies in it, and the points below the margin compacted in voxel order.  Minima and integer
+//            sums only: the report does not depend on the launch geometry, and two runs give the same bytes.
+#include "swept_field.hpp"
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+// the last check's violating points (kept like the swept mesh is) and the host form's trajectory upload
+struct TrajCheckState {
+    double *d_traj = nullptr; size_t traj_cap = 0;
+    double *d_rows = nullptr;       // n_rows x (x, y, z, value, t*)
+    long long n_rows = 0;
+    bool have = false;
+};
+
+namespace {
+
+constexpr int BRICK = 8;                 // voxels per brick edge
+constexpr int SEL_WAVES = 4;             // z-rows per workgroup of the row kernels
+
+int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
+
+struct SelBox {
+    int X, Y, Z;                 // grid
+    double res, bmin[3];
+    int lo[3], hi[3];            // voxel box, inclusive
+    int b0[3], nb[3];            // first brick of the box per axis, bricks per axis
+    int n_chunks;                // 64-voxel chunks of a z-row of the box
+    int cull;                    // 0: every occupied voxel of the box is a candidate
+    double far2;                 // (far_r)^2, slightly enlarged: the single-voxel test
+    double bfar2;                // (far_r + brick half-diagonal)^2: the brick test
+};
+
+// a voxel's centre as numpy forms it, (index + 0.5) * res + origin with both operations rounded (no contraction into an fma)
+__device__ __forceinline__ double voxel_centre(int i, double res, double origin) {
+#pragma clang fp contract(off)
+    const double m = ((double)i + 0.5) * res;
+    return m + origin;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// the coarse positions into LDS as [x | y | z] (pose table: component-major, SWEPT_MAX_COARSE rows)
+__device__ __forceinline__ void stage_samples(const double *pose, int n, double *s_pos) {
+    for (int k = threadIdx.x; k < 3 * n; k += blockDim.x) {
+        const int a = k / n, i = k - a * n;
+        s_pos[a * SWEPT_MAX_COARSE + i] = pose[(size_t)a * SWEPT_MAX_COARSE + i];
+    }
+    __syncthreads();
+}
+
+// per brick of the box: the first and last coarse sample within far_r + half-diagonal of its centre (first > last: none)
+__global__ __launch_bounds__(256) void tc_brick_kernel(SelBox B, const double *__restrict__ pose, const int *__restrict__ n_coarse,
+                                                       int2 *__restrict__ range) {
+    __shared__ double s_pos[3 * SWEPT_MAX_COARSE];
+    const int n = min(*n_coarse, SWEPT_MAX_COARSE);
+    stage_samples(pose, n, s_pos);
+    const long long n_bricks = (long long)B.nb[0] * B.nb[1] * B.nb[2];
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n_bricks; t += (long long)gridDim.x * blockDim.x) {
+        const int bz = (int)(t % B.nb[2]), by = (int)((t / B.nb[2]) % B.nb[1]), bx = (int)(t / ((long long)B.nb[2] * B.nb[1]));
+        // centre of the brick's 8 x 8 x 8 voxel centres: index + 3.5 -> (index + 4) * res + origin
+        const double cx = (double)((B.b0[0] + bx) * BRICK + BRICK / 2) * B.res + B.bmin[0];
+        const double cy = (double)((B.b0[1] + by) * BRICK + BRICK / 2) * B.res + B.bmin[1];
+        const double cz = (double)((B.b0[2] + bz) * BRICK + BRICK / 2) * B.res + B.bmin[2];
+        int first = n, last = -1;
+        for (int k = 0; k < n; k++) {
+            const double dx = cx - s_pos[k], dy = cy - s_pos[SWEPT_MAX_COARSE + k], dz = cz - s_pos[2 * SWEPT_MAX_COARSE + k];
+            if (!(dx * dx + dy * dy + dz * dz > B.bfar2)) { first = min(first, k); last = k; }
+        }
+        range[t] = make_int2(first, last);
+    }
+}
+
+// one wavefront per z-row (x, y) of the box: mask[row][chunk] = the candidates among 64 consecutive voxels, count[row] = their
+// number; stats[0] += occupied voxels of the box, stats[1] += candidates
+__global__ __launch_bounds__(64 * SEL_WAVES) void tc_row_kernel(SelBox B, const uint8_t *__restrict__ occ, const int2 *__restrict__ range,
+                                                                const double *__restrict__ pose, const int *__restrict__ n_coarse,
+                                                                unsigned long long *__restrict__ mask, int *__restrict__ count,
+                                                                unsigned long long *stats) {
+    __shared__ double s_pos[3 * SWEPT_MAX_COARSE];
+    const int n = min(*n_coarse, SWEPT_MAX_COARSE);
+    if (B.cull) stage_samples(pose, n, s_pos);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ny = B.hi[1] - B.lo[1] + 1;
+    const long long n_rows = (long long)(B.hi[0] - B.lo[0] + 1) * ny;
+    const long long row = (long long)blockIdx.x * SEL_WAVES + wave;
+    if (row >= n_rows) return;
+    const int x = B.lo[0] + (int)(row / ny), y = B.lo[1] + (int)(row % ny);
+    const uint8_t *o = occ + ((size_t)x * B.Y + y) * B.Z;
+    const double px = voxel_centre(x, B.res, B.bmin[0]), py = voxel_centre(y, B.res, B.bmin[1]);
+    const long long brick_row = ((long long)(x / BRICK - B.b0[0]) * B.nb[1] + (y / BRICK - B.b0[1])) * B.nb[2];
+    unsigned long long n_occ = 0;
+    int n_sel = 0;
+    for (int ch = 0; ch < B.n_chunks; ch++) {
+        const int z = B.lo[2] + ch * 64 + lane;
+        const bool occupied = z <= B.hi[2] && o[z] != 0;
+        bool sel = occupied;
+        if (occupied && B.cull) {
+            const int2 r = range[brick_row + (z / BRICK - B.b0[2])];
+            const double pz = voxel_centre(z, B.res, B.bmin[2]);
+            sel = false;
+            for (int k = r.x; k <= r.y && !sel; k++) {
+                const double dx = px - s_pos[k], dy = py - s_pos[SWEPT_MAX_COARSE + k], dz = pz - s_pos[2 * SWEPT_MAX_COARSE + k];
+                sel = !(dx * dx + dy * dy + dz * dz > B.far2);
+            }
+        }
+        const unsigned long long m = __ballot(sel);
+        if (lane == 0) mask[row * B.n_chunks + ch] = m;
+        n_sel += __popcll(m);
+        n_occ += occupied ? 1ull : 0ull;
+    }
+    n_occ = wave_sum_u64(n_occ);
+    if (lane == 0) {
+        count[row] = n_sel;
+        if (n_occ) atomicAdd(&stats[0], n_occ);
+        if (n_sel) atomicAdd(&stats[1], (unsigned long long)n_sel);
+    }
+}
+
+// candidates of a row from its masks, at base[row]: voxel index (x * Y + y) * Z + z and centre
+__global__ __launch_bounds__(64 * SEL_WAVES) void tc_emit_kernel(SelBox B, const unsigned long long *__restrict__ mask,
+                                                                 const int *__restrict__ base, long long *__restrict__ vox,
+                                                                 double *__restrict__ xyz) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ny = B.hi[1] - B.lo[1] + 1;
+    const long long n_rows = (long long)(B.hi[0] - B.lo[0] + 1) * ny;
+    const long long row = (long long)blockIdx.x * SEL_WAVES + wave;
+    if (row >= n_rows) return;
+    const int x = B.lo[0] + (int)(row / ny), y = B.lo[1] + (int)(row % ny);
+    const double px = voxel_centre(x, B.res, B.bmin[0]), py = voxel_centre(y, B.res, B.bmin[1]);
+    long long out = base[row];
+    for (int ch = 0; ch < B.n_chunks; ch++) {
+        const unsigned long long m = mask[row * B.n_chunks + ch];
+        if ((m >> lane) & 1ull) {
+            const int z = B.lo[2] + ch * 64 + lane;
+            const long long pos = out + __popcll(m & ((1ull << lane) - 1ull));
+            vox[pos] = ((long long)x * B.Y + y) * B.Z + z;
+            xyz[3 * pos] = px; xyz[3 * pos + 1] = py; xyz[3 * pos + 2] = voxel_centre(z, B.res, B.bmin[2]);
+        }
+        out += __popcll(m);
+    }
+}
+
+// ---- reduction ------------------------------------------------------------------------------------------------------
+// doubles as unsigned keys of the same order (an integer atomicMin then is the minimum of the doubles)
+__device__ __forceinline__ unsigned long long ordered_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ordered_value(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+// the piece a global time lies in: Trajectory::locatePieceIdx's sequential subtraction with its `>` rule (traj_locate_l)
+__device__ __forceinline__ int locate_piece(const double *T, int N, double t) {
+    int idx = 0;
+    while (idx < N && t > T[idx]) { t -= T[idx]; idx++; }
+    return idx == N ? N - 1 : idx;
+}
+struct MinRec { double v; long long j; };          // value and list position; j = LLONG_MAX: nothing yet
+__device__ __forceinline__ MinRec min_rec(MinRec a, MinRec b) { return (b.v < a.v || (b.v == a.v && b.j < a.j)) ? b : a; }
+__device__ __forceinline__ MinRec wave_min_rec(MinRec r) {
+    for (int off = 32; off >= 1; off >>= 1) {
+        MinRec o;
+        o.v = __shfl_xor(r.v, off, 64); o.j = __shfl_xor(r.j, off, 64);
+        r = min_rec(r, o);
+    }
+    return r;
+}
+__device__ __forceinline__ MinRec block_min_rec(MinRec r, MinRec *s_w) {       // 256 threads; the result in thread 0
+    r = wave_min_rec(r);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) for (int w = 1; w < 4; w++) r = min_rec(r, s_w[w]);
+    return r;
+}
+
+// per candidate: qualified (value != 10), below the margin (flag), below 0, the piece of its t* (piece_key: ordered-key minimum);
+// per workgroup the smallest (value, position); counts[0..2] += qualified, below margin, penetrating
+__global__ __launch_bounds__(256) void tc_reduce_kernel(long long n, const double *__restrict__ val, const double *__restrict__ ts,
+                                                        const double *__restrict__ T, int N, double margin, int *__restrict__ flag,
+                                                        unsigned long long *piece_key, MinRec *__restrict__ partial,
+                                                        unsigned long long *counts) {
+    __shared__ MinRec s_w[4];
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    MinRec r{1.0e300, LLONG_MAX};
+    unsigned long long q = 0, below = 0, pen = 0;
+    if (j < n) {
+        const double v = val[j];
+        const bool qualified = v != 1e1;
+        if (qualified) {
+            r.v = v; r.j = j;
+            q = 1; below = v < margin ? 1 : 0; pen = v < 0.0 ? 1 : 0;
+            atomicMin(&piece_key[locate_piece(T, N, ts[j])], ordered_key(v));
+        }
+        flag[j] = (int)below;
+    }
+    q = wave_sum_u64(q); below = wave_sum_u64(below); pen = wave_sum_u64(pen);
+    if ((threadIdx.x & 63) == 0) {
+        if (q) atomicAdd(&counts[0], q);
+        if (below) atomicAdd(&counts[1], below);
+        if (pen) atomicAdd(&counts[2], pen);
+    }
+    r = block_min_rec(r, s_w);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// what the device hands back: [0] min value [1] its t* [2..4] its point [5] voxel (as int64 bits) [6] piece (as int64 bits)
+constexpr int REPORT_WORDS = 7;
+__global__ __launch_bounds__(256) void tc_final_kernel(const MinRec *__restrict__ partial, int n_partial, const double *__restrict__ val,
+                                                       const double *__restrict__ ts, const long long *__restrict__ vox,
+                                                       const double *__restrict__ xyz, const double *__restrict__ T, int N,
+                                                       const unsigned long long *__restrict__ piece_key, double *__restrict__ piece_min,
+                                                       double *__restrict__ report) {
+    __shared__ MinRec s_w[4];
+    MinRec r{1.0e300, LLONG_MAX};
+    for (int k = threadIdx.x; k < n_partial; k += blockDim.x) r = min_rec(r, partial[k]);
+    r = block_min_rec(r, s_w);
+    if (threadIdx.x == 0) {
+        long long voxel = -1, piece = -1;
+        if (r.j == LLONG_MAX) {
+            report[0] = 1e1; report[1] = -1.0; report[2] = report[3] = report[4] = 0.0;
+        } else {
+            report[0] = r.v; report[1] = ts[r.j];
+            report[2] = xyz[3 * r.j]; report[3] = xyz[3 * r.j + 1]; report[4] = xyz[3 * r.j + 2];
+            voxel = vox[r.j]; piece = locate_piece(T, N, ts[r.j]);
+        }
+        report[5] = __longlong_as_double(voxel); report[6] = __longlong_as_double(piece);
+    }
+    for (int i = threadIdx.x; i < N; i += blockDim.x) piece_min[i] = ordered_value(piece_key[i]);
+}
+__global__ void tc_key_fill_kernel(unsigned long long *piece_key, int N) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N) piece_key[i] = ordered_key(1e1);
+}
+// the points below the margin, in list (= voxel) order: (x, y, z, value, t*)
+__global__ void tc_rows_kernel(long long n, const int *__restrict__ flag, const int *__restrict__ base, const double *__restrict__ xyz,
+                               const double *__restrict__ val, const double *__restrict__ ts, double *__restrict__ rows) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n || !flag[j]) return;
+    double *o = rows + 5 * (size_t)base[j];
+    o[0] = xyz[3 * j]; o[1] = xyz[3 * j + 1]; o[2] = xyz[3 * j + 2]; o[3] = val[j]; o[4] = ts[j];
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------
+void free_rows(TrajCheckState *s) {
+    if (s->d_rows) (void)hipFree(s->d_rows);
+    s->d_rows = nullptr; s->n_rows = 0; s->have = false;
+}
+
+// what can be checked without a ctx (reported through isdf_last_error(NULL) when there is none)
+int check_args(isdf_ctx *c, int N, const void *T, const void *coeffs, const isdf_traj_check_params *p) {
+    if (N < 1 || !T || !coeffs) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: null trajectory");
+    if (p) {
+        if (p->mode != ISDF_SWEPT_FIELD_PLANNER && p->mode != ISDF_SWEPT_FIELD_CLOSED) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: unknown mode");
+        if (!std::isfinite(p->margin)) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: margin must be finite");
+    }
+    return ISDF_OK;
+}
+// ... and what needs one; margin_out = the margin in force
+int check_state(isdf_ctx *c, const isdf_traj_check_params *p, double *margin_out) {
+    { const int rc = swept_check_ctx(c); if (rc) return rc; }
+    if (!c->have_geom || !c->d_occ)
+        return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: no occupancy grid (isdf_set_grid with ISDF_GRID_OCCUPANCY, or isdf_set_pointcloud)");
+    const double band = 2 * c->cfg.safety_hor + 0.1;
+    const double margin = (p && p->margin >= 0.0) ? p->margin : c->cfg.safety_hor;
+    if (margin > band)
+        return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: margin above 2 safety_hor + 0.1 - points beyond that band read 10, the query cannot answer it");
+    *margin_out = margin;
+    return ISDF_OK;
+}
+
+// the check on device arrays; hT = the durations on the host.  d_piece_min: N doubles on the device (required).
+int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const int mode, const double margin,
+              isdf_traj_check_info *info, double *d_piece_min, hipStream_t st) {
+    if (!c->tck) c->tck = new TrajCheckState();
+    TrajCheckState *k = c->tck;
+    free_rows(k);
+    SweptMeshState *s;
+    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    hipEvent_t ev[4];
+    for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
+    struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
+    HIPCHK(c, hipEventRecord(ev[0], st));
+
+    // ---- select: the coarse positions, their box, bricks, rows, scan, emit
+    { const int rc = swept_field_coarse_table(c, N, d_T, d_C, mode, st); if (rc) return rc; }
+    std::vector<double> pos(3 * (size_t)SWEPT_MAX_COARSE);
+    int n_coarse = 0;
+    HIPCHK(c, hipMemcpyAsync(pos.data(), s->d_coarse_pose, pos.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&n_coarse, s->d_n_coarse, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const bool mesh = c->shape.kind == ISDF_SHAPE_MESH;
+    const double R = mesh ? std::max(c->mesh_rmax, c->shape.bound_radius) : c->shape.bound_radius;
+    const bool cull = R > 0.0 && std::isfinite(R);
+    const double band = 2 * c->cfg.safety_hor + 0.1;
+    const double far_r = cull ? R + band * (mesh ? 1.05 : 1.0) : 0.0;       // the scan's own expression (swept_sweep.hip, scan_body)
+    const DevGrid &G = c->grid;
+    SelBox B{};
+    B.X = G.X; B.Y = G.Y; B.Z = G.Z; B.res = G.res;
+    const int dim[3] = {G.X, G.Y, G.Z};
+    bool empty = n_coarse < 1;
+    for (int a = 0; a < 3 && !empty; a++) {
+        B.bmin[a] = G.bmin[a];
+        if (!cull) { B.lo[a] = 0; B.hi[a] = dim[a] - 1; continue; }
+        double mn = 1e300, mx = -1e300;
+        for (int i = 0; i < n_coarse; i++) { const double v = pos[(size_t)a * SWEPT_MAX_COARSE + i]; mn = std::min(mn, v); mx = std::max(mx, v); }
+        if (!std::isfinite(mn) || !std::isfinite(mx)) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: non-finite trajectory position");
+        // voxels whose centre (i + 0.5) res + origin can lie within far_r of a sample on this axis, one more on either side for the rounding
+        const double l = std::floor((mn - far_r - G.bmin[a]) / G.res - 0.5) - 1.0, h = std::floor((mx + far_r - G.bmin[a]) / G.res - 0.5) + 2.0;
+        if (h < 0.0 || l > (double)(dim[a] - 1)) { empty = true; break; }
+        B.lo[a] = (int)std::max(l, 0.0); B.hi[a] = (int)std::min(h, (double)(dim[a] - 1));
+    }
+    B.cull = cull ? 1 : 0;
+    const double slack = 1.0 + 1e-9;        // the scan compares its own rounding of the same distance: never tighter than it
+    const double bdiag = std::sqrt(3.0) * (BRICK / 2) * G.res;        // brick centre to its farthest voxel centre is sqrt(3) 3.5 res
+    B.far2 = far_r * far_r * slack; B.bfar2 = (far_r + bdiag) * (far_r + bdiag) * slack;
+    unsigned long long cnt[2] = {0, 0};
+    DBuf<long long> vox;
+    DBuf<double> xyz;
+    if (!empty) {
+        for (int a = 0; a < 3; a++) { B.b0[a] = B.lo[a] / BRICK; B.nb[a] = B.hi[a] / BRICK - B.b0[a] + 1; }
+        B.n_chunks = (B.hi[2] - B.lo[2] + 64) / 64;
+        const long long n_rows = (long long)(B.hi[0] - B.lo[0] + 1) * (B.hi[1] - B.lo[1] + 1);
+        const long long n_bricks = (long long)B.nb[0] * B.nb[1] * B.nb[2];
+        DBuf<int2> range;
+        DBuf<unsigned long long> mask, d_cnt;
+        DBuf<int> count, base;
+        HIPCHK(c, range.alloc((size_t)n_bricks));
+        HIPCHK(c, mask.alloc((size_t)n_rows * B.n_chunks));
+        HIPCHK(c, count.alloc((size_t)n_rows)); HIPCHK(c, base.alloc((size_t)n_rows));
+        HIPCHK(c, d_cnt.alloc(2));
+        HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+        if (cull) hipLaunchKernelGGL(tc_brick_kernel, dim3(std::min<unsigned>(blocks(n_bricks), 4096u)), dim3(256), 0, st, B,
+                                     (const double *)s->d_coarse_pose, (const int *)s->d_n_coarse, range.p);
+        hipLaunchKernelGGL(tc_row_kernel, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B, (const uint8_t *)c->d_occ,
+                           (const int2 *)range.p, (const double *)s->d_coarse_pose, (const int *)s->d_n_coarse, mask.p, count.p, d_cnt.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (cnt[1] > (unsigned long long)INT32_MAX) return fail(c, ISDF_ERR_OVERFLOW, "trajectory check: more than 2^31 candidate voxels");
+        if (cnt[1]) {
+            { const int rc = exclusive_sum(c, count.p, base.p, n_rows, st); if (rc) return rc; }
+            HIPCHK(c, vox.alloc((size_t)cnt[1]));
+            HIPCHK(c, xyz.alloc((size_t)cnt[1] * 3));
+            hipLaunchKernelGGL(tc_emit_kernel, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B,
+                               (const unsigned long long *)mask.p, (const int *)base.p, vox.p, xyz.p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipStreamSynchronize(st));          // (mask / count / base go out of scope here)
+        }
+    }
+    const long long n = (long long)cnt[1];
+    HIPCHK(c, hipEventRecord(ev[1], st));
+
+    // ---- field
+    DBuf<double> val, ts;
+    HIPCHK(c, val.alloc((size_t)n)); HIPCHK(c, ts.alloc((size_t)n));
+    { const int rc = swept_field_run(c, N, d_T, d_C, xyz.p, n, mode, val.p, ts.p, st); if (rc) return rc; }
+    HIPCHK(c, hipEventRecord(ev[2], st));
+
+    // ---- reduce
+    const int n_part = (int)std::max<long long>(1, blocks(n));
+    DBuf<int> flag, fbase;
+    DBuf<unsigned long long> key, d_counts;
+    DBuf<MinRec> partial;
+    DBuf<double> report;
+    HIPCHK(c, flag.alloc((size_t)n)); HIPCHK(c, fbase.alloc((size_t)n));
+    HIPCHK(c, key.alloc((size_t)N)); HIPCHK(c, d_counts.alloc(3));
+    HIPCHK(c, partial.alloc((size_t)n_part)); HIPCHK(c, report.alloc(REPORT_WORDS));
+    HIPCHK(c, hipMemsetAsync(d_counts.p, 0, 3 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(tc_key_fill_kernel, dim3(blocks(N)), dim3(256), 0, st, key.p, N);
+    if (n > 0) hipLaunchKernelGGL(tc_reduce_kernel, dim3(n_part), dim3(256), 0, st, n, (const double *)val.p, (const double *)ts.p, d_T, N,
+                                  margin, flag.p, key.p, partial.p, d_counts.p);
+    hipLaunchKernelGGL(tc_final_kernel, dim3(1), dim3(256), 0, st, (const MinRec *)partial.p, n > 0 ? n_part : 0, (const double *)val.p,
+                       (const double *)ts.p, (const long long *)vox.p, (const double *)xyz.p, d_T, N,
+                       (const unsigned long long *)key.p, d_piece_min, report.p);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long counts[3];
+    double rep[REPORT_WORDS];
+    HIPCHK(c, hipMemcpyAsync(counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rep, report.p, sizeof(rep), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (counts[1]) {
+        { const int rc = exclusive_sum(c, flag.p, fbase.p, n, st); if (rc) return rc; }
+        HIPCHK(c, hipMalloc(&k->d_rows, (size_t)counts[1] * 5 * sizeof(double)));
+        hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)flag.p, (const int *)fbase.p,
+                           (const double *)xyz.p, (const double *)val.p, (const double *)ts.p, k->d_rows);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[3], st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    k->n_rows = (long long)counts[1]; k->have = true;
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->occupied_in_box = (long long)cnt[0];
+        info->candidates = n;
+        info->qualified = (long long)counts[0];
+        info->n_below_margin = (long long)counts[1];
+        info->n_penetrating = (long long)counts[2];
+        info->min_clearance = rep[0]; info->min_tstar = rep[1];
+        for (int a = 0; a < 3; a++) info->min_point[a] = rep[2 + a];
+        long long w;
+        std::memcpy(&w, &rep[5], sizeof(w)); info->min_voxel = w;
+        std::memcpy(&w, &rep[6], sizeof(w)); info->min_piece = (int32_t)w;
+        info->culled = cull ? 1 : 0;
+        info->margin = margin; info->far_r = far_r;
+        float ms[3] = {0.f, 0.f, 0.f};
+        for (int q = 0; q < 3; q++) HIPCHK(c, hipEventElapsedTime(&ms[q], ev[q], ev[q + 1]));
+        info->select_ms = ms[0]; info->field_ms = ms[1]; info->reduce_ms = ms[2];
+    }
+    return ISDF_OK;
+}
+
+}  // namespace
+
+void isdf_traj_check_release_all(isdf_ctx *c) {
+    if (!c->tck) return;
+    free_rows(c->tck);
+    if (c->tck->d_traj) (void)hipFree(c->tck->d_traj);
+    delete c->tck;
+    c->tck = nullptr;
+}
+
+extern "C" void isdf_traj_check_params_default(isdf_traj_check_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->margin = -1.0;                       // negative: cfg.safety_hor of the ctx
+    p->mode = ISDF_SWEPT_FIELD_PLANNER;
+}
+
+extern "C" int isdf_traj_check_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const isdf_traj_check_params *p,
+                                      isdf_traj_check_info *info_out, double *d_piece_min_out, void *stream) {
+    { const int rc = check_args(c, N, d_T, d_coeffs, p); if (rc) return rc; }
+    if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "trajectory check: null ctx");
+    double margin = 0.0;
+    { const int rc = check_state(c, p, &margin); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<double> hT(N);          // the 300 s rule needs the durations on the host
+    HIPCHK(c, hipMemcpyAsync(hT.data(), d_T, N * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    { const int rc = swept_check_traj(c, N, hT.data()); if (rc) return rc; }
+    DBuf<double> own;
+    if (!d_piece_min_out) { HIPCHK(c, own.alloc((size_t)N)); d_piece_min_out = own.p; }
+    return check_run(c, N, d_T, d_coeffs, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, d_piece_min_out, st);
+}
+
+extern "C" int isdf_traj_check(isdf_ctx *c, int N, const double *T, const double *coeffs, const isdf_traj_check_params *p,
+                               isdf_traj_check_info *info_out, double *piece_min_out) {
+    { const int rc = check_args(c, N, T, coeffs, p); if (rc) return rc; }
+    if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "trajectory check: null ctx");
+    double margin = 0.0;
+    { const int rc = check_state(c, p, &margin); if (rc) return rc; }
+    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
+    for (int q = 0; q < 18 * N; q++) if (!std::isfinite(coeffs[q])) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: non-finite coefficient");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->tck) c->tck = new TrajCheckState();
+    TrajCheckState *k = c->tck;
+    hipStream_t st = c->stream;
+    { const int rc = isdf_ensure_doubles(c, &k->d_traj, &k->traj_cap, (size_t)20 * N); if (rc) return rc; }     // T | coeffs | per-piece minima
+    HIPCHK(c, hipMemcpyAsync(k->d_traj, T, N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(k->d_traj + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
+    double *d_pm = k->d_traj + 19 * (size_t)N;
+    { const int rc = check_run(c, N, k->d_traj, k->d_traj + N, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, d_pm, st); if (rc) return rc; }
+    if (piece_min_out) HIPCHK(c, hipMemcpy(piece_min_out, d_pm, N * sizeof(double), hipMemcpyDeviceToHost));
+    return ISDF_OK;
+}
+
+extern "C" int isdf_traj_check_get(isdf_ctx *c, double *rows_out, long long capacity) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!c->tck || !c->tck->have) return fail(c, ISDF_ERR_STATE, "trajectory check: nothing kept (isdf_traj_check)");
+    TrajCheckState *k = c->tck;
+    if (capacity < k->n_rows) return fail(c, ISDF_ERR_OVERFLOW, "trajectory check: output capacity smaller than the number of points below the margin");
+    if (k->n_rows > 0 && !rows_out) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: null output");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (k->n_rows) HIPCHK(c, hipMemcpy(rows_out, k->d_rows, (size_t)k->n_rows * 5 * sizeof(double), hipMemcpyDeviceToHost));
+    return ISDF_OK;
+}
+
+extern "C" int isdf_traj_check_release(isdf_ctx *c) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (c->tck) free_rows(c->tck);
+    return ISDF_OK;
+}
+
+extern "C" int isdf_traj_collide(isdf_ctx *c, int N, const double *T, const double *coeffs) {
+    isdf_traj_check_info info;
+    const int rc = isdf_traj_check(c, N, T, coeffs, nullptr, &info, nullptr);
+    if (rc) return rc;
+    return info.n_penetrating > 0 ? 1 : 0;
+}

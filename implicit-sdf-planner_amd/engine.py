@@ -406,6 +406,61 @@ class Engine:
     def write_obj(self, path, V, F):
         return write_obj(path, V, F, self.lib)
 
+    # ---- trajectory clearance against the whole occupancy grid (isdf_traj_check*, isdf_traj_collide)
+    def _traj_check_params(self, margin, mode):
+        p = capi.IsdfTrajCheckParams()
+        self.lib.isdf_traj_check_params_default(C.byref(p))
+        if margin is not None:
+            p.margin = float(margin)
+        p.mode = int(mode)
+        return p
+
+    @staticmethod
+    def _traj_check_report(info, piece_min):
+        d = {name: (np.array(getattr(info, name)) if name == "min_point" else getattr(info, name))
+             for name, _ in capi.IsdfTrajCheckInfo._fields_}
+        d["piece_min"] = piece_min
+        return d
+
+    def traj_check(self, T, coeffs_colmajor, margin=None, mode=capi.SWEPT_FIELD_PLANNER):
+        """Clearance of the trajectory's swept volume against every occupied voxel centre of the ctx's occupancy grid: a dict of the
+        isdf_traj_check_info fields and "piece_min" (N,).  margin None = cfg.safety_hor.  The points below the margin: traj_check_points()."""
+        T = np.ascontiguousarray(T, dtype=np.float64); N = T.size
+        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(-1)
+        p = self._traj_check_params(margin, mode)
+        info = capi.IsdfTrajCheckInfo()
+        piece_min = np.zeros(N)
+        self._check(self.lib.isdf_traj_check(self.h, N, _p(T), _p(Cc), C.byref(p), C.byref(info), _p(piece_min)))
+        self._traj_check_rows = int(info.n_below_margin)
+        return self._traj_check_report(info, piece_min)
+
+    def traj_check_device(self, N, d_T, d_coeffs, margin=None, mode=capi.SWEPT_FIELD_PLANNER, d_piece_min=0, stream=0):
+        """The same with the trajectory (and, if given, the N per-piece minima) on the device; "piece_min" of the dict is None."""
+        p = self._traj_check_params(margin, mode)
+        info = capi.IsdfTrajCheckInfo()
+        self._check(self.lib.isdf_traj_check_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), C.byref(p), C.byref(info),
+                                                    C.c_void_p(d_piece_min), C.c_void_p(stream)))
+        self._traj_check_rows = int(info.n_below_margin)
+        return self._traj_check_report(info, None)
+
+    def traj_check_points(self):
+        """The last check's points below the margin in voxel order: rows (x, y, z, value, t*)."""
+        rows = np.zeros((getattr(self, "_traj_check_rows", 0), 5))
+        self._check(self.lib.isdf_traj_check_get(self.h, _p(rows), rows.shape[0]))
+        return rows
+
+    def traj_check_release(self):
+        self._check(self.lib.isdf_traj_check_release(self.h))
+
+    def traj_collide(self, T, coeffs_colmajor):
+        """isTrajCollide: True if an occupied voxel centre lies inside the swept volume (default parameters)."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(-1)
+        rc = self.lib.isdf_traj_collide(self.h, T.size, _p(T), _p(Cc))
+        if rc < 0:
+            self._check(rc)
+        return bool(rc)
+
     # ---- full objective callback (TrajOptimizer::costFunctionLmbm)
     def set_trajectory(self, N, head_pva, tail_pva, rho):
         """head/tail: 3x3 arrays whose COLUMNS are position, velocity, acceleration (Eigen::Matrix3d of setConditions)."""

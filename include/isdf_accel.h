@@ -398,6 +398,57 @@ int isdf_swept_mesh_build(isdf_ctx *ctx, int N, const double *T, const double *c
 int isdf_swept_mesh_get(isdf_ctx *ctx, double *V_out, int capV, int32_t *F_out, int capF);
 int isdf_swept_mesh_release(isdf_ctx *ctx);      /* frees the kept mesh */
 
+/* ---- trajectory clearance check -------------------------------------------------------------------------------- */
+/* SweptVolumeManager::isTrajCollide (sw_manager.hpp:764: a stub, "currently always returns false"), the verdict generateTraj asks
+ * for once the back end has finished (plan_manager.cpp, end of generateTraj): how close the swept volume of a trajectory comes to
+ * any occupied voxel centre of the WHOLE map - not only to the points isdf_gather_points collected around the A* path.
+ * The map is the ctx's occupancy grid (isdf_set_grid with ISDF_GRID_OCCUPANCY, or isdf_set_pointcloud; none:
+ * ISDF_ERR_INVALID_ARG); obstacle points are voxel centres (index + 0.5) * res + origin, each operation rounded on its own.  The
+ * trajectory is passed as isdf_eval takes it.  Rules as for isdf_swept_sdf: any single-device ctx whatever cfg.variant is, a
+ * multi-device ctx ISDF_ERR_UNSUPPORTED, 300 s or more ISDF_ERR_INVALID_ARG, a point with more than 32 intervals
+ * ISDF_ERR_OVERFLOW; own scratch - the V1 step's points, lastTstar, duration state and the kept swept mesh are not touched.
+ * Three steps on the device: the occupied voxels within far_r = R + (2 safety_hor + 0.1) of some coarse (0.2 s)
+ * sample of the trajectory (R: isdf_shape.bound_radius; mesh robots: their largest vertex norm, band x 1.05) are selected in
+ * ascending voxel index - every other point reads 10 / -1 from the field query, so nothing is lost; a shape without a radius
+ * takes every occupied voxel (culled = 0) -, put through the field query in `mode`, and reduced.  The report is the field
+ * query's answer at voxel centres, bit for bit and the same bytes on every run; it is not a continuous certificate between them. */
+typedef struct isdf_traj_check_params {
+    double margin;       /* level below which a point is reported; negative (default) = cfg.safety_hor, the level below which the
+                            V1 term charges; above 2 safety_hor + 0.1 the query cannot answer: ISDF_ERR_INVALID_ARG            */
+    int32_t mode;        /* ISDF_SWEPT_FIELD_PLANNER (default: the collision term's own query) or ISDF_SWEPT_FIELD_CLOSED       */
+    int32_t reserved;
+} isdf_traj_check_params;
+typedef struct isdf_traj_check_info {
+    int64_t occupied_in_box;     /* occupied voxels of the selection box (the samples' box grown by far_r; all of the grid if !culled) */
+    int64_t candidates;          /* voxels put through the field query                                                         */
+    int64_t qualified;           /* candidates with a qualifying interval (value != 10)                                        */
+    int64_t n_below_margin;      /* qualified candidates with value < margin: the rows isdf_traj_check_get returns             */
+    int64_t n_penetrating;       /* ... with value < 0                                                                         */
+    double min_clearance;        /* smallest value (10: nothing qualified); ties go to the lowest voxel index                  */
+    double min_tstar;            /* its t* (-1: nothing qualified)                                                             */
+    double min_point[3];         /* its voxel centre                                                                           */
+    int64_t min_voxel;           /* its voxel index (x * ny + y) * nz + z (-1: nothing qualified)                              */
+    int32_t min_piece;           /* the piece min_tstar lies in (Trajectory::locatePieceIdx; -1: nothing qualified)            */
+    int32_t culled;              /* 1: candidates selected by the bounding sphere; 0: the shape has none, every occupied voxel  */
+    double margin, far_r;        /* the margin in force; the selection radius (0 if !culled)                                   */
+    double select_ms, field_ms, reduce_ms;       /* device time of the three steps (events on the stream)                      */
+} isdf_traj_check_info;
+void isdf_traj_check_params_default(isdf_traj_check_params *p);
+/* params NULL = defaults.  piece_min_out (N doubles or NULL): per piece the smallest value among the points whose t* lies in it
+ * (10: none).  The points below the margin are kept in the ctx (replacing the previous check's) until released. */
+int isdf_traj_check(isdf_ctx *ctx, int N, const double *T, const double *coeffs, const isdf_traj_check_params *params,
+                    isdf_traj_check_info *info_out, double *piece_min_out);
+/* the same with the trajectory (and the per-piece array, or NULL) on the device; synchronises `stream` before it returns */
+int isdf_traj_check_device(isdf_ctx *ctx, int N, const double *d_T, const double *d_coeffs, const isdf_traj_check_params *params,
+                           isdf_traj_check_info *info_out, double *d_piece_min_out, void *stream);
+/* the last check's points below the margin in voxel order, rows_out capacity x 5: (x, y, z, value, t*); ISDF_ERR_OVERFLOW
+ * (nothing written) if capacity < n_below_margin */
+int isdf_traj_check_get(isdf_ctx *ctx, double *rows_out, long long capacity);
+int isdf_traj_check_release(isdf_ctx *ctx);      /* frees the kept rows */
+/* isTrajCollide (sw_manager.hpp:764) as plan_manager.cpp calls it: 1 = some occupied voxel centre lies inside the swept volume
+ * (n_penetrating > 0 at the default parameters), 0 = none, negative = isdf_status */
+int isdf_traj_collide(isdf_ctx *ctx, int N, const double *T, const double *coeffs);
+
 /* ---- full objective callback ------------------------------------------------------------------------------ */
 /* TrajOptimizer::costFunctionLmbm (back_end_optimizer.hpp:358-430): x = [tau(N) | inner waypoints 3(N-1)] ->
  * cost, g.  MINCO (minco.hpp:397-655: setParameters, energy and its partials, propogateGrad) and the sweeps: for
