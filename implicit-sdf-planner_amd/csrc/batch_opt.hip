@@ -169,7 +169,7 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
     // device + pinned buffers for a full batch per slot: N_SLOTS rounds are in flight, each on its own stream
     constexpr int N_SLOTS = 4;          // rounds in flight at most (slots_used of them are used)
     struct Slot {
-        double *h_pin = nullptr, *d_buf = nullptr;
+        PinBuf<double> h_pin; DevBuf<double> d_buf;
         std::vector<int> active; int group = -1; hipStream_t stream = nullptr; hipEvent_t done = nullptr, sweep_done = nullptr; bool busy = false;
     } slots[N_SLOTS];
     const size_t in_all = (size_t)n_traj * b.in_per, out_all = (size_t)n_traj * b.ostride;
@@ -182,16 +182,14 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
     const size_t word_at = b.dev ? pin_res + res_all : in_all + out_all;
     auto release = [&] {
         for (Slot &q : slots) {
-            if (q.h_pin) (void)hipHostFree(q.h_pin);
-            if (q.d_buf) (void)hipFree(q.d_buf);
+            q.h_pin.release(); q.d_buf.release();
             if (q.done) (void)hipEventDestroy(q.done); if (q.sweep_done) (void)hipEventDestroy(q.sweep_done);
             if (q.stream) (void)hipStreamDestroy(q.stream);
         }
     };
     for (Slot &q : slots) {
         // pinned: [T | coeffs of the round | sweep out | overflow word]; device: [T | coeffs | sweep out]
-        if (hipHostMalloc((void **)&q.h_pin, (word_at + 1) * sizeof(double), hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(&q.d_buf, dev_all * sizeof(double)) != hipSuccess ||
+        if (q.h_pin.reserve(c, word_at + 1) != ISDF_OK || q.d_buf.alloc(dev_all) != hipSuccess ||
             hipStreamCreate(&q.stream) != hipSuccess ||
             hipEventCreateWithFlags(&q.done, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&q.sweep_done, hipEventDisableTiming) != hipSuccess) { release(); return isdf_fail(c, ISDF_ERR_HIP, "batch buffers: allocation failed"); }

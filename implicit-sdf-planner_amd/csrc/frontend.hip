@@ -262,9 +262,7 @@ void bfs_order(int xk, int yk, int sx, int sy, std::vector<unsigned short> &out)
 
 void fe_free(isdf_ctx *c) {
     if (c->fe.h_cspace) { if (c->fe.h_cspace_pinned) (void)hipHostFree(c->fe.h_cspace); else std::free(c->fe.h_cspace); }
-    void *ptrs[] = {c->fe.d_rows, c->fe.d_bits, c->fe.d_rot, c->fe.d_seq, c->fe.d_seq_len, c->fe.d_row_list, c->fe.d_row_ptr, c->fe.d_cspace};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    c->fe = isdf_ctx::FrontEnd{};
+    c->fe = isdf_ctx::FrontEnd{};           // (the tables free themselves)
 }
 
 FeParams fe_params(const isdf_ctx *c) {
@@ -309,10 +307,10 @@ extern "C" int isdf_frontend_build(isdf_ctx *c, const isdf_frontend_config *cfg)
         }
     }
     const FeParams F = fe_params(c);
-    HIPCHK(c, hipMalloc(&fe.d_rot, rot.size() * sizeof(double)));
+    HIPCHK(c, fe.d_rot.alloc(rot.size()));
     HIPCHK(c, hipMemcpy(fe.d_rot, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice));
     const size_t n_rows = (size_t)n_att * F.k * F.k;
-    HIPCHK(c, hipMalloc(&fe.d_rows, n_rows * sizeof(unsigned)));
+    HIPCHK(c, fe.d_rows.alloc(n_rows));
     {
         const dim3 grid((unsigned)((n_rows + 255) / 256)), block(256);
         if (c->shape.kind == ISDF_SHAPE_MESH) hipLaunchKernelGGL(fe_shape_rows_kernel<ISDF_SHAPE_MESH>, grid, block, 0, c->stream, c->shape, F, fe.d_rot, fe.d_rows);
@@ -323,7 +321,7 @@ extern "C" int isdf_frontend_build(isdf_ctx *c, const isdf_frontend_config *cfg)
     for (int a = 0; a < n_att; a++)
         if (!reached[a]) HIPCHK(c, hipMemsetAsync(fe.d_rows + (size_t)a * F.k * F.k, 0, (size_t)F.k * F.k * sizeof(unsigned), c->stream));
     const size_t n_bits = (size_t)F.iX * F.iY * F.iZW;
-    HIPCHK(c, hipMalloc(&fe.d_bits, (n_bits + 2) * sizeof(unsigned)));
+    HIPCHK(c, fe.d_bits.alloc(n_bits + 2));
     HIPCHK(c, hipMemsetAsync(fe.d_bits + n_bits, 0, 2 * sizeof(unsigned), c->stream));
     hipLaunchKernelGGL(fe_map_bits_kernel, dim3(2048), dim3(256), 0, c->stream, F, c->d_occ, fe.d_bits);
     HIPCHK(c, hipGetLastError());
@@ -337,8 +335,8 @@ extern "C" int isdf_frontend_build(isdf_ctx *c, const isdf_frontend_config *cfg)
     for (int a = 0; a < n_att; a++) { std::copy(orders[a].begin(), orders[a].end(), seq.begin() + (size_t)a * stride); seq_len[a] = (int)orders[a].size(); }
     fe.seq_stride = (int)stride;
     fe.h_seq = seq; fe.h_seq_len = seq_len;
-    HIPCHK(c, hipMalloc(&fe.d_seq, seq.size() * sizeof(unsigned short)));
-    HIPCHK(c, hipMalloc(&fe.d_seq_len, seq_len.size() * sizeof(int)));
+    HIPCHK(c, fe.d_seq.alloc(seq.size()));
+    HIPCHK(c, fe.d_seq_len.alloc(seq_len.size()));
     HIPCHK(c, hipMemcpyAsync(fe.d_seq, seq.data(), seq.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(fe.d_seq_len, seq_len.data(), seq_len.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -357,8 +355,8 @@ extern "C" int isdf_frontend_build(isdf_ctx *c, const isdf_frontend_config *cfg)
             ptr[a + 1] = (int)list.size();
         }
         fe.n_row_list = (int)list.size();
-        HIPCHK(c, hipMalloc(&fe.d_row_list, std::max<size_t>(1, list.size()) * sizeof(FeRow)));
-        HIPCHK(c, hipMalloc(&fe.d_row_ptr, ptr.size() * sizeof(int)));
+        HIPCHK(c, fe.d_row_list.alloc(std::max<size_t>(1, list.size()) * sizeof(FeRow)));
+        HIPCHK(c, fe.d_row_ptr.alloc(ptr.size()));
         if (!list.empty()) HIPCHK(c, hipMemcpy(fe.d_row_list, list.data(), list.size() * sizeof(FeRow), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(fe.d_row_ptr, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
     }
@@ -373,12 +371,12 @@ extern "C" int isdf_frontend_cspace(isdf_ctx *c, uint32_t *free_mask_out, double
     const size_t nw = 4 * (size_t)((F.n_att + 127) / 128);             // dwords per voxel
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)F.X * F.Y * F.Z;
-    if (!c->fe.d_cspace) HIPCHK(c, hipMalloc(&c->fe.d_cspace, n * nw * sizeof(unsigned)));
+    if (!c->fe.d_cspace) HIPCHK(c, c->fe.d_cspace.alloc(n * nw));
     hipEvent_t e0, e1;
     HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
     const long long n_wv = (long long)F.X * F.Y * ((F.Z + 63) >> 6);
-    hipExtLaunchKernelGGL(fe_cspace_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, c->stream, e0, e1, 0, F, c->d_occ, c->fe.d_bits,
-                          (const FeRow *)c->fe.d_row_list, c->fe.d_row_ptr, (uint4 *)c->fe.d_cspace);
+    hipExtLaunchKernelGGL(fe_cspace_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, c->stream, e0, e1, 0, F, c->d_occ.get(), c->fe.d_bits.get(),
+                          (const FeRow *)c->fe.d_row_list.get(), c->fe.d_row_ptr.get(), (uint4 *)c->fe.d_cspace.get());
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && free_mask_out) e = hipMemcpyAsync(free_mask_out, c->fe.d_cspace, n * nw * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -399,12 +397,11 @@ extern "C" int isdf_frontend_get_shape_kernels(isdf_ctx *c, uint8_t *out, int di
     if (!out) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)F.n_att * per;
-    uint8_t *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, n));
+    DevBuf<uint8_t> d;
+    HIPCHK(c, d.alloc(n));
     hipLaunchKernelGGL(fe_pack_shape_bytes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, F, c->fe.d_rows, d);
     hipError_t e = hipMemcpyAsync(out, d, n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     HIPCHK(c, e);
     return ISDF_OK;
 }
@@ -418,12 +415,11 @@ extern "C" int isdf_frontend_get_map_kernel(isdf_ctx *c, uint8_t *out, int dims_
     if (!out) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)F.iX * F.iY * zb;
-    uint8_t *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, n));
+    DevBuf<uint8_t> d;
+    HIPCHK(c, d.alloc(n));
     hipLaunchKernelGGL(fe_pack_map_bytes_kernel, dim3(2048), dim3(256), 0, c->stream, F, c->fe.d_bits, d, zb);
     hipError_t e = hipMemcpyAsync(out, d, n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     HIPCHK(c, e);
     return ISDF_OK;
 }
@@ -438,9 +434,9 @@ extern "C" int isdf_frontend_check(isdf_ctx *c, int n, const int32_t *index, con
     const FeParams F = fe_params(c);
     // one allocation: [index 3n int | fr n | fp n | cr n | cp n | kidx n int | ok n]
     const size_t bytes = (size_t)n * (3 * 4 + 8 * 4 + 4 + 1) + 64;
-    char *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, bytes));
-    double *d_fr = (double *)d, *d_fp = d_fr + n, *d_cr = d_fp + n, *d_cp = d_cr + n;
+    DevBuf<void> d;
+    HIPCHK(c, d.alloc(bytes));
+    double *d_fr = (double *)d.get(), *d_fp = d_fr + n, *d_cr = d_fp + n, *d_cp = d_cr + n;
     int *d_idx = (int *)(d_cp + n), *d_kidx = d_idx + (size_t)3 * n;
     uint8_t *d_ok = (uint8_t *)(d_kidx + n);
     int rc = ISDF_OK;
@@ -462,7 +458,6 @@ extern "C" int isdf_frontend_check(isdf_ctx *c, int n, const int32_t *index, con
     if (rc == ISDF_OK) chk(hipMemcpyAsync(child_pitch, d_cp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream), "download pitch");
     if (rc == ISDF_OK && kernel_index_out) chk(hipMemcpyAsync(kernel_index_out, d_kidx, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream), "download index");
     chk(hipStreamSynchronize(c->stream), "front-end sync");
-    (void)hipFree(d);
     return rc;
 }
 

@@ -144,9 +144,8 @@ extern "C" int isdf_create(isdf_ctx **out, const isdf_config *cfg) {
         c->env_no_lpt = on("ISDF_NO_LPT");
         c->minco_mode = on("ISDF_HOST_MINCO") ? 1 : (on("ISDF_DEVICE_MINCO") ? 2 : 0);
     }
-    if (hipSetDevice(c->device) != hipSuccess || hipMalloc(&c->d_stats, 8 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&c->d_traj_duration, sizeof(double)) != hipSuccess || hipMalloc(&c->d_n_coarse, sizeof(int)) != hipSuccess ||
-        hipMemset(c->d_traj_duration, 0, sizeof(double)) != hipSuccess || hipMemset(c->d_stats, 0, 8 * sizeof(unsigned long long)) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess) {
+    if (hipSetDevice(c->device) != hipSuccess || c->d_stats.alloc(8, 0x00) != hipSuccess ||
+        c->v1.traj_duration.alloc(1, 0x00) != hipSuccess || c->v1.n_coarse.alloc(1) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess) {
         delete c;
         return fail(nullptr, ISDF_ERR_HIP, "device initialisation failed");
     }
@@ -155,18 +154,9 @@ extern "C" int isdf_create(isdf_ctx **out, const isdf_config *cfg) {
 }
 
 static void free_mesh(isdf_ctx *c) {
-    if (c->d_mesh) (void)hipFree(c->d_mesh);
-    if (c->d_mesh_tri) (void)hipFree(c->d_mesh_tri);
-    if (c->d_mesh_trif) (void)hipFree(c->d_mesh_trif);
-    if (c->d_fwn_child) (void)hipFree(c->d_fwn_child);
-    if (c->d_fwn_box) (void)hipFree(c->d_fwn_box);
-    if (c->d_fwn_boxq) (void)hipFree(c->d_fwn_boxq);
-    if (c->d_fwn_triq) (void)hipFree(c->d_fwn_triq);
-    if (c->d_mesh_dl) (void)hipFree(c->d_mesh_dl);
-    c->d_mesh_dl = nullptr;
-    if (c->d_mesh_flat) (void)hipFree(c->d_mesh_flat);
-    c->d_mesh_flat = nullptr;
-    c->d_mesh = nullptr; c->d_mesh_tri = nullptr; c->d_mesh_trif = nullptr; c->d_fwn_child = nullptr; c->d_fwn_box = nullptr; c->d_fwn_boxq = nullptr; c->d_fwn_triq = nullptr;
+    for (DevBuf<float> *b : {&c->d_mesh_trif, &c->d_fwn_box, &c->d_fwn_boxq, &c->d_mesh_dl}) b->release();
+    for (DevBuf<double> *b : {&c->d_mesh_tri, &c->d_fwn_triq}) b->release();
+    c->d_mesh.release(); c->d_fwn_child.release(); c->d_mesh_flat.release();
 }
 
 static void multi_release(isdf_ctx *c);
@@ -178,22 +168,10 @@ extern "C" int isdf_destroy(isdf_ctx *c) {
     multi_release(c);
     (void)hipDeviceSynchronize();
     for (auto &p : c->prof_events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); (void)hipEventDestroy(p.c); (void)hipEventDestroy(p.d); }
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    if (c->h_eval_pin) (void)hipHostFree(c->h_eval_pin);
-    if (c->h_dir) (void)hipHostFree(c->h_dir);
-    if (c->h_cbres) (void)hipHostFree(c->h_cbres);
-    if (c->h_v1_pin) (void)hipHostFree(c->h_v1_pin);
     isdf_frontend_release(c);
     isdf_xchg_release(c);
-    isdf_swept_release_all(c);
-    isdf_traj_check_release_all(c);
-    void *ptrs[] = {c->d_cb, c->d_cbdev, c->d_esdf_stage, c->d_esdf_bricks, c->d_esdf, c->d_occ, c->d_points, c->d_tstar, c->d_acc, c->d_sample_info, c->d_bits, c->d_piece_cost, c->d_in, c->d_out, c->d_stats,
-                    c->d_traj_duration, c->d_coarse_t, c->d_coarse_pose, c->d_n_coarse, c->d_point_partial, c->d_point_piece, c->d_point_stat, c->d_point_nr, c->d_task_buf,
-                    c->d_task_map, c->d_v1_words, c->d_point_lmask, c->d_scan_ticks, c->d_scan_order, c->d_hist, c->d_shape_grid, c->d_pose, c->d_mq_entries, c->d_mq_items, c->d_mq_res, c->d_mq_sample_items, c->d_mq_sample_n, c->d_mq_count, c->d_msum_blocks, c->d_dbg, c->d_stage, c->d_stage_flags, c->d_sample_map, c->d_plan_cls, c->d_plan_map, c->d_plan_lr, c->d_plan_hist};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    free_mesh(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;               // every buffer frees itself (dev_buf.hpp), with this ctx's device current
     return ISDF_OK;
 }
 
@@ -211,8 +189,8 @@ extern "C" int isdf_set_grid(isdf_ctx *c, const void *vox, int dtype, int nx, in
     const size_t n = (size_t)nx * ny * nz;
     if (c->have_geom && (c->grid.X != nx || c->grid.Y != ny || c->grid.Z != nz)) {
         // new geometry: drop the other grid kind, it no longer matches
-        if (c->d_esdf) { (void)hipFree(c->d_esdf); c->d_esdf = nullptr; }
-        if (c->d_occ) { (void)hipFree(c->d_occ); c->d_occ = nullptr; }
+        c->d_esdf.release();
+        c->d_occ.release();
     }
     c->grid.X = nx; c->grid.Y = ny; c->grid.Z = nz; c->grid.res = res;
     for (int a = 0; a < 3; a++) {
@@ -231,16 +209,14 @@ extern "C" int isdf_set_grid(isdf_ctx *c, const void *vox, int dtype, int nx, in
             else for (size_t i = 0; i < n; i++) tmp[i] = (float)((const uint8_t *)vox)[i];
             src = tmp.data();
         }
-        if (c->d_esdf) { (void)hipFree(c->d_esdf); c->d_esdf = nullptr; }
-        HIPCHK(c, hipMalloc(&c->d_esdf, n * sizeof(float)));
+        { const int rc = c->d_esdf.renew(c, n); if (rc) return rc; }
         HIPCHK(c, hipMemcpy(c->d_esdf, src, n * sizeof(float), hipMemcpyHostToDevice));
     } else {
         std::vector<uint8_t> tmp(n);
         if (dtype == ISDF_U8) for (size_t i = 0; i < n; i++) tmp[i] = ((const uint8_t *)vox)[i] != 0;
         else if (dtype == ISDF_F32) for (size_t i = 0; i < n; i++) tmp[i] = ((const float *)vox)[i] != 0;
         else for (size_t i = 0; i < n; i++) tmp[i] = ((const double *)vox)[i] != 0;
-        if (c->d_occ) { (void)hipFree(c->d_occ); c->d_occ = nullptr; }
-        HIPCHK(c, hipMalloc(&c->d_occ, n));
+        { const int rc = c->d_occ.renew(c, n); if (rc) return rc; }
         HIPCHK(c, hipMemcpy(c->d_occ, tmp.data(), n, hipMemcpyHostToDevice));
     }
     c->grid.esdf = c->d_esdf;
@@ -333,13 +309,13 @@ extern "C" int isdf_set_shape(isdf_ctx *c, const isdf_shape *s) {
         isdf_host::fwn_build(s->mesh_vertices, s->n_vertices, s->mesh_faces, s->n_faces, tree);
         if (3 * isdf_host::fwn_depth(tree) + 1 > isdf::MESH_STACK) return fail(c, ISDF_ERR_UNSUPPORTED, "mesh hierarchy too deep for the device traversal stack");
         free_mesh(c);
-        HIPCHK(c, hipMalloc(&c->d_fwn_child, tree.child.size() * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(&c->d_fwn_box, tree.box.size() * sizeof(float)));
+        HIPCHK(c, c->d_fwn_child.alloc(tree.child.size()));
+        HIPCHK(c, c->d_fwn_box.alloc(tree.box.size()));
         HIPCHK(c, hipMemcpy(c->d_fwn_child, tree.child.data(), tree.child.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_fwn_box, tree.box.data(), tree.box.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc(&c->d_mesh_tri, tri.size() * sizeof(double)));
-        HIPCHK(c, hipMalloc(&c->d_mesh_trif, trif.size() * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->d_mesh, sizeof(DevMesh)));
+        HIPCHK(c, c->d_mesh_tri.alloc(tri.size()));
+        HIPCHK(c, c->d_mesh_trif.alloc(trif.size()));
+        HIPCHK(c, c->d_mesh.alloc(1));
         HIPCHK(c, hipMemcpy(c->d_mesh_tri, tri.data(), tri.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_mesh_trif, trif.data(), trif.size() * sizeof(float), hipMemcpyHostToDevice));
         // child-major copies for the quad-cooperative walks (csrc/dev_mesh.hpp): lane l of a quad reads child l's record, child
@@ -390,9 +366,9 @@ extern "C" int isdf_set_shape(isdf_ctx *c, const isdf_shape *s) {
                     for (int k = 0; k < 9; k++) triq[((size_t)4 * nd + ch) * isdf::MESH_Q_TRI + k] = tri[(size_t)9 * ci + k];
                 }
             }
-        HIPCHK(c, hipMalloc(&c->d_fwn_boxq, boxq.size() * sizeof(float)));
+        HIPCHK(c, c->d_fwn_boxq.alloc(boxq.size()));
         HIPCHK(c, hipMemcpy(c->d_fwn_boxq, boxq.data(), boxq.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc(&c->d_fwn_triq, triq.size() * sizeof(double)));
+        HIPCHK(c, c->d_fwn_triq.alloc(triq.size()));
         HIPCHK(c, hipMemcpy(c->d_fwn_triq, triq.data(), triq.size() * sizeof(double), hipMemcpyHostToDevice));
         DevMesh hm{c->d_mesh_tri, c->d_mesh_trif, s->n_faces, c->d_fwn_child, c->d_fwn_box, tree.n_nodes(), c->d_fwn_boxq, c->d_fwn_triq, depth, nullptr, {0, 0, 0}, {0.f, 0.f, 0.f}, 0.f, 0.f, 0.f, 0.f,
                    nullptr, 0, 0, 0, 0, 0, 0};
@@ -468,7 +444,7 @@ extern "C" int isdf_set_shape(isdf_ctx *c, const isdf_shape *s) {
         {
             const std::vector<int> flat = build_blob(0, isdf::MESH_FLAT_SLOTS);
             if (!flat.empty()) {
-                HIPCHK(c, hipMalloc(&c->d_mesh_flat, flat.size() * sizeof(int)));
+                HIPCHK(c, c->d_mesh_flat.alloc(flat.size()));
                 HIPCHK(c, hipMemcpy(c->d_mesh_flat, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
                 hm.flat_words = (int)flat.size(); hm.flat_rec = flat[22]; hm.flat_trec = flat[23];
                 hm.flat = c->d_mesh_flat; hm.flat_slots = flat[19]; hm.flat_nodes = nn_all; hm.flat_levels = flat[20];
@@ -574,8 +550,7 @@ extern "C" int isdf_set_shape_grid(isdf_ctx *c, const double *cells, int nx, int
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)nx * ny * nz;
     free_mesh(c);
-    if (c->d_shape_grid) { (void)hipFree(c->d_shape_grid); c->d_shape_grid = nullptr; }
-    HIPCHK(c, hipMalloc(&c->d_shape_grid, n * 4 * sizeof(double)));
+    { const int rc = c->d_shape_grid.renew(c, n * 4); if (rc) return rc; }
     HIPCHK(c, hipMemcpy(c->d_shape_grid, cells, n * 4 * sizeof(double), hipMemcpyHostToDevice));
     DevShape d{};
     d.kind = ISDF_SHAPE_GRID; d.grad_mode = ISDF_GRAD_GRID;
@@ -634,16 +609,15 @@ extern "C" int isdf_set_points(isdf_ctx *c, const double *xyz, int M) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (M < 0 || (M > 0 && !xyz)) return fail(c, ISDF_ERR_INVALID_ARG, "bad points");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->d_points) { (void)hipFree(c->d_points); c->d_points = nullptr; }
-    if (c->d_tstar) { (void)hipFree(c->d_tstar); c->d_tstar = nullptr; }
+    c->d_points.release();
+    c->d_tstar.release();
     c->M = M;
     c->points_epoch++;
-    if (c->d_v1_words) HIPCHK(c, hipMemset(c->d_v1_words, 0, 8 * sizeof(unsigned)));
+    if (c->v1.words) HIPCHK(c, hipMemset(c->v1.words, 0, 8 * sizeof(unsigned)));
     if (M > 0) {
-        HIPCHK(c, hipMalloc(&c->d_points, (size_t)3 * M * sizeof(double)));
+        HIPCHK(c, c->d_points.alloc((size_t)3 * M));
         HIPCHK(c, hipMemcpy(c->d_points, xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc(&c->d_tstar, (size_t)M * sizeof(double)));
-        HIPCHK(c, hipMemset(c->d_tstar, 0, (size_t)M * sizeof(double)));   // lastTstar starts at 0 (plan_manager.cpp:254)
+        HIPCHK(c, c->d_tstar.alloc((size_t)M, 0x00));   // lastTstar starts at 0 (plan_manager.cpp:254)
     }
     ISDF_REPLICATE(c, isdf_set_points(p_, xyz, M));
     return ISDF_OK;
@@ -666,18 +640,16 @@ static void shard_range(long long total, int rank, int world, long long &b, long
     e = b + q + (rank < r ? 1 : 0);
 }
 
-int isdf_ensure_doubles(isdf_ctx *c, double **p, size_t *cap, size_t need) {
-    if (*cap >= need) return ISDF_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIPCHK(c, hipMalloc(p, need * sizeof(double)));
-    *cap = need;
-    return ISDF_OK;
+int isdf_hip_fail(isdf_ctx *c, const char *what, hipError_t e) {
+    if (c) c->err = std::string(what) + ": " + hipGetErrorString(e);
+    return ISDF_ERR_HIP;
+}
+extern "C" void isdf_debug_live_bytes(long long out[2]) {
+    if (!out) return;
+    for (int k = 0; k < 2; k++) out[k] = isdf::g_live_bytes[k].load(std::memory_order_relaxed);
 }
 
-static int ensure(isdf_ctx *c, double **p, size_t *cap, size_t need) { return isdf_ensure_doubles(c, p, cap, need); }
-
-static void fill_flat(const isdf_config &cfg, FlatP &f) {
+void isdf_fill_flat(const isdf_config &cfg, FlatP &f) {
     f.mass = cfg.vehicle_mass; f.grav = cfg.grav_acc; f.dh = cfg.horiz_drag; f.dv = cfg.vert_drag;
     f.cp = cfg.paras_drag; f.veps = cfg.speed_eps; f.dh_over_m = f.dh / f.mass;
 }
@@ -702,25 +674,17 @@ static int prof_begin(isdf_ctx *c, hipStream_t st, ProfEvent **ev) {
 // round up front so that no round reallocates while another is in flight)
 int isdf_reserve_sweep_buffers(isdf_ctx *c, long long total_pieces) {
     const size_t n_samples = (size_t)total_pieces * (c->cfg.integral_intervs + 1);
-    if (c->sample_cap < n_samples) {
-        if (c->d_acc) (void)hipFree(c->d_acc);
-        if (c->d_sample_info) (void)hipFree(c->d_sample_info);
-        c->d_acc = nullptr; c->d_sample_info = nullptr; c->sample_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_acc, n_samples * ACC_STRIDE * sizeof(double)));
-        HIPCHK(c, hipMalloc(&c->d_sample_info, n_samples * 2 * sizeof(int)));
-        // result slots are created EMPTY (all-ones, tile_sweep.hip SLOT_EMPTY); every step leaves them empty again
-        HIPCHK(c, hipMemset(c->d_acc, 0xFF, n_samples * ACC_STRIDE * sizeof(double)));
+    // result slots are created EMPTY (all-ones, tile_sweep.hip SLOT_EMPTY); every step leaves them empty again
+    if (c->d_acc.capacity() < n_samples * ACC_STRIDE) {
+        int rc = c->d_acc.reserve(c, n_samples * ACC_STRIDE, 0xFF);
+        if (!rc) rc = c->d_sample_info.reserve(c, n_samples * 2);
+        if (rc) { c->d_acc.release(); return rc; }
         HIPCHK(c, hipDeviceSynchronize());
-        c->sample_cap = n_samples;
     }
-    if (c->piece_cap < (size_t)total_pieces) {
-        // piece-cost slots: created EMPTY like the collision sums' slots
-        if (c->d_piece_cost) (void)hipFree(c->d_piece_cost);
-        c->d_piece_cost = nullptr; c->piece_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_piece_cost, (size_t)total_pieces * sizeof(double)));
-        HIPCHK(c, hipMemset(c->d_piece_cost, 0xFF, (size_t)total_pieces * sizeof(double)));
+    if (c->d_piece_cost.capacity() < (size_t)total_pieces) {         // piece-cost slots: created EMPTY like the collision sums' slots
+        const int rc = c->d_piece_cost.reserve(c, (size_t)total_pieces, 0xFF);
+        if (rc) return rc;
         HIPCHK(c, hipDeviceSynchronize());
-        c->piece_cap = (size_t)total_pieces;
     }
     return ISDF_OK;
 }
@@ -731,8 +695,8 @@ int isdf_reserve_sweep_buffers(isdf_ctx *c, long long total_pieces) {
 int isdf_reset_result_slots(isdf_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->d_acc) HIPCHK(c, hipMemset(c->d_acc, 0xFF, c->sample_cap * ACC_STRIDE * sizeof(double)));
-    if (c->d_piece_cost) HIPCHK(c, hipMemset(c->d_piece_cost, 0xFF, c->piece_cap * sizeof(double)));
+    if (c->d_acc) HIPCHK(c, hipMemset(c->d_acc, 0xFF, c->d_acc.capacity() * sizeof(double)));
+    if (c->d_piece_cost) HIPCHK(c, hipMemset(c->d_piece_cost, 0xFF, c->d_piece_cost.capacity() * sizeof(double)));
     isdf_xchg_reset_board(c);
     HIPCHK(c, hipDeviceSynchronize());
     for (isdf_ctx *p : c->peers) {                  // a multi-device ctx: the peers' sticky overflow words and slots as well
@@ -750,17 +714,234 @@ int isdf_reset_result_slots(isdf_ctx *c) {
 struct HostDirect { const double *T, *coeffs; double *out; unsigned long long *flags; unsigned long long seq; bool via_bar; };
 static int ensure_stage(isdf_ctx *c, size_t total_pieces) {
     const size_t n_groups = (total_pieces + STAGE_G - 1) / STAGE_G;
-    { int rc1 = isdf_ensure_doubles(c, &c->d_stage, &c->stage_cap, total_pieces * 19); if (rc1) return rc1; }
-    if (c->stage_flags_cap < n_groups) {
-        if (c->d_stage_flags) (void)hipFree(c->d_stage_flags);
-        c->d_stage_flags = nullptr; c->stage_flags_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_stage_flags, n_groups * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemset(c->d_stage_flags, 0, n_groups * sizeof(unsigned long long)));
-        c->stage_flags_cap = n_groups;
-    }
-    return ISDF_OK;
+    const int rc = c->d_stage.reserve(c, total_pieces * 19);
+    return rc ? rc : c->d_stage_flags.reserve(c, n_groups, 0x00);
 }
 constexpr int ISDF_DIRECT_NA = 1;        // eval_device_impl: the step cannot run host-direct (nothing was launched)
+
+// ISDF_DEBUG_TIMING=1 (developer tool): `need` zeroed words for this step's launches; *out stays null when the switch is off
+static int debug_timing_buffer(isdf_ctx *c, size_t need, hipStream_t st, unsigned long long **out) {
+    const char *e = getenv("ISDF_DEBUG_TIMING");
+    if (!e || e[0] != '1') return ISDF_OK;
+    { const int rc = c->d_dbg.reserve(c, need); if (rc) return rc; }
+    HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, need * sizeof(unsigned long long), st));
+    c->dbg_used = need;
+    *out = c->d_dbg;
+    return ISDF_OK;
+}
+
+int SweptScratch::reserve(isdf_ctx *c, size_t n_points, bool with_step_arrays, bool *regrown) {
+    if (regrown) *regrown = false;
+    if (!traj_duration) HIPCHK(c, traj_duration.alloc(1, 0x00));
+    if (!n_coarse) HIPCHK(c, n_coarse.alloc(1));
+    if (!coarse_t) {
+        HIPCHK(c, coarse_t.alloc((size_t)SWEPT_MAX_COARSE));
+        HIPCHK(c, coarse_pose.alloc((size_t)SWEPT_MAX_COARSE * 12));
+    }
+    if (points >= n_points) return ISDF_OK;
+    points = 0;                                    // the whole group grows together
+    if (with_step_arrays) {
+        HIPCHK(c, point_partial.alloc(n_points * PARTIAL_STRIDE));
+        HIPCHK(c, point_piece.alloc(n_points));
+        HIPCHK(c, point_stat.alloc(n_points));
+        HIPCHK(c, scan_ticks.alloc(n_points, 0x00));
+        HIPCHK(c, scan_order.alloc(n_points));
+    }
+    HIPCHK(c, point_nr.alloc(n_points, 0x00));       // "scan passes last step": none yet
+    HIPCHK(c, task_buf.alloc(n_points * SWEPT_MAX_RANGES * SWEPT_TASK_STRIDE));
+    HIPCHK(c, task_map.alloc(n_points * SWEPT_MAX_RANGES));
+    HIPCHK(c, point_lmask.alloc(n_points, 0x00));
+    if (!words) HIPCHK(c, words.alloc(SWEPT_WORDS));
+    HIPCHK(c, hipMemset(words, 0, SWEPT_WORDS * sizeof(unsigned)));
+    points = n_points;
+    if (regrown) *regrown = true;
+    return ISDF_OK;
+}
+void SweptScratch::bind(SweptParams &P) const {
+    P.traj_duration = traj_duration;
+    P.coarse_t = coarse_t; P.coarse_pose = coarse_pose; P.n_coarse = n_coarse; P.max_coarse = SWEPT_MAX_COARSE;
+    P.point_partial = point_partial; P.point_piece = point_piece; P.point_stat = point_stat;
+    P.point_nr = point_nr; P.task_buf = task_buf; P.task_map = task_map; P.words = words; P.point_lmask = point_lmask;
+}
+
+// the swept-volume step (V1): prepare, sweep, back-prop + sums - or, the minimisers given, the fixed kernel and the sums
+static int v1_step(isdf_ctx *c, const isdf_config &cfg, int n_traj, int N, const double *d_T, const double *d_coeffs, double *d_out,
+                   double *d_tstar, hipStream_t st, bool fixed_tstar) {
+    if (n_traj != 1) return fail(c, ISDF_ERR_UNSUPPORTED, "the swept-volume sweep takes one trajectory");
+    if (isdf_xchg_fuse_on(c)) return fail(c, ISDF_ERR_UNSUPPORTED, "the in-kernel exchange belongs to the integral sweep (V2/V3)");
+    if (c->M <= 0) {                 // no obstacle points: nothing to add
+        HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)n_traj * isdf_out_stride(N) * sizeof(double), st));
+        HIPCHK(c, hipMemsetAsync(c->d_stats, 0, 8 * sizeof(unsigned long long), st));
+        return ISDF_OK;
+    }
+    // (no clearing here: the prepare / fixed kernel zeroes the statistics words and the reduction writes every output)
+    long long b, e;
+    shard_range(c->M, c->rank, c->world, b, e);
+    SweptParams P{};
+    P.shape = c->shape;
+    isdf_fill_flat(cfg, P.flat);
+    P.N = N; P.M = c->M; P.point_begin = (int)b; P.point_end = (int)e;
+    P.safety_hor = cfg.safety_hor; P.weight_p = cfg.weight_p;
+    P.T = d_T; P.coeffs = d_coeffs; P.points = c->d_points;
+    P.tstar = (d_tstar && !fixed_tstar) ? d_tstar : c->d_tstar;
+    P.tstar_stage = fixed_tstar ? nullptr : c->v1_tstar_stage;
+    c->v1_tstar_stage = nullptr;
+    bool regrown;
+    { const int rc = c->v1.reserve(c, (size_t)c->M, true, &regrown); if (rc) return rc; }
+    if (regrown) c->scan_order_b = c->scan_order_e = -1;
+    c->v1.bind(P);
+    // The scan's dispatch order, longest first.  Mesh robots: sorted in this step's prepare kernel from last step's durations.  Analytic
+    // robots: written by step k's back-prop kernel for step k + 1 - valid only for the same shard of the same points.
+    const bool scan_lpt = !c->env_no_lpt && !fixed_tstar;
+    const bool sort_here = c->shape.kind == ISDF_SHAPE_MESH;
+    P.scan_ticks = scan_lpt ? c->v1.scan_ticks.get() : nullptr; P.scan_order_out = scan_lpt ? c->v1.scan_order.get() : nullptr; P.scan_sort_here = (scan_lpt && sort_here) ? 1 : 0;
+    const bool order_valid = sort_here || (c->scan_order_b == (long long)b && c->scan_order_e == (long long)e && c->scan_order_epoch == c->points_epoch);
+    P.scan_order = (scan_lpt && order_valid) ? c->v1.scan_order.get() : nullptr;
+    // (what scan_order will hold once this step's launches are QUEUED; until then it counts as unwritten - a failure in between must
+    // not leave the next step scanning through an order nobody wrote)
+    const long long order_b = sort_here ? -1 : b, order_e = sort_here ? -1 : e;
+    if (scan_lpt) { c->scan_order_b = c->scan_order_e = -1; }
+    P.direct_records = fixed_tstar ? 1 : 0;
+    { const int rc = c->d_hist.reserve(c, (size_t)N); if (rc) return rc; }
+    P.hist = c->d_hist;
+    P.stats = c->d_stats;
+    P.dbg = nullptr;
+    { const int rc = debug_timing_buffer(c, (size_t)c->M * 7 + (size_t)(N + 1) * 8, st, &P.dbg); if (rc) return rc; }
+    if (fixed_tstar) {               // the minimisers are given (isdf_eval_swept_at_tstar): no search
+        launch_swept_fixed(P, d_tstar, st);
+        launch_swept_reduce(P, d_out, st);
+        HIPCHK(c, hipGetLastError());
+        return ISDF_OK;
+    }
+    launch_swept_prepare(P, st);
+    ProfEvent *ev;
+    const int rc = prof_begin(c, st, &ev);
+    if (rc) return rc;
+    launch_swept_sweep(P, st, ev ? ev->a : nullptr, ev ? ev->b : nullptr);
+    const bool ev2 = ev && c->prof_secondary;
+    if (ev2) { HIPCHK(c, hipEventRecord(ev->c, st)); }
+    launch_swept_reduce(P, d_out, st);
+    if (ev2) { HIPCHK(c, hipEventRecord(ev->d, st)); }
+    HIPCHK(c, hipGetLastError());
+    if (scan_lpt) { c->scan_order_b = order_b; c->scan_order_e = order_e; c->scan_order_epoch = c->points_epoch; }
+    return ISDF_OK;
+}
+
+// the bit-packed occupancy (z, x and y words) of the tile sweep's row scans, rebuilt after a new grid
+static int rebuild_bit_grids(isdf_ctx *c, const isdf_config &cfg, SweepParams &P, hipStream_t st) {
+    const int zw = (c->grid.Z + 31) / 32, xw = (c->grid.X + 31) / 32, yw = (c->grid.Y + 31) / 32;
+    const size_t nwz = (size_t)c->grid.X * c->grid.Y * zw, nwx = (size_t)c->grid.Y * c->grid.Z * xw, nwy = (size_t)c->grid.X * c->grid.Z * yw;
+    { const int rc = c->d_bits.reserve(c, nwz + nwx + nwy); if (rc) return rc; }
+    c->grid.ZW = zw; c->grid.XW = xw; c->grid.YW = yw;
+    c->grid.bits = c->d_bits; c->grid.bits_x = c->d_bits + nwz; c->grid.bits_y = c->d_bits + nwz + nwx;
+    launch_build_bits(c->grid, cfg.variant == ISDF_V3_ESDF_TILE ? 1 : 0, cfg.occ_thresh, c->d_bits, st);
+    launch_build_bits_xy(c->grid, cfg.variant == ISDF_V3_ESDF_TILE ? 1 : 0, cfg.occ_thresh, c->d_bits + nwz, c->d_bits + nwz + nwx, st);
+    c->bits_dirty = false;
+    P.grid = c->grid;
+    return ISDF_OK;
+}
+
+// Dispatch order built on the device from the work of earlier steps (tile_sweep.hip, plan_wave): a resident (fused) launch
+// gives the heaviest samples to the workgroups that are first on their CU; every other launch groups samples of like weight
+// into workgroups and dispatches the heaviest first.  Pieces [pb, pe) of total_pieces are this shard's.
+static int plan_order(isdf_ctx *c, const isdf_config &cfg, SweepParams &P, bool fused, long long pb, long long pe, long long total_pieces, hipStream_t st) {
+    const int N = P.N;
+    P.plan_cls_in = nullptr; P.plan_cls_out = nullptr; P.plan_map_out = nullptr; P.plan_zone = 0; P.plan_group = 1;
+    P.plan_lr_in = P.plan_hist_in = nullptr; P.plan_lr_out = P.plan_hist_out = nullptr;
+    const int K1 = cfg.integral_intervs + 1;
+    const long long n_loc = pe - pb, ns_local = n_loc * K1;
+    const int nb = (int)((ns_local + 3) / 4);
+    P.n_sweep_blocks = nb;                  // (launch_sweep sets it again for its own copy; the tail launch needs it for the order it writes)
+    if (c->n_cus == 0) { hipDeviceProp_t pr; c->n_cus = (hipGetDeviceProperties(&pr, c->device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
+    const bool no_plan = c->env_no_lpt;
+    // (not for the mesh kind: the cost of a mesh sample is its hierarchy walks, which the pair count does not predict -
+    // measured 230 -> 256 us per step with the order on, 20-face mesh)
+    bool plan = cfg.enable_pos && !no_plan && !P.sample_map && K1 <= 128 && nb > c->n_cus && ns_local < (1LL << 28) && c->shape.kind != ISDF_SHAPE_MESH;
+    long long group = n_loc;
+    int zone = 0;
+    if (plan) {
+        if (fused) {
+            // resident launch: zones; the exchange inside a fused multi-GPU launch keeps the plain order
+            plan = P.xf.world <= 1 && pb == 0 && pe == total_pieces && ns_local <= PLAN_GROUP_MAX_SAMPLES;
+            zone = c->n_cus;
+        } else if (nb <= sweep_resident_blocks(P, c->n_cus) && ns_local <= PLAN_GROUP_MAX_SAMPLES) {
+            zone = c->n_cus;          // a two-launch step whose sweep is resident anyway (a 50-piece shard): zones as well
+        } else if (ns_local > PLAN_GROUP_MAX_SAMPLES) {
+            // a batch: every trajectory is sorted by itself (the shard must hold whole trajectories)
+            group = N;
+            plan = (long long)N * K1 <= PLAN_GROUP_MAX_SAMPLES && pb % N == 0 && pe % N == 0;
+        }
+    }
+    if (!plan) { c->plan_k = 0; return ISDF_OK; }
+    const size_t ns_cap = (size_t)4 * nb, np_cap = (size_t)n_loc;
+    if (c->plan_ns_cap < ns_cap || c->plan_np_cap < np_cap) {       // two generations of each, with floors
+        HIPCHK(c, hipStreamSynchronize(st));
+        c->plan_ns_cap = c->plan_np_cap = 0; c->plan_k = 0; c->plan_cur = 0;
+        const size_t nsc = std::max(ns_cap, (size_t)4096), npc = std::max(np_cap, (size_t)256);
+        HIPCHK(c, c->d_plan_cls.alloc(2 * nsc));
+        HIPCHK(c, c->d_plan_map.alloc(2 * nsc));
+        HIPCHK(c, c->d_plan_lr.alloc(2 * nsc));
+        HIPCHK(c, c->d_plan_hist.alloc(2 * npc * PLAN_CLASSES));
+        c->plan_ns_cap = nsc; c->plan_np_cap = npc;
+    }
+    // the records of earlier steps are laid out by piece: they only carry over to a launch of the same geometry
+    const long long geo = ((long long)n_loc << 32) | ((long long)K1 << 20) | ((long long)(fused ? 1 : 0) << 19) | (long long)(group & 0x7FFFF);
+    if (c->plan_ns != ns_local || c->plan_nb != nb || c->plan_geo != geo) { c->plan_k = 0; c->plan_ns = ns_local; c->plan_nb = nb; c->plan_geo = geo; }
+    // The order is rebuilt once per cycle of PLAN_CYCLE steps (the trajectory moves little between optimizer steps, and
+    // building costs the step 0.4 us): step 0 of a cycle - the sweep leaves the classes; step 1 - the tail workgroups
+    // turn them into records; step 2 - into the order, written into the buffer NOT in use; from step 3 on the launches
+    // run in it.  Single copies of classes / records suffice: each is written in one step and read in the next.
+    constexpr int PLAN_CYCLE = 8;
+    const int k = c->plan_k, ph = k % PLAN_CYCLE;
+    const size_t nsc = c->plan_ns_cap;
+    P.plan_zone = zone;
+    P.plan_group = (int)group;
+    if (ph == 0) P.plan_cls_out = c->d_plan_cls;
+    if (ph == 1) { P.plan_cls_in = c->d_plan_cls; P.plan_lr_out = c->d_plan_lr; P.plan_hist_out = c->d_plan_hist; }
+    if (ph == 2) { P.plan_lr_in = c->d_plan_lr; P.plan_hist_in = c->d_plan_hist; P.plan_map_out = c->d_plan_map + (size_t)(1 - c->plan_cur) * nsc; }
+    if (ph == 3) c->plan_cur = 1 - c->plan_cur;          // the order written by the previous step is complete
+    if (k >= 3) P.sample_map = c->d_plan_map + (size_t)c->plan_cur * nsc;
+    if (c->plan_k < (1 << 30)) c->plan_k++;
+    return ISDF_OK;
+}
+
+// Mesh robots: the exact pass runs as its own launch over a queue of 64-voxel blocks (every block an independent work item:
+// the launch is balanced over the whole device instead of ending on its heaviest workgroup).  Sized for the worst case the
+// geometry allows - every voxel of the robot's inflated bounding box (or of the tile, if smaller) occupied; beyond the budget
+// below the exact pass stays inside the sweep kernel (ISDF_MESH_QUEUE=0 forces that).
+static int mesh_queue(isdf_ctx *c, const isdf_config &cfg, SweepParams &P, size_t ns_loc) {
+    const double k3 = (double)cfg.kernel_size * cfg.kernel_size * cfg.kernel_size;
+    double vox = k3;
+    if (c->shape.prune_rows) {
+        double v = 1.0;
+        for (int a = 0; a < 3; a++) v *= ((double)c->shape.bbox_hi[a] - (double)c->shape.bbox_lo[a] + 2.2 * cfg.safety_hor) / P.grid.res + 3.0;
+        vox = std::min(k3, v * 1.8);                  // (rows are pruned by the box's extent on the WORLD axes: up to sqrt(3) per axis for a rotated box)
+    }
+    const int kmax = (int)(k3 / 16.0) + 2;            // items are 16 voxels (tile_sweep.hip MQ_BLOCK)
+    const size_t per_sample = (size_t)(vox / 16.0) + 2;
+    const size_t cap = ns_loc * per_sample;
+    const size_t bytes = cap * (16 * 4 + 8 + 80) + ns_loc * ((size_t)kmax * 4 + 4);
+    // budget: 1 GiB per ctx (ISDF_MESH_QUEUE_MAX_MB overrides).  A launch whose worst case needs more keeps the exact pass inside
+    // the sweep kernel (whose 64-voxel blocks partition a sample's sums differently: equal to rounding, not bitwise)
+    static const size_t mq_budget = [] { const char *e = getenv("ISDF_MESH_QUEUE_MAX_MB"); const long v = e ? atol(e) : 0; return (size_t)(v > 0 ? v : 1024) << 20; }();
+    if (ns_loc == 0 || bytes > mq_budget || cap >= 0x7fffffffull) return ISDF_OK;
+    if (c->mq_cap < cap || c->mq_samples_cap < ns_loc || c->mq_kmax != kmax) {
+        HIPCHK(c, hipDeviceSynchronize());               // (an earlier step may still be reading the old queue)
+        c->mq_cap = 0; c->mq_samples_cap = 0;
+        c->d_mq_entries.release(); c->d_mq_items.release(); c->d_mq_res.release(); c->d_mq_sample_items.release(); c->d_mq_sample_n.release();
+        HIPCHK(c, c->d_mq_entries.alloc(cap * 16));
+        HIPCHK(c, c->d_mq_items.alloc(cap));
+        HIPCHK(c, c->d_mq_res.alloc(cap * 10));
+        HIPCHK(c, c->d_mq_sample_items.alloc(ns_loc * (size_t)kmax));
+        HIPCHK(c, c->d_mq_sample_n.alloc(ns_loc));
+        if (!c->d_mq_count) HIPCHK(c, c->d_mq_count.alloc(4));
+        c->mq_cap = cap; c->mq_samples_cap = ns_loc; c->mq_kmax = kmax;
+    }
+    P.mq_entries = c->d_mq_entries; P.mq_items = c->d_mq_items; P.mq_res = c->d_mq_res;
+    P.mq_sample_items = c->d_mq_sample_items; P.mq_sample_n = c->d_mq_sample_n; P.mq_count = c->d_mq_count;
+    P.mq_cap = (unsigned)c->mq_cap; P.mq_kmax = kmax;
+    return ISDF_OK;
+}
 
 static int eval_device_impl(isdf_ctx *c, int n_traj, int N, const double *d_T, const double *d_coeffs, double *d_out,
                             double *d_tstar, hipStream_t st, int mode = 0, bool fixed_tstar = false, const HostDirect *hd = nullptr) {
@@ -772,116 +953,8 @@ static int eval_device_impl(isdf_ctx *c, int n_traj, int N, const double *d_T, c
     if (!d_T || !d_coeffs || !d_out) return fail(c, ISDF_ERR_INVALID_ARG, "null device buffer");
     if (!c->have_shape && (cfg.variant == ISDF_V1_SWEPT || cfg.enable_pos)) return fail(c, ISDF_ERR_STATE, "shape not set");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t ostride = isdf_out_stride(N);
 
-    if (cfg.variant == ISDF_V1_SWEPT) {
-        if (hd) return ISDF_DIRECT_NA;
-        if (n_traj != 1) return fail(c, ISDF_ERR_UNSUPPORTED, "the swept-volume sweep takes one trajectory");
-        if (isdf_xchg_fuse_on(c)) return fail(c, ISDF_ERR_UNSUPPORTED, "the in-kernel exchange belongs to the integral sweep (V2/V3)");
-        if (c->M <= 0) {                 // no obstacle points: nothing to add
-            HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)n_traj * ostride * sizeof(double), st));
-            HIPCHK(c, hipMemsetAsync(c->d_stats, 0, 8 * sizeof(unsigned long long), st));
-            return ISDF_OK;
-        }
-        // (no clearing here: the prepare / fixed kernel zeroes the statistics words and the reduction writes every output)
-        long long b, e;
-        shard_range(c->M, c->rank, c->world, b, e);
-        SweptParams P{};
-        P.shape = c->shape;
-        fill_flat(cfg, P.flat);
-        P.N = N; P.M = c->M; P.point_begin = (int)b; P.point_end = (int)e;
-        P.safety_hor = cfg.safety_hor; P.weight_p = cfg.weight_p;
-        P.T = d_T; P.coeffs = d_coeffs; P.points = c->d_points;
-        P.tstar = (d_tstar && !fixed_tstar) ? d_tstar : c->d_tstar;
-        P.tstar_stage = fixed_tstar ? nullptr : c->v1_tstar_stage;
-        c->v1_tstar_stage = nullptr;
-        P.traj_duration = c->d_traj_duration;
-        P.max_coarse = 1536;   // traj_duration < 300 s, coarse step 0.2 s -> at most 1501 samples
-        if (!c->d_coarse_t) {
-            HIPCHK(c, hipMalloc(&c->d_coarse_t, (size_t)P.max_coarse * sizeof(double)));
-            HIPCHK(c, hipMalloc(&c->d_coarse_pose, (size_t)P.max_coarse * 12 * sizeof(double)));
-        }
-        if (c->point_cap < c->M) {
-            if (c->d_point_partial) (void)hipFree(c->d_point_partial);
-            if (c->d_point_piece) (void)hipFree(c->d_point_piece);
-            if (c->d_point_stat) (void)hipFree(c->d_point_stat);
-            if (c->d_point_nr) (void)hipFree(c->d_point_nr);
-            if (c->d_task_buf) (void)hipFree(c->d_task_buf);
-            if (c->d_task_map) (void)hipFree(c->d_task_map);
-            if (c->d_point_lmask) (void)hipFree(c->d_point_lmask);
-            c->d_point_lmask = nullptr;
-            if (c->d_scan_ticks) (void)hipFree(c->d_scan_ticks);
-            if (c->d_scan_order) (void)hipFree(c->d_scan_order);
-            c->d_scan_ticks = nullptr; c->d_scan_order = nullptr;
-            c->d_point_partial = nullptr; c->d_point_piece = nullptr; c->d_point_stat = nullptr; c->point_cap = 0;
-            c->d_point_nr = nullptr; c->d_task_buf = nullptr; c->d_task_map = nullptr;
-            HIPCHK(c, hipMalloc(&c->d_point_partial, (size_t)c->M * PARTIAL_STRIDE * sizeof(double)));
-            HIPCHK(c, hipMalloc(&c->d_point_piece, (size_t)c->M * sizeof(int)));
-            HIPCHK(c, hipMalloc(&c->d_point_stat, (size_t)c->M * sizeof(unsigned long long)));
-            HIPCHK(c, hipMalloc(&c->d_point_nr, (size_t)c->M * sizeof(int)));
-            HIPCHK(c, hipMemset(c->d_point_nr, 0, (size_t)c->M * sizeof(int)));          // "scan passes last step": none yet
-            HIPCHK(c, hipMalloc(&c->d_task_buf, (size_t)c->M * 32 * 6 * sizeof(double)));       // SW_MAX_RANGES x TASK_STRIDE per point
-            HIPCHK(c, hipMalloc(&c->d_task_map, (size_t)c->M * 32 * sizeof(unsigned)));
-            HIPCHK(c, hipMalloc(&c->d_point_lmask, (size_t)c->M * sizeof(unsigned)));
-            HIPCHK(c, hipMemset(c->d_point_lmask, 0, (size_t)c->M * sizeof(unsigned)));
-            HIPCHK(c, hipMalloc(&c->d_scan_ticks, (size_t)c->M * sizeof(unsigned)));
-            HIPCHK(c, hipMemset(c->d_scan_ticks, 0, (size_t)c->M * sizeof(unsigned)));
-            HIPCHK(c, hipMalloc(&c->d_scan_order, (size_t)c->M * sizeof(int)));
-            if (!c->d_v1_words) HIPCHK(c, hipMalloc(&c->d_v1_words, 32 * sizeof(unsigned)));
-            HIPCHK(c, hipMemset(c->d_v1_words, 0, 32 * sizeof(unsigned)));
-            c->scan_order_b = c->scan_order_e = -1;
-            c->point_cap = c->M;
-        }
-        P.coarse_t = c->d_coarse_t; P.coarse_pose = c->d_coarse_pose; P.n_coarse = c->d_n_coarse;
-        P.point_partial = c->d_point_partial; P.point_piece = c->d_point_piece; P.point_stat = c->d_point_stat;
-        P.point_nr = c->d_point_nr; P.task_buf = c->d_task_buf; P.task_map = c->d_task_map; P.words = c->d_v1_words; P.point_lmask = c->d_point_lmask;
-        // The scan's dispatch order, longest first.  Mesh robots: sorted in this step's prepare kernel from last step's durations.  Analytic
-        // robots: written by step k's back-prop kernel for step k + 1 - valid only for the same shard of the same points.
-        const bool scan_lpt = !c->env_no_lpt && !fixed_tstar;
-        const bool sort_here = c->shape.kind == ISDF_SHAPE_MESH;
-        P.scan_ticks = scan_lpt ? c->d_scan_ticks : nullptr; P.scan_order_out = scan_lpt ? c->d_scan_order : nullptr; P.scan_sort_here = (scan_lpt && sort_here) ? 1 : 0;
-        const bool order_valid = sort_here || (c->scan_order_b == (long long)b && c->scan_order_e == (long long)e && c->scan_order_epoch == c->points_epoch);
-        P.scan_order = (scan_lpt && order_valid) ? c->d_scan_order : nullptr;
-        // (what d_scan_order will hold once this step's launches are QUEUED; until then it counts as unwritten - a failure in between must
-        // not leave the next step scanning through an order nobody wrote)
-        const long long order_b = sort_here ? -1 : b, order_e = sort_here ? -1 : e;
-        if (scan_lpt) { c->scan_order_b = c->scan_order_e = -1; }
-        P.direct_records = fixed_tstar ? 1 : 0;
-        { int rc2 = ensure(c, &c->d_hist, &c->hist_cap, (size_t)N); if (rc2) return rc2; }
-        P.hist = c->d_hist;
-        P.stats = c->d_stats;
-        P.dbg = nullptr;
-        if (const char *e = getenv("ISDF_DEBUG_TIMING")) if (e[0] == '1') {
-            const size_t need = (size_t)c->M * 7 + (size_t)(N + 1) * 8;
-            if (c->dbg_cap < need) {
-                if (c->d_dbg) (void)hipFree(c->d_dbg);
-                c->d_dbg = nullptr; c->dbg_cap = 0;
-                HIPCHK(c, hipMalloc(&c->d_dbg, need * sizeof(unsigned long long)));
-                c->dbg_cap = need;
-            }
-            HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, need * sizeof(unsigned long long), st));
-            c->dbg_used = need;
-            P.dbg = c->d_dbg;
-        }
-        if (fixed_tstar) {               // the minimisers are given (isdf_eval_swept_at_tstar): no search
-            launch_swept_fixed(P, d_tstar, st);
-            launch_swept_reduce(P, d_out, st);
-            HIPCHK(c, hipGetLastError());
-            return ISDF_OK;
-        }
-        launch_swept_prepare(P, st);
-        ProfEvent *ev;
-        int rc = prof_begin(c, st, &ev);
-        if (rc) return rc;
-        launch_swept_sweep(P, st, ev ? ev->a : nullptr, ev ? ev->b : nullptr);
-        const bool ev2 = ev && c->prof_secondary;
-        if (ev2) { HIPCHK(c, hipEventRecord(ev->c, st)); }
-        launch_swept_reduce(P, d_out, st);
-        if (ev2) { HIPCHK(c, hipEventRecord(ev->d, st)); }
-        HIPCHK(c, hipGetLastError());
-        if (scan_lpt) { c->scan_order_b = order_b; c->scan_order_e = order_e; c->scan_order_epoch = c->points_epoch; }
-        return ISDF_OK;
-    }
+    if (cfg.variant == ISDF_V1_SWEPT) return hd ? ISDF_DIRECT_NA : v1_step(c, cfg, n_traj, N, d_T, d_coeffs, d_out, d_tstar, st, fixed_tstar);
 
     // ---- V2 / V3 integral sweep
     // the tile sweep's mesh walks keep MESH_Q_LEVELS levels of frames in LDS: a deeper hierarchy (a strongly unbalanced mesh)
@@ -897,13 +970,14 @@ static int eval_device_impl(isdf_ctx *c, int n_traj, int N, const double *d_T, c
     long long pb, pe;
     shard_range(total_pieces, c->rank, c->world, pb, pe);
     const size_t n_samples = (size_t)total_pieces * (cfg.integral_intervs + 1);
+    const size_t ns_loc = (size_t)(pe - pb) * (cfg.integral_intervs + 1);
     { int rc0 = isdf_reserve_sweep_buffers(c, total_pieces); if (rc0) return rc0; }
     int rc = ISDF_OK;
     SweepParams P{};
     P.grid = c->grid;
     if (!c->have_geom) { P.grid.X = P.grid.Y = P.grid.Z = 1; P.grid.res = 1.0; }
     P.shape = c->shape;
-    fill_flat(cfg, P.flat);
+    isdf_fill_flat(cfg, P.flat);
     P.variant = cfg.variant; P.K = cfg.integral_intervs; P.enable_dyn = cfg.enable_dyn; P.enable_pos = cfg.enable_pos;
     P.enable_cull = cfg.enable_cull;
     P.n_traj = n_traj; P.N = N; P.piece_begin = (int)pb; P.piece_end = (int)pe;
@@ -919,38 +993,12 @@ static int eval_device_impl(isdf_ctx *c, int n_traj, int N, const double *d_T, c
     P.T = d_T; P.coeffs = d_coeffs; P.acc = c->d_acc; P.sample_info = c->d_sample_info; P.piece_cost = c->d_piece_cost;
     P.out = d_out; P.stats = c->d_stats;
     P.dbg = nullptr;
-    P.sample_map = (c->d_sample_map && c->sample_map_n == 4 * (((size_t)(pe - pb) * (cfg.integral_intervs + 1) + 3) / 4)) ? c->d_sample_map : nullptr;
+    P.sample_map = (c->d_sample_map && c->sample_map_n == 4 * ((ns_loc + 3) / 4)) ? c->d_sample_map.get() : nullptr;
     P.dbg_flags = 0;
     if (const char *e = getenv("ISDF_DEBUG_FLAGS")) P.dbg_flags = atoi(e);
-    if (const char *e = getenv("ISDF_DEBUG_TIMING")) if (e[0] == '1') {
-        const size_t need = n_samples * 8 + (size_t)total_pieces * 4 + 4;
-        if (c->dbg_cap < need) {
-            if (c->d_dbg) (void)hipFree(c->d_dbg);
-            c->d_dbg = nullptr; c->dbg_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_dbg, need * sizeof(unsigned long long)));
-            c->dbg_cap = need;
-        }
-        HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, need * sizeof(unsigned long long), st));
-        c->dbg_used = need;
-        P.dbg = c->d_dbg;
-    }
-    if (cfg.enable_pos && c->bits_dirty) {
-        const int zw = (c->grid.Z + 31) / 32, xw = (c->grid.X + 31) / 32, yw = (c->grid.Y + 31) / 32;
-        const size_t nwz = (size_t)c->grid.X * c->grid.Y * zw, nwx = (size_t)c->grid.Y * c->grid.Z * xw, nwy = (size_t)c->grid.X * c->grid.Z * yw;
-        const size_t nw = nwz + nwx + nwy;
-        if (c->bits_cap < nw) {
-            if (c->d_bits) (void)hipFree(c->d_bits);
-            c->d_bits = nullptr; c->bits_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_bits, nw * sizeof(unsigned)));
-            c->bits_cap = nw;
-        }
-        c->grid.ZW = zw; c->grid.XW = xw; c->grid.YW = yw;
-        c->grid.bits = c->d_bits; c->grid.bits_x = c->d_bits + nwz; c->grid.bits_y = c->d_bits + nwz + nwx;
-        launch_build_bits(c->grid, cfg.variant == ISDF_V3_ESDF_TILE ? 1 : 0, cfg.occ_thresh, c->d_bits, st);
-        launch_build_bits_xy(c->grid, cfg.variant == ISDF_V3_ESDF_TILE ? 1 : 0, cfg.occ_thresh, c->d_bits + nwz, c->d_bits + nwz + nwx, st);
-        c->bits_dirty = false;
-        P.grid = c->grid;
-    }
+    rc = debug_timing_buffer(c, n_samples * 8 + (size_t)total_pieces * 4 + 4, st, &P.dbg);
+    if (rc) return rc;
+    if (cfg.enable_pos && c->bits_dirty) { rc = rebuild_bit_grids(c, cfg, P, st); if (rc) return rc; }
     c->last_P = P; c->have_last_P = true;
     ProfEvent *ev;
     rc = prof_begin(c, st, &ev);
@@ -974,121 +1022,21 @@ static int eval_device_impl(isdf_ctx *c, int n_traj, int N, const double *d_T, c
         if (!hd->via_bar) { P.host_T = hd->T; P.host_coeffs = hd->coeffs; P.stage = c->d_stage; P.stage_flags = c->d_stage_flags; }
         c->last_P = P;
     }
-    // dispatch order built on the device from the work of earlier steps (tile_sweep.hip, plan_wave): a resident (fused) launch
-    // gives the heaviest samples to the workgroups that are first on their CU; every other launch groups samples of like weight
-    // into workgroups and dispatches the heaviest first
-    P.plan_cls_in = nullptr; P.plan_cls_out = nullptr; P.plan_map_out = nullptr; P.plan_zone = 0; P.plan_group = 1;
-    P.plan_lr_in = P.plan_hist_in = nullptr; P.plan_lr_out = P.plan_hist_out = nullptr;
-    {
-        const int K1 = cfg.integral_intervs + 1;
-        const long long n_loc = pe - pb, ns_local = n_loc * K1;
-        const int nb = (int)((ns_local + 3) / 4);
-        P.n_sweep_blocks = nb;                  // (launch_sweep sets it again for its own copy; the tail launch needs it for the order it writes)
-        if (c->n_cus == 0) { hipDeviceProp_t pr; c->n_cus = (hipGetDeviceProperties(&pr, c->device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
-        const bool no_plan = c->env_no_lpt;
-        // (not for the mesh kind: the cost of a mesh sample is its hierarchy walks, which the pair count does not predict -
-        // measured 230 -> 256 us per step with the order on, 20-face mesh)
-        bool plan = cfg.enable_pos && !no_plan && !P.sample_map && K1 <= 128 && nb > c->n_cus && ns_local < (1LL << 28) && c->shape.kind != ISDF_SHAPE_MESH;
-        long long group = n_loc;
-        int zone = 0;
-        if (plan) {
-            if (fused) {
-                // resident launch: zones; the exchange inside a fused multi-GPU launch keeps the plain order
-                plan = P.xf.world <= 1 && pb == 0 && pe == total_pieces && ns_local <= PLAN_GROUP_MAX_SAMPLES;
-                zone = c->n_cus;
-            } else if (nb <= sweep_resident_blocks(P, c->n_cus) && ns_local <= PLAN_GROUP_MAX_SAMPLES) {
-                zone = c->n_cus;          // a two-launch step whose sweep is resident anyway (a 50-piece shard): zones as well
-            } else if (ns_local > PLAN_GROUP_MAX_SAMPLES) {
-                // a batch: every trajectory is sorted by itself (the shard must hold whole trajectories)
-                group = N;
-                plan = (long long)N * K1 <= PLAN_GROUP_MAX_SAMPLES && pb % N == 0 && pe % N == 0;
-            }
-        }
-        if (!plan) c->plan_k = 0;
-        else {
-            const size_t ns_cap = (size_t)4 * nb, np_cap = (size_t)n_loc;
-            if (c->plan_ns_cap < ns_cap || c->plan_np_cap < np_cap) {
-                HIPCHK(c, hipStreamSynchronize(st));
-                for (void *q : {(void *)c->d_plan_cls, (void *)c->d_plan_map, (void *)c->d_plan_lr, (void *)c->d_plan_hist}) if (q) (void)hipFree(q);
-                c->d_plan_cls = nullptr; c->d_plan_map = nullptr; c->d_plan_lr = nullptr; c->d_plan_hist = nullptr;
-                c->plan_ns_cap = c->plan_np_cap = 0; c->plan_k = 0; c->plan_cur = 0;
-                const size_t nsc = std::max(ns_cap, (size_t)4096), npc = std::max(np_cap, (size_t)256);
-                HIPCHK(c, hipMalloc(&c->d_plan_cls, 2 * nsc));
-                HIPCHK(c, hipMalloc(&c->d_plan_map, 2 * nsc * sizeof(int)));
-                HIPCHK(c, hipMalloc(&c->d_plan_lr, 2 * nsc * sizeof(unsigned short)));
-                HIPCHK(c, hipMalloc(&c->d_plan_hist, 2 * npc * PLAN_CLASSES * sizeof(unsigned short)));
-                c->plan_ns_cap = nsc; c->plan_np_cap = npc;
-            }
-            // the records of earlier steps are laid out by piece: they only carry over to a launch of the same geometry
-            const long long geo = ((long long)n_loc << 32) | ((long long)K1 << 20) | ((long long)(fused ? 1 : 0) << 19) | (long long)(group & 0x7FFFF);
-            if (c->plan_ns != ns_local || c->plan_nb != nb || c->plan_geo != geo) { c->plan_k = 0; c->plan_ns = ns_local; c->plan_nb = nb; c->plan_geo = geo; }
-            // The order is rebuilt once per cycle of PLAN_CYCLE steps (the trajectory moves little between optimizer steps, and
-            // building costs the step 0.4 us): step 0 of a cycle - the sweep leaves the classes; step 1 - the tail workgroups
-            // turn them into records; step 2 - into the order, written into the buffer NOT in use; from step 3 on the launches
-            // run in it.  Single copies of classes / records suffice: each is written in one step and read in the next.
-            constexpr int PLAN_CYCLE = 8;
-            const int k = c->plan_k, ph = k % PLAN_CYCLE;
-            const size_t nsc = c->plan_ns_cap;
-            P.plan_zone = zone;
-            P.plan_group = (int)group;
-            if (ph == 0) P.plan_cls_out = c->d_plan_cls;
-            if (ph == 1) { P.plan_cls_in = c->d_plan_cls; P.plan_lr_out = c->d_plan_lr; P.plan_hist_out = c->d_plan_hist; }
-            if (ph == 2) { P.plan_lr_in = c->d_plan_lr; P.plan_hist_in = c->d_plan_hist; P.plan_map_out = c->d_plan_map + (size_t)(1 - c->plan_cur) * nsc; }
-            if (ph == 3) c->plan_cur = 1 - c->plan_cur;          // the order written by the previous step is complete
-            if (k >= 3) P.sample_map = c->d_plan_map + (size_t)c->plan_cur * nsc;
-            if (c->plan_k < (1 << 30)) c->plan_k++;
-        }
-    }
+    rc = plan_order(c, cfg, P, fused, pb, pe, total_pieces, st);
+    if (rc) return rc;
     if (!fused && cfg.enable_pos) {                 // the poses of a non-fused launch come from pose_kernel (tile_sweep.hip)
-        const size_t need = (size_t)(pe - pb) * (cfg.integral_intervs + 1) * sweep_pose_bytes();
-        if (c->pose_cap < need) {
+        const size_t need = ns_loc * sweep_pose_bytes();
+        if (c->d_pose.capacity() < need) {
             HIPCHK(c, hipStreamSynchronize(st));
-            if (c->d_pose) (void)hipFree(c->d_pose);
-            c->d_pose = nullptr; c->pose_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_pose, need));
-            c->pose_cap = need;
+            rc = c->d_pose.reserve(c, need);
+            if (rc) return rc;
         }
         P.poses = c->d_pose;
     }
-    // ---- mesh robots: the exact pass runs as its own launch over a queue of 64-voxel blocks (every block an independent work item:
-    // the launch is balanced over the whole device instead of ending on its heaviest workgroup).  Sized for the worst case the
-    // geometry allows - every voxel of the robot's inflated bounding box (or of the tile, if smaller) occupied; beyond the budget
-    // below the exact pass stays inside the sweep kernel (ISDF_MESH_QUEUE=0 forces that).
     P.mq_items = nullptr;
     if (c->shape.kind == ISDF_SHAPE_MESH && cfg.enable_pos && !fused && !(getenv("ISDF_MESH_QUEUE") && getenv("ISDF_MESH_QUEUE")[0] == '0')) {
-        const size_t ns_loc = (size_t)(pe - pb) * (cfg.integral_intervs + 1);
-        const double k3 = (double)cfg.kernel_size * cfg.kernel_size * cfg.kernel_size;
-        double vox = k3;
-        if (c->shape.prune_rows) {
-            double v = 1.0;
-            for (int a = 0; a < 3; a++) v *= ((double)c->shape.bbox_hi[a] - (double)c->shape.bbox_lo[a] + 2.2 * cfg.safety_hor) / P.grid.res + 3.0;
-            vox = std::min(k3, v * 1.8);                  // (rows are pruned by the box's extent on the WORLD axes: up to sqrt(3) per axis for a rotated box)
-        }
-        const int kmax = (int)(k3 / 16.0) + 2;            // items are 16 voxels (tile_sweep.hip MQ_BLOCK)
-        const size_t per_sample = (size_t)(vox / 16.0) + 2;
-        const size_t cap = ns_loc * per_sample;
-        const size_t bytes = cap * (16 * 4 + 8 + 80) + ns_loc * ((size_t)kmax * 4 + 4);
-        // budget: 1 GiB per ctx (ISDF_MESH_QUEUE_MAX_MB overrides).  A launch whose worst case needs more keeps the exact pass inside
-        // the sweep kernel (whose 64-voxel blocks partition a sample's sums differently: equal to rounding, not bitwise)
-        static const size_t mq_budget = [] { const char *e = getenv("ISDF_MESH_QUEUE_MAX_MB"); const long v = e ? atol(e) : 0; return (size_t)(v > 0 ? v : 1024) << 20; }();
-        if (ns_loc > 0 && bytes <= mq_budget && cap < 0x7fffffffull) {
-            if (c->mq_cap < cap || c->mq_samples_cap < ns_loc || c->mq_kmax != kmax) {
-                HIPCHK(c, hipDeviceSynchronize());               // (an earlier step may still be reading the old queue)
-                for (void *q : {(void *)c->d_mq_entries, c->d_mq_items, (void *)c->d_mq_res, (void *)c->d_mq_sample_items, (void *)c->d_mq_sample_n}) if (q) (void)hipFree(q);
-                c->d_mq_entries = nullptr; c->d_mq_items = nullptr; c->d_mq_res = nullptr; c->d_mq_sample_items = nullptr; c->d_mq_sample_n = nullptr;
-                c->mq_cap = 0; c->mq_samples_cap = 0;
-                HIPCHK(c, hipMalloc(&c->d_mq_entries, cap * 16 * sizeof(unsigned)));
-                HIPCHK(c, hipMalloc(&c->d_mq_items, cap * 8));
-                HIPCHK(c, hipMalloc(&c->d_mq_res, cap * 10 * sizeof(double)));
-                HIPCHK(c, hipMalloc(&c->d_mq_sample_items, ns_loc * (size_t)kmax * sizeof(int)));
-                HIPCHK(c, hipMalloc(&c->d_mq_sample_n, ns_loc * sizeof(int)));
-                if (!c->d_mq_count) HIPCHK(c, hipMalloc(&c->d_mq_count, 4 * sizeof(unsigned)));
-                c->mq_cap = cap; c->mq_samples_cap = ns_loc; c->mq_kmax = kmax;
-            }
-            P.mq_entries = c->d_mq_entries; P.mq_items = (int2 *)c->d_mq_items; P.mq_res = c->d_mq_res;
-            P.mq_sample_items = c->d_mq_sample_items; P.mq_sample_n = c->d_mq_sample_n; P.mq_count = c->d_mq_count;
-            P.mq_cap = (unsigned)c->mq_cap; P.mq_kmax = kmax;
-        }
+        rc = mesh_queue(c, cfg, P, ns_loc);
+        if (rc) return rc;
     }
     launch_sweep(P, st, ev ? ev->a : nullptr, ev ? ev->b : nullptr, fused);
     if (!fused) launch_tail(P, st, ev2 ? ev->c : nullptr, ev2 ? ev->d : nullptr);
@@ -1180,8 +1128,6 @@ static void multi_release(isdf_ctx *c) {
     if (c->rccl_comm && g_rccl.CommDestroy) { (void)g_rccl.CommDestroy(c->rccl_comm); c->rccl_comm = nullptr; }
     if (c->mev_in) { (void)hipEventDestroy(c->mev_in); c->mev_in = nullptr; }
     if (c->mev_done) { (void)hipEventDestroy(c->mev_done); c->mev_done = nullptr; }
-    if (c->d_mpart) { (void)hipFree(c->d_mpart); c->d_mpart = nullptr; }
-    if (c->d_mstage) { (void)hipFree(c->d_mstage); c->d_mstage = nullptr; }
 }
 
 extern "C" int isdf_create_multi(isdf_ctx **out, const isdf_config *cfg, const int *devices, int n_devices) {
@@ -1276,8 +1222,8 @@ static int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, 
     for (int r = 1; r < n; r++) {
         isdf_ctx *p = c->peers[r - 1];
         HIPCHK(c, hipSetDevice(p->device));
-        int rc = pull ? ISDF_OK : ensure(p, &p->d_in, &p->in_cap, in_T + in_C);
-        if (rc == ISDF_OK) rc = ensure(p, &p->d_mpart, &p->mpart_cap, count + MULTI_TAIL);
+        int rc = pull ? ISDF_OK : p->d_in.reserve(p, in_T + in_C);
+        if (rc == ISDF_OK) rc = p->d_mpart.reserve(p, count + MULTI_TAIL);
         if (rc) { c->err = p->err; return rc; }
         HIPCHK(c, hipStreamWaitEvent(p->stream, c->mev_in, 0));
         long long pb = 0, pe = 0;
@@ -1302,7 +1248,7 @@ static int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, 
         parts.p[r] = p->d_mpart;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure(c, &c->d_mpart, &c->mpart_cap, count + MULTI_TAIL);
+    int rc = c->d_mpart.reserve(c, count + MULTI_TAIL);
     if (rc) return rc;
     rc = eval_device_impl(c, n_traj, N, d_T, d_coeffs, c->d_mpart, d_tstar, st, mode, false);
     if (rc) return rc;
@@ -1328,7 +1274,7 @@ static int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, 
     } else {
         for (int r = 1; r < n; r++) HIPCHK(c, hipStreamWaitEvent(st, c->peers[r - 1]->mev_done, 0));
         if (c->multi_collective == ISDF_MULTI_STAGED) {
-            rc = ensure(c, &c->d_mstage, &c->mstage_cap, (size_t)(n - 1) * (count + MULTI_TAIL));
+            rc = c->d_mstage.reserve(c, (size_t)(n - 1) * (count + MULTI_TAIL));
             if (rc) return rc;
             for (int r = 1; r < n; r++) {
                 double *dst = c->d_mstage + (size_t)(r - 1) * (count + MULTI_TAIL);
@@ -1381,9 +1327,9 @@ extern "C" int isdf_eval_swept_at_tstar_host(isdf_ctx *c, int N, const double *T
     if (c->M <= 0) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t in_all = (size_t)19 * N, ostride = isdf_out_stride(N);
-    int rc = ensure(c, &c->d_in, &c->in_cap, in_all + (size_t)c->M);
+    int rc = c->d_in.reserve(c, in_all + (size_t)c->M);
     if (rc) return rc;
-    rc = ensure(c, &c->d_out, &c->out_cap, ostride);
+    rc = c->d_out.reserve(c, ostride);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_in, T, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_in + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1437,16 +1383,7 @@ static int fetch_stats(isdf_ctx *c) {
 }
 
 // pinned staging buffer of the host entry points (isdf_eval): [inputs | outputs | 8 statistics words]
-static int ensure_eval_pin(isdf_ctx *c, size_t doubles) {
-    if (c->eval_pin_cap >= doubles) return ISDF_OK;
-    if (c->h_eval_pin) (void)hipHostFree(c->h_eval_pin);
-    c->h_eval_pin = nullptr; c->eval_pin_cap = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_eval_pin, doubles * sizeof(double), hipHostMallocDefault));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_eval_pin_dev, c->h_eval_pin, 0));
-    std::memset(c->h_eval_pin, 0, doubles * sizeof(double));
-    c->eval_pin_cap = doubles;
-    return ISDF_OK;
-}
+static int ensure_eval_pin(isdf_ctx *c, size_t doubles) { return c->h_eval_pin.reserve(c, doubles); }
 
 // ---- host-direct steps -----------------------------------------------------------------------------------------------
 static bool direct_enabled(const isdf_ctx *c) {
@@ -1479,14 +1416,7 @@ static bool host_rows_wait(isdf_ctx *c, const double *p, size_t n, bool another_
 
 static int direct_reserve(isdf_ctx *c, int nb, int n) {
     const size_t in = (size_t)19 * n * nb, out = isdf_out_stride(n) * nb, need = in + out + (size_t)nb;
-    if (c->dir_cap < need) {
-        if (c->h_dir) (void)hipHostFree(c->h_dir);
-        c->h_dir = nullptr; c->dir_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_dir, need * sizeof(double), hipHostMallocDefault));      // pinned host memory is device-visible (unified addressing)
-        HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_dir_dev, c->h_dir, 0));
-        c->dir_cap = need;
-        std::memset(c->h_dir, 0, need * sizeof(double));
-    }
+    { const int rc = c->h_dir.reserve(c, need); if (rc) return rc; }      // pinned host memory is device-visible (unified addressing)
     c->dir_in = in; c->dir_out = out; c->dir_flags = (size_t)nb;
     return ISDF_OK;
 }
@@ -1509,11 +1439,10 @@ static bool bar_usable(isdf_ctx *c, double *d_buf, size_t n) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, d_buf) != hipSuccess) { (void)hipGetLastError(); return false; }
     const int m = (int)(n < 64 ? n : 64);
-    double *d_copy = nullptr;
-    unsigned long long *h_flag = nullptr, *h_flag_dev = nullptr;
-    bool ok = hipMalloc(&d_copy, 2 * 64 * sizeof(double)) == hipSuccess &&
-              hipHostMalloc((void **)&h_flag, 64, hipHostMallocDefault) == hipSuccess &&
-              hipHostGetDevicePointer((void **)&h_flag_dev, h_flag, 0) == hipSuccess;
+    DevBuf<double> d_copy;
+    PinBuf<unsigned long long> flag;
+    bool ok = d_copy.alloc(2 * 64) == hipSuccess && flag.reserve(nullptr, 8) == ISDF_OK;
+    unsigned long long *const h_flag = flag, *const h_flag_dev = flag.dev();
     std::vector<double> pat(2 * (size_t)m), back(2 * (size_t)m, 0.0);
     for (int i = 0; i < m; i++) { pat[i] = 1.0 + (double)i * 0.5; pat[m + i] = -3.0 - (double)i * 0.25; }
     for (int round = 0; ok && round < 2; round++) {
@@ -1531,8 +1460,6 @@ static bool bar_usable(isdf_ctx *c, double *d_buf, size_t n) {
                  std::memcmp(pat.data(), back.data(), 2 * (size_t)m * sizeof(double)) == 0;
     (void)hipStreamSynchronize(c->stream);
     (void)hipGetLastError();
-    if (d_copy) (void)hipFree(d_copy);
-    if (h_flag) (void)hipHostFree(h_flag);
     if (ok) c->bar_state = 1;
     return ok;
 }
@@ -1542,7 +1469,7 @@ static int direct_launch(isdf_ctx *c, int nb, int n, const double *const *T, con
     int rc = direct_reserve(c, nb, n);
     if (rc) return rc;
     const size_t in_all = (size_t)19 * n * nb;
-    rc = ensure(c, &c->d_in, &c->in_cap, in_all);
+    rc = c->d_in.reserve(c, in_all);
     if (rc) return rc;
     HostDirect hd;
     hd.via_bar = bar_usable(c, c->d_in, in_all);
@@ -1555,9 +1482,9 @@ static int direct_launch(isdf_ctx *c, int nb, int n, const double *const *T, con
     }
     host_rows_mark(c->h_dir + c->dir_in, c->dir_out);            // (the step STORES its sums there; it never reads them)
     __sync_synchronize();
-    hd.T = c->h_dir_dev; hd.coeffs = c->h_dir_dev + (size_t)n * nb;
-    hd.out = c->h_dir_dev + c->dir_in;
-    hd.flags = (unsigned long long *)(c->h_dir_dev + c->dir_in + c->dir_out);
+    hd.T = c->h_dir.dev(); hd.coeffs = c->h_dir.dev() + (size_t)n * nb;
+    hd.out = c->h_dir.dev() + c->dir_in;
+    hd.flags = (unsigned long long *)(c->h_dir.dev() + c->dir_in + c->dir_out);
     hd.seq = ++c->dir_seq;
     rc = eval_device_impl(c, nb, n, c->d_in, c->d_in + (size_t)n * nb, hd.out, nullptr, st, mode, false, &hd);
     if (rc == ISDF_OK) { c->dir_pending = true; c->dir_nb = nb; c->dir_n = n; c->last_host_path = hd.via_bar ? ISDF_HOST_PATH_DIRECT_BAR : ISDF_HOST_PATH_DIRECT_MAPPED; }
@@ -1614,21 +1541,15 @@ static int v1_direct_eval(isdf_ctx *c, int n, const double *T, const double *coe
     // d_in: [T | coeffs | lastTstar] - CPU-written, GPU-read only.  (lastTstar does NOT go straight into d_tstar: the GPU itself wrote
     // that array in the step before, and CPU stores through the BAR into memory the device has written are outside what bar_usable
     // probes; the prepare kernel copies the staged values over, SweptParams::tstar_stage)
-    int rc = ensure(c, &c->d_in, &c->in_cap, in_all + (size_t)(ts ? c->M : 0));
+    int rc = c->d_in.reserve(c, in_all + (size_t)(ts ? c->M : 0));
     if (rc) return rc;
-    rc = ensure(c, &c->d_out, &c->out_cap, ostride);
+    rc = c->d_out.reserve(c, ostride);
     if (rc) return rc;
     if (!bar_usable(c, c->d_in, in_all + (size_t)(ts ? c->M : 0))) return ISDF_DIRECT_NA;
     // pinned, device-mapped: [out | 8 statistics words | flag | lastTstar]
     const size_t need = ostride + 8 + 2 + (size_t)(ts ? c->M : 0);
-    if (c->v1_pin_cap < need) {
-        if (c->h_v1_pin) (void)hipHostFree(c->h_v1_pin);
-        c->h_v1_pin = nullptr; c->v1_pin_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_v1_pin, need * sizeof(double), hipHostMallocDefault));
-        HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_v1_pin_dev, c->h_v1_pin, 0));
-        std::memset(c->h_v1_pin, 0, need * sizeof(double));
-        c->v1_pin_cap = need;
-    }
+    rc = c->h_v1_pin.reserve(c, need);
+    if (rc) return rc;
     std::memcpy(c->d_in, T, (size_t)n * sizeof(double));                       // CPU stores into device memory
     std::memcpy(c->d_in + n, coeffs, (size_t)18 * n * sizeof(double));
     if (ts) { std::memcpy(c->d_in + in_all, tstar_inout, (size_t)c->M * sizeof(double)); c->v1_tstar_stage = c->d_in + in_all; }
@@ -1640,10 +1561,10 @@ static int v1_direct_eval(isdf_ctx *c, int n, const double *T, const double *coe
     host_rows_mark(c->h_v1_pin, ostride);
     if (ts) host_rows_mark(c->h_v1_pin + ostride + 10, (size_t)c->M);
     __sync_synchronize();
-    double *ho = c->h_v1_pin_dev;
-    unsigned long long *hs = (unsigned long long *)(c->h_v1_pin_dev + ostride);
+    double *ho = c->h_v1_pin.dev();
+    unsigned long long *hs = (unsigned long long *)(c->h_v1_pin.dev() + ostride);
     hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_out, ostride, c->d_stats, ts ? c->d_tstar : nullptr, c->M,
-                       ho, hs, c->h_v1_pin_dev + ostride + 10, hs + 8, seq);
+                       ho, hs, c->h_v1_pin.dev() + ostride + 10, hs + 8, seq);
     HIPCHK(c, hipGetLastError());
     volatile unsigned long long *flag = (volatile unsigned long long *)(c->h_v1_pin + ostride) + 8;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1759,9 +1680,9 @@ extern "C" int isdf_eval(isdf_ctx *c, int n_traj, const int *N, const double *co
             }
         }
         c->last_host_path = ISDF_HOST_PATH_COPY;
-        int rc = ensure(c, &c->d_in, &c->in_cap, in_all);
+        int rc = c->d_in.reserve(c, in_all);
         if (rc) return rc;
-        rc = ensure(c, &c->d_out, &c->out_cap, out_all);
+        rc = c->d_out.reserve(c, out_all);
         if (rc) return rc;
         rc = ensure_eval_pin(c, in_all + out_all + 16);
         if (rc) return rc;
@@ -1783,14 +1704,14 @@ extern "C" int isdf_eval(isdf_ctx *c, int n_traj, const int *N, const double *co
         // a multi-device step ends in a sum kernel on the lead: it writes straight into the pinned buffer and raises a word there
         const bool host_out = (!c->peers.empty() || c->rccl_comm) && !dts && !c->env_multi_no_hostout && !c->prof_on;
         if (host_out) {
-            if (!c->d_msum_blocks) { HIPCHK(c, hipMalloc(&c->d_msum_blocks, sizeof(unsigned))); HIPCHK(c, hipMemset(c->d_msum_blocks, 0, sizeof(unsigned))); }
-            c->mh_words = (unsigned long long *)(c->h_eval_pin_dev + in_all + out_all);
+            if (!c->d_msum_blocks) HIPCHK(c, c->d_msum_blocks.alloc(1, 0x00));
+            c->mh_words = (unsigned long long *)(c->h_eval_pin.dev() + in_all + out_all);
             c->mh_seq++;
             host_rows_mark(hout, out_all);                       // (see host_rows_wait: the word does not order the results for the CPU)
             host_rows_mark((double *)hstat, 8);
             __sync_synchronize();
         }
-        rc = sweep_dispatch(c, nb, n, dT, dC, host_out ? c->h_eval_pin_dev + in_all : c->d_out, dts, c->stream);
+        rc = sweep_dispatch(c, nb, n, dT, dC, host_out ? c->h_eval_pin.dev() + in_all : c->d_out, dts, c->stream);
         if (rc) { c->mh_words = nullptr; return rc; }
         if (host_out) {
             volatile unsigned long long *word = hstat + 8;
@@ -1905,20 +1826,14 @@ static int cb_dev_fill(isdf_ctx *c, int N, CbDev *P, hipStream_t st) {
     // device: [x | ends | u | energy block]
     const size_t off_ends = nvar, off_u = off_ends + 18, off_e = off_u + (size_t)6 * (N + 1);
     const size_t need = off_e + ostride;
-    if (c->cbdev_cap < need) { c->cb_ends_dirty = true; }
-    int rc = ensure(c, &c->d_cbdev, &c->cbdev_cap, need);
+    if (c->d_cbdev.capacity() < need) { c->cb_ends_dirty = true; }
+    int rc = c->d_cbdev.reserve(c, need);
     if (rc) return rc;
-    rc = ensure(c, &c->d_cb, &c->cb_cap, in_len + 2 * ostride);
+    rc = c->d_cb.reserve(c, in_len + 2 * ostride);
     if (rc) return rc;
     const size_t rs = cb_res_stride(N), pin_need = nvar + rs + 2;
-    if (c->cbres_cap < pin_need) {
-        if (c->h_cbres) (void)hipHostFree(c->h_cbres);
-        c->h_cbres = nullptr; c->cbres_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_cbres, pin_need * sizeof(double), hipHostMallocDefault));
-        HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_cbres_dev, c->h_cbres, 0));
-        std::memset(c->h_cbres, 0, pin_need * sizeof(double));
-        c->cbres_cap = pin_need;
-    }
+    rc = c->h_cbres.reserve(c, pin_need);
+    if (rc) return rc;
     if (c->cb_ends_dirty) {
         HIPCHK(c, hipMemcpyAsync(c->d_cbdev + off_ends, c->cb_ends, 18 * sizeof(double), hipMemcpyHostToDevice, st));
         HIPCHK(c, hipStreamSynchronize(st));            // (cb_ends may change before an asynchronous copy has read it)
@@ -1928,7 +1843,7 @@ static int cb_dev_fill(isdf_ctx *c, int N, CbDev *P, hipStream_t st) {
     P->x = c->d_cbdev; P->ends = c->d_cbdev + off_ends; P->u = c->d_cbdev + off_u; P->epart = c->d_cbdev + off_e;
     P->T = c->d_cb; P->coeffs = c->d_cb + N; P->sweep = c->d_cb + in_len;
     P->rho = c->rho;
-    P->res = c->h_cbres_dev + nvar; P->flag = (unsigned long long *)(c->h_cbres_dev + nvar + rs);
+    P->res = c->h_cbres.dev() + nvar; P->flag = (unsigned long long *)(c->h_cbres.dev() + nvar + rs);
     P->seq = c->cb_seq; P->stats = c->d_stats;
     return ISDF_OK;
 }
@@ -1955,7 +1870,7 @@ static int cost_function_launch_dev(isdf_ctx *c, const double *x, int n, hipStre
     if (rc) return rc;
     const size_t nvar = (size_t)n;
     if (bar_usable(c, c->d_cbdev, nvar)) std::memcpy(c->d_cbdev, x, nvar * sizeof(double));      // CPU stores into device memory
-    else { std::memcpy(c->h_cbres, x, nvar * sizeof(double)); P.x = c->h_cbres_dev; }
+    else { std::memcpy(c->h_cbres, x, nvar * sizeof(double)); P.x = c->h_cbres.dev(); }
     host_rows_mark(c->h_cbres + nvar, cb_res_stride(N));
     __sync_synchronize();
     const size_t ostride = isdf_out_stride(N);
@@ -1984,7 +1899,7 @@ static int cost_function_finish_dev(isdf_ctx *c, double *g, double *cost_out, hi
         CbDev P{};
         const int rc = cb_dev_fill(c, N, &P, st);
         if (rc) return rc;
-        if (!bar_usable(c, c->d_cbdev, nvar)) P.x = c->h_cbres_dev;
+        if (!bar_usable(c, c->d_cbdev, nvar)) P.x = c->h_cbres.dev();
         launch_cb_post(P, st);
         HIPCHK(c, hipGetLastError());
     }
@@ -2045,13 +1960,8 @@ static int cost_function_launch(isdf_ctx *c, const double *x, int n, hipStream_t
     }
     c->last_host_path = ISDF_HOST_PATH_COPY;
     const size_t need = in_len + c->cb_n_out * ostride;
-    if (c->pin_cap < need) {
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->h_pin = nullptr; c->pin_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_pin, need * sizeof(double), hipHostMallocDefault));
-        c->pin_cap = need;
-    }
-    int rc = ensure(c, &c->d_cb, &c->cb_cap, need);
+    { const int rc0 = c->h_pin.reserve(c, need); if (rc0) return rc0; }
+    int rc = c->d_cb.reserve(c, need);
     if (rc) return rc;
     std::memcpy(c->h_pin, c->cb_T.data(), (size_t)N * sizeof(double));
     std::memcpy(c->h_pin + N, c->minco.c.data(), (size_t)18 * N * sizeof(double));
@@ -2304,10 +2214,9 @@ extern "C" int isdf_debug_set_sample_map(isdf_ctx *c, const int *map, long long 
     if (!c) return ISDF_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    if (c->d_sample_map) (void)hipFree(c->d_sample_map);
-    c->d_sample_map = nullptr; c->sample_map_n = 0;
+    c->d_sample_map.release(); c->sample_map_n = 0;
     if (!map || n <= 0) return ISDF_OK;
-    if (hipMalloc(&c->d_sample_map, (size_t)n * sizeof(int)) != hipSuccess) return ISDF_ERR_HIP;
+    if (c->d_sample_map.alloc((size_t)n) != hipSuccess) return ISDF_ERR_HIP;
     (void)hipMemcpy(c->d_sample_map, map, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
     c->sample_map_n = (size_t)n;
     return ISDF_OK;

@@ -24,6 +24,11 @@ constexpr int PLAN_CLASSES = 8;          // work classes of the longest-first or
 constexpr int PLAN_GROUP_MAX_SAMPLES = 65535;   // samples sorted together: their per-class counts are added in packed 16-bit fields
 constexpr int ACC_STRIDE = 8;       // costp, dL/dpos(3), dL/dquat(4) of one pose, before weight_p
 constexpr int PARTIAL_STRIDE = 20;  // V1: per-point record = 18 gradC entries (d*6 + r), gdT, pena
+// V1: the sizes the swept-volume kernels assume of their scratch (SweptParams), named once for the kernels and the host
+constexpr int SWEPT_MAX_COARSE = 1536;    // rows of the coarse table: traj_duration < 300 s, coarse step 0.2 s -> at most 1501 samples (and the CLOSED one)
+constexpr int SWEPT_MAX_RANGES = 32;      // interval slots per point (more set the overflow flag); 5 bits of a task word
+constexpr int SWEPT_TASK_STRIDE = 6;      // doubles per (point, interval) slot: in (lb, ub, seed) / out (t, sdf, grad(3), counters)
+constexpr int SWEPT_WORDS = 32;           // SweptParams::words
 
 // In-kernel exchange of a fused multi-GPU step (set up by csrc/xchg.hip, used by tile_sweep.hip's tail): every rank has a
 // BOARD in IPC-mapped uncached memory, [2 step parities][pieces of the launch][XF_ROW] result slots (19 output rows + cost of

@@ -182,14 +182,12 @@ using namespace isdf;
 static size_t n_bit_words(const DevGrid &G) { return (size_t)G.X * G.Y * ((G.Z + 31) / 32); }
 
 // occupancy bit-grid (padding bits of the last word of a row are zero)
-static int occupancy_bits(isdf_ctx *c, unsigned **out_bits) {
+static int occupancy_bits(isdf_ctx *c, DevBuf<unsigned> &b) {
     DevGrid G = c->grid;
     G.ZW = (G.Z + 31) / 32;
-    unsigned *b = nullptr;
-    HIPCHK(c, hipMalloc(&b, n_bit_words(G) * sizeof(unsigned)));
+    HIPCHK(c, b.alloc(n_bit_words(G)));
     G.occ = c->d_occ;
     launch_build_bits(G, 0, 0.0, b, c->stream);
-    *out_bits = b;
     return ISDF_OK;
 }
 
@@ -216,23 +214,22 @@ extern "C" int isdf_set_pointcloud(isdf_ctx *c, const float *xyz, long long n_po
         if (dim[a] < 1 || dim[a] > 4096) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "grid dimension out of range [1, 4096]");
     }
     const size_t n = (size_t)dim[0] * dim[1] * dim[2];
-    if (c->d_esdf) { (void)hipFree(c->d_esdf); c->d_esdf = nullptr; }
+    c->d_esdf.release();
     isdf_frontend_release(c);
-    if (c->d_occ) { (void)hipFree(c->d_occ); c->d_occ = nullptr; }
+    c->d_occ.release();
     c->grid.X = (int)dim[0]; c->grid.Y = (int)dim[1]; c->grid.Z = (int)dim[2]; c->grid.res = resolution;
     for (int a = 0; a < 3; a++) { c->grid.bmin[a] = bmin[a]; c->grid.bmax[a] = bmax[a]; }
     c->have_geom = true;
-    float *d_xyz = nullptr; unsigned *d_cnt = nullptr;
-    HIPCHK(c, hipMalloc(&d_xyz, (size_t)n_points * 3 * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_cnt, n * sizeof(unsigned)));
-    HIPCHK(c, hipMalloc(&c->d_occ, n));
+    DevBuf<float> d_xyz; DevBuf<unsigned> d_cnt;
+    HIPCHK(c, d_xyz.alloc((size_t)n_points * 3));
+    HIPCHK(c, d_cnt.alloc(n));
+    HIPCHK(c, c->d_occ.alloc(n));
     HIPCHK(c, hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, n * sizeof(unsigned), c->stream));
     hipLaunchKernelGGL(pc_count_kernel, dim3(2048), dim3(256), 0, c->stream, d_xyz, n_points, c->grid, d_cnt);
     hipLaunchKernelGGL(pc_threshold_kernel, dim3(4096), dim3(256), 0, c->stream, d_cnt, n, (unsigned)sta_threshold, c->d_occ);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(d_xyz); (void)hipFree(d_cnt);
     c->grid.esdf = nullptr; c->grid.occ = c->d_occ;
     c->bits_dirty = true;
     if (dims_out) { dims_out[0] = (int)dim[0]; dims_out[1] = (int)dim[1]; dims_out[2] = (int)dim[2]; }
@@ -247,20 +244,18 @@ extern "C" int isdf_generate_esdf(isdf_ctx *c) {
     DevGrid G = c->grid;
     G.ZW = (G.Z + 31) / 32;
     const size_t n = (size_t)G.X * G.Y * G.Z;
-    unsigned *bits = nullptr;
-    int rc = occupancy_bits(c, &bits);
+    DevBuf<unsigned> bits;
+    int rc = occupancy_bits(c, bits);
     if (rc) return rc;
-    int *a = nullptr, *b = nullptr;
-    HIPCHK(c, hipMalloc(&a, n * sizeof(int)));
-    HIPCHK(c, hipMalloc(&b, n * sizeof(int)));
-    if (c->d_esdf) { (void)hipFree(c->d_esdf); c->d_esdf = nullptr; }
-    HIPCHK(c, hipMalloc(&c->d_esdf, n * sizeof(float)));
+    DevBuf<int> a, b;
+    HIPCHK(c, a.alloc(n));
+    HIPCHK(c, b.alloc(n));
+    HIPCHK(c, c->d_esdf.alloc(n));
     hipLaunchKernelGGL(edt_z_kernel, dim3(4096), dim3(256), 0, c->stream, G, bits, a);
     hipLaunchKernelGGL(edt_line_kernel<1>, dim3(8192), dim3(256), 0, c->stream, G, a, b, (float *)nullptr);
     hipLaunchKernelGGL(edt_line_kernel<0>, dim3(8192), dim3(256), 0, c->stream, G, b, (int *)nullptr, c->d_esdf);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(bits);
     c->grid.esdf = c->d_esdf;
     c->bits_dirty = true;
     c->bricks_stale = true;
@@ -399,12 +394,10 @@ extern "C" int isdf_esdf_sample_device(isdf_ctx *c, const double *d_xyz, long lo
 static int esdf_bricks_ready(isdf_ctx *c, hipStream_t st) {
     const int BX = (c->grid.X + 1) / 2, BY = (c->grid.Y + 1) / 2, BZ = (c->grid.Z + 1) / 2;
     const size_t need = (size_t)BX * BY * BZ * isdf::BRICK_FLOATS;
-    if (c->d_esdf_bricks && !c->bricks_stale && c->bricks_cap == need) return ISDF_OK;
-    if (c->bricks_cap != need) {
-        if (c->d_esdf_bricks) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(c->d_esdf_bricks); }
-        c->d_esdf_bricks = nullptr; c->bricks_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_esdf_bricks, need * sizeof(float)));
-        c->bricks_cap = need;
+    if (c->d_esdf_bricks && !c->bricks_stale && c->d_esdf_bricks.capacity() == need) return ISDF_OK;
+    if (c->d_esdf_bricks.capacity() != need) {
+        if (c->d_esdf_bricks) HIPCHK(c, hipDeviceSynchronize());
+        HIPCHK(c, c->d_esdf_bricks.alloc(need));
     }
     DevGrid G = c->grid;
     G.esdf = c->d_esdf;
@@ -440,7 +433,7 @@ static int esdf_sample_host(isdf_ctx *c, const double *xyz, long long n, double 
     HIPCHK(c, hipSetDevice(c->device));
     // staging in the ctx (grows only): a caller that samples every optimizer step pays no allocation and no implicit device
     // synchronisation (hipFree) per call
-    { const int rc0 = isdf_ensure_doubles(c, &c->d_esdf_stage, &c->esdf_stage_cap, (size_t)n * 7); if (rc0) return rc0; }
+    { const int rc0 = c->d_esdf_stage.reserve(c, (size_t)n * 7); if (rc0) return rc0; }
     double *const d = c->d_esdf_stage;
     double *d_p = d, *d_v = d + (size_t)3 * n, *d_g = d + (size_t)4 * n;
     int rc = ISDF_OK;
@@ -511,19 +504,19 @@ extern "C" int isdf_gather_points(isdf_ctx *c, const double *waypoints, int n_wa
         for (int a = 0; a < 3; a++) last[a] = p[a];
     }
     int M = 0;
-    if (c->d_points) { (void)hipFree(c->d_points); c->d_points = nullptr; }
-    if (c->d_tstar) { (void)hipFree(c->d_tstar); c->d_tstar = nullptr; }
+    c->d_points.release();
+    c->d_tstar.release();
     c->M = 0;
     if (n_waypoints > 0) {
         const size_t nw = n_bit_words(G);
         const int n_chunks = (int)((nw + GATHER_CHUNK - 1) / GATHER_CHUNK);
-        unsigned *bits = nullptr, *marks = nullptr, *chunk = nullptr;
-        GatherBox *d_boxes = nullptr;
-        int rc = occupancy_bits(c, &bits);
+        DevBuf<unsigned> bits, marks, chunk;
+        DevBuf<GatherBox> d_boxes;
+        int rc = occupancy_bits(c, bits);
         if (rc) return rc;
-        HIPCHK(c, hipMalloc(&marks, nw * sizeof(unsigned)));
-        HIPCHK(c, hipMalloc(&chunk, ((size_t)n_chunks + 1) * sizeof(unsigned)));
-        HIPCHK(c, hipMalloc(&d_boxes, boxes.size() * sizeof(GatherBox)));
+        HIPCHK(c, marks.alloc(nw));
+        HIPCHK(c, chunk.alloc((size_t)n_chunks + 1));
+        HIPCHK(c, d_boxes.alloc(boxes.size()));
         HIPCHK(c, hipMemsetAsync(marks, 0, nw * sizeof(unsigned), c->stream));
         HIPCHK(c, hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(GatherBox), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(gather_mark_kernel, dim3(n_waypoints), dim3(256), 0, c->stream, G, d_boxes, bits, marks);
@@ -534,14 +527,13 @@ extern "C" int isdf_gather_points(isdf_ctx *c, const double *waypoints, int n_wa
         HIPCHK(c, hipStreamSynchronize(c->stream));
         M = (int)total;
         if (M > 0) {
-            HIPCHK(c, hipMalloc(&c->d_points, (size_t)3 * M * sizeof(double)));
-            HIPCHK(c, hipMalloc(&c->d_tstar, (size_t)M * sizeof(double)));
+            HIPCHK(c, c->d_points.alloc((size_t)3 * M));
+            HIPCHK(c, c->d_tstar.alloc((size_t)M));
             HIPCHK(c, hipMemsetAsync(c->d_tstar, 0, (size_t)M * sizeof(double), c->stream));     // lastTstar = 0 (plan_manager.cpp:254)
             hipLaunchKernelGGL(gather_emit_kernel, dim3(n_chunks), dim3(64), 0, c->stream, G, marks, nw, chunk, c->d_points, total);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        (void)hipFree(bits); (void)hipFree(marks); (void)hipFree(chunk); (void)hipFree(d_boxes);
     }
     c->M = M;
     c->points_epoch++;

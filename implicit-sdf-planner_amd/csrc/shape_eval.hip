@@ -121,8 +121,8 @@ __global__ __launch_bounds__(256) void mesh_lattice_kernel(const DevMesh *m, flo
 // thickness of the thickest defect pocket found (0: none) and the largest |1 - 2 w| inside one
 int isdf_mesh_surface_valid(isdf_ctx *c, const double *d_tri, int nF, double extent, double tau_limit, int *valid_out, float defect_out[2]) {
     *valid_out = 0; defect_out[0] = defect_out[1] = 0.f;
-    unsigned *d_flag = nullptr;
-    HIPCHK(c, hipMalloc(&d_flag, 3 * sizeof(unsigned)));
+    DevBuf<unsigned> d_flag;
+    HIPCHK(c, d_flag.alloc(3));
     HIPCHK(c, hipMemsetAsync(d_flag, 0, 3 * sizeof(unsigned), c->stream));
     const int samples = nF <= 4096 ? 4 : 1;            // (the test is quadratic in the faces: the reference's 12 000-face Trefoil.obj takes the centroids)
     // (... and beyond 32 768 faces every k-th face only, so that isdf_set_shape stays within ~0.1 s: 1e9 solid angles)
@@ -133,7 +133,6 @@ int isdf_mesh_surface_valid(isdf_ctx *c, const double *d_tri, int nF, double ext
     const hipError_t e1 = hipGetLastError();
     const hipError_t e2 = hipMemcpyAsync(back, d_flag, sizeof(back), hipMemcpyDeviceToHost, c->stream);
     const hipError_t e3 = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_flag);
     HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3);
     *valid_out = (back[0] & 1u) ? 0 : 1;
     std::memcpy(&defect_out[0], &back[1], 4); std::memcpy(&defect_out[1], &back[2], 4);
@@ -151,7 +150,7 @@ int isdf_mesh_lattice_build(isdf_ctx *c, isdf::DevMesh *hm, const double lo[3], 
     int dims[3];
     for (int a = 0; a < 3; a++) dims[a] = (int)std::ceil((hi[a] - lo[a]) / cell) + 1;
     const size_t total = (size_t)dims[0] * dims[1] * dims[2];
-    HIPCHK(c, hipMalloc(&c->d_mesh_dl, (total + 3) * sizeof(float)));      // (+ the flag word and the two range words)
+    HIPCHK(c, c->d_mesh_dl.alloc(total + 3));      // (+ the flag word and the two range words)
     unsigned *d_flag = reinterpret_cast<unsigned *>(c->d_mesh_dl + total);
     const unsigned init[3] = {0u, 0x7F7FFFFFu, 0u};
     HIPCHK(c, hipMemcpyAsync(d_flag, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
@@ -163,7 +162,7 @@ int isdf_mesh_lattice_build(isdf_ctx *c, isdf::DevMesh *hm, const double lo[3], 
     HIPCHK(c, hipMemcpyAsync(back, d_flag, sizeof(back), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (back[2] != 0u) { std::memcpy(&s_range_out[0], &back[1], 4); std::memcpy(&s_range_out[1], &back[2], 4); }
-    if (back[0]) { (void)hipFree(c->d_mesh_dl); c->d_mesh_dl = nullptr; return ISDF_OK; }      // not a mesh the lattice's users can reason about
+    if (back[0]) { c->d_mesh_dl.release(); return ISDF_OK; }      // not a mesh the lattice's users can reason about
     hm->dl = c->d_mesh_dl;
     for (int a = 0; a < 3; a++) { hm->dln[a] = dims[a]; hm->dl_min[a] = (float)lo[a]; }
     hm->dl_inv = 1.0f / cell;
@@ -177,8 +176,8 @@ extern "C" int isdf_shape_eval(isdf_ctx *c, const double *p_rel, int n, double *
     if (!c->have_shape) return isdf_fail(c, ISDF_ERR_STATE, "isdf_set_shape has not been called");
     if (n == 0 || (!sdf_out && !grad_out)) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    double *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, (size_t)n * 7 * sizeof(double)));
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)n * 7));
     double *d_p = d, *d_s = d + (size_t)3 * n, *d_g = d + (size_t)4 * n;
     int rc = ISDF_OK;
     auto chk = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == ISDF_OK) { c->err = std::string(what) + ": " + hipGetErrorString(e); rc = ISDF_ERR_HIP; } };
@@ -192,7 +191,6 @@ extern "C" int isdf_shape_eval(isdf_ctx *c, const double *p_rel, int n, double *
     if (rc == ISDF_OK && sdf_out) chk(hipMemcpyAsync(sdf_out, d_s, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream), "download sdf");
     if (rc == ISDF_OK && grad_out) chk(hipMemcpyAsync(grad_out, d_g, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream), "download grad");
     chk(hipStreamSynchronize(c->stream), "shape_eval sync");
-    (void)hipFree(d);
     return rc;
 }
 

@@ -5,20 +5,17 @@
 #include <hipcub/hipcub.hpp>
 
 constexpr int FIELD_CHUNK = 65536;                        // points per field launch: 65 536 x 1.5 KB of interval slots = 96 MiB
-constexpr int SWEPT_MAX_COARSE = 1536;                    // rows of the coarse table (300 s / 0.2 s, and the CLOSED sample)
 constexpr double MAX_DURATION = 300.0;                    // the reference's stale-duration rule (sw_manager.hpp:287-296)
 
 // scratch of the field query and the last mesh (never shared with the optimizer step's state)
 struct SweptMeshState {
-    // field
-    double *d_traj_duration = nullptr, *d_coarse_t = nullptr, *d_coarse_pose = nullptr;
-    int *d_n_coarse = nullptr;
-    int *d_point_nr = nullptr; double *d_task_buf = nullptr; unsigned *d_task_map = nullptr, *d_point_lmask = nullptr, *d_words = nullptr;
-    unsigned long long *d_stats = nullptr;
-    unsigned long long *h_overflow = nullptr;
+    // field: FIELD_CHUNK points of scratch, the statistics words and the overflow word as the host reads it
+    SweptScratch field;
+    DevBuf<unsigned long long> d_stats;
+    PinBuf<unsigned long long> h_overflow;
     // mesh build inputs (T | coeffs) and the last mesh
-    double *d_traj = nullptr; size_t traj_cap = 0;
-    double *d_V = nullptr; int32_t *d_F = nullptr;
+    DevBuf<double> d_traj;
+    DevBuf<double> d_V; DevBuf<int32_t> d_F;
     long long nV = 0, nF = 0;
     bool have_mesh = false;
 };
@@ -33,18 +30,11 @@ int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeff
 
 inline unsigned blocks(long long n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
-// a device buffer that frees itself
-template <typename T> struct DBuf {
-    T *p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
-};
-
 template <typename In, typename Out> int exclusive_sum(isdf_ctx *c, In in, Out out, long long n, hipStream_t st) {
     size_t bytes = 0;
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
-    DBuf<unsigned char> tmp;
+    DevBuf<unsigned char> tmp;
     HIPCHK(c, tmp.alloc(bytes));
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, in, out, (int)n, st));
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(tmp.get(), bytes, in, out, (int)n, st));
     return ISDF_OK;
 }

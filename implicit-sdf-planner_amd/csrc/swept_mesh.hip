@@ -28,16 +28,9 @@ namespace {
 
 constexpr long long MESH_MAX_NODES = 1ll << 27;           // fine lattice nodes of one mesh build (~20 B of scratch per node)
 
-void free_field_scratch(SweptMeshState *s) {
-    void *ptrs[] = {s->d_traj_duration, s->d_coarse_t, s->d_coarse_pose, s->d_n_coarse, s->d_point_nr, s->d_task_buf, s->d_task_map,
-                    s->d_point_lmask, s->d_words, s->d_stats};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (s->h_overflow) (void)hipHostFree(s->h_overflow);
-}
 void free_mesh_result(SweptMeshState *s) {
-    if (s->d_V) (void)hipFree(s->d_V);
-    if (s->d_F) (void)hipFree(s->d_F);
-    s->d_V = nullptr; s->d_F = nullptr; s->nV = s->nF = 0; s->have_mesh = false;
+    s->d_V.release(); s->d_F.release();
+    s->nV = s->nF = 0; s->have_mesh = false;
 }
 
 int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
@@ -48,21 +41,9 @@ int swept_field_scratch(isdf_ctx *c, SweptMeshState **out) {
     if (!c->swm) c->swm = new SweptMeshState();
     SweptMeshState *s = c->swm;
     *out = s;
-    if (s->d_task_buf) return ISDF_OK;
-    HIPCHK(c, hipMalloc(&s->d_traj_duration, sizeof(double)));
-    HIPCHK(c, hipMalloc(&s->d_coarse_t, SWEPT_MAX_COARSE * sizeof(double)));
-    HIPCHK(c, hipMalloc(&s->d_coarse_pose, SWEPT_MAX_COARSE * 12 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&s->d_n_coarse, sizeof(int)));
-    HIPCHK(c, hipMalloc(&s->d_point_nr, (size_t)FIELD_CHUNK * sizeof(int)));
-    HIPCHK(c, hipMalloc(&s->d_task_map, (size_t)FIELD_CHUNK * 32 * sizeof(unsigned)));
-    HIPCHK(c, hipMalloc(&s->d_point_lmask, (size_t)FIELD_CHUNK * sizeof(unsigned)));
-    HIPCHK(c, hipMemset(s->d_point_lmask, 0, (size_t)FIELD_CHUNK * sizeof(unsigned)));
-    HIPCHK(c, hipMalloc(&s->d_words, 32 * sizeof(unsigned)));
-    HIPCHK(c, hipMemset(s->d_words, 0, 32 * sizeof(unsigned)));
-    HIPCHK(c, hipMalloc(&s->d_stats, 8 * sizeof(unsigned long long)));
-    HIPCHK(c, hipHostMalloc(&s->h_overflow, sizeof(unsigned long long), hipHostMallocDefault));
-    HIPCHK(c, hipMalloc(&s->d_task_buf, (size_t)FIELD_CHUNK * 32 * 6 * sizeof(double)));      // SW_MAX_RANGES x TASK_STRIDE per point
-    return ISDF_OK;
+    if (!s->d_stats) HIPCHK(c, s->d_stats.alloc(8));
+    { const int rc = s->h_overflow.reserve(c, 1); if (rc) return rc; }
+    return s->field.reserve(c, (size_t)FIELD_CHUNK, false);
 }
 
 // host-side checks shared by both field entry points and the mesh build
@@ -85,15 +66,12 @@ int swept_check_ctx(isdf_ctx *c) {
 static SweptParams field_params(isdf_ctx *c, SweptMeshState *s, int N, const double *d_T, const double *d_coeffs) {
     SweptParams P{};
     P.shape = c->shape;
-    P.flat.mass = c->cfg.vehicle_mass; P.flat.grav = c->cfg.grav_acc; P.flat.dh = c->cfg.horiz_drag; P.flat.dv = c->cfg.vert_drag;
-    P.flat.cp = c->cfg.paras_drag; P.flat.veps = c->cfg.speed_eps; P.flat.dh_over_m = P.flat.dh / P.flat.mass;
+    isdf_fill_flat(c->cfg, P.flat);
     P.N = N;
     P.safety_hor = c->cfg.safety_hor; P.weight_p = c->cfg.weight_p;
     P.T = d_T; P.coeffs = d_coeffs;
-    P.traj_duration = s->d_traj_duration;
-    P.coarse_t = s->d_coarse_t; P.coarse_pose = s->d_coarse_pose; P.n_coarse = s->d_n_coarse; P.max_coarse = SWEPT_MAX_COARSE;
-    P.point_nr = s->d_point_nr; P.task_buf = s->d_task_buf; P.task_map = s->d_task_map;
-    P.point_lmask = s->d_point_lmask; P.words = s->d_words; P.stats = s->d_stats;
+    s->field.bind(P);
+    P.stats = s->d_stats;
     return P;
 }
 
@@ -124,14 +102,14 @@ int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeff
     for (long long b = 0; b < n; b += FIELD_CHUNK) {
         const int m = (int)std::min<long long>(FIELD_CHUNK, n - b);
         P.points = d_xyz + 3 * b; P.M = m; P.point_begin = 0; P.point_end = m;
-        if (b > 0) HIPCHK(c, hipMemsetAsync(s->d_words, 0, 2 * sizeof(unsigned), st));    // the descent's task counters (the prepare kernel zeroed the first chunk's)
+        if (b > 0) HIPCHK(c, hipMemsetAsync(s->field.words, 0, 2 * sizeof(unsigned), st));    // the descent's task counters (the prepare kernel zeroed the first chunk's)
         launch_swept_sweep(P, st, nullptr, nullptr, closed);
         launch_swept_field_reduce(P, d_value + b, d_tstar ? d_tstar + b : nullptr, st);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(s->h_overflow, s->d_stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    if (*s->h_overflow) return fail(c, ISDF_ERR_OVERFLOW, "swept-volume field: a point has more than 32 in-range intervals (results not valid)");
+    if (*s->h_overflow.get()) return fail(c, ISDF_ERR_OVERFLOW, "swept-volume field: a point has more than 32 in-range intervals (results not valid)");
     return ISDF_OK;
 }
 
@@ -400,16 +378,16 @@ __global__ void tri_emit_kernel(Lattice L, const double *f, double iso, const un
 // the field at the nodes [0, n) of a list (ids) or of the lattice (ids == null) into f[node]
 int field_nodes(isdf_ctx *c, int N, const double *d_T, const double *d_C, const Lattice &L, const int *ids, long long n, int mode,
                 double *f, hipStream_t st) {
-    DBuf<double> xyz, val;
+    DevBuf<double> xyz, val;
     const long long chunk = std::min<long long>(n, 16 * (long long)FIELD_CHUNK);
     HIPCHK(c, xyz.alloc((size_t)chunk * 3));
     HIPCHK(c, val.alloc((size_t)chunk));
     for (long long b = 0; b < n; b += chunk) {
         const int m = (int)std::min(chunk, n - b);
-        hipLaunchKernelGGL(node_xyz_kernel, dim3(blocks(m)), dim3(256), 0, st, L, ids, b, m, xyz.p);
-        const int rc = swept_field_run(c, N, d_T, d_C, xyz.p, m, mode, val.p, nullptr, st);
+        hipLaunchKernelGGL(node_xyz_kernel, dim3(blocks(m)), dim3(256), 0, st, L, ids, b, m, xyz.get());
+        const int rc = swept_field_run(c, N, d_T, d_C, xyz.get(), m, mode, val.get(), nullptr, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(node_scatter_kernel, dim3(blocks(m)), dim3(256), 0, st, ids, b, m, val.p, f);
+        hipLaunchKernelGGL(node_scatter_kernel, dim3(blocks(m)), dim3(256), 0, st, ids, b, m, val.get(), f);
     }
     HIPCHK(c, hipGetLastError());
     return ISDF_OK;
@@ -455,9 +433,6 @@ void traj_aabb(int N, const double *T, const double *C, double lo[3], double hi[
 
 void isdf_swept_release_all(isdf_ctx *c) {
     if (!c->swm) return;
-    free_mesh_result(c->swm);
-    free_field_scratch(c->swm);
-    if (c->swm->d_traj) (void)hipFree(c->swm->d_traj);
     delete c->swm;
     c->swm = nullptr;
 }
@@ -487,18 +462,18 @@ extern "C" int isdf_swept_sdf(isdf_ctx *c, int N, const double *T, const double 
     { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    DBuf<double> d_in, d_xyz, d_out;
+    DevBuf<double> d_in, d_xyz, d_out;
     HIPCHK(c, d_in.alloc((size_t)19 * N));
     HIPCHK(c, d_xyz.alloc((size_t)3 * n));
     HIPCHK(c, d_out.alloc((size_t)2 * n));
-    HIPCHK(c, hipMemcpyAsync(d_in.p, T, N * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_in.p + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(d_xyz.p, xyz, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-    const int rc = swept_field_run(c, N, d_in.p, d_in.p + N, d_xyz.p, n, mode, d_out.p, d_out.p + n, st);
+    HIPCHK(c, hipMemcpyAsync(d_in.get(), T, N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_in.get() + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(d_xyz.get(), xyz, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, st));
+    const int rc = swept_field_run(c, N, d_in.get(), d_in.get() + N, d_xyz.get(), n, mode, d_out.get(), d_out.get() + n, st);
     if (rc) return rc;
     if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(value_out, d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (tstar_out) HIPCHK(c, hipMemcpyAsync(tstar_out, d_out.p + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(value_out, d_out.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (tstar_out) HIPCHK(c, hipMemcpyAsync(tstar_out, d_out.get() + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipStreamSynchronize(st));
     return ISDF_OK;
@@ -562,7 +537,7 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     const long long n_cells = (dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1);
 
     // ---- the trajectory on the device
-    { const int rc = isdf_ensure_doubles(c, &s->d_traj, &s->traj_cap, (size_t)19 * N); if (rc) return rc; }
+    { const int rc = s->d_traj.reserve(c, (size_t)19 * N); if (rc) return rc; }
     HIPCHK(c, hipMemcpyAsync(s->d_traj, T, N * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(s->d_traj + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
     const double *d_T = s->d_traj, *d_C = s->d_traj + N;
@@ -570,76 +545,76 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     hipEvent_t ev[3];
     for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
     struct EvFree { hipEvent_t *e; ~EvFree() { for (int k = 0; k < 3; k++) (void)hipEventDestroy(e[k]); } } ev_free{ev};
-    DBuf<double> f;
+    DevBuf<double> f;
     HIPCHK(c, f.alloc((size_t)n_nodes));
-    HIPCHK(c, hipMemsetAsync(f.p, 0xFF, (size_t)n_nodes * sizeof(double), st));      // all-ones = NaN: not evaluated
+    HIPCHK(c, hipMemsetAsync(f.get(), 0xFF, (size_t)n_nodes * sizeof(double), st));      // all-ones = NaN: not evaluated
     HIPCHK(c, hipEventRecord(ev[0], st));
 
     // ---- the field: dense, or coarse lattice + narrow band
     long long coarse_points = 0, fine_points = 0;
     if (p->band == 0) {
-        const int rc = field_nodes(c, N, d_T, d_C, L, nullptr, n_nodes, p->mode, f.p, st);
+        const int rc = field_nodes(c, N, d_T, d_C, L, nullptr, n_nodes, p->mode, f.get(), st);
         if (rc) return rc;
         fine_points = n_nodes;
     } else {
         const int B = p->band;
         Coarse Q{B, (int)((dims[0] - 1 + B - 1) / B + 1), (int)((dims[1] - 1 + B - 1) / B + 1), (int)((dims[2] - 1 + B - 1) / B + 1)};
         const long long n_coarse = (long long)Q.cx * Q.cy * Q.cz, n_ccells = (long long)(Q.cx - 1) * (Q.cy - 1) * (Q.cz - 1);
-        DBuf<int> cids;
+        DevBuf<int> cids;
         HIPCHK(c, cids.alloc((size_t)n_coarse));
-        hipLaunchKernelGGL(coarse_ids_kernel, dim3(blocks(n_coarse)), dim3(256), 0, st, L, Q, cids.p);
-        { const int rc = field_nodes(c, N, d_T, d_C, L, cids.p, n_coarse, p->mode, f.p, st); if (rc) return rc; }
+        hipLaunchKernelGGL(coarse_ids_kernel, dim3(blocks(n_coarse)), dim3(256), 0, st, L, Q, cids.get());
+        { const int rc = field_nodes(c, N, d_T, d_C, L, cids.get(), n_coarse, p->mode, f.get(), st); if (rc) return rc; }
         coarse_points = n_coarse;
-        DBuf<unsigned char> refine, flag;
+        DevBuf<unsigned char> refine, flag;
         HIPCHK(c, refine.alloc((size_t)n_ccells));
         HIPCHK(c, flag.alloc((size_t)n_nodes));
         const double thr = p->lipschitz * std::sqrt(3.0) * B * eps;
-        hipLaunchKernelGGL(refine_kernel, dim3(blocks(n_ccells)), dim3(256), 0, st, L, Q, f.p, p->iso, thr, refine.p);
-        hipLaunchKernelGGL(flag_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, Q, refine.p, flag.p);
-        DBuf<int> fids, d_nsel;
+        hipLaunchKernelGGL(refine_kernel, dim3(blocks(n_ccells)), dim3(256), 0, st, L, Q, f.get(), p->iso, thr, refine.get());
+        hipLaunchKernelGGL(flag_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, Q, refine.get(), flag.get());
+        DevBuf<int> fids, d_nsel;
         HIPCHK(c, fids.alloc((size_t)n_nodes));
         HIPCHK(c, d_nsel.alloc(1));
         size_t bytes = 0;
         hipcub::CountingInputIterator<int> it(0);
-        HIPCHK(c, hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag.p, fids.p, d_nsel.p, (int)n_nodes, st));
+        HIPCHK(c, hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag.get(), fids.get(), d_nsel.get(), (int)n_nodes, st));
         {
-            DBuf<unsigned char> tmp;
+            DevBuf<unsigned char> tmp;
             HIPCHK(c, tmp.alloc(bytes));
-            HIPCHK(c, hipcub::DeviceSelect::Flagged(tmp.p, bytes, it, flag.p, fids.p, d_nsel.p, (int)n_nodes, st));
+            HIPCHK(c, hipcub::DeviceSelect::Flagged(tmp.get(), bytes, it, flag.get(), fids.get(), d_nsel.get(), (int)n_nodes, st));
             int nsel = 0;
-            HIPCHK(c, hipMemcpyAsync(&nsel, d_nsel.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(&nsel, d_nsel.get(), sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
             fine_points = nsel;
         }
-        { const int rc = field_nodes(c, N, d_T, d_C, L, fids.p, fine_points, p->mode, f.p, st); if (rc) return rc; }
+        { const int rc = field_nodes(c, N, d_T, d_C, L, fids.get(), fine_points, p->mode, f.get(), st); if (rc) return rc; }
     }
     HIPCHK(c, hipEventRecord(ev[1], st));
 
     // ---- extraction: count, scan, emit
-    DBuf<unsigned char> known, mask;
-    DBuf<int> tcount, tbase, vcount, vbase;
-    DBuf<unsigned long long> d_cnt;
+    DevBuf<unsigned char> known, mask;
+    DevBuf<int> tcount, tbase, vcount, vbase;
+    DevBuf<unsigned long long> d_cnt;
     HIPCHK(c, known.alloc((size_t)n_cells)); HIPCHK(c, tcount.alloc((size_t)n_cells)); HIPCHK(c, tbase.alloc((size_t)n_cells));
     HIPCHK(c, mask.alloc((size_t)n_nodes)); HIPCHK(c, vcount.alloc((size_t)n_nodes)); HIPCHK(c, vbase.alloc((size_t)n_nodes));
     HIPCHK(c, d_cnt.alloc(4));
-    HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(cell_count_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, (const double *)f.p, p->iso, known.p, tcount.p, d_cnt.p);
-    hipLaunchKernelGGL(vertex_count_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, (const double *)f.p, (const unsigned char *)known.p,
-                       p->iso, mask.p, vcount.p, d_cnt.p);
+    HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(cell_count_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, (const double *)f.get(), p->iso, known.get(), tcount.get(), d_cnt.get());
+    hipLaunchKernelGGL(vertex_count_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, (const double *)f.get(), (const unsigned char *)known.get(),
+                       p->iso, mask.get(), vcount.get(), d_cnt.get());
     HIPCHK(c, hipGetLastError());
     unsigned long long cnt[4];
-    HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (cnt[1] > (unsigned long long)INT32_MAX / 3 || cnt[2] > (unsigned long long)INT32_MAX / 3)
         return fail(c, ISDF_ERR_OVERFLOW, "swept mesh: more than 2^31 / 3 vertices or triangles");
-    { const int rc = exclusive_sum(c, tcount.p, tbase.p, n_cells, st); if (rc) return rc; }
-    { const int rc = exclusive_sum(c, vcount.p, vbase.p, n_nodes, st); if (rc) return rc; }
-    HIPCHK(c, hipMalloc(&s->d_V, (size_t)(cnt[2] ? cnt[2] : 1) * 3 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&s->d_F, (size_t)(cnt[1] ? cnt[1] : 1) * 3 * sizeof(int32_t)));
-    hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, (const double *)f.p, p->iso,
-                       (const unsigned char *)mask.p, (const int *)vbase.p, s->d_V);
-    hipLaunchKernelGGL(tri_emit_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, (const double *)f.p, p->iso,
-                       (const unsigned char *)known.p, (const int *)tbase.p, (const unsigned char *)mask.p, (const int *)vbase.p, s->d_F);
+    { const int rc = exclusive_sum(c, tcount.get(), tbase.get(), n_cells, st); if (rc) return rc; }
+    { const int rc = exclusive_sum(c, vcount.get(), vbase.get(), n_nodes, st); if (rc) return rc; }
+    HIPCHK(c, s->d_V.alloc((size_t)(cnt[2] ? cnt[2] : 1) * 3));
+    HIPCHK(c, s->d_F.alloc((size_t)(cnt[1] ? cnt[1] : 1) * 3));
+    hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, (const double *)f.get(), p->iso,
+                       (const unsigned char *)mask.get(), (const int *)vbase.get(), s->d_V);
+    hipLaunchKernelGGL(tri_emit_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, (const double *)f.get(), p->iso,
+                       (const unsigned char *)known.get(), (const int *)tbase.get(), (const unsigned char *)mask.get(), (const int *)vbase.get(), s->d_F);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev[2], st));
     HIPCHK(c, hipStreamSynchronize(st));

@@ -43,8 +43,8 @@ constexpr int SW_WAVES = 4;
 #ifndef ISDF_MESH_WPE
 #define ISDF_MESH_WPE 4      // wavefronts per SIMD the workgroup-form mesh kernels are compiled for (register budget 512 / this)
 #endif
-constexpr int SW_MAX_RANGES = 32;                // intervals kept per point (more set the overflow flag); 5 bits of a task word
-constexpr int TASK_STRIDE = 6;                   // doubles per (point, interval) slot: in (lb, ub, seed) / out (t, sdf, grad(3), counters)
+constexpr int SW_MAX_RANGES = SWEPT_MAX_RANGES;  // intervals kept per point (isdf_internal.hpp)
+constexpr int TASK_STRIDE = SWEPT_TASK_STRIDE;   // doubles per (point, interval) slot (isdf_internal.hpp)
 constexpr int LPT_TASK = 8;                      // descents of >= this many passes (last step) are dispatched first
 // ... mesh robots: descents that lasted at least TWICE the mean of the step before (words[4..6]: sum of the durations in 1.28 us units,
 // their count, the threshold the prepare kernel forms from them; wall_clock64 = 100 MHz)

@@ -24,8 +24,8 @@
 
 // the last check's violating points (kept like the swept mesh is) and the host form's trajectory upload
 struct TrajCheckState {
-    double *d_traj = nullptr; size_t traj_cap = 0;
-    double *d_rows = nullptr;       // n_rows x (x, y, z, value, t*)
+    DevBuf<double> d_traj;
+    DevBuf<double> d_rows;          // n_rows x (x, y, z, value, t*)
     long long n_rows = 0;
     bool have = false;
 };
@@ -263,8 +263,8 @@ __global__ void tc_rows_kernel(long long n, const int *__restrict__ flag, const 
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 void free_rows(TrajCheckState *s) {
-    if (s->d_rows) (void)hipFree(s->d_rows);
-    s->d_rows = nullptr; s->n_rows = 0; s->have = false;
+    s->d_rows.release();
+    s->n_rows = 0; s->have = false;
 }
 
 // what can be checked without a ctx (reported through isdf_last_error(NULL) when there is none)
@@ -306,8 +306,8 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     { const int rc = swept_field_coarse_table(c, N, d_T, d_C, mode, st); if (rc) return rc; }
     std::vector<double> pos(3 * (size_t)SWEPT_MAX_COARSE);
     int n_coarse = 0;
-    HIPCHK(c, hipMemcpyAsync(pos.data(), s->d_coarse_pose, pos.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&n_coarse, s->d_n_coarse, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(pos.data(), s->field.coarse_pose, pos.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&n_coarse, s->field.n_coarse, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     const bool mesh = c->shape.kind == ISDF_SHAPE_MESH;
     const double R = mesh ? std::max(c->mesh_rmax, c->shape.bound_radius) : c->shape.bound_radius;
@@ -335,35 +335,35 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     const double bdiag = std::sqrt(3.0) * (BRICK / 2) * G.res;        // brick centre to its farthest voxel centre is sqrt(3) 3.5 res
     B.far2 = far_r * far_r * slack; B.bfar2 = (far_r + bdiag) * (far_r + bdiag) * slack;
     unsigned long long cnt[2] = {0, 0};
-    DBuf<long long> vox;
-    DBuf<double> xyz;
+    DevBuf<long long> vox;
+    DevBuf<double> xyz;
     if (!empty) {
         for (int a = 0; a < 3; a++) { B.b0[a] = B.lo[a] / BRICK; B.nb[a] = B.hi[a] / BRICK - B.b0[a] + 1; }
         B.n_chunks = (B.hi[2] - B.lo[2] + 64) / 64;
         const long long n_rows = (long long)(B.hi[0] - B.lo[0] + 1) * (B.hi[1] - B.lo[1] + 1);
         const long long n_bricks = (long long)B.nb[0] * B.nb[1] * B.nb[2];
-        DBuf<int2> range;
-        DBuf<unsigned long long> mask, d_cnt;
-        DBuf<int> count, base;
+        DevBuf<int2> range;
+        DevBuf<unsigned long long> mask, d_cnt;
+        DevBuf<int> count, base;
         HIPCHK(c, range.alloc((size_t)n_bricks));
         HIPCHK(c, mask.alloc((size_t)n_rows * B.n_chunks));
         HIPCHK(c, count.alloc((size_t)n_rows)); HIPCHK(c, base.alloc((size_t)n_rows));
         HIPCHK(c, d_cnt.alloc(2));
-        HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+        HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 2 * sizeof(unsigned long long), st));
         if (cull) hipLaunchKernelGGL(tc_brick_kernel, dim3(std::min<unsigned>(blocks(n_bricks), 4096u)), dim3(256), 0, st, B,
-                                     (const double *)s->d_coarse_pose, (const int *)s->d_n_coarse, range.p);
+                                     (const double *)s->field.coarse_pose, (const int *)s->field.n_coarse, range.get());
         hipLaunchKernelGGL(tc_row_kernel, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B, (const uint8_t *)c->d_occ,
-                           (const int2 *)range.p, (const double *)s->d_coarse_pose, (const int *)s->d_n_coarse, mask.p, count.p, d_cnt.p);
+                           (const int2 *)range.get(), (const double *)s->field.coarse_pose, (const int *)s->field.n_coarse, mask.get(), count.get(), d_cnt.get());
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (cnt[1] > (unsigned long long)INT32_MAX) return fail(c, ISDF_ERR_OVERFLOW, "trajectory check: more than 2^31 candidate voxels");
         if (cnt[1]) {
-            { const int rc = exclusive_sum(c, count.p, base.p, n_rows, st); if (rc) return rc; }
+            { const int rc = exclusive_sum(c, count.get(), base.get(), n_rows, st); if (rc) return rc; }
             HIPCHK(c, vox.alloc((size_t)cnt[1]));
             HIPCHK(c, xyz.alloc((size_t)cnt[1] * 3));
             hipLaunchKernelGGL(tc_emit_kernel, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B,
-                               (const unsigned long long *)mask.p, (const int *)base.p, vox.p, xyz.p);
+                               (const unsigned long long *)mask.get(), (const int *)base.get(), vox.get(), xyz.get());
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(st));          // (mask / count / base go out of scope here)
         }
@@ -372,38 +372,38 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     HIPCHK(c, hipEventRecord(ev[1], st));
 
     // ---- field
-    DBuf<double> val, ts;
+    DevBuf<double> val, ts;
     HIPCHK(c, val.alloc((size_t)n)); HIPCHK(c, ts.alloc((size_t)n));
-    { const int rc = swept_field_run(c, N, d_T, d_C, xyz.p, n, mode, val.p, ts.p, st); if (rc) return rc; }
+    { const int rc = swept_field_run(c, N, d_T, d_C, xyz.get(), n, mode, val.get(), ts.get(), st); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(ev[2], st));
 
     // ---- reduce
     const int n_part = (int)std::max<long long>(1, blocks(n));
-    DBuf<int> flag, fbase;
-    DBuf<unsigned long long> key, d_counts;
-    DBuf<MinRec> partial;
-    DBuf<double> report;
+    DevBuf<int> flag, fbase;
+    DevBuf<unsigned long long> key, d_counts;
+    DevBuf<MinRec> partial;
+    DevBuf<double> report;
     HIPCHK(c, flag.alloc((size_t)n)); HIPCHK(c, fbase.alloc((size_t)n));
     HIPCHK(c, key.alloc((size_t)N)); HIPCHK(c, d_counts.alloc(3));
     HIPCHK(c, partial.alloc((size_t)n_part)); HIPCHK(c, report.alloc(REPORT_WORDS));
-    HIPCHK(c, hipMemsetAsync(d_counts.p, 0, 3 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(tc_key_fill_kernel, dim3(blocks(N)), dim3(256), 0, st, key.p, N);
-    if (n > 0) hipLaunchKernelGGL(tc_reduce_kernel, dim3(n_part), dim3(256), 0, st, n, (const double *)val.p, (const double *)ts.p, d_T, N,
-                                  margin, flag.p, key.p, partial.p, d_counts.p);
-    hipLaunchKernelGGL(tc_final_kernel, dim3(1), dim3(256), 0, st, (const MinRec *)partial.p, n > 0 ? n_part : 0, (const double *)val.p,
-                       (const double *)ts.p, (const long long *)vox.p, (const double *)xyz.p, d_T, N,
-                       (const unsigned long long *)key.p, d_piece_min, report.p);
+    HIPCHK(c, hipMemsetAsync(d_counts.get(), 0, 3 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(tc_key_fill_kernel, dim3(blocks(N)), dim3(256), 0, st, key.get(), N);
+    if (n > 0) hipLaunchKernelGGL(tc_reduce_kernel, dim3(n_part), dim3(256), 0, st, n, (const double *)val.get(), (const double *)ts.get(), d_T, N,
+                                  margin, flag.get(), key.get(), partial.get(), d_counts.get());
+    hipLaunchKernelGGL(tc_final_kernel, dim3(1), dim3(256), 0, st, (const MinRec *)partial.get(), n > 0 ? n_part : 0, (const double *)val.get(),
+                       (const double *)ts.get(), (const long long *)vox.get(), (const double *)xyz.get(), d_T, N,
+                       (const unsigned long long *)key.get(), d_piece_min, report.get());
     HIPCHK(c, hipGetLastError());
     unsigned long long counts[3];
     double rep[REPORT_WORDS];
-    HIPCHK(c, hipMemcpyAsync(counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(rep, report.p, sizeof(rep), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(counts, d_counts.get(), sizeof(counts), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rep, report.get(), sizeof(rep), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (counts[1]) {
-        { const int rc = exclusive_sum(c, flag.p, fbase.p, n, st); if (rc) return rc; }
-        HIPCHK(c, hipMalloc(&k->d_rows, (size_t)counts[1] * 5 * sizeof(double)));
-        hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)flag.p, (const int *)fbase.p,
-                           (const double *)xyz.p, (const double *)val.p, (const double *)ts.p, k->d_rows);
+        { const int rc = exclusive_sum(c, flag.get(), fbase.get(), n, st); if (rc) return rc; }
+        HIPCHK(c, k->d_rows.alloc((size_t)counts[1] * 5));
+        hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)flag.get(), (const int *)fbase.get(),
+                           (const double *)xyz.get(), (const double *)val.get(), (const double *)ts.get(), k->d_rows);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(ev[3], st));
@@ -434,8 +434,6 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
 
 void isdf_traj_check_release_all(isdf_ctx *c) {
     if (!c->tck) return;
-    free_rows(c->tck);
-    if (c->tck->d_traj) (void)hipFree(c->tck->d_traj);
     delete c->tck;
     c->tck = nullptr;
 }
@@ -459,8 +457,8 @@ extern "C" int isdf_traj_check_device(isdf_ctx *c, int N, const double *d_T, con
     HIPCHK(c, hipMemcpyAsync(hT.data(), d_T, N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     { const int rc = swept_check_traj(c, N, hT.data()); if (rc) return rc; }
-    DBuf<double> own;
-    if (!d_piece_min_out) { HIPCHK(c, own.alloc((size_t)N)); d_piece_min_out = own.p; }
+    DevBuf<double> own;
+    if (!d_piece_min_out) { HIPCHK(c, own.alloc((size_t)N)); d_piece_min_out = own.get(); }
     return check_run(c, N, d_T, d_coeffs, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, d_piece_min_out, st);
 }
 
@@ -476,7 +474,7 @@ extern "C" int isdf_traj_check(isdf_ctx *c, int N, const double *T, const double
     if (!c->tck) c->tck = new TrajCheckState();
     TrajCheckState *k = c->tck;
     hipStream_t st = c->stream;
-    { const int rc = isdf_ensure_doubles(c, &k->d_traj, &k->traj_cap, (size_t)20 * N); if (rc) return rc; }     // T | coeffs | per-piece minima
+    { const int rc = k->d_traj.reserve(c, (size_t)20 * N); if (rc) return rc; }     // T | coeffs | per-piece minima
     HIPCHK(c, hipMemcpyAsync(k->d_traj, T, N * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(k->d_traj + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
     double *d_pm = k->d_traj + 19 * (size_t)N;

@@ -185,7 +185,7 @@ struct isdf_xchg {
     unsigned long long fuse_seq = 0;
     void *peer_base[XCHG_MAX_WORLD] = {nullptr};
     bool opened[XCHG_MAX_WORLD] = {false};
-    unsigned *d_status = nullptr;               // [status word | pad | 64-bit push counter | 64-bit decision word]
+    DevBuf<unsigned> d_status;                  // [status word | pad | 64-bit push counter | 64-bit decision word]
     unsigned long long seq = 0;
     double ticks_per_ms = 1e5;                  // wall_clock64() rate of this device (hipDeviceAttributeWallClockRate, kHz): 100 MHz on gfx950
     bool connected = false;
@@ -197,7 +197,6 @@ static void xchg_free(isdf_ctx *c) {
     for (int r = 0; r < x->world; r++)
         if (x->opened[r] && x->peer_base[r]) (void)hipIpcCloseMemHandle(x->peer_base[r]);
     if (x->own) (void)hipFree(x->own);
-    if (x->d_status) (void)hipFree(x->d_status);
     delete x;
     c->xchg = nullptr;
 }
@@ -229,8 +228,7 @@ extern "C" int isdf_xchg_create(isdf_ctx *c, int rank, int world, size_t max_dou
     if (hipExtMallocWithFlags(&x->own, x->own_bytes, hipDeviceMallocUncached) != hipSuccess) { xchg_free(c); return isdf_fail(c, ISDF_ERR_HIP, "uncached mailbox allocation failed"); }
     HIPCHK(c, hipMemset(x->own, 0, x->own_bytes));
     HIPCHK(c, hipMemset((char *)x->own + x->board_offset, 0xFF, x->board_doubles * sizeof(double)));    // every slot empty
-    HIPCHK(c, hipMalloc(&x->d_status, 32));
-    HIPCHK(c, hipMemset(x->d_status, 0, 32));
+    HIPCHK(c, x->d_status.alloc(8, 0x00));
     HIPCHK(c, hipDeviceSynchronize());
     hipIpcMemHandle_t h;
     if (hipIpcGetMemHandle(&h, x->own) != hipSuccess) { xchg_free(c); return isdf_fail(c, ISDF_ERR_HIP, "hipIpcGetMemHandle failed"); }
@@ -264,7 +262,7 @@ extern "C" int isdf_xchg_allreduce(isdf_ctx *c, double *d_buf, size_t count, voi
     if (!x || !x->connected) return isdf_fail(c, ISDF_ERR_STATE, "exchange not connected");
     if (count > x->slot_doubles) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "vector longer than the exchange was created for");
     XchgParams X{};
-    X.rank = x->rank; X.world = x->world; X.slot_doubles = x->slot_doubles; X.seq = ++x->seq; X.t_wait = (unsigned long long)(c->xchg_timeout_ms * x->ticks_per_ms); X.status = x->d_status; X.pushes = (unsigned long long *)((char *)x->d_status + 8); X.decision = (unsigned long long *)((char *)x->d_status + 16);
+    X.rank = x->rank; X.world = x->world; X.slot_doubles = x->slot_doubles; X.seq = ++x->seq; X.t_wait = (unsigned long long)(c->xchg_timeout_ms * x->ticks_per_ms); X.status = x->d_status; X.pushes = (unsigned long long *)((char *)x->d_status.get() + 8); X.decision = (unsigned long long *)((char *)x->d_status.get() + 16);
     for (int r = 0; r < x->world; r++) {
         X.peer_slots[r] = (double *)x->peer_base[r];
         X.peer_flags[r] = (unsigned long long *)((char *)x->peer_base[r] + x->flags_offset);

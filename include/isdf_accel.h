@@ -309,6 +309,10 @@ int isdf_host_path(const isdf_ctx *ctx);
  * word is there, waits until none of it is left.  info_out: [0] hand-overs so far, [1] how many of them had results still
  * missing when the word arrived, [2] polls spent waiting for those; [3..7] reserved (0). */
 int isdf_host_info(const isdf_ctx *ctx, int64_t info_out[8]);
+/* Developer entry: the bytes the library's own buffers hold at this moment, process-wide - out[0] device memory, out[1] pinned
+ * host memory (every ctx, every scratch and temporary; not the exchange's IPC mailbox, not the A* table).  Both return to
+ * what they were once every ctx created since has been destroyed. */
+void isdf_debug_live_bytes(long long out[2]);
 
 /* Device-resident entry point, asynchronous on `stream` (a hipStream_t passed as void*; NULL = default
  * stream).  All trajectories have N pieces.  d_T: n_traj*N, d_coeffs: n_traj * (6N x 3 col-major),
