@@ -3,6 +3,8 @@
 #include "isdf_internal.hpp"
 #include "dev_buf.hpp"
 #include "minco_host.hpp"
+#include <chrono>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -122,7 +124,7 @@ struct isdf_ctx {
     double last_parts[4] = {0, 0, 0, 0};
     std::vector<double> cb_x; double cb_energy = 0.0; int cb_n_out = 1; bool cb_pending = false;
     // device half of the callback (csrc/minco_dev.hip): MINCO, energy, adjoint and chain rule in two small kernels either side
-    // of the sweeps - a callback moves n doubles down and n + 5 up.  minco_mode 0: wherever it is faster (isdf_host.hip
+    // of the sweeps - a callback moves n doubles down and n + 5 up.  minco_mode 0: wherever it is faster (callback.hip
     // cb_device_minco), 1 (ISDF_HOST_MINCO=1): the host's band LU, bitwise the reference's elimination order, 2
     // (ISDF_DEVICE_MINCO=1): on the device whenever N <= CB_MAX_N
     int minco_mode = 0; int last_minco_path = 0;          // last_minco_path: 1 = the last callback ran MINCO on the device
@@ -203,3 +205,51 @@ int isdf_mesh_surface_valid(isdf_ctx *c, const double *d_tri, int nF, double ext
 
 int isdf_fail(isdf_ctx *c, int code, const char *msg);      // records the message, returns code
 void isdf_fill_flat(const isdf_config &cfg, isdf::FlatP &f);      // isdf_host.hip: the dynamics constants of a launch
+
+// ---- shared between the host files (isdf_host.hip, shape_setup.hip, multi_dev.hip, host_step.hip, callback.hip)
+inline bool env_is(const char *name, char ch) { const char *e = getenv(name); return e && e[0] == ch; }     // a one-character switch, read when called
+// host-direct step: device-visible addresses of the pinned inputs / outputs / flags of this step
+struct HostDirect { const double *T, *coeffs; double *out; unsigned long long *flags; unsigned long long seq; bool via_bar; };
+constexpr int ISDF_DIRECT_NA = 1;        // eval_device_impl: the step cannot run host-direct (nothing was launched)
+void shard_range(long long total, int rank, int world, long long &b, long long &e);     // isdf_host.hip: this rank's contiguous share [b, e)
+// isdf_host.hip: one step of one device.  mode 0: the sweep cfg.variant names; 1: the swept-volume sweep; 2: the integral sweep with the collision term off
+int eval_device_impl(isdf_ctx *c, int n_traj, int N, const double *d_T, const double *d_coeffs, double *d_out,
+                     double *d_tstar, hipStream_t st, int mode = 0, bool fixed_tstar = false, const HostDirect *hd = nullptr);
+// isdf_host.hip: every sweep of the host paths goes through here (one device or several)
+int sweep_dispatch(isdf_ctx *c, int n_traj, int N, const double *d_T, const double *d_coeffs, double *d_out, double *d_tstar,
+                   hipStream_t st, int mode = 0, bool fixed_tstar = false);
+int fetch_stats(isdf_ctx *c);             // isdf_host.hip: the last launch's statistics words into last_stats (reads the sticky overflow word)
+int clear_overflow(isdf_ctx *c);          // isdf_host.hip: clears the sticky overflow word, then isdf_reset_result_slots
+void multi_release(isdf_ctx *c);          // multi_dev.hip: the multi-device ctx's events and communicator (isdf_destroy)
+int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, const double *d_coeffs, double *d_out,
+                      double *d_tstar, hipStream_t st, int mode, bool fixed_tstar);      // multi_dev.hip: one step on every device, summed on the lead
+int add_peer_stats(isdf_ctx *c);          // multi_dev.hip: the peers' pair statistics added to the lead's last_stats
+bool direct_enabled(const isdf_ctx *c);   // host_step.hip: this ctx's small steps may run host-direct
+int direct_launch(isdf_ctx *c, int nb, int n, const double *const *T, const double *const *coeffs, int first, hipStream_t st, int mode);     // host_step.hip: places the inputs, launches
+int direct_wait(isdf_ctx *c, hipStream_t st, bool *overflow);      // host_step.hip: the host's side of that step's hand-over
+bool bar_usable(isdf_ctx *c, double *d_buf, size_t n);             // host_step.hip: the host can write device memory through the PCIe BAR (probed once per ctx)
+void host_rows_mark(double *p, size_t n);                          // host_step.hip: fills a host-mapped result area with the "not written yet" pattern
+bool host_rows_wait(isdf_ctx *c, const double *p, size_t n, bool another_area_of_the_same_step = false);   // host_step.hip: waits until none of it is left
+// the four counts of a step added to a running total (not the overflow word): from another isdf_stats / from a step's statistics words
+static inline void stats_add(isdf_stats &t, const isdf_stats &s) {
+    t.n_units += s.n_units; t.n_units_culled += s.n_units_culled; t.n_pairs += s.n_pairs; t.n_grad_pairs += s.n_grad_pairs;
+}
+static inline void stats_add(isdf_stats &t, const unsigned long long *w) {
+    t.n_units += (int64_t)w[0]; t.n_units_culled += (int64_t)w[1]; t.n_pairs += (int64_t)w[2]; t.n_grad_pairs += (int64_t)w[3];
+}
+
+// The host's side of every hand-over through host-mapped memory (host_step.hip, callback.hip): spins until the completion word, its
+// `mask` bits aside, equals seq.  Bounded: `seconds` after t0 (the clock is read every 0x4000 spins only) it drains the stream, looks
+// once more and gives up.  *value: the word as last read.  The caller's acquire fence and host_rows_wait follow.
+static inline bool host_flag_wait(const volatile unsigned long long *word, unsigned long long seq, unsigned long long mask,
+                                  std::chrono::steady_clock::time_point t0, double seconds, hipStream_t st, unsigned long long *value) {
+    for (unsigned spin = 0;; spin++) {
+        *value = *word;
+        if ((*value & ~mask) == seq) return true;
+        if ((spin & 0x3FFFu) == 0x3FFFu && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > seconds) {
+            (void)hipStreamSynchronize(st);
+            *value = *word;
+            return (*value & ~mask) == seq;
+        }
+    }
+}

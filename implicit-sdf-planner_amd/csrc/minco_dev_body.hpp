@@ -24,7 +24,7 @@
 // the launch's other 2 700 wavefronts poll its ready flags (46.9 us: the polling starves the solve); the same with EVERY
 // workgroup repeating the solve into an LDS table (39.0 us: no polling, but three workgroups per CU share its SIMDs for the
 // solve, and the adjoint still sits behind the last sample).  The host's band LU costs 10 us at N = 40: that configuration keeps
-// it (isdf_host.hip cb_device_minco).
+// it (callback.hip cb_device_minco).
 #pragma once
 #include "isdf_internal.hpp"
 #include "dev_math.hpp"

@@ -376,7 +376,7 @@ def test_device_minco_gradient_is_the_derivative(pkg, orc, product_lib):
 def test_first_host_mapped_step_of_fresh_ctxs_is_complete(pkg, orc, product_lib):
     """The hand-overs that end in a flag in host-mapped memory (host-direct step, device callback): the FIRST step of a fresh ctx must
     return what every later step returns - the flag can reach the CPU before the result rows (seen on MI355X: a wrong first gradient
-    about once in twenty fresh processes; csrc/isdf_host.hip host_rows_wait).  isdf_host_info counts the hand-overs."""
+    about once in twenty fresh processes; csrc/host_step.hip host_rows_wait).  isdf_host_info counts the hand-overs."""
     capi, synth = pkg.capi, pkg.synth
     occ, esdf, res = small_world(pkg)
     N = 6
