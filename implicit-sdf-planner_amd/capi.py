@@ -115,6 +115,20 @@ class IsdfTrajCheckInfo(C.Structure):
                 ("select_ms", C.c_double), ("field_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+class IsdfPointsMergeInfo(C.Structure):
+    _fields_ = [("M_before", C.c_int32), ("M_after", C.c_int32), ("n_rows", C.c_int32), ("n_added", C.c_int32),
+                ("n_duplicate", C.c_int32), ("n_outside", C.c_int32), ("reserved", C.c_int32 * 2), ("merge_ms", C.c_double)]
+
+
+class IsdfRefineParams(C.Structure):
+    _fields_ = [("max_rounds", C.c_int32), ("mode", C.c_int32), ("margin", C.c_double), ("below", C.c_double)]
+
+
+class IsdfRefineResult(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("clear", C.c_int32), ("stalled", C.c_int32), ("reserved", C.c_int32),
+                ("M_round", C.c_int32 * 16), ("last_opt", IsdfLbfgsResult), ("last_check", IsdfTrajCheckInfo)]
+
+
 EVALUATE_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int)
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_int)   # isdf_progress_fn
 
@@ -141,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "isdf_swept_sdf", "isdf_swept_sdf_device", "isdf_swept_mesh_params_default", "isdf_swept_mesh_build", "isdf_swept_mesh_get",
     "isdf_swept_mesh_release", "isdf_write_obj", "isdf_traj_check_params_default", "isdf_traj_check", "isdf_traj_check_device",
     "isdf_traj_check_get", "isdf_traj_check_release", "isdf_traj_collide",
+    "isdf_points_merge_check", "isdf_refine_params_default", "isdf_optimize_lbfgs_checked",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -270,6 +285,11 @@ def load_library(path=None):
     lib.isdf_traj_check_get.argtypes = [C.c_void_p, dp, C.c_longlong]
     lib.isdf_traj_check_release.argtypes = [C.c_void_p]
     lib.isdf_traj_collide.argtypes = [C.c_void_p, C.c_int, dp, dp]
+    lib.isdf_points_merge_check.argtypes = [C.c_void_p, C.c_double, C.POINTER(IsdfPointsMergeInfo)]
+    lib.isdf_refine_params_default.argtypes = [C.POINTER(IsdfRefineParams)]
+    lib.isdf_refine_params_default.restype = None
+    lib.isdf_optimize_lbfgs_checked.argtypes = [C.c_void_p, dp, C.c_int, C.POINTER(IsdfLbfgsParams), C.POINTER(IsdfRefineParams),
+                                                C.POINTER(IsdfRefineResult)]
     if path is None:
         _lib = lib
     return lib

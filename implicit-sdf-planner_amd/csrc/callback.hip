@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 using namespace isdf;
 
@@ -367,4 +368,57 @@ extern "C" int isdf_optimize_lbfgs(isdf_ctx *c, double *x_inout, int n, const is
     if (!c->have_traj) return isdf_fail(c, ISDF_ERR_STATE, "isdf_set_trajectory not called");
     if (n != isdf_num_variables(c)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "n must be N + 3(N-1)");
     return lbfgs_run(isdf_cost_function_lmbm, c, c->progress, c->progress_instance, x_inout, n, p, out);
+}
+
+// --------------------------------------------------------------------------------------------------------------
+// lazy constraint generation: optimise, check the result against the whole map, merge what the check found into the point set
+// (where plan_manager.cpp:306-309 only warns), again
+// --------------------------------------------------------------------------------------------------------------
+extern "C" void isdf_refine_params_default(isdf_refine_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->max_rounds = 4;
+    p->mode = ISDF_SWEPT_FIELD_PLANNER;
+    p->margin = -1.0;                       // negative: cfg.safety_hor of the ctx
+    p->below = -1.0;                        // negative: every kept row
+}
+
+extern "C" int isdf_optimize_lbfgs_checked(isdf_ctx *c, double *x_inout, int n, const isdf_lbfgs_params *lp,
+                                           const isdf_refine_params *rp, isdf_refine_result *out) {
+    isdf_refine_params dflt;
+    isdf_refine_params_default(&dflt);
+    const isdf_refine_params &R = rp ? *rp : dflt;
+    // the arguments are checked before the ctx (reported through isdf_last_error(NULL) when there is none)
+    if (R.max_rounds < 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "checked optimisation: max_rounds must be >= 1");
+    if (R.mode != ISDF_SWEPT_FIELD_PLANNER && R.mode != ISDF_SWEPT_FIELD_CLOSED) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "checked optimisation: unknown mode");
+    if (!std::isfinite(R.margin)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "checked optimisation: margin must be finite");
+    if (!std::isfinite(R.below)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "checked optimisation: below must be finite");
+    if (!c) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "checked optimisation: null ctx");
+    if (!x_inout || !lp || !out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null argument");
+    if (c->cfg.variant != ISDF_V1_SWEPT) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "checked optimisation: the obstacle-point set belongs to the swept-volume variant (V1)");
+    if (!c->have_traj) return isdf_fail(c, ISDF_ERR_STATE, "isdf_set_trajectory not called");
+    if (!c->have_geom || !c->d_occ)
+        return isdf_fail(c, ISDF_ERR_STATE, "trajectory check: no occupancy grid (isdf_set_grid with ISDF_GRID_OCCUPANCY, or isdf_set_pointcloud)");
+    std::memset(out, 0, sizeof(*out));
+    const int N = c->minco.N;
+    std::vector<double> T((size_t)N), coeffs((size_t)18 * N);
+    isdf_traj_check_params cp;
+    isdf_traj_check_params_default(&cp);
+    cp.margin = R.margin; cp.mode = R.mode;
+    for (int round = 0; round < R.max_rounds; round++) {
+        if (round < 16) out->M_round[round] = c->M;
+        out->rounds = round + 1;
+        int rc = isdf_optimize_lbfgs(c, x_inout, n, lp, &out->last_opt);
+        if (rc) return rc;
+        rc = isdf_unpack_variables(c, x_inout, T.data(), coeffs.data());
+        if (rc) return rc;
+        rc = isdf_traj_check(c, N, T.data(), coeffs.data(), &cp, &out->last_check, nullptr);
+        if (rc) return rc;
+        if (out->last_check.n_below_margin == 0) { out->clear = 1; break; }
+        isdf_points_merge_info mi;
+        rc = isdf_points_merge_check(c, R.below, &mi);
+        if (rc) return rc;
+        if (mi.n_added == 0) { out->stalled = 1; break; }
+    }
+    return ISDF_OK;
 }

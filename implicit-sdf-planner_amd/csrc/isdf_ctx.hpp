@@ -13,7 +13,7 @@ using namespace isdf;
 struct ProfEvent { hipEvent_t a, b, c, d; };   // start/stop of the dominant kernel, start/stop of the one after it
 struct isdf_xchg;
 struct SweptMeshState;          // swept_mesh.hip: scratch of the swept-volume field query and the last mesh
-struct TrajCheckState;          // traj_check.hip: the last clearance check's points below the margin
+struct TrajCheckState;          // swept_field.hpp: the last clearance check's points below the margin
 void isdf_swept_release_all(isdf_ctx *c);     // swept_mesh.hip: drops the field scratch and the mesh
 void isdf_traj_check_release_all(isdf_ctx *c);        // traj_check.hip: drops the kept clearance report
 
@@ -49,6 +49,7 @@ struct isdf_ctx {
     DevBuf<uint8_t> d_occ;
     DevBuf<unsigned> d_bits; bool bits_dirty = true;
     bool have_geom = false;
+    unsigned long long grid_epoch = 0;          // counts isdf_set_grid / isdf_set_pointcloud: what was derived from voxel indices of an older grid is stale
     // shape
     DevShape shape{};
     isdf_shape shape_host{};
@@ -67,6 +68,7 @@ struct isdf_ctx {
     DevBuf<double> d_points;
     int M = 0;
     DevBuf<double> d_tstar;          // internal lastTstar when the caller passes none
+    DevBuf<unsigned> d_merge_bits;   // isdf_points_merge_check: one bit per voxel, set where a point of the set lies (grows only)
     // shard
     int rank = 0, world = 1;
     // per-step scratch

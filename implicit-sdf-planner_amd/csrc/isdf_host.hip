@@ -124,6 +124,7 @@ extern "C" int isdf_set_grid(isdf_ctx *c, const void *vox, int dtype, int nx, in
         c->grid.bmax[a] = bmax ? bmax[a] : origin[a] + dim * res;
     }
     c->have_geom = true;
+    c->grid_epoch++;
     if (kind == ISDF_GRID_ESDF) {
         std::vector<float> tmp;
         const float *src = nullptr;

@@ -10,6 +10,7 @@
 // (z: nearest set bit of the occupancy bit-row; y, x: bounded outward scan, exact because a candidate at offset r
 // cannot beat the current best once r^2 >= best) and res * sqrt(d2) is bit-identical to the reference's double.
 #include "isdf_ctx.hpp"
+#include "grid_index.hpp"
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -24,14 +25,8 @@ constexpr int EDT_INF = 0x3fffffff;        // "no occupied voxel on this line / 
 __global__ __launch_bounds__(256) void pc_count_kernel(const float *__restrict__ xyz, long long n, DevGrid G, unsigned *__restrict__ counts) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const double x = (double)xyz[3 * i], y = (double)xyz[3 * i + 1], z = (double)xyz[3 * i + 2];
-        int ix = 0, iy = 0, iz = 0;      // getGridIndex: a point outside the map lands in voxel (0,0,0) (:137-140)
-        const bool in = !(x < G.bmin[0] || y < G.bmin[1] || z < G.bmin[2] || x > G.bmax[0] || y > G.bmax[1] || z > G.bmax[2]);
-        if (in) {
-            ix = (int)floor((x - G.bmin[0]) / G.res); iy = (int)floor((y - G.bmin[1]) / G.res); iz = (int)floor((z - G.bmin[2]) / G.res);
-            if (ix >= G.X) ix = G.X - 1;       // the lower clamps of :149-168 cannot trigger inside the map
-            if (iy >= G.Y) iy = G.Y - 1;
-            if (iz >= G.Z) iz = G.Z - 1;
-        }
+        int ix, iy, iz;
+        (void)grid_index(G, x, y, z, ix, iy, iz);      // getGridIndex: a point outside the map lands in voxel (0,0,0) (:137-140)
         atomicAdd(&counts[((size_t)ix * G.Y + iy) * G.Z + iz], 1u);
     }
 }
@@ -220,6 +215,7 @@ extern "C" int isdf_set_pointcloud(isdf_ctx *c, const float *xyz, long long n_po
     c->grid.X = (int)dim[0]; c->grid.Y = (int)dim[1]; c->grid.Z = (int)dim[2]; c->grid.res = resolution;
     for (int a = 0; a < 3; a++) { c->grid.bmin[a] = bmin[a]; c->grid.bmax[a] = bmax[a]; }
     c->have_geom = true;
+    c->grid_epoch++;
     DevBuf<float> d_xyz; DevBuf<unsigned> d_cnt;
     HIPCHK(c, d_xyz.alloc((size_t)n_points * 3));
     HIPCHK(c, d_cnt.alloc(n));

@@ -20,6 +20,17 @@ struct SweptMeshState {
     bool have_mesh = false;
 };
 
+// the last clearance check's violating points (kept like the swept mesh is) and the host form's trajectory upload (traj_check.hip);
+// points_merge.hip reads the rows
+struct TrajCheckState {
+    DevBuf<double> d_traj;
+    DevBuf<double> d_rows;          // n_rows x (x, y, z, value, t*)
+    DevBuf<long long> d_row_vox;    // n_rows voxel indices (x * ny + y) * nz + z, ascending
+    long long n_rows = 0;
+    unsigned long long grid_epoch = 0;      // the ctx's grid_epoch the check ran on
+    bool have = false;
+};
+
 // swept_mesh.hip
 int swept_field_scratch(isdf_ctx *c, SweptMeshState **out);          // allocates the query's scratch on first use
 int swept_check_traj(isdf_ctx *c, int N, const double *T);           // durations finite and > 0, total below 300 s

@@ -22,14 +22,6 @@
 #include <cstring>
 #include <vector>
 
-// the last check's violating points (kept like the swept mesh is) and the host form's trajectory upload
-struct TrajCheckState {
-    DevBuf<double> d_traj;
-    DevBuf<double> d_rows;          // n_rows x (x, y, z, value, t*)
-    long long n_rows = 0;
-    bool have = false;
-};
-
 namespace {
 
 constexpr int BRICK = 8;                 // voxels per brick edge
@@ -260,10 +252,18 @@ __global__ void tc_rows_kernel(long long n, const int *__restrict__ flag, const 
     double *o = rows + 5 * (size_t)base[j];
     o[0] = xyz[3 * j]; o[1] = xyz[3 * j + 1]; o[2] = xyz[3 * j + 2]; o[3] = val[j]; o[4] = ts[j];
 }
+// ... and their voxel indices next to them (isdf_points_merge_check keys the obstacle-point set by them)
+__global__ void tc_row_vox_kernel(long long n, const int *__restrict__ flag, const int *__restrict__ base, const long long *__restrict__ vox,
+                                  long long *__restrict__ row_vox) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n || !flag[j]) return;
+    row_vox[base[j]] = vox[j];
+}
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 void free_rows(TrajCheckState *s) {
     s->d_rows.release();
+    s->d_row_vox.release();
     s->n_rows = 0; s->have = false;
 }
 
@@ -404,11 +404,14 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
         HIPCHK(c, k->d_rows.alloc((size_t)counts[1] * 5));
         hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)flag.get(), (const int *)fbase.get(),
                            (const double *)xyz.get(), (const double *)val.get(), (const double *)ts.get(), k->d_rows);
+        HIPCHK(c, k->d_row_vox.alloc((size_t)counts[1]));
+        hipLaunchKernelGGL(tc_row_vox_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)flag.get(), (const int *)fbase.get(),
+                           (const long long *)vox.get(), k->d_row_vox.get());
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(ev[3], st));
     HIPCHK(c, hipStreamSynchronize(st));
-    k->n_rows = (long long)counts[1]; k->have = true;
+    k->n_rows = (long long)counts[1]; k->have = true; k->grid_epoch = c->grid_epoch;
     if (info) {
         std::memset(info, 0, sizeof(*info));
         info->occupied_in_box = (long long)cnt[0];

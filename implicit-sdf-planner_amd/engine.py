@@ -37,6 +37,9 @@ def lbfgs_params(lib, **kw):
     return p
 
 
+_lbfgs_params = lbfgs_params        # (Engine.optimize_lbfgs_checked has an argument of that name)
+
+
 def lbfgs_minimize(fun, x0, lib=None, progress=None, **params):
     """Driver on an arbitrary Python callback fun(x) -> (f, g) (host only; used by the CPU tests).
     progress(x, g, fx, step, k, ls) -> truthy cancels (isdf_lbfgs_minimize_progress: the reference's lbfgs_progress_t)."""
@@ -461,6 +464,13 @@ class Engine:
             self._check(rc)
         return bool(rc)
 
+    def points_merge_check(self, below=None):
+        """Merges the last check's kept points with value < below (None: all of them) into the obstacle-point set on the device: the
+        isdf_points_merge_info fields as a dict.  New points are appended in voxel order; existing ones keep index and lastTstar."""
+        info = capi.IsdfPointsMergeInfo()
+        self._check(self.lib.isdf_points_merge_check(self.h, -1.0 if below is None else float(below), C.byref(info)))
+        return {name: getattr(info, name) for name, _ in capi.IsdfPointsMergeInfo._fields_ if name != "reserved"}
+
     # ---- full objective callback (TrajOptimizer::costFunctionLmbm)
     def set_trajectory(self, N, head_pva, tail_pva, rho):
         """head/tail: 3x3 arrays whose COLUMNS are position, velocity, acceleration (Eigen::Matrix3d of setConditions)."""
@@ -547,6 +557,27 @@ class Engine:
         r = capi.IsdfLbfgsResult()
         self._check(self.lib.isdf_optimize_lbfgs(self.h, _p(x), x.size, C.byref(p), C.byref(r)))
         return x, {"f": r.f, "status": r.status, "iterations": r.iterations, "evaluations": r.evaluations, "wall_ms": r.wall_ms}
+
+    def optimize_lbfgs_checked(self, x0, lbfgs_params=None, max_rounds=4, margin=None, below=None, mode=capi.SWEPT_FIELD_PLANNER):
+        """optimise -> traj_check -> points_merge_check until the check is clear, a merge adds nothing or max_rounds is reached
+        (isdf_optimize_lbfgs_checked).  lbfgs_params: a dict of overrides as optimize_lbfgs takes them.  Returns (x, dict) with
+        "rounds", "clear", "stalled", "M_round" (one entry per round, at most 16), "last_opt" and "last_check" (dicts)."""
+        x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+        p = _lbfgs_params(self.lib, **(lbfgs_params or {}))
+        rp = capi.IsdfRefineParams()
+        self.lib.isdf_refine_params_default(C.byref(rp))
+        rp.max_rounds, rp.mode = int(max_rounds), int(mode)
+        if margin is not None:
+            rp.margin = float(margin)
+        if below is not None:
+            rp.below = float(below)
+        r = capi.IsdfRefineResult()
+        self._check(self.lib.isdf_optimize_lbfgs_checked(self.h, _p(x), x.size, C.byref(p), C.byref(rp), C.byref(r)))
+        self._traj_check_rows = int(r.last_check.n_below_margin)
+        o = r.last_opt
+        return x, {"rounds": r.rounds, "clear": bool(r.clear), "stalled": bool(r.stalled), "M_round": list(r.M_round)[:min(r.rounds, 16)],
+                   "last_opt": {"f": o.f, "status": o.status, "iterations": o.iterations, "evaluations": o.evaluations, "wall_ms": o.wall_ms},
+                   "last_check": self._traj_check_report(r.last_check, None)}
 
     def optimize_lbfgs_batch(self, N, heads, tails, rho, x0s, **params):
         """heads / tails: n_traj x 3 x 3 (columns pos, vel, acc); x0s: n_traj x n.  Returns (xs, [result dicts], wall_ms)."""

@@ -453,6 +453,30 @@ int isdf_traj_check_release(isdf_ctx *ctx);      /* frees the kept rows */
  * (n_penetrating > 0 at the default parameters), 0 = none, negative = isdf_status */
 int isdf_traj_collide(isdf_ctx *ctx, int N, const double *T, const double *coeffs);
 
+/* ---- the clearance report merged into the obstacle-point set ---------------------------------------------------------- */
+/* Where the reference only warns that the optimised trajectory collides (plan_manager.cpp:306-309), the report can be fed back:
+ * the points the last isdf_traj_check* kept (value < its margin), narrowed to value < below (a negative `below`: all of them;
+ * NaN / inf: ISDF_ERR_INVALID_ARG), are merged into the ctx's obstacle-point set on the device.  The set is keyed by
+ * voxel id as the reference's aabb_points is (PCSmap_manager.h:182-216; gathered at plan_manager.cpp:232-254): a row is a
+ * duplicate when ANY point of the set lies in its voxel (getGridIndex of the point, Gridmap3D.cpp:135-175); a point of the set
+ * outside the grid occupies no voxel (n_outside).  Existing points keep their index, their bytes and their lastTstar; the new
+ * ones are APPENDED in ascending voxel index with the report's centre bytes and lastTstar = 0 (plan_manager.cpp:254) - a
+ * tstar_inout array of isdf_eval stays aligned with its first M_before entries.  n_added == 0 changes nothing; otherwise the
+ * set counts as new exactly as after isdf_set_points (the per-point scratch of the V1 step grows at its next step).  The kept
+ * report stays: a second merge finds every row a duplicate.  No point crosses PCIe, two merges from the same state give the
+ * same bytes.  ISDF_ERR_STATE: no kept report (never checked, or released), or the occupancy grid was replaced after the check
+ * (isdf_set_grid / isdf_set_pointcloud: the voxel ids are stale); multi-device ctx: ISDF_ERR_UNSUPPORTED. */
+typedef struct isdf_points_merge_info {
+    int32_t M_before, M_after;   /* size of the ctx's point set before / after                                   */
+    int32_t n_rows;              /* kept report rows considered (value < below)                                   */
+    int32_t n_added;             /* rows appended                                                                 */
+    int32_t n_duplicate;         /* rows whose voxel already holds a point of the set                             */
+    int32_t n_outside;           /* points of the existing set that lie outside the grid (they occupy no voxel)   */
+    int32_t reserved[2];
+    double merge_ms;             /* device time (events on the ctx's stream)                                      */
+} isdf_points_merge_info;
+int isdf_points_merge_check(isdf_ctx *ctx, double below, isdf_points_merge_info *info_out);
+
 /* ---- full objective callback ------------------------------------------------------------------------------ */
 /* TrajOptimizer::costFunctionLmbm (back_end_optimizer.hpp:358-430): x = [tau(N) | inner waypoints 3(N-1)] ->
  * cost, g.  MINCO (minco.hpp:397-655: setParameters, energy and its partials, propogateGrad) and the sweeps: for
@@ -558,6 +582,35 @@ int isdf_lbfgs_minimize_progress(isdf_evaluate_fn evaluate, isdf_progress_fn pro
 int isdf_set_progress(isdf_ctx *ctx, isdf_progress_fn progress, void *instance, size_t batch_instance_stride);
 /* the ctx's own objective: isdf_cost_function */
 int isdf_optimize_lbfgs(isdf_ctx *ctx, double *x_inout, int n, const isdf_lbfgs_params *p, isdf_lbfgs_result *out);
+
+/* Lazy constraint generation around it: the V1 term sees only the ctx's obstacle points - in the reference those
+ * gathered in boxes around the A* waypoints (plan_manager.cpp:232-254, PCSmap_manager.h:182-216) - while the optimised
+ * trajectory is free to leave the boxes, which the reference notices and only reports (plan_manager.cpp:306-309).  Per round:
+ * isdf_optimize_lbfgs from the current x (a negative L-BFGS status does not end the loop: the reference extracts the trajectory
+ * even then, back_end_optimizer.cpp:61-95), isdf_unpack_variables, isdf_traj_check with `margin` and `mode`; nothing below the
+ * margin: clear = 1, stop; else isdf_points_merge_check(below); nothing added: stalled = 1, stop.  At most max_rounds rounds.
+ * The last check's rows stay kept in the ctx.  The point set may start empty (isdf_set_points(ctx, NULL, 0)): the check then
+ * discovers the obstacle points that matter.  V1 ctx only (else ISDF_ERR_UNSUPPORTED); isdf_set_trajectory and an occupancy grid
+ * are needed as the pieces need them. */
+typedef struct isdf_refine_params {
+    int32_t max_rounds;      /* optimise+check rounds, >= 1; default 4                                            */
+    int32_t mode;            /* field mode of the check; default ISDF_SWEPT_FIELD_PLANNER                         */
+    double margin;           /* the check's margin; negative (default) = cfg.safety_hor                           */
+    double below;            /* passed to the merge; negative (default) = every kept row                          */
+} isdf_refine_params;
+typedef struct isdf_refine_result {
+    int32_t rounds;          /* rounds run                                                                        */
+    int32_t clear;           /* 1: the last check found nothing below the margin                                  */
+    int32_t stalled;         /* 1: stopped because a merge added nothing (every offending voxel already a point)  */
+    int32_t reserved;
+    int32_t M_round[16];     /* size of the point set each round optimised with (first 16 rounds)                 */
+    isdf_lbfgs_result last_opt;
+    isdf_traj_check_info last_check;
+} isdf_refine_result;
+void isdf_refine_params_default(isdf_refine_params *p);
+/* rp NULL = defaults */
+int isdf_optimize_lbfgs_checked(isdf_ctx *ctx, double *x_inout, int n, const isdf_lbfgs_params *lp,
+                                const isdf_refine_params *rp, isdf_refine_result *out);
 
 /* A batch of trajectories optimised CONCURRENTLY on the shared map (BASELINE.json configs[2]): trajectory t has its own
  * boundary states heads_pva[9t..], tails_pva[9t..] (3x3 column-major each, like isdf_set_trajectory) and its own
