@@ -85,6 +85,13 @@ class IsdfPlanConfig(C.Structure):
                 ("inputdata", C.c_char * 256), ("pcdmapname", C.c_char * 128)]
 
 
+class IsdfMidendParams(C.Structure):
+    """isdf_midend_params (include/isdf_accel.h): the mid end's weights and its driver's parameters."""
+    _fields_ = [("weight_pr", C.c_double), ("rho_mid_end", C.c_double), ("rel_cost_tol", C.c_double), ("min_step", C.c_double),
+                ("g_epsilon", C.c_double), ("integral_intervs", C.c_int32), ("mem_size", C.c_int32), ("past", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class IsdfLbfgsResult(C.Structure):
     _fields_ = [("f", C.c_double), ("wall_ms", C.c_double), ("status", C.c_int32), ("iterations", C.c_int32),
                 ("evaluations", C.c_int32), ("reserved", C.c_int32)]
@@ -156,6 +163,8 @@ EXPORTED_SYMBOLS = [
     "isdf_swept_mesh_release", "isdf_write_obj", "isdf_traj_check_params_default", "isdf_traj_check", "isdf_traj_check_device",
     "isdf_traj_check_get", "isdf_traj_check_release", "isdf_traj_collide",
     "isdf_points_merge_check", "isdf_refine_params_default", "isdf_optimize_lbfgs_checked",
+    "isdf_midend_params_default", "isdf_load_yaml_midend", "isdf_midend_cost", "isdf_midend_cost_batch", "isdf_midend_fit",
+    "isdf_midend_fit_batch",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -267,6 +276,14 @@ def load_library(path=None):
     lib.isdf_plan_config_default.argtypes = [C.POINTER(IsdfPlanConfig)]
     lib.isdf_plan_config_default.restype = None
     lib.isdf_load_yaml_config.argtypes = [C.c_char_p, C.POINTER(IsdfPlanConfig)]
+    mp = C.POINTER(IsdfMidendParams)
+    lib.isdf_midend_params_default.argtypes = [mp]
+    lib.isdf_midend_params_default.restype = None
+    lib.isdf_load_yaml_midend.argtypes = [C.c_char_p, mp]
+    lib.isdf_midend_cost.argtypes = [C.c_void_p, mp, dp, dp, dp, C.c_int, dp, dp]
+    lib.isdf_midend_cost_batch.argtypes = [C.c_void_p, mp, C.c_int, dp, dp, dp, dp, dp, dp]
+    lib.isdf_midend_fit.argtypes = [C.c_void_p, mp, dp, dp, dp, dp, dp, C.POINTER(IsdfLbfgsResult)]
+    lib.isdf_midend_fit_batch.argtypes = [C.c_void_p, mp, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.POINTER(IsdfLbfgsResult), dp]
     lib.isdf_shape_from_config.argtypes = [C.POINTER(IsdfShape), C.POINTER(IsdfPlanConfig), C.c_char_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
     lib.isdf_swept_sdf.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, C.c_longlong, C.c_int, dp, dp]
     lib.isdf_swept_sdf_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,

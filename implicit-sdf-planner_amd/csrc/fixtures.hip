@@ -260,6 +260,36 @@ extern "C" int isdf_load_yaml_config(const char *path, isdf_plan_config *p) {
     return ISDF_OK;
 }
 
+
+// the mid end's fields of the same files (Config::loadParameters, config.hpp:96-154 -> OriTraj::setParam, mid_end.hpp:310-323, and
+// getOriTraj's driver parameters, mid_end.cpp:48-54)
+extern "C" int isdf_load_yaml_midend(const char *path, isdf_midend_params *p) {
+    if (!path || !p) return ISDF_ERR_INVALID_ARG;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return ISDF_ERR_INVALID_ARG;
+    isdf_midend_params_default(p);
+    char buf[4096];
+    while (std::fgets(buf, sizeof(buf), f)) {
+        std::string line(buf);
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.resize(hash);
+        const size_t colon = line.find(':');
+        if (colon == std::string::npos) continue;
+        const std::string key = trim(line.substr(0, colon)), val = trim(line.substr(colon + 1));
+        if (key.empty() || val.empty()) continue;
+        const double d = std::strtod(val.c_str(), nullptr);
+        if (key == "weight_pr") p->weight_pr = d;
+        else if (key == "rho_mid_end") p->rho_mid_end = d;
+        else if (key == "relCostTolMidEnd") p->rel_cost_tol = d;
+        else if (key == "min_step") p->min_step = d;
+        else if (key == "g_epsilon") p->g_epsilon = d;
+        else if (key == "integralIntervs") p->integral_intervs = (int)d;
+        else if (key == "mem_size") p->mem_size = (int)d;
+        else if (key == "past") p->past = (int)d;
+    }
+    std::fclose(f);
+    return ISDF_OK;
+}
 extern "C" int isdf_shape_from_config(isdf_shape *shape, const isdf_plan_config *p, const char *package_dir, double *V_buf, int capV,
                                       int32_t *F_buf, int capF) {
     if (!shape || !p) return ISDF_ERR_INVALID_ARG;

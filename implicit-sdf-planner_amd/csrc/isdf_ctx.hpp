@@ -3,6 +3,7 @@
 #include "isdf_internal.hpp"
 #include "dev_buf.hpp"
 #include "minco_host.hpp"
+#include "midend_host.hpp"
 #include <chrono>
 #include <cstdlib>
 #include <string>
@@ -134,6 +135,10 @@ struct isdf_ctx {
     PinBuf<double> h_cbres;         // pinned, device-mapped: [x staging | cost, g, parts | flag]
     unsigned long long cb_seq = 0; bool cb_dev = false, cb_post_queued = false; bool cb_ends_dirty = true;
     double cb_ends[18] = {0};
+    // mid end (csrc/midend.hip): the host form's state; the device form's scratch [x | ends | ref | T | coeffs | u | energy block |
+    // penalty block] per trajectory and its pinned, device-mapped hand-over [inputs | cost, g, parts | one flag per trajectory]
+    isdf_host::Midend mid_host;
+    DevBuf<double> d_mid; PinBuf<double> h_mid; unsigned long long mid_seq = 0;
     // front end (csrc/frontend.hip): attitude kernels of the robot, inflated bit-packed occupancy, breadth-first order tables
     struct FrontEnd {
         isdf_frontend_config cfg{}; int xk = 0, yk = 0; double margin = 0.0; bool built = false;

@@ -37,6 +37,16 @@ def lbfgs_params(lib, **kw):
     return p
 
 
+def midend_params(lib, **kw):
+    p = capi.IsdfMidendParams()
+    lib.isdf_midend_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown mid-end parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
 _lbfgs_params = lbfgs_params        # (Engine.optimize_lbfgs_checked has an argument of that name)
 
 
@@ -589,6 +599,59 @@ class Engine:
         res = (capi.IsdfLbfgsResult * n_traj)()
         wall = C.c_double(0)
         self._check(self.lib.isdf_optimize_lbfgs_batch(self.h, n_traj, int(N), _p(h), _p(t), float(rho), _p(x), C.byref(p), res, C.byref(wall)))
+        out = [{"f": r.f, "status": r.status, "iterations": r.iterations, "evaluations": r.evaluations, "rounds": r.reserved} for r in res]
+        return x, out, wall.value
+
+    # ---- mid end (OriTraj::getOriTraj: the MINCO fit to the front end's waypoints, whose x the back end starts from)
+    def midend_params(self, **kw):
+        """isdf_midend_params_default with overrides (weight_pr, rho_mid_end, rel_cost_tol, min_step, g_epsilon, integral_intervs,
+        mem_size, past)."""
+        return midend_params(self.lib, **kw)
+
+    def midend_cost(self, ref_points, x, params=None):
+        """ref_points: (N-1) x 3.  Returns (cost, g, {"energy", "pose", "time"}) - isdf_midend_cost on isdf_set_trajectory's ends."""
+        p = params or midend_params(self.lib)
+        R = np.ascontiguousarray(np.asarray(ref_points, dtype=np.float64).reshape(-1))
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        g = np.zeros_like(x); parts = np.zeros(3); cost = C.c_double(0)
+        self._check(self.lib.isdf_midend_cost(self.h, C.byref(p), _p(R), _p(x), _p(g), x.size, C.byref(cost), _p(parts)))
+        return cost.value, g, {"energy": parts[0], "pose": parts[1], "time": parts[2]}
+
+    def midend_cost_batch(self, heads, tails, ref_points, xs, params=None):
+        """heads / tails: nb x 3 x 3 (columns pos, vel, acc); ref_points: nb x (N-1) x 3; xs: nb x n.  Returns (costs, gs)."""
+        p = params or midend_params(self.lib)
+        x = np.ascontiguousarray(xs, dtype=np.float64)
+        nb = x.shape[0]
+        h = np.ascontiguousarray(np.asarray(heads, dtype=np.float64).transpose(0, 2, 1)).reshape(-1)
+        t = np.ascontiguousarray(np.asarray(tails, dtype=np.float64).transpose(0, 2, 1)).reshape(-1)
+        R = np.ascontiguousarray(np.asarray(ref_points, dtype=np.float64).reshape(-1))
+        g = np.zeros_like(x); cost = np.zeros(nb)
+        self._check(self.lib.isdf_midend_cost_batch(self.h, C.byref(p), nb, _p(h), _p(t), _p(R), _p(x), _p(g), _p(cost)))
+        return cost, g
+
+    def midend_fit(self, ref_points, T_init, params=None):
+        """Returns (x, T, coeffs 18N column-major, result dict); x is isdf_optimize_lbfgs's start (isdf_midend_fit)."""
+        p = params or midend_params(self.lib)
+        R = np.ascontiguousarray(np.asarray(ref_points, dtype=np.float64).reshape(-1))
+        T0 = np.ascontiguousarray(T_init, dtype=np.float64)
+        N = T0.size
+        x = np.zeros(N + 3 * (N - 1)); T = np.zeros(N); cm = np.zeros(18 * N)
+        r = capi.IsdfLbfgsResult()
+        self._check(self.lib.isdf_midend_fit(self.h, C.byref(p), _p(R), _p(T0), _p(x), _p(T), _p(cm), C.byref(r)))
+        return x, T, cm, {"f": r.f, "status": r.status, "iterations": r.iterations, "evaluations": r.evaluations, "wall_ms": r.wall_ms}
+
+    def midend_fit_batch(self, heads, tails, ref_points, T_inits, params=None):
+        """heads / tails: nb x 3 x 3; ref_points: nb x (N-1) x 3; T_inits: nb x N.  Returns (xs, [result dicts], wall_ms)."""
+        p = params or midend_params(self.lib)
+        T0 = np.ascontiguousarray(T_inits, dtype=np.float64)
+        nb, N = T0.shape
+        h = np.ascontiguousarray(np.asarray(heads, dtype=np.float64).transpose(0, 2, 1)).reshape(-1)
+        t = np.ascontiguousarray(np.asarray(tails, dtype=np.float64).transpose(0, 2, 1)).reshape(-1)
+        R = np.ascontiguousarray(np.asarray(ref_points, dtype=np.float64).reshape(-1))
+        x = np.zeros((nb, N + 3 * (N - 1)))
+        res = (capi.IsdfLbfgsResult * nb)()
+        wall = C.c_double(0)
+        self._check(self.lib.isdf_midend_fit_batch(self.h, C.byref(p), nb, N, _p(h), _p(t), _p(R), _p(T0), _p(x), res, C.byref(wall)))
         out = [{"f": r.f, "status": r.status, "iterations": r.iterations, "evaluations": r.evaluations, "rounds": r.reserved} for r in res]
         return x, out, wall.value
 

@@ -628,6 +628,57 @@ int isdf_optimize_lbfgs_checked(isdf_ctx *ctx, double *x_inout, int n, const isd
 int isdf_optimize_lbfgs_batch(isdf_ctx *ctx, int n_traj, int N, const double *heads_pva, const double *tails_pva, double rho,
                               double *x_inout, const isdf_lbfgs_params *p, isdf_lbfgs_result *results, double *wall_ms_out);
 
+/* ---- mid end: the MINCO fit to the front end's waypoints ------------------------------------------------------------ */
+/* OriTraj (src/planner_algorithm/include/planner_algorithm/mid_end.hpp, src/planner_algorithm/src/mid_end.cpp): between the A*
+ * and the back end the reference fits a MINCO trajectory to the path's waypoints and starts the back end from the result
+ * (plan_manager.cpp:202-313, opt_x at :270,289).  Variables x = [tau(N) | inner waypoints 3(N-1), point-major] - the layout of
+ * isdf_pack_variables, so the fit's x goes straight into isdf_optimize_lbfgs.  cost = MINCO jerk energy + weight_pr * sum(pose
+ * penalty) + rho_mid_end * sum(T) (mid_end.hpp:262-304); constraint i (0 .. N-2) samples PIECE i+1 at T(i+1) / integral_intervs
+ * (:228-247), cost_p = |pos - ref_i|^3 (:184-199), and the time gradient of the penalty carries the reference's extra factor cost_p
+ * (:256).  The reference stores attitudes and accelerations (:41-43) and never reads them: there is no attitude term.
+ * The boundary states are isdf_set_trajectory's (its rho is not used here); no grid, shape or points are needed, on a ctx of any
+ * variant.  isdf_set_minco_mode picks the form as for the back end: 1 = host (csrc/midend_host.hpp: the reference's arithmetic on
+ * the band LU), 2 = device (csrc/midend.hip: the whole callback in ONE launch, one workgroup per trajectory), 0 = host for a single
+ * trajectory of <= 64 pieces, device otherwise and for every batch; more than 400 pieces always take the host.  isdf_minco_path
+ * tells which form ran.  N < 2: ISDF_ERR_INVALID_ARG (the reference always has a waypoint, plan_manager.cpp:209-213); a
+ * multi-device ctx: ISDF_ERR_UNSUPPORTED. */
+typedef struct isdf_midend_params {
+    double weight_pr;            /* weight_pr: 1000                                                                   */
+    double rho_mid_end;          /* rho_mid_end: 200                                                                  */
+    double rel_cost_tol;         /* relCostTolMidEnd -> the driver's delta (mid_end.cpp:54): 1e-6                     */
+    double min_step, g_epsilon;  /* min_step 1e-32, g_epsilon 0 (mid_end.cpp:51-52)                                   */
+    int32_t integral_intervs;    /* integralIntervs (mid_end.hpp:323); default: isdf_config_default's                 */
+    int32_t mem_size, past;      /* mem_size 16, past 10 (mid_end.cpp:49-50)                                          */
+    int32_t reserved;
+} isdf_midend_params;
+void isdf_midend_params_default(isdf_midend_params *p);
+/* the same fields from a plan yaml of src/plan_manager/config (Config::loadParameters, config.hpp:96-154); what the file leaves
+ * out keeps isdf_midend_params_default's value */
+int isdf_load_yaml_midend(const char *yaml_path, isdf_midend_params *out);
+/* OriTraj::costFunction (mid_end.hpp:262-304) at x: ref_points (N-1) x 3 point-major, g: n = N + 3(N-1), parts_out (nullable):
+ * energy | weight_pr * sum(pose penalty) | rho_mid_end * sum(T). */
+int isdf_midend_cost(isdf_ctx *ctx, const isdf_midend_params *params, const double *ref_points, const double *x, double *g, int n,
+                     double *cost_out, double parts_out[3]);
+/* ... of nb trajectories of isdf_set_trajectory's N pieces, each with its own boundary states (heads_pva / tails_pva: 9 doubles per
+ * trajectory, like isdf_optimize_lbfgs_batch), ref_points [nb][(N-1) x 3], x and g [nb][n], cost_out [nb]: one launch, one workgroup
+ * per trajectory; every row is bitwise what isdf_midend_cost returns for it alone in device mode. */
+int isdf_midend_cost_batch(isdf_ctx *ctx, const isdf_midend_params *params, int nb, const double *heads_pva, const double *tails_pva,
+                           const double *ref_points, const double *x, double *g, double *cost_out);
+/* OriTraj::getOriTraj (mid_end.cpp:3-94): x seeded with tau = backwardT(T_init), xi = ref_points (:27-41), then the L-BFGS driver
+ * with mem_size, past, min_step, g_epsilon, max_iterations = 100000 and delta = rel_cost_tol (:48-62) and the hook of
+ * isdf_set_progress.  x_out (n) is the last iterate and is written whatever out->status says, as the reference extracts the
+ * trajectory either way (:65-92); T_out (N) and coeffs_out (6N x 3 column-major), either nullable, are forwardT and setParameters
+ * of it (:67-71). */
+int isdf_midend_fit(isdf_ctx *ctx, const isdf_midend_params *params, const double *ref_points, const double *T_init, double *x_out,
+                    double *T_out, double *coeffs_out, isdf_lbfgs_result *out);
+/* nb fits of N pieces each (T_init [nb][N], x_out [nb][n]), one host thread per trajectory (ISDF_BATCH_THREADS caps the live ones); a
+ * round starts when every live trajectory waits for its callback and is ONE launch with one workgroup per live trajectory.  The
+ * iterates are bit for bit those of isdf_midend_fit on each trajectory alone in device mode.  The hook of isdf_set_progress is
+ * called per trajectory as in isdf_optimize_lbfgs_batch; results[t].reserved = rounds of the whole batch.  Needs no
+ * isdf_set_trajectory. */
+int isdf_midend_fit_batch(isdf_ctx *ctx, const isdf_midend_params *params, int nb, int N, const double *heads_pva, const double *tails_pva,
+                          const double *ref_points, const double *T_init, double *x_out, isdf_lbfgs_result *results, double *wall_ms_out);
+
 /* ---- front end: pose feasibility by kernel convolution ------------------------------------- */
 /* The A* front end decides whether the robot fits at a voxel by AND-ing a bit-packed voxelisation of the robot at a
  * (roll, pitch) attitude against the bit-packed occupancy map, trying attitudes breadth-first from the parent's
