@@ -165,6 +165,7 @@ EXPORTED_SYMBOLS = [
     "isdf_points_merge_check", "isdf_refine_params_default", "isdf_optimize_lbfgs_checked",
     "isdf_midend_params_default", "isdf_load_yaml_midend", "isdf_midend_cost", "isdf_midend_cost_batch", "isdf_midend_fit",
     "isdf_midend_fit_batch",
+    "isdf_set_shape_program", "isdf_shape_program_eval_host", "isdf_shape_program_validate",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -173,6 +174,20 @@ MULTI_NONE, MULTI_PEER_SUM, MULTI_STAGED, MULTI_RCCL = 0, 1, 2, 3
 
 SDF_WITH_GRAD_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double))   # isdf_sdf_with_grad_fn
 SHAPE_GRID, GRAD_GRID = 16, 4
+SHAPE_PROGRAM = 17
+PROGRAM_MAX_INSTR, PROGRAM_MAX_DEPTH = 64, 8
+
+
+class IsdfShapeInstr(C.Structure):      # isdf_shape_instr
+    _fields_ = [("op", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 9)]
+
+
+# isdf_shape_op
+(OP_SPHERE, OP_CAPSULE, OP_BOX, OP_ROUNDED_BOX, OP_WIREFRAME_BOX, OP_TORUS, OP_CYLINDER, OP_CAPPED_CYLINDER, OP_ROUNDED_CYLINDER,
+ OP_CAPPED_CONE, OP_ROUNDED_CONE, OP_ELLIPSOID, OP_PYRAMID, OP_TETRAHEDRON, OP_OCTAHEDRON, OP_DODECAHEDRON, OP_ICOSAHEDRON) = range(1, 18)
+OP_TRANSLATE, OP_SCALE, OP_ROTATE, OP_ROTATE_TO, OP_TWIST, OP_BEND = range(32, 38)
+OP_MUL, OP_NEGATE, OP_DILATE, OP_ERODE, OP_SHELL = range(48, 53)
+OP_UNION, OP_DIFFERENCE, OP_INTERSECTION, OP_BLEND = range(64, 68)
 
 _lib = None
 
@@ -203,6 +218,10 @@ def load_library(path=None):
     lib.isdf_set_points.argtypes = [C.c_void_p, dp, C.c_int]
     lib.isdf_set_shape_grid.argtypes = [C.c_void_p, dp, C.c_int, C.c_int, C.c_int, dp, C.c_double, C.c_double, dp, dp]
     lib.isdf_set_shape_sampled.argtypes = [C.c_void_p, SDF_WITH_GRAD_FN, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, dp, dp]
+    ins = C.POINTER(IsdfShapeInstr)
+    lib.isdf_set_shape_program.argtypes = [C.c_void_p, ins, C.c_int, dp, dp, C.c_double, dp, dp]
+    lib.isdf_shape_program_eval_host.argtypes = [ins, C.c_int, dp, dp, dp, C.c_longlong, dp, dp]
+    lib.isdf_shape_program_validate.argtypes = [ins, C.c_int, C.c_char_p, C.c_int]
     lib.isdf_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.isdf_eval.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(dp), C.POINTER(dp), dp,
                               C.POINTER(dp), C.POINTER(dp), dp]

@@ -80,6 +80,9 @@ struct DevShape {
     const double *grid;
     int gn[3];
     double gres, gmin[3];
+    // ISDF_SHAPE_PROGRAM: the lowered instruction list in device memory (dev_shape_program.hpp; d.trans / d.rot: its body offset)
+    const isdf_shape_instr *prog;
+    int prog_n;
 };
 
 template <typename T> __device__ __forceinline__ T clipT(T v, T lo, T hi) { return m_max(m_min(v, hi), lo); }
@@ -304,6 +307,10 @@ __device__ __forceinline__ d3 grid_grad(const DevShape &S, d3 p) {
     return c.inside ? grid_gradient(S, c) : mk3(0, 0, 0);
 }
 
+} // namespace isdf
+#include "dev_shape_program.hpp"      // prog_sdf: the interpreter of ISDF_SHAPE_PROGRAM
+namespace isdf {
+
 __device__ double mesh_sdf(const DevMesh *m, d3 p);              // dev_mesh.hpp
 __device__ double mesh_sdf_grad(const DevMesh *m, d3 p, d3 &g);  // dev_mesh.hpp
 
@@ -311,6 +318,7 @@ __device__ double mesh_sdf_grad(const DevMesh *m, d3 p, d3 &g);  // dev_mesh.hpp
 template <int KIND, bool IDENT = false>
 __device__ __forceinline__ double shape_sdf(const DevShape &S, d3 pr) {
     if constexpr (KIND == ISDF_SHAPE_MESH) return mesh_sdf(S.mesh, pr);     // the mesh kind has its own instantiation
+    else if constexpr (KIND == ISDF_SHAPE_PROGRAM) return prog_sdf(S, body_offset<IDENT>(S.d, pr));      // ... and so has the program kind
     else {
         if constexpr (KIND < 0) if (S.kind == ISDF_SHAPE_GRID) return grid_sdf(S, pr);      // (run-time kinds: Ball, sampled grid)
         return analytic_sdf<KIND, double, IDENT>(S.d, S.kind, pr);
@@ -324,6 +332,9 @@ template <int KIND>
 __device__ __forceinline__ double shape_sdf_rotated(const DevShape &S, d3 pos, const double *Ro) {
     if constexpr (KIND == ISDF_SHAPE_MESH) {
         return mesh_sdf(S.mesh, mk3(pos.x * Ro[0] + pos.y * Ro[3] + pos.z * Ro[6], pos.x * Ro[1] + pos.y * Ro[4] + pos.z * Ro[7], pos.x * Ro[2] + pos.y * Ro[5] + pos.z * Ro[8]));
+    } else if constexpr (KIND == ISDF_SHAPE_PROGRAM) {      // offset, then R_obj, then the program
+        const d3 q = body_offset(S.d, pos);
+        return prog_sdf(S, mk3(q.x * Ro[0] + q.y * Ro[3] + q.z * Ro[6], q.x * Ro[1] + q.y * Ro[4] + q.z * Ro[7], q.x * Ro[2] + q.y * Ro[5] + q.z * Ro[8]));
     } else {
         if (S.kind == ISDF_SHAPE_BALL) return norm3(pos) - S.d.p[0];
         if constexpr (KIND < 0) if (S.kind == ISDF_SHAPE_GRID)       // the lattice holds the shape incl. its body offset: sampled at pos * R_obj
@@ -338,6 +349,25 @@ __device__ __forceinline__ double shape_sdf_rotated(const DevShape &S, d3 pos, c
 template <int KIND, bool IDENT = false>
 __device__ __forceinline__ d3 shape_grad(const DevShape &S, d3 pr) {
     if constexpr (KIND == ISDF_SHAPE_MESH) { d3 g; mesh_sdf_grad(S.mesh, pr, g); return g; }
+    if constexpr (KIND == ISDF_SHAPE_PROGRAM) {
+        // always the central difference (a program is an exact analytic expression); the six evaluations as ONE loop around the
+        // interpreter instead of six copies of it: the same operands in the same order as the code below
+        const double dx = 0.000005;
+        double gx = 0.0, gy = 0.0, gz = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < 6; k++) {       // (k wave-uniform: the selects below are scalar)
+            const int a = k >> 1;
+            const double c = a == 0 ? pr.x : (a == 1 ? pr.y : pr.z), lo = c - dx, t = (k & 1) ? lo : lo + 2 * dx;
+            const double v = shape_sdf<KIND, IDENT>(S, mk3(a == 0 ? t : pr.x, a == 1 ? t : pr.y, a == 2 ? t : pr.z));
+            const double g = a == 0 ? gx : (a == 1 ? gy : gz), r = (k & 1) ? g - v : v;
+            gx = a == 0 ? r : gx; gy = a == 1 ? r : gy; gz = a == 2 ? r : gz;
+        }
+#ifdef ISDF_LEAN_MATH
+        return normalized3_lean(mk3(gx, gy, gz));
+#else
+        return normalized3(mk3(gx / (2 * dx), gy / (2 * dx), gz / (2 * dx)));
+#endif
+    }
     const int mode = S.grad_mode;   // resolved (never DEFAULT) by the host
     if (mode == ISDF_GRAD_ANALYTIC_BALL) return normalized3(pr);
     if constexpr (KIND < 0) if (mode == ISDF_GRAD_GRID) return grid_grad(S, pr);

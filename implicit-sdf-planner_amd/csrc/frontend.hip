@@ -314,6 +314,7 @@ extern "C" int isdf_frontend_build(isdf_ctx *c, const isdf_frontend_config *cfg)
     {
         const dim3 grid((unsigned)((n_rows + 255) / 256)), block(256);
         if (c->shape.kind == ISDF_SHAPE_MESH) hipLaunchKernelGGL(fe_shape_rows_kernel<ISDF_SHAPE_MESH>, grid, block, 0, c->stream, c->shape, F, fe.d_rot, fe.d_rows);
+        else if (c->shape.kind == ISDF_SHAPE_PROGRAM) hipLaunchKernelGGL(fe_shape_rows_kernel<ISDF_SHAPE_PROGRAM>, grid, block, 0, c->stream, c->shape, F, fe.d_rot, fe.d_rows);
         else hipLaunchKernelGGL(fe_shape_rows_kernel<-1>, grid, block, 0, c->stream, c->shape, F, fe.d_rot, fe.d_rows);
         HIPCHK(c, hipGetLastError());
     }

@@ -64,6 +64,7 @@ struct isdf_ctx {
     DevBuf<int> d_mesh_flat;             // the flat slot table of a small mesh (DevMesh::flat)
     DevBuf<float> d_mesh_dl;             // the mesh kind's distance lattice (DevMesh::dl)
     DevBuf<double> d_shape_grid;         // ISDF_SHAPE_GRID: the sampled lattice
+    DevBuf<isdf_shape_instr> d_shape_prog;       // ISDF_SHAPE_PROGRAM: the lowered instruction list (DevShape::prog)
     DevBuf<void> d_pose;                 // pose records of a non-fused integral step (bytes)
     // points (V1)
     DevBuf<double> d_points;

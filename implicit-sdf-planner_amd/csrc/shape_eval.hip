@@ -185,6 +185,7 @@ extern "C" int isdf_shape_eval(isdf_ctx *c, const double *p_rel, int n, double *
     if (rc == ISDF_OK) {
         const dim3 grid((n + 255) / 256), block(256);
         if (c->shape.kind == ISDF_SHAPE_MESH) hipLaunchKernelGGL(isdf::shape_eval_kernel<ISDF_SHAPE_MESH>, grid, block, 0, c->stream, c->shape, d_p, n, sdf_out ? d_s : nullptr, grad_out ? d_g : nullptr);
+        else if (c->shape.kind == ISDF_SHAPE_PROGRAM) hipLaunchKernelGGL(isdf::shape_eval_kernel<ISDF_SHAPE_PROGRAM>, grid, block, 0, c->stream, c->shape, d_p, n, sdf_out ? d_s : nullptr, grad_out ? d_g : nullptr);
         else hipLaunchKernelGGL(isdf::shape_eval_kernel<-1>, grid, block, 0, c->stream, c->shape, d_p, n, sdf_out ? d_s : nullptr, grad_out ? d_g : nullptr);
         chk(hipGetLastError(), "shape_eval_kernel");
     }

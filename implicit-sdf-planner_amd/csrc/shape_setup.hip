@@ -1,7 +1,8 @@
 // Robot-shape setup of the C ABI: the analytic-shape registry, isdf_set_shape (mesh robots: hierarchy, device tables, form of the
-// sweep, distance lattice), the sampled-lattice kind.
+// sweep, distance lattice), the sampled-lattice kind, the program kind (a composition from the CSG class's op library).
 #include "isdf_ctx.hpp"
 #include "mesh_tables.hpp"
+#include "shape_program_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -276,6 +277,7 @@ extern "C" int isdf_set_shape(isdf_ctx *c, const isdf_shape *s) {
     if (!s || s->kind < 0 || s->kind >= ISDF_SHAPE_KIND_COUNT) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad shape kind");
     if (s->grad_mode < ISDF_GRAD_DEFAULT || s->grad_mode > ISDF_GRAD_ANALYTIC_BALL) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad grad_mode");
     if (s->kind == ISDF_SHAPE_GRID) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "ISDF_SHAPE_GRID is installed with isdf_set_shape_grid / isdf_set_shape_sampled");
+    if (s->kind == ISDF_SHAPE_PROGRAM) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "ISDF_SHAPE_PROGRAM is installed with isdf_set_shape_program");
     HIPCHK(c, hipSetDevice(c->device));
     DevShape d{};
     double bb_c[3], bb_h[3];
@@ -283,6 +285,7 @@ extern "C" int isdf_set_shape(isdf_ctx *c, const isdf_shape *s) {
     if (s->kind == ISDF_SHAPE_MESH) { const int rc = install_mesh(c, s, d, bb_h); if (rc) return rc; }
     if (s->kind != ISDF_SHAPE_MESH) std::memset(c->mesh_info, 0, sizeof(c->mesh_info));
     isdf_frontend_release(c);       // the attitude kernels were voxelised from the previous shape
+    c->d_shape_prog.release();
     c->shape = d;
     c->mesh_rmax = 0.0;
     if (s->kind == ISDF_SHAPE_MESH)
@@ -333,6 +336,7 @@ extern "C" int isdf_set_shape_grid(isdf_ctx *c, const double *cells, int nx, int
     d.filter_f32 = 0;                      // no fp32 formula to pre-filter with
     d.mesh = nullptr;
     isdf_frontend_release(c);
+    c->d_shape_prog.release();
     c->shape = d;
     c->shape_host = isdf_shape{};
     c->shape_host.kind = ISDF_SHAPE_GRID; c->shape_host.grad_mode = ISDF_GRAD_GRID;
@@ -361,6 +365,70 @@ extern "C" int isdf_set_shape_sampled(isdf_ctx *c, isdf_sdf_with_grad_fn fn, voi
                 o[0] = g[0]; o[1] = g[1]; o[2] = g[2]; o[3] = dis;
             }
     return isdf_set_shape_grid(c, cells.data(), X, Y, Z, mn, nres, bound_radius, bbox_center, bbox_half);
+}
+
+// ---- ISDF_SHAPE_PROGRAM: a composition from the op library of the reference's CSG class (Shape.hpp:1684-2317) as an instruction
+// list the device interprets (dev_shape_program.hpp).  Validated and lowered on the host (shape_program_host.hpp) before the ctx
+// is touched: a rejected program leaves the installed shape as it was.
+extern "C" int isdf_set_shape_program(isdf_ctx *c, const isdf_shape_instr *instr, int n, const double *trans, const double *rotate,
+                                      double bound_radius, const double *bbox_center, const double *bbox_half) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    std::vector<isdf_shape_instr> low;
+    {
+        std::string why;
+        if (isdf_host::prog_lower(instr, n, low, why) != ISDF_OK) return isdf_fail(c, ISDF_ERR_INVALID_ARG, why.c_str());
+    }
+    bool finite = std::isfinite(bound_radius) && bound_radius >= 0;
+    for (int i = 0; i < 3; i++) finite = finite && (!trans || std::isfinite(trans[i])) && (!bbox_center || std::isfinite(bbox_center[i])) && (!bbox_half || std::isfinite(bbox_half[i]));
+    for (int i = 0; i < 9; i++) finite = finite && (!rotate || std::isfinite(rotate[i]));
+    if (!finite) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "shape program: non-finite body offset or bound");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the instructions first, into a buffer of their own: a failure up to here leaves the installed shape usable
+    DevBuf<isdf_shape_instr> d_prog;
+    HIPCHK(c, d_prog.alloc(std::max<size_t>(low.size(), 1)));
+    if (!low.empty()) HIPCHK(c, hipMemcpy(d_prog, low.data(), low.size() * sizeof(isdf_shape_instr), hipMemcpyHostToDevice));
+    isdf_shape s;
+    shape_identity(&s, ISDF_SHAPE_PROGRAM);
+    s.grad_mode = ISDF_GRAD_CENTRAL;
+    if (trans) std::memcpy(s.trans, trans, sizeof(s.trans));
+    if (rotate) std::memcpy(s.rotate, rotate, sizeof(s.rotate));
+    s.bound_radius = bound_radius;
+    if (bbox_center) std::memcpy(s.bbox_center, bbox_center, sizeof(s.bbox_center));
+    if (bbox_half) std::memcpy(s.bbox_half, bbox_half, sizeof(s.bbox_half));
+    DevShape d{};
+    double bb_c[3], bb_h[3];
+    fill_dev_shape(&s, d, bb_c, bb_h);
+    d.filter_f32 = 0;               // no float instantiation of the interpreter (yet): every listed voxel goes to the exact pass
+    std::memset(c->mesh_info, 0, sizeof(c->mesh_info));
+    isdf_frontend_release(c);
+    c->d_shape_prog = std::move(d_prog);
+    d.prog = c->d_shape_prog; d.prog_n = (int)low.size();
+    c->shape = d;
+    c->mesh_rmax = 0.0;
+    c->shape_host = s;
+    c->have_shape = true;
+    ISDF_REPLICATE(c, isdf_set_shape_program(p_, instr, n, trans, rotate, bound_radius, bbox_center, bbox_half));
+    return ISDF_OK;
+}
+extern "C" int isdf_shape_program_validate(const isdf_shape_instr *instr, int n, char *err_out, int err_cap) {
+    std::vector<isdf_shape_instr> low;
+    std::string why;
+    const int rc = isdf_host::prog_lower(instr, n, low, why);
+    if (err_out && err_cap > 0) { std::strncpy(err_out, why.c_str(), (size_t)err_cap - 1); err_out[err_cap - 1] = 0; }
+    return rc;
+}
+extern "C" int isdf_shape_program_eval_host(const isdf_shape_instr *instr, int n, const double *trans, const double *rotate,
+                                            const double *xyz, long long n_points, double *sdf_out, double *grad_out) {
+    if (n_points < 0 || (n_points > 0 && !xyz)) return ISDF_ERR_INVALID_ARG;
+    std::vector<isdf_shape_instr> low;
+    std::string why;
+    if (isdf_host::prog_lower(instr, n, low, why) != ISDF_OK) return ISDF_ERR_INVALID_ARG;
+    const isdf_host::ProgBody B = isdf_host::prog_body(trans, rotate);
+    for (long long i = 0; i < n_points; i++) {
+        if (sdf_out) sdf_out[i] = isdf_host::prog_sdf(low.data(), (int)low.size(), B, xyz + 3 * i);
+        if (grad_out) isdf_host::prog_grad(low.data(), (int)low.size(), B, xyz + 3 * i, grad_out + 3 * i);
+    }
+    return ISDF_OK;
 }
 
 extern "C" int isdf_mesh_info(const isdf_ctx *c, int info_out[16]) {

@@ -1287,6 +1287,7 @@ static void launch_swept_sweep_impl(const SweptParams &P, hipStream_t stream, hi
     ISDF_SWEPT_CASE(ISDF_SHAPE_TWISTBOX) ISDF_SWEPT_CASE(ISDF_SHAPE_BENDBOX) ISDF_SWEPT_CASE(ISDF_SHAPE_TABLE)
     ISDF_SWEPT_CASE(ISDF_SHAPE_TREFOIL) ISDF_SWEPT_CASE(ISDF_SHAPE_SMOOTHDIFFERENCE) ISDF_SWEPT_CASE(ISDF_SHAPE_SMOOTHINTERSECTION)
     ISDF_SWEPT_CASE(ISDF_SHAPE_CSG) ISDF_SWEPT_CASE(ISDF_SHAPE_BOX) ISDF_SWEPT_CASE(ISDF_SHAPE_MESH)
+    ISDF_SWEPT_CASE(ISDF_SHAPE_PROGRAM)
     default: ISDF_SWEPT_CASE(-1)      // Ball
     }
 #undef ISDF_SWEPT_CASE
@@ -1310,6 +1311,7 @@ void launch_swept_fixed(const SweptParams &P, const double *tstar_in, hipStream_
     ISDF_FIXED_CASE(ISDF_SHAPE_TWISTBOX) ISDF_FIXED_CASE(ISDF_SHAPE_BENDBOX) ISDF_FIXED_CASE(ISDF_SHAPE_TABLE)
     ISDF_FIXED_CASE(ISDF_SHAPE_TREFOIL) ISDF_FIXED_CASE(ISDF_SHAPE_SMOOTHDIFFERENCE) ISDF_FIXED_CASE(ISDF_SHAPE_SMOOTHINTERSECTION)
     ISDF_FIXED_CASE(ISDF_SHAPE_CSG) ISDF_FIXED_CASE(ISDF_SHAPE_BOX) ISDF_FIXED_CASE(ISDF_SHAPE_MESH)
+    ISDF_FIXED_CASE(ISDF_SHAPE_PROGRAM)
     default: hipLaunchKernelGGL(swept_fixed_kernel<-1>, grid, block, 0, stream, P, tstar_in); break;
     }
 #undef ISDF_FIXED_CASE

@@ -315,7 +315,7 @@ constexpr int sweep_waves_per_simd(int kind, bool ident) {
     case ISDF_SHAPE_BOX: return ident ? 6 : 4;      // 86 registers as it was: one more than a sixth wave allows - held to 85, the batch gains 6 %
     case ISDF_SHAPE_CAPPEDCONE: case ISDF_SHAPE_WIREFRAMEBOX: return 4;
     case ISDF_SHAPE_TWISTBOX: case ISDF_SHAPE_BENDBOX: case ISDF_SHAPE_TABLE: case ISDF_SHAPE_TREFOIL: case ISDF_SHAPE_CSG: return ident ? 4 : 3;
-    default: return 3;      // mesh, generic
+    default: return 3;      // mesh, generic, program (ISDF_SHAPE_PROGRAM: the interpreter's formulas together are larger than any class)
     }
 }
 
@@ -1714,6 +1714,7 @@ void launch_sweep(const SweepParams &P0, hipStream_t stream, hipEvent_t ev_start
     ISDF_SWEEP_CASE(ISDF_SHAPE_TWISTBOX) ISDF_SWEEP_CASE(ISDF_SHAPE_BENDBOX) ISDF_SWEEP_CASE(ISDF_SHAPE_TABLE)
     ISDF_SWEEP_CASE(ISDF_SHAPE_TREFOIL) ISDF_SWEEP_CASE(ISDF_SHAPE_SMOOTHDIFFERENCE) ISDF_SWEEP_CASE(ISDF_SHAPE_SMOOTHINTERSECTION)
     ISDF_SWEEP_CASE(ISDF_SHAPE_CSG) ISDF_SWEEP_CASE(ISDF_SHAPE_BOX)
+    ISDF_SWEEP_CASE(ISDF_SHAPE_PROGRAM)      // the interpreter (dev_shape_program.hpp): fused / identity offset / general like a class
     case ISDF_SHAPE_MESH:
         if (P.mq_items) {      // scan launch -> queue -> exact launch -> per-sample sums (the events span the three)
             hipExtLaunchKernelGGL((sweep_kernel<ISDF_SHAPE_MESH, false, false>), grid, block, 0, stream, ev_start, nullptr, 0, P);

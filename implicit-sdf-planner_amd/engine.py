@@ -146,6 +146,19 @@ class Engine:
         self._check(self.lib.isdf_set_shape_grid(self.h, _p(cells), nx, ny, nz, _p(gm), float(nres), float(bound_radius),
                                                  None if bc is None else _p(bc), None if bh is None else _p(bh)))
 
+    def set_shape_program(self, program, trans=None, rotate=None, bound_radius=0.0, bbox=None):
+        """ISDF_SHAPE_PROGRAM: a composition from the reference's CSG op library.  program: a csg expression tree (compiled
+        here) or an instruction array from csg.compile(); trans / rotate: the body offset (p - trans) * Rotate; bbox = (centre, half)."""
+        from . import csg
+        instr = csg.compile(program) if isinstance(program, csg.Node) else program
+        tr = None if trans is None else np.ascontiguousarray(trans, dtype=np.float64).reshape(3)
+        ro = None if rotate is None else np.ascontiguousarray(rotate, dtype=np.float64).reshape(9)
+        bc = bh = None
+        if bbox is not None:
+            bc = np.ascontiguousarray(bbox[0], dtype=np.float64); bh = np.ascontiguousarray(bbox[1], dtype=np.float64)
+        opt = lambda a: None if a is None else _p(a)
+        self._check(self.lib.isdf_set_shape_program(self.h, instr, csg._n(instr), opt(tr), opt(ro), float(bound_radius), opt(bc), opt(bh)))
+
     def set_shape_sampled(self, fn, nd, nres, bound_radius=0.0):
         """fn(p[3]) -> (distance, gradient[3]): any host shape's getSDFwithGrad1; tabulated like BasicShape::initShape."""
         def tramp(_u, pp, gp):

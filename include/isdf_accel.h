@@ -88,7 +88,8 @@ typedef enum isdf_shape_kind {
     ISDF_SHAPE_BALL = 14,
     ISDF_SHAPE_MESH = 15,
     ISDF_SHAPE_GRID = 16,   /* a body-frame lattice of (unit gradient, distance) sampled from ANY host shape: isdf_set_shape_grid */
-    ISDF_SHAPE_KIND_COUNT = 17
+    ISDF_SHAPE_PROGRAM = 17,/* a composition from the CSG class's op library (Shape.hpp:1684-2317) as an instruction list: isdf_set_shape_program */
+    ISDF_SHAPE_KIND_COUNT = 18
 } isdf_shape_kind;
 
 /* How getonlyGrad1 / getSDFwithGrad1 form the body-frame gradient. */
@@ -219,6 +220,66 @@ int isdf_set_shape_grid(isdf_ctx *ctx, const double *cells, int nx, int ny, int 
                         double bound_radius, const double *bbox_center, const double *bbox_half);
 int isdf_set_shape_sampled(isdf_ctx *ctx, isdf_sdf_with_grad_fn fn, void *user, double ndx, double ndy, double ndz, double nres,
                            double bound_radius, const double *bbox_center, const double *bbox_half);
+
+/* ---- composed robot shapes: the op library of the reference's CSG class (Shape.hpp:1684-2317) as a device program --------
+ * A reference-side Generalshape written with that construction kit maps to a flat instruction list (1 .. ISDF_PROGRAM_MAX_INSTR
+ * instructions) that the device evaluates at a body-frame point p.  It is a stack machine: a working point q (starts as p) and a
+ * value stack of depth <= ISDF_PROGRAM_MAX_DEPTH.  A DOMAIN instruction rewrites q; a PRIMITIVE pushes its SDF at q and resets q
+ * to p; a UNARY instruction rewrites the top of the stack; a BINARY one pops d2 (top), then d1, and pushes one value.  A valid
+ * program ends with exactly one value.  A transform that wraps a whole subtree in the reference is written in front of EVERY
+ * primitive of that subtree, outermost first (the order the nested closures apply them); transforms are never pre-multiplied, so
+ * the arithmetic stays operation for operation.  Every formula is an exact analytic SDF expression: the gradient is the central
+ * difference of DEFINE_USEFUL_FUNCTION (Shape.hpp:32-88), ISDF_GRAD_CENTRAL.
+ * Parameters p[] per opcode (vectors take three slots) and the lines they restate:
+ *   primitives   SPHERE radius, centre :1724 | CAPSULE a, b, radius :1734 | BOX size, centre :1748 | ROUNDED_BOX size, radius :1761
+ *                WIREFRAME_BOX size, thickness :1774 (as written there: q is formed from p, not from the shifted point as the
+ *                WireframeBox CLASS does, :1076 - the two differ) | TORUS r1, r2 :1799 (xy plane) | CYLINDER radius :1812
+ *                CAPPED_CYLINDER a, b, radius :1823 | ROUNDED_CYLINDER ra, rb, h :1851 | CAPPED_CONE ra, rb, a, b :1864
+ *                ROUNDED_CONE r1, r2, h :1886 | ELLIPSOID size :1902 | PYRAMID h :1913 | TETRAHEDRON r :1941 | OCTAHEDRON r :1953
+ *                DODECAHEDRON r :1962 | ICOSAHEDRON r :1978
+ *   domain       TRANSLATE offset :1996 | SCALE factor :2006 (q / factor; the reference's "x min(factor)" is the unary MUL after
+ *                the subtree) | ROTATE angle, axis :2021 | ROTATE_TO a, b :2043 (resolved on the host to nothing, to
+ *                rotate(pi, perpendicular(a)) or to rotate(acos(a.b), b x a); the rotation matrices are built once on the host)
+ *                TWIST k :2198 | BEND k :2215
+ *   unary        MUL m :2015 | NEGATE :2250 | DILATE r :2259 | ERODE r :2268 | SHELL thickness :2277
+ *   binary       UNION k :2087 | DIFFERENCE k :2134 | INTERSECTION k :2178 (the hard min / max form exactly when k == 0.0)
+ *                BLEND k :2232 (one operand: k d2 + (1 - k) d1)
+ * Of the reference's vector overloads only the fold of unionOp (:2061) has a meaning of its own - a chain of UNIONs - and blendOp
+ * folds the same way.  The vector differenceOp / intersectionOp (:2110-2132, :2155-2176) return inside their loop after the first
+ * operand: they ARE the binary forms and are not offered separately.
+ * isdf_set_shape_program installs the program in place of isdf_set_shape (which rejects this kind as it rejects GRID).
+ * trans / rotate (NULL: none) are the body offset (p - trans) * Rotate that precedes every class formula - for the front end's
+ * kernels the order is offset, R_obj, program.  bound_radius / bbox_center / bbox_half (NULL: zeros) mean what they mean in
+ * isdf_shape: zeros disable the cull and the row pruning, results are identical either way.  The fp32 pre-filter of the tile sweep
+ * is off for this kind.  The whole program is validated BEFORE the ctx is touched; ISDF_ERR_INVALID_ARG (message in
+ * isdf_last_error; the installed shape stays installed and usable) for: an unknown opcode, a stack underflow, a depth above 8, a
+ * final depth other than 1, fewer than 1 or more than 64 instructions, a non-finite parameter, a zero SCALE factor, a CAPSULE /
+ * CAPPED_CYLINDER / CAPPED_CONE with a == b, a ROUNDED_CONE with h == 0, a smoothing k < 0.
+ * isdf_shape_program_eval_host: the same arithmetic in plain C++ on the host - no ctx, no device; n_points x 3 body-frame points,
+ * sdf_out[n_points] and grad_out[n_points x 3] (either may be NULL).  The same validation applies: ISDF_ERR_INVALID_ARG, and
+ * isdf_shape_program_validate gives the message. */
+#define ISDF_PROGRAM_MAX_INSTR 64
+#define ISDF_PROGRAM_MAX_DEPTH 8
+typedef enum isdf_shape_op {
+    ISDF_OP_SPHERE = 1, ISDF_OP_CAPSULE = 2, ISDF_OP_BOX = 3, ISDF_OP_ROUNDED_BOX = 4, ISDF_OP_WIREFRAME_BOX = 5, ISDF_OP_TORUS = 6,
+    ISDF_OP_CYLINDER = 7, ISDF_OP_CAPPED_CYLINDER = 8, ISDF_OP_ROUNDED_CYLINDER = 9, ISDF_OP_CAPPED_CONE = 10,
+    ISDF_OP_ROUNDED_CONE = 11, ISDF_OP_ELLIPSOID = 12, ISDF_OP_PYRAMID = 13, ISDF_OP_TETRAHEDRON = 14, ISDF_OP_OCTAHEDRON = 15,
+    ISDF_OP_DODECAHEDRON = 16, ISDF_OP_ICOSAHEDRON = 17,
+    ISDF_OP_TRANSLATE = 32, ISDF_OP_SCALE = 33, ISDF_OP_ROTATE = 34, ISDF_OP_ROTATE_TO = 35, ISDF_OP_TWIST = 36, ISDF_OP_BEND = 37,
+    ISDF_OP_MUL = 48, ISDF_OP_NEGATE = 49, ISDF_OP_DILATE = 50, ISDF_OP_ERODE = 51, ISDF_OP_SHELL = 52,
+    ISDF_OP_UNION = 64, ISDF_OP_DIFFERENCE = 65, ISDF_OP_INTERSECTION = 66, ISDF_OP_BLEND = 67
+} isdf_shape_op;
+typedef struct isdf_shape_instr {
+    int32_t op;            /* isdf_shape_op */
+    int32_t reserved;      /* 0 */
+    double p[9];           /* the opcode's parameters in the order listed above; unused slots are ignored */
+} isdf_shape_instr;
+int isdf_set_shape_program(isdf_ctx *ctx, const isdf_shape_instr *instr, int n, const double *trans, const double *rotate,
+                           double bound_radius, const double *bbox_center, const double *bbox_half);
+int isdf_shape_program_eval_host(const isdf_shape_instr *instr, int n, const double *trans, const double *rotate,
+                                 const double *xyz, long long n_points, double *sdf_out, double *grad_out);
+/* the validation alone: ISDF_OK, or ISDF_ERR_INVALID_ARG with the message in err_out (nullable; err_cap bytes incl. the 0) */
+int isdf_shape_program_validate(const isdf_shape_instr *instr, int n, char *err_out, int err_cap);
 
 int isdf_set_points(isdf_ctx *ctx, const double *xyz, int M);   /* V1: M x 3 row-major obstacle points  */
 /* Multi-GPU: this ctx evaluates only its share of the constraint points (pieces for V2/V3, obstacle points
