@@ -122,6 +122,22 @@ class IsdfTrajCheckInfo(C.Structure):
                 ("select_ms", C.c_double), ("field_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+LIMITS_CHANNELS, TRAJ_SAMPLE_ROW = 6, 20
+LIMIT_SPEED, LIMIT_ACC, LIMIT_OMG, LIMIT_TILT, LIMIT_THRUST_MAX, LIMIT_THRUST_MIN = range(6)
+LIMIT_NAMES = ["speed", "acc", "omg", "tilt", "thrust_max", "thrust_min"]
+
+
+class IsdfTrajLimitsParams(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("reserved", C.c_int32), ("tol_t", C.c_double), ("max_acc", C.c_double),
+                ("max_thrust", C.c_double), ("min_thrust", C.c_double)]
+
+
+class IsdfTrajLimitsInfo(C.Structure):
+    _fields_ = [("value", C.c_double * 6), ("time", C.c_double * 6), ("limit", C.c_double * 6), ("piece", C.c_int32 * 6),
+                ("n_pieces_over", C.c_int32 * 6), ("judged", C.c_int32), ("feasible", C.c_int32), ("samples", C.c_int32),
+                ("reserved", C.c_int32), ("tol_t", C.c_double), ("device_ms", C.c_double)]
+
+
 class IsdfPointsMergeInfo(C.Structure):
     _fields_ = [("M_before", C.c_int32), ("M_after", C.c_int32), ("n_rows", C.c_int32), ("n_added", C.c_int32),
                 ("n_duplicate", C.c_int32), ("n_outside", C.c_int32), ("reserved", C.c_int32 * 2), ("merge_ms", C.c_double)]
@@ -166,6 +182,8 @@ EXPORTED_SYMBOLS = [
     "isdf_midend_params_default", "isdf_load_yaml_midend", "isdf_midend_cost", "isdf_midend_cost_batch", "isdf_midend_fit",
     "isdf_midend_fit_batch",
     "isdf_set_shape_program", "isdf_shape_program_eval_host", "isdf_shape_program_validate",
+    "isdf_traj_limits_params_default", "isdf_traj_limits", "isdf_traj_limits_device", "isdf_traj_limits_batch", "isdf_traj_limits_host",
+    "isdf_traj_sample", "isdf_traj_sample_device", "isdf_traj_sample_host", "isdf_traj_limits_sizes",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -326,6 +344,18 @@ def load_library(path=None):
     lib.isdf_refine_params_default.restype = None
     lib.isdf_optimize_lbfgs_checked.argtypes = [C.c_void_p, dp, C.c_int, C.POINTER(IsdfLbfgsParams), C.POINTER(IsdfRefineParams),
                                                 C.POINTER(IsdfRefineResult)]
+    lp, li = C.POINTER(IsdfTrajLimitsParams), C.POINTER(IsdfTrajLimitsInfo)
+    lib.isdf_traj_limits_params_default.argtypes = [lp]
+    lib.isdf_traj_limits_params_default.restype = None
+    lib.isdf_traj_limits_sizes.argtypes = [ip]
+    lib.isdf_traj_limits_sizes.restype = None
+    lib.isdf_traj_limits.argtypes = [C.c_void_p, C.c_int, dp, dp, lp, li, dp]
+    lib.isdf_traj_limits_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, lp, li, C.c_void_p, C.c_void_p]
+    lib.isdf_traj_limits_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, lp, li, dp]
+    lib.isdf_traj_limits_host.argtypes = [C.POINTER(IsdfConfig), C.c_int, dp, dp, lp, li, dp]
+    lib.isdf_traj_sample.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_longlong, dp, dp]
+    lib.isdf_traj_sample_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.isdf_traj_sample_host.argtypes = [C.POINTER(IsdfConfig), C.c_int, dp, dp, C.c_longlong, dp, dp]
     if path is None:
         _lib = lib
     return lib

@@ -187,6 +187,13 @@ __device__ __forceinline__ d4 flat_quat(const FlatS &s) {
     [[maybe_unused]] const double inv_t = m_rcp(s.tilt_den);
     d4 q; q.w = 0.5 * s.tilt_den; q.x = ISDF_QUOT(-s.z1, s.tilt_den, inv_t); q.y = ISDF_QUOT(s.z0, s.tilt_den, inv_t); q.z = 0.0; return q;
 }
+// `thr` of FlatnessMap::forward (flatness.hpp:203-206) from the intermediates of flat_core of the same v, a (psi plays no part in it)
+__device__ __forceinline__ double flat_thrust(const FlatP &P, d3 v, d3 a, const FlatS &s) {
+    const double f0 = P.mass * a.x + P.dv * (s.w_term * v.x);
+    const double f1 = P.mass * a.y + P.dv * (s.w_term * v.y);
+    const double f2 = P.mass * (a.z + P.grav) + P.dv * (s.w_term * v.z);
+    return s.z0 * f0 + s.z1 * f1 + s.z2 * f2;
+}
 struct FlatS2 {
     double ng_den, ng00, ng01, ng02, ng11, ng12, ng22, zu01, zu12, zu02, v_dot_a, dw_term;
     double dw0, dw1, dw2, dzt0, dzt1, dzt2, dz0, dz1, dz2, omg_den, omg_term;

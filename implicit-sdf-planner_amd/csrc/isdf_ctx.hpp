@@ -17,6 +17,8 @@ struct SweptMeshState;          // swept_mesh.hip: scratch of the swept-volume f
 struct TrajCheckState;          // swept_field.hpp: the last clearance check's points below the margin
 void isdf_swept_release_all(isdf_ctx *c);     // swept_mesh.hip: drops the field scratch and the mesh
 void isdf_traj_check_release_all(isdf_ctx *c);        // traj_check.hip: drops the kept clearance report
+struct TrajLimitsState;         // traj_limits.hip: scratch of the dynamic-limits report and the state sampler
+void isdf_traj_limits_release_all(isdf_ctx *c);       // traj_limits.hip: drops it
 
 // What the swept-volume kernels need per point set (SweptParams): the optimizer step's (the ctx holds it) or the field query's
 // (SweptMeshState holds its own: the query never shares scratch with the step).  The point arrays grow together.
@@ -44,6 +46,7 @@ struct isdf_ctx {
     double mesh_rmax = 0.0;                     // mesh robots: largest body-frame vertex norm (the swept mesh's box margin)
     SweptMeshState *swm = nullptr;              // isdf_swept_sdf / isdf_swept_mesh_*: own scratch, never the V1 step's
     TrajCheckState *tck = nullptr;              // isdf_traj_check*: the kept report rows
+    TrajLimitsState *tlm = nullptr;             // isdf_traj_limits* / isdf_traj_sample*: own scratch (grows only)
     const double *v1_tstar_stage = nullptr;     // set by the host-direct V1 step for ONE eval_device_impl call (SweptParams::tstar_stage)
     DevBuf<double> d_esdf_stage;        // isdf_esdf_sample's staging (points | values | gradients): grows only, no allocation per call
     DevBuf<float> d_esdf_bricks; bool bricks_stale = true;     // the ESDF as 2 x 2 x 2-cell bricks with apron, one 128-byte line each (map_build.hip: scattered points)
@@ -177,8 +180,8 @@ struct isdf_ctx {
     void *rccl_lib = nullptr; void *rccl_comm = nullptr;  // RCCL by dlopen (only when asked for): this device's communicator
     DevBuf<double> d_mpart;         // every shard of a multi-device step writes [packed outputs | 8 statistics as doubles] here
     DevBuf<double> d_mstage;        // lead, staged mode: the peers' parts copied next to each other
-    // every buffer above frees itself; the two states held by pointer are dropped here (isdf_destroy makes the device current)
-    ~isdf_ctx() { isdf_swept_release_all(this); isdf_traj_check_release_all(this); }
+    // every buffer above frees itself; the states held by pointer are dropped here (isdf_destroy makes the device current)
+    ~isdf_ctx() { isdf_swept_release_all(this); isdf_traj_check_release_all(this); isdf_traj_limits_release_all(this); }
 };
 namespace isdf { struct XFuse; }
 // xchg.hip: fills the in-kernel exchange block of a fused step when isdf_xchg_fuse is on (returns false: not requested;

@@ -87,6 +87,61 @@ def write_obj(path, V, F, lib=None):
         raise IsdfError(rc, f"isdf_write_obj {path}")
 
 
+def traj_limits_params(lib, samples=0, tol_t=None, max_acc=None, max_thrust=None, min_thrust=None):
+    """isdf_traj_limits_params from its defaults; None keeps a default (a limit left None is not judged)."""
+    p = capi.IsdfTrajLimitsParams()
+    lib.isdf_traj_limits_params_default(C.byref(p))
+    p.samples = int(samples)
+    for name, v in (("tol_t", tol_t), ("max_acc", max_acc), ("max_thrust", max_thrust), ("min_thrust", min_thrust)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def traj_limits_report(info, piece=None):
+    """An isdf_traj_limits_info as a dict of numpy arrays / ints, "piece_out" (N x 12: per piece [2 ch] value, [2 ch + 1] time) next to it."""
+    d = {}
+    for name, _ in capi.IsdfTrajLimitsInfo._fields_:
+        v = getattr(info, name)
+        if name != "reserved":
+            d[name] = np.array(v) if hasattr(v, "__len__") else v
+    d["piece_out"] = piece
+    return d
+
+
+def _traj_arrays(T, coeffs_colmajor):
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+    Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(-1)
+    if Cc.size != 18 * T.size:
+        raise ValueError(f"coefficients: {Cc.size} doubles for {T.size} pieces (18 per piece)")
+    return T, Cc
+
+
+def traj_limits_host(cfg, T, coeffs_colmajor, lib=None, **params):
+    """isdf_traj_limits_host: the dynamic-limits report in plain host code (no ctx, no device)."""
+    lib = lib or capi.load_library()
+    T, Cc = _traj_arrays(T, coeffs_colmajor)
+    p = traj_limits_params(lib, **params)
+    info = capi.IsdfTrajLimitsInfo()
+    piece = np.zeros((T.size, 12))
+    rc = lib.isdf_traj_limits_host(C.byref(cfg), T.size, _p(T), _p(Cc), C.byref(p), C.byref(info), _p(piece))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, (lib.isdf_last_error(None) or b"").decode())
+    return traj_limits_report(info, piece)
+
+
+def traj_sample_host(cfg, T, coeffs_colmajor, t, lib=None):
+    """isdf_traj_sample_host: rows pos3 | vel3 | acc3 | jer3 | quat4 | omg3 | thr at the stamps t."""
+    lib = lib or capi.load_library()
+    T, Cc = _traj_arrays(T, coeffs_colmajor)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+    rows = np.zeros((t.size, capi.TRAJ_SAMPLE_ROW))
+    rc = lib.isdf_traj_sample_host(C.byref(cfg), T.size, _p(T), _p(Cc), t.size, _p(t), _p(rows))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, (lib.isdf_last_error(None) or b"").decode())
+    return rows
+
+
 class Engine:
     def __init__(self, cfg, lib=None, devices=None):
         """devices: None = one device (cfg.device); a list = ONE ctx over those devices (isdf_create_multi), used like any other."""
@@ -486,6 +541,53 @@ class Engine:
         if rc < 0:
             self._check(rc)
         return bool(rc)
+
+    # ---- dynamic limits of a trajectory and its per-time state (isdf_traj_limits*, isdf_traj_sample*)
+    def traj_limits(self, T, coeffs_colmajor, **params):
+        """Largest speed, acceleration, body rate, tilt, thrust and smallest thrust of the trajectory: a dict of the
+        isdf_traj_limits_info fields (arrays of 6, capi.LIMIT_*) and "piece_out" (N x 12).  params: samples, tol_t, max_acc, max_thrust,
+        min_thrust (None: not judged); speed, body rate and tilt are judged against the configuration's vmax, omgmax, thetamax."""
+        T, Cc = _traj_arrays(T, coeffs_colmajor)
+        p = traj_limits_params(self.lib, **params)
+        info = capi.IsdfTrajLimitsInfo()
+        piece = np.zeros((T.size, 12))
+        self._check(self.lib.isdf_traj_limits(self.h, T.size, _p(T), _p(Cc), C.byref(p), C.byref(info), _p(piece)))
+        return traj_limits_report(info, piece)
+
+    def traj_limits_batch(self, T, coeffs_colmajor, **params):
+        """B trajectories of N pieces each (T: B x N, coefficients: B x 18 N) in one call: a list of B dicts."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 2:
+            raise ValueError("T must be B x N")
+        B, N = T.shape
+        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(B, -1)
+        if Cc.shape[1] != 18 * N:
+            raise ValueError(f"coefficients: {Cc.shape[1]} doubles per trajectory for {N} pieces (18 per piece)")
+        p = traj_limits_params(self.lib, **params)
+        infos = (capi.IsdfTrajLimitsInfo * B)()
+        piece = np.zeros((B, N, 12))
+        self._check(self.lib.isdf_traj_limits_batch(self.h, B, N, _p(T), _p(Cc), C.byref(p), infos, _p(piece)))
+        return [traj_limits_report(infos[b], piece[b]) for b in range(B)]
+
+    def traj_limits_device(self, N, d_T, d_coeffs, d_piece_out=0, stream=0, **params):
+        """The same with the trajectory (and, if given, the N x 12 per-piece rows) on the device; "piece_out" of the dict is None."""
+        p = traj_limits_params(self.lib, **params)
+        info = capi.IsdfTrajLimitsInfo()
+        self._check(self.lib.isdf_traj_limits_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), C.byref(p), C.byref(info),
+                                                     C.c_void_p(d_piece_out), C.c_void_p(stream)))
+        return traj_limits_report(info, None)
+
+    def traj_sample(self, T, coeffs_colmajor, t):
+        """The state at the time stamps t: rows pos3 | vel3 | acc3 | jer3 | quat4 | omg3 | thr (psi = 0)."""
+        T, Cc = _traj_arrays(T, coeffs_colmajor)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+        rows = np.zeros((t.size, capi.TRAJ_SAMPLE_ROW))
+        self._check(self.lib.isdf_traj_sample(self.h, T.size, _p(T), _p(Cc), t.size, _p(t), _p(rows)))
+        return rows
+
+    def traj_sample_device(self, N, d_T, d_coeffs, n, d_t, d_rows, stream=0):
+        self._check(self.lib.isdf_traj_sample_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), n, C.c_void_p(d_t), C.c_void_p(d_rows),
+                                                     C.c_void_p(stream)))
 
     def points_merge_check(self, below=None):
         """Merges the last check's kept points with value < below (None: all of them) into the obstacle-point set on the device: the

@@ -514,6 +514,86 @@ int isdf_traj_check_release(isdf_ctx *ctx);      /* frees the kept rows */
  * (n_penetrating > 0 at the default parameters), 0 = none, negative = isdf_status */
 int isdf_traj_collide(isdf_ctx *ctx, int N, const double *T, const double *coeffs);
 
+/* ---- dynamic limits of a trajectory -------------------------------------------------------------------------------- */
+/* The back end keeps the vehicle inside vmax / omgmax / thetamax only through soft penalties at K + 1 samples per piece
+ * (back_end_optimizer.hpp:453-536), so a finished trajectory can exceed them, between the samples or at them.  These entry
+ * points say by how much: the counterpart of Trajectory::getMaxVelRate / getMaxAccRate / checkMaxVelRate / checkMaxAccRate
+ * (trajectory.hpp:253-390, :631-680) extended to the body rate, tilt and thrust of the flatness map, and of the per-time
+ * state SweptVolumeManager::getStateOnTrajStamp (sw_manager.hpp:307-341) hands out.  Conventions of the penalty: psi = 0, the
+ * vehicle constants of the ctx's isdf_config, pieces located by Trajectory::locatePieceIdx (trajectory.hpp:545-563: a junction
+ * time belongs to the earlier piece, a stamp below 0 is evaluated on the first piece and one above sum(T) on the last),
+ * trajectory arrays as isdf_eval takes them.
+ *
+ * Channels:  0 speed |vel|   1 acceleration |acc|   2 body rate |omg| of optimizated_forward (flatness.hpp:88-148)
+ *            3 tilt acos(1 - 2 (q1^2 + q2^2)) (back_end_optimizer.hpp:505-508)
+ *            4 largest / 5 smallest thrust `thr` of FlatnessMap::forward (flatness.hpp:203-206)
+ *
+ * isdf_traj_sample: the state at n time stamps, rows of ISDF_TRAJ_SAMPLE_ROW doubles pos3 | vel3 | acc3 | jer3 | quat4 | omg3 | thr.
+ *
+ * isdf_traj_limits: per piece and channel, `samples` + 1 uniform coarse samples; a golden-section search starts on
+ * [s_(j-1), s_(j+1)] at every interior sample that is no smaller than both neighbours and, with one-sided brackets, at both end
+ * samples, and stops when its bracket is shorter than tol_t * T_i (64 iterations at most).  Its result is the largest value it
+ * EVALUATED with the time of that evaluation, never an interval midpoint; a piece reports the largest result (ties: the smallest
+ * time), a trajectory the largest piece (ties: the smallest time, then the earlier piece).  Channels 0-2 are maximised in squared
+ * form and reported as the square root, channel 5 is channel 4 minimised.  The report is therefore a LOWER bound of the true
+ * extremum that is never below a coarse sample: a peak narrower than two coarse intervals can be missed, and it is no
+ * certificate between the evaluated times.  Same bytes on every run; a trajectory's rows do not depend on its place in a batch.
+ * Any single-device ctx whatever cfg.variant is; a multi-device ctx ISDF_ERR_UNSUPPORTED; N < 1, a null array or a duration that
+ * is not positive and finite ISDF_ERR_INVALID_ARG.  Own scratch (grows only): the step's state, lastTstar, the kept clearance
+ * rows and the swept mesh are not touched.  Two launches per call for any B.  A report costs what its longest
+ * chain of dependent evaluations costs, about a millisecond on the device whatever N is: for ONE trajectory of a few dozen pieces
+ * isdf_traj_limits_host on one thread is as fast or faster; the device forms pay off for hundreds of pieces, for batches, and
+ * where the trajectory already lives on the device. */
+#define ISDF_LIMITS_CHANNELS 6
+#define ISDF_LIMIT_SPEED 0
+#define ISDF_LIMIT_ACC 1
+#define ISDF_LIMIT_OMG 2
+#define ISDF_LIMIT_TILT 3
+#define ISDF_LIMIT_THRUST_MAX 4
+#define ISDF_LIMIT_THRUST_MIN 5
+#define ISDF_TRAJ_SAMPLE_ROW 20
+typedef struct isdf_traj_limits_params {
+    int32_t samples;     /* coarse intervals per piece; <= 0 (default): 4 * cfg.integral_intervs                                  */
+    int32_t reserved;
+    double tol_t;        /* a search stops when its bracket is shorter than tol_t * T_i; <= 0 or NaN (default 2^-26): 2^-26         */
+    double max_acc, max_thrust, min_thrust;      /* limits of channels 1, 4, 5; NaN (default): not judged.  Channels 0, 2, 3 are
+                                                    judged against cfg.vmax, cfg.omgmax, cfg.thetamax                             */
+} isdf_traj_limits_params;
+typedef struct isdf_traj_limits_info {
+    double value[ISDF_LIMITS_CHANNELS];          /* the extreme value of the channel                                              */
+    double time[ISDF_LIMITS_CHANNELS];           /* the global time it was evaluated at                                           */
+    double limit[ISDF_LIMITS_CHANNELS];          /* the limit in force (NaN: not judged)                                          */
+    int32_t piece[ISDF_LIMITS_CHANNELS];         /* the piece it lies in                                                          */
+    int32_t n_pieces_over[ISDF_LIMITS_CHANNELS]; /* pieces whose own extreme value is STRICTLY beyond the limit (0: not judged)   */
+    int32_t judged;      /* bit ch: the channel has a limit                                                                        */
+    int32_t feasible;    /* bit ch: it has one and value[ch] is not strictly beyond it; all is well when feasible == judged        */
+    int32_t samples;     /* the coarse intervals per piece in force                                                                */
+    int32_t reserved;
+    double tol_t;        /* the tolerance in force                                                                                 */
+    double device_ms;    /* device time of the launches (events on the stream); 0 for the host form                               */
+} isdf_traj_limits_info;
+void isdf_traj_limits_params_default(isdf_traj_limits_params *p);
+/* params NULL = defaults.  piece_out (N x 12 doubles or NULL): per piece, [2 ch] the value and [2 ch + 1] the global time of channel ch */
+int isdf_traj_limits(isdf_ctx *ctx, int N, const double *T, const double *coeffs, const isdf_traj_limits_params *params,
+                     isdf_traj_limits_info *info_out, double *piece_out);
+/* the same with the trajectory (and the per-piece array, or NULL) on the device; synchronises `stream` before it returns */
+int isdf_traj_limits_device(isdf_ctx *ctx, int N, const double *d_T, const double *d_coeffs, const isdf_traj_limits_params *params,
+                            isdf_traj_limits_info *info_out, double *d_piece_out, void *stream);
+/* B trajectories of N pieces each (T: B x N, coeffs: B x 6N x 3 column-major each, host arrays) -> B infos, piece_out B x N x 12 or NULL */
+int isdf_traj_limits_batch(isdf_ctx *ctx, int B, int N, const double *T, const double *coeffs, const isdf_traj_limits_params *params,
+                           isdf_traj_limits_info *infos_out, double *piece_out);
+/* the same rules in plain host code: needs no ctx and no device (csrc/traj_limits_host.hpp); agrees with the device to rounding */
+int isdf_traj_limits_host(const isdf_config *cfg, int N, const double *T, const double *coeffs, const isdf_traj_limits_params *params,
+                          isdf_traj_limits_info *info_out, double *piece_out);
+/* rows_out: n x ISDF_TRAJ_SAMPLE_ROW */
+int isdf_traj_sample(isdf_ctx *ctx, int N, const double *T, const double *coeffs, long long n, const double *t, double *rows_out);
+int isdf_traj_sample_device(isdf_ctx *ctx, int N, const double *d_T, const double *d_coeffs, long long n, const double *d_t,
+                            double *d_rows_out, void *stream);
+int isdf_traj_sample_host(const isdf_config *cfg, int N, const double *T, const double *coeffs, long long n, const double *t,
+                          double *rows_out);
+/* sizeof of the two structs above as the library was compiled (the Python mirror checks itself against them) */
+void isdf_traj_limits_sizes(int out[2]);
+
 /* ---- the clearance report merged into the obstacle-point set ---------------------------------------------------------- */
 /* Where the reference only warns that the optimised trajectory collides (plan_manager.cpp:306-309), the report can be fed back:
  * the points the last isdf_traj_check* kept (value < its margin), narrowed to value < below (a negative `below`: all of them;
