@@ -138,6 +138,21 @@ class IsdfTrajLimitsInfo(C.Structure):
                 ("reserved", C.c_int32), ("tol_t", C.c_double), ("device_ms", C.c_double)]
 
 
+RETIME_OK, RETIME_AT_LOWER, RETIME_NOT_REACHABLE = 0, 1, 2
+TRAJ_RETIME_MAX_PIECES = 1 << 20
+
+
+class IsdfTrajRetimeParams(C.Structure):
+    _fields_ = [("s_lo", C.c_double), ("s_hi", C.c_double), ("ladder", C.c_int32), ("rounds", C.c_int32), ("check", C.c_int32),
+                ("reserved", C.c_int32), ("limits", IsdfTrajLimitsParams)]
+
+
+class IsdfTrajRetimeInfo(C.Structure):
+    _fields_ = [("scale", C.c_double), ("scale_below", C.c_double), ("status", C.c_int32), ("rounds", C.c_int32), ("candidates", C.c_int32),
+                ("nonmonotone", C.c_int32), ("binding", C.c_int32), ("checked", C.c_int32), ("duration_in", C.c_double),
+                ("duration_out", C.c_double), ("limits", IsdfTrajLimitsInfo), ("check", IsdfTrajCheckInfo), ("device_ms", C.c_double)]
+
+
 class IsdfPointsMergeInfo(C.Structure):
     _fields_ = [("M_before", C.c_int32), ("M_after", C.c_int32), ("n_rows", C.c_int32), ("n_added", C.c_int32),
                 ("n_duplicate", C.c_int32), ("n_outside", C.c_int32), ("reserved", C.c_int32 * 2), ("merge_ms", C.c_double)]
@@ -184,6 +199,8 @@ EXPORTED_SYMBOLS = [
     "isdf_set_shape_program", "isdf_shape_program_eval_host", "isdf_shape_program_validate",
     "isdf_traj_limits_params_default", "isdf_traj_limits", "isdf_traj_limits_device", "isdf_traj_limits_batch", "isdf_traj_limits_host",
     "isdf_traj_sample", "isdf_traj_sample_device", "isdf_traj_sample_host", "isdf_traj_limits_sizes",
+    "isdf_traj_retime_params_default", "isdf_traj_retime", "isdf_traj_retime_device", "isdf_traj_retime_batch", "isdf_traj_retime_host",
+    "isdf_traj_scale_host", "isdf_traj_retime_sizes",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -356,6 +373,21 @@ def load_library(path=None):
     lib.isdf_traj_sample.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_longlong, dp, dp]
     lib.isdf_traj_sample_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.isdf_traj_sample_host.argtypes = [C.POINTER(IsdfConfig), C.c_int, dp, dp, C.c_longlong, dp, dp]
+    rp, ri = C.POINTER(IsdfTrajRetimeParams), C.POINTER(IsdfTrajRetimeInfo)
+    lib.isdf_traj_retime_params_default.argtypes = [rp]
+    lib.isdf_traj_retime_params_default.restype = None
+    lib.isdf_traj_retime_sizes.argtypes = [ip]
+    lib.isdf_traj_retime_sizes.restype = None
+    lib.isdf_traj_retime.argtypes = [C.c_void_p, C.c_int, dp, dp, rp, dp, dp, ri]
+    lib.isdf_traj_retime_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, rp, C.c_void_p, C.c_void_p, ri, C.c_void_p]
+    lib.isdf_traj_retime_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, rp, dp, dp, ri]
+    lib.isdf_traj_retime_host.argtypes = [C.POINTER(IsdfConfig), C.c_int, dp, dp, rp, dp, dp, ri]
+    lib.isdf_traj_scale_host.argtypes = [C.c_int, dp, dp, C.c_double, dp, dp]
+    sz = (C.c_int * 2)()
+    lib.isdf_traj_retime_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfTrajRetimeParams), C.sizeof(IsdfTrajRetimeInfo)]:
+        raise RuntimeError(f"isdf_traj_retime structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfTrajRetimeParams), C.sizeof(IsdfTrajRetimeInfo)]}")
     if path is None:
         _lib = lib
     return lib

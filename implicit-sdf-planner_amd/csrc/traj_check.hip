@@ -435,6 +435,11 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
 
 }  // namespace
 
+int isdf_traj_check_ready(isdf_ctx *c) {
+    double margin = 0.0;
+    return check_state(c, nullptr, &margin);
+}
+
 void isdf_traj_check_release_all(isdf_ctx *c) {
     if (!c->tck) return;
     delete c->tck;

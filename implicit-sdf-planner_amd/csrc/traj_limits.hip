@@ -223,6 +223,37 @@ int state(isdf_ctx *c, TrajLimitsState **out) {
     return ISDF_OK;
 }
 
+// the two launches of B trajectories on device arrays, nothing else: no event, no copy, no synchronisation
+int limits_launch(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, const isdf_traj_limits_params *p, double *d_piece, double *d_info,
+                  hipStream_t st) {
+    const size_t pieces = (size_t)B * N;
+    TLArgs A{};
+    isdf_fill_flat(c->cfg, A.flat);
+    A.B = B; A.N = N; A.S = isdf_host::tl_samples(p, c->cfg); A.tol_t = isdf_host::tl_tol(p);
+    A.T = d_T; A.C = d_C; A.piece = d_piece;
+    TLLimits L;
+    isdf_host::tl_limits(p, c->cfg, L.limit);
+    hipLaunchKernelGGL(tl_piece_kernel, dim3((unsigned)((pieces + TL_WAVES - 1) / TL_WAVES)), dim3(64 * TL_WAVES), 0, st, A);
+    hipLaunchKernelGGL(tl_traj_kernel, dim3((unsigned)B), dim3(64), 0, st, N, (const double *)d_piece, L, d_info);
+    HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+// a trajectory's INFO_WORDS -> its info (device_ms left 0)
+void limits_unpack(const isdf_config &cfg, const isdf_traj_limits_params *p, const double *w, isdf_traj_limits_info *info) {
+    double limit[CH];
+    isdf_host::tl_limits(p, cfg, limit);
+    std::memset(info, 0, sizeof(*info));
+    for (int ch = 0; ch < CH; ch++) {
+        info->value[ch] = w[4 * ch]; info->time[ch] = w[4 * ch + 1]; info->piece[ch] = (int32_t)w[4 * ch + 2];
+        info->n_pieces_over[ch] = (int32_t)w[4 * ch + 3]; info->limit[ch] = limit[ch];
+        if (!std::isnan(limit[ch])) {
+            info->judged |= 1 << ch;
+            if (!isdf_host::tl_over(ch, info->value[ch], limit[ch])) info->feasible |= 1 << ch;
+        }
+    }
+    info->samples = isdf_host::tl_samples(p, cfg); info->tol_t = isdf_host::tl_tol(p);
+}
+
 // the report of B trajectories on device arrays.  d_piece: B N x 12 on the device, or null (the state's own)
 int limits_run(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, const isdf_traj_limits_params *p,
                isdf_traj_limits_info *infos, double *d_piece, hipStream_t st) {
@@ -231,16 +262,8 @@ int limits_run(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, 
     const size_t pieces = (size_t)B * N;
     if (!d_piece) { const int rc = k->d_piece.reserve(c, pieces * 12); if (rc) return rc; d_piece = k->d_piece; }
     { const int rc = k->d_info.reserve(c, (size_t)B * INFO_WORDS); if (rc) return rc; }
-    TLArgs A{};
-    isdf_fill_flat(c->cfg, A.flat);
-    A.B = B; A.N = N; A.S = isdf_host::tl_samples(p, c->cfg); A.tol_t = isdf_host::tl_tol(p);
-    A.T = d_T; A.C = d_C; A.piece = d_piece;
-    TLLimits L;
-    isdf_host::tl_limits(p, c->cfg, L.limit);
     HIPCHK(c, hipEventRecord(k->ev[0], st));
-    hipLaunchKernelGGL(tl_piece_kernel, dim3((unsigned)((pieces + TL_WAVES - 1) / TL_WAVES)), dim3(64 * TL_WAVES), 0, st, A);
-    hipLaunchKernelGGL(tl_traj_kernel, dim3((unsigned)B), dim3(64), 0, st, N, (const double *)d_piece, L, k->d_info.get());
-    HIPCHK(c, hipGetLastError());
+    { const int rc = limits_launch(c, B, N, d_T, d_C, p, d_piece, k->d_info, st); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(k->ev[1], st));
     if (k->h_info.size() < (size_t)B * INFO_WORDS) k->h_info.resize((size_t)B * INFO_WORDS);
     HIPCHK(c, hipMemcpyAsync(k->h_info.data(), k->d_info, (size_t)B * INFO_WORDS * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -248,18 +271,8 @@ int limits_run(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, 
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
     if (infos) for (int b = 0; b < B; b++) {
-        isdf_traj_limits_info *info = infos + b;
-        const double *w = k->h_info.data() + (size_t)b * INFO_WORDS;
-        std::memset(info, 0, sizeof(*info));
-        for (int ch = 0; ch < CH; ch++) {
-            info->value[ch] = w[4 * ch]; info->time[ch] = w[4 * ch + 1]; info->piece[ch] = (int32_t)w[4 * ch + 2];
-            info->n_pieces_over[ch] = (int32_t)w[4 * ch + 3]; info->limit[ch] = L.limit[ch];
-            if (!std::isnan(L.limit[ch])) {
-                info->judged |= 1 << ch;
-                if (!isdf_host::tl_over(ch, info->value[ch], L.limit[ch])) info->feasible |= 1 << ch;
-            }
-        }
-        info->samples = A.S; info->tol_t = A.tol_t; info->device_ms = ms;
+        limits_unpack(c->cfg, p, k->h_info.data() + (size_t)b * INFO_WORDS, infos + b);
+        infos[b].device_ms = ms;
     }
     return ISDF_OK;
 }
@@ -279,6 +292,14 @@ int check_device_traj(isdf_ctx *c, TrajLimitsState *k, int N, const double *d_T,
 }
 
 }  // namespace
+
+int isdf_traj_limits_launch(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, const isdf_traj_limits_params *p, double *d_piece,
+                            double *d_info, hipStream_t st) {
+    return limits_launch(c, B, N, d_T, d_C, p, d_piece, d_info, st);
+}
+void isdf_traj_limits_unpack(const isdf_config &cfg, const isdf_traj_limits_params *p, const double *words, isdf_traj_limits_info *info) {
+    limits_unpack(cfg, p, words, info);
+}
 
 void isdf_traj_limits_release_all(isdf_ctx *c) {
     if (!c->tlm) return;

@@ -43,8 +43,8 @@ inline void tl_limits(const isdf_traj_limits_params *p, const isdf_config &cfg, 
     limit[ISDF_LIMIT_THRUST_MAX] = p ? p->max_thrust : nan;
     limit[ISDF_LIMIT_THRUST_MIN] = p ? p->min_thrust : nan;
 }
-// strictly beyond the limit (a NaN limit: never)
-inline bool tl_over(int ch, double value, double limit) { return ch == ISDF_LIMIT_THRUST_MIN ? value < limit : value > limit; }
+// strictly beyond the limit (a NaN limit: never); constexpr: the retiming's pick kernel judges with the same text
+constexpr bool tl_over(int ch, double value, double limit) { return ch == ISDF_LIMIT_THRUST_MIN ? value < limit : value > limit; }
 
 inline int tl_check_traj(int N, const double *T, const double *coeffs) {
     if (N < 1 || !T || !coeffs) return ISDF_ERR_INVALID_ARG;

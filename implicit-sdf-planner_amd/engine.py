@@ -142,6 +142,65 @@ def traj_sample_host(cfg, T, coeffs_colmajor, t, lib=None):
     return rows
 
 
+def traj_retime_params(lib, s_lo=None, s_hi=None, ladder=None, rounds=None, check=False, **limits):
+    """isdf_traj_retime_params from its defaults; None keeps a default.  limits: the keywords of traj_limits_params."""
+    p = capi.IsdfTrajRetimeParams()
+    lib.isdf_traj_retime_params_default(C.byref(p))
+    for name, v, conv in (("s_lo", s_lo, float), ("s_hi", s_hi, float), ("ladder", ladder, int), ("rounds", rounds, int)):
+        if v is not None:
+            setattr(p, name, conv(v))
+    p.check = 1 if check else 0
+    p.limits = traj_limits_params(lib, **limits)
+    return p
+
+
+def _struct_dict(st):
+    d = {}
+    for name, _ in st._fields_:
+        v = getattr(st, name)
+        if name != "reserved":
+            d[name] = np.array(v) if hasattr(v, "__len__") else v
+    return d
+
+
+def traj_retime_report(info, T_out=None, coeffs_out=None):
+    """An isdf_traj_retime_info as a dict: its scalars, "limits" (the dict traj_limits returns, at `scale`), "check" (a dict of the
+    isdf_traj_check_info fields, or None when nothing was checked), and the retimed arrays "T" and "coeffs" (None: they are on the device)."""
+    d = {}
+    for name, _ in capi.IsdfTrajRetimeInfo._fields_:
+        if name not in ("limits", "check"):
+            d[name] = getattr(info, name)
+    d["limits"] = traj_limits_report(info.limits)
+    d["check"] = _struct_dict(info.check) if info.checked else None
+    d["T"], d["coeffs"] = T_out, coeffs_out
+    return d
+
+
+def traj_scale_host(T, coeffs_colmajor, s, lib=None):
+    """isdf_traj_scale_host: (T * s, the coefficient of t^k divided by s^k), the bytes every form of the retiming returns for the factor s."""
+    lib = lib or capi.load_library()
+    T, Cc = _traj_arrays(T, coeffs_colmajor)
+    To, Co = np.zeros_like(T), np.zeros_like(Cc)
+    rc = lib.isdf_traj_scale_host(T.size, _p(T), _p(Cc), float(s), _p(To), _p(Co))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, (lib.isdf_last_error(None) or b"").decode())
+    return To, Co
+
+
+def traj_retime_host(cfg, T, coeffs_colmajor, lib=None, **params):
+    """isdf_traj_retime_host: the retiming in plain host code (no ctx, no device); the dict of traj_retime_report."""
+    lib = lib or capi.load_library()
+    T, Cc = _traj_arrays(T, coeffs_colmajor)
+    params.pop("check", None)
+    p = traj_retime_params(lib, **params)
+    info = capi.IsdfTrajRetimeInfo()
+    To, Co = np.zeros_like(T), np.zeros_like(Cc)
+    rc = lib.isdf_traj_retime_host(C.byref(cfg), T.size, _p(T), _p(Cc), C.byref(p), _p(To), _p(Co), C.byref(info))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, (lib.isdf_last_error(None) or b"").decode())
+    return traj_retime_report(info, To, Co)
+
+
 class Engine:
     def __init__(self, cfg, lib=None, devices=None):
         """devices: None = one device (cfg.device); a list = ONE ctx over those devices (isdf_create_multi), used like any other."""
@@ -588,6 +647,45 @@ class Engine:
     def traj_sample_device(self, N, d_T, d_coeffs, n, d_t, d_rows, stream=0):
         self._check(self.lib.isdf_traj_sample_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), n, C.c_void_p(d_t), C.c_void_p(d_rows),
                                                      C.c_void_p(stream)))
+
+    # ---- retiming a trajectory to its dynamic limits (isdf_traj_retime*)
+    def traj_retime(self, T, coeffs_colmajor, **params):
+        """The smallest uniform slow-down factor of a ladder search at which the limits report is feasible, and the trajectory scaled by
+        it: the dict of traj_retime_report.  params: s_lo, s_hi, ladder, rounds, check (True: the result goes through the clearance
+        check, "check" of the dict), and the limits' keywords (samples, tol_t, max_acc, max_thrust, min_thrust)."""
+        T, Cc = _traj_arrays(T, coeffs_colmajor)
+        p = traj_retime_params(self.lib, **params)
+        info = capi.IsdfTrajRetimeInfo()
+        To, Co = np.zeros_like(T), np.zeros_like(Cc)
+        self._check(self.lib.isdf_traj_retime(self.h, T.size, _p(T), _p(Cc), C.byref(p), _p(To), _p(Co), C.byref(info)))
+        if info.checked:
+            self._traj_check_rows = int(info.check.n_below_margin)
+        return traj_retime_report(info, To, Co)
+
+    def traj_retime_batch(self, T, coeffs_colmajor, **params):
+        """B trajectories of N pieces each (T: B x N, coefficients: B x 18 N), each with its own brackets and status: a list of B dicts."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 2:
+            raise ValueError("T must be B x N")
+        B, N = T.shape
+        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(B, -1)
+        if Cc.shape[1] != 18 * N:
+            raise ValueError(f"coefficients: {Cc.shape[1]} doubles per trajectory for {N} pieces (18 per piece)")
+        p = traj_retime_params(self.lib, **params)
+        infos = (capi.IsdfTrajRetimeInfo * B)()
+        To, Co = np.zeros_like(T), np.zeros_like(Cc)
+        self._check(self.lib.isdf_traj_retime_batch(self.h, B, N, _p(T), _p(Cc), C.byref(p), _p(To), _p(Co), infos))
+        return [traj_retime_report(infos[b], To[b], Co[b]) for b in range(B)]
+
+    def traj_retime_device(self, N, d_T, d_coeffs, d_T_out, d_coeffs_out, stream=0, **params):
+        """The same with every array on the device (d_T_out: N, d_coeffs_out: 18 N doubles); "T" and "coeffs" of the dict are None."""
+        p = traj_retime_params(self.lib, **params)
+        info = capi.IsdfTrajRetimeInfo()
+        self._check(self.lib.isdf_traj_retime_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), C.byref(p), C.c_void_p(d_T_out),
+                                                     C.c_void_p(d_coeffs_out), C.byref(info), C.c_void_p(stream)))
+        if info.checked:
+            self._traj_check_rows = int(info.check.n_below_margin)
+        return traj_retime_report(info)
 
     def points_merge_check(self, below=None):
         """Merges the last check's kept points with value < below (None: all of them) into the obstacle-point set on the device: the

@@ -594,6 +594,81 @@ int isdf_traj_sample_host(const isdf_config *cfg, int N, const double *T, const 
 /* sizeof of the two structs above as the library was compiled (the Python mirror checks itself against them) */
 void isdf_traj_limits_sizes(int out[2]);
 
+/* ---- retiming a trajectory to its dynamic limits --------------------------------------------------------------------- */
+/* What a caller can DO with an infeasible limits report: slow the whole trajectory down uniformly until the report is feasible.
+ * The reference has no counterpart (trajectory.hpp:253-390, :631-680 only report).
+ *
+ * Scaling by s > 0:  T'_i = s * T_i, and the coefficient of t^k of every piece and axis becomes c_k / p_k with p_0 = 1,
+ * p_k = p_(k-1) * s - plain IEEE operations, never contracted, so host and device give the same bytes and s = 1 returns the input
+ * bit for bit.  The path keeps its geometry; speed falls as 1/s, acceleration as 1/s^2, jerk as 1/s^3, body rate, tilt and thrust
+ * move towards hover.
+ * Feasible at s, F(s):  feasible == judged in the report isdf_traj_limits* gives for the scaled arrays under params.limits - by
+ * definition the existing entry point's report, no numerics of its own.
+ * Ladder:  a round with bracket [a, b] evaluates `ladder` = L candidates s_0 = a, s_(L-1) = b exactly and
+ * s_i = a + (b - a) * i / (L - 1) in between (the product, then the quotient, then the sum).
+ * Pick:  i* = the smallest i such that F(s_j) holds for EVERY j >= i (a suffix, which guards against an F that is not monotone;
+ * `nonmonotone` is set when any round saw a feasible candidate below an infeasible one).
+ * Rounds:  round 0 uses [s_lo, s_hi].  F(s_hi) fails: status 2 (not reachable), the result is the candidate s_hi.  i* == 0 in
+ * round 0: status 1, the result is s_lo.  Otherwise the next round's bracket is [s_(i*-1), s_(i*)], `rounds` rounds in all,
+ * status 0.  The result is always an EVALUATED candidate; scale_below is the largest infeasible candidate evaluated below it (NaN:
+ * none), so after R rounds scale - scale_below <= (s_hi - s_lo) / (L - 1)^R up to rounding.  A later round evaluates its
+ * bracket's two ends again (the same bytes, the same verdict); `candidates` counts them.
+ *
+ * Errors as for isdf_traj_limits*, and ISDF_ERR_INVALID_ARG for: s_lo not positive or not finite, s_hi not finite or <= s_lo,
+ * ladder outside 2..64, rounds outside 1..4, B * ladder * N above ISDF_TRAJ_RETIME_MAX_PIECES, check != 0 in the batch form.
+ * check = 1 needs what isdf_traj_check needs (shape, occupancy grid, a total below 300 s at s_hi in the host-array form); its
+ * absence is reported before anything is computed.  The result then goes through isdf_traj_check_device with the default
+ * parameters (margin cfg.safety_hor, PLANNER mode) and the ctx keeps THAT check's rows: a slower vehicle tilts less, so the
+ * clearance a planner found by tilting through a gap has to be looked at again.  Without check the kept rows, the step's points
+ * and lastTstar are not touched.  The output arrays must not overlap the inputs.
+ * On the device: 1 + 4 * rounds launches for any B, no host synchronisation between rounds, one at the end (with
+ * check = 0); nothing is decided by an atomic; own scratch that grows only; the same bytes on every run; a trajectory's result
+ * does not depend on its place in a batch.  The device forms report a duration that is not positive and finite only at that
+ * one synchronisation (the outputs are then undefined). */
+#define ISDF_TRAJ_RETIME_MAX_PIECES (1 << 20)
+#define ISDF_RETIME_OK 0             /* scale is the smallest feasible candidate of the last round's ladder                    */
+#define ISDF_RETIME_AT_LOWER 1       /* s_lo is feasible already (and every candidate above it): scale == s_lo                 */
+#define ISDF_RETIME_NOT_REACHABLE 2  /* s_hi is not feasible: the result is the candidate s_hi, limits says what still binds    */
+typedef struct isdf_traj_retime_params {
+    double s_lo, s_hi;   /* round 0's bracket (defaults 1 and 8)                                                                    */
+    int32_t ladder;      /* candidates per round, 2..64 (default 32)                                                                */
+    int32_t rounds;      /* 1..4 (default 3)                                                                                        */
+    int32_t check;       /* 1: the result goes through the clearance check (not in the batch form)                                  */
+    int32_t reserved;
+    isdf_traj_limits_params limits;
+} isdf_traj_retime_params;
+typedef struct isdf_traj_retime_info {
+    double scale;        /* the factor of the returned arrays                                                                       */
+    double scale_below;  /* the largest infeasible candidate evaluated below it (NaN: none)                                         */
+    int32_t status;      /* ISDF_RETIME_*                                                                                           */
+    int32_t rounds;      /* rounds that decided something for this trajectory (1 for status 1 and 2)                                */
+    int32_t candidates;  /* limits reports that decided it: ladder * rounds (the device forms launch every round for every trajectory)      */
+    int32_t nonmonotone; /* 1: some round saw a feasible candidate below an infeasible one                                          */
+    int32_t binding;     /* bit ch: channel ch is judged and infeasible at scale_below (0: no scale_below)                          */
+    int32_t checked;     /* 1: `check` is filled                                                                                    */
+    double duration_in, duration_out;    /* the durations summed in order, before and after                                         */
+    isdf_traj_limits_info limits;        /* the report at `scale` (device_ms: 0)                                                    */
+    isdf_traj_check_info check;
+    double device_ms;    /* device time of the launches without the check's (events on the stream); 0 for the host form             */
+} isdf_traj_retime_info;
+void isdf_traj_retime_params_default(isdf_traj_retime_params *p);
+/* params NULL = defaults.  T_out: N, coeffs_out: 6N x 3 column-major (both required) */
+int isdf_traj_retime(isdf_ctx *ctx, int N, const double *T, const double *coeffs, const isdf_traj_retime_params *params,
+                     double *T_out, double *coeffs_out, isdf_traj_retime_info *info_out);
+/* every array on the device; synchronises `stream` once, before it returns (check = 1: the check synchronises as it always does) */
+int isdf_traj_retime_device(isdf_ctx *ctx, int N, const double *d_T, const double *d_coeffs, const isdf_traj_retime_params *params,
+                            double *d_T_out, double *d_coeffs_out, isdf_traj_retime_info *info_out, void *stream);
+/* B trajectories of N pieces each (host arrays, laid out as isdf_traj_limits_batch takes them): own brackets and status each */
+int isdf_traj_retime_batch(isdf_ctx *ctx, int B, int N, const double *T, const double *coeffs, const isdf_traj_retime_params *params,
+                           double *T_out, double *coeffs_out, isdf_traj_retime_info *infos_out);
+/* the same rules in plain host code over isdf_traj_limits_host: no ctx, no device, params.check ignored */
+int isdf_traj_retime_host(const isdf_config *cfg, int N, const double *T, const double *coeffs, const isdf_traj_retime_params *params,
+                          double *T_out, double *coeffs_out, isdf_traj_retime_info *info_out);
+/* the scaling alone */
+int isdf_traj_scale_host(int N, const double *T, const double *coeffs, double s, double *T_out, double *coeffs_out);
+/* sizeof of the two structs above as the library was compiled */
+void isdf_traj_retime_sizes(int out[2]);
+
 /* ---- the clearance report merged into the obstacle-point set ---------------------------------------------------------- */
 /* Where the reference only warns that the optimised trajectory collides (plan_manager.cpp:306-309), the report can be fed back:
  * the points the last isdf_traj_check* kept (value < its margin), narrowed to value < below (a negative `below`: all of them;
