@@ -153,6 +153,20 @@ class IsdfTrajRetimeInfo(C.Structure):
                 ("duration_out", C.c_double), ("limits", IsdfTrajLimitsInfo), ("check", IsdfTrajCheckInfo), ("device_ms", C.c_double)]
 
 
+REALLOC_OK, REALLOC_ALREADY, REALLOC_NOT_REACHED = 0, 1, 2
+TRAJ_REALLOC_MAX_ROUNDS, TRAJ_REALLOC_MAX_N = 16, 400
+
+
+class IsdfTrajReallocParams(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("check", C.c_int32), ("headroom", C.c_double), ("f_max", C.c_double), ("limits", IsdfTrajLimitsParams)]
+
+
+class IsdfTrajReallocInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rounds", C.c_int32), ("pieces_changed", C.c_int32), ("binding", C.c_int32), ("checked", C.c_int32),
+                ("reserved", C.c_int32), ("duration_in", C.c_double), ("duration_out", C.c_double), ("max_factor", C.c_double),
+                ("limits", IsdfTrajLimitsInfo), ("check", IsdfTrajCheckInfo), ("device_ms", C.c_double)]
+
+
 class IsdfPointsMergeInfo(C.Structure):
     _fields_ = [("M_before", C.c_int32), ("M_after", C.c_int32), ("n_rows", C.c_int32), ("n_added", C.c_int32),
                 ("n_duplicate", C.c_int32), ("n_outside", C.c_int32), ("reserved", C.c_int32 * 2), ("merge_ms", C.c_double)]
@@ -201,6 +215,8 @@ EXPORTED_SYMBOLS = [
     "isdf_traj_sample", "isdf_traj_sample_device", "isdf_traj_sample_host", "isdf_traj_limits_sizes",
     "isdf_traj_retime_params_default", "isdf_traj_retime", "isdf_traj_retime_device", "isdf_traj_retime_batch", "isdf_traj_retime_host",
     "isdf_traj_scale_host", "isdf_traj_retime_sizes",
+    "isdf_traj_realloc_params_default", "isdf_traj_realloc", "isdf_traj_realloc_device", "isdf_traj_realloc_batch", "isdf_traj_realloc_host",
+    "isdf_traj_minco_host", "isdf_traj_realloc_sizes",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -388,6 +404,20 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfTrajRetimeParams), C.sizeof(IsdfTrajRetimeInfo)]:
         raise RuntimeError(f"isdf_traj_retime structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfTrajRetimeParams), C.sizeof(IsdfTrajRetimeInfo)]}")
+    ap, ai = C.POINTER(IsdfTrajReallocParams), C.POINTER(IsdfTrajReallocInfo)
+    lib.isdf_traj_realloc_params_default.argtypes = [ap]
+    lib.isdf_traj_realloc_params_default.restype = None
+    lib.isdf_traj_realloc_sizes.argtypes = [ip]
+    lib.isdf_traj_realloc_sizes.restype = None
+    lib.isdf_traj_realloc.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, ap, dp, dp, ai]
+    lib.isdf_traj_realloc_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ap, C.c_void_p, C.c_void_p, ai, C.c_void_p]
+    lib.isdf_traj_realloc_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp, ap, dp, dp, ai]
+    lib.isdf_traj_realloc_host.argtypes = [C.POINTER(IsdfConfig), C.c_int, dp, dp, dp, dp, ap, dp, dp, ai]
+    lib.isdf_traj_minco_host.argtypes = [C.c_int, dp, dp, dp, dp, dp]
+    lib.isdf_traj_realloc_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfTrajReallocParams), C.sizeof(IsdfTrajReallocInfo)]:
+        raise RuntimeError(f"isdf_traj_realloc structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfTrajReallocParams), C.sizeof(IsdfTrajReallocInfo)]}")
     if path is None:
         _lib = lib
     return lib

@@ -27,6 +27,8 @@ int isdf_traj_limits_launch(isdf_ctx *c, int B, int N, const double *d_T, const 
 void isdf_traj_limits_unpack(const isdf_config &cfg, const isdf_traj_limits_params *p, const double *words, isdf_traj_limits_info *info);
 struct TrajRetimeState;         // traj_retime.hip: scratch of the retiming (ladder copies, piece rows, reports, search state)
 void isdf_traj_retime_release_all(isdf_ctx *c);       // traj_retime.hip: drops it
+struct TrajReallocState;        // traj_realloc.hip: scratch of the per-piece re-allocation (iterate, piece rows, reports, state)
+void isdf_traj_realloc_release_all(isdf_ctx *c);      // traj_realloc.hip: drops it
 int isdf_traj_check_ready(isdf_ctx *c);               // traj_check.hip: what isdf_traj_check needs of the ctx (shape, occupancy grid), or the error
 
 // What the swept-volume kernels need per point set (SweptParams): the optimizer step's (the ctx holds it) or the field query's
@@ -57,6 +59,7 @@ struct isdf_ctx {
     TrajCheckState *tck = nullptr;              // isdf_traj_check*: the kept report rows
     TrajLimitsState *tlm = nullptr;             // isdf_traj_limits* / isdf_traj_sample*: own scratch (grows only)
     TrajRetimeState *trt = nullptr;             // isdf_traj_retime*: own scratch (grows only)
+    TrajReallocState *tra = nullptr;            // isdf_traj_realloc*: own scratch (grows only)
     const double *v1_tstar_stage = nullptr;     // set by the host-direct V1 step for ONE eval_device_impl call (SweptParams::tstar_stage)
     DevBuf<double> d_esdf_stage;        // isdf_esdf_sample's staging (points | values | gradients): grows only, no allocation per call
     DevBuf<float> d_esdf_bricks; bool bricks_stale = true;     // the ESDF as 2 x 2 x 2-cell bricks with apron, one 128-byte line each (map_build.hip: scattered points)
@@ -191,7 +194,7 @@ struct isdf_ctx {
     DevBuf<double> d_mpart;         // every shard of a multi-device step writes [packed outputs | 8 statistics as doubles] here
     DevBuf<double> d_mstage;        // lead, staged mode: the peers' parts copied next to each other
     // every buffer above frees itself; the states held by pointer are dropped here (isdf_destroy makes the device current)
-    ~isdf_ctx() { isdf_swept_release_all(this); isdf_traj_check_release_all(this); isdf_traj_limits_release_all(this); isdf_traj_retime_release_all(this); }
+    ~isdf_ctx() { isdf_swept_release_all(this); isdf_traj_check_release_all(this); isdf_traj_limits_release_all(this); isdf_traj_retime_release_all(this); isdf_traj_realloc_release_all(this); }
 };
 namespace isdf { struct XFuse; }
 // xchg.hip: fills the in-kernel exchange block of a fused step when isdf_xchg_fuse is on (returns false: not requested;

@@ -201,6 +201,71 @@ def traj_retime_host(cfg, T, coeffs_colmajor, lib=None, **params):
     return traj_retime_report(info, To, Co)
 
 
+def traj_realloc_params(lib, rounds=None, headroom=None, f_max=None, check=False, **limits):
+    """isdf_traj_realloc_params from its defaults; None keeps a default.  limits: the keywords of traj_limits_params."""
+    p = capi.IsdfTrajReallocParams()
+    lib.isdf_traj_realloc_params_default(C.byref(p))
+    for name, v, conv in (("rounds", rounds, int), ("headroom", headroom, float), ("f_max", f_max, float)):
+        if v is not None:
+            setattr(p, name, conv(v))
+    p.check = 1 if check else 0
+    p.limits = traj_limits_params(lib, **limits)
+    return p
+
+
+def traj_realloc_report(info, T_out=None, coeffs_out=None):
+    """An isdf_traj_realloc_info as a dict: its scalars, "limits" (the dict traj_limits returns, of the result), "check" (a dict of the
+    isdf_traj_check_info fields, or None when nothing was checked), and the arrays "T" and "coeffs" (None: they are on the device)."""
+    d = {}
+    for name, _ in capi.IsdfTrajReallocInfo._fields_:
+        if name not in ("limits", "check", "reserved"):
+            d[name] = getattr(info, name)
+    d["limits"] = traj_limits_report(info.limits)
+    d["check"] = _struct_dict(info.check) if info.checked else None
+    d["T"], d["coeffs"] = T_out, coeffs_out
+    return d
+
+
+def _realloc_arrays(head_pva, tail_pva, Q, T):
+    """One trajectory's inputs as flat arrays: head / tail position | velocity | acceleration (9), Q (N - 1) x 3 point-major, T (N)."""
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+    h = np.ascontiguousarray(head_pva, dtype=np.float64).reshape(-1)
+    t = np.ascontiguousarray(tail_pva, dtype=np.float64).reshape(-1)
+    q = np.zeros(3) if Q is None else np.ascontiguousarray(Q, dtype=np.float64).reshape(-1)
+    if h.size != 9 or t.size != 9:
+        raise ValueError("head_pva and tail_pva hold 9 doubles each: position, velocity, acceleration")
+    if T.size > 1 and q.size != 3 * (T.size - 1):
+        raise ValueError(f"waypoints: {q.size} doubles for {T.size} pieces (3 per inner waypoint)")
+    if T.size <= 1:
+        q = np.zeros(3)
+    return h, t, q, T
+
+
+def traj_minco_host(head_pva, tail_pva, Q, T, lib=None):
+    """isdf_traj_minco_host: the MINCO (s = 3) coefficients (6N x 3 column-major, flat) through the waypoints Q with durations T."""
+    lib = lib or capi.load_library()
+    h, t, q, T = _realloc_arrays(head_pva, tail_pva, Q, T)
+    Co = np.zeros(18 * T.size)
+    rc = lib.isdf_traj_minco_host(T.size, _p(h), _p(t), _p(q), _p(T), _p(Co))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, (lib.isdf_last_error(None) or b"").decode())
+    return Co
+
+
+def traj_realloc_host(cfg, head_pva, tail_pva, Q, T, lib=None, **params):
+    """isdf_traj_realloc_host: the per-piece re-allocation in plain host code (no ctx, no device); the dict of traj_realloc_report."""
+    lib = lib or capi.load_library()
+    h, t, q, T = _realloc_arrays(head_pva, tail_pva, Q, T)
+    params.pop("check", None)
+    p = traj_realloc_params(lib, **params)
+    info = capi.IsdfTrajReallocInfo()
+    To, Co = np.zeros_like(T), np.zeros(18 * T.size)
+    rc = lib.isdf_traj_realloc_host(C.byref(cfg), T.size, _p(h), _p(t), _p(q), _p(T), C.byref(p), _p(To), _p(Co), C.byref(info))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, (lib.isdf_last_error(None) or b"").decode())
+    return traj_realloc_report(info, To, Co)
+
+
 class Engine:
     def __init__(self, cfg, lib=None, devices=None):
         """devices: None = one device (cfg.device); a list = ONE ctx over those devices (isdf_create_multi), used like any other."""
@@ -686,6 +751,46 @@ class Engine:
         if info.checked:
             self._traj_check_rows = int(info.check.n_below_margin)
         return traj_retime_report(info)
+
+    # ---- re-allocating piece durations to the dynamic limits (isdf_traj_realloc*)
+    def traj_realloc(self, head_pva, tail_pva, Q, T, **params):
+        """Slows down only the pieces that are over a limit, keeps the waypoints Q and solves MINCO again, until the limits report is
+        clean: the dict of traj_realloc_report.  params: rounds, headroom, f_max, check (True: the result goes through the clearance
+        check), and the limits' keywords (samples, tol_t, max_acc, max_thrust, min_thrust)."""
+        h, t, q, T = _realloc_arrays(head_pva, tail_pva, Q, T)
+        p = traj_realloc_params(self.lib, **params)
+        info = capi.IsdfTrajReallocInfo()
+        To, Co = np.zeros_like(T), np.zeros(18 * T.size)
+        self._check(self.lib.isdf_traj_realloc(self.h, T.size, _p(h), _p(t), _p(q), _p(T), C.byref(p), _p(To), _p(Co), C.byref(info)))
+        if info.checked:
+            self._traj_check_rows = int(info.check.n_below_margin)
+        return traj_realloc_report(info, To, Co)
+
+    def traj_realloc_batch(self, heads, tails, Q, T, **params):
+        """B trajectories of N pieces each (heads, tails: B x 9; Q: B x (N - 1) x 3; T: B x N), each with its own status: a list of B dicts."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 2:
+            raise ValueError("T must be B x N")
+        B, N = T.shape
+        h = np.ascontiguousarray(heads, dtype=np.float64).reshape(B, 9)
+        t = np.ascontiguousarray(tails, dtype=np.float64).reshape(B, 9)
+        q = np.ascontiguousarray(Q, dtype=np.float64).reshape(B, 3 * (N - 1)) if N > 1 else np.zeros((B, 3))
+        p = traj_realloc_params(self.lib, **params)
+        infos = (capi.IsdfTrajReallocInfo * B)()
+        To, Co = np.zeros_like(T), np.zeros((B, 18 * N))
+        self._check(self.lib.isdf_traj_realloc_batch(self.h, B, N, _p(h), _p(t), _p(q), _p(T), C.byref(p), _p(To), _p(Co), infos))
+        return [traj_realloc_report(infos[b], To[b], Co[b]) for b in range(B)]
+
+    def traj_realloc_device(self, N, d_head, d_tail, d_Q, d_T, d_T_out, d_coeffs_out, stream=0, **params):
+        """The same with every array on the device (d_head, d_tail: 9; d_Q: 3 (N - 1); d_T, d_T_out: N; d_coeffs_out: 18 N doubles);
+        "T" and "coeffs" of the dict are None."""
+        p = traj_realloc_params(self.lib, **params)
+        info = capi.IsdfTrajReallocInfo()
+        self._check(self.lib.isdf_traj_realloc_device(self.h, N, C.c_void_p(d_head), C.c_void_p(d_tail), C.c_void_p(d_Q), C.c_void_p(d_T), C.byref(p),
+                                                      C.c_void_p(d_T_out), C.c_void_p(d_coeffs_out), C.byref(info), C.c_void_p(stream)))
+        if info.checked:
+            self._traj_check_rows = int(info.check.n_below_margin)
+        return traj_realloc_report(info)
 
     def points_merge_check(self, below=None):
         """Merges the last check's kept points with value < below (None: all of them) into the obstacle-point set on the device: the

@@ -669,6 +669,84 @@ int isdf_traj_scale_host(int N, const double *T, const double *coeffs, double s,
 /* sizeof of the two structs above as the library was compiled */
 void isdf_traj_retime_sizes(int out[2]);
 
+/* ---- re-allocating piece durations to the dynamic limits --------------------------------------------------------------- */
+/* Uniform retiming lets the worst piece set the pace of the whole flight.  Re-allocation slows down only the pieces that are over
+ * a limit, keeps the path points and solves MINCO again for the new durations, until the limits report is clean.
+ * The reference has no counterpart: its back end holds vmax / omgmax / thetamax through soft penalties at K + 1 samples per piece
+ * (back_end_optimizer.hpp:453-536) and its Trajectory class only reports (trajectory.hpp:253-390, :631-680).
+ *
+ * Inputs:  N pieces; head_pva[9] and tail_pva[9] = position | velocity | acceleration (3 each); the N - 1 inner waypoints Q,
+ * point-major as isdf_pack_variables takes them (N = 1: not read, may be NULL); durations T[N].
+ * Solve:  C(T) is the MINCO (s = 3) trajectory through Q with durations T and the given end states, in the junction-state form of
+ * csrc/minco_pcr.hpp (junction rows, parallel cyclic reduction, quintic Hermite pieces): no gradient, no energy.
+ * Evaluate:  the report isdf_traj_limits* gives for (T_k, C(T_k)) under params.limits - the existing rules, no numerics of its own.
+ * Iterate k is feasible when feasible == judged.
+ * Piece factor:  for piece i and a judged channel ch whose per-piece value is STRICTLY beyond its limit, rho = value / limit for
+ * speed, body rate, tilt and largest thrust, sqrt(value / limit) for acceleration, limit / value for the smallest thrust when
+ * value > 0 and f_max otherwise.  f_i = min(f_max, (1 + headroom) * max_ch rho), never below 1; f_i = 1 exactly when no channel of
+ * the piece is over; a ratio that is NaN or infinite gives f_max.  A channel that is not judged is ignored.
+ * Update:  T_(k+1),i = T_k,i * f_i - one product, never contracted.  Durations never shrink.
+ * Rounds:  iterates k = 0 .. rounds are evaluated; the first feasible one is the result, status ISDF_REALLOC_OK and info.rounds = k
+ * (k = 0: ISDF_REALLOC_ALREADY, T_out is T bit for bit).  Iterate `rounds` still infeasible: ISDF_REALLOC_NOT_REACHED, the result is
+ * that iterate and info.limits says what still binds - isdf_traj_retime takes it from there.
+ *
+ * Errors as for isdf_traj_limits*, and ISDF_ERR_INVALID_ARG for: rounds outside 1..16, headroom negative or not finite, f_max not
+ * finite or <= 1, check != 0 in the batch form, outputs overlapping inputs (host-array forms), N above 400 in the ctx forms (the
+ * solve kernel's rows sit in LDS; isdf_traj_realloc_host takes any N).  check = 1 needs what isdf_traj_check needs (shape, occupancy
+ * grid; in the host-array form a total below 300 s of the input): its absence is reported before anything is computed.  The path
+ * between the waypoints moves when durations change, so the result then goes, still on the device, through isdf_traj_check_device
+ * with the default parameters and the ctx keeps THAT check's rows; without check the kept rows are not touched.
+ * On the device: at most 4 * (rounds + 1) launches for any B, nothing on the host between them, one synchronisation at the end (with
+ * check = 0); nothing is decided by an atomic; own scratch that grows only; the same bytes on every run; a trajectory's result does
+ * not depend on its place in a batch.  A trajectory that is done keeps its durations, and later rounds reproduce its bytes.  The
+ * device forms report a duration that is not positive and finite only at that one synchronisation (the outputs are then
+ * undefined).  The device solve and the host solve agree to rounding (the pin of minco_pcr.hpp: 1e-10 relative), not bit for bit. */
+#define ISDF_TRAJ_REALLOC_MAX_ROUNDS 16
+#define ISDF_TRAJ_REALLOC_MAX_N 400
+#define ISDF_REALLOC_OK 0            /* iterate `rounds` >= 1 is the first feasible one                                        */
+#define ISDF_REALLOC_ALREADY 1       /* the input's own durations are feasible: T_out is T bit for bit                          */
+#define ISDF_REALLOC_NOT_REACHED 2   /* iterate params.rounds is still infeasible: it is the result, limits says what binds     */
+typedef struct isdf_traj_realloc_params {
+    int32_t rounds;      /* updates at most, 1..16 (default 8)                                                                      */
+    int32_t check;       /* 1: the result goes through the clearance check (not in the batch form)                                  */
+    double headroom;     /* eta >= 0 (default 0.02): a piece over a limit is slowed by (1 + eta) times its ratio                    */
+    double f_max;        /* > 1 (default 2): the largest factor of one piece in one round                                           */
+    isdf_traj_limits_params limits;
+} isdf_traj_realloc_params;
+typedef struct isdf_traj_realloc_info {
+    int32_t status;      /* ISDF_REALLOC_*                                                                                          */
+    int32_t rounds;      /* index k of the returned iterate = updates applied                                                       */
+    int32_t pieces_changed;      /* pieces with T_out,i != T_i                                                                      */
+    int32_t binding;     /* bit ch: channel ch was over its limit on some piece of some evaluated iterate                           */
+    int32_t checked;     /* 1: `check` is filled                                                                                    */
+    int32_t reserved;
+    double duration_in, duration_out;    /* the durations summed in order, before and after                                         */
+    double max_factor;   /* the largest T_out,i / T_i                                                                               */
+    isdf_traj_limits_info limits;        /* the report of the returned arrays (device_ms: 0)                                        */
+    isdf_traj_check_info check;
+    double device_ms;    /* device time of the launches without the check's (events on the stream); 0 for the host form             */
+} isdf_traj_realloc_info;
+void isdf_traj_realloc_params_default(isdf_traj_realloc_params *p);
+/* params NULL = defaults.  T_out: N, coeffs_out: 6N x 3 column-major (both required) */
+int isdf_traj_realloc(isdf_ctx *ctx, int N, const double *head_pva, const double *tail_pva, const double *Q, const double *T,
+                      const isdf_traj_realloc_params *params, double *T_out, double *coeffs_out, isdf_traj_realloc_info *info_out);
+/* every array on the device; synchronises `stream` once, before it returns (check = 1: the check synchronises as it always does) */
+int isdf_traj_realloc_device(isdf_ctx *ctx, int N, const double *d_head_pva, const double *d_tail_pva, const double *d_Q, const double *d_T,
+                             const isdf_traj_realloc_params *params, double *d_T_out, double *d_coeffs_out,
+                             isdf_traj_realloc_info *info_out, void *stream);
+/* B trajectories of N pieces each (host arrays): heads B x 9, tails B x 9, Q B x (N - 1) x 3, T B x N; T_out B x N, coeffs_out
+ * B x 6N x 3 column-major each; every trajectory has its own status */
+int isdf_traj_realloc_batch(isdf_ctx *ctx, int B, int N, const double *heads, const double *tails, const double *Q, const double *T,
+                            const isdf_traj_realloc_params *params, double *T_out, double *coeffs_out, isdf_traj_realloc_info *infos_out);
+/* the same rules in plain host code over isdf_traj_limits_host and the host loops of csrc/minco_pcr.hpp: no ctx, no device, any N,
+ * params.check ignored */
+int isdf_traj_realloc_host(const isdf_config *cfg, int N, const double *head_pva, const double *tail_pva, const double *Q, const double *T,
+                           const isdf_traj_realloc_params *params, double *T_out, double *coeffs_out, isdf_traj_realloc_info *info_out);
+/* the solve alone: coeffs_out = C(T), 6N x 3 column-major */
+int isdf_traj_minco_host(int N, const double *head_pva, const double *tail_pva, const double *Q, const double *T, double *coeffs_out);
+/* sizeof of the two structs above as the library was compiled */
+void isdf_traj_realloc_sizes(int out[2]);
+
 /* ---- the clearance report merged into the obstacle-point set ---------------------------------------------------------- */
 /* Where the reference only warns that the optimised trajectory collides (plan_manager.cpp:306-309), the report can be fed back:
  * the points the last isdf_traj_check* kept (value < its margin), narrowed to value < below (a negative `below`: all of them;
