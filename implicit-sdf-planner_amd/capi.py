@@ -76,6 +76,17 @@ class IsdfAstarResult(C.Structure):
                 ("cspace_ms", C.c_double), ("table_ms", C.c_double), ("search_ms", C.c_double)]
 
 
+class IsdfFrontendFieldParams(C.Structure):
+    """isdf_frontend_field_params (include/isdf_accel.h)."""
+    _fields_ = [("max_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IsdfFrontendFieldInfo(C.Structure):
+    """isdf_frontend_field_info (include/isdf_accel.h)."""
+    _fields_ = [("reachable", C.c_int32), ("status", C.c_int32), ("rounds", C.c_int32), ("bricks", C.c_int32), ("brick_visits", C.c_int64),
+                ("free_voxels", C.c_int64), ("reached_voxels", C.c_int64), ("device_ms", C.c_double)]
+
+
 class IsdfPlanConfig(C.Structure):
     """isdf_plan_config: what a plan needs from the reference's yaml files (include/isdf_accel.h)."""
     _fields_ = [("sweep", IsdfConfig), ("frontend", IsdfFrontendConfig), ("occupancy_resolution", C.c_double),
@@ -217,6 +228,8 @@ EXPORTED_SYMBOLS = [
     "isdf_traj_scale_host", "isdf_traj_retime_sizes",
     "isdf_traj_realloc_params_default", "isdf_traj_realloc", "isdf_traj_realloc_device", "isdf_traj_realloc_batch", "isdf_traj_realloc_host",
     "isdf_traj_minco_host", "isdf_traj_realloc_sizes",
+    "isdf_frontend_field_params_default", "isdf_frontend_field_build", "isdf_frontend_field_get", "isdf_frontend_field_value",
+    "isdf_frontend_field_paths", "isdf_frontend_field_paths_device", "isdf_frontend_field_host", "isdf_frontend_field_release",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -328,6 +341,15 @@ def load_library(path=None):
     lib.isdf_debug_live_bytes.restype = None
     lib.isdf_frontend_astar_search.argtypes = [C.c_void_p, dp, dp, C.POINTER(IsdfAstarResult)]
     lib.isdf_frontend_astar_path.argtypes = [C.c_void_p, C.c_int, dp, dp, dp]
+    lib.isdf_frontend_field_params_default.argtypes = [C.POINTER(IsdfFrontendFieldParams)]
+    lib.isdf_frontend_field_params_default.restype = None
+    lib.isdf_frontend_field_build.argtypes = [C.c_void_p, dp, C.POINTER(IsdfFrontendFieldParams), C.POINTER(IsdfFrontendFieldInfo)]
+    lib.isdf_frontend_field_get.argtypes = [C.c_void_p, dp]
+    lib.isdf_frontend_field_value.argtypes = [C.c_void_p, dp, C.c_int, dp]
+    lib.isdf_frontend_field_paths.argtypes = [C.c_void_p, dp, C.c_int, C.c_int, C.c_void_p, dp, dp]
+    lib.isdf_frontend_field_paths_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.isdf_frontend_field_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, dp]
+    lib.isdf_frontend_field_release.argtypes = [C.c_void_p]
     lib.isdf_frontend_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, dp, dp, C.c_void_p, dp, dp, C.c_void_p]
     lib.isdf_lbfgs_params_default.argtypes = [C.POINTER(IsdfLbfgsParams)]
     lib.isdf_lbfgs_params_default.restype = None

@@ -1,0 +1,533 @@
+// Front end: the cost-to-go field of one goal over the configuration space, and paths read off it - on the device.
+// Graph = that of AstarPathSearcher::AstarGetSucc (front_end_Astar.hpp:197-236): voxel v is FREE when any attitude bit of its word of
+// the configuration-space table (fe.d_cspace, left by fe_cspace_kernel) is set - occupied voxels hold 0 -, a step goes to any of the
+// 26 neighbours that is free and inside the map, its cost is edge[i*i + j*j + k*k] = sqrt(i*i + j*j + k*k) in cells (:230).
+// "Any bit set" equals the reference's checkKernelValue (sw_manager.hpp:911-942) when the parent's attitude lies on the attitude grid
+// and the grid has at most 801 attitudes: visit_kernels_by_distance (:850-909) pops at most maxdeepth + 1 = 801 attitudes, and only
+// then does its breadth-first order reach every attitude.
+//   d[goal] = 0;  d[v] = min over free neighbours u of fl(d[u] + w(u, v)) for free v, the least fixed point from +inf (fp64, one plain
+//   addition per candidate); +inf where v is not free or cannot reach the goal.
+// Addition is monotone and every intermediate value is the length of a real path summed from the goal outward, so every relaxation
+// order that reaches a fixed point reaches the same BYTES - those of frontend_field_host.hpp's Dijkstra.
+//   ff_init_kernel     one wavefront per 64 consecutive z: the free bits of the column (one ballot -> one 64-bit word), d = +inf, d[goal] = 0,
+//                      the goal's brick as the first active list, the count of free voxels;
+//   ff_relax_kernel    one workgroup per ACTIVE brick of 8 x 8 x 64 voxels (z fastest, 64 consecutive z per wavefront as in
+//                      fe_cspace_kernel): the brick and its one-voxel halo of d in LDS (10 x 10 x 66 doubles, 52.8 KB: three workgroups per
+//                      CU; a wavefront's 64 lanes read 64 consecutive doubles, which ds_read_b64 serves without bank conflicts), the
+//                      brick's free bits in a register; Jacobi relaxation inside LDS until nothing in the brick changes; the lowered
+//                      voxels are stored and every neighbouring brick whose halo was lowered is flagged;
+//   ff_compact_kernel  one workgroup: flags -> the next round's list in brick order (a scan, no atomics) and its length, also written to the
+//                      host's pinned word.
+// A round is ff_relax_kernel over the list + ff_compact_kernel; the host reads one word, the next list's length, and stops at 0.  No
+// workgroup waits for another inside a kernel.  A brick is stored by its own workgroup only (a brick is in a list once); a neighbour
+// that reads a halo voxel while it is being lowered sees the old or the new value (8-byte relaxed atomic accesses), both lengths of real
+// paths, and is flagged by the writer, so it runs again next round with the new value in sight: the fixed point does not depend on which
+// it saw.  Only counts of events (free voxels, bricks seen) go through integer atomics; nothing is decided by their order.
+//   ff_paths_kernel    one lane per start: the steepest walk down the field with the A*'s attitude bookkeeping (below).
+// Compiled with -ffp-contract=off like frontend.hip (cell indices and cube centres round like the A*'s).
+#include "isdf_ctx.hpp"
+#include "frontend_field_host.hpp"
+#include <cmath>
+#include <limits>
+#include <vector>
+
+namespace isdf {
+
+constexpr int FF_BX = 8, FF_BY = 8, FF_BZ = 64;
+constexpr int FF_TX = FF_BX + 2, FF_TY = FF_BY + 2, FF_TZ = FF_BZ + 2;
+constexpr int FF_PER_LANE = FF_BX * FF_BY / 4;             // columns of the brick per wavefront (4 wavefronts)
+constexpr int FF_CNT_ACTIVE = 0, FF_CNT_FREE = 1, FF_CNT_REACHED = 2, FF_CNT_BRICKS = 3, FF_CNT_WORDS = 4;
+
+struct FfDims {
+    int X, Y, Z, nbx, nby, nbz, zblocks, nw;
+    double w1, w2, w3;                                     // sqrt(1), sqrt(2), sqrt(3) as the host's std::sqrt gives them
+    long long goal;                                        // voxel index of the goal cell, -1: outside the map
+};
+
+__device__ __forceinline__ double ff_load(const double *p) {
+    return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ void ff_store(double *p, double v) {
+    __hip_atomic_store((unsigned long long *)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void ff_init_kernel(FfDims D, const unsigned *__restrict__ cspace, unsigned long long *__restrict__ fm,
+                                                       double *__restrict__ d, int *__restrict__ list, unsigned long long *__restrict__ cnt) {
+    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long n_wv = (long long)D.X * D.Y * D.zblocks;
+    if (wv >= n_wv) return;
+    const int lane = threadIdx.x & 63;
+    const int zb = (int)(wv % D.zblocks);
+    const long long xy = wv / D.zblocks;
+    const int z = (zb << 6) + lane;
+    bool fr = false;
+    const long long v = xy * D.Z + z;
+    if (z < D.Z) {
+        const unsigned *m = cspace + (size_t)v * D.nw;
+        unsigned any = 0;
+        for (int w = 0; w < D.nw; w++) any |= m[w];
+        fr = any != 0u;
+        const bool is_goal = fr && v == D.goal;
+        d[v] = is_goal ? 0.0 : __longlong_as_double(0x7FF0000000000000ll);
+        if (is_goal) {
+            const int x = (int)(xy / D.Y), y = (int)(xy % D.Y);
+            list[0] = ((x / FF_BX) * D.nby + y / FF_BY) * D.nbz + zb;
+            cnt[FF_CNT_ACTIVE] = 1ull;
+        }
+    }
+    const unsigned long long bits = __ballot(fr);
+    if (lane == 0) {
+        fm[wv] = bits;
+        if (bits) atomicAdd(cnt + FF_CNT_FREE, (unsigned long long)__popcll(bits));
+    }
+}
+
+__device__ __forceinline__ int ff_tile(int tx, int ty, int tz) { return (tx * FF_TY + ty) * FF_TZ + tz; }
+
+__global__ __launch_bounds__(256) void ff_relax_kernel(FfDims D, const int *__restrict__ list, double *d, const unsigned long long *__restrict__ fm,
+                                                        unsigned *flags, unsigned *seen, unsigned long long *cnt) {
+    __shared__ double tile[FF_TX * FF_TY * FF_TZ];
+    __shared__ unsigned s_mark;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = list[blockIdx.x];
+    const int bz = b % D.nbz, by = (b / D.nbz) % D.nby, bx = b / (D.nbz * D.nby);
+    const int x0 = bx * FF_BX, y0 = by * FF_BY, z0 = bz * FF_BZ;
+    const double inf = __longlong_as_double(0x7FF0000000000000ll);
+    if (tid == 0) {
+        s_mark = 0u;
+        if (!seen[b]) { seen[b] = 1u; atomicAdd(cnt + FF_CNT_BRICKS, 1ull); }           // (a brick is in a list once: its own workgroup only)
+    }
+    for (int c = wave; c < FF_TX * FF_TY; c += 4) {
+        const int tx = c / FF_TY, ty = c - tx * FF_TY;
+        const int gx = x0 + tx - 1, gy = y0 + ty - 1;
+        const bool in_xy = gx >= 0 && gx < D.X && gy >= 0 && gy < D.Y;
+        for (int tz = lane; tz < FF_TZ; tz += 64) {
+            const int gz = z0 + tz - 1;
+            double v = inf;
+            if (in_xy && gz >= 0 && gz < D.Z) v = ff_load(d + ((size_t)gx * D.Y + gy) * D.Z + gz);
+            tile[ff_tile(tx, ty, tz)] = v;
+        }
+    }
+    // this lane's voxels: column c = wave + 4 i of the brick (cx = i / 2, cy = 4 (i & 1) + wave), z = z0 + lane
+    unsigned fbits = 0u;
+#pragma unroll
+    for (int i = 0; i < FF_PER_LANE; i++) {
+        const int gx = x0 + (i >> 1), gy = y0 + 4 * (i & 1) + wave;
+        if (gx < D.X && gy < D.Y && ((fm[((size_t)gx * D.Y + gy) * D.zblocks + bz] >> lane) & 1ull)) fbits |= 1u << i;
+    }
+    __syncthreads();
+    double own[FF_PER_LANE];
+#pragma unroll
+    for (int i = 0; i < FF_PER_LANE; i++) own[i] = tile[ff_tile((i >> 1) + 1, 4 * (i & 1) + wave + 1, lane + 1)];
+    unsigned low = 0u;
+    for (;;) {
+        double nv[FF_PER_LANE];
+        unsigned ch = 0u;
+#pragma unroll
+        for (int i = 0; i < FF_PER_LANE; i++) {
+            nv[i] = own[i];
+            if ((fbits >> i) & 1u) {
+                const double *p = tile + ff_tile(i >> 1, 4 * (i & 1) + wave, lane);      // the (-1, -1, -1) neighbour
+                double m = own[i];
+#pragma unroll
+                for (int a = 0; a < 3; a++)
+#pragma unroll
+                    for (int e = 0; e < 3; e++)
+#pragma unroll
+                        for (int g = 0; g < 3; g++) {
+                            const int q = (a != 1) + (e != 1) + (g != 1);
+                            if (q == 0) continue;
+                            const double cand = p[(a * FF_TY + e) * FF_TZ + g] + (q == 1 ? D.w1 : q == 2 ? D.w2 : D.w3);
+                            m = cand < m ? cand : m;
+                        }
+                nv[i] = m;
+                if (m < own[i]) ch |= 1u << i;
+            }
+        }
+        __syncthreads();                                   // every read of this sweep is done
+#pragma unroll
+        for (int i = 0; i < FF_PER_LANE; i++)
+            if ((ch >> i) & 1u) { own[i] = nv[i]; tile[ff_tile((i >> 1) + 1, 4 * (i & 1) + wave + 1, lane + 1)] = nv[i]; }
+        low |= ch;
+        if (!__syncthreads_or((int)ch)) break;
+    }
+    // store what fell; flag the neighbouring bricks that have a lowered voxel in their halo
+    unsigned mk = 0u;
+#pragma unroll
+    for (int i = 0; i < FF_PER_LANE; i++) {
+        if (!((low >> i) & 1u)) continue;
+        const int cx = i >> 1, cy = 4 * (i & 1) + wave;
+        ff_store(d + ((size_t)(x0 + cx) * D.Y + (y0 + cy)) * D.Z + (z0 + lane), own[i]);
+        const int xs = cx == 0 ? -1 : cx == FF_BX - 1 ? 1 : 0, ys = cy == 0 ? -1 : cy == FF_BY - 1 ? 1 : 0, zs = lane == 0 ? -1 : lane == FF_BZ - 1 ? 1 : 0;
+        for (int a = 0; a < 2; a++)
+            for (int e = 0; e < 2; e++)
+                for (int g = 0; g < 2; g++) {
+                    const int ax = a ? xs : 0, ay = e ? ys : 0, az = g ? zs : 0;
+                    if (ax | ay | az) mk |= 1u << ((ax + 1) * 9 + (ay + 1) * 3 + (az + 1));
+                }
+    }
+    if (mk) atomicOr(&s_mark, mk);
+    __syncthreads();
+    if (tid < 27 && ((s_mark >> tid) & 1u)) {
+        const int nx = bx + tid / 9 - 1, ny = by + (tid / 3) % 3 - 1, nz = bz + tid % 3 - 1;
+        if (nx >= 0 && nx < D.nbx && ny >= 0 && ny < D.nby && nz >= 0 && nz < D.nbz) flags[(nx * D.nby + ny) * D.nbz + nz] = 1u;
+    }
+}
+
+__global__ __launch_bounds__(1024) void ff_compact_kernel(unsigned *flags, int *__restrict__ list, unsigned long long *cnt, unsigned long long *host_cnt, int n_bricks) {
+    __shared__ int s_sum[1024];
+    const int tid = threadIdx.x;
+    const int chunk = (n_bricks + 1023) / 1024;
+    const int b0 = min(tid * chunk, n_bricks), b1 = min(b0 + chunk, n_bricks);
+    int k = 0;
+    for (int b = b0; b < b1; b++) k += flags[b] != 0u;
+    s_sum[tid] = k;
+    __syncthreads();
+    for (int s = 1; s < 1024; s <<= 1) {
+        const int add = tid >= s ? s_sum[tid - s] : 0;
+        __syncthreads();
+        s_sum[tid] += add;
+        __syncthreads();
+    }
+    int off = s_sum[tid] - k;
+    for (int b = b0; b < b1; b++)
+        if (flags[b]) { list[off++] = b; flags[b] = 0u; }
+    if (tid == 1023) { cnt[FF_CNT_ACTIVE] = (unsigned long long)s_sum[1023]; host_cnt[FF_CNT_ACTIVE] = (unsigned long long)s_sum[1023]; }     // (host_cnt: pinned, device-mapped)
+}
+
+__global__ __launch_bounds__(256) void ff_count_kernel(const double *__restrict__ d, long long n, unsigned long long *cnt) {
+    unsigned long long k = 0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) k += d[t] < __longlong_as_double(0x7FF0000000000000ll);
+    for (int s = 32; s > 0; s >>= 1) k += __shfl_down(k, s);
+    if ((threadIdx.x & 63) == 0 && k) atomicAdd(cnt + FF_CNT_REACHED, k);
+}
+
+// GridMap3D::isInMap / getGridIndex as isdf_frontend_astar_search restates them (Gridmap3D.cpp:41-69,135-175)
+struct FfMap { int X, Y, Z; double res, bmin[3], bmax[3]; };
+__host__ __device__ inline bool ff_cell(const FfMap &M, const double p[3], int idx[3]) {
+    for (int a = 0; a < 3; a++) if (p[a] < M.bmin[a]) return false;
+    for (int a = 0; a < 3; a++) if (p[a] > M.bmax[a]) return false;
+    const int dims[3] = {M.X, M.Y, M.Z};
+    for (int a = 0; a < 3; a++) {
+        const double dd = p[a] - M.bmin[a];
+        int i = (int)floor(dd / M.res);
+        if (i < 0) i = 0;
+        if (i >= dims[a]) i = dims[a] - 1;
+        idx[a] = i;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void ff_value_kernel(FfMap M, const double *__restrict__ d, const double *__restrict__ xyz, int n, double *__restrict__ out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const double p[3] = {xyz[3 * (size_t)t], xyz[3 * (size_t)t + 1], xyz[3 * (size_t)t + 2]};
+    int c[3];
+    out[t] = ff_cell(M, p, c) ? d[((size_t)c[0] * M.Y + c[1]) * M.Z + c[2]] : __longlong_as_double(0x7FF0000000000000ll);
+}
+
+// One lane per start.  From the start's cell, step to the neighbour u that minimises fl(d[u] + w) - the first one in the A*'s i, j, k loop
+// order (:207-211) among equals - until the goal cell; d is +inf on voxels that are not free, so only free voxels are stepped on, while
+// the start cell itself need not be free (the A* never tests it, :260-278).  Attitudes as checkKernelValue would give them walking that
+// way: the start at roll = pitch = 0, then the first set bit of the node's word in the breadth-first order of the previous node's
+// attitude, roll = fr + (ri - fi) * ang_res (sw_manager.hpp:914-932); a node whose word has no bit in that order keeps its parent's
+// attitude (cannot happen under the condition in this file's header).  A path longer than cap is walked to its end and truncated.
+struct FfWalk {
+    FfMap M;
+    int gx, gy, gz, reachable;
+    int xk, yk, nw, seq_stride;
+    double max_roll, max_pitch, ang_res, w1, w2, w3;
+};
+
+__global__ __launch_bounds__(64) void ff_paths_kernel(FfWalk W, const double *__restrict__ d, const unsigned *__restrict__ cspace,
+                                                       const unsigned short *__restrict__ seq, const int *__restrict__ seq_len,
+                                                       const double *__restrict__ starts, int B, int cap, int *__restrict__ n_out,
+                                                       double *__restrict__ xyz, double *__restrict__ rp) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B) return;
+    const FfMap &M = W.M;
+    const double p[3] = {starts[3 * (size_t)t], starts[3 * (size_t)t + 1], starts[3 * (size_t)t + 2]};
+    int c[3];
+    if (!W.reachable || !ff_cell(M, p, c)) { n_out[t] = 0; return; }
+    const double inf = __longlong_as_double(0x7FF0000000000000ll);
+    double roll = 0.0, pitch = 0.0;
+    const long long max_steps = (long long)M.X * M.Y * M.Z;
+    long long n = 0;
+    double *oxyz = xyz + (size_t)t * cap * 3, *orp = rp + (size_t)t * cap * 2;
+    for (;;) {
+        const bool at_goal = c[0] == W.gx && c[1] == W.gy && c[2] == W.gz;
+        double best = inf;
+        int bi = 0, bj = 0, bk = 0;
+        if (!at_goal) {
+            for (int i = -1; i < 2; i++)
+                for (int j = -1; j < 2; j++)
+                    for (int k = -1; k < 2; k++) {
+                        if (!(i | j | k)) continue;
+                        const int vx = c[0] + i, vy = c[1] + j, vz = c[2] + k;
+                        if (vx < 0 || vx >= M.X || vy < 0 || vy >= M.Y || vz < 0 || vz >= M.Z) continue;
+                        const int q = i * i + j * j + k * k;
+                        const double cand = d[((size_t)vx * M.Y + vy) * M.Z + vz] + (q == 1 ? W.w1 : q == 2 ? W.w2 : W.w3);
+                        if (cand < best) { best = cand; bi = i; bj = j; bk = k; }
+                    }
+            if (!(best < inf)) { n = 0; break; }                                // every neighbour is +inf: no path (only at a start: nothing is written)
+        }
+        if (n < cap) {
+            oxyz[3 * n] = (c[0] + 0.5) * M.res + M.bmin[0];                   // getGridCubeCenter, Gridmap3D.cpp:182-194
+            oxyz[3 * n + 1] = (c[1] + 0.5) * M.res + M.bmin[1];
+            oxyz[3 * n + 2] = (c[2] + 0.5) * M.res + M.bmin[2];
+            orp[2 * n] = roll; orp[2 * n + 1] = pitch;
+        }
+        n++;
+        if (at_goal) break;
+        if (n > max_steps) { n = 0; break; }                                    // (d falls strictly along a walk: cannot happen)
+        c[0] += bi; c[1] += bj; c[2] += bk;
+        const int fi = (int)((roll + W.max_roll) / W.ang_res), fj = (int)((pitch + W.max_pitch) / W.ang_res);
+        if (fi >= 0 && fi < W.xk && fj >= 0 && fj < W.yk) {
+            const int from = fi * W.yk + fj;
+            const unsigned short *order = seq + (size_t)from * W.seq_stride;
+            const int len = seq_len[from];
+            const unsigned *m = cspace + (((size_t)c[0] * M.Y + c[1]) * M.Z + c[2]) * W.nw;
+            for (int s = 0; s < len; s++) {
+                const int a = order[s];
+                if ((m[a >> 5] >> (a & 31)) & 1u) {
+                    const int ri = a / W.yk, rj = a - ri * W.yk;
+                    roll = roll + (ri - fi) * W.ang_res;
+                    pitch = pitch + (rj - fj) * W.ang_res;
+                    break;
+                }
+            }
+        }
+    }
+    n_out[t] = (int)n;
+}
+
+}  // namespace isdf
+
+using namespace isdf;
+
+namespace {
+
+int ff_ready(isdf_ctx *c) {
+    if (!c->peers.empty() || c->is_peer || c->rccl_comm) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "cost-to-go field on a multi-device ctx");
+    if (!c->fe.built) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_build has not been called");
+    return ISDF_OK;
+}
+
+FfMap ff_map(const isdf_ctx *c) {
+    FfMap M{};
+    M.X = c->grid.X; M.Y = c->grid.Y; M.Z = c->grid.Z; M.res = c->grid.res;
+    for (int a = 0; a < 3; a++) { M.bmin[a] = c->grid.bmin[a]; M.bmax[a] = c->grid.bmax[a]; }
+    return M;
+}
+
+FfWalk ff_walk(const isdf_ctx *c) {
+    const isdf_ctx::FrontEnd &fe = c->fe;
+    FfWalk W{};
+    W.M = ff_map(c);
+    W.gx = fe.field_goal[0]; W.gy = fe.field_goal[1]; W.gz = fe.field_goal[2]; W.reachable = fe.field_reachable ? 1 : 0;
+    W.xk = fe.xk; W.yk = fe.yk; W.nw = 4 * ((fe.xk * fe.yk + 127) / 128); W.seq_stride = fe.seq_stride;
+    W.max_roll = fe.cfg.kernel_max_roll; W.max_pitch = fe.cfg.kernel_max_pitch; W.ang_res = fe.cfg.kernel_ang_res;
+    W.w1 = std::sqrt(1.0); W.w2 = std::sqrt(2.0); W.w3 = std::sqrt(3.0);
+    return W;
+}
+
+int ff_paths_launch(isdf_ctx *c, const double *d_starts, int B, int cap, int *d_n, double *d_xyz, double *d_rp, hipStream_t st) {
+    hipLaunchKernelGGL(ff_paths_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, ff_walk(c), c->fe.d_field.get(), c->fe.d_cspace.get(),
+                       c->fe.d_seq.get(), c->fe.d_seq_len.get(), d_starts, B, cap, d_n, d_xyz, d_rp);
+    HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+
+}  // namespace
+
+extern "C" void isdf_frontend_field_params_default(isdf_frontend_field_params *out) {
+    if (!out) return;
+    *out = isdf_frontend_field_params{};
+}
+
+extern "C" int isdf_frontend_field_release(isdf_ctx *c) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    isdf_ctx::FrontEnd &fe = c->fe;
+    (void)hipSetDevice(c->device);
+    fe.d_field.release(); fe.d_field_free.release(); fe.d_field_list.release(); fe.d_field_flags.release(); fe.d_field_cnt.release();
+    fe.h_field_cnt.release();
+    fe.field_valid = false; fe.field_reachable = false;
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], const isdf_frontend_field_params *params, isdf_frontend_field_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!goal_xyz || !info_out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null goal / info");
+    if (params && params->max_rounds < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "negative max_rounds");
+    const int rdy = ff_ready(c);
+    if (rdy != ISDF_OK) return rdy;
+    isdf_ctx::FrontEnd &fe = c->fe;
+    const DevGrid &G = c->grid;
+    const size_t n_vox = (size_t)G.X * G.Y * G.Z;
+    if (n_vox > (size_t)0x7FFFFFF0) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the field indexes voxels with 31 bits");
+    *info_out = isdf_frontend_field_info{};
+    HIPCHK(c, hipSetDevice(c->device));
+    fe.field_valid = false;
+    if (!fe.d_cspace) {                                    // the table stays on the device: nothing of it comes to the host
+        const int rc = isdf_frontend_cspace(c, nullptr, nullptr);
+        if (rc != ISDF_OK) return rc;
+    }
+    FfDims D{};
+    D.X = G.X; D.Y = G.Y; D.Z = G.Z;
+    D.nbx = (G.X + FF_BX - 1) / FF_BX; D.nby = (G.Y + FF_BY - 1) / FF_BY; D.nbz = (G.Z + FF_BZ - 1) / FF_BZ;
+    D.zblocks = D.nbz; D.nw = 4 * ((fe.xk * fe.yk + 127) / 128);
+    D.w1 = std::sqrt(1.0); D.w2 = std::sqrt(2.0); D.w3 = std::sqrt(3.0);
+    const int n_bricks = D.nbx * D.nby * D.nbz;
+    int gi[3] = {-1, -1, -1};
+    const FfMap M = ff_map(c);
+    const bool goal_in = ff_cell(M, goal_xyz, gi);                                          // outside the map: reachable = 0, as the A* (:244-249)
+    D.goal = goal_in ? ((long long)gi[0] * G.Y + gi[1]) * G.Z + gi[2] : -1ll;
+    fe.field_goal[0] = gi[0]; fe.field_goal[1] = gi[1]; fe.field_goal[2] = gi[2];
+    const size_t n_cols = (size_t)G.X * G.Y * D.zblocks;
+    if (fe.d_field.reserve(c, n_vox) || fe.d_field_free.reserve(c, n_cols) || fe.d_field_list.reserve(c, (size_t)n_bricks) ||
+        fe.d_field_flags.reserve(c, 2 * (size_t)n_bricks) || fe.d_field_cnt.reserve(c, FF_CNT_WORDS) || fe.h_field_cnt.reserve(c, FF_CNT_WORDS))
+        return ISDF_ERR_HIP;
+    unsigned *flags = fe.d_field_flags.get(), *seen = flags + n_bricks;
+    unsigned long long *cnt = fe.d_field_cnt.get();
+    volatile unsigned long long *h = fe.h_field_cnt.get();
+    hipStream_t st = c->stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    long long rounds = 0, visits = 0, n_active = 0, n_free = 0;
+    int status = 0;
+    auto fetch = [&]() {                                   // the counters -> host, one synchronisation
+        hipError_t r = hipMemcpyAsync((void *)fe.h_field_cnt.get(), cnt, FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+        return r == hipSuccess ? hipStreamSynchronize(st) : r;
+    };
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ff_init_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                           fe.d_field_list.get(), cnt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = fetch();
+    if (e == hipSuccess) {
+        n_active = (long long)h[FF_CNT_ACTIVE]; n_free = (long long)h[FF_CNT_FREE];
+        // Jacobi relaxation fixes at least the voxels with one more edge on their shortest path per round: free voxels bound the rounds
+        long long bound = n_free;
+        if (params && params->max_rounds > 0 && params->max_rounds < bound) bound = params->max_rounds;
+        while (n_active > 0) {
+            if (rounds >= bound) { status = 2; break; }
+            hipLaunchKernelGGL(ff_relax_kernel, dim3((unsigned)n_active), dim3(256), 0, st, D, fe.d_field_list.get(), fe.d_field.get(), fe.d_field_free.get(), flags, seen, cnt);
+            hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
+            if ((e = hipGetLastError()) != hipSuccess) break;
+            if ((e = hipStreamSynchronize(st)) != hipSuccess) break;            // the one word the host reads per round: the next list's length
+            visits += n_active; rounds++;
+            n_active = (long long)h[FF_CNT_ACTIVE];
+        }
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)n_vox, cnt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = fetch();
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    HIPCHK(c, e);
+    fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
+    fe.field_valid = true;
+    info_out->reachable = fe.field_reachable ? 1 : 0;
+    info_out->status = fe.field_reachable ? status : 1;
+    info_out->rounds = (int32_t)rounds;
+    info_out->bricks = (int32_t)h[FF_CNT_BRICKS];
+    info_out->brick_visits = visits;
+    info_out->free_voxels = n_free;
+    info_out->reached_voxels = (long long)h[FF_CNT_REACHED];
+    info_out->device_ms = ms;
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_get(isdf_ctx *c, double *d_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!d_out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
+    const int rdy = ff_ready(c);
+    if (rdy != ISDF_OK) return rdy;
+    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_vox = (size_t)c->grid.X * c->grid.Y * c->grid.Z;
+    HIPCHK(c, hipMemcpyAsync(d_out, c->fe.d_field.get(), n_vox * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_value(isdf_ctx *c, const double *xyz, int n, double *out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (n < 0 || (n > 0 && (!xyz || !out))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad field query");
+    const int rdy = ff_ready(c);
+    if (rdy != ISDF_OK) return rdy;
+    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
+    if (n == 0) return ISDF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> buf;                                    // [xyz 3n | values n]
+    HIPCHK(c, buf.alloc((size_t)4 * n));
+    HIPCHK(c, hipMemcpyAsync(buf.get(), xyz, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(ff_value_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, ff_map(c), c->fe.d_field.get(), buf.get(), n, buf.get() + (size_t)3 * n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, buf.get() + (size_t)3 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);                                  // (before the scoped buffer goes)
+    HIPCHK(c, e);
+    HIPCHK(c, es);
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_paths_device(isdf_ctx *c, const double *d_starts_xyz, int B, int cap, int32_t *d_n_out, double *d_xyz_out,
+                                                double *d_roll_pitch_out, void *stream) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (B < 0 || cap < 1 || (B > 0 && (!d_starts_xyz || !d_n_out || !d_xyz_out || !d_roll_pitch_out))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad field path query");
+    const int rdy = ff_ready(c);
+    if (rdy != ISDF_OK) return rdy;
+    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
+    if (B == 0) return ISDF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return ff_paths_launch(c, d_starts_xyz, B, cap, d_n_out, d_xyz_out, d_roll_pitch_out, (hipStream_t)stream);
+}
+
+extern "C" int isdf_frontend_field_paths(isdf_ctx *c, const double *starts_xyz, int B, int cap, int32_t *n_out, double *xyz_out, double *roll_pitch_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (B < 0 || cap < 1 || (B > 0 && (!starts_xyz || !n_out || !xyz_out || !roll_pitch_out))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad field path query");
+    const int rdy = ff_ready(c);
+    if (rdy != ISDF_OK) return rdy;
+    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
+    if (B == 0) return ISDF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // one scoped allocation: [starts 3B | xyz 3 B cap | roll, pitch 2 B cap | n B ints]
+    const size_t n_d = (size_t)3 * B + (size_t)5 * B * cap;
+    DevBuf<double> buf;
+    HIPCHK(c, buf.alloc(n_d + ((size_t)B + 1) / 2));
+    double *d_s = buf.get(), *d_xyz = d_s + (size_t)3 * B, *d_rp = d_xyz + (size_t)3 * B * cap;
+    int *d_n = (int *)(d_rp + (size_t)2 * B * cap);
+    hipError_t e = hipMemcpyAsync(d_s, starts_xyz, (size_t)3 * B * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    // rows come back whole: what lies past a path's end is zero
+    if (e == hipSuccess) e = hipMemsetAsync(d_xyz, 0, (size_t)5 * B * cap * sizeof(double), c->stream);
+    int rc = ISDF_OK;
+    if (e == hipSuccess) rc = ff_paths_launch(c, d_s, B, cap, d_n, d_xyz, d_rp, c->stream);
+    if (e == hipSuccess && rc == ISDF_OK) e = hipMemcpyAsync(n_out, d_n, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && rc == ISDF_OK) e = hipMemcpyAsync(xyz_out, d_xyz, (size_t)3 * B * cap * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && rc == ISDF_OK) e = hipMemcpyAsync(roll_pitch_out, d_rp, (size_t)2 * B * cap * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (rc != ISDF_OK) return rc;
+    HIPCHK(c, e);
+    HIPCHK(c, es);
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_host(const uint32_t *free_mask, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_out) {
+    if (!free_mask || !dims || !goal_index || !d_out || n_att < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ISDF_ERR_INVALID_ARG;
+    const int g[3] = {goal_index[0], goal_index[1], goal_index[2]};
+    try {
+        return isdf_host::field_dijkstra(free_mask, dims[0], dims[1], dims[2], n_att, g, d_out) ? 1 : 0;
+    } catch (const std::bad_alloc &) {
+        return ISDF_ERR_HIP;
+    }
+}

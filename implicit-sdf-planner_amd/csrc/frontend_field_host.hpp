@@ -1,0 +1,81 @@
+// Cost-to-go field of one goal over the front end's free graph, host form (no device, no HIP): Dijkstra with a binary heap.
+// Graph = that of AstarPathSearcher::AstarGetSucc (front_end_Astar.hpp:197-236): voxel v is FREE when any attitude bit of its word of
+// the configuration-space table is set (occupied voxels hold 0); a step goes to any of the 26 neighbours that is free and inside the
+// map; its cost is edge[i*i + j*j + k*k] = sqrt(i*i + j*j + k*k), in cells (:230).
+//   d[goal] = 0;  d[v] = min over free neighbours u of fl(d[u] + w(u, v)) for free v, the least fixed point from +inf;
+//   +inf on voxels that are not free or cannot reach the goal; everything +inf when the goal cell is not free.
+// One plain fp64 addition per candidate (build without FMA contraction - there is no product to contract, the rule is for the record).
+// Addition is monotone and every value is a real path's length summed from the goal outward, so EVERY relaxation order that reaches a
+// fixed point reaches these bytes: the device form (frontend_field.hip) is held to this one byte for byte.
+// "Any bit set" equals the reference's checkKernelValue (sw_manager.hpp:911-942) when the parent's attitude lies on the attitude grid
+// and the grid has at most 801 attitudes: visit_kernels_by_distance (:850-909) pops at most maxdeepth + 1 = 801 attitudes, and only
+// then does its breadth-first order reach every attitude of the grid.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <limits>
+#include <vector>
+
+namespace isdf_host {
+
+inline bool field_voxel_free(const uint32_t *mask, size_t nw, size_t v) {
+    uint32_t any = 0;
+    for (size_t w = 0; w < nw; w++) any |= mask[nw * v + w];
+    return any != 0u;
+}
+
+// mask: nw = 4 * ceil(n_att / 128) dwords per voxel, grid order (z fastest).  goal: voxel index, any component outside the map = no goal.
+// d_out: X * Y * Z doubles.  Returns true when the goal cell is inside the map and free.
+inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att, const int goal[3], double *d_out) {
+    const size_t nw = 4 * (size_t)((n_att + 127) / 128);
+    const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
+    const double inf = std::numeric_limits<double>::infinity();
+    for (size_t v = 0; v < n; v++) d_out[v] = inf;
+    if (goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z) return false;
+    const size_t g = (size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2];
+    if (!field_voxel_free(mask, nw, g)) return false;
+    double edge[4];
+    for (int q = 0; q < 4; q++) edge[q] = std::sqrt((double)q);
+    struct E { double key; size_t v; };
+    std::vector<E> heap;
+    auto push = [&](double key, size_t v) {
+        heap.push_back(E{key, v});
+        size_t i = heap.size() - 1;
+        while (i > 0) { const size_t p = (i - 1) >> 1; if (!(heap[i].key < heap[p].key)) break; std::swap(heap[i], heap[p]); i = p; }
+    };
+    auto pop = [&]() {
+        const E top = heap[0];
+        heap[0] = heap.back(); heap.pop_back();
+        const size_t m = heap.size();
+        for (size_t i = 0;;) {
+            const size_t l = 2 * i + 1, r = l + 1; size_t s = i;
+            if (l < m && heap[l].key < heap[s].key) s = l;
+            if (r < m && heap[r].key < heap[s].key) s = r;
+            if (s == i) break;
+            std::swap(heap[i], heap[s]); i = s;
+        }
+        return top;
+    };
+    d_out[g] = 0.0;
+    push(0.0, g);
+    while (!heap.empty()) {
+        const E e = pop();
+        if (e.key > d_out[e.v]) continue;                 // a stale entry: the voxel was lowered after this one was pushed
+        const int x = (int)(e.v / YZ), y = (int)((e.v / Z) % Y), z = (int)(e.v % Z);
+        for (int i = -1; i < 2; i++)
+            for (int j = -1; j < 2; j++)
+                for (int k = -1; k < 2; k++) {
+                    if (!(i | j | k)) continue;
+                    const int vx = x + i, vy = y + j, vz = z + k;
+                    if (vx < 0 || vx >= X || vy < 0 || vy >= Y || vz < 0 || vz >= Z) continue;
+                    const size_t u = (size_t)vx * YZ + (size_t)vy * Z + (size_t)vz;
+                    if (!field_voxel_free(mask, nw, u)) continue;
+                    const double cand = e.key + edge[i * i + j * j + k * k];
+                    if (cand < d_out[u]) { d_out[u] = cand; push(cand, u); }
+                }
+    }
+    return true;
+}
+
+}  // namespace isdf_host

@@ -167,6 +167,11 @@ struct isdf_ctx {
         unsigned *h_cspace = nullptr; bool h_cspace_valid = false, h_cspace_pinned = false;   // pinned when the host lets us (16 B per voxel), else pageable
         std::vector<unsigned short> h_seq; std::vector<int> h_seq_len;
         std::vector<double> path_xyz, path_rp;
+        // the cost-to-go field (frontend_field.hip): d per voxel, free bits (one 64-bit word per 64 z), the active-brick list, the
+        // [next round's flags | bricks seen], the counters and their pinned copy; all grow only, a new isdf_frontend_build drops them
+        DevBuf<double> d_field; DevBuf<unsigned long long> d_field_free; DevBuf<int> d_field_list; DevBuf<unsigned> d_field_flags;
+        DevBuf<unsigned long long> d_field_cnt; PinBuf<unsigned long long> h_field_cnt;
+        bool field_valid = false, field_reachable = false; int field_goal[3] = {-1, -1, -1};
     } fe;
     struct isdf_xchg *xchg = nullptr;           // peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip)
     isdf_progress_fn progress = nullptr;        // isdf_set_progress: the optimizer drivers' progress / cancel hook

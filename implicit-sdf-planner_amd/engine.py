@@ -266,6 +266,23 @@ def traj_realloc_host(cfg, head_pva, tail_pva, Q, T, lib=None, **params):
     return traj_realloc_report(info, To, Co)
 
 
+def frontend_field_host(free_mask, goal_index, n_att, lib=None):
+    """isdf_frontend_field_host: the cost-to-go field in plain host code (Dijkstra, no ctx, no device).  free_mask: uint32
+    [X, Y, Z, 4 * ceil(n_att / 128)] in isdf_frontend_cspace's layout; goal_index: the goal's voxel.  Returns (d [X, Y, Z], reachable)."""
+    lib = lib or capi.load_library()
+    m = np.ascontiguousarray(free_mask, dtype=np.uint32)
+    nw = 4 * ((int(n_att) + 127) // 128)
+    if m.ndim != 4 or m.shape[3] != nw:
+        raise ValueError(f"free_mask must be [X, Y, Z, {nw}]")
+    dims = np.array(m.shape[:3], dtype=np.int32)
+    g = np.ascontiguousarray(goal_index, dtype=np.int32).reshape(3)
+    d = np.zeros(m.shape[:3])
+    rc = lib.isdf_frontend_field_host(m.ctypes.data_as(C.c_void_p), dims.ctypes.data_as(C.c_void_p), int(n_att), g.ctypes.data_as(C.c_void_p), _p(d))
+    if rc < 0:
+        raise IsdfError(rc, "isdf_frontend_field_host: bad arguments")
+    return d, bool(rc)
+
+
 class Engine:
     def __init__(self, cfg, lib=None, devices=None):
         """devices: None = one device (cfg.device); a list = ONE ctx over those devices (isdf_create_multi), used like any other."""
@@ -487,6 +504,55 @@ class Engine:
         if got != n:
             raise RuntimeError(f"isdf_frontend_astar_path returned {got}, the search said {n}")
         return xyz, rp, rot, r
+
+    # ---- the cost-to-go field of one goal over the front end's free graph (csrc/frontend_field.hip), and paths read off it
+    def _grid_dims(self):
+        dims = (C.c_int * 3)()
+        o = np.zeros(3); bm = np.zeros(3)
+        self._check(self.lib.isdf_get_grid(self.h, capi.GRID_OCCUPANCY, None, capi.U8, dims, _p(o), _p(bm)))
+        return int(dims[0]), int(dims[1]), int(dims[2])
+
+    def frontend_field_build(self, goal, max_rounds=0):
+        """isdf_frontend_field_build: the field of the cell of `goal` (world coordinates); returns IsdfFrontendFieldInfo
+        (reachable, status 0 fixed point / 1 no reachable goal / 2 max_rounds hit, rounds, bricks, brick_visits, free_voxels,
+        reached_voxels, device_ms).  The configuration-space table stays on the device."""
+        g = np.ascontiguousarray(goal, dtype=np.float64).reshape(3)
+        p = capi.IsdfFrontendFieldParams()
+        self.lib.isdf_frontend_field_params_default(C.byref(p))
+        p.max_rounds = int(max_rounds)
+        info = capi.IsdfFrontendFieldInfo()
+        self._check(self.lib.isdf_frontend_field_build(self.h, _p(g), C.byref(p), C.byref(info)))
+        return info
+
+    def frontend_field(self, xyz=None):
+        """The whole field, float64 [X, Y, Z] (cells; +inf where a voxel is not free or cannot reach the goal), or, with `xyz`
+        (n, 3) world points, the values at their cells (+inf outside the map)."""
+        if xyz is None:
+            out = np.zeros(self._grid_dims())
+            self._check(self.lib.isdf_frontend_field_get(self.h, _p(out)))
+            return out
+        q = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(q.shape[0])
+        self._check(self.lib.isdf_frontend_field_value(self.h, _p(q), q.shape[0], _p(out)))
+        return out
+
+    def frontend_field_paths(self, starts, cap):
+        """Paths for B starts in one launch: (n [B] int32, xyz [B, cap, 3], roll/pitch degrees [B, cap, 2]).  n[b] is the true
+        number of nodes of path b (0: none; more than cap: truncated); rows are zero past a path's end.  xyz[b, :n[b]] is what
+        the mid end's fit takes as reference points."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        B = s.shape[0]
+        n = np.zeros(B, dtype=np.int32); xyz = np.zeros((B, int(cap), 3)); rp = np.zeros((B, int(cap), 2))
+        self._check(self.lib.isdf_frontend_field_paths(self.h, _p(s), B, int(cap), n.ctypes.data_as(C.c_void_p), _p(xyz), _p(rp)))
+        return n, xyz, rp
+
+    def frontend_field_paths_device(self, d_starts, B, cap, d_n, d_xyz, d_rp, stream=0):
+        """device pointers (ints), asynchronous on `stream`"""
+        self._check(self.lib.isdf_frontend_field_paths_device(self.h, C.c_void_p(d_starts), int(B), int(cap), C.c_void_p(d_n), C.c_void_p(d_xyz),
+                                                              C.c_void_p(d_rp), C.c_void_p(stream)))
+
+    def frontend_field_release(self):
+        self._check(self.lib.isdf_frontend_field_release(self.h))
 
     # ---- one-shot peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip); see parallel.XgmiExchange
     def xchg_create(self, rank, world, max_doubles):

@@ -1042,6 +1042,63 @@ int isdf_frontend_astar_search(isdf_ctx *ctx, const double start[3], const doubl
  * Writes at most `capacity` nodes; returns the number of nodes of the path (0 = no path), or a negative isdf_status. */
 int isdf_frontend_astar_path(isdf_ctx *ctx, int capacity, double *xyz, double *roll_pitch, double *rot);
 
+/* ---- front end: the cost-to-go field of one goal, and paths read off it ------------------------------------------------- */
+/* The search above is one chain of heap pops per start.  For MANY starts towards one goal (or one robot replanning towards a
+ * fixed goal) the same graph is solved once for every voxel, on the device, and any number of paths are read off in parallel.
+ * Graph = that of AstarPathSearcher::AstarGetSucc (planner_algorithm/front_end_Astar.hpp:197-236): a voxel is FREE when any
+ * attitude bit of its word of the isdf_frontend_cspace table is set; a step goes to any of the 26 neighbours that is free and
+ * inside the map and costs edge[i*i + j*j + k*k] = sqrt(i*i + j*j + k*k) CELLS (:230).  "Any bit set" equals checkKernelValue
+ * (sw_manager.hpp:911-942) when the parent's attitude lies on the attitude grid and the grid has at most 801 attitudes.
+ *   d[goal] = 0;  d[v] = min over free neighbours u of fl(d[u] + w(u, v)) for free v - fp64, one addition per candidate, the least
+ *   fixed point from +inf; +inf where v is not free or cannot reach the goal.
+ * Every relaxation order reaches the same bytes, those of Dijkstra with the same fl(d[u] + w): the device form (active bricks of
+ * 8 x 8 x 64 voxels relaxed in LDS, one launch per round) and isdf_frontend_field_host agree byte for byte. */
+typedef struct isdf_frontend_field_params {
+    int32_t max_rounds;         /* bound of the relaxation rounds; 0 = the proven bound, the number of free voxels            */
+    int32_t reserved;
+} isdf_frontend_field_params;
+void isdf_frontend_field_params_default(isdf_frontend_field_params *out);
+typedef struct isdf_frontend_field_info {
+    int32_t reachable;          /* 1: the goal cell is inside the map and free; 0: the whole field is +inf (the A* would     */
+                                /*    return success = 0, front_end_Astar.hpp:244-249)                                        */
+    int32_t status;             /* 0 the fixed point; 1 no reachable goal; 2 max_rounds hit: the field as it stands, an upper */
+                                /*    bound of d everywhere                                                                   */
+    int32_t rounds;             /* launches of the relaxation                                                                 */
+    int32_t bricks;             /* bricks relaxed at least once                                                               */
+    int64_t brick_visits;       /* bricks relaxed, over all rounds                                                            */
+    int64_t free_voxels;
+    int64_t reached_voxels;     /* voxels with a finite d                                                                     */
+    double device_ms;           /* device time from the first launch to the end of the last                                   */
+} isdf_frontend_field_info;
+/* Builds the field of the cell of goal_xyz (world coordinates, the cell as AstarPathSearch takes it, :250-252).  Runs the
+ * configuration-space pass if the table is not on the device yet and does NOT bring the table to the host.  params may be NULL.
+ * Needs isdf_frontend_build (else ISDF_ERR_STATE); a new isdf_frontend_build drops the field.  Not on a multi-device ctx. */
+int isdf_frontend_field_build(isdf_ctx *ctx, const double goal_xyz[3], const isdf_frontend_field_params *params, isdf_frontend_field_info *info_out);
+/* The whole field, X * Y * Z doubles in the grid's own order (z fastest). */
+int isdf_frontend_field_get(isdf_ctx *ctx, double *d_out);
+/* d at the cells of n world points (3 doubles each; the cell as getGridIndex gives it); +inf for a point outside the map. */
+int isdf_frontend_field_value(isdf_ctx *ctx, const double *xyz, int n, double *out);
+/* Paths for B starts in one launch, one lane per start.  From the start's cell the walk steps to the neighbour u that minimises
+ * fl(d[u] + w), the first in AstarGetSucc's i, j, k loop order (:207-211) among equals, until the goal cell.  The start cell need
+ * not be free (the A* never tests it, :260-278).  Per node: the cube centre (getGridCubeCenter) and the attitude checkKernelValue
+ * would give walking that way - the start at roll = pitch = 0, then the first set bit of the node's word in the breadth-first
+ * order of the previous node's attitude, roll = fr + (ri - fi) * ang_res (sw_manager.hpp:914-932), degrees.
+ * n_out[b]: nodes of path b, start and goal cells included; 0 = no path (start outside the map, all neighbours +inf, or no
+ * reachable goal); 1 = the start is in the goal cell.  A path longer than cap is reported by its true length and truncated, as
+ * isdf_frontend_astar_path does.  xyz_out: B x cap x 3, roll_pitch_out: B x cap x 2; the host form zeroes what lies past a
+ * path's end, the device form leaves it.  cap < 1 and null pointers are argument errors. */
+int isdf_frontend_field_paths(isdf_ctx *ctx, const double *starts_xyz, int B, int cap, int32_t *n_out, double *xyz_out, double *roll_pitch_out);
+/* The same with device arrays, asynchronous on `stream` (a hipStream_t); the field must not be rebuilt before it has run. */
+int isdf_frontend_field_paths_device(isdf_ctx *ctx, const double *d_starts_xyz, int B, int cap, int32_t *d_n_out, double *d_xyz_out,
+                                     double *d_roll_pitch_out, void *stream);
+/* The host form, no device and no ctx: Dijkstra with a binary heap over a caller-supplied table in isdf_frontend_cspace's layout
+ * (4 * ceil(n_att / 128) dwords per voxel, dims = {X, Y, Z}, z fastest; free = any bit set - the graph of AstarGetSucc,
+ * front_end_Astar.hpp:197-236).  goal_index: the goal's voxel; outside the map or not free => every d is +inf.
+ * Returns 1 (reachable), 0 (not), or a negative isdf_status. */
+int isdf_frontend_field_host(const uint32_t *free_mask, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_out);
+/* Frees the field and its scratch (isdf_frontend_field_build allocates again). */
+int isdf_frontend_field_release(isdf_ctx *ctx);
+
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
  * the shipped src/plan_manager/map_pcds are "FIELDS x y z / DATA ascii"): xyz_out = up to `capacity` points x 3 floats (may be
