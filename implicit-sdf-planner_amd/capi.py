@@ -87,6 +87,22 @@ class IsdfFrontendFieldInfo(C.Structure):
                 ("free_voxels", C.c_int64), ("reached_voxels", C.c_int64), ("device_ms", C.c_double)]
 
 
+MAP_UPDATE_NONE, MAP_UPDATE_INCREMENTAL, MAP_UPDATE_FULL = 0, 1, 2      # isdf_map_update_info.path
+
+
+class IsdfMapUpdateParams(C.Structure):
+    """isdf_map_update_params (include/isdf_accel.h)."""
+    _fields_ = [("max_new_voxels", C.c_int64), ("full_fraction", C.c_double), ("refresh_esdf", C.c_int32), ("refresh_frontend", C.c_int32)]
+
+
+class IsdfMapUpdateInfo(C.Structure):
+    """isdf_map_update_info (include/isdf_accel.h)."""
+    _fields_ = [("n_points", C.c_int64), ("n_new_voxels", C.c_int64), ("dirty_lo", C.c_int32 * 3), ("dirty_hi", C.c_int32 * 3),
+                ("path", C.c_int32), ("esdf_refreshed", C.c_int32), ("frontend_refreshed", C.c_int32), ("cspace_refreshed", C.c_int32),
+                ("host_table_patched", C.c_int32), ("field_dropped", C.c_int32), ("esdf_voxels_lowered", C.c_int64),
+                ("cspace_voxels_recomputed", C.c_int64), ("count_ms", C.c_double), ("esdf_ms", C.c_double), ("frontend_ms", C.c_double)]
+
+
 class IsdfPlanConfig(C.Structure):
     """isdf_plan_config: what a plan needs from the reference's yaml files (include/isdf_accel.h)."""
     _fields_ = [("sweep", IsdfConfig), ("frontend", IsdfFrontendConfig), ("occupancy_resolution", C.c_double),
@@ -230,6 +246,7 @@ EXPORTED_SYMBOLS = [
     "isdf_traj_minco_host", "isdf_traj_realloc_sizes",
     "isdf_frontend_field_params_default", "isdf_frontend_field_build", "isdf_frontend_field_get", "isdf_frontend_field_value",
     "isdf_frontend_field_paths", "isdf_frontend_field_paths_device", "isdf_frontend_field_host", "isdf_frontend_field_release",
+    "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -440,6 +457,19 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfTrajReallocParams), C.sizeof(IsdfTrajReallocInfo)]:
         raise RuntimeError(f"isdf_traj_realloc structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfTrajReallocParams), C.sizeof(IsdfTrajReallocInfo)]}")
+    up, ui = C.POINTER(IsdfMapUpdateParams), C.POINTER(IsdfMapUpdateInfo)
+    lib.isdf_map_update_params_default.argtypes = [up]
+    lib.isdf_map_update_params_default.restype = None
+    lib.isdf_map_update_sizes.argtypes = [ip]
+    lib.isdf_map_update_sizes.restype = None
+    lib.isdf_update_pointcloud.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_longlong, up, ui]
+    lib.isdf_update_voxels.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_longlong, up, ui]
+    lib.isdf_map_counts_get.argtypes = [C.c_void_p, C.c_void_p]
+    lib.isdf_frontend_cspace_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.isdf_map_update_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfMapUpdateParams), C.sizeof(IsdfMapUpdateInfo)]:
+        raise RuntimeError(f"isdf_map_update structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfMapUpdateParams), C.sizeof(IsdfMapUpdateInfo)]}")
     if path is None:
         _lib = lib
     return lib

@@ -17,11 +17,13 @@
 // This file is compiled with -ffp-contract=off: the voxelisation compares an SDF with a margin, and robots aligned with
 // the grid put voxel centres exactly ON that margin - the comparison must see the reference's roundings.
 #include "isdf_ctx.hpp"
+#include "frontend_dev.hpp"
 #include "dev_mesh.hpp"
 #include <hip/hip_ext.h>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <new>
@@ -29,13 +31,6 @@
 #include <vector>
 
 namespace isdf {
-
-struct FeParams {
-    int k, n_att, side;          // kernel_size, attitudes, (k - 1) / 2
-    double res, margin;
-    int iX, iY, iZW;             // inflated map: X + 2h, Y + 2h, dwords per z-row (one spare dword at the end of every row)
-    int X, Y, Z;
-};
 
 template <int KIND>
 __global__ __launch_bounds__(256) void fe_shape_rows_kernel(DevShape S, FeParams F, const double *__restrict__ rot, unsigned *__restrict__ rows) {
@@ -59,16 +54,7 @@ __global__ __launch_bounds__(256) void fe_map_bits_kernel(FeParams F, const uint
         const int w = (int)(t % F.iZW);
         const size_t xy = t / F.iZW;
         const int fy = (int)(xy % F.iY), fx = (int)(xy / F.iY);
-        const int x = fx - F.side, y = fy - F.side;
-        unsigned v = 0;
-        if (x >= 0 && x < F.X && y >= 0 && y < F.Y) {
-            const uint8_t *row = occ + ((size_t)x * F.Y + y) * F.Z;
-            for (int bit = 0; bit < 32; bit++) {
-                const int z = (w << 5) + bit - F.side;
-                if (z >= 0 && z < F.Z && row[z] == 1) v |= 1u << bit;
-            }
-        }
-        bits[t] = v;
+        bits[t] = fe_map_bits_word(F, occ, fx, fy, w);
     }
 }
 
@@ -167,8 +153,6 @@ __global__ __launch_bounds__(256) void fe_check_kernel(FeParams F, FeQuery Q, co
 // wave-uniform (scalar loads) and only the NON-EMPTY rows of an attitude are visited (host-built lists: the robot fills a
 // small part of its k^3 box).  Output: 4 dwords per voxel and 128 attitudes, bit a = attitude a is collision-free; occupied voxels get 0
 // (AstarGetSucc never asks about them).
-struct FeRow { unsigned off, word; };      // off = (i * iY + j) * iZW: where the tile row starts relative to the voxel's own row
-
 __global__ __launch_bounds__(256) void fe_cspace_kernel(FeParams F, const uint8_t *__restrict__ occ, const unsigned *__restrict__ bits,
                                                          const FeRow *__restrict__ rows, const int *__restrict__ row_ptr, uint4 *__restrict__ out) {
     const int zblocks = (F.Z + 63) >> 6;
@@ -180,32 +164,7 @@ __global__ __launch_bounds__(256) void fe_cspace_kernel(FeParams F, const uint8_
     const long long xy = wv / zblocks;
     const int y = (int)(xy % F.Y), x = (int)(xy / F.Y);
     const int z = (zb << 6) + lane;
-    const bool valid = z < F.Z;
-    const int zc = valid ? z : F.Z - 1;
-    const bool is_occ = occ[((size_t)x * F.Y + y) * F.Z + zc] == 1;
-    const unsigned *base = bits + ((size_t)x * F.iY + y) * F.iZW + (zc >> 5);
-    const int sh = zc & 31;
-    const unsigned kmask = (F.k >= 32) ? 0xFFFFFFFFu : ((1u << F.k) - 1u);
-    const bool work = valid && !is_occ;
-    const int nq = (F.n_att + 127) >> 7;                  // 128-attitude groups = uint4 words per voxel
-    for (int q = 0; q < nq; q++) {
-        unsigned m[4] = {0u, 0u, 0u, 0u};
-        const int a_end = min(F.n_att, (q + 1) << 7);
-        for (int a = q << 7; a < a_end; a++) {
-            const int r0 = row_ptr[a], r1 = row_ptr[a + 1];
-            unsigned hit = work ? 0u : 1u;
-            for (int r = r0; r < r1; r++) {
-                if ((r & 7) == 0 && __ballot(hit == 0u) == 0ull) break;          // every lane has already collided (or has no work)
-                const FeRow e = rows[r];                                           // wave-uniform
-                const unsigned *p = base + e.off;
-                const unsigned b0 = p[0], b1 = p[1];
-                const unsigned mb = (sh ? ((b0 >> sh) | (b1 << (32 - sh))) : b0) & kmask;
-                hit |= mb & e.word;
-            }
-            if (hit == 0u) m[(a >> 5) & 3] |= 1u << (a & 31);
-        }
-        if (valid) out[(((size_t)x * F.Y + y) * F.Z + z) * nq + q] = make_uint4(m[0], m[1], m[2], m[3]);
-    }
+    fe_cspace_voxel(F, occ, bits, rows, row_ptr, out, x, y, z, z < F.Z);
 }
 
 }  // namespace isdf
@@ -263,15 +222,6 @@ void bfs_order(int xk, int yk, int sx, int sy, std::vector<unsigned short> &out)
 void fe_free(isdf_ctx *c) {
     if (c->fe.h_cspace) { if (c->fe.h_cspace_pinned) (void)hipHostFree(c->fe.h_cspace); else std::free(c->fe.h_cspace); }
     c->fe = isdf_ctx::FrontEnd{};           // (the tables free themselves)
-}
-
-FeParams fe_params(const isdf_ctx *c) {
-    FeParams F{};
-    F.k = c->fe.cfg.kernel_size; F.n_att = c->fe.xk * c->fe.yk; F.side = (F.k - 1) / 2;
-    F.res = c->grid.res; F.margin = c->fe.margin;
-    F.X = c->grid.X; F.Y = c->grid.Y; F.Z = c->grid.Z;
-    F.iX = F.X + 2 * F.side; F.iY = F.Y + 2 * F.side; F.iZW = (F.Z + 2 * F.side + 31) / 32 + 1;
-    return F;
 }
 
 }  // namespace
@@ -386,6 +336,35 @@ extern "C" int isdf_frontend_cspace(isdf_ctx *c, uint32_t *free_mask_out, double
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     HIPCHK(c, e);
     if (kernel_ms_out) *kernel_ms_out = ms;
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_cspace_get(isdf_ctx *c, int which, uint32_t *out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!out || (which != 0 && which != 1)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad table selector or null output");
+    if (!c->fe.built) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_build has not been called");
+    const FeParams F = fe_params(c);
+    const size_t bytes = (size_t)F.X * F.Y * F.Z * 4 * (size_t)((F.n_att + 127) / 128) * sizeof(unsigned);
+    if (which == 0) {
+        if (!c->fe.d_cspace) return isdf_fail(c, ISDF_ERR_STATE, "no configuration-space table on the device (isdf_frontend_cspace has not run)");
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipMemcpyAsync(out, c->fe.d_cspace, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+        if (!c->fe.h_cspace_valid) return isdf_fail(c, ISDF_ERR_STATE, "no valid host copy of the configuration-space table (no isdf_frontend_astar_search since the map changed)");
+        std::memcpy(out, c->fe.h_cspace, bytes);
+    }
+    return ISDF_OK;
+}
+
+int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms) {
+    if (cspace_ms) *cspace_ms = 0.0;
+    if (!c->fe.built) return ISDF_OK;
+    const FeParams F = fe_params(c);
+    hipLaunchKernelGGL(fe_map_bits_kernel, dim3(2048), dim3(256), 0, c->stream, F, c->d_occ, c->fe.d_bits);
+    HIPCHK(c, hipGetLastError());
+    c->fe.h_cspace_valid = false;
+    if (c->fe.d_cspace) return isdf_frontend_cspace(c, nullptr, cspace_ms);
     return ISDF_OK;
 }
 

@@ -111,6 +111,7 @@ extern "C" int isdf_set_grid(isdf_ctx *c, const void *vox, int dtype, int nx, in
     if (kind != ISDF_GRID_OCCUPANCY && kind != ISDF_GRID_ESDF) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad grid kind");
     HIPCHK(c, hipSetDevice(c->device));
     isdf_frontend_release(c);       // the inflated bit-packed map was built from the previous grid
+    c->d_counts.release();          // a point cloud's counts describe its own occupancy only
     const size_t n = (size_t)nx * ny * nz;
     if (c->have_geom && (c->grid.X != nx || c->grid.Y != ny || c->grid.Z != nz)) {
         // new geometry: drop the other grid kind, it no longer matches
@@ -142,7 +143,7 @@ extern "C" int isdf_set_grid(isdf_ctx *c, const void *vox, int dtype, int nx, in
         if (dtype == ISDF_U8) for (size_t i = 0; i < n; i++) tmp[i] = ((const uint8_t *)vox)[i] != 0;
         else if (dtype == ISDF_F32) for (size_t i = 0; i < n; i++) tmp[i] = ((const float *)vox)[i] != 0;
         else for (size_t i = 0; i < n; i++) tmp[i] = ((const double *)vox)[i] != 0;
-        { const int rc = c->d_occ.renew(c, n); if (rc) return rc; }
+        { const int rc = c->d_occ.renew(c, (n + 3) & ~(size_t)3); if (rc) return rc; }
         HIPCHK(c, hipMemcpy(c->d_occ, tmp.data(), n, hipMemcpyHostToDevice));
     }
     c->grid.esdf = c->d_esdf;

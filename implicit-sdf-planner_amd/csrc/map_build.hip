@@ -170,6 +170,11 @@ __global__ __launch_bounds__(64) void gather_emit_kernel(DevGrid G, const unsign
 
 void launch_build_bits(const DevGrid &G, int use_esdf, double thresh, unsigned *out, hipStream_t stream);   // tile_sweep.hip
 
+// the map update's full path: the occupancy again from the kept counts (on the ctx's stream, no synchronisation)
+void launch_threshold_counts(const unsigned *counts, size_t n, unsigned thr, uint8_t *occ, hipStream_t stream) {
+    hipLaunchKernelGGL(pc_threshold_kernel, dim3(4096), dim3(256), 0, stream, counts, n, thr, occ);
+}
+
 } // namespace isdf
 
 using namespace isdf;
@@ -212,14 +217,18 @@ extern "C" int isdf_set_pointcloud(isdf_ctx *c, const float *xyz, long long n_po
     c->d_esdf.release();
     isdf_frontend_release(c);
     c->d_occ.release();
+    c->d_counts.release();
     c->grid.X = (int)dim[0]; c->grid.Y = (int)dim[1]; c->grid.Z = (int)dim[2]; c->grid.res = resolution;
     for (int a = 0; a < 3; a++) { c->grid.bmin[a] = bmin[a]; c->grid.bmax[a] = bmax[a]; }
     c->have_geom = true;
     c->grid_epoch++;
-    DevBuf<float> d_xyz; DevBuf<unsigned> d_cnt;
+    // the counts stay for isdf_update_pointcloud - except on the ctxs of a multi-device context, where the update is not offered
+    DevBuf<float> d_xyz; DevBuf<unsigned> tmp_cnt;
+    DevBuf<unsigned> &d_cnt = (!c->peers.empty() || c->is_peer) ? tmp_cnt : c->d_counts;
+    c->counts_thr = sta_threshold;
     HIPCHK(c, d_xyz.alloc((size_t)n_points * 3));
     HIPCHK(c, d_cnt.alloc(n));
-    HIPCHK(c, c->d_occ.alloc(n));
+    HIPCHK(c, c->d_occ.alloc((n + 3) & ~(size_t)3));
     HIPCHK(c, hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, n * sizeof(unsigned), c->stream));
     hipLaunchKernelGGL(pc_count_kernel, dim3(2048), dim3(256), 0, c->stream, d_xyz, n_points, c->grid, d_cnt);

@@ -395,6 +395,40 @@ class Engine:
         self._check(self.lib.isdf_get_grid(self.h, kind, out.ctypes.data_as(C.c_void_p), dt, dims, _p(o), _p(bm)))
         return out, o, bm
 
+    # ---- the map updated in place (csrc/map_update.hip)
+    def _map_update_params(self, max_new_voxels=None, full_fraction=None, refresh_esdf=True, refresh_frontend=True):
+        p = capi.IsdfMapUpdateParams()
+        self.lib.isdf_map_update_params_default(C.byref(p))
+        if max_new_voxels is not None:
+            p.max_new_voxels = int(max_new_voxels)
+        if full_fraction is not None:
+            p.full_fraction = float(full_fraction)
+        p.refresh_esdf = int(bool(refresh_esdf)); p.refresh_frontend = int(bool(refresh_frontend))
+        return p
+
+    def update_pointcloud(self, xyz, **params):
+        """isdf_update_pointcloud: NEW points (n x 3 float32) added to the map of set_pointcloud; every derived product is refreshed
+        where it can change.  params: max_new_voxels, full_fraction, refresh_esdf, refresh_frontend.  Returns IsdfMapUpdateInfo."""
+        pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        p = self._map_update_params(**params)
+        info = capi.IsdfMapUpdateInfo()
+        self._check(self.lib.isdf_update_pointcloud(self.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], C.byref(p), C.byref(info)))
+        return info
+
+    def update_voxels(self, ijk, **params):
+        """isdf_update_voxels: the listed voxels (n x 3 indices) become occupied.  Returns IsdfMapUpdateInfo."""
+        v = np.ascontiguousarray(ijk, dtype=np.int32).reshape(-1, 3)
+        p = self._map_update_params(**params)
+        info = capi.IsdfMapUpdateInfo()
+        self._check(self.lib.isdf_update_voxels(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.shape[0], C.byref(p), C.byref(info)))
+        return info
+
+    def map_counts(self):
+        """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""
+        out = np.zeros(self._grid_dims(), dtype=np.uint32)
+        self._check(self.lib.isdf_map_counts_get(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def gather_points(self, waypoints, half, offset=None):
         W = np.ascontiguousarray(np.asarray(waypoints, dtype=np.float64).reshape(-1, 3))
         h = np.asarray(half, dtype=np.float64) * np.ones(3)
@@ -482,6 +516,16 @@ class Engine:
         ms = C.c_double(0.0)
         self._check(self.lib.isdf_frontend_cspace(self.h, out.ctypes.data_as(C.c_void_p) if download else None, C.byref(ms)))
         return out, ms.value
+
+    def frontend_cspace_table(self, host=False):
+        """isdf_frontend_cspace_get: the table as it stands, not computed again - the device's, or (host=True) the copy the A* keeps
+        on the host.  Same layout as frontend_cspace()."""
+        X, Y, Z = self._grid_dims()
+        kd = (C.c_int * 3)()
+        self._check(self.lib.isdf_frontend_get_shape_kernels(self.h, None, kd))
+        out = np.zeros((X, Y, Z, 4 * ((kd[0] * kd[1] + 127) // 128)), dtype=np.uint32)
+        self._check(self.lib.isdf_frontend_cspace_get(self.h, int(bool(host)), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def host_info(self):
         """isdf_host_info: {"handovers", "late", "late_polls"} of the host-mapped result hand-overs of this ctx."""

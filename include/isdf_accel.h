@@ -1014,6 +1014,10 @@ int isdf_frontend_check(isdf_ctx *ctx, int n, const int32_t *index, const double
  * bit (i * ykernel + j) set = that attitude fits; occupied voxels get 0.  An A* that holds this table answers checkKernelValue with a few
  * bit tests in the breadth-first order instead of k^2 byte-ANDs per attitude.  kernel_ms_out (optional): device time. */
 int isdf_frontend_cspace(isdf_ctx *ctx, uint32_t *free_mask_out, double *kernel_ms_out);
+/* The table as it stands, WITHOUT computing it again (same layout): which = 0 the device's table (ISDF_ERR_STATE before the first
+ * isdf_frontend_cspace / search / field build), which = 1 the copy the A* keeps on the host (ISDF_ERR_STATE while it holds none that
+ * is valid).  What isdf_update_pointcloud / isdf_update_voxels left behind is read with this. */
+int isdf_frontend_cspace_get(isdf_ctx *ctx, int which, uint32_t *table_out);
 
 /* The SE(3) A* of the front end (AstarPathSearcher, planner_algorithm/front_end_Astar.hpp:172-403) over the table above, called
  * like PlannerManager::generatePath calls the reference's (plan_manager.cpp:181-198):
@@ -1098,6 +1102,56 @@ int isdf_frontend_field_paths_device(isdf_ctx *ctx, const double *d_starts_xyz, 
 int isdf_frontend_field_host(const uint32_t *free_mask, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_out);
 /* Frees the field and its scratch (isdf_frontend_field_build allocates again). */
 int isdf_frontend_field_release(isdf_ctx *ctx);
+
+/* ---- the map updated in place from new sensor points ---------------------------------------------------------- */
+/* isdf_set_pointcloud rebuilds everything from the full cloud.  isdf_update_pointcloud takes only the NEW points (n_points x 3
+ * floats, binned as isdf_set_pointcloud bins them: a point outside the box counts for voxel (0,0,0)), adds them to the per-voxel
+ * counts that isdf_set_pointcloud keeps, and refreshes every derived product only where it can change: the occupancy, the ESDF
+ * (new = min(old, distance to the nearest newly occupied voxel); occupancy only grows, as in the reference, whose
+ * PCSmap_manager.cpp:87-200 only counts points up), the front end's inflated bit map over the box of the new voxels and its
+ * configuration-space table - and, when the A* holds the table on the host, that copy - over the box grown by (kernel_size - 1) / 2.
+ * Afterwards every product is byte for byte what a fresh ctx holds after isdf_set_pointcloud(old ++ new) with the same explicit
+ * boundaries, resolution and threshold, then isdf_generate_esdf if an ESDF was installed (it is taken to be the exact distance
+ * transform of the occupancy), isdf_frontend_build and isdf_frontend_cspace if they had been run.
+ * The grid's geometry and the voxel indices handed out before (clearance reports, isdf_points_merge_check) stay valid; the
+ * occupancy bit grid and the ESDF bricks are rebuilt lazily as after any map change.  The V1 obstacle-point set and lastTstar are
+ * NOT touched: new obstacles reach the optimizer the usual way, through isdf_traj_check and isdf_points_merge_check.  The
+ * cost-to-go field cannot be repaired by a decrease-only relaxation when voxels close: it is dropped whenever a voxel became
+ * occupied (isdf_frontend_field_* then answer as before a build).  When no voxel became occupied nothing but the counts changes.
+ * isdf_update_voxels is the same for a map that came from isdf_set_grid, or for a caller with its own voxel list: ijk = n_voxels x 3
+ * indices to set occupied (duplicates and occupied voxels are fine; an index outside the grid: ISDF_ERR_INVALID_ARG, nothing
+ * changed).  It invalidates kept counts when it occupies a voxel.
+ * A failure (ISDF_ERR_HIP) after the counts and the occupancy have advanced leaves those two consistent and drops what was derived
+ * from the old map - the ESDF and the front end, as isdf_set_pointcloud drops them - so that nothing stale can be read.
+ * isdf_update_pointcloud: ISDF_ERR_STATE without kept counts (no isdf_set_pointcloud, or isdf_set_grid / isdf_update_voxels since).
+ * Both: a multi-device ctx ISDF_ERR_UNSUPPORTED.  params may be NULL (defaults), info_out may be NULL. */
+typedef struct isdf_map_update_params {
+    int64_t max_new_voxels;     /* more newly occupied voxels than this: rebuild everything (default 65536)                    */
+    double full_fraction;       /* the grown dirty box holds more than this share of the map's voxels: rebuild everything      */
+                                /* (default 0.5).  Both defaults are placeholders: the incremental path won at every size that */
+                                /* tools/map_update_bench.py measured, none near these caps                      */
+    int32_t refresh_esdf;       /* 1 (default): refresh the ESDF if one is installed; 0: drop it, as isdf_set_pointcloud does  */
+    int32_t refresh_frontend;   /* 1 (default): refresh the front end if built; 0: release it                                  */
+} isdf_map_update_params;
+typedef struct isdf_map_update_info {
+    int64_t n_points, n_new_voxels;     /* points (or voxel entries) counted; voxels that became occupied                      */
+    int32_t dirty_lo[3], dirty_hi[3];   /* index box of the new voxels (inclusive; lo > hi when none)                          */
+    int32_t path;                       /* 0 nothing changed, 1 incremental, 2 full rebuild (a cap of params exceeded, or an   */
+                                        /*   ESDF of a map that had no occupied voxel)                                         */
+    int32_t esdf_refreshed, frontend_refreshed, cspace_refreshed, host_table_patched;
+    int32_t field_dropped;              /* 1: a VALID cost-to-go field was dropped by this call (0 also when there was none to drop) */
+    int64_t esdf_voxels_lowered;        /* incremental path: ESDF values that fell                                             */
+    int64_t cspace_voxels_recomputed;   /* voxels of the grown box (the whole map on the full path)                            */
+    double count_ms, esdf_ms, frontend_ms;      /* device time, events on the ctx's stream                                     */
+} isdf_map_update_info;
+void isdf_map_update_params_default(isdf_map_update_params *p);
+void isdf_map_update_sizes(int sizes_out[2]);      /* sizeof of the two structs above, for mirrors of this header            */
+int isdf_update_pointcloud(isdf_ctx *ctx, const float *xyz, long long n_points, const isdf_map_update_params *params,
+                           isdf_map_update_info *info_out);
+int isdf_update_voxels(isdf_ctx *ctx, const int32_t *ijk, long long n_voxels, const isdf_map_update_params *params,
+                       isdf_map_update_info *info_out);
+/* The kept per-voxel point counts, X * Y * Z values in the grid's own order; ISDF_ERR_STATE when there are none. */
+int isdf_map_counts_get(isdf_ctx *ctx, uint32_t *counts_out);
 
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
