@@ -87,6 +87,16 @@ class IsdfFrontendFieldInfo(C.Structure):
                 ("free_voxels", C.c_int64), ("reached_voxels", C.c_int64), ("device_ms", C.c_double)]
 
 
+FIELD_REPAIR_DROP, FIELD_REPAIR_REPAIR = 0, 1           # isdf_frontend_field_set_repair
+
+
+class IsdfFieldRepairInfo(C.Structure):
+    """isdf_field_repair_info (include/isdf_accel.h)."""
+    _fields_ = [("closed_voxels", C.c_int64), ("closed_reached", C.c_int64), ("tau", C.c_double), ("reset_voxels", C.c_int64),
+                ("brick_visits", C.c_int64), ("free_voxels", C.c_int64), ("reached_voxels", C.c_int64), ("seeded_bricks", C.c_int32),
+                ("rounds", C.c_int32), ("reachable", C.c_int32), ("status", C.c_int32), ("device_ms", C.c_double)]
+
+
 MAP_UPDATE_NONE, MAP_UPDATE_INCREMENTAL, MAP_UPDATE_FULL = 0, 1, 2      # isdf_map_update_info.path
 
 
@@ -246,6 +256,7 @@ EXPORTED_SYMBOLS = [
     "isdf_traj_minco_host", "isdf_traj_realloc_sizes",
     "isdf_frontend_field_params_default", "isdf_frontend_field_build", "isdf_frontend_field_get", "isdf_frontend_field_value",
     "isdf_frontend_field_paths", "isdf_frontend_field_paths_device", "isdf_frontend_field_host", "isdf_frontend_field_release",
+    "isdf_frontend_field_set_repair", "isdf_frontend_field_repair_info", "isdf_frontend_field_repair_sizes", "isdf_frontend_field_repair_host",
     "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
 ]
 
@@ -470,6 +481,14 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfMapUpdateParams), C.sizeof(IsdfMapUpdateInfo)]:
         raise RuntimeError(f"isdf_map_update structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfMapUpdateParams), C.sizeof(IsdfMapUpdateInfo)]}")
+    lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
+    lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
+    lib.isdf_frontend_field_repair_sizes.argtypes = [ip]
+    lib.isdf_frontend_field_repair_sizes.restype = None
+    lib.isdf_frontend_field_repair_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, dp, C.POINTER(IsdfFieldRepairInfo)]
+    lib.isdf_frontend_field_repair_sizes(sz)
+    if sz[0] != C.sizeof(IsdfFieldRepairInfo):
+        raise RuntimeError(f"isdf_field_repair_info: the library has {sz[0]}, the mirror {C.sizeof(IsdfFieldRepairInfo)}")
     if path is None:
         _lib = lib
     return lib

@@ -75,3 +75,11 @@ __device__ __forceinline__ void fe_cspace_voxel(const FeParams &F, const uint8_t
 // frontend.hip, for the map update's full path: the whole inflated map again from the ctx's occupancy, the whole configuration space
 // again if there was one (device time of that pass in *cspace_ms), the host copy of the table marked stale
 int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms);
+
+// frontend_field.hip, for the map update: the cost-to-go field repaired after voxels closed (isdf_frontend_field_set_repair, mode 1).
+// ..._wanted: mode 1 and a valid field that is a fixed point (not status 2).  ..._begin enqueues the mark over the box lo .. hi
+// (null: the whole grid), the reset and the first list on the ctx's stream, after the configuration-space refresh; the caller
+// synchronises the stream; ..._end runs the rounds.  *repaired = 0: a bit had opened, the field stays dropped.
+bool isdf_field_repair_wanted(const isdf_ctx *c);
+int isdf_field_repair_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start);
+int isdf_field_repair_end(isdf_ctx *c, hipEvent_t ev_start, hipEvent_t ev_end, int *repaired);

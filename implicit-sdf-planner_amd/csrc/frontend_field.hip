@@ -24,10 +24,20 @@
 // paths, and is flagged by the writer, so it runs again next round with the new value in sight: the fixed point does not depend on which
 // it saw.  Only counts of events (free voxels, bricks seen) go through integer atomics; nothing is decided by their order.
 //   ff_paths_kernel    one lane per start: the steepest walk down the field with the A*'s attitude bookkeeping (below).
+// The field REPAIRED after a map update that closed voxels (occupancy only grows; DESIGN 4.6.2, isdf_frontend_field_set_repair):
+//   ff_repair_mark_kernel   one wavefront per 64 consecutive z of a column of the changed box: the new free ballot against the kept word;
+//                           a closed lane folds its finite old d into tau (an integer atomicMin on the bit pattern: non-negative
+//                           doubles order like their bits) and takes +inf; the new word is written; closed voxels are counted;
+//   ff_repair_reset_kernel  one workgroup per brick: +inf wherever tau <= d < +inf (tau read from device memory), the brick flagged
+//                           when it reset a voxel;
+// then ff_compact_kernel and the rounds of the build.  Every d < tau is kept: the chain of minimising neighbours from such a voxel to
+// the goal passes only voxels with d < tau, none of them closed, and the new graph is a subgraph of the old.  From the kept values
+// every intermediate value is again a real path's length, so the fixed point has the bytes of a build on the new map.
 // Compiled with -ffp-contract=off like frontend.hip (cell indices and cube centres round like the A*'s).
 #include "isdf_ctx.hpp"
 #include "frontend_field_host.hpp"
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <vector>
 
@@ -202,6 +212,78 @@ __global__ __launch_bounds__(256) void ff_count_kernel(const double *__restrict_
     if ((threadIdx.x & 63) == 0 && k) atomicAdd(cnt + FF_CNT_REACHED, k);
 }
 
+// the repair's record: [tau's bits | closed | closed with a finite d | a bit opened | reset by the threshold | bricks seeded]
+constexpr int FF_REP_TAU = 0, FF_REP_CLOSED = 1, FF_REP_CLOSED_REACHED = 2, FF_REP_OPENED = 3, FF_REP_RESET = 4, FF_REP_SEEDED = 5, FF_REP_WORDS = 8;
+constexpr unsigned long long FF_INF_BITS = 0x7FF0000000000000ull;
+
+// columns x in [x0, x0 + ex), y in [y0, y0 + ey), 64-voxel z blocks zb in [zb0, zb0 + ezb): the changed box, whole columns in z
+__global__ __launch_bounds__(256) void ff_repair_mark_kernel(FfDims D, int x0, int y0, int zb0, int ex, int ey, int ezb, const unsigned *__restrict__ cspace,
+                                                              unsigned long long *__restrict__ fm, double *__restrict__ d, unsigned long long *__restrict__ rep) {
+    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long n_wv = (long long)ex * ey * ezb;
+    if (wv >= n_wv) return;
+    const int lane = threadIdx.x & 63;
+    const int zb = zb0 + (int)(wv % ezb);
+    const long long xy = wv / ezb;
+    const int y = y0 + (int)(xy % ey), x = x0 + (int)(xy / ey);
+    const int z = (zb << 6) + lane;
+    const size_t col = (size_t)x * D.Y + y;
+    const size_t v = col * D.Z + z;
+    bool fr = false;
+    if (z < D.Z) {
+        const unsigned *m = cspace + v * D.nw;
+        unsigned any = 0;
+        for (int w = 0; w < D.nw; w++) any |= m[w];
+        fr = any != 0u;
+    }
+    const unsigned long long now = __ballot(fr);
+    const unsigned long long old = fm[col * D.zblocks + zb];
+    const unsigned long long closed = old & ~now;
+    bool reached = false;
+    if ((closed >> lane) & 1ull) {                         // (a set bit of the kept word: z < D.Z)
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(d[v]);
+        reached = bits < FF_INF_BITS;                      // d is never negative and never NaN
+        if (reached) { atomicMin(rep + FF_REP_TAU, bits); d[v] = __longlong_as_double((long long)FF_INF_BITS); }
+    }
+    const unsigned long long hit = __ballot(reached);
+    if (lane == 0 && now != old) {
+        fm[col * D.zblocks + zb] = now;
+        if (closed) atomicAdd(rep + FF_REP_CLOSED, (unsigned long long)__popcll(closed));
+        if (hit) atomicAdd(rep + FF_REP_CLOSED_REACHED, (unsigned long long)__popcll(hit));
+        if (now & ~old) rep[FF_REP_OPENED] = 1ull;        // outside the premise: the host drops the field
+    }
+}
+
+// one workgroup per brick, the lanes on the voxels as in ff_relax_kernel
+__global__ __launch_bounds__(256) void ff_repair_reset_kernel(FfDims D, double *__restrict__ d, unsigned *__restrict__ flags, unsigned long long *__restrict__ rep) {
+    __shared__ unsigned s_n;
+    const unsigned long long tau = rep[FF_REP_TAU];
+    if (tau >= FF_INF_BITS) return;                        // nothing reached has closed (the same word in every thread)
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.x;
+    const int bz = b % D.nbz, by = (b / D.nbz) % D.nby, bx = b / (D.nbz * D.nby);
+    const int x0 = bx * FF_BX, y0 = by * FF_BY, gz = bz * FF_BZ + lane;
+    if (tid == 0) s_n = 0u;
+    __syncthreads();
+    unsigned k = 0u;
+    if (gz < D.Z)
+        for (int i = 0; i < FF_PER_LANE; i++) {
+            const int gx = x0 + (i >> 1), gy = y0 + 4 * (i & 1) + wave;
+            if (gx >= D.X || gy >= D.Y) continue;
+            double *p = d + ((size_t)gx * D.Y + gy) * D.Z + gz;
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(*p);
+            if (bits >= tau && bits < FF_INF_BITS) { *p = __longlong_as_double((long long)FF_INF_BITS); k++; }
+        }
+    for (int s = 32; s > 0; s >>= 1) k += __shfl_down(k, s);
+    if (lane == 0 && k) atomicAdd(&s_n, k);
+    __syncthreads();
+    if (tid == 0 && s_n) {
+        flags[b] = 1u;
+        atomicAdd(rep + FF_REP_RESET, (unsigned long long)s_n);
+        atomicAdd(rep + FF_REP_SEEDED, 1ull);
+    }
+}
+
 // GridMap3D::isInMap / getGridIndex as isdf_frontend_astar_search restates them (Gridmap3D.cpp:41-69,135-175)
 struct FfMap { int X, Y, Z; double res, bmin[3], bmax[3]; };
 __host__ __device__ inline bool ff_cell(const FfMap &M, const double p[3], int idx[3]) {
@@ -331,6 +413,38 @@ FfWalk ff_walk(const isdf_ctx *c) {
     return W;
 }
 
+FfDims ff_dims(const isdf_ctx *c) {
+    const DevGrid &G = c->grid;
+    FfDims D{};
+    D.X = G.X; D.Y = G.Y; D.Z = G.Z;
+    D.nbx = (G.X + FF_BX - 1) / FF_BX; D.nby = (G.Y + FF_BY - 1) / FF_BY; D.nbz = (G.Z + FF_BZ - 1) / FF_BZ;
+    D.zblocks = D.nbz; D.nw = 4 * ((c->fe.xk * c->fe.yk + 127) / 128);
+    D.w1 = std::sqrt(1.0); D.w2 = std::sqrt(2.0); D.w3 = std::sqrt(3.0);
+    D.goal = -1ll;
+    return D;
+}
+
+// The rounds, shared by the build and the repair: ff_relax_kernel over the list + ff_compact_kernel, one pinned word read per round,
+// until the list is empty or `bound` rounds have run (status 2).  n_active: the length of the list as it stands.
+struct FfRounds { long long rounds = 0, visits = 0; int status = 0; };
+hipError_t ff_run_rounds(isdf_ctx::FrontEnd &fe, const FfDims &D, long long n_active, long long bound, hipStream_t st, FfRounds &R) {
+    const int n_bricks = D.nbx * D.nby * D.nbz;
+    unsigned *flags = fe.d_field_flags.get(), *seen = flags + n_bricks;
+    unsigned long long *cnt = fe.d_field_cnt.get();
+    volatile unsigned long long *h = fe.h_field_cnt.get();
+    hipError_t e = hipSuccess;
+    while (n_active > 0) {
+        if (R.rounds >= bound) { R.status = 2; break; }
+        hipLaunchKernelGGL(ff_relax_kernel, dim3((unsigned)n_active), dim3(256), 0, st, D, fe.d_field_list.get(), fe.d_field.get(), fe.d_field_free.get(), flags, seen, cnt);
+        hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) break;            // the one word the host reads per round: the next list's length
+        R.visits += n_active; R.rounds++;
+        n_active = (long long)h[FF_CNT_ACTIVE];
+    }
+    return e;
+}
+
 int ff_paths_launch(isdf_ctx *c, const double *d_starts, int B, int cap, int *d_n, double *d_xyz, double *d_rp, hipStream_t st) {
     hipLaunchKernelGGL(ff_paths_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, ff_walk(c), c->fe.d_field.get(), c->fe.d_cspace.get(),
                        c->fe.d_seq.get(), c->fe.d_seq_len.get(), d_starts, B, cap, d_n, d_xyz, d_rp);
@@ -350,8 +464,8 @@ extern "C" int isdf_frontend_field_release(isdf_ctx *c) {
     isdf_ctx::FrontEnd &fe = c->fe;
     (void)hipSetDevice(c->device);
     fe.d_field.release(); fe.d_field_free.release(); fe.d_field_list.release(); fe.d_field_flags.release(); fe.d_field_cnt.release();
-    fe.h_field_cnt.release();
-    fe.field_valid = false; fe.field_reachable = false;
+    fe.h_field_cnt.release(); fe.d_field_rep.release(); fe.h_field_rep.release();
+    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false;
     return ISDF_OK;
 }
 
@@ -367,16 +481,12 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     if (n_vox > (size_t)0x7FFFFFF0) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the field indexes voxels with 31 bits");
     *info_out = isdf_frontend_field_info{};
     HIPCHK(c, hipSetDevice(c->device));
-    fe.field_valid = false;
+    fe.field_valid = false; fe.field_repaired = false;
     if (!fe.d_cspace) {                                    // the table stays on the device: nothing of it comes to the host
         const int rc = isdf_frontend_cspace(c, nullptr, nullptr);
         if (rc != ISDF_OK) return rc;
     }
-    FfDims D{};
-    D.X = G.X; D.Y = G.Y; D.Z = G.Z;
-    D.nbx = (G.X + FF_BX - 1) / FF_BX; D.nby = (G.Y + FF_BY - 1) / FF_BY; D.nbz = (G.Z + FF_BZ - 1) / FF_BZ;
-    D.zblocks = D.nbz; D.nw = 4 * ((fe.xk * fe.yk + 127) / 128);
-    D.w1 = std::sqrt(1.0); D.w2 = std::sqrt(2.0); D.w3 = std::sqrt(3.0);
+    FfDims D = ff_dims(c);
     const int n_bricks = D.nbx * D.nby * D.nbz;
     int gi[3] = {-1, -1, -1};
     const FfMap M = ff_map(c);
@@ -387,15 +497,15 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     if (fe.d_field.reserve(c, n_vox) || fe.d_field_free.reserve(c, n_cols) || fe.d_field_list.reserve(c, (size_t)n_bricks) ||
         fe.d_field_flags.reserve(c, 2 * (size_t)n_bricks) || fe.d_field_cnt.reserve(c, FF_CNT_WORDS) || fe.h_field_cnt.reserve(c, FF_CNT_WORDS))
         return ISDF_ERR_HIP;
-    unsigned *flags = fe.d_field_flags.get(), *seen = flags + n_bricks;
+    unsigned *flags = fe.d_field_flags.get();
     unsigned long long *cnt = fe.d_field_cnt.get();
     volatile unsigned long long *h = fe.h_field_cnt.get();
     hipStream_t st = c->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(c, hipEventCreate(&e0));
     hipError_t e = hipEventCreate(&e1);
-    long long rounds = 0, visits = 0, n_active = 0, n_free = 0;
-    int status = 0;
+    long long n_free = 0;
+    FfRounds R;
     auto fetch = [&]() {                                   // the counters -> host, one synchronisation
         hipError_t r = hipMemcpyAsync((void *)fe.h_field_cnt.get(), cnt, FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
         return r == hipSuccess ? hipStreamSynchronize(st) : r;
@@ -410,19 +520,11 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     }
     if (e == hipSuccess) e = fetch();
     if (e == hipSuccess) {
-        n_active = (long long)h[FF_CNT_ACTIVE]; n_free = (long long)h[FF_CNT_FREE];
+        n_free = (long long)h[FF_CNT_FREE];
         // Jacobi relaxation fixes at least the voxels with one more edge on their shortest path per round: free voxels bound the rounds
         long long bound = n_free;
         if (params && params->max_rounds > 0 && params->max_rounds < bound) bound = params->max_rounds;
-        while (n_active > 0) {
-            if (rounds >= bound) { status = 2; break; }
-            hipLaunchKernelGGL(ff_relax_kernel, dim3((unsigned)n_active), dim3(256), 0, st, D, fe.d_field_list.get(), fe.d_field.get(), fe.d_field_free.get(), flags, seen, cnt);
-            hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
-            if ((e = hipGetLastError()) != hipSuccess) break;
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) break;            // the one word the host reads per round: the next list's length
-            visits += n_active; rounds++;
-            n_active = (long long)h[FF_CNT_ACTIVE];
-        }
+        e = ff_run_rounds(fe, D, (long long)h[FF_CNT_ACTIVE], bound, st, R);
     }
     if (e == hipSuccess) {
         hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)n_vox, cnt);
@@ -437,15 +539,125 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     HIPCHK(c, e);
     fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
     fe.field_valid = true;
+    fe.field_status = fe.field_reachable ? R.status : 1;
+    fe.field_max_rounds = params ? params->max_rounds : 0;
+    fe.field_free_voxels = n_free;
+    fe.field_repaired = false;
     info_out->reachable = fe.field_reachable ? 1 : 0;
-    info_out->status = fe.field_reachable ? status : 1;
-    info_out->rounds = (int32_t)rounds;
+    info_out->status = fe.field_status;
+    info_out->rounds = (int32_t)R.rounds;
     info_out->bricks = (int32_t)h[FF_CNT_BRICKS];
-    info_out->brick_visits = visits;
+    info_out->brick_visits = R.visits;
     info_out->free_voxels = n_free;
     info_out->reached_voxels = (long long)h[FF_CNT_REACHED];
     info_out->device_ms = ms;
     return ISDF_OK;
+}
+
+// ---- the repair after a map update (called by map_update.hip; the rule and its premise: this file's header) -----------------------
+bool isdf_field_repair_wanted(const isdf_ctx *c) {
+    const isdf_ctx::FrontEnd &fe = c->fe;
+    return c->field_repair_mode == 1 && fe.built && fe.field_valid && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
+}
+
+// Enqueues, after the configuration-space refresh on the ctx's stream: the mark kernel over the box lo .. hi (null: the whole grid),
+// the reset kernel, ff_compact_kernel and the record's copy to the host.  The caller synchronises the stream, then calls ..._end.
+int isdf_field_repair_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    const DevGrid &G = c->grid;
+    FfDims D = ff_dims(c);
+    const int n_bricks = D.nbx * D.nby * D.nbz;
+    if (fe.d_field_rep.reserve(c, FF_REP_WORDS) || fe.h_field_rep.reserve(c, 2 * FF_REP_WORDS)) return ISDF_ERR_HIP;
+    const int x0 = lo ? lo[0] : 0, y0 = lo ? lo[1] : 0, zb0 = lo ? lo[2] >> 6 : 0;
+    const int ex = (hi ? hi[0] : G.X - 1) - x0 + 1, ey = (hi ? hi[1] : G.Y - 1) - y0 + 1, ezb = ((hi ? hi[2] : G.Z - 1) >> 6) - zb0 + 1;
+    if (x0 < 0 || y0 < 0 || zb0 < 0 || ex < 1 || ey < 1 || ezb < 1 || x0 + ex > G.X || y0 + ey > G.Y || zb0 + ezb > D.zblocks)
+        return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field repair's box lies outside the grid");
+    unsigned long long *h = fe.h_field_rep.get();          // [the record as it starts | the record as the kernels left it]
+    for (int i = 0; i < 2 * FF_REP_WORDS; i++) h[i] = 0ull;
+    h[FF_REP_TAU] = FF_INF_BITS;
+    unsigned long long *rep = fe.d_field_rep.get(), *cnt = fe.d_field_cnt.get();
+    unsigned *flags = fe.d_field_flags.get();
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipEventRecord(ev_start, st));
+    HIPCHK(c, hipMemcpyAsync(rep, h, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
+    const long long n_wv = (long long)ex * ey * ezb;
+    hipLaunchKernelGGL(ff_repair_mark_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, D, x0, y0, zb0, ex, ey, ezb, fe.d_cspace.get(), fe.d_field_free.get(),
+                       fe.d_field.get(), rep);
+    hipLaunchKernelGGL(ff_repair_reset_kernel, dim3((unsigned)n_bricks), dim3(256), 0, st, D, fe.d_field.get(), flags, rep);
+    hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h + FF_REP_WORDS, rep, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    return ISDF_OK;
+}
+
+// After the stream has been synchronised: the rounds from the seeded bricks, the count of reached voxels.  *repaired = 1: the field is
+// valid again (status 2 when the round bound was hit, as after a build); 0: a bit had opened, the field stays dropped.
+int isdf_field_repair_end(isdf_ctx *c, hipEvent_t ev_start, hipEvent_t ev_end, int *repaired) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    *repaired = 0;
+    const unsigned long long *rep = fe.h_field_rep.get() + FF_REP_WORDS;
+    if (rep[FF_REP_OPENED]) return ISDF_OK;
+    const DevGrid &G = c->grid;
+    FfDims D = ff_dims(c);
+    const hipStream_t st = c->stream;
+    volatile unsigned long long *h = fe.h_field_cnt.get();
+    const long long n_free = fe.field_free_voxels - (long long)rep[FF_REP_CLOSED];
+    long long bound = n_free;
+    if (fe.field_max_rounds > 0 && fe.field_max_rounds < bound) bound = fe.field_max_rounds;
+    FfRounds R;
+    HIPCHK(c, ff_run_rounds(fe, D, (long long)h[FF_CNT_ACTIVE], bound, st, R));
+    hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)G.X * G.Y * G.Z, fe.d_field_cnt.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev_end, st));
+    HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), fe.d_field_cnt.get(), FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev_start, ev_end));
+    const bool goal_in = fe.field_goal[0] >= 0;
+    fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
+    fe.field_status = fe.field_reachable ? R.status : 1;
+    fe.field_free_voxels = n_free;
+    fe.field_valid = true;
+    fe.field_repaired = true;
+    isdf_field_repair_info &I = fe.field_repair;
+    I = isdf_field_repair_info{};
+    I.closed_voxels = (int64_t)rep[FF_REP_CLOSED];
+    I.closed_reached = (int64_t)rep[FF_REP_CLOSED_REACHED];
+    const unsigned long long tau_bits = rep[FF_REP_TAU];
+    std::memcpy(&I.tau, &tau_bits, sizeof(double));
+    I.reset_voxels = (int64_t)(rep[FF_REP_RESET] + rep[FF_REP_CLOSED_REACHED]);
+    I.seeded_bricks = (int32_t)rep[FF_REP_SEEDED];
+    I.rounds = (int32_t)R.rounds;
+    I.brick_visits = R.visits;
+    I.free_voxels = n_free;
+    I.reached_voxels = (int64_t)h[FF_CNT_REACHED];
+    I.reachable = fe.field_reachable ? 1 : 0;
+    I.status = fe.field_status;
+    I.device_ms = ms;
+    *repaired = 1;
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_set_repair(isdf_ctx *c, int mode) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (mode != 0 && mode != 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field's repair mode is 0 (drop) or 1 (repair)");
+    if (!c->peers.empty() || c->is_peer || c->rccl_comm) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "cost-to-go field on a multi-device ctx");
+    c->field_repair_mode = mode;
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_repair_info(isdf_ctx *c, isdf_field_repair_info *out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
+    if (!c->fe.field_repaired) return isdf_fail(c, ISDF_ERR_STATE, "no repair since the last isdf_frontend_field_build");
+    *out = c->fe.field_repair;
+    return ISDF_OK;
+}
+
+extern "C" void isdf_frontend_field_repair_sizes(int sizes_out[1]) {
+    if (sizes_out) sizes_out[0] = (int)sizeof(isdf_field_repair_info);
 }
 
 extern "C" int isdf_frontend_field_get(isdf_ctx *c, double *d_out) {
@@ -527,6 +739,29 @@ extern "C" int isdf_frontend_field_host(const uint32_t *free_mask, const int32_t
     const int g[3] = {goal_index[0], goal_index[1], goal_index[2]};
     try {
         return isdf_host::field_dijkstra(free_mask, dims[0], dims[1], dims[2], n_att, g, d_out) ? 1 : 0;
+    } catch (const std::bad_alloc &) {
+        return ISDF_ERR_HIP;
+    }
+}
+
+extern "C" int isdf_frontend_field_repair_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_inout,
+                                               isdf_field_repair_info *info_out) {
+    if (!free_mask_new || !dims || !goal_index || !d_inout || n_att < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ISDF_ERR_INVALID_ARG;
+    const int g[3] = {goal_index[0], goal_index[1], goal_index[2]};
+    try {
+        isdf_host::FieldRepairCounts C;
+        const bool goal_free = isdf_host::field_repair(free_mask_new, dims[0], dims[1], dims[2], n_att, g, d_inout, &C);
+        if (info_out) {
+            *info_out = isdf_field_repair_info{};
+            info_out->closed_voxels = info_out->closed_reached = C.closed_reached;      // (a closed voxel that had not been reached cannot be told from one that was never free)
+            info_out->tau = C.tau;
+            info_out->reset_voxels = C.reset_voxels;
+            info_out->free_voxels = C.free_voxels;
+            info_out->reached_voxels = C.reached_voxels;
+            info_out->reachable = goal_free ? 1 : 0;
+            info_out->status = goal_free ? 0 : 1;
+        }
+        return goal_free ? 1 : 0;
     } catch (const std::bad_alloc &) {
         return ISDF_ERR_HIP;
     }

@@ -25,26 +25,17 @@ inline bool field_voxel_free(const uint32_t *mask, size_t nw, size_t v) {
     return any != 0u;
 }
 
-// mask: nw = 4 * ceil(n_att / 128) dwords per voxel, grid order (z fastest).  goal: voxel index, any component outside the map = no goal.
-// d_out: X * Y * Z doubles.  Returns true when the goal cell is inside the map and free.
-inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att, const int goal[3], double *d_out) {
-    const size_t nw = 4 * (size_t)((n_att + 127) / 128);
-    const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
-    const double inf = std::numeric_limits<double>::infinity();
-    for (size_t v = 0; v < n; v++) d_out[v] = inf;
-    if (goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z) return false;
-    const size_t g = (size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2];
-    if (!field_voxel_free(mask, nw, g)) return false;
-    double edge[4];
-    for (int q = 0; q < 4; q++) edge[q] = std::sqrt((double)q);
+// a binary min-heap of (key, voxel); stale entries are skipped by the consumer
+struct FieldHeap {
     struct E { double key; size_t v; };
     std::vector<E> heap;
-    auto push = [&](double key, size_t v) {
+    bool empty() const { return heap.empty(); }
+    void push(double key, size_t v) {
         heap.push_back(E{key, v});
         size_t i = heap.size() - 1;
         while (i > 0) { const size_t p = (i - 1) >> 1; if (!(heap[i].key < heap[p].key)) break; std::swap(heap[i], heap[p]); i = p; }
-    };
-    auto pop = [&]() {
+    }
+    E pop() {
         const E top = heap[0];
         heap[0] = heap.back(); heap.pop_back();
         const size_t m = heap.size();
@@ -56,12 +47,17 @@ inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att,
             std::swap(heap[i], heap[s]); i = s;
         }
         return top;
-    };
-    d_out[g] = 0.0;
-    push(0.0, g);
+    }
+};
+
+// Dijkstra's loop from whatever the heap holds: every popped voxel offers fl(key + w) to its free neighbours
+inline void field_relax_heap(const uint32_t *mask, int X, int Y, int Z, size_t nw, FieldHeap &heap, double *d) {
+    const size_t YZ = (size_t)Y * Z;
+    double edge[4];
+    for (int q = 0; q < 4; q++) edge[q] = std::sqrt((double)q);
     while (!heap.empty()) {
-        const E e = pop();
-        if (e.key > d_out[e.v]) continue;                 // a stale entry: the voxel was lowered after this one was pushed
+        const FieldHeap::E e = heap.pop();
+        if (e.key > d[e.v]) continue;                     // a stale entry: the voxel was lowered after this one was pushed
         const int x = (int)(e.v / YZ), y = (int)((e.v / Z) % Y), z = (int)(e.v % Z);
         for (int i = -1; i < 2; i++)
             for (int j = -1; j < 2; j++)
@@ -72,10 +68,59 @@ inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att,
                     const size_t u = (size_t)vx * YZ + (size_t)vy * Z + (size_t)vz;
                     if (!field_voxel_free(mask, nw, u)) continue;
                     const double cand = e.key + edge[i * i + j * j + k * k];
-                    if (cand < d_out[u]) { d_out[u] = cand; push(cand, u); }
+                    if (cand < d[u]) { d[u] = cand; heap.push(cand, u); }
                 }
     }
+}
+
+// mask: nw = 4 * ceil(n_att / 128) dwords per voxel, grid order (z fastest).  goal: voxel index, any component outside the map = no goal.
+// d_out: X * Y * Z doubles.  Returns true when the goal cell is inside the map and free.
+inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att, const int goal[3], double *d_out) {
+    const size_t nw = 4 * (size_t)((n_att + 127) / 128);
+    const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
+    const double inf = std::numeric_limits<double>::infinity();
+    for (size_t v = 0; v < n; v++) d_out[v] = inf;
+    if (goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z) return false;
+    const size_t g = (size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2];
+    if (!field_voxel_free(mask, nw, g)) return false;
+    FieldHeap heap;
+    d_out[g] = 0.0;
+    heap.push(0.0, g);
+    field_relax_heap(mask, X, Y, Z, nw, heap, d_out);
     return true;
+}
+
+// The field REPAIRED after voxels closed (occupancy only grows).  d: the field of the same goal on a mask of which
+// mask_new is a subset (every voxel free in mask_new was free before) - the premise; nothing here can check it.
+//   tau = the smallest d over the voxels with a finite d whose new word is 0 (the closed voxels that had been reached), +inf if none;
+//   every d < tau is kept: the chain of minimising neighbours from such a voxel to the goal only passes voxels with d < tau, none of
+//   them closed, so the old value is still reached, and the new graph being a subgraph it cannot be beaten;
+//   every finite d >= tau becomes +inf, and Dijkstra runs on from the kept voxels as its sources.
+// The result has the bytes of field_dijkstra on mask_new.  Returns true when the goal cell is inside the map and free in mask_new.
+struct FieldRepairCounts { long long closed_reached = 0, reset_voxels = 0, free_voxels = 0, reached_voxels = 0; double tau = 0.0; };
+inline bool field_repair(const uint32_t *mask_new, int X, int Y, int Z, int n_att, const int goal[3], double *d, FieldRepairCounts *counts) {
+    const size_t nw = 4 * (size_t)((n_att + 127) / 128);
+    const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
+    const double inf = std::numeric_limits<double>::infinity();
+    FieldRepairCounts C;
+    C.tau = inf;
+    std::vector<unsigned char> fr(n);
+    for (size_t v = 0; v < n; v++) {
+        fr[v] = field_voxel_free(mask_new, nw, v) ? 1 : 0;
+        C.free_voxels += fr[v];
+        if (!fr[v] && d[v] < inf) { C.closed_reached++; if (d[v] < C.tau) C.tau = d[v]; }
+    }
+    FieldHeap heap;
+    for (size_t v = 0; v < n; v++) {
+        if (!(d[v] < inf)) continue;
+        if (d[v] >= C.tau) { d[v] = inf; C.reset_voxels++; }
+        else heap.push(d[v], v);
+    }
+    field_relax_heap(mask_new, X, Y, Z, nw, heap, d);
+    for (size_t v = 0; v < n; v++) C.reached_voxels += d[v] < inf;
+    if (counts) *counts = C;
+    if (goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z) return false;
+    return fr[(size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2]] != 0;
 }
 
 }  // namespace isdf_host

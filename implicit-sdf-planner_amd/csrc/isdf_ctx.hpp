@@ -178,7 +178,13 @@ struct isdf_ctx {
         DevBuf<double> d_field; DevBuf<unsigned long long> d_field_free; DevBuf<int> d_field_list; DevBuf<unsigned> d_field_flags;
         DevBuf<unsigned long long> d_field_cnt; PinBuf<unsigned long long> h_field_cnt;
         bool field_valid = false, field_reachable = false; int field_goal[3] = {-1, -1, -1};
+        // what the repair after a map update needs of the last build: its status and round bound, the count of free voxels; the
+        // repair's record on the device and its pinned copy, the last repair's report (field_repaired: there was one since the build)
+        int field_status = 0, field_max_rounds = 0; long long field_free_voxels = 0;
+        DevBuf<unsigned long long> d_field_rep; PinBuf<unsigned long long> h_field_rep;
+        bool field_repaired = false; isdf_field_repair_info field_repair{};
     } fe;
+    int field_repair_mode = 0;                  // isdf_frontend_field_set_repair: outlives isdf_frontend_build (fe is reset by it)
     struct isdf_xchg *xchg = nullptr;           // peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip)
     isdf_progress_fn progress = nullptr;        // isdf_set_progress: the optimizer drivers' progress / cancel hook
     void *progress_instance = nullptr;

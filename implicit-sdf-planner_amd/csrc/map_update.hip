@@ -154,7 +154,7 @@ struct MapUpdateState {
     DevBuf<MuVoxel> d_list;             // the new voxels, in no defined order
     DevBuf<MuRecord> d_rec; PinBuf<MuRecord> h_rec;
     DevBuf<uint4> d_pack; PinBuf<uint32_t> h_pack;          // the grown box of the configuration space on its way to the host table
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};          // [6], [7]: around the field's repair
     ~MapUpdateState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
@@ -222,6 +222,9 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_param
     const bool full = (unsigned long long)R.n_new > (unsigned long long)cap || (double)mu_box_voxels(grown) > P.full_fraction * (double)n_vox ||
                       (do_esdf && std::isinf(esdf0));
     info.path = full ? 2 : 1;
+    // The cost-to-go field: dropped (mode 0 of isdf_frontend_field_set_repair), or repaired once the configuration space is the new
+    // map's (mode 1).  It is invalid from here until the repair has gone through: every error path leaves it dropped.
+    const bool repair = do_fe && isdf_field_repair_wanted(c);
     if (fe.field_valid) { fe.field_valid = false; fe.field_reachable = false; info.field_dropped = 1; }
 
     // ---- ESDF
@@ -289,7 +292,13 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_param
     HIPCHK(c, hipEventRecord(S.ev[5], st));
     if (patch) HIPCHK(c, hipMemcpyAsync(S.h_pack.get(), S.d_pack, pack_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(S.h_rec.get(), S.d_rec, sizeof(MuRecord), hipMemcpyDeviceToHost, st));
+    if (repair && (rc = isdf_field_repair_begin(c, full ? nullptr : grown.lo, full ? nullptr : grown.hi, S.ev[6]))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
+    if (repair) {                       // the rounds read one word each; the host table is patched after them
+        int repaired = 0;
+        if ((rc = isdf_field_repair_end(c, S.ev[6], S.ev[7], &repaired))) return rc;
+        if (repaired) info.field_dropped = 0;
+    }
     if (patch) {
         mu_scatter_box(fe.h_cspace, dims, nw, grown, S.h_pack.get());
         info.host_table_patched = 1;

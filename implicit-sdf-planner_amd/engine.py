@@ -283,6 +283,28 @@ def frontend_field_host(free_mask, goal_index, n_att, lib=None):
     return d, bool(rc)
 
 
+def frontend_field_repair_host(free_mask_new, goal_index, n_att, d, lib=None):
+    """isdf_frontend_field_repair_host: the field `d` of `goal_index` (float64 [X, Y, Z], of a table of which free_mask_new is a subset:
+    voxels only closed) repaired in plain host code - every d below the smallest d of a closed voxel is kept, the rest is reset and
+    Dijkstra runs on from the kept voxels.  Returns (d_new [X, Y, Z], reachable, IsdfFieldRepairInfo); `d` itself is not changed."""
+    lib = lib or capi.load_library()
+    m = np.ascontiguousarray(free_mask_new, dtype=np.uint32)
+    nw = 4 * ((int(n_att) + 127) // 128)
+    if m.ndim != 4 or m.shape[3] != nw:
+        raise ValueError(f"free_mask_new must be [X, Y, Z, {nw}]")
+    out = np.array(d, dtype=np.float64, order="C")
+    if out.shape != m.shape[:3]:
+        raise ValueError(f"d must be {m.shape[:3]}")
+    dims = np.array(m.shape[:3], dtype=np.int32)
+    g = np.ascontiguousarray(goal_index, dtype=np.int32).reshape(3)
+    info = capi.IsdfFieldRepairInfo()
+    rc = lib.isdf_frontend_field_repair_host(m.ctypes.data_as(C.c_void_p), dims.ctypes.data_as(C.c_void_p), int(n_att), g.ctypes.data_as(C.c_void_p), _p(out),
+                                             C.byref(info))
+    if rc < 0:
+        raise IsdfError(rc, "isdf_frontend_field_repair_host: bad arguments")
+    return out, bool(rc), info
+
+
 class Engine:
     def __init__(self, cfg, lib=None, devices=None):
         """devices: None = one device (cfg.device); a list = ONE ctx over those devices (isdf_create_multi), used like any other."""
@@ -594,6 +616,17 @@ class Engine:
         """device pointers (ints), asynchronous on `stream`"""
         self._check(self.lib.isdf_frontend_field_paths_device(self.h, C.c_void_p(d_starts), int(B), int(cap), C.c_void_p(d_n), C.c_void_p(d_xyz),
                                                               C.c_void_p(d_rp), C.c_void_p(stream)))
+
+    def frontend_field_set_repair(self, mode):
+        """isdf_frontend_field_set_repair: what update_pointcloud / update_voxels do with a valid field when a voxel became occupied -
+        0 (default) drop it, 1 repair it in place (only the values that a closed voxel can have fed are reset and relaxed again)."""
+        self._check(self.lib.isdf_frontend_field_set_repair(self.h, int(mode)))
+
+    def frontend_field_repair_info(self):
+        """isdf_frontend_field_repair_info: the last repair's IsdfFieldRepairInfo (ISDF_ERR_STATE: none since the last build)."""
+        info = capi.IsdfFieldRepairInfo()
+        self._check(self.lib.isdf_frontend_field_repair_info(self.h, C.byref(info)))
+        return info
 
     def frontend_field_release(self):
         self._check(self.lib.isdf_frontend_field_release(self.h))

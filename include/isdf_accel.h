@@ -1103,6 +1103,55 @@ int isdf_frontend_field_host(const uint32_t *free_mask, const int32_t dims[3], i
 /* Frees the field and its scratch (isdf_frontend_field_build allocates again). */
 int isdf_frontend_field_release(isdf_ctx *ctx);
 
+/* ---- the field repaired after a map update ------------------------------------------------------------------ */
+/* isdf_update_pointcloud / isdf_update_voxels (below) only ever CLOSE voxels: occupancy grows, free bits of the configuration-space
+ * table fall.  That is the premise of the rule:
+ *   closed = the voxels that were free when the field was built (or last repaired) and whose word is 0 now;
+ *   tau    = the smallest OLD d over the closed voxels, +inf when none of them had a finite d.
+ *   Every d < tau is kept, every finite d >= tau (the closed voxels included) becomes +inf, and the build's relaxation runs on from
+ *   there, starting at the bricks that hold a reset voxel.
+ * Why the bytes are those of a build on the new map: the new graph is a subgraph of the old, so no d can fall; every step costs
+ * w > 0 and fl is monotone, so along the chain of minimising neighbours from a voxel to the goal d does not rise - from a voxel
+ * with d < tau the chain passes only voxels with d < tau, none of them closed, so the old value is still reached.  From the kept
+ * values every intermediate value is again the length of a real path summed from the goal outward, and the fixed point is the
+ * least one.  tau = 0 when the goal cell closes (everything is reset, reachable = 0); tau = +inf when nothing reached closes
+ * (zero rounds, the bytes unchanged).  If a bit OPENED - impossible while occupancy only grows - the rule is not trusted and the
+ * field is dropped.
+ * isdf_frontend_field_set_repair: mode 0 (default) - an update that occupies a voxel drops the field, field_dropped = 1: what the
+ * sentence about the field under isdf_update_pointcloud describes; mode 1 - such an update repairs a valid field in place, on both
+ * of its paths and in both of its forms, on the ctx's stream after the configuration-space refresh; afterwards field_dropped = 0 and
+ * isdf_frontend_field_get / _value / _paths[_device] answer as after isdf_frontend_field_build on the new map.  A field without a
+ * reachable goal stays valid and all +inf.  A repair that hits its round bound (the free voxels, or the max_rounds of the build)
+ * leaves a valid status-2 field, as the build does.  Also with mode 1 the field is dropped, field_dropped = 1, when it had status 2
+ * (an upper bound, not a fixed point), when refresh_frontend = 0, when a bit opened, or when a step of the repair fails (the
+ * update then fails as a whole and drops every derived product).  The mode outlives isdf_frontend_build.
+ * Other modes: ISDF_ERR_INVALID_ARG; a multi-device ctx: ISDF_ERR_UNSUPPORTED. */
+int isdf_frontend_field_set_repair(isdf_ctx *ctx, int mode);
+typedef struct isdf_field_repair_info {
+    int64_t closed_voxels;      /* voxels whose free bit fell                                                                 */
+    int64_t closed_reached;     /* ... that had a finite d                                                                    */
+    double tau;                 /* the smallest old d of a closed voxel; +inf: nothing reached closed                         */
+    int64_t reset_voxels;       /* finite values set to +inf: the shell d >= tau, the closed voxels included                  */
+    int64_t brick_visits;       /* bricks relaxed, over all rounds                                                            */
+    int64_t free_voxels;        /* of the new map                                                                             */
+    int64_t reached_voxels;     /* voxels with a finite d after the repair                                                    */
+    int32_t seeded_bricks;      /* bricks that held a reset voxel other than a closed one: the first active list              */
+    int32_t rounds;             /* launches of the relaxation                                                                 */
+    int32_t reachable, status;  /* as isdf_frontend_field_info                                                                */
+    double device_ms;           /* device time from the mark kernel to the end of the count                                   */
+} isdf_field_repair_info;
+/* The last repair's report; ISDF_ERR_STATE when there was none since the last isdf_frontend_field_build. */
+int isdf_frontend_field_repair_info(isdf_ctx *ctx, isdf_field_repair_info *out);
+void isdf_frontend_field_repair_sizes(int sizes_out[1]);      /* sizeof of the struct above, for mirrors of this header        */
+/* The same rule in plain host code, no ctx and no device.  d_inout: on entry the field of goal_index on a table of which
+ * free_mask_new (isdf_frontend_field_host's layout) is a subset - every voxel free in it was free before -, on return the field on
+ * free_mask_new, the bytes of isdf_frontend_field_host.  tau is taken over the voxels with a finite d and a zero new word; after
+ * the reset Dijkstra runs on from the kept finite voxels.  info_out may be NULL; of it closed_voxels = closed_reached (no old table
+ * is given), seeded_bricks, rounds, brick_visits and device_ms stay 0.  Returns 1 (the goal cell is in the map and free), 0 (not),
+ * or a negative isdf_status. */
+int isdf_frontend_field_repair_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3],
+                                    double *d_inout, isdf_field_repair_info *info_out);
+
 /* ---- the map updated in place from new sensor points ---------------------------------------------------------- */
 /* isdf_set_pointcloud rebuilds everything from the full cloud.  isdf_update_pointcloud takes only the NEW points (n_points x 3
  * floats, binned as isdf_set_pointcloud bins them: a point outside the box counts for voxel (0,0,0)), adds them to the per-voxel
@@ -1117,7 +1166,9 @@ int isdf_frontend_field_release(isdf_ctx *ctx);
  * occupancy bit grid and the ESDF bricks are rebuilt lazily as after any map change.  The V1 obstacle-point set and lastTstar are
  * NOT touched: new obstacles reach the optimizer the usual way, through isdf_traj_check and isdf_points_merge_check.  The
  * cost-to-go field cannot be repaired by a decrease-only relaxation when voxels close: it is dropped whenever a voxel became
- * occupied (isdf_frontend_field_* then answer as before a build).  When no voxel became occupied nothing but the counts changes.
+ * occupied (isdf_frontend_field_* then answer as before a build) - mode 0 of isdf_frontend_field_set_repair, the default; mode 1
+ * resets the part of the field that the closed voxels can have fed and relaxes it again.  When no voxel became occupied nothing but
+ * the counts changes.
  * isdf_update_voxels is the same for a map that came from isdf_set_grid, or for a caller with its own voxel list: ijk = n_voxels x 3
  * indices to set occupied (duplicates and occupied voxels are fine; an index outside the grid: ISDF_ERR_INVALID_ARG, nothing
  * changed).  It invalidates kept counts when it occupies a voxel.
