@@ -159,6 +159,19 @@ class IsdfTrajCheckInfo(C.Structure):
                 ("select_ms", C.c_double), ("field_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+TRAJ_WATCH_OFF, TRAJ_WATCH_FOLD = 0, 1                  # isdf_traj_check_set_watch
+TRAJ_WATCH_PATH_NONE, TRAJ_WATCH_PATH_LIST, TRAJ_WATCH_PATH_FULL = 0, 1, 2      # isdf_traj_watch_info.path
+
+
+class IsdfTrajWatchInfo(C.Structure):
+    """isdf_traj_watch_info (include/isdf_accel.h)."""
+    _fields_ = [("updates_folded", C.c_int64), ("new_voxels", C.c_int64), ("new_in_box", C.c_int64), ("new_candidates", C.c_int64),
+                ("new_qualified", C.c_int64), ("new_below_margin", C.c_int64), ("new_penetrating", C.c_int64),
+                ("new_min_clearance", C.c_double), ("new_min_tstar", C.c_double), ("new_min_voxel", C.c_int64),
+                ("new_min_piece", C.c_int32), ("path", C.c_int32), ("min_changed", C.c_int32), ("reserved", C.c_int32),
+                ("select_ms", C.c_double), ("field_ms", C.c_double), ("reduce_ms", C.c_double), ("merge_ms", C.c_double)]
+
+
 LIMITS_CHANNELS, TRAJ_SAMPLE_ROW = 6, 20
 LIMIT_SPEED, LIMIT_ACC, LIMIT_OMG, LIMIT_TILT, LIMIT_THRUST_MAX, LIMIT_THRUST_MIN = range(6)
 LIMIT_NAMES = ["speed", "acc", "omg", "tilt", "thrust_max", "thrust_min"]
@@ -244,6 +257,7 @@ EXPORTED_SYMBOLS = [
     "isdf_swept_sdf", "isdf_swept_sdf_device", "isdf_swept_mesh_params_default", "isdf_swept_mesh_build", "isdf_swept_mesh_get",
     "isdf_swept_mesh_release", "isdf_write_obj", "isdf_traj_check_params_default", "isdf_traj_check", "isdf_traj_check_device",
     "isdf_traj_check_get", "isdf_traj_check_release", "isdf_traj_collide",
+    "isdf_traj_check_set_watch", "isdf_traj_check_watch_info", "isdf_traj_check_watch_sizes", "isdf_traj_check_fold_host",
     "isdf_points_merge_check", "isdf_refine_params_default", "isdf_optimize_lbfgs_checked",
     "isdf_midend_params_default", "isdf_load_yaml_midend", "isdf_midend_cost", "isdf_midend_cost_batch", "isdf_midend_fit",
     "isdf_midend_fit_batch",
@@ -421,6 +435,16 @@ def load_library(path=None):
                                            C.POINTER(IsdfTrajCheckInfo), C.c_void_p, C.c_void_p]
     lib.isdf_traj_check_get.argtypes = [C.c_void_p, dp, C.c_longlong]
     lib.isdf_traj_check_release.argtypes = [C.c_void_p]
+    lib.isdf_traj_check_set_watch.argtypes = [C.c_void_p, C.c_int]
+    lib.isdf_traj_check_watch_info.argtypes = [C.c_void_p, C.POINTER(IsdfTrajCheckInfo), dp, C.POINTER(IsdfTrajWatchInfo)]
+    lib.isdf_traj_check_watch_sizes.argtypes = [C.POINTER(C.c_int)]
+    lib.isdf_traj_check_watch_sizes.restype = None
+    lib.isdf_traj_check_fold_host.argtypes = [C.c_int, C.POINTER(IsdfTrajCheckInfo), dp, dp, C.c_void_p, C.POINTER(IsdfTrajCheckInfo), dp, dp, C.c_void_p,
+                                              C.POINTER(IsdfTrajCheckInfo), dp, dp, C.c_void_p, C.c_longlong]
+    wsz = (C.c_int * 1)()
+    lib.isdf_traj_check_watch_sizes(wsz)
+    if wsz[0] != C.sizeof(IsdfTrajWatchInfo):
+        raise RuntimeError(f"isdf_traj_watch_info: the library has {wsz[0]}, the mirror {C.sizeof(IsdfTrajWatchInfo)}")
     lib.isdf_traj_collide.argtypes = [C.c_void_p, C.c_int, dp, dp]
     lib.isdf_points_merge_check.argtypes = [C.c_void_p, C.c_double, C.POINTER(IsdfPointsMergeInfo)]
     lib.isdf_refine_params_default.argtypes = [C.POINTER(IsdfRefineParams)]

@@ -17,6 +17,7 @@ struct SweptMeshState;          // swept_mesh.hip: scratch of the swept-volume f
 struct TrajCheckState;          // swept_field.hpp: the last clearance check's points below the margin
 void isdf_swept_release_all(isdf_ctx *c);     // swept_mesh.hip: drops the field scratch and the mesh
 void isdf_traj_check_release_all(isdf_ctx *c);        // traj_check.hip: drops the kept clearance report
+void traj_watch_disarm(isdf_ctx *c);                  // traj_watch.hip: the kept report is no longer folded across map updates (a new shape)
 struct TrajLimitsState;         // traj_limits.hip: scratch of the dynamic-limits report and the state sampler
 void isdf_traj_limits_release_all(isdf_ctx *c);       // traj_limits.hip: drops it
 // traj_limits.hip, for callers that hold B trajectories on the device already: the report's two launches on `st` and nothing else (no
@@ -185,6 +186,7 @@ struct isdf_ctx {
         bool field_repaired = false; isdf_field_repair_info field_repair{};
     } fe;
     int field_repair_mode = 0;                  // isdf_frontend_field_set_repair: outlives isdf_frontend_build (fe is reset by it)
+    int traj_watch_mode = 0;                    // isdf_traj_check_set_watch: outlives the check (the watch itself: TrajCheckState::w)
     struct isdf_xchg *xchg = nullptr;           // peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip)
     isdf_progress_fn progress = nullptr;        // isdf_set_progress: the optimizer drivers' progress / cancel hook
     void *progress_instance = nullptr;

@@ -17,6 +17,7 @@
 #include "frontend_dev.hpp"
 #include "grid_index.hpp"
 #include "map_update_host.hpp"
+#include "swept_field.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -33,8 +34,6 @@ struct MuRecord {
     unsigned pad[6];
 };
 static_assert(sizeof(MuRecord) == 64, "the hand-over record is one 64-byte line");
-
-struct MuVoxel { unsigned short x, y, z, pad; };        // a grid dimension is at most 4096
 
 void launch_threshold_counts(const unsigned *counts, size_t n, unsigned thr, uint8_t *occ, hipStream_t stream);     // map_build.hip
 
@@ -306,6 +305,9 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_param
     info.esdf_voxels_lowered = (long long)S.h_rec.get()->lowered;
     info.esdf_ms = event_ms(S.ev[2], S.ev[3]);
     info.frontend_ms = event_ms(S.ev[4], S.ev[5]);
+    // the kept clearance report (mode 1 of isdf_traj_check_set_watch): the new voxels folded in, after every product above.  A failing
+    // step drops the report and fails the update as a whole, as a failing repair does.
+    if (traj_watch_armed(c) && (rc = traj_watch_fold(c, S.d_list.get(), R.n_new, cap))) return rc;
     return ISDF_OK;
 }
 

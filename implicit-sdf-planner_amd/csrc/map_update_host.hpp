@@ -15,6 +15,7 @@
 namespace isdf {
 
 struct MuBox { int lo[3], hi[3]; };       // inclusive voxel indices; lo > hi on some axis: empty
+struct MuVoxel { unsigned short x, y, z, pad; };        // an entry of the update's new-voxel list (a grid dimension is at most 4096)
 
 inline bool mu_box_empty(const MuBox &b) { return b.lo[0] > b.hi[0] || b.lo[1] > b.hi[1] || b.lo[2] > b.hi[2]; }
 

@@ -297,6 +297,7 @@ extern "C" int isdf_set_shape(isdf_ctx *c, const isdf_shape *s) {
     c->shape_host.mesh_vertices = nullptr;
     c->shape_host.mesh_faces = nullptr;
     c->have_shape = true;
+    traj_watch_disarm(c);               // a kept clearance report answers for the old shape
     ISDF_REPLICATE(c, isdf_set_shape(p_, s));
     return ISDF_OK;
 }
@@ -343,6 +344,7 @@ extern "C" int isdf_set_shape_grid(isdf_ctx *c, const double *cells, int nx, int
     c->shape_host.bound_radius = d.bound_radius;
     for (int a = 0; a < 3; a++) { c->shape_host.bbox_center[a] = bb_c[a]; c->shape_host.bbox_half[a] = bb_h[a]; }
     c->have_shape = true;
+    traj_watch_disarm(c);               // a kept clearance report answers for the old shape
     ISDF_REPLICATE(c, isdf_set_shape_grid(p_, cells, nx, ny, nz, grid_min, nres, bound_radius, bbox_center, bbox_half));
     return ISDF_OK;
 }
@@ -407,6 +409,7 @@ extern "C" int isdf_set_shape_program(isdf_ctx *c, const isdf_shape_instr *instr
     c->mesh_rmax = 0.0;
     c->shape_host = s;
     c->have_shape = true;
+    traj_watch_disarm(c);               // a kept clearance report answers for the old shape
     ISDF_REPLICATE(c, isdf_set_shape_program(p_, instr, n, trans, rotate, bound_radius, bbox_center, bbox_half));
     return ISDF_OK;
 }

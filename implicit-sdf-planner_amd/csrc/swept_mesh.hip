@@ -87,9 +87,9 @@ int swept_field_coarse_table(isdf_ctx *c, int N, const double *d_T, const double
     return ISDF_OK;
 }
 
-// the field at n points (device arrays), synchronous on `st` at the end (the overflow word is read back)
-int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
-                    double *d_value, double *d_tstar, hipStream_t st) {
+// the field's launches at n points (device arrays) on `st`; the overflow word stays on the device (d_stats[4])
+int swept_field_launch(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
+                       double *d_value, double *d_tstar, hipStream_t st) {
     SweptMeshState *s;
     { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
     if (n <= 0) return ISDF_OK;
@@ -107,6 +107,15 @@ int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeff
         launch_swept_field_reduce(P, d_value + b, d_tstar ? d_tstar + b : nullptr, st);
     }
     HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+
+// the field at n points (device arrays), synchronous on `st` at the end (the overflow word is read back)
+int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
+                    double *d_value, double *d_tstar, hipStream_t st) {
+    { const int rc = swept_field_launch(c, N, d_T, d_coeffs, d_xyz, n, mode, d_value, d_tstar, st); if (rc) return rc; }
+    if (n <= 0) return ISDF_OK;
+    SweptMeshState *s = c->swm;
     HIPCHK(c, hipMemcpyAsync(s->h_overflow, s->d_stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (*s->h_overflow.get()) return fail(c, ISDF_ERR_OVERFLOW, "swept-volume field: a point has more than 32 in-range intervals (results not valid)");

@@ -29,36 +29,11 @@ constexpr int SEL_WAVES = 4;             // z-rows per workgroup of the row kern
 
 int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
 
-struct SelBox {
-    int X, Y, Z;                 // grid
-    double res, bmin[3];
-    int lo[3], hi[3];            // voxel box, inclusive
-    int b0[3], nb[3];            // first brick of the box per axis, bricks per axis
-    int n_chunks;                // 64-voxel chunks of a z-row of the box
-    int cull;                    // 0: every occupied voxel of the box is a candidate
-    double far2;                 // (far_r)^2, slightly enlarged: the single-voxel test
-    double bfar2;                // (far_r + brick half-diagonal)^2: the brick test
-};
-
-// a voxel's centre as numpy forms it, (index + 0.5) * res + origin with both operations rounded (no contraction into an fma)
-__device__ __forceinline__ double voxel_centre(int i, double res, double origin) {
-#pragma clang fp contract(off)
-    const double m = ((double)i + 0.5) * res;
-    return m + origin;
-}
+// (SelBox, voxel_centre, stage_samples and the single-voxel test sample_within: swept_field.hpp - the fold's list kernel shares them)
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
     for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
     return x;
-}
-
-// the coarse positions into LDS as [x | y | z] (pose table: component-major, SWEPT_MAX_COARSE rows)
-__device__ __forceinline__ void stage_samples(const double *pose, int n, double *s_pos) {
-    for (int k = threadIdx.x; k < 3 * n; k += blockDim.x) {
-        const int a = k / n, i = k - a * n;
-        s_pos[a * SWEPT_MAX_COARSE + i] = pose[(size_t)a * SWEPT_MAX_COARSE + i];
-    }
-    __syncthreads();
 }
 
 // per brick of the box: the first and last coarse sample within far_r + half-diagonal of its centre (first > last: none)
@@ -111,10 +86,7 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void tc_row_kernel(SelBox B, const 
             const int2 r = range[brick_row + (z / BRICK - B.b0[2])];
             const double pz = voxel_centre(z, B.res, B.bmin[2]);
             sel = false;
-            for (int k = r.x; k <= r.y && !sel; k++) {
-                const double dx = px - s_pos[k], dy = py - s_pos[SWEPT_MAX_COARSE + k], dz = pz - s_pos[2 * SWEPT_MAX_COARSE + k];
-                sel = !(dx * dx + dy * dy + dz * dz > B.far2);
-            }
+            for (int k = r.x; k <= r.y && !sel; k++) sel = sample_within(px, py, pz, s_pos, k, B.far2);
         }
         const unsigned long long m = __ballot(sel);
         if (lane == 0) mask[row * B.n_chunks + ch] = m;
@@ -216,8 +188,8 @@ __global__ __launch_bounds__(256) void tc_reduce_kernel(long long n, const doubl
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 
-// what the device hands back: [0] min value [1] its t* [2..4] its point [5] voxel (as int64 bits) [6] piece (as int64 bits)
-constexpr int REPORT_WORDS = 7;
+// what the device hands back: TC_REPORT_WORDS doubles (swept_field.hpp)
+constexpr int REPORT_WORDS = TC_REPORT_WORDS;
 __global__ __launch_bounds__(256) void tc_final_kernel(const MinRec *__restrict__ partial, int n_partial, const double *__restrict__ val,
                                                        const double *__restrict__ ts, const long long *__restrict__ vox,
                                                        const double *__restrict__ xyz, const double *__restrict__ T, int N,
@@ -265,6 +237,7 @@ void free_rows(TrajCheckState *s) {
     s->d_rows.release();
     s->d_row_vox.release();
     s->n_rows = 0; s->have = false;
+    s->w.armed = false;                 // the report the watch folds into is gone
 }
 
 // what can be checked without a ctx (reported through isdf_last_error(NULL) when there is none)
@@ -378,40 +351,27 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     HIPCHK(c, hipEventRecord(ev[2], st));
 
     // ---- reduce
-    const int n_part = (int)std::max<long long>(1, blocks(n));
-    DevBuf<int> flag, fbase;
-    DevBuf<unsigned long long> key, d_counts;
-    DevBuf<MinRec> partial;
+    TcReduceScratch red;
+    DevBuf<unsigned long long> d_counts;
     DevBuf<double> report;
-    HIPCHK(c, flag.alloc((size_t)n)); HIPCHK(c, fbase.alloc((size_t)n));
-    HIPCHK(c, key.alloc((size_t)N)); HIPCHK(c, d_counts.alloc(3));
-    HIPCHK(c, partial.alloc((size_t)n_part)); HIPCHK(c, report.alloc(REPORT_WORDS));
-    HIPCHK(c, hipMemsetAsync(d_counts.get(), 0, 3 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(tc_key_fill_kernel, dim3(blocks(N)), dim3(256), 0, st, key.get(), N);
-    if (n > 0) hipLaunchKernelGGL(tc_reduce_kernel, dim3(n_part), dim3(256), 0, st, n, (const double *)val.get(), (const double *)ts.get(), d_T, N,
-                                  margin, flag.get(), key.get(), partial.get(), d_counts.get());
-    hipLaunchKernelGGL(tc_final_kernel, dim3(1), dim3(256), 0, st, (const MinRec *)partial.get(), n > 0 ? n_part : 0, (const double *)val.get(),
-                       (const double *)ts.get(), (const long long *)vox.get(), (const double *)xyz.get(), d_T, N,
-                       (const unsigned long long *)key.get(), d_piece_min, report.get());
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, d_counts.alloc(3)); HIPCHK(c, report.alloc(REPORT_WORDS));
+    { const int rc = tc_reduce_launch(c, red, n, val.get(), ts.get(), vox.get(), xyz.get(), d_T, N, margin, d_counts.get(), report.get(), d_piece_min, st); if (rc) return rc; }
     unsigned long long counts[3];
     double rep[REPORT_WORDS];
     HIPCHK(c, hipMemcpyAsync(counts, d_counts.get(), sizeof(counts), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(rep, report.get(), sizeof(rep), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (counts[1]) {
-        { const int rc = exclusive_sum(c, flag.get(), fbase.get(), n, st); if (rc) return rc; }
         HIPCHK(c, k->d_rows.alloc((size_t)counts[1] * 5));
-        hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)flag.get(), (const int *)fbase.get(),
-                           (const double *)xyz.get(), (const double *)val.get(), (const double *)ts.get(), k->d_rows);
         HIPCHK(c, k->d_row_vox.alloc((size_t)counts[1]));
-        hipLaunchKernelGGL(tc_row_vox_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)flag.get(), (const int *)fbase.get(),
-                           (const long long *)vox.get(), k->d_row_vox.get());
-        HIPCHK(c, hipGetLastError());
+        { const int rc = tc_rows_launch(c, red, n, val.get(), ts.get(), vox.get(), xyz.get(), k->d_rows.get(), k->d_row_vox.get(), st); if (rc) return rc; }
     }
     HIPCHK(c, hipEventRecord(ev[3], st));
     HIPCHK(c, hipStreamSynchronize(st));
     k->n_rows = (long long)counts[1]; k->have = true; k->grid_epoch = c->grid_epoch;
+    isdf_traj_check_info own_info;
+    const bool watch = c->traj_watch_mode == 1;
+    if (!info && watch) info = &own_info;
     if (info) {
         std::memset(info, 0, sizeof(*info));
         info->occupied_in_box = (long long)cnt[0];
@@ -430,10 +390,66 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
         for (int q = 0; q < 3; q++) HIPCHK(c, hipEventElapsedTime(&ms[q], ev[q], ev[q + 1]));
         info->select_ms = ms[0]; info->field_ms = ms[1]; info->reduce_ms = ms[2];
     }
+    if (watch) {
+        // arm: the trajectory, the parameters in force, the report and its piece minima, the selection box (mode 1 of
+        // isdf_traj_check_set_watch; the rows and their voxel ids are the kept ones)
+        TrajWatchState &w = k->w;
+        { const int rc = w.d_traj.reserve(c, (size_t)20 * N); if (rc) return rc; }
+        if (d_T != w.d_traj.get()) {            // (a whole-map re-check runs on the kept copy itself)
+            HIPCHK(c, hipMemcpyAsync(w.d_traj, d_T, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(w.d_traj + N, d_C, (size_t)18 * N * sizeof(double), hipMemcpyDeviceToDevice, st));
+        }
+        w.piece_min.assign((size_t)N, 1e1);
+        HIPCHK(c, hipMemcpyAsync(w.piece_min.data(), d_piece_min, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        w.N = N; w.mode = mode; w.margin = margin;
+        w.info = *info;
+        w.box = B; w.box_empty = empty;
+        w.last = isdf_traj_watch_info{};
+        w.last.new_min_clearance = 1e1; w.last.new_min_tstar = -1.0; w.last.new_min_voxel = -1; w.last.new_min_piece = -1;
+        w.armed = true;
+    }
     return ISDF_OK;
 }
 
 }  // namespace
+
+int tc_reduce_launch(isdf_ctx *c, TcReduceScratch &S, long long n, const double *d_val, const double *d_ts, const long long *d_vox, const double *d_xyz,
+                     const double *d_T, int N, double margin, unsigned long long *d_counts, double *d_report, double *d_piece_min, hipStream_t st) {
+    const int n_part = (int)std::max<long long>(1, blocks(n));
+    { const int rc = S.flag.reserve(c, (size_t)std::max<long long>(n, 1)); if (rc) return rc; }
+    { const int rc = S.fbase.reserve(c, (size_t)std::max<long long>(n, 1)); if (rc) return rc; }
+    { const int rc = S.key.reserve(c, (size_t)N); if (rc) return rc; }
+    { const int rc = S.partial.reserve(c, (size_t)n_part * sizeof(MinRec)); if (rc) return rc; }
+    HIPCHK(c, hipMemsetAsync(d_counts, 0, 3 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(tc_key_fill_kernel, dim3(blocks(N)), dim3(256), 0, st, S.key.get(), N);
+    if (n > 0) hipLaunchKernelGGL(tc_reduce_kernel, dim3(n_part), dim3(256), 0, st, n, d_val, d_ts, d_T, N, margin, S.flag.get(), S.key.get(),
+                                  (MinRec *)S.partial.get(), d_counts);
+    hipLaunchKernelGGL(tc_final_kernel, dim3(1), dim3(256), 0, st, (const MinRec *)S.partial.get(), n > 0 ? n_part : 0, d_val, d_ts, d_vox, d_xyz, d_T, N,
+                       (const unsigned long long *)S.key.get(), d_piece_min, d_report);
+    HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+
+int tc_rows_launch(isdf_ctx *c, TcReduceScratch &S, long long n, const double *d_val, const double *d_ts, const long long *d_vox, const double *d_xyz,
+                   double *d_rows, long long *d_row_vox, hipStream_t st) {
+    if (n <= 0) return ISDF_OK;
+    size_t bytes = 0;
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, S.flag.get(), S.fbase.get(), (int)n, st));
+    { const int rc = S.scan_tmp.reserve(c, std::max<size_t>(bytes, 1)); if (rc) return rc; }
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S.scan_tmp.get(), bytes, S.flag.get(), S.fbase.get(), (int)n, st));
+    hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)S.flag.get(), (const int *)S.fbase.get(), d_xyz, d_val, d_ts, d_rows);
+    hipLaunchKernelGGL(tc_row_vox_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)S.flag.get(), (const int *)S.fbase.get(), d_vox, d_row_vox);
+    HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+
+int traj_check_rerun_kept(isdf_ctx *c, isdf_traj_check_info *info) {
+    TrajWatchState &w = c->tck->w;
+    return check_run(c, w.N, w.d_traj, w.d_traj + w.N, w.mode, w.margin, info, w.d_traj + 19 * (size_t)w.N, c->stream);
+}
+
+void traj_check_drop_report(isdf_ctx *c) { if (c->tck) free_rows(c->tck); }
 
 int isdf_traj_check_ready(isdf_ctx *c) {
     double margin = 0.0;

@@ -305,6 +305,37 @@ def frontend_field_repair_host(free_mask_new, goal_index, n_att, d, lib=None):
     return out, bool(rc), info
 
 
+def _traj_check_info_from(d):
+    info = capi.IsdfTrajCheckInfo()
+    for name, _ in capi.IsdfTrajCheckInfo._fields_:
+        if name == "min_point":
+            for q in range(3):
+                info.min_point[q] = float(d[name][q])
+        elif name in d:
+            setattr(info, name, d[name])
+    return info
+
+
+def traj_check_fold_host(a, rows_a, vox_a, b, rows_b, vox_b, lib=None):
+    """isdf_traj_check_fold_host: see Engine.traj_check_fold_host.  Raises ValueError on a negative status."""
+    lib = lib or capi.load_library()
+    ia, ib, out = _traj_check_info_from(a), _traj_check_info_from(b), capi.IsdfTrajCheckInfo()
+    pa, pb = a.get("piece_min"), b.get("piece_min")
+    N = len(pa) if pa is not None else (len(pb) if pb is not None else 1)
+    pa = None if pa is None else np.ascontiguousarray(pa, dtype=np.float64)
+    pb = None if pb is None else np.ascontiguousarray(pb, dtype=np.float64)
+    ra = np.ascontiguousarray(rows_a, dtype=np.float64).reshape(-1, 5); rb = np.ascontiguousarray(rows_b, dtype=np.float64).reshape(-1, 5)
+    va = np.ascontiguousarray(vox_a, dtype=np.int64).reshape(-1); vb = np.ascontiguousarray(vox_b, dtype=np.int64).reshape(-1)
+    n = ra.shape[0] + rb.shape[0]
+    rows = np.zeros((n, 5)); vox = np.zeros(n, dtype=np.int64); pm = np.zeros(N)
+    rc = lib.isdf_traj_check_fold_host(N, C.byref(ia), None if pa is None else _p(pa), _p(ra), va.ctypes.data_as(C.c_void_p),
+                                       C.byref(ib), None if pb is None else _p(pb), _p(rb), vb.ctypes.data_as(C.c_void_p),
+                                       C.byref(out), _p(pm), _p(rows), vox.ctypes.data_as(C.c_void_p), n)
+    if rc != 0:
+        raise ValueError(f"isdf_traj_check_fold_host: status {rc}")
+    return Engine._traj_check_report(out, pm), rows, vox
+
+
 class Engine:
     def __init__(self, cfg, lib=None, devices=None):
         """devices: None = one device (cfg.device); a list = ONE ctx over those devices (isdf_create_multi), used like any other."""
@@ -435,6 +466,7 @@ class Engine:
         p = self._map_update_params(**params)
         info = capi.IsdfMapUpdateInfo()
         self._check(self.lib.isdf_update_pointcloud(self.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], C.byref(p), C.byref(info)))
+        self._watch_refresh_rows()
         return info
 
     def update_voxels(self, ijk, **params):
@@ -443,6 +475,7 @@ class Engine:
         p = self._map_update_params(**params)
         info = capi.IsdfMapUpdateInfo()
         self._check(self.lib.isdf_update_voxels(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.shape[0], C.byref(p), C.byref(info)))
+        self._watch_refresh_rows()
         return info
 
     def map_counts(self):
@@ -780,6 +813,7 @@ class Engine:
         piece_min = np.zeros(N)
         self._check(self.lib.isdf_traj_check(self.h, N, _p(T), _p(Cc), C.byref(p), C.byref(info), _p(piece_min)))
         self._traj_check_rows = int(info.n_below_margin)
+        self._traj_check_N = N
         return self._traj_check_report(info, piece_min)
 
     def traj_check_device(self, N, d_T, d_coeffs, margin=None, mode=capi.SWEPT_FIELD_PLANNER, d_piece_min=0, stream=0):
@@ -799,6 +833,37 @@ class Engine:
 
     def traj_check_release(self):
         self._check(self.lib.isdf_traj_check_release(self.h))
+
+    # ---- the kept report folded across map updates (isdf_traj_check_set_watch)
+    def traj_check_set_watch(self, mode):
+        """isdf_traj_check_set_watch: 0 - a map update leaves the kept report alone (default); 1 - every successful check arms a watch and
+        every update_pointcloud / update_voxels that occupies a voxel folds the new voxels into the kept report."""
+        self._check(self.lib.isdf_traj_check_set_watch(self.h, int(mode)))
+        self._watch_mode = int(mode)
+
+    def _watch_refresh_rows(self):
+        # a fold changes the number of kept rows traj_check_points() sizes its array by
+        if getattr(self, "_watch_mode", 0) != 1:
+            return
+        info = capi.IsdfTrajCheckInfo()
+        if self.lib.isdf_traj_check_watch_info(self.h, C.byref(info), None, None) == 0:
+            self._traj_check_rows = int(info.n_below_margin)
+
+    def traj_check_watch_info(self, N=None):
+        """isdf_traj_check_watch_info: (report, last) - the current folded report as traj_check returns it ("piece_min": N values; N
+        None = the N of the last traj_check, None when unknown) and the isdf_traj_watch_info fields of the last fold as a dict."""
+        N = getattr(self, "_traj_check_N", None) if N is None else int(N)
+        info = capi.IsdfTrajCheckInfo(); last = capi.IsdfTrajWatchInfo()
+        piece_min = np.zeros(N) if N else None
+        self._check(self.lib.isdf_traj_check_watch_info(self.h, C.byref(info), _p(piece_min) if N else None, C.byref(last)))
+        self._traj_check_rows = int(info.n_below_margin)
+        return (self._traj_check_report(info, piece_min),
+                {name: getattr(last, name) for name, _ in capi.IsdfTrajWatchInfo._fields_ if name != "reserved"})
+
+    def traj_check_fold_host(self, a, rows_a, vox_a, b, rows_b, vox_b):
+        """isdf_traj_check_fold_host (no ctx, no device): two report dicts as traj_check returns them (IsdfTrajCheckInfo fields and
+        "piece_min"), over DISJOINT voxel sets, with their rows (n x 5) and ascending voxel ids -> (report, rows, vox) of the union."""
+        return traj_check_fold_host(a, rows_a, vox_a, b, rows_b, vox_b, self.lib)
 
     def traj_collide(self, T, coeffs_colmajor):
         """isTrajCollide: True if an occupied voxel centre lies inside the swept volume (default parameters)."""

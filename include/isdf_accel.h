@@ -514,6 +514,49 @@ int isdf_traj_check_release(isdf_ctx *ctx);      /* frees the kept rows */
  * (n_penetrating > 0 at the default parameters), 0 = none, negative = isdf_status */
 int isdf_traj_collide(isdf_ctx *ctx, int N, const double *T, const double *coeffs);
 
+/* ---- the kept report folded across map updates ---------------------------------------------------------------- */
+/* Occupancy only grows, the field query answers every point on its own, and every quantity of the report is a sum, a minimum or a
+ * voxel-ordered list.  So the check on an updated map is the kept report of the old map merged with a report over only the voxels
+ * the update made occupied - the same bytes as isdf_traj_check on the updated map, for work proportional to the update.
+ * isdf_traj_check_set_watch: mode 0 (default) - an update leaves the kept report alone (stale, its voxel ids still valid); mode 1 -
+ * every successful isdf_traj_check[_device] (those of isdf_optimize_lbfgs_checked, the retiming and the re-allocation included) arms a
+ * watch: the ctx keeps the trajectory, the margin and mode in force, the report, the N piece minima and the rows with their voxel
+ * ids, and from then on every isdf_update_pointcloud / isdf_update_voxels that occupies a voxel folds the new voxels in, on both of
+ * the update's paths, on the ctx's stream after the map products and the field repair of the same call.  Afterwards
+ * isdf_traj_check_get, isdf_points_merge_check and isdf_traj_check_watch_info answer as after isdf_traj_check on the updated map.  An
+ * update that occupies nothing folds nothing.  The watch is disarmed by isdf_traj_check_release, by isdf_set_grid /
+ * isdf_set_pointcloud, by a new shape or shape program, and by a failing step of the fold - the update then fails as a whole, as a
+ * failing field repair makes it, and the kept report is dropped, never left half-merged.  The mode outlives the check.
+ * Other modes: ISDF_ERR_INVALID_ARG; a multi-device ctx: ISDF_ERR_UNSUPPORTED. */
+int isdf_traj_check_set_watch(isdf_ctx *ctx, int mode);
+typedef struct isdf_traj_watch_info {
+    int64_t updates_folded;      /* updates folded into the report since the watch was armed                                      */
+    int64_t new_voxels;          /* the last folded update: voxels it occupied                                                    */
+    int64_t new_in_box, new_candidates, new_qualified, new_below_margin, new_penetrating;   /* ... their share of the report's sums */
+    double new_min_clearance;    /* the minimum over the NEW voxels alone (10: none qualified) ...                                */
+    double new_min_tstar;        /* ... its t* (-1), voxel index (-1) and piece (-1).  path 2: those of the report when min_changed, */
+    int64_t new_min_voxel;       /*     else 10 / -1 / -1 / -1 (the whole map was checked, not the new voxels apart)              */
+    int32_t new_min_piece;
+    int32_t path;                /* 0 nothing folded yet; 1 the new voxels came from the update's list; 2 the kept trajectory was  */
+                                 /*   checked against the whole map again (the update's list was cut at max_new_voxels)           */
+    int32_t min_changed;         /* 1: the folded global minimum came from this update                                            */
+    int32_t reserved;
+    double select_ms, field_ms, reduce_ms, merge_ms;     /* device time of the fold's steps (events on the ctx's stream)          */
+} isdf_traj_watch_info;
+/* The current folded report, the N piece minima of the watched trajectory (piece_min_out may be NULL) and the record of the last
+ * fold (last_out may be NULL).  ISDF_ERR_STATE when no watch is armed. */
+int isdf_traj_check_watch_info(isdf_ctx *ctx, isdf_traj_check_info *report_out, double *piece_min_out, isdf_traj_watch_info *last_out);
+void isdf_traj_check_watch_sizes(int sizes_out[1]);      /* sizeof of the struct above, for mirrors of this header              */
+/* The merge rule in plain host code, no ctx and no device: two reports over DISJOINT voxel sets of one trajectory of N pieces - info
+ * words, N piece minima (NULL: all 10), n_below_margin rows of 5 doubles and their ascending voxel ids each - into the report of the
+ * union.  Integer sums add; the minimum is the lexicographic (value, voxel index) with -1 for "none"; piece minima are element-wise
+ * minima; rows interleave by ascending voxel id; culled, margin, far_r and the times are a's.  rows_out / vox_out hold `capacity`
+ * rows (ISDF_ERR_OVERFLOW if fewer than the sum; both may be NULL when the sum is 0).  Lists that are not ascending or share an id:
+ * ISDF_ERR_INVALID_ARG.  The device fold calls the same functions (csrc/traj_watch_host.hpp). */
+int isdf_traj_check_fold_host(int N, const isdf_traj_check_info *a, const double *piece_min_a, const double *rows_a, const int64_t *vox_a,
+                              const isdf_traj_check_info *b, const double *piece_min_b, const double *rows_b, const int64_t *vox_b,
+                              isdf_traj_check_info *out, double *piece_min_out, double *rows_out, int64_t *vox_out, long long capacity);
+
 /* ---- dynamic limits of a trajectory -------------------------------------------------------------------------------- */
 /* The back end keeps the vehicle inside vmax / omgmax / thetamax only through soft penalties at K + 1 samples per piece
  * (back_end_optimizer.hpp:453-536), so a finished trajectory can exceed them, between the samples or at them.  These entry
@@ -1164,7 +1207,9 @@ int isdf_frontend_field_repair_host(const uint32_t *free_mask_new, const int32_t
  * transform of the occupancy), isdf_frontend_build and isdf_frontend_cspace if they had been run.
  * The grid's geometry and the voxel indices handed out before (clearance reports, isdf_points_merge_check) stay valid; the
  * occupancy bit grid and the ESDF bricks are rebuilt lazily as after any map change.  The V1 obstacle-point set and lastTstar are
- * NOT touched: new obstacles reach the optimizer the usual way, through isdf_traj_check and isdf_points_merge_check.  The
+ * NOT touched: new obstacles reach the optimizer the usual way, through isdf_traj_check and isdf_points_merge_check.  With mode 1
+ * of isdf_traj_check_set_watch an update that occupies a voxel also folds the new voxels into the kept clearance report, which then
+ * reads as after isdf_traj_check on the updated map.  The
  * cost-to-go field cannot be repaired by a decrease-only relaxation when voxels close: it is dropped whenever a voxel became
  * occupied (isdf_frontend_field_* then answer as before a build) - mode 0 of isdf_frontend_field_set_repair, the default; mode 1
  * resets the part of the field that the closed voxels can have fed and relaxes it again.  When no voxel became occupied nothing but
