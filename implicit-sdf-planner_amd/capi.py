@@ -113,6 +113,24 @@ class IsdfMapUpdateInfo(C.Structure):
                 ("cspace_voxels_recomputed", C.c_int64), ("count_ms", C.c_double), ("esdf_ms", C.c_double), ("frontend_ms", C.c_double)]
 
 
+MAP_CLEAR_NONE, MAP_CLEAR_INCREMENTAL, MAP_CLEAR_FULL = 0, 1, 2         # isdf_map_clear_info.path
+
+
+class IsdfMapClearParams(C.Structure):
+    """isdf_map_clear_params (include/isdf_accel.h)."""
+    _fields_ = [("max_cleared_voxels", C.c_int64), ("full_fraction", C.c_double), ("refresh_esdf", C.c_int32), ("refresh_frontend", C.c_int32)]
+
+
+class IsdfMapClearInfo(C.Structure):
+    """isdf_map_clear_info (include/isdf_accel.h)."""
+    _fields_ = [("n_points", C.c_int64), ("n_points_ignored", C.c_int64), ("n_cleared_voxels", C.c_int64), ("dirty_lo", C.c_int32 * 3),
+                ("dirty_hi", C.c_int32 * 3), ("touched_lo", C.c_int32 * 3), ("touched_hi", C.c_int32 * 3), ("path", C.c_int32),
+                ("esdf_refreshed", C.c_int32), ("frontend_refreshed", C.c_int32), ("cspace_refreshed", C.c_int32),
+                ("host_table_patched", C.c_int32), ("field_dropped", C.c_int32), ("watch_rechecked", C.c_int32), ("reserved", C.c_int32),
+                ("esdf_voxels_recomputed", C.c_int64), ("esdf_voxels_raised", C.c_int64), ("cspace_voxels_recomputed", C.c_int64),
+                ("count_ms", C.c_double), ("esdf_ms", C.c_double), ("frontend_ms", C.c_double)]
+
+
 class IsdfPlanConfig(C.Structure):
     """isdf_plan_config: what a plan needs from the reference's yaml files (include/isdf_accel.h)."""
     _fields_ = [("sweep", IsdfConfig), ("frontend", IsdfFrontendConfig), ("occupancy_resolution", C.c_double),
@@ -272,6 +290,7 @@ EXPORTED_SYMBOLS = [
     "isdf_frontend_field_paths", "isdf_frontend_field_paths_device", "isdf_frontend_field_host", "isdf_frontend_field_release",
     "isdf_frontend_field_set_repair", "isdf_frontend_field_repair_info", "isdf_frontend_field_repair_sizes", "isdf_frontend_field_repair_host",
     "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
+    "isdf_map_clear_params_default", "isdf_map_clear_sizes", "isdf_clear_pointcloud", "isdf_clear_voxels", "isdf_clear_esdf_host", "isdf_clear_touched_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -505,6 +524,20 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfMapUpdateParams), C.sizeof(IsdfMapUpdateInfo)]:
         raise RuntimeError(f"isdf_map_update structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfMapUpdateParams), C.sizeof(IsdfMapUpdateInfo)]}")
+    cp, ci = C.POINTER(IsdfMapClearParams), C.POINTER(IsdfMapClearInfo)
+    lib.isdf_map_clear_params_default.argtypes = [cp]
+    lib.isdf_map_clear_params_default.restype = None
+    lib.isdf_map_clear_sizes.argtypes = [ip]
+    lib.isdf_map_clear_sizes.restype = None
+    lib.isdf_clear_pointcloud.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_longlong, cp, ci]
+    lib.isdf_clear_voxels.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_longlong, cp, ci]
+    lib.isdf_clear_esdf_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_double, C.c_void_p, C.c_longlong, ci]
+    lib.isdf_clear_touched_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_double, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.isdf_clear_touched_host.restype = C.c_longlong
+    lib.isdf_map_clear_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfMapClearParams), C.sizeof(IsdfMapClearInfo)]:
+        raise RuntimeError(f"isdf_map_clear structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfMapClearParams), C.sizeof(IsdfMapClearInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

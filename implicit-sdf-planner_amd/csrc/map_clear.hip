@@ -1,0 +1,444 @@
+// Voxels cleared from the map in place: isdf_clear_pointcloud / isdf_clear_voxels, the inverse of map_update.hip.
+//   mc_mark_kernel     one lane per point (or listed voxel).  The point form takes one off the kept count with a compare-and-swap
+//                      loop that never stores below 0 (a lane that reads 0 gives up and is counted as ignored).  EXACTLY ONE LANE SEES
+//                      THE CROSSING: the successful swaps on one count are totally ordered and each takes it from v to v - 1, v >= 1;
+//                      nothing adds during the kernel, so the count's values strictly fall, the value thr is left at most once - by the
+//                      one swap whose expected value was thr - and it is left exactly when the count starts >= thr and ends < thr.
+//                      That lane frees the voxel, appends it to the cleared list and widens the dirty box.  The voxel form clears the
+//                      occupancy byte with a 32-bit atomic AND on the dword that holds it; the lane that read a set byte freed it.
+//   mc_touched_kernel  the ESDF raise, part one.  One lane per voxel of the map: is some cleared voxel near enough to have been this
+//                      voxel's nearest obstacle (mc_touched on the old float, map_clear_host.hpp)?  Box pre-test, workgroup early-out,
+//                      then the list through LDS - the update's mu_esdf_kernel with the comparison turned round.  Leaves the touched
+//                      voxels' box and count, and whether any voxel of the map is still occupied.
+//   mc_edt_z / _y / _x the raise, part two: the exact transform again over the touched box Tx x Ty x Tz.  It is separable: z pass over
+//                      X x Y x Tz (one lane per column, two sweeps over the occupancy bytes), y pass over X x Ty x Tz, x pass over the
+//                      box with edt_line_kernel<0>'s conversion - the integer d2 is unique, so float(res * sqrt(d2)) is the byte
+//                      isdf_generate_esdf writes.  Scratch: the two slabs, not the map.
+//   front end          map_update.hip's boxed kernels through mu_frontend_box_launch: they recompute from the occupancy.
+// A value can only rise, an untouched value stays, and every consumer of the cleared list asks "is there an entry that ...": its
+// order, which the atomics leave undefined, never shows.
+#include "isdf_ctx.hpp"
+#include "frontend_dev.hpp"
+#include "grid_index.hpp"
+#include "map_clear_host.hpp"
+#include "map_update_state.hpp"
+#include "swept_field.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace isdf {
+
+// the count stage's hand-over record: 64 bytes, zeroed (box: empty) before every clear
+struct McRecord {
+    unsigned n_cleared;                 // voxels that became free (may exceed the list's capacity: the full path follows)
+    unsigned pad0;
+    int lo[3], hi[3];                   // the dirty box
+    unsigned long long ignored;         // points whose voxel's count was 0
+    unsigned pad[6];
+};
+// the ESDF stage's record, the second 64 bytes
+struct McEsdfRecord {
+    int lo[3], hi[3];                   // the touched box
+    unsigned any_occ, pad0;             // some voxel of the map is still occupied
+    unsigned long long touched, raised;
+    unsigned pad[4];
+};
+static_assert(sizeof(McRecord) == 64 && sizeof(McEsdfRecord) == 64 && sizeof(MuRecord) == 64, "each hand-over record is one 64-byte line");
+
+template <bool VOXELS>
+__global__ __launch_bounds__(256) void mc_mark_kernel(const void *__restrict__ in, long long n, DevGrid G, unsigned *__restrict__ counts, unsigned thr,
+                                                      uint8_t *__restrict__ occ, MuVoxel *__restrict__ list, unsigned cap, McRecord *__restrict__ rec) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        int ix, iy, iz;
+        bool crossed = false;
+        if (VOXELS) {
+            const int *ijk = (const int *)in;
+            ix = ijk[3 * i]; iy = ijk[3 * i + 1]; iz = ijk[3 * i + 2];      // (checked against the grid on the host)
+            const size_t a = ((size_t)ix * G.Y + iy) * G.Z + iz;
+            const unsigned sh = 8u * (unsigned)(a & 3);
+            const unsigned old = atomicAnd((unsigned *)(occ + (a & ~(size_t)3)), ~(0xFFu << sh));        // occ is allocated as whole dwords
+            crossed = ((old >> sh) & 0xFFu) != 0u;
+        } else {
+            const float *xyz = (const float *)in;
+            (void)grid_index(G, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], ix, iy, iz);
+            const size_t a = ((size_t)ix * G.Y + iy) * G.Z + iz;
+            unsigned seen = counts[a];
+            for (;;) {
+                if (seen == 0u) { atomicAdd(&rec->ignored, 1ull); break; }
+                const unsigned was = atomicCAS(&counts[a], seen, seen - 1u);
+                if (was == seen) { crossed = thr >= 1u && seen == thr; break; }          // thr == 0: every voxel stays occupied
+                seen = was;
+            }
+            if (crossed) occ[a] = 0;
+        }
+        if (crossed) {
+            const unsigned pos = atomicAdd(&rec->n_cleared, 1u);
+            if (pos < cap) list[pos] = MuVoxel{(unsigned short)ix, (unsigned short)iy, (unsigned short)iz, 0};
+            atomicMin(&rec->lo[0], ix); atomicMin(&rec->lo[1], iy); atomicMin(&rec->lo[2], iz);
+            atomicMax(&rec->hi[0], ix); atomicMax(&rec->hi[1], iy); atomicMax(&rec->hi[2], iz);
+        }
+    }
+}
+
+constexpr int MC_CHUNK = 1024;          // cleared voxels staged per round: 8 KiB of LDS
+
+__global__ __launch_bounds__(256) void mc_touched_kernel(DevGrid G, const float *__restrict__ esdf, const uint8_t *__restrict__ occ,
+                                                         const MuVoxel *__restrict__ list, int n_list, MuBox box, McEsdfRecord *__restrict__ rec) {
+    __shared__ MuVoxel s_list[MC_CHUNK];
+    __shared__ int s_lo[3], s_hi[3];
+    __shared__ unsigned s_cnt;
+    const size_t total = (size_t)G.X * G.Y * G.Z;
+    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool in = a < total;
+    if (threadIdx.x < 3) { s_lo[threadIdx.x] = 0x7FFFFFFF; s_hi[threadIdx.x] = -1; }
+    if (threadIdx.x == 0) s_cnt = 0u;
+    int x = 0, y = 0, z = 0;
+    float old = 0.f;
+    bool scan = false;
+    if (in) {
+        z = (int)(a % G.Z); y = (int)((a / G.Z) % G.Y); x = (int)(a / ((size_t)G.Y * G.Z));
+        old = esdf[a];
+        scan = mc_touched(old, G.res, mu_box_dist2(x, y, z, box.lo, box.hi));
+    }
+    if (__syncthreads_or(in && occ[a] == 1 ? 1 : 0) && threadIdx.x == 0) atomicOr(&rec->any_occ, 1u);
+    if (!__syncthreads_or(scan ? 1 : 0)) return;          // the same answer in every thread: the barriers below are uniform
+    bool hit = false;
+    for (int c0 = 0; c0 < n_list; c0 += MC_CHUNK) {
+        const int m = min(MC_CHUNK, n_list - c0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < m; t += 256) s_list[t] = list[c0 + t];
+        __syncthreads();
+        if (scan && !hit)
+            for (int t = 0; t < m && !hit; t++) {
+                const MuVoxel v = s_list[t];
+                const long long dx = x - (int)v.x, dy = y - (int)v.y, dz = z - (int)v.z;
+                hit = mc_touched(old, G.res, dx * dx + dy * dy + dz * dz);
+            }
+    }
+    if (hit) {
+        atomicMin(&s_lo[0], x); atomicMin(&s_lo[1], y); atomicMin(&s_lo[2], z);
+        atomicMax(&s_hi[0], x); atomicMax(&s_hi[1], y); atomicMax(&s_hi[2], z);
+        atomicAdd(&s_cnt, 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) {
+        atomicMin(&rec->lo[0], s_lo[0]); atomicMin(&rec->lo[1], s_lo[1]); atomicMin(&rec->lo[2], s_lo[2]);
+        atomicMax(&rec->hi[0], s_hi[0]); atomicMax(&rec->hi[1], s_hi[1]); atomicMax(&rec->hi[2], s_hi[2]);
+        atomicAdd(&rec->touched, (unsigned long long)s_cnt);
+    }
+}
+
+// z pass: one lane per column (x, y) of the map; out: [X * Y][Tz], the squared distance to the nearest occupied voxel of the column
+__global__ __launch_bounds__(256) void mc_edt_z_kernel(DevGrid G, const uint8_t *__restrict__ occ, int z0, int z1, int *__restrict__ out_a) {
+    const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= (long long)G.X * G.Y) return;
+    const int Tz = z1 - z0 + 1;
+    const uint8_t *c = occ + (size_t)col * G.Z;
+    int *out = out_a + (size_t)col * Tz;
+    int last = -1;
+    for (int z = 0; z <= z1; z++) {
+        if (c[z] == 1) last = z;
+        if (z >= z0) out[z - z0] = last < 0 ? MC_EDT_INF : (z - last) * (z - last);
+    }
+    int next = -1;
+    for (int z = G.Z - 1; z >= z0; z--) {
+        if (c[z] == 1) next = z;
+        if (z <= z1 && next >= 0) out[z - z0] = min(out[z - z0], (next - z) * (next - z));
+    }
+}
+
+// y pass: in [X][Y][Tz] -> out [X][Ty][Tz], lanes along z
+__global__ __launch_bounds__(256) void mc_edt_y_kernel(DevGrid G, const int *__restrict__ in_a, int *__restrict__ out_b, MuBox T) {
+    const int Ty = T.hi[1] - T.lo[1] + 1, Tz = T.hi[2] - T.lo[2] + 1;
+    const long long n = (long long)G.X * Ty * Tz;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        const int tz = (int)(t % Tz);
+        const long long xy = t / Tz;
+        const int ty = (int)(xy % Ty), x = (int)(xy / Ty);
+        out_b[t] = mc_line_min(in_a + (size_t)x * G.Y * Tz + tz, G.Y, Tz, T.lo[1] + ty);
+    }
+}
+
+// x pass over the box and the conversion: in [X][Ty][Tz] -> the ESDF's voxels of the box
+__global__ __launch_bounds__(256) void mc_edt_x_kernel(DevGrid G, const int *__restrict__ in_b, float *__restrict__ esdf, MuBox T, McEsdfRecord *__restrict__ rec) {
+    const int Tx = T.hi[0] - T.lo[0] + 1, Ty = T.hi[1] - T.lo[1] + 1, Tz = T.hi[2] - T.lo[2] + 1;
+    const long long n = (long long)Tx * Ty * Tz;
+    unsigned long long mine = 0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        const int tz = (int)(t % Tz);
+        const long long xy = t / Tz;
+        const int ty = (int)(xy % Ty), tx = (int)(xy / Ty);
+        const int d2 = mc_line_min(in_b + (size_t)ty * Tz + tz, G.X, (long long)Ty * Tz, T.lo[0] + tx);
+        const float nv = mc_esdf_value(G.res, d2);
+        const size_t a = ((size_t)(T.lo[0] + tx) * G.Y + T.lo[1] + ty) * G.Z + T.lo[2] + tz;
+        if (__float_as_uint(esdf[a]) != __float_as_uint(nv)) { esdf[a] = nv; mine++; }
+    }
+    if (mine) atomicAdd(&rec->raised, mine);
+}
+
+}  // namespace isdf
+
+using namespace isdf;
+
+extern "C" void isdf_map_clear_params_default(isdf_map_clear_params *p) {
+    if (!p) return;
+    p->max_cleared_voxels = 65536;
+    p->full_fraction = 0.5;
+    p->refresh_esdf = 1;
+    p->refresh_frontend = 1;
+}
+
+extern "C" void isdf_map_clear_sizes(int sizes_out[2]) {
+    if (!sizes_out) return;
+    sizes_out[0] = (int)sizeof(isdf_map_clear_params); sizes_out[1] = (int)sizeof(isdf_map_clear_info);
+}
+
+namespace {
+
+void empty_boxes(isdf_map_clear_info &info) {
+    for (int a = 0; a < 3; a++) { info.dirty_lo[a] = info.touched_lo[a] = 0; info.dirty_hi[a] = info.touched_hi[a] = -1; }
+}
+
+// everything after the hand-over of a call that freed at least one voxel
+int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const McRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info) {
+    const hipStream_t st = c->stream;
+    const DevGrid &G = c->grid;
+    const int dims[3] = {G.X, G.Y, G.Z};
+    const size_t n_vox = (size_t)G.X * G.Y * G.Z;
+    int rc;
+    MuBox box;
+    for (int a = 0; a < 3; a++) { box.lo[a] = info.dirty_lo[a] = R.lo[a]; box.hi[a] = info.dirty_hi[a] = R.hi[a]; }
+    if (voxels) c->d_counts.release();              // the counts no longer describe the occupancy
+    c->bits_dirty = true;
+
+    isdf_ctx::FrontEnd &fe = c->fe;
+    const bool do_esdf = (bool)c->d_esdf && P.refresh_esdf != 0;
+    const bool do_fe = fe.built && P.refresh_frontend != 0;
+    const MuBox grown = mu_box_grow(box, do_fe ? (fe.cfg.kernel_size - 1) / 2 : 0, dims);
+    bool full = (unsigned long long)R.n_cleared > (unsigned long long)cap || (double)mu_box_voxels(grown) > P.full_fraction * (double)n_vox;
+    // The cost-to-go field: a clear opens bits, which the repair's rule is not proved for - dropped in both repair modes.
+    if (fe.field_valid) { fe.field_valid = false; fe.field_reachable = false; info.field_dropped = 1; }
+
+    // ---- ESDF
+    if (c->d_esdf && !P.refresh_esdf) {
+        c->d_esdf.release();
+        c->grid.esdf = nullptr;
+        c->bricks_stale = true;
+    }
+    McEsdfRecord *const d_er = (McEsdfRecord *)(S.d_rec.get() + 1);
+    const McEsdfRecord *const h_er = (const McEsdfRecord *)(S.h_rec.get() + 1);
+    HIPCHK(c, hipEventRecord(S.ev[2], st));
+    if (do_esdf) {
+        MuBox T{{0, 0, 0}, {-1, -1, -1}};
+        if (!full) {
+            // part one: the touched voxels.  Their box sizes the slabs and decides the path: the second hand-over of the call.
+            hipLaunchKernelGGL(mc_touched_kernel, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, st, G, (const float *)c->d_esdf.get(), (const uint8_t *)c->d_occ.get(),
+                               (const MuVoxel *)S.d_list.get(), (int)R.n_cleared, box, d_er);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(S.h_rec.get() + 1, S.d_rec.get() + 1, sizeof(McEsdfRecord), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            for (int a = 0; a < 3; a++) { T.lo[a] = h_er->lo[a]; T.hi[a] = h_er->hi[a]; }
+            if (!mu_box_empty(T))
+                for (int a = 0; a < 3; a++)
+                    if (T.lo[a] < 0 || T.hi[a] >= dims[a]) return isdf_fail(c, ISDF_ERR_HIP, "map clear: inconsistent hand-over record");
+            full = !h_er->any_occ || (double)mu_box_voxels(T) > P.full_fraction * (double)n_vox;
+        }
+        if (full) { if ((rc = isdf_generate_esdf(c))) return rc; info.esdf_voxels_recomputed = (long long)n_vox; }
+        else if (!mu_box_empty(T)) {
+            const int Tx = T.hi[0] - T.lo[0] + 1, Ty = T.hi[1] - T.lo[1] + 1, Tz = T.hi[2] - T.lo[2] + 1;
+            const size_t na = (size_t)G.X * G.Y * Tz, nb = (size_t)G.X * Ty * Tz, nc = (size_t)Tx * Ty * Tz;
+            if ((rc = S.d_edt_a.reserve(c, na)) || (rc = S.d_edt_b.reserve(c, nb))) return rc;
+            hipLaunchKernelGGL(mc_edt_z_kernel, dim3((unsigned)(((size_t)G.X * G.Y + 255) / 256)), dim3(256), 0, st, G, (const uint8_t *)c->d_occ.get(), T.lo[2], T.hi[2], S.d_edt_a.get());
+            hipLaunchKernelGGL(mc_edt_y_kernel, dim3((unsigned)std::min<size_t>((nb + 255) / 256, 8192)), dim3(256), 0, st, G, (const int *)S.d_edt_a.get(), S.d_edt_b.get(), T);
+            hipLaunchKernelGGL(mc_edt_x_kernel, dim3((unsigned)std::min<size_t>((nc + 255) / 256, 8192)), dim3(256), 0, st, G, (const int *)S.d_edt_b.get(), c->d_esdf.get(), T, d_er);
+            HIPCHK(c, hipGetLastError());
+            for (int a = 0; a < 3; a++) { info.touched_lo[a] = T.lo[a]; info.touched_hi[a] = T.hi[a]; }
+            info.esdf_voxels_recomputed = mu_box_voxels(T);
+        }
+        c->bricks_stale = true;
+        info.esdf_refreshed = 1;
+    }
+    info.path = full ? 2 : 1;
+    HIPCHK(c, hipEventRecord(S.ev[3], st));
+
+    // ---- front end
+    bool patch = false;
+    size_t pack_words = 0;
+    const size_t nw = 4 * (size_t)((fe.xk * fe.yk + 127) / 128);
+    if (fe.built && !P.refresh_frontend) isdf_frontend_release(c);
+    HIPCHK(c, hipEventRecord(S.ev[4], st));
+    if (do_fe) {
+        info.frontend_refreshed = 1;
+        info.cspace_refreshed = fe.d_cspace ? 1 : 0;
+        if (full) {
+            if ((rc = isdf_frontend_refresh_map(c, nullptr))) return rc;
+            if (fe.d_cspace) info.cspace_voxels_recomputed = (long long)n_vox;
+        } else {
+            long long cs_voxels = 0;
+            if ((rc = mu_frontend_box_launch(c, S, box, grown, &patch, &pack_words, &cs_voxels))) return rc;
+            info.cspace_voxels_recomputed = cs_voxels;
+        }
+    }
+    HIPCHK(c, hipEventRecord(S.ev[5], st));
+    if (patch) HIPCHK(c, hipMemcpyAsync(S.h_pack.get(), S.d_pack, pack_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(S.h_rec.get() + 1, S.d_rec.get() + 1, sizeof(McEsdfRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (patch) {
+        mu_scatter_box(fe.h_cspace, dims, nw, grown, S.h_pack.get());
+        info.host_table_patched = 1;
+    }
+    if (do_esdf && !full) info.esdf_voxels_raised = (long long)h_er->raised;
+    info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
+    info.frontend_ms = mu_event_ms(S.ev[4], S.ev[5]);
+    // the kept clearance report (mode 1 of isdf_traj_check_set_watch): removed voxels cannot be subtracted from the piece minima, so the
+    // kept trajectory is checked against the whole new map again.  A failing check drops the report and fails the clear as a whole.
+    if (traj_watch_armed(c)) {
+        const long long folded = c->tck->w.last.updates_folded;
+        isdf_traj_check_info now;
+        if ((rc = traj_check_rerun_kept(c, &now))) {
+            const std::string err = c->err;
+            (void)hipStreamSynchronize(st);
+            traj_check_drop_report(c);
+            c->err = err;
+            return rc;
+        }
+        isdf_traj_watch_info &L = c->tck->w.last;           // (the re-check armed the watch again and cleared this)
+        L.updates_folded = folded + 1;
+        L.path = 2;
+        L.select_ms = now.select_ms; L.field_ms = now.field_ms; L.reduce_ms = now.reduce_ms;
+        info.watch_rechecked = 1;
+    }
+    return ISDF_OK;
+}
+
+// the clear proper; `in` is the host array of the points (voxels == false) or of the checked voxel indices
+int map_clear(isdf_ctx *c, const void *in, long long n_in, bool voxels, const isdf_map_clear_params *params, isdf_map_clear_info *info_out) {
+    isdf_map_clear_params P;
+    isdf_map_clear_params_default(&P);
+    if (params) P = *params;
+    if (P.max_cleared_voxels < 0 || !(P.full_fraction >= 0.0)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad map clear parameters");
+    isdf_map_clear_info info{};
+    empty_boxes(info);
+    info.n_points = n_in;
+    HIPCHK(c, hipSetDevice(c->device));
+    MapUpdateState *Sp;
+    { const int rc0 = mu_state(c, &Sp); if (rc0) return rc0; }
+    MapUpdateState &S = *Sp;
+    const hipStream_t st = c->stream;
+    const DevGrid &G = c->grid;
+    const size_t n_vox = (size_t)G.X * G.Y * G.Z;
+    int rc;
+
+    // ---- count down, find the cleared voxels: one hand-over record, one synchronisation
+    const size_t in_bytes = (size_t)n_in * 3 * (voxels ? sizeof(int) : sizeof(float));
+    const unsigned cap = (unsigned)std::min<unsigned long long>({(unsigned long long)P.max_cleared_voxels, (unsigned long long)n_in, (unsigned long long)n_vox, 0x7FFFFFFFull});
+    if ((rc = S.d_in.reserve(c, in_bytes))) return rc;
+    if ((rc = S.d_list.reserve(c, std::max<size_t>(cap, 1)))) return rc;
+    if ((rc = S.d_rec.reserve(c, 2))) return rc;
+    if ((rc = S.h_rec.reserve(c, 2))) return rc;
+    {
+        McRecord zero{};
+        McEsdfRecord ezero{};
+        for (int a = 0; a < 3; a++) { zero.lo[a] = ezero.lo[a] = 0x7FFFFFFF; zero.hi[a] = ezero.hi[a] = -1; }
+        std::memcpy(S.h_rec.get(), &zero, sizeof(zero));
+        std::memcpy(S.h_rec.get() + 1, &ezero, sizeof(ezero));
+    }
+    HIPCHK(c, hipMemcpyAsync(S.d_rec, S.h_rec.get(), 2 * sizeof(MuRecord), hipMemcpyHostToDevice, st));
+    if (n_in > 0) HIPCHK(c, hipMemcpyAsync(S.d_in, in, in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(S.ev[0], st));
+    if (n_in > 0) {
+        const unsigned blocks = (unsigned)std::min<long long>((n_in + 255) / 256, 2048);
+        if (voxels) hipLaunchKernelGGL(mc_mark_kernel<true>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, (unsigned *)nullptr, 0u, c->d_occ.get(),
+                                       S.d_list.get(), cap, (McRecord *)S.d_rec.get());
+        else hipLaunchKernelGGL(mc_mark_kernel<false>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, c->d_counts.get(), (unsigned)c->counts_thr,
+                                c->d_occ.get(), S.d_list.get(), cap, (McRecord *)S.d_rec.get());
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        hipError_t e = hipEventRecord(S.ev[1], st);
+        if (e == hipSuccess) e = hipMemcpyAsync(S.h_rec.get(), S.d_rec, sizeof(McRecord), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {          // the kernel may have run: the occupancy may have moved
+            c->err = std::string("map clear hand-over: ") + hipGetErrorString(e);
+            mu_drop_derived(c, voxels);
+            return ISDF_ERR_HIP;
+        }
+    }
+    McRecord R;
+    std::memcpy(&R, S.h_rec.get(), sizeof(R));
+    info.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
+    info.n_cleared_voxels = R.n_cleared;
+    info.n_points_ignored = (long long)R.ignored;
+    if (R.n_cleared == 0) {             // nothing but the counts changed: every product stays in place, the field and the watch included
+        if (info_out) *info_out = info;
+        return ISDF_OK;
+    }
+    // from here on the occupancy has moved: a failure must not leave products behind that describe the old map
+    rc = refresh_products(c, S, P, R, cap, voxels, info);
+    if (rc != ISDF_OK) { mu_drop_derived(c, voxels); return rc; }
+    if (info_out) *info_out = info;
+    return ISDF_OK;
+}
+
+int clear_ready(isdf_ctx *c, const void *in, long long n) {
+    if (n < 0 || (n > 0 && !in)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad clear arguments");
+    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "clearing the map in place is not offered on a multi-device ctx");
+    if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "clearing the map needs an occupancy grid");
+    return ISDF_OK;
+}
+
+bool host_args_bad(const int32_t dims[3], double res, const int32_t *ijk, long long n) {
+    if (!dims || !(res > 0.0) || n < 0 || (n > 0 && !ijk)) return true;
+    for (int a = 0; a < 3; a++) if (dims[a] < 1 || dims[a] > 4096) return true;
+    for (long long i = 0; i < 3 * n; i++) if (ijk[i] < 0 || ijk[i] >= dims[i % 3]) return true;
+    return false;
+}
+
+}  // namespace
+
+extern "C" int isdf_clear_pointcloud(isdf_ctx *c, const float *xyz, long long n_points, const isdf_map_clear_params *params, isdf_map_clear_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    const int rc = clear_ready(c, xyz, n_points);
+    if (rc) return rc;
+    if (!c->d_counts) return isdf_fail(c, ISDF_ERR_STATE, "no kept point counts: the map did not come from isdf_set_pointcloud, or isdf_update_voxels / isdf_clear_voxels changed it since");
+    return map_clear(c, xyz, n_points, false, params, info_out);
+}
+
+extern "C" int isdf_clear_voxels(isdf_ctx *c, const int32_t *ijk, long long n_voxels, const isdf_map_clear_params *params, isdf_map_clear_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    const int rc = clear_ready(c, ijk, n_voxels);
+    if (rc) return rc;
+    for (long long i = 0; i < n_voxels; i++)
+        if (ijk[3 * i] < 0 || ijk[3 * i] >= c->grid.X || ijk[3 * i + 1] < 0 || ijk[3 * i + 1] >= c->grid.Y || ijk[3 * i + 2] < 0 || ijk[3 * i + 2] >= c->grid.Z)
+            return isdf_fail(c, ISDF_ERR_INVALID_ARG, "a voxel index lies outside the grid");
+    return map_clear(c, ijk, n_voxels, true, params, info_out);
+}
+
+extern "C" long long isdf_clear_touched_host(const float *esdf_old, const int32_t dims[3], double resolution, const int32_t *cleared_ijk, long long n_cleared,
+                                             uint8_t *touched_out) {
+    if (!esdf_old || host_args_bad(dims, resolution, cleared_ijk, n_cleared)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "clear (host form): bad arguments");
+    McRaise R;
+    mc_touched_host(esdf_old, dims, resolution, cleared_ijk, n_cleared, touched_out, R);
+    return R.n_touched;
+}
+
+extern "C" int isdf_clear_esdf_host(const uint8_t *occ_new, float *esdf_inout, const int32_t dims[3], double resolution, const int32_t *cleared_ijk,
+                                    long long n_cleared, isdf_map_clear_info *info_out) {
+    if (!occ_new || !esdf_inout || host_args_bad(dims, resolution, cleared_ijk, n_cleared)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "clear (host form): bad arguments");
+    McRaise R;
+    mc_esdf_raise_host(occ_new, esdf_inout, dims, resolution, cleared_ijk, n_cleared, R);
+    if (info_out) {
+        isdf_map_clear_info info{};
+        empty_boxes(info);
+        info.n_points = info.n_cleared_voxels = n_cleared;
+        info.path = n_cleared == 0 ? 0 : (R.none_left ? 2 : 1);
+        if (n_cleared > 0) for (int a = 0; a < 3; a++) { info.dirty_lo[a] = R.dirty.lo[a]; info.dirty_hi[a] = R.dirty.hi[a]; }
+        if (!R.none_left && !mu_box_empty(R.touched)) for (int a = 0; a < 3; a++) { info.touched_lo[a] = R.touched.lo[a]; info.touched_hi[a] = R.touched.hi[a]; }
+        info.esdf_refreshed = n_cleared > 0 ? 1 : 0;
+        info.esdf_voxels_recomputed = R.recomputed; info.esdf_voxels_raised = R.raised;
+        *info_out = info;
+    }
+    return ISDF_OK;
+}

@@ -17,6 +17,7 @@
 #include "frontend_dev.hpp"
 #include "grid_index.hpp"
 #include "map_update_host.hpp"
+#include "map_update_state.hpp"
 #include "swept_field.hpp"
 #include <algorithm>
 #include <cmath>
@@ -24,16 +25,6 @@
 #include <new>
 
 namespace isdf {
-
-// the hand-over record: 64 bytes, zeroed (box: empty) before every update
-struct MuRecord {
-    unsigned n_new;                     // voxels that became occupied (may exceed the list's capacity: the full path follows)
-    unsigned esdf0;                     // bits of the ESDF's first value before the update: +inf = the map had no occupied voxel
-    int lo[3], hi[3];                   // the dirty box
-    unsigned long long lowered;         // mu_esdf_kernel: values that fell
-    unsigned pad[6];
-};
-static_assert(sizeof(MuRecord) == 64, "the hand-over record is one 64-byte line");
 
 void launch_threshold_counts(const unsigned *counts, size_t n, unsigned thr, uint8_t *occ, hipStream_t stream);     // map_build.hip
 
@@ -148,15 +139,6 @@ __global__ __launch_bounds__(256) void mu_pack_box_kernel(const uint4 *__restric
 
 using namespace isdf;
 
-struct MapUpdateState {
-    DevBuf<void> d_in;                  // the call's points or voxel indices
-    DevBuf<MuVoxel> d_list;             // the new voxels, in no defined order
-    DevBuf<MuRecord> d_rec; PinBuf<MuRecord> h_rec;
-    DevBuf<uint4> d_pack; PinBuf<uint32_t> h_pack;          // the grown box of the configuration space on its way to the host table
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};          // [6], [7]: around the field's repair
-    ~MapUpdateState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
 void isdf_map_update_release_all(isdf_ctx *c) { delete c->mup; c->mup = nullptr; }
 
 extern "C" void isdf_map_update_params_default(isdf_map_update_params *p) {
@@ -181,16 +163,13 @@ extern "C" int isdf_map_counts_get(isdf_ctx *c, uint32_t *out) {
     return ISDF_OK;
 }
 
-namespace {
-
-float event_ms(hipEvent_t a, hipEvent_t b) {
+// ---- shared with map_clear.hip (map_update_state.hpp)
+float isdf::mu_event_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
 }
 
-// After a failure past the point where the occupancy advanced: what was derived from the old map goes (as isdf_set_pointcloud drops
-// it), the error message stays.  The occupancy and the counts are consistent with each other and stay.
-void drop_derived(isdf_ctx *c, bool voxels) {
+void isdf::mu_drop_derived(isdf_ctx *c, bool voxels) {
     const std::string err = c->err;
     c->d_esdf.release(); c->grid.esdf = nullptr;
     c->bricks_stale = true; c->bits_dirty = true;
@@ -198,6 +177,47 @@ void drop_derived(isdf_ctx *c, bool voxels) {
     if (voxels) c->d_counts.release();
     c->err = err;
 }
+
+int isdf::mu_state(isdf_ctx *c, MapUpdateState **out) {
+    if (!c->mup) { c->mup = new (std::nothrow) MapUpdateState(); if (!c->mup) return isdf_fail(c, ISDF_ERR_HIP, "out of host memory"); }
+    for (hipEvent_t &e : c->mup->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    *out = c->mup;
+    return ISDF_OK;
+}
+
+int isdf::mu_frontend_box_launch(isdf_ctx *c, MapUpdateState &S, const MuBox &box, const MuBox &grown, bool *patch, size_t *pack_words, long long *cspace_voxels) {
+    const hipStream_t st = c->stream;
+    const DevGrid &G = c->grid;
+    isdf_ctx::FrontEnd &fe = c->fe;
+    const size_t nw = 4 * (size_t)((fe.xk * fe.yk + 127) / 128);
+    int rc;
+    const FeParams F = fe_params(c);
+    // inflated rows x + side, y + side; bit z + side lies in dword (z + side) >> 5 (< iZW - 1: the spare dword stays zero)
+    const int w0 = (box.lo[2] + F.side) >> 5, w1 = (box.hi[2] + F.side) >> 5;
+    const int e0 = box.hi[0] - box.lo[0] + 1, e1 = box.hi[1] - box.lo[1] + 1, e2 = w1 - w0 + 1;
+    const long long nb = (long long)e0 * e1 * e2;
+    hipLaunchKernelGGL(mu_map_bits_box_kernel, dim3((unsigned)std::min<long long>((nb + 255) / 256, 2048)), dim3(256), 0, st, F, c->d_occ.get(), fe.d_bits.get(),
+                       box.lo[0] + F.side, box.lo[1] + F.side, w0, e0, e1, e2);
+    HIPCHK(c, hipGetLastError());
+    if (!fe.d_cspace) return ISDF_OK;
+    const long long n_wv = (long long)(grown.hi[0] - grown.lo[0] + 1) * (grown.hi[1] - grown.lo[1] + 1) * ((grown.hi[2] - grown.lo[2] + 64) >> 6);
+    hipLaunchKernelGGL(mu_cspace_box_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, F, c->d_occ.get(), fe.d_bits.get(),
+                       (const FeRow *)fe.d_row_list.get(), fe.d_row_ptr.get(), (uint4 *)fe.d_cspace.get(), grown);
+    HIPCHK(c, hipGetLastError());
+    *cspace_voxels = mu_box_voxels(grown);
+    if (!fe.h_cspace_valid) return ISDF_OK;
+    *pack_words = (size_t)mu_box_voxels(grown) * nw;
+    if ((rc = S.d_pack.reserve(c, *pack_words / 4))) return rc;
+    if ((rc = S.h_pack.reserve(c, *pack_words))) return rc;
+    const long long np = (long long)(*pack_words / 4);
+    hipLaunchKernelGGL(mu_pack_box_kernel, dim3((unsigned)std::min<long long>((np + 255) / 256, 2048)), dim3(256), 0, st, (const uint4 *)fe.d_cspace.get(),
+                       S.d_pack.get(), G.Y, G.Z, (int)(nw / 4), grown);
+    HIPCHK(c, hipGetLastError());
+    *patch = true;
+    return ISDF_OK;
+}
+
+namespace {
 
 // everything after the hand-over of a frame that occupied at least one voxel
 int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_params &P, const MuRecord &R, unsigned cap, bool voxels, isdf_map_update_info &info) {
@@ -261,31 +281,9 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_param
             if ((rc = isdf_frontend_refresh_map(c, nullptr))) return rc;
             if (fe.d_cspace) info.cspace_voxels_recomputed = (long long)n_vox;
         } else {
-            const FeParams F = fe_params(c);
-            // inflated rows x + side, y + side; bit z + side lies in dword (z + side) >> 5 (< iZW - 1: the spare dword stays zero)
-            const int w0 = (box.lo[2] + F.side) >> 5, w1 = (box.hi[2] + F.side) >> 5;
-            const int e0 = box.hi[0] - box.lo[0] + 1, e1 = box.hi[1] - box.lo[1] + 1, e2 = w1 - w0 + 1;
-            const long long nb = (long long)e0 * e1 * e2;
-            hipLaunchKernelGGL(mu_map_bits_box_kernel, dim3((unsigned)std::min<long long>((nb + 255) / 256, 2048)), dim3(256), 0, st, F, c->d_occ.get(), fe.d_bits.get(),
-                               box.lo[0] + F.side, box.lo[1] + F.side, w0, e0, e1, e2);
-            HIPCHK(c, hipGetLastError());
-            if (fe.d_cspace) {
-                const long long n_wv = (long long)(grown.hi[0] - grown.lo[0] + 1) * (grown.hi[1] - grown.lo[1] + 1) * ((grown.hi[2] - grown.lo[2] + 64) >> 6);
-                hipLaunchKernelGGL(mu_cspace_box_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, F, c->d_occ.get(), fe.d_bits.get(),
-                                   (const FeRow *)fe.d_row_list.get(), fe.d_row_ptr.get(), (uint4 *)fe.d_cspace.get(), grown);
-                HIPCHK(c, hipGetLastError());
-                info.cspace_voxels_recomputed = mu_box_voxels(grown);
-                if (fe.h_cspace_valid) {
-                    pack_words = (size_t)mu_box_voxels(grown) * nw;
-                    if ((rc = S.d_pack.reserve(c, pack_words / 4))) return rc;
-                    if ((rc = S.h_pack.reserve(c, pack_words))) return rc;
-                    const long long np = (long long)(pack_words / 4);
-                    hipLaunchKernelGGL(mu_pack_box_kernel, dim3((unsigned)std::min<long long>((np + 255) / 256, 2048)), dim3(256), 0, st, (const uint4 *)fe.d_cspace.get(),
-                                       S.d_pack.get(), G.Y, G.Z, (int)(nw / 4), grown);
-                    HIPCHK(c, hipGetLastError());
-                    patch = true;
-                }
-            }
+            long long cs_voxels = 0;
+            if ((rc = mu_frontend_box_launch(c, S, box, grown, &patch, &pack_words, &cs_voxels))) return rc;
+            info.cspace_voxels_recomputed = cs_voxels;
         }
     }
     HIPCHK(c, hipEventRecord(S.ev[5], st));
@@ -303,8 +301,8 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_param
         info.host_table_patched = 1;
     }
     info.esdf_voxels_lowered = (long long)S.h_rec.get()->lowered;
-    info.esdf_ms = event_ms(S.ev[2], S.ev[3]);
-    info.frontend_ms = event_ms(S.ev[4], S.ev[5]);
+    info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
+    info.frontend_ms = mu_event_ms(S.ev[4], S.ev[5]);
     // the kept clearance report (mode 1 of isdf_traj_check_set_watch): the new voxels folded in, after every product above.  A failing
     // step drops the report and fails the update as a whole, as a failing repair does.
     if (traj_watch_armed(c) && (rc = traj_watch_fold(c, S.d_list.get(), R.n_new, cap))) return rc;
@@ -322,9 +320,9 @@ int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const i
     for (int a = 0; a < 3; a++) { info.dirty_lo[a] = 0; info.dirty_hi[a] = -1; }
     info.n_points = n_in;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->mup) { c->mup = new (std::nothrow) MapUpdateState(); if (!c->mup) return isdf_fail(c, ISDF_ERR_HIP, "out of host memory"); }
-    MapUpdateState &S = *c->mup;
-    for (hipEvent_t &e : S.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    MapUpdateState *Sp;
+    { const int rc0 = mu_state(c, &Sp); if (rc0) return rc0; }
+    MapUpdateState &S = *Sp;
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     const size_t n_vox = (size_t)G.X * G.Y * G.Z;
@@ -357,12 +355,12 @@ int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const i
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) {          // the kernel may have run: the occupancy may have advanced
             c->err = std::string("map update hand-over: ") + hipGetErrorString(e);
-            drop_derived(c, voxels);
+            mu_drop_derived(c, voxels);
             return ISDF_ERR_HIP;
         }
     }
     const MuRecord R = *S.h_rec.get();
-    info.count_ms = event_ms(S.ev[0], S.ev[1]);
+    info.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
     info.n_new_voxels = R.n_new;
     if (R.n_new == 0) {                 // nothing but the counts changed: every product stays in place, the field included
         if (info_out) *info_out = info;
@@ -370,7 +368,7 @@ int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const i
     }
     // from here on the occupancy has advanced: a failure must not leave products behind that describe the old map
     rc = refresh_products(c, S, P, R, cap, voxels, info);
-    if (rc != ISDF_OK) { drop_derived(c, voxels); return rc; }
+    if (rc != ISDF_OK) { mu_drop_derived(c, voxels); return rc; }
     if (info_out) *info_out = info;
     return ISDF_OK;
 }

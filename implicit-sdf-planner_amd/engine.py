@@ -478,6 +478,37 @@ class Engine:
         self._watch_refresh_rows()
         return info
 
+    # ---- voxels cleared from the map in place (csrc/map_clear.hip)
+    def _map_clear_params(self, max_cleared_voxels=None, full_fraction=None, refresh_esdf=True, refresh_frontend=True):
+        p = capi.IsdfMapClearParams()
+        self.lib.isdf_map_clear_params_default(C.byref(p))
+        if max_cleared_voxels is not None:
+            p.max_cleared_voxels = int(max_cleared_voxels)
+        if full_fraction is not None:
+            p.full_fraction = float(full_fraction)
+        p.refresh_esdf = int(bool(refresh_esdf)); p.refresh_frontend = int(bool(refresh_frontend))
+        return p
+
+    def clear_pointcloud(self, xyz, **params):
+        """isdf_clear_pointcloud: points (n x 3 float32) taken OUT of the counts set_pointcloud keeps; a voxel that falls below the
+        threshold becomes free and every derived product is refreshed where it can change.  params: max_cleared_voxels, full_fraction,
+        refresh_esdf, refresh_frontend.  Returns IsdfMapClearInfo."""
+        pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        p = self._map_clear_params(**params)
+        info = capi.IsdfMapClearInfo()
+        self._check(self.lib.isdf_clear_pointcloud(self.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], C.byref(p), C.byref(info)))
+        self._watch_refresh_rows()
+        return info
+
+    def clear_voxels(self, ijk, **params):
+        """isdf_clear_voxels: the listed voxels (n x 3 indices) become free.  Returns IsdfMapClearInfo."""
+        v = np.ascontiguousarray(ijk, dtype=np.int32).reshape(-1, 3)
+        p = self._map_clear_params(**params)
+        info = capi.IsdfMapClearInfo()
+        self._check(self.lib.isdf_clear_voxels(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.shape[0], C.byref(p), C.byref(info)))
+        self._watch_refresh_rows()
+        return info
+
     def map_counts(self):
         """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""
         out = np.zeros(self._grid_dims(), dtype=np.uint32)

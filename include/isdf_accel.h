@@ -515,8 +515,9 @@ int isdf_traj_check_release(isdf_ctx *ctx);      /* frees the kept rows */
 int isdf_traj_collide(isdf_ctx *ctx, int N, const double *T, const double *coeffs);
 
 /* ---- the kept report folded across map updates ---------------------------------------------------------------- */
-/* Occupancy only grows, the field query answers every point on its own, and every quantity of the report is a sum, a minimum or a
- * voxel-ordered list.  So the check on an updated map is the kept report of the old map merged with a report over only the voxels
+/* Occupancy only grows under isdf_update_* (isdf_clear_pointcloud / isdf_clear_voxels take voxels out and re-check an armed watch
+ * against the whole map instead, see there), the field query answers every point on its own, and every quantity of the report is a
+ * sum, a minimum or a voxel-ordered list.  So the check on an updated map is the kept report of the old map merged with a report over only the voxels
  * the update made occupied - the same bytes as isdf_traj_check on the updated map, for work proportional to the update.
  * isdf_traj_check_set_watch: mode 0 (default) - an update leaves the kept report alone (stale, its voxel ids still valid); mode 1 -
  * every successful isdf_traj_check[_device] (those of isdf_optimize_lbfgs_checked, the retiming and the re-allocation included) arms a
@@ -1200,7 +1201,8 @@ int isdf_frontend_field_repair_host(const uint32_t *free_mask_new, const int32_t
  * floats, binned as isdf_set_pointcloud bins them: a point outside the box counts for voxel (0,0,0)), adds them to the per-voxel
  * counts that isdf_set_pointcloud keeps, and refreshes every derived product only where it can change: the occupancy, the ESDF
  * (new = min(old, distance to the nearest newly occupied voxel); occupancy only grows, as in the reference, whose
- * PCSmap_manager.cpp:87-200 only counts points up), the front end's inflated bit map over the box of the new voxels and its
+ * PCSmap_manager.cpp:87-200 only counts points up - voxels are taken OUT again by isdf_clear_pointcloud / isdf_clear_voxels, the
+ * section after this one), the front end's inflated bit map over the box of the new voxels and its
  * configuration-space table - and, when the A* holds the table on the host, that copy - over the box grown by (kernel_size - 1) / 2.
  * Afterwards every product is byte for byte what a fresh ctx holds after isdf_set_pointcloud(old ++ new) with the same explicit
  * boundaries, resolution and threshold, then isdf_generate_esdf if an ESDF was installed (it is taken to be the exact distance
@@ -1248,6 +1250,76 @@ int isdf_update_voxels(isdf_ctx *ctx, const int32_t *ijk, long long n_voxels, co
                        isdf_map_update_info *info_out);
 /* The kept per-voxel point counts, X * Y * Z values in the grid's own order; ISDF_ERR_STATE when there are none. */
 int isdf_map_counts_get(isdf_ctx *ctx, uint32_t *counts_out);
+
+/* ---- voxels cleared from the map in place --------------------------------------------------------------------- */
+/* The inverse of the update above: occupancy that shrinks (a door opens, a moving obstacle has passed, a false return is corrected).
+ * isdf_clear_pointcloud takes points OUT of the kept per-voxel counts (n_points x 3 floats, binned exactly as isdf_update_pointcloud
+ * bins them: a point outside the box counts for voxel (0,0,0)).  A count never goes below 0: a point that finds its voxel's count at
+ * 0 changes nothing and is counted in n_points_ignored.  A voxel whose count falls from >= sta_threshold to below it becomes free.
+ * isdf_clear_voxels sets the listed voxels free (ijk = n_voxels x 3 indices; duplicates and free voxels are fine; an index outside
+ * the grid: ISDF_ERR_INVALID_ARG, nothing changed); it invalidates kept counts when it frees a voxel.
+ * Every derived product is refreshed only where it can change.  The ESDF can only rise, and only at a voxel whose old nearest
+ * occupied voxel was cleared: those voxels are found from the old values (a conservative superset, the TOUCHED voxels) and their
+ * bounding box is recomputed exactly - the integer squared distance to the nearest voxel still occupied, converted as
+ * isdf_generate_esdf converts it.  The front end's inflated bit map is recomputed over the box of the cleared voxels and its
+ * configuration-space table - and the A*'s host copy - over that box grown by (kernel_size - 1) / 2.
+ * Afterwards every product is byte for byte what a fresh ctx holds after the from-scratch sequence: isdf_set_pointcloud(the old
+ * cloud minus the removed points, as multisets) with the same explicit boundaries, resolution and threshold - for isdf_clear_voxels
+ * isdf_set_grid of the new occupancy -, then isdf_generate_esdf, isdf_frontend_build and isdf_frontend_cspace where they had been
+ * run.  As after an update the geometry, grid_epoch and the voxel indices handed out before stay, the occupancy bit grid and the ESDF
+ * bricks are rebuilt lazily, and nothing is allocated after the first call of a size on the incremental path.
+ * A clear OPENS bits of the configuration space, which the repair rule of isdf_frontend_field_set_repair is not proved for: a valid
+ * cost-to-go field is dropped in both repair modes (field_dropped = 1).  Removed voxels cannot be subtracted from the piece minima of
+ * a kept clearance report: with mode 1 of isdf_traj_check_set_watch an armed watch is re-checked against the whole new map
+ * (watch_rechecked = 1; isdf_traj_watch_info: path 2, one more update folded, the new_* fields empty) and then reads as after
+ * isdf_traj_check on the new map.  The V1 obstacle-point set and lastTstar are NOT touched: a caller who merged voxels that are now
+ * cleared (isdf_points_merge_check) must rebuild the set, or the optimizer keeps avoiding them.  When no voxel became free nothing
+ * but the counts changes.
+ * A failure (ISDF_ERR_HIP) after the counts and the occupancy have moved drops the ESDF and the front end, as the update does.
+ * isdf_clear_pointcloud: ISDF_ERR_STATE without kept counts.  Both: a multi-device ctx ISDF_ERR_UNSUPPORTED.  params may be NULL
+ * (defaults), info_out may be NULL. */
+typedef struct isdf_map_clear_params {
+    int64_t max_cleared_voxels; /* more cleared voxels than this: rebuild everything (default 65536)                           */
+    double full_fraction;       /* the grown dirty box, or the touched box of the ESDF, holds more than this share of the map's */
+                                /* voxels: rebuild everything (default 0.5).  Placeholders, as the update's       */
+    int32_t refresh_esdf;       /* 1 (default): refresh the ESDF if one is installed; 0: drop it                               */
+    int32_t refresh_frontend;   /* 1 (default): refresh the front end if built; 0: release it                                  */
+} isdf_map_clear_params;
+typedef struct isdf_map_clear_info {
+    int64_t n_points;                   /* points (or voxel entries) given                                                     */
+    int64_t n_points_ignored;           /* points whose voxel's count was 0 already (0 in the voxel form)                      */
+    int64_t n_cleared_voxels;           /* voxels that became free                                                             */
+    int32_t dirty_lo[3], dirty_hi[3];   /* index box of the cleared voxels (inclusive; lo > hi when none)                      */
+    int32_t touched_lo[3], touched_hi[3];       /* index box of the ESDF voxels recomputed on the incremental path (lo > hi: none) */
+    int32_t path;                       /* 0 nothing changed, 1 incremental, 2 full rebuild (a cap of params exceeded, or - with */
+                                        /*   an ESDF to refresh - no occupied voxel left)                                      */
+    int32_t esdf_refreshed, frontend_refreshed, cspace_refreshed, host_table_patched;
+    int32_t field_dropped;              /* 1: a VALID cost-to-go field was dropped by this call                                */
+    int32_t watch_rechecked;            /* 1: an armed clearance watch was re-checked against the whole new map                */
+    int32_t reserved;
+    int64_t esdf_voxels_recomputed;     /* voxels of the touched box (the whole map on the full path)                          */
+    int64_t esdf_voxels_raised;         /* incremental path: ESDF values that rose                                             */
+    int64_t cspace_voxels_recomputed;   /* voxels of the grown box (the whole map on the full path)                            */
+    double count_ms, esdf_ms, frontend_ms;      /* device time, events on the ctx's stream                                     */
+} isdf_map_clear_info;
+void isdf_map_clear_params_default(isdf_map_clear_params *p);
+void isdf_map_clear_sizes(int sizes_out[2]);       /* sizeof of the two structs above, for mirrors of this header            */
+int isdf_clear_pointcloud(isdf_ctx *ctx, const float *xyz, long long n_points, const isdf_map_clear_params *params,
+                          isdf_map_clear_info *info_out);
+int isdf_clear_voxels(isdf_ctx *ctx, const int32_t *ijk, long long n_voxels, const isdf_map_clear_params *params,
+                      isdf_map_clear_info *info_out);
+/* The ESDF raise in plain host code, no ctx and no device.  occ_new: the occupancy AFTER the clear (X * Y * Z bytes, 1 = occupied,
+ * z fastest; dims = {X, Y, Z}, each in [1, 4096]); esdf_inout: on entry the exact transform of the map before the clear (what
+ * isdf_generate_esdf gives for occ_new plus the cleared voxels), on return that of occ_new, the bytes of isdf_generate_esdf;
+ * cleared_ijk: the n voxels that were occupied and are free in occ_new.  info_out (nullable): n_points = n_cleared_voxels = n, the
+ * dirty and the touched box, esdf_voxels_recomputed / _raised, path 1 - or 2 when no occupied voxel is left -, the rest 0.
+ * Returns ISDF_OK or ISDF_ERR_INVALID_ARG (a null array, a bad dimension or resolution, an index outside the grid). */
+int isdf_clear_esdf_host(const uint8_t *occ_new, float *esdf_inout, const int32_t dims[3], double resolution, const int32_t *cleared_ijk,
+                         long long n_cleared, isdf_map_clear_info *info_out);
+/* The touched test alone, on the transform BEFORE the clear: touched_out (nullable) gets one byte per voxel, 1 = the voxel is
+ * recomputed.  Returns the number of touched voxels, or a negative isdf_status. */
+long long isdf_clear_touched_host(const float *esdf_old, const int32_t dims[3], double resolution, const int32_t *cleared_ijk, long long n_cleared,
+                                  uint8_t *touched_out);
 
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
