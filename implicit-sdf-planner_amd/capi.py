@@ -97,6 +97,16 @@ class IsdfFieldRepairInfo(C.Structure):
                 ("rounds", C.c_int32), ("reachable", C.c_int32), ("status", C.c_int32), ("device_ms", C.c_double)]
 
 
+FIELD_REOPEN_DROP, FIELD_REOPEN_LOWER = 0, 1             # isdf_frontend_field_set_reopen
+
+
+class IsdfFieldReopenInfo(C.Structure):
+    """isdf_field_reopen_info (include/isdf_accel.h)."""
+    _fields_ = [("opened_voxels", C.c_int64), ("opened_reached", C.c_int64), ("reached_before", C.c_int64), ("reached_voxels", C.c_int64),
+                ("free_voxels", C.c_int64), ("brick_visits", C.c_int64), ("seeded_bricks", C.c_int32), ("rounds", C.c_int32),
+                ("goal_opened", C.c_int32), ("reachable", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32), ("device_ms", C.c_double)]
+
+
 MAP_UPDATE_NONE, MAP_UPDATE_INCREMENTAL, MAP_UPDATE_FULL = 0, 1, 2      # isdf_map_update_info.path
 
 
@@ -289,6 +299,7 @@ EXPORTED_SYMBOLS = [
     "isdf_frontend_field_params_default", "isdf_frontend_field_build", "isdf_frontend_field_get", "isdf_frontend_field_value",
     "isdf_frontend_field_paths", "isdf_frontend_field_paths_device", "isdf_frontend_field_host", "isdf_frontend_field_release",
     "isdf_frontend_field_set_repair", "isdf_frontend_field_repair_info", "isdf_frontend_field_repair_sizes", "isdf_frontend_field_repair_host",
+    "isdf_frontend_field_set_reopen", "isdf_frontend_field_reopen_info", "isdf_frontend_field_reopen_sizes", "isdf_frontend_field_reopen_host",
     "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
     "isdf_map_clear_params_default", "isdf_map_clear_sizes", "isdf_clear_pointcloud", "isdf_clear_voxels", "isdf_clear_esdf_host", "isdf_clear_touched_host",
 ]
@@ -546,6 +557,14 @@ def load_library(path=None):
     lib.isdf_frontend_field_repair_sizes(sz)
     if sz[0] != C.sizeof(IsdfFieldRepairInfo):
         raise RuntimeError(f"isdf_field_repair_info: the library has {sz[0]}, the mirror {C.sizeof(IsdfFieldRepairInfo)}")
+    lib.isdf_frontend_field_set_reopen.argtypes = [C.c_void_p, C.c_int]
+    lib.isdf_frontend_field_reopen_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldReopenInfo)]
+    lib.isdf_frontend_field_reopen_sizes.argtypes = [ip]
+    lib.isdf_frontend_field_reopen_sizes.restype = None
+    lib.isdf_frontend_field_reopen_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, dp, C.POINTER(IsdfFieldReopenInfo)]
+    lib.isdf_frontend_field_reopen_sizes(sz)
+    if sz[0] != C.sizeof(IsdfFieldReopenInfo):
+        raise RuntimeError(f"isdf_field_reopen_info: the library has {sz[0]}, the mirror {C.sizeof(IsdfFieldReopenInfo)}")
     if path is None:
         _lib = lib
     return lib

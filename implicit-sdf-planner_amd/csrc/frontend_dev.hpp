@@ -83,3 +83,11 @@ int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms);
 bool isdf_field_repair_wanted(const isdf_ctx *c);
 int isdf_field_repair_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start);
 int isdf_field_repair_end(isdf_ctx *c, hipEvent_t ev_start, hipEvent_t ev_end, int *repaired);
+
+// frontend_field.hip, for the map clear: the field lowered in place after voxels opened (isdf_frontend_field_set_reopen, mode 1).  The
+// same three steps: ..._wanted: mode 1 and a valid field that is a fixed point; ..._begin enqueues the opening mark over the box
+// lo .. hi (null: the whole grid) and the first list; the caller synchronises; ..._end, given the same box, runs the rounds and the counts.
+// *reopened = 0: a bit had closed, the field stays dropped.
+bool isdf_field_reopen_wanted(const isdf_ctx *c);
+int isdf_field_reopen_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start);
+int isdf_field_reopen_end(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *reopened);

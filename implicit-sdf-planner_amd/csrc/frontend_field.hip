@@ -33,6 +33,16 @@
 // then ff_compact_kernel and the rounds of the build.  Every d < tau is kept: the chain of minimising neighbours from such a voxel to
 // the goal passes only voxels with d < tau, none of them closed, and the new graph is a subgraph of the old.  From the kept values
 // every intermediate value is again a real path's length, so the fixed point has the bytes of a build on the new map.
+// The field LOWERED after a map clear that opened voxels (occupancy only shrinks; DESIGN 4.6.3, isdf_frontend_field_set_reopen):
+//   ff_reopen_mark_kernel   the same work layout as ff_repair_mark_kernel, the comparison turned round: the opened bits (new and not
+//                           kept) are counted and kept in a word per wavefront, the new word is written, the brick is flagged, a
+//                           closed bit raises a record word (outside the premise); the lane on the goal voxel, when it opened,
+//                           stores d = 0;
+//   ff_reopen_count_kernel  after the rounds, over the same box: the opened voxels that hold a finite d;
+// between them ff_compact_kernel and the rounds of the build.  Nothing is reset: the old graph is a subgraph of the new, so every old
+// value is a path's length that still exists - an upper bound of the new least fixed point d* -, relaxation keeps it one, and a fixed
+// point >= d* with d[goal] = 0 is d* (in Dijkstra order of d*, v's predecessor u holds d*[u], so d[v] <= fl(d*[u] + w) = d*[v]).
+// A brick without an opened voxel or a lowered halo voxel satisfies its equations as before.
 // Compiled with -ffp-contract=off like frontend.hip (cell indices and cube centres round like the A*'s).
 #include "isdf_ctx.hpp"
 #include "frontend_field_host.hpp"
@@ -284,6 +294,68 @@ __global__ __launch_bounds__(256) void ff_repair_reset_kernel(FfDims D, double *
     }
 }
 
+// the reopen's record, in the repair's buffer: [opened | a bit closed | the goal cell opened | opened with a finite d afterwards]
+constexpr int FF_ROP_OPENED = 0, FF_ROP_CLOSED = 1, FF_ROP_GOAL = 2, FF_ROP_REACHED = 3;
+
+// The opening direction over the same box as ff_repair_mark_kernel, one wavefront per 64 consecutive z of a column.  open[wv]: the
+// opened bits of this wavefront's word, for ff_reopen_count_kernel (written by every wavefront of the box: nothing stale is read).
+__global__ __launch_bounds__(256) void ff_reopen_mark_kernel(FfDims D, int x0, int y0, int zb0, int ex, int ey, int ezb, const unsigned *__restrict__ cspace,
+                                                              unsigned long long *__restrict__ fm, double *__restrict__ d, unsigned *__restrict__ flags,
+                                                              unsigned long long *__restrict__ open, unsigned long long *__restrict__ rep) {
+    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long n_wv = (long long)ex * ey * ezb;
+    if (wv >= n_wv) return;
+    const int lane = threadIdx.x & 63;
+    const int zb = zb0 + (int)(wv % ezb);
+    const long long xy = wv / ezb;
+    const int y = y0 + (int)(xy % ey), x = x0 + (int)(xy / ey);
+    const int z = (zb << 6) + lane;
+    const size_t col = (size_t)x * D.Y + y;
+    const size_t v = col * D.Z + z;
+    bool fr = false;
+    if (z < D.Z) {
+        const unsigned *m = cspace + v * D.nw;
+        unsigned any = 0;
+        for (int w = 0; w < D.nw; w++) any |= m[w];
+        fr = any != 0u;
+    }
+    const unsigned long long now = __ballot(fr);
+    const unsigned long long old = fm[col * D.zblocks + zb];
+    const unsigned long long opened = now & ~old;
+    if (((opened >> lane) & 1ull) && (long long)v == D.goal) {               // (a set bit of the new word: z < D.Z)
+        d[v] = 0.0;                                        // the goal cell had not been free: the field was all +inf
+        rep[FF_ROP_GOAL] = 1ull;
+    }
+    if (lane == 0) {
+        open[wv] = opened;
+        if (now != old) {
+            fm[col * D.zblocks + zb] = now;
+            if (opened) {
+                atomicAdd(rep + FF_ROP_OPENED, (unsigned long long)__popcll(opened));
+                flags[((x / FF_BX) * D.nby + y / FF_BY) * D.nbz + zb] = 1u;
+            }
+            if (old & ~now) rep[FF_ROP_CLOSED] = 1ull;    // outside the premise: the host drops the field
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ff_reopen_count_kernel(FfDims D, int x0, int y0, int zb0, int ex, int ey, int ezb, const double *__restrict__ d,
+                                                               const unsigned long long *__restrict__ open, unsigned long long *__restrict__ rep) {
+    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wv >= (long long)ex * ey * ezb) return;
+    const unsigned long long opened = open[wv];
+    if (!opened) return;                                   // (the same word in every lane of the wavefront)
+    const int lane = threadIdx.x & 63;
+    const int zb = zb0 + (int)(wv % ezb);
+    const long long xy = wv / ezb;
+    const int y = y0 + (int)(xy % ey), x = x0 + (int)(xy / ey);
+    bool reached = false;
+    if ((opened >> lane) & 1ull)                           // (an opened bit: z < D.Z)
+        reached = (unsigned long long)__double_as_longlong(d[((size_t)x * D.Y + y) * D.Z + (zb << 6) + lane]) < FF_INF_BITS;
+    const unsigned long long hit = __ballot(reached);
+    if (lane == 0 && hit) atomicAdd(rep + FF_ROP_REACHED, (unsigned long long)__popcll(hit));
+}
+
 // GridMap3D::isInMap / getGridIndex as isdf_frontend_astar_search restates them (Gridmap3D.cpp:41-69,135-175)
 struct FfMap { int X, Y, Z; double res, bmin[3], bmax[3]; };
 __host__ __device__ inline bool ff_cell(const FfMap &M, const double p[3], int idx[3]) {
@@ -464,8 +536,8 @@ extern "C" int isdf_frontend_field_release(isdf_ctx *c) {
     isdf_ctx::FrontEnd &fe = c->fe;
     (void)hipSetDevice(c->device);
     fe.d_field.release(); fe.d_field_free.release(); fe.d_field_list.release(); fe.d_field_flags.release(); fe.d_field_cnt.release();
-    fe.h_field_cnt.release(); fe.d_field_rep.release(); fe.h_field_rep.release();
-    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false;
+    fe.h_field_cnt.release(); fe.d_field_rep.release(); fe.h_field_rep.release(); fe.d_field_open.release();
+    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false;
     return ISDF_OK;
 }
 
@@ -481,7 +553,7 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     if (n_vox > (size_t)0x7FFFFFF0) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the field indexes voxels with 31 bits");
     *info_out = isdf_frontend_field_info{};
     HIPCHK(c, hipSetDevice(c->device));
-    fe.field_valid = false; fe.field_repaired = false;
+    fe.field_valid = false; fe.field_repaired = false; fe.field_reopened = false;
     if (!fe.d_cspace) {                                    // the table stays on the device: nothing of it comes to the host
         const int rc = isdf_frontend_cspace(c, nullptr, nullptr);
         if (rc != ISDF_OK) return rc;
@@ -542,7 +614,8 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     fe.field_status = fe.field_reachable ? R.status : 1;
     fe.field_max_rounds = params ? params->max_rounds : 0;
     fe.field_free_voxels = n_free;
-    fe.field_repaired = false;
+    fe.field_reached_voxels = (long long)h[FF_CNT_REACHED];
+    fe.field_repaired = false; fe.field_reopened = false;
     info_out->reachable = fe.field_reachable ? 1 : 0;
     info_out->status = fe.field_status;
     info_out->rounds = (int32_t)R.rounds;
@@ -619,6 +692,7 @@ int isdf_field_repair_end(isdf_ctx *c, hipEvent_t ev_start, hipEvent_t ev_end, i
     fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
     fe.field_status = fe.field_reachable ? R.status : 1;
     fe.field_free_voxels = n_free;
+    fe.field_reached_voxels = (long long)h[FF_CNT_REACHED];
     fe.field_valid = true;
     fe.field_repaired = true;
     isdf_field_repair_info &I = fe.field_repair;
@@ -638,6 +712,134 @@ int isdf_field_repair_end(isdf_ctx *c, hipEvent_t ev_start, hipEvent_t ev_end, i
     I.device_ms = ms;
     *repaired = 1;
     return ISDF_OK;
+}
+
+// ---- the reopen after a map clear (called by map_clear.hip; the rule and its premise: this file's header) -------------------------
+bool isdf_field_reopen_wanted(const isdf_ctx *c) {
+    const isdf_ctx::FrontEnd &fe = c->fe;
+    return c->field_reopen_mode == 1 && fe.built && fe.field_valid && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
+}
+
+namespace {
+
+// the changed box as the two reopen kernels take it: whole 64-voxel blocks in z
+struct FfBox { int x0, y0, zb0, ex, ey, ezb; };
+FfBox ff_box(const DevGrid &G, const int lo[3], const int hi[3]) {
+    FfBox B;
+    B.x0 = lo ? lo[0] : 0; B.y0 = lo ? lo[1] : 0; B.zb0 = lo ? lo[2] >> 6 : 0;
+    B.ex = (hi ? hi[0] : G.X - 1) - B.x0 + 1; B.ey = (hi ? hi[1] : G.Y - 1) - B.y0 + 1; B.ezb = ((hi ? hi[2] : G.Z - 1) >> 6) - B.zb0 + 1;
+    return B;
+}
+
+}  // namespace
+
+// Enqueues, after the configuration-space refresh on the ctx's stream: the opening mark over the box lo .. hi (null: the whole grid),
+// ff_compact_kernel and the record's copy to the host.  The caller synchronises the stream, then calls ..._end with the same box.
+int isdf_field_reopen_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    const DevGrid &G = c->grid;
+    FfDims D = ff_dims(c);
+    const int n_bricks = D.nbx * D.nby * D.nbz;
+    const size_t n_cols = (size_t)G.X * G.Y * D.zblocks;
+    // the record shares the repair's buffers; the opened words are sized for the whole grid at once: no box of a later clear grows them
+    if (fe.d_field_rep.reserve(c, FF_REP_WORDS) || fe.h_field_rep.reserve(c, 2 * FF_REP_WORDS) || fe.d_field_open.reserve(c, n_cols)) return ISDF_ERR_HIP;
+    const FfBox B = ff_box(G, lo, hi);
+    if (B.x0 < 0 || B.y0 < 0 || B.zb0 < 0 || B.ex < 1 || B.ey < 1 || B.ezb < 1 || B.x0 + B.ex > G.X || B.y0 + B.ey > G.Y || B.zb0 + B.ezb > D.zblocks)
+        return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field reopen's box lies outside the grid");
+    const bool goal_in = fe.field_goal[0] >= 0;
+    D.goal = goal_in ? ((long long)fe.field_goal[0] * G.Y + fe.field_goal[1]) * G.Z + fe.field_goal[2] : -1ll;
+    unsigned long long *h = fe.h_field_rep.get();          // [the record as it starts | the record as the kernels left it]
+    for (int i = 0; i < 2 * FF_REP_WORDS; i++) h[i] = 0ull;
+    unsigned long long *rep = fe.d_field_rep.get(), *cnt = fe.d_field_cnt.get();
+    unsigned *flags = fe.d_field_flags.get();
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipEventRecord(ev_start, st));
+    HIPCHK(c, hipMemcpyAsync(rep, h, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
+    const long long n_wv = (long long)B.ex * B.ey * B.ezb;
+    hipLaunchKernelGGL(ff_reopen_mark_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, D, B.x0, B.y0, B.zb0, B.ex, B.ey, B.ezb, fe.d_cspace.get(),
+                       fe.d_field_free.get(), fe.d_field.get(), flags, fe.d_field_open.get(), rep);
+    hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h + FF_REP_WORDS, rep, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    return ISDF_OK;
+}
+
+// After the stream has been synchronised: the rounds from the seeded bricks, the counts.  *reopened = 1: the field is valid again
+// (status 2 when the round bound was hit, as after a build); 0: a bit had closed, the field stays dropped.
+int isdf_field_reopen_end(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *reopened) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    *reopened = 0;
+    unsigned long long *rep = fe.h_field_rep.get() + FF_REP_WORDS;
+    if (rep[FF_ROP_CLOSED]) return ISDF_OK;
+    const DevGrid &G = c->grid;
+    FfDims D = ff_dims(c);
+    const FfBox B = ff_box(G, lo, hi);
+    const hipStream_t st = c->stream;
+    volatile unsigned long long *h = fe.h_field_cnt.get();
+    const long long n_opened = (long long)rep[FF_ROP_OPENED], n_seeded = (long long)h[FF_CNT_ACTIVE];
+    const bool goal_opened = rep[FF_ROP_GOAL] != 0ull;
+    const long long n_free = fe.field_free_voxels + n_opened;
+    long long bound = n_free;
+    if (fe.field_max_rounds > 0 && fe.field_max_rounds < bound) bound = fe.field_max_rounds;
+    FfRounds R;
+    // a field without a reachable goal whose goal cell did not open is all +inf and stays so: nothing to relax
+    if (fe.field_reached_voxels > 0 || goal_opened) HIPCHK(c, ff_run_rounds(fe, D, n_seeded, bound, st, R));
+    hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)G.X * G.Y * G.Z, fe.d_field_cnt.get());
+    const long long n_wv = (long long)B.ex * B.ey * B.ezb;
+    hipLaunchKernelGGL(ff_reopen_count_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, D, B.x0, B.y0, B.zb0, B.ex, B.ey, B.ezb, fe.d_field.get(),
+                       fe.d_field_open.get(), fe.d_field_rep.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev_end, st));
+    HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), fe.d_field_cnt.get(), FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rep, fe.d_field_rep.get(), FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev_start, ev_end));
+    const bool goal_in = fe.field_goal[0] >= 0;
+    isdf_field_reopen_info &I = fe.field_reopen;
+    I = isdf_field_reopen_info{};
+    I.reached_before = fe.field_reached_voxels;
+    fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
+    fe.field_status = fe.field_reachable ? R.status : 1;
+    fe.field_free_voxels = n_free;
+    fe.field_reached_voxels = (long long)h[FF_CNT_REACHED];
+    fe.field_valid = true;
+    fe.field_reopened = true;
+    I.opened_voxels = n_opened;
+    I.opened_reached = (int64_t)rep[FF_ROP_REACHED];
+    I.reached_voxels = (int64_t)h[FF_CNT_REACHED];
+    I.free_voxels = n_free;
+    I.brick_visits = R.visits;
+    I.seeded_bricks = (int32_t)n_seeded;
+    I.rounds = (int32_t)R.rounds;
+    I.goal_opened = goal_opened ? 1 : 0;
+    I.reachable = fe.field_reachable ? 1 : 0;
+    I.status = fe.field_status;
+    I.device_ms = ms;
+    *reopened = 1;
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_set_reopen(isdf_ctx *c, int mode) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (mode != 0 && mode != 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field's reopen mode is 0 (drop) or 1 (lower in place)");
+    if (!c->peers.empty() || c->is_peer || c->rccl_comm) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "cost-to-go field on a multi-device ctx");
+    c->field_reopen_mode = mode;
+    return ISDF_OK;
+}
+
+extern "C" int isdf_frontend_field_reopen_info(isdf_ctx *c, isdf_field_reopen_info *out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
+    if (!c->fe.field_reopened) return isdf_fail(c, ISDF_ERR_STATE, "no reopen since the last isdf_frontend_field_build");
+    *out = c->fe.field_reopen;
+    return ISDF_OK;
+}
+
+extern "C" void isdf_frontend_field_reopen_sizes(int sizes_out[1]) {
+    if (sizes_out) sizes_out[0] = (int)sizeof(isdf_field_reopen_info);
 }
 
 extern "C" int isdf_frontend_field_set_repair(isdf_ctx *c, int mode) {
@@ -758,6 +960,29 @@ extern "C" int isdf_frontend_field_repair_host(const uint32_t *free_mask_new, co
             info_out->reset_voxels = C.reset_voxels;
             info_out->free_voxels = C.free_voxels;
             info_out->reached_voxels = C.reached_voxels;
+            info_out->reachable = goal_free ? 1 : 0;
+            info_out->status = goal_free ? 0 : 1;
+        }
+        return goal_free ? 1 : 0;
+    } catch (const std::bad_alloc &) {
+        return ISDF_ERR_HIP;
+    }
+}
+
+extern "C" int isdf_frontend_field_reopen_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_inout,
+                                               isdf_field_reopen_info *info_out) {
+    if (!free_mask_new || !dims || !goal_index || !d_inout || n_att < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ISDF_ERR_INVALID_ARG;
+    const int g[3] = {goal_index[0], goal_index[1], goal_index[2]};
+    try {
+        isdf_host::FieldReopenCounts C;
+        const bool goal_free = isdf_host::field_reopen(free_mask_new, dims[0], dims[1], dims[2], n_att, g, d_inout, &C);
+        if (info_out) {
+            *info_out = isdf_field_reopen_info{};
+            info_out->opened_voxels = info_out->opened_reached = C.newly_reached;       // (an opened voxel that stays +inf cannot be told from a free one that was never reached)
+            info_out->reached_before = C.reached_before;
+            info_out->reached_voxels = C.reached_voxels;
+            info_out->free_voxels = C.free_voxels;
+            info_out->goal_opened = C.goal_opened ? 1 : 0;
             info_out->reachable = goal_free ? 1 : 0;
             info_out->status = goal_free ? 0 : 1;
         }

@@ -123,4 +123,49 @@ inline bool field_repair(const uint32_t *mask_new, int X, int Y, int Z, int n_at
     return fr[(size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2]] != 0;
 }
 
+// The field LOWERED after voxels opened (occupancy only shrinks).  d: the field of the same goal on a mask of which
+// mask_new is a superset (every voxel free before is free in mask_new) - the premise; nothing here can check it.
+//   every old value is kept: it is the length of a path that still exists, an upper bound of the new least fixed point;
+//   the goal cell, free in mask_new and +inf, takes 0 (it had not been free: the field was all +inf);
+//   the heap is seeded from the finite neighbours of the voxels that are free and +inf - the opened voxels are among them -, and
+//   Dijkstra runs on.  A voxel that is never pushed has no lowered neighbour and satisfies its old equation.
+// A fixed point that is >= the least one and has d[goal] = 0 is the least one: the bytes of field_dijkstra on mask_new.
+// No old mask is given, so the counts speak of the voxels that were +inf and are finite now.  Returns true when the goal cell is
+// inside the map and free in mask_new.
+struct FieldReopenCounts { long long newly_reached = 0, reached_before = 0, free_voxels = 0, reached_voxels = 0; bool goal_opened = false; };
+inline bool field_reopen(const uint32_t *mask_new, int X, int Y, int Z, int n_att, const int goal[3], double *d, FieldReopenCounts *counts) {
+    const size_t nw = 4 * (size_t)((n_att + 127) / 128);
+    const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
+    const double inf = std::numeric_limits<double>::infinity();
+    FieldReopenCounts C;
+    std::vector<unsigned char> fr(n);
+    for (size_t v = 0; v < n; v++) {
+        fr[v] = field_voxel_free(mask_new, nw, v) ? 1 : 0;
+        C.free_voxels += fr[v];
+        C.reached_before += d[v] < inf;
+    }
+    const bool goal_in = !(goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z);
+    const size_t g = goal_in ? (size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2] : 0;
+    FieldHeap heap;
+    if (goal_in && fr[g] && !(d[g] < inf)) { C.goal_opened = true; d[g] = 0.0; heap.push(0.0, g); }
+    for (size_t v = 0; v < n; v++) {
+        if (!fr[v] || d[v] < inf) continue;
+        const int x = (int)(v / YZ), y = (int)((v / Z) % Y), z = (int)(v % Z);
+        for (int i = -1; i < 2; i++)
+            for (int j = -1; j < 2; j++)
+                for (int k = -1; k < 2; k++) {
+                    if (!(i | j | k)) continue;
+                    const int ux = x + i, uy = y + j, uz = z + k;
+                    if (ux < 0 || ux >= X || uy < 0 || uy >= Y || uz < 0 || uz >= Z) continue;
+                    const size_t u = (size_t)ux * YZ + (size_t)uy * Z + (size_t)uz;
+                    if (fr[u] && d[u] < inf) heap.push(d[u], u);
+                }
+    }
+    field_relax_heap(mask_new, X, Y, Z, nw, heap, d);
+    for (size_t v = 0; v < n; v++) C.reached_voxels += d[v] < inf;
+    C.newly_reached = C.reached_voxels - C.reached_before;
+    if (counts) *counts = C;
+    return goal_in && fr[g] != 0;
+}
+
 }  // namespace isdf_host

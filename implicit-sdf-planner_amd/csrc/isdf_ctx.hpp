@@ -184,8 +184,13 @@ struct isdf_ctx {
         int field_status = 0, field_max_rounds = 0; long long field_free_voxels = 0;
         DevBuf<unsigned long long> d_field_rep; PinBuf<unsigned long long> h_field_rep;
         bool field_repaired = false; isdf_field_repair_info field_repair{};
+        // the reopen after a clear (it shares the repair's record buffers): the opened bits of the changed box, one word per
+        // wavefront of the mark kernel; the voxels reached by the last build / repair / reopen; the last reopen's report
+        DevBuf<unsigned long long> d_field_open; long long field_reached_voxels = 0;
+        bool field_reopened = false; isdf_field_reopen_info field_reopen{};
     } fe;
     int field_repair_mode = 0;                  // isdf_frontend_field_set_repair: outlives isdf_frontend_build (fe is reset by it)
+    int field_reopen_mode = 0;                  // isdf_frontend_field_set_reopen: likewise
     int traj_watch_mode = 0;                    // isdf_traj_check_set_watch: outlives the check (the watch itself: TrajCheckState::w)
     struct isdf_xchg *xchg = nullptr;           // peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip)
     isdf_progress_fn progress = nullptr;        // isdf_set_progress: the optimizer drivers' progress / cancel hook

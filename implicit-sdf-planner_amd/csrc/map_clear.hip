@@ -218,7 +218,10 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params
     const bool do_fe = fe.built && P.refresh_frontend != 0;
     const MuBox grown = mu_box_grow(box, do_fe ? (fe.cfg.kernel_size - 1) / 2 : 0, dims);
     bool full = (unsigned long long)R.n_cleared > (unsigned long long)cap || (double)mu_box_voxels(grown) > P.full_fraction * (double)n_vox;
-    // The cost-to-go field: a clear opens bits, which the repair's rule is not proved for - dropped in both repair modes.
+    // The cost-to-go field: dropped (mode 0 of isdf_frontend_field_set_reopen; the repair's rule is not proved for opened bits), or
+    // lowered in place once the configuration space is the new map's (mode 1).  It is invalid from here until the reopen has gone
+    // through: every error path leaves it dropped.
+    const bool reopen = do_fe && isdf_field_reopen_wanted(c);
     if (fe.field_valid) { fe.field_valid = false; fe.field_reachable = false; info.field_dropped = 1; }
 
     // ---- ESDF
@@ -284,7 +287,14 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params
     HIPCHK(c, hipEventRecord(S.ev[5], st));
     if (patch) HIPCHK(c, hipMemcpyAsync(S.h_pack.get(), S.d_pack, pack_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(S.h_rec.get() + 1, S.d_rec.get() + 1, sizeof(McEsdfRecord), hipMemcpyDeviceToHost, st));
+    const int *const f_lo = full ? nullptr : grown.lo, *const f_hi = full ? nullptr : grown.hi;
+    if (reopen && (rc = isdf_field_reopen_begin(c, f_lo, f_hi, S.ev[6]))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
+    if (reopen) {                       // the rounds read one word each; the host table is patched after them
+        int reopened = 0;
+        if ((rc = isdf_field_reopen_end(c, f_lo, f_hi, S.ev[6], S.ev[7], &reopened))) return rc;
+        if (reopened) info.field_dropped = 0;
+    }
     if (patch) {
         mu_scatter_box(fe.h_cspace, dims, nw, grown, S.h_pack.get());
         info.host_table_patched = 1;

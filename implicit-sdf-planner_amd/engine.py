@@ -305,6 +305,29 @@ def frontend_field_repair_host(free_mask_new, goal_index, n_att, d, lib=None):
     return out, bool(rc), info
 
 
+def frontend_field_reopen_host(free_mask_new, goal_index, n_att, d, lib=None):
+    """isdf_frontend_field_reopen_host: the field `d` of `goal_index` (float64 [X, Y, Z], of a table of which free_mask_new is a superset:
+    voxels only opened) lowered in plain host code - every old value is kept, an opened goal cell takes 0, and Dijkstra runs on from the
+    finite neighbours of the free voxels that hold +inf.  Returns (d_new [X, Y, Z], reachable, IsdfFieldReopenInfo); `d` itself is not
+    changed.  No old table is given: opened_voxels counts the voxels that were +inf and are finite now."""
+    lib = lib or capi.load_library()
+    m = np.ascontiguousarray(free_mask_new, dtype=np.uint32)
+    nw = 4 * ((int(n_att) + 127) // 128)
+    if m.ndim != 4 or m.shape[3] != nw:
+        raise ValueError(f"free_mask_new must be [X, Y, Z, {nw}]")
+    out = np.array(d, dtype=np.float64, order="C")
+    if out.shape != m.shape[:3]:
+        raise ValueError(f"d must be {m.shape[:3]}")
+    dims = np.array(m.shape[:3], dtype=np.int32)
+    g = np.ascontiguousarray(goal_index, dtype=np.int32).reshape(3)
+    info = capi.IsdfFieldReopenInfo()
+    rc = lib.isdf_frontend_field_reopen_host(m.ctypes.data_as(C.c_void_p), dims.ctypes.data_as(C.c_void_p), int(n_att), g.ctypes.data_as(C.c_void_p), _p(out),
+                                             C.byref(info))
+    if rc < 0:
+        raise IsdfError(rc, "isdf_frontend_field_reopen_host: bad arguments")
+    return out, bool(rc), info
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -690,6 +713,17 @@ class Engine:
         """isdf_frontend_field_repair_info: the last repair's IsdfFieldRepairInfo (ISDF_ERR_STATE: none since the last build)."""
         info = capi.IsdfFieldRepairInfo()
         self._check(self.lib.isdf_frontend_field_repair_info(self.h, C.byref(info)))
+        return info
+
+    def frontend_field_set_reopen(self, mode):
+        """isdf_frontend_field_set_reopen: what clear_pointcloud / clear_voxels do with a valid field when a voxel became free -
+        0 (default) drop it, 1 lower it in place (every old value is kept, the relaxation starts at the opened voxels' bricks)."""
+        self._check(self.lib.isdf_frontend_field_set_reopen(self.h, int(mode)))
+
+    def frontend_field_reopen_info(self):
+        """isdf_frontend_field_reopen_info: the last reopen's IsdfFieldReopenInfo (ISDF_ERR_STATE: none since the last build)."""
+        info = capi.IsdfFieldReopenInfo()
+        self._check(self.lib.isdf_frontend_field_reopen_info(self.h, C.byref(info)))
         return info
 
     def frontend_field_release(self):

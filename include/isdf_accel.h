@@ -1196,6 +1196,57 @@ void isdf_frontend_field_repair_sizes(int sizes_out[1]);      /* sizeof of the s
 int isdf_frontend_field_repair_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3],
                                     double *d_inout, isdf_field_repair_info *info_out);
 
+/* ---- the field lowered in place after a clear --------------------------------------------------------------- */
+/* isdf_clear_pointcloud / isdf_clear_voxels (below) only ever OPEN voxels: occupancy shrinks, free bits of the configuration-space
+ * table rise.  That is the premise of the rule:
+ *   opened = the voxels that were not free when the field was built (or last repaired / reopened) and whose word is non-zero now;
+ *            their old d is +inf.
+ *   Every old value is kept; when the goal cell is among the opened voxels (the field was all +inf) it takes d = 0; the build's
+ *   relaxation runs on from there, starting at the bricks that hold an opened voxel.
+ * Why the bytes are those of a build on the new map: the old graph is a subgraph of the new, so every old finite d is the length of
+ * a path that still exists, an upper bound of the new least fixed point d*; relaxation only forms further such sums, so nothing
+ * falls below d*; and a fixed point that is >= d* with d[goal] = 0 IS d* (walk the voxels in Dijkstra order of d*: the predecessor
+ * u of v already holds d*[u], so d[v] <= fl(d*[u] + w) = d*[v]).  A brick without an opened voxel and without a lowered halo voxel
+ * satisfies its equations as before, so starting at the opened voxels' bricks loses nothing.  An opened voxel whose neighbours are
+ * all +inf stays +inf; a field without a reachable goal whose goal cell did not open stays all +inf, with zero rounds.  If a bit
+ * CLOSED - impossible while occupancy only shrinks - the rule is not trusted and the field is dropped.
+ * isdf_frontend_field_set_reopen: mode 0 (default) - a clear that frees a voxel drops a valid field, field_dropped = 1; mode 1 -
+ * such a clear lowers a valid field in place, on both of its paths and in both of its forms, on the ctx's stream after the
+ * configuration-space refresh; afterwards field_dropped = 0 and isdf_frontend_field_get / _value / _paths[_device] answer as after
+ * isdf_frontend_field_build on the new map.  A reopen that hits its round bound (the free voxels of the new map, or the max_rounds
+ * of the build) leaves a valid status-2 field, as the build does.  Also with mode 1 the field is dropped, field_dropped = 1, when
+ * it had status 2, when refresh_frontend = 0, when a bit closed, or when a step fails (the clear then fails as a whole and drops
+ * every derived product).  The mode outlives isdf_frontend_build and is independent of isdf_frontend_field_set_repair, which
+ * decides about updates only.  Other modes: ISDF_ERR_INVALID_ARG; a multi-device ctx: ISDF_ERR_UNSUPPORTED. */
+int isdf_frontend_field_set_reopen(isdf_ctx *ctx, int mode);
+typedef struct isdf_field_reopen_info {
+    int64_t opened_voxels;      /* voxels whose free bit rose                                                                 */
+    int64_t opened_reached;     /* ... that have a finite d afterwards                                                        */
+    int64_t reached_before;     /* voxels with a finite d before the reopen                                                   */
+    int64_t reached_voxels;     /* ... and after it                                                                           */
+    int64_t free_voxels;        /* of the new map                                                                             */
+    int64_t brick_visits;       /* bricks relaxed, over all rounds                                                            */
+    int32_t seeded_bricks;      /* bricks that hold an opened voxel: the first active list                                    */
+    int32_t rounds;             /* launches of the relaxation                                                                 */
+    int32_t goal_opened;        /* 1: the goal cell was among the opened voxels                                               */
+    int32_t reachable, status;  /* as isdf_frontend_field_info                                                                */
+    int32_t reserved;
+    double device_ms;           /* device time from the mark kernel to the end of the counts                                  */
+} isdf_field_reopen_info;
+/* The last reopen's report; ISDF_ERR_STATE when there was none since the last isdf_frontend_field_build.  A repair does not touch
+ * it, and a reopen does not touch isdf_frontend_field_repair_info. */
+int isdf_frontend_field_reopen_info(isdf_ctx *ctx, isdf_field_reopen_info *out);
+void isdf_frontend_field_reopen_sizes(int sizes_out[1]);      /* sizeof of the struct above, for mirrors of this header        */
+/* The same rule in plain host code, no ctx and no device.  d_inout: on entry the field of goal_index on a table of which
+ * free_mask_new (isdf_frontend_field_host's layout) is a superset - every voxel free before is free in it -, on return the field on
+ * free_mask_new, the bytes of isdf_frontend_field_host.  Dijkstra continues from the kept finite voxels: the heap is seeded from the
+ * finite neighbours of the voxels with a non-zero word and d = +inf, and from the goal when it is free and +inf.  info_out may be
+ * NULL.  No old table is given, so an opened voxel that stays +inf cannot be told from one that was free and unreached:
+ * opened_voxels = opened_reached = the voxels that were +inf and are finite now; seeded_bricks, rounds, brick_visits and device_ms
+ * stay 0.  Returns 1 (the goal cell is in the map and free), 0 (not), or a negative isdf_status. */
+int isdf_frontend_field_reopen_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3],
+                                    double *d_inout, isdf_field_reopen_info *info_out);
+
 /* ---- the map updated in place from new sensor points ---------------------------------------------------------- */
 /* isdf_set_pointcloud rebuilds everything from the full cloud.  isdf_update_pointcloud takes only the NEW points (n_points x 3
  * floats, binned as isdf_set_pointcloud bins them: a point outside the box counts for voxel (0,0,0)), adds them to the per-voxel
@@ -1268,8 +1319,10 @@ int isdf_map_counts_get(isdf_ctx *ctx, uint32_t *counts_out);
  * isdf_set_grid of the new occupancy -, then isdf_generate_esdf, isdf_frontend_build and isdf_frontend_cspace where they had been
  * run.  As after an update the geometry, grid_epoch and the voxel indices handed out before stay, the occupancy bit grid and the ESDF
  * bricks are rebuilt lazily, and nothing is allocated after the first call of a size on the incremental path.
- * A clear OPENS bits of the configuration space, which the repair rule of isdf_frontend_field_set_repair is not proved for: a valid
- * cost-to-go field is dropped in both repair modes (field_dropped = 1).  Removed voxels cannot be subtracted from the piece minima of
+ * A clear OPENS bits of the configuration space, which the repair rule of isdf_frontend_field_set_repair is not proved for: that
+ * switch does not bear on a clear.  A valid cost-to-go field is dropped (field_dropped = 1) in mode 0 of
+ * isdf_frontend_field_set_reopen, the default, and lowered in place by a relaxation seeded at the opened voxels in mode 1
+ * (field_dropped = 0).  Removed voxels cannot be subtracted from the piece minima of
  * a kept clearance report: with mode 1 of isdf_traj_check_set_watch an armed watch is re-checked against the whole new map
  * (watch_rechecked = 1; isdf_traj_watch_info: path 2, one more update folded, the new_* fields empty) and then reads as after
  * isdf_traj_check on the new map.  The V1 obstacle-point set and lastTstar are NOT touched: a caller who merged voxels that are now
