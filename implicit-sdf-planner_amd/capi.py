@@ -141,6 +141,18 @@ class IsdfMapClearInfo(C.Structure):
                 ("count_ms", C.c_double), ("esdf_ms", C.c_double), ("frontend_ms", C.c_double)]
 
 
+class IsdfMapScanParams(C.Structure):
+    """isdf_map_scan_params (include/isdf_accel.h)."""
+    _fields_ = [("miss_weight", C.c_int32), ("reserved", C.c_int32), ("clear", IsdfMapClearParams), ("update", IsdfMapUpdateParams)]
+
+
+class IsdfMapScanInfo(C.Structure):
+    """isdf_map_scan_info (include/isdf_accel.h)."""
+    _fields_ = [("n_rays", C.c_int64), ("n_rays_skipped", C.c_int64), ("n_hits", C.c_int64), ("n_free_voxels", C.c_int64),
+                ("n_hit_voxels", C.c_int64), ("ray_lo", C.c_int32 * 3), ("ray_hi", C.c_int32 * 3), ("trace_ms", C.c_double),
+                ("clear", IsdfMapClearInfo), ("update", IsdfMapUpdateInfo)]
+
+
 class IsdfPlanConfig(C.Structure):
     """isdf_plan_config: what a plan needs from the reference's yaml files (include/isdf_accel.h)."""
     _fields_ = [("sweep", IsdfConfig), ("frontend", IsdfFrontendConfig), ("occupancy_resolution", C.c_double),
@@ -302,6 +314,7 @@ EXPORTED_SYMBOLS = [
     "isdf_frontend_field_set_reopen", "isdf_frontend_field_reopen_info", "isdf_frontend_field_reopen_sizes", "isdf_frontend_field_reopen_host",
     "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
     "isdf_map_clear_params_default", "isdf_map_clear_sizes", "isdf_clear_pointcloud", "isdf_clear_voxels", "isdf_clear_esdf_host", "isdf_clear_touched_host",
+    "isdf_map_scan_params_default", "isdf_map_scan_sizes", "isdf_integrate_scan", "isdf_scan_sets_host", "isdf_scan_ray_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -549,6 +562,21 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfMapClearParams), C.sizeof(IsdfMapClearInfo)]:
         raise RuntimeError(f"isdf_map_clear structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfMapClearParams), C.sizeof(IsdfMapClearInfo)]}")
+    sp, si = C.POINTER(IsdfMapScanParams), C.POINTER(IsdfMapScanInfo)
+    lib.isdf_map_scan_params_default.argtypes = [sp]
+    lib.isdf_map_scan_params_default.restype = None
+    lib.isdf_map_scan_sizes.argtypes = [ip]
+    lib.isdf_map_scan_sizes.restype = None
+    lib.isdf_integrate_scan.argtypes = [C.c_void_p, dp, C.POINTER(C.c_float), C.c_void_p, C.c_longlong, sp, si]
+    lib.isdf_scan_sets_host.argtypes = [dp, dp, C.c_double, C.POINTER(C.c_int32), dp, C.POINTER(C.c_float), C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_longlong)]
+    lib.isdf_scan_sets_host.restype = C.c_longlong
+    lib.isdf_scan_ray_host.argtypes = [dp, dp, C.c_double, C.POINTER(C.c_int32), dp, C.POINTER(C.c_float), C.c_void_p, C.c_longlong]
+    lib.isdf_scan_ray_host.restype = C.c_longlong
+    lib.isdf_map_scan_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfMapScanParams), C.sizeof(IsdfMapScanInfo)]:
+        raise RuntimeError(f"isdf_map_scan structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfMapScanParams), C.sizeof(IsdfMapScanInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

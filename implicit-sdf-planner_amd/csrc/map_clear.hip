@@ -30,23 +30,6 @@
 
 namespace isdf {
 
-// the count stage's hand-over record: 64 bytes, zeroed (box: empty) before every clear
-struct McRecord {
-    unsigned n_cleared;                 // voxels that became free (may exceed the list's capacity: the full path follows)
-    unsigned pad0;
-    int lo[3], hi[3];                   // the dirty box
-    unsigned long long ignored;         // points whose voxel's count was 0
-    unsigned pad[6];
-};
-// the ESDF stage's record, the second 64 bytes
-struct McEsdfRecord {
-    int lo[3], hi[3];                   // the touched box
-    unsigned any_occ, pad0;             // some voxel of the map is still occupied
-    unsigned long long touched, raised;
-    unsigned pad[4];
-};
-static_assert(sizeof(McRecord) == 64 && sizeof(McEsdfRecord) == 64 && sizeof(MuRecord) == 64, "each hand-over record is one 64-byte line");
-
 template <bool VOXELS>
 __global__ __launch_bounds__(256) void mc_mark_kernel(const void *__restrict__ in, long long n, DevGrid G, unsigned *__restrict__ counts, unsigned thr,
                                                       uint8_t *__restrict__ occ, MuVoxel *__restrict__ list, unsigned cap, McRecord *__restrict__ rec) {
@@ -201,8 +184,10 @@ void empty_boxes(isdf_map_clear_info &info) {
     for (int a = 0; a < 3; a++) { info.dirty_lo[a] = info.touched_lo[a] = 0; info.dirty_hi[a] = info.touched_hi[a] = -1; }
 }
 
+}  // namespace
+
 // everything after the hand-over of a call that freed at least one voxel
-int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const McRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info) {
+int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const McRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info) {
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     const int dims[3] = {G.X, G.Y, G.Z};
@@ -323,6 +308,8 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params
     return ISDF_OK;
 }
 
+namespace {
+
 // the clear proper; `in` is the host array of the points (voxels == false) or of the checked voxel indices
 int map_clear(isdf_ctx *c, const void *in, long long n_in, bool voxels, const isdf_map_clear_params *params, isdf_map_clear_info *info_out) {
     isdf_map_clear_params P;
@@ -386,7 +373,7 @@ int map_clear(isdf_ctx *c, const void *in, long long n_in, bool voxels, const is
         return ISDF_OK;
     }
     // from here on the occupancy has moved: a failure must not leave products behind that describe the old map
-    rc = refresh_products(c, S, P, R, cap, voxels, info);
+    rc = mc_refresh_products(c, S, P, R, cap, voxels, info);
     if (rc != ISDF_OK) { mu_drop_derived(c, voxels); return rc; }
     if (info_out) *info_out = info;
     return ISDF_OK;

@@ -1,0 +1,356 @@
+// A range scan integrated into the map: isdf_integrate_scan, the producer of map_clear.hip's and map_update.hip's inputs.
+//   ms_trace_kernel  one ray per lane, grid-stride: the integer walk of map_scan_host.hpp from the sensor's tick to the end point's.
+//                    Every visited voxel sets its bit in the free-bit grid, the end voxel of a hit ray its bit in the hit-bit grid
+//                    instead.  The rays of one scan share their first voxels: a lane reads the word and leaves the atomic OR out when
+//                    the bit is set already (bits only go from 0 to 1 during the kernel, so a stale read costs an OR, never a bit).
+//                    The visited box - every walk stays in the box of its two ends - the skipped rays and the hit rays are reduced per
+//                    workgroup in LDS and then into the call's record.
+//   ms_apply_kernel  over the visited box, which it reads from that record: one lane per dword of a column's bits.  F = free bit set and
+//                    hit bit clear: the count goes down by miss_weight and not below 0, and the voxel whose count leaves
+//                    [thr, inf) is freed, listed and boxed into an McRecord exactly as mc_mark_kernel's crossing lane does it -
+//                    `ignored` counts what miss_weight single removals would have found at 0.  One lane owns a voxel: no atomics on the
+//                    counts.  Also |F| and the distinct voxels of H.
+//   ms_hits_kernel   one lane per ray again, after the clear's products are in place: the end voxel of a hit ray counts up by one,
+//                    mu_mark_kernel's crossing test and MuRecord.
+// Then map_clear.hip's and map_update.hip's own refresh stages, in that order: the call IS isdf_clear_pointcloud of miss_weight
+// centres of every voxel of F followed by isdf_update_pointcloud of the hit end points, and reports what those two calls report.
+#include "isdf_ctx.hpp"
+#include "map_scan_host.hpp"
+#include "map_update_state.hpp"
+#include "swept_field.hpp"
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+namespace isdf {
+
+// the ray stage's record, the third 64 bytes of the hand-over
+struct MsRecord {
+    unsigned long long n_skipped, n_hits, n_free, n_hit_voxels;
+    int lo[3], hi[3];                   // the visited box
+    unsigned pad[2];
+};
+static_assert(sizeof(MsRecord) == 64, "each hand-over record is one 64-byte line");
+
+struct MsOrigin { int q[3]; };
+
+__device__ __forceinline__ bool ms_end_tick(const DevGrid &G, const float *__restrict__ xyz, long long i, int q[3]) {
+    const int dims[3] = {G.X, G.Y, G.Z};
+    return ms_quantize(G.bmin, G.bmax, G.res, dims, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], q);
+}
+
+__device__ __forceinline__ void ms_set_bit(unsigned *bits, size_t a) {
+    unsigned *const w = bits + (a >> 5);
+    const unsigned b = 1u << (unsigned)(a & 31);
+    if (!(*w & b)) atomicOr(w, b);
+}
+
+__global__ __launch_bounds__(256) void ms_trace_kernel(const float *__restrict__ xyz, const uint8_t *__restrict__ hit, long long n, DevGrid G, MsOrigin O,
+                                                       unsigned *free_bits, unsigned *hit_bits, MsRecord *__restrict__ rec) {
+    __shared__ int s_lo[3], s_hi[3];
+    __shared__ unsigned s_skipped, s_hits;
+    if (threadIdx.x < 3) { s_lo[threadIdx.x] = 0x7FFFFFFF; s_hi[threadIdx.x] = -1; }
+    if (threadIdx.x == 0) { s_skipped = 0u; s_hits = 0u; }
+    __syncthreads();
+    int lo[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, hi[3] = {-1, -1, -1};
+    unsigned skipped = 0, hits = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        int qe[3];
+        if (!ms_end_tick(G, xyz, i, qe)) { skipped++; continue; }
+        const bool is_hit = !hit || hit[i] != 0;
+        MsRay r;
+        ms_ray_begin(O.q, qe, r);
+        for (int a = 0; a < 3; a++) {
+            const int ve = qe[a] >> MS_TICKS_LOG2;
+            lo[a] = min(lo[a], min(r.v[a], ve));
+            hi[a] = max(hi[a], max(r.v[a], ve));
+        }
+        for (;;) {
+            const size_t a = ((size_t)r.v[0] * G.Y + r.v[1]) * G.Z + r.v[2];           // inside the grid: the walk stays between two voxels of it
+            const bool last = ms_ray_done(r);
+            if (last && is_hit) { ms_set_bit(hit_bits, a); hits++; }
+            else ms_set_bit(free_bits, a);
+            if (last) break;
+            ms_ray_step(r);
+        }
+    }
+    if (hi[0] >= 0) {
+        atomicMin(&s_lo[0], lo[0]); atomicMin(&s_lo[1], lo[1]); atomicMin(&s_lo[2], lo[2]);
+        atomicMax(&s_hi[0], hi[0]); atomicMax(&s_hi[1], hi[1]); atomicMax(&s_hi[2], hi[2]);
+    }
+    if (skipped) atomicAdd(&s_skipped, skipped);
+    if (hits) atomicAdd(&s_hits, hits);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_hi[0] >= 0) {
+            atomicMin(&rec->lo[0], s_lo[0]); atomicMin(&rec->lo[1], s_lo[1]); atomicMin(&rec->lo[2], s_lo[2]);
+            atomicMax(&rec->hi[0], s_hi[0]); atomicMax(&rec->hi[1], s_hi[1]); atomicMax(&rec->hi[2], s_hi[2]);
+        }
+        if (s_skipped) atomicAdd(&rec->n_skipped, (unsigned long long)s_skipped);
+        if (s_hits) atomicAdd(&rec->n_hits, (unsigned long long)s_hits);
+    }
+}
+
+__global__ __launch_bounds__(256) void ms_apply_kernel(DevGrid G, const unsigned *__restrict__ free_bits, const unsigned *__restrict__ hit_bits,
+                                                       unsigned *__restrict__ counts, unsigned thr, unsigned miss, uint8_t *__restrict__ occ,
+                                                       MuVoxel *__restrict__ list, unsigned cap, MsRecord *__restrict__ srec, McRecord *__restrict__ rec) {
+    const int lo0 = srec->lo[0], lo1 = srec->lo[1], lo2 = srec->lo[2], hi0 = srec->hi[0], hi1 = srec->hi[1], hi2 = srec->hi[2];
+    if (hi0 < lo0 || hi1 < lo1 || hi2 < lo2) return;            // no ray was traced
+    const int e1 = hi1 - lo1 + 1;
+    const int wz = ((hi2 - lo2 + 32) >> 5) + 1;                 // dwords that the z range of one column can touch, at any alignment
+    const long long n = (long long)(hi0 - lo0 + 1) * e1 * wz;
+    unsigned long long n_free = 0, n_hitv = 0, ignored = 0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        const int k = (int)(t % wz);
+        const long long xy = t / wz;
+        const int y = lo1 + (int)(xy % e1), x = lo0 + (int)(xy / e1);
+        const size_t base = ((size_t)x * G.Y + y) * G.Z;
+        const size_t a0 = base + lo2, a1 = base + hi2;
+        const size_t w = (a0 >> 5) + k;
+        if (w > (a1 >> 5)) continue;
+        const size_t first = max(a0, w << 5), last = min(a1, (w << 5) + 31);             // this column's own bits of the dword
+        const unsigned mask = (0xFFFFFFFFu << (unsigned)(first & 31)) & (0xFFFFFFFFu >> (31u - (unsigned)(last & 31)));
+        const unsigned hb = hit_bits[w] & mask;
+        unsigned fb = free_bits[w] & mask & ~hb;
+        n_hitv += __popc(hb);
+        n_free += __popc(fb);
+        if (miss == 0u) continue;
+        while (fb) {
+            const int b = __ffs(fb) - 1;
+            fb &= fb - 1;
+            const size_t a = (w << 5) + b;
+            const unsigned was = counts[a];
+            const unsigned now = was > miss ? was - miss : 0u;
+            ignored += miss - (was - now);
+            if (now != was) counts[a] = now;
+            if (thr >= 1u && was >= thr && now < thr) {         // thr == 0: every voxel stays occupied
+                occ[a] = 0;
+                const int z = (int)(a - base);
+                const unsigned pos = atomicAdd(&rec->n_cleared, 1u);
+                if (pos < cap) list[pos] = MuVoxel{(unsigned short)x, (unsigned short)y, (unsigned short)z, 0};
+                atomicMin(&rec->lo[0], x); atomicMin(&rec->lo[1], y); atomicMin(&rec->lo[2], z);
+                atomicMax(&rec->hi[0], x); atomicMax(&rec->hi[1], y); atomicMax(&rec->hi[2], z);
+            }
+        }
+    }
+    if (n_free) atomicAdd(&srec->n_free, n_free);
+    if (n_hitv) atomicAdd(&srec->n_hit_voxels, n_hitv);
+    if (ignored) atomicAdd(&rec->ignored, ignored);
+}
+
+__global__ __launch_bounds__(256) void ms_hits_kernel(const float *__restrict__ xyz, const uint8_t *__restrict__ hit, long long n, DevGrid G,
+                                                      unsigned *__restrict__ counts, unsigned thr, uint8_t *__restrict__ occ, const float *__restrict__ esdf,
+                                                      MuVoxel *__restrict__ list, unsigned cap, MuRecord *__restrict__ rec) {
+    if (esdf && blockIdx.x == 0 && threadIdx.x == 0) rec->esdf0 = __float_as_uint(esdf[0]);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        int qe[3];
+        if ((hit && hit[i] == 0) || !ms_end_tick(G, xyz, i, qe)) continue;
+        const int ix = qe[0] >> MS_TICKS_LOG2, iy = qe[1] >> MS_TICKS_LOG2, iz = qe[2] >> MS_TICKS_LOG2;
+        const size_t a = ((size_t)ix * G.Y + iy) * G.Z + iz;
+        const unsigned old = atomicAdd(&counts[a], 1u);
+        if (thr >= 1u && old + 1u == thr) {                     // mu_mark_kernel's crossing: exactly one add sees it
+            occ[a] = 1;
+            const unsigned pos = atomicAdd(&rec->n_new, 1u);
+            if (pos < cap) list[pos] = MuVoxel{(unsigned short)ix, (unsigned short)iy, (unsigned short)iz, 0};
+            atomicMin(&rec->lo[0], ix); atomicMin(&rec->lo[1], iy); atomicMin(&rec->lo[2], iz);
+            atomicMax(&rec->hi[0], ix); atomicMax(&rec->hi[1], iy); atomicMax(&rec->hi[2], iz);
+        }
+    }
+}
+
+}  // namespace isdf
+
+using namespace isdf;
+
+extern "C" void isdf_map_scan_params_default(isdf_map_scan_params *p) {
+    if (!p) return;
+    p->miss_weight = 1;
+    p->reserved = 0;
+    isdf_map_clear_params_default(&p->clear);
+    isdf_map_update_params_default(&p->update);
+}
+
+extern "C" void isdf_map_scan_sizes(int sizes_out[2]) {
+    if (!sizes_out) return;
+    sizes_out[0] = (int)sizeof(isdf_map_scan_params); sizes_out[1] = (int)sizeof(isdf_map_scan_info);
+}
+
+namespace {
+
+void empty_info(isdf_map_scan_info &info) {
+    for (int a = 0; a < 3; a++) {
+        info.ray_lo[a] = info.clear.dirty_lo[a] = info.clear.touched_lo[a] = info.update.dirty_lo[a] = 0;
+        info.ray_hi[a] = info.clear.dirty_hi[a] = info.clear.touched_hi[a] = info.update.dirty_hi[a] = -1;
+    }
+}
+
+// the hand-over of a count stage: the record(s) to the host and one synchronisation.  The kernels before it may have run: a failure
+// here leaves counts and occupancy consistent with each other and drops what was derived from the old map.
+int hand_over(isdf_ctx *c, MapUpdateState &S, hipEvent_t ev_end, int n_records) {
+    hipError_t e = hipEventRecord(ev_end, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(S.h_rec.get(), S.d_rec, (size_t)n_records * sizeof(MuRecord), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) return ISDF_OK;
+    c->err = std::string("scan hand-over: ") + hipGetErrorString(e);
+    mu_drop_derived(c, false);
+    return ISDF_ERR_HIP;
+}
+
+int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8_t *hit, long long n_rays, const isdf_map_scan_params &P, isdf_map_scan_info *info_out) {
+    isdf_map_scan_info info{};
+    empty_info(info);
+    info.n_rays = n_rays;
+    HIPCHK(c, hipSetDevice(c->device));
+    MapUpdateState *Sp;
+    { const int rc0 = mu_state(c, &Sp); if (rc0) return rc0; }
+    MapUpdateState &S = *Sp;
+    for (hipEvent_t &e : S.ev_scan) if (!e) HIPCHK(c, hipEventCreate(&e));
+    const hipStream_t st = c->stream;
+    const DevGrid &G = c->grid;
+    const unsigned long long n_vox = (unsigned long long)G.X * G.Y * G.Z;
+    const size_t n_words = (size_t)((n_vox + 31) / 32);
+    const unsigned thr = (unsigned)c->counts_thr, miss = (unsigned)P.miss_weight;
+    int rc;
+
+    // ---- scratch: nothing below allocates after the first call of a size.  The lists' capacities as the two calls would choose them,
+    // with the number of voxels the rays can visit in place of the number of points (which is known only after the trace).
+    const unsigned long long reach = (unsigned long long)n_rays >= n_vox ? n_vox : std::min<unsigned long long>(n_vox, (unsigned long long)n_rays * (unsigned)(G.X + G.Y + G.Z));
+    const unsigned cap_clear = (unsigned)std::min<unsigned long long>({(unsigned long long)P.clear.max_cleared_voxels, reach, 0x7FFFFFFFull});
+    const unsigned long long cap_update_most = std::min<unsigned long long>({(unsigned long long)P.update.max_new_voxels, (unsigned long long)n_rays, n_vox, 0x7FFFFFFFull});
+    const size_t xyz_bytes = (size_t)n_rays * 3 * sizeof(float);
+    if ((rc = S.d_in.reserve(c, xyz_bytes + (hit ? (size_t)n_rays : 0)))) return rc;
+    if ((rc = S.d_list.reserve(c, (size_t)std::max<unsigned long long>({cap_clear, cap_update_most, 1ull})))) return rc;
+    if ((rc = S.d_rec.reserve(c, 3))) return rc;
+    if ((rc = S.h_rec.reserve(c, 3))) return rc;
+    if ((rc = S.d_free_bits.reserve(c, n_words))) return rc;
+    if ((rc = S.d_hit_bits.reserve(c, n_words))) return rc;
+    const float *const d_xyz = (const float *)S.d_in.get();
+    const uint8_t *const d_hit = hit ? (const uint8_t *)S.d_in.get() + xyz_bytes : nullptr;
+    McRecord *const d_mc = (McRecord *)S.d_rec.get();
+    MsRecord *const d_ms = (MsRecord *)(S.d_rec.get() + 2);
+    {
+        McRecord zero{};
+        McEsdfRecord ezero{};
+        MsRecord szero{};
+        for (int a = 0; a < 3; a++) { zero.lo[a] = ezero.lo[a] = szero.lo[a] = 0x7FFFFFFF; zero.hi[a] = ezero.hi[a] = szero.hi[a] = -1; }
+        std::memcpy(S.h_rec.get(), &zero, sizeof(zero));
+        std::memcpy(S.h_rec.get() + 1, &ezero, sizeof(ezero));
+        std::memcpy(S.h_rec.get() + 2, &szero, sizeof(szero));
+    }
+    HIPCHK(c, hipMemcpyAsync(S.d_rec, S.h_rec.get(), 3 * sizeof(MuRecord), hipMemcpyHostToDevice, st));
+    if (n_rays > 0) {
+        HIPCHK(c, hipMemcpyAsync(S.d_in, xyz, xyz_bytes, hipMemcpyHostToDevice, st));
+        if (hit) HIPCHK(c, hipMemcpyAsync((uint8_t *)S.d_in.get() + xyz_bytes, hit, (size_t)n_rays, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(S.d_free_bits, 0, n_words * sizeof(unsigned), st));
+        HIPCHK(c, hipMemsetAsync(S.d_hit_bits, 0, n_words * sizeof(unsigned), st));
+    }
+    const unsigned ray_blocks = (unsigned)std::min<long long>((n_rays + 255) / 256, 2048);
+
+    // ---- the rays, then the frees: one hand-over
+    HIPCHK(c, hipEventRecord(S.ev_scan[0], st));
+    if (n_rays > 0) {
+        hipLaunchKernelGGL(ms_trace_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, G, O, S.d_free_bits.get(), S.d_hit_bits.get(), d_ms);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(S.ev_scan[1], st));
+    HIPCHK(c, hipEventRecord(S.ev[0], st));
+    if (n_rays > 0) {
+        hipLaunchKernelGGL(ms_apply_kernel, dim3(1024), dim3(256), 0, st, G, (const unsigned *)S.d_free_bits.get(), (const unsigned *)S.d_hit_bits.get(), c->d_counts.get(), thr,
+                           miss, c->d_occ.get(), S.d_list.get(), cap_clear, d_ms, d_mc);
+        HIPCHK(c, hipGetLastError());
+    }
+    if ((rc = hand_over(c, S, S.ev[1], 3))) return rc;
+    McRecord R;
+    MsRecord RS;
+    std::memcpy(&R, S.h_rec.get(), sizeof(R));
+    std::memcpy(&RS, S.h_rec.get() + 2, sizeof(RS));
+    info.trace_ms = mu_event_ms(S.ev_scan[0], S.ev_scan[1]);
+    info.n_rays_skipped = (long long)RS.n_skipped;
+    info.n_hits = (long long)RS.n_hits;
+    info.n_free_voxels = (long long)RS.n_free;
+    info.n_hit_voxels = (long long)RS.n_hit_voxels;
+    if (RS.hi[0] >= RS.lo[0]) for (int a = 0; a < 3; a++) { info.ray_lo[a] = RS.lo[a]; info.ray_hi[a] = RS.hi[a]; }
+    const unsigned long long n_clear_points = (unsigned long long)miss * RS.n_free;          // what isdf_clear_pointcloud would have been given
+    info.clear.n_points = (long long)n_clear_points;
+    info.clear.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
+    info.clear.n_cleared_voxels = R.n_cleared;
+    info.clear.n_points_ignored = (long long)R.ignored;
+    if (R.n_cleared > 0) {
+        // from here on the occupancy has moved: a failure must not leave products behind that describe the old map
+        const unsigned cap = (unsigned)std::min<unsigned long long>({(unsigned long long)P.clear.max_cleared_voxels, n_clear_points, n_vox, 0x7FFFFFFFull});
+        rc = mc_refresh_products(c, S, P.clear, R, cap, false, info.clear);
+        if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
+    }
+
+    // ---- the hits, on the map the clear left
+    info.update.n_points = info.n_hits;
+    const unsigned cap_update = (unsigned)std::min<unsigned long long>({(unsigned long long)P.update.max_new_voxels, RS.n_hits, n_vox, 0x7FFFFFFFull});
+    MuRecord zero{};
+    for (int a = 0; a < 3; a++) { zero.lo[a] = 0x7FFFFFFF; zero.hi[a] = -1; }
+    *S.h_rec.get() = zero;
+    {
+        hipError_t e = hipMemcpyAsync(S.d_rec, S.h_rec.get(), sizeof(MuRecord), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventRecord(S.ev[0], st);
+        if (e == hipSuccess && RS.n_hits > 0) {
+            hipLaunchKernelGGL(ms_hits_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, G, c->d_counts.get(), thr, c->d_occ.get(),
+                               (const float *)c->d_esdf.get(), S.d_list.get(), cap_update, S.d_rec.get());
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            c->err = std::string("scan hits: ") + hipGetErrorString(e);
+            mu_drop_derived(c, false);
+            return ISDF_ERR_HIP;
+        }
+    }
+    if ((rc = hand_over(c, S, S.ev[1], 1))) return rc;
+    const MuRecord RU = *S.h_rec.get();
+    info.update.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
+    info.update.n_new_voxels = RU.n_new;
+    if (RU.n_new > 0) {
+        rc = mu_refresh_products(c, S, P.update, RU, cap_update, false, info.update);
+        if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
+    }
+    if (info_out) *info_out = info;
+    return ISDF_OK;
+}
+
+}  // namespace
+
+extern "C" int isdf_integrate_scan(isdf_ctx *c, const double origin[3], const float *xyz, const uint8_t *hit, long long n_rays, const isdf_map_scan_params *params,
+                                   isdf_map_scan_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!origin || n_rays < 0 || (n_rays > 0 && !xyz)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad scan arguments");
+    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "integrating a scan in place is not offered on a multi-device ctx");
+    if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "integrating a scan needs an occupancy grid");
+    if (!c->d_counts) return isdf_fail(c, ISDF_ERR_STATE, "no kept point counts: the map did not come from isdf_set_pointcloud, or isdf_update_voxels / isdf_clear_voxels changed it since");
+    isdf_map_scan_params P;
+    isdf_map_scan_params_default(&P);
+    if (params) P = *params;
+    if (P.miss_weight < 0 || P.clear.max_cleared_voxels < 0 || !(P.clear.full_fraction >= 0.0) || P.update.max_new_voxels < 0 || !(P.update.full_fraction >= 0.0))
+        return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad scan parameters");
+    const DevGrid &G = c->grid;
+    const int dims[3] = {G.X, G.Y, G.Z};
+    MsOrigin O;
+    if (!ms_quantize(G.bmin, G.bmax, G.res, dims, origin[0], origin[1], origin[2], O.q)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the scan's origin lies outside the map");
+    return integrate_scan(c, O, xyz, hit, n_rays, P, info_out);
+}
+
+extern "C" long long isdf_scan_sets_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3], const float *xyz,
+                                         const uint8_t *hit, long long n_rays, uint8_t *free_out, uint32_t *hits_out, long long *n_skipped_out) {
+    if (ms_geometry_bad(bmin, bmax, resolution, dims) || !origin || n_rays < 0 || (n_rays > 0 && !xyz)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): bad arguments");
+    std::vector<uint8_t> free_set;
+    std::vector<uint32_t> hits;
+    MsSets S;
+    if (!ms_sets_host(bmin, bmax, resolution, dims, origin, xyz, hit, n_rays, free_set, hits, S)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): the origin lies outside the map");
+    if (free_out) std::memcpy(free_out, free_set.data(), free_set.size());
+    if (hits_out) std::memcpy(hits_out, hits.data(), hits.size() * sizeof(uint32_t));
+    if (n_skipped_out) *n_skipped_out = S.n_skipped;
+    return S.n_free;
+}
+
+extern "C" long long isdf_scan_ray_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3], const float end[3],
+                                        int32_t *ijk_out, long long capacity) {
+    if (ms_geometry_bad(bmin, bmax, resolution, dims) || !origin || !end || capacity < 0 || (capacity > 0 && !ijk_out)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): bad arguments");
+    const long long n = ms_ray_host(bmin, bmax, resolution, dims, origin, end, ijk_out, capacity);
+    return n < 0 ? isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): the origin lies outside the map") : n;
+}

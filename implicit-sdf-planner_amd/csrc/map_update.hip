@@ -217,10 +217,8 @@ int isdf::mu_frontend_box_launch(isdf_ctx *c, MapUpdateState &S, const MuBox &bo
     return ISDF_OK;
 }
 
-namespace {
-
 // everything after the hand-over of a frame that occupied at least one voxel
-int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_params &P, const MuRecord &R, unsigned cap, bool voxels, isdf_map_update_info &info) {
+int isdf::mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_params &P, const MuRecord &R, unsigned cap, bool voxels, isdf_map_update_info &info) {
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     const int dims[3] = {G.X, G.Y, G.Z};
@@ -309,6 +307,7 @@ int refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_param
     return ISDF_OK;
 }
 
+namespace {
 
 // the update proper; `in` is the host array of the points (voxels == false) or of the checked voxel indices
 int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const isdf_map_update_params *params, isdf_map_update_info *info_out) {
@@ -367,7 +366,7 @@ int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const i
         return ISDF_OK;
     }
     // from here on the occupancy has advanced: a failure must not leave products behind that describe the old map
-    rc = refresh_products(c, S, P, R, cap, voxels, info);
+    rc = mu_refresh_products(c, S, P, R, cap, voxels, info);
     if (rc != ISDF_OK) { mu_drop_derived(c, voxels); return rc; }
     if (info_out) *info_out = info;
     return ISDF_OK;

@@ -328,6 +328,44 @@ def frontend_field_reopen_host(free_mask_new, goal_index, n_att, d, lib=None):
     return out, bool(rc), info
 
 
+def _scan_geometry(bmin, bmax, dims, origin):
+    return (np.ascontiguousarray(bmin, dtype=np.float64).reshape(3), np.ascontiguousarray(bmax, dtype=np.float64).reshape(3),
+            (C.c_int32 * 3)(*[int(v) for v in dims]), np.ascontiguousarray(origin, dtype=np.float64).reshape(3))
+
+
+def scan_ray_host(bmin, bmax, res, dims, origin, end, lib=None):
+    """isdf_scan_ray_host: the voxels the ray origin -> end visits, int32 [n, 3] in the order of the walk (n = 0: the end point lies
+    outside the map).  Raises IsdfError on a negative status (the origin outside the map)."""
+    lib = lib or capi.load_library()
+    b0, b1, d, o = _scan_geometry(bmin, bmax, dims, origin)
+    e = np.ascontiguousarray(end, dtype=np.float32).reshape(3)
+    ep = e.ctypes.data_as(C.POINTER(C.c_float))
+    n = lib.isdf_scan_ray_host(_p(b0), _p(b1), float(res), d, _p(o), ep, None, 0)
+    if n < 0:
+        raise IsdfError(int(n), "isdf_scan_ray_host")
+    out = np.zeros((int(n), 3), dtype=np.int32)
+    if n > 0:
+        assert lib.isdf_scan_ray_host(_p(b0), _p(b1), float(res), d, _p(o), ep, out.ctypes.data_as(C.c_void_p), int(n)) == n
+    return out
+
+
+def scan_sets_host(bmin, bmax, res, dims, origin, xyz, hit=None, lib=None):
+    """isdf_scan_sets_host: (free uint8 [X, Y, Z] - 1 = in F -, hits uint32 [X, Y, Z] - the multiplicity in H -, rays skipped)."""
+    lib = lib or capi.load_library()
+    b0, b1, d, o = _scan_geometry(bmin, bmax, dims, origin)
+    pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    h = None if hit is None else np.ascontiguousarray(hit, dtype=np.uint8).reshape(pts.shape[0])
+    shape = tuple(int(v) for v in dims)
+    free, hits = np.zeros(shape, dtype=np.uint8), np.zeros(shape, dtype=np.uint32)
+    skipped = C.c_longlong(0)
+    n = lib.isdf_scan_sets_host(_p(b0), _p(b1), float(res), d, _p(o), pts.ctypes.data_as(C.POINTER(C.c_float)), None if h is None else h.ctypes.data_as(C.c_void_p),
+                                pts.shape[0], free.ctypes.data_as(C.c_void_p), hits.ctypes.data_as(C.c_void_p), C.byref(skipped))
+    if n < 0:
+        raise IsdfError(int(n), "isdf_scan_sets_host")
+    assert n == int(free.sum())
+    return free, hits, int(skipped.value)
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -529,6 +567,27 @@ class Engine:
         p = self._map_clear_params(**params)
         info = capi.IsdfMapClearInfo()
         self._check(self.lib.isdf_clear_voxels(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.shape[0], C.byref(p), C.byref(info)))
+        self._watch_refresh_rows()
+        return info
+
+    # ---- a range scan integrated into the map (csrc/map_scan.hip)
+    def integrate_scan(self, origin, xyz, hit=None, miss_weight=None, max_cleared_voxels=None, max_new_voxels=None, full_fraction=None, refresh_esdf=True,
+                       refresh_frontend=True):
+        """isdf_integrate_scan: the rays from `origin` to the end points xyz (n x 3 float32) traced on the device; the counts go down by
+        miss_weight once in every voxel a ray passes and up by one at the end voxel of every ray with hit != 0 (hit None: all).  The
+        other params go to the clear stage (max_cleared_voxels), the update stage (max_new_voxels) or both.  Returns IsdfMapScanInfo."""
+        pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        h = None if hit is None else np.ascontiguousarray(hit, dtype=np.uint8).reshape(pts.shape[0])
+        p = capi.IsdfMapScanParams()
+        self.lib.isdf_map_scan_params_default(C.byref(p))
+        if miss_weight is not None:
+            p.miss_weight = int(miss_weight)
+        p.clear = self._map_clear_params(max_cleared_voxels=max_cleared_voxels, full_fraction=full_fraction, refresh_esdf=refresh_esdf, refresh_frontend=refresh_frontend)
+        p.update = self._map_update_params(max_new_voxels=max_new_voxels, full_fraction=full_fraction, refresh_esdf=refresh_esdf, refresh_frontend=refresh_frontend)
+        info = capi.IsdfMapScanInfo()
+        self._check(self.lib.isdf_integrate_scan(self.h, _p(o), pts.ctypes.data_as(C.POINTER(C.c_float)), None if h is None else h.ctypes.data_as(C.c_void_p),
+                                                 pts.shape[0], C.byref(p), C.byref(info)))
         self._watch_refresh_rows()
         return info
 

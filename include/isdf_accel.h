@@ -1374,6 +1374,61 @@ int isdf_clear_esdf_host(const uint8_t *occ_new, float *esdf_inout, const int32_
 long long isdf_clear_touched_host(const float *esdf_old, const int32_t dims[3], double resolution, const int32_t *cleared_ijk, long long n_cleared,
                                   uint8_t *touched_out);
 
+/* ---- a range scan integrated into the map: free space ray-cast on the device ----------------------------------- */
+/* The producer of the two sections above: WHICH voxels to clear is what a range scan says - a ray that passes through a voxel proves
+ * it empty.  isdf_integrate_scan takes the sensor's origin (3 doubles), the scan's end points (xyz = n_rays x 3 floats) and hit
+ * (nullable, n_rays bytes: NULL = every ray ends on a surface, 0 = this ray ends in free space, e.g. a max-range reading the caller has
+ * cut to length), traces the rays on the device and takes the kept per-voxel counts down along the rays and up at the hits.
+ * The ray is defined in integers, so that the device and isdf_scan_ray_host visit the same voxels bit for bit.  A point is inside by
+ * the binning's own test (no coordinate < the lower or > the upper boundary) and when it is finite; u = (p - bmin) / resolution in
+ * fp64, q = floor(u * 1024) clamped to dim * 1024 - 1, voxel q >> 10 (the binning's voxel).  The ray runs between the tick centres
+ * P = 2 q + 1; on axis a it takes |ve_a - vo_a| steps; the next step is on the axis, among those with steps left, whose next voxel
+ * boundary comes first - m_a / D_a smallest, m_a = 2048 (v_a + 1) - Po_a or Po_a - 2048 v_a by direction, D_a = |Pe_a - Po_a|, compared
+ * as m_a D_b < m_b D_a in 64-bit integers, a tie to the lowest axis.  The visited voxels are vo and every voxel entered: 1 + the sum
+ * of the steps, the last one ve.
+ * A ray whose end point is outside the map is skipped whole (n_rays_skipped; it does NOT count for voxel (0,0,0): a ray is no map
+ * point); an origin outside: ISDF_ERR_INVALID_ARG, nothing changed.  H = the multiset of the end voxels of the hit rays.  F = the SET
+ * of voxels visited by any ray - a hit ray's end voxel left out, a no-hit ray's included - minus every voxel of H: a voxel hit in this
+ * scan is never counted down by it.  counts'[v] = max(counts[v] - miss_weight, 0) on F, counts[v] + multiplicity on H; occupancy is
+ * counts' >= sta_threshold.  F is a set per scan, not a sum per ray: the voxel next to the sensor that every ray crosses loses
+ * miss_weight once, and the result depends neither on the order of the rays nor on the order of the device's atomics.
+ * The call IS this sequence, and every product - counts, occupancy, ESDF, inflated bit map, configuration-space table, the A*'s host
+ * copy, the cost-to-go field in every repair / reopen mode, a kept clearance report - is byte for byte what a second ctx holds after
+ * it: isdf_clear_pointcloud of miss_weight copies of the centre of every voxel of F (params.clear), then isdf_update_pointcloud of
+ * the end points of the hit rays that were not skipped (params.update).  The frees are applied and refreshed first, then the hits;
+ * info.clear and info.update are what those two calls report (the *_ms apart).  A failure after counts or occupancy moved drops the
+ * ESDF and the front end, as those calls do.  Nothing is allocated after the first call of a size beyond what the two stages allocate.
+ * ISDF_ERR_STATE without kept counts; a multi-device ctx ISDF_ERR_UNSUPPORTED; n_rays = 0 is legal (path 0 twice).  params may be
+ * NULL (defaults), info_out may be NULL.  Not offered: a voxel form for maps from isdf_set_grid; one merged refresh of both directions. */
+typedef struct isdf_map_scan_params {
+    int32_t miss_weight;        /* taken off the count of every voxel of F, default 1; < 0: ISDF_ERR_INVALID_ARG; 0: only the hits count */
+    int32_t reserved;
+    isdf_map_clear_params clear;    /* handed to the clear stage  */
+    isdf_map_update_params update;  /* handed to the update stage */
+} isdf_map_scan_params;
+typedef struct isdf_map_scan_info {
+    int64_t n_rays, n_rays_skipped, n_hits;     /* given; end point outside the map; hit rays that were not skipped */
+    int64_t n_free_voxels, n_hit_voxels;        /* |F|; distinct voxels of H                                        */
+    int32_t ray_lo[3], ray_hi[3];               /* index box of every visited voxel (lo > hi: no ray traced)        */
+    double trace_ms;                            /* device time of the ray stage, events on the ctx's stream         */
+    isdf_map_clear_info clear;                  /* as isdf_clear_pointcloud of the two-call sequence reports        */
+    isdf_map_update_info update;                /* as isdf_update_pointcloud of it reports                          */
+} isdf_map_scan_info;
+void isdf_map_scan_params_default(isdf_map_scan_params *p);     /* null-safe */
+void isdf_map_scan_sizes(int sizes_out[2]);                     /* null-safe; sizeof of the two structs above */
+int isdf_integrate_scan(isdf_ctx *ctx, const double origin[3], const float *xyz, const uint8_t *hit, long long n_rays,
+                        const isdf_map_scan_params *params, isdf_map_scan_info *info_out);
+/* plain host code, no ctx, no device: the sets of one scan.  bmin / bmax / resolution / dims: the map's geometry (each dim in
+ * [1, 4096]).  free_out (nullable): one byte per voxel, 1 = in F; hits_out (nullable): uint32 per voxel, the multiplicity in H;
+ * n_skipped_out (nullable).  Returns |F| or a negative isdf_status (ISDF_ERR_INVALID_ARG: a null array, a bad geometry, an origin
+ * outside the map). */
+long long isdf_scan_sets_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3],
+                              const float *xyz, const uint8_t *hit, long long n_rays, uint8_t *free_out, uint32_t *hits_out, long long *n_skipped_out);
+/* one ray's visited voxels, for tests and callers who want the list: ijk_out = capacity x 3; returns their number (also when it
+ * exceeds capacity), 0 when the end point lies outside the map or is not finite, or a negative isdf_status */
+long long isdf_scan_ray_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3],
+                             const float end[3], int32_t *ijk_out, long long capacity);
+
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
  * the shipped src/plan_manager/map_pcds are "FIELDS x y z / DATA ascii"): xyz_out = up to `capacity` points x 3 floats (may be
