@@ -141,6 +141,22 @@ class IsdfMapClearInfo(C.Structure):
                 ("count_ms", C.c_double), ("esdf_ms", C.c_double), ("frontend_ms", C.c_double)]
 
 
+MAP_SHIFT_NONE, MAP_SHIFT_INCREMENTAL, MAP_SHIFT_FULL = 0, 1, 2         # isdf_map_shift_info.path
+
+
+class IsdfMapShiftParams(C.Structure):
+    """isdf_map_shift_params (include/isdf_accel.h)."""
+    _fields_ = [("full_fraction", C.c_double), ("force_path", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class IsdfMapShiftInfo(C.Structure):
+    """isdf_map_shift_info (include/isdf_accel.h)."""
+    _fields_ = [("path", C.c_int32), ("shift", C.c_int32 * 3), ("bmin_new", C.c_double * 3), ("voxels_entered", C.c_int64), ("occupied_left", C.c_int64),
+                ("counts_left", C.c_int64), ("n_boxes", C.c_int32), ("host_table_patched", C.c_int32), ("field_dropped", C.c_int32),
+                ("watch_rechecked", C.c_int32), ("cspace_voxels", C.c_int64), ("translate_ms", C.c_double), ("esdf_ms", C.c_double),
+                ("frontend_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 class IsdfMapScanParams(C.Structure):
     """isdf_map_scan_params (include/isdf_accel.h)."""
     _fields_ = [("miss_weight", C.c_int32), ("reserved", C.c_int32), ("clear", IsdfMapClearParams), ("update", IsdfMapUpdateParams)]
@@ -315,6 +331,8 @@ EXPORTED_SYMBOLS = [
     "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
     "isdf_map_clear_params_default", "isdf_map_clear_sizes", "isdf_clear_pointcloud", "isdf_clear_voxels", "isdf_clear_esdf_host", "isdf_clear_touched_host",
     "isdf_map_scan_params_default", "isdf_map_scan_sizes", "isdf_integrate_scan", "isdf_scan_sets_host", "isdf_scan_ray_host",
+    "isdf_map_shift_params_default", "isdf_map_shift_sizes", "isdf_shift_map", "isdf_map_follow", "isdf_shift_geometry_host", "isdf_shift_grid_host",
+    "isdf_shift_bands_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -577,6 +595,20 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfMapScanParams), C.sizeof(IsdfMapScanInfo)]:
         raise RuntimeError(f"isdf_map_scan structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfMapScanParams), C.sizeof(IsdfMapScanInfo)]}")
+    hp, hi, i3 = C.POINTER(IsdfMapShiftParams), C.POINTER(IsdfMapShiftInfo), C.POINTER(C.c_int32)
+    lib.isdf_map_shift_params_default.argtypes = [hp]
+    lib.isdf_map_shift_params_default.restype = None
+    lib.isdf_map_shift_sizes.argtypes = [ip]
+    lib.isdf_map_shift_sizes.restype = None
+    lib.isdf_shift_map.argtypes = [C.c_void_p, i3, hp, hi]
+    lib.isdf_map_follow.argtypes = [C.c_void_p, dp, C.c_int, hp, i3, hi]
+    lib.isdf_shift_geometry_host.argtypes = [dp, dp, C.c_double, i3, i3, dp, dp]
+    lib.isdf_shift_grid_host.argtypes = [C.c_void_p, C.c_int, i3, i3, C.c_void_p]
+    lib.isdf_shift_bands_host.argtypes = [i3, i3, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    lib.isdf_map_shift_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfMapShiftParams), C.sizeof(IsdfMapShiftInfo)]:
+        raise RuntimeError(f"isdf_map_shift structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfMapShiftParams), C.sizeof(IsdfMapShiftInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

@@ -357,12 +357,17 @@ extern "C" int isdf_frontend_cspace_get(isdf_ctx *c, int which, uint32_t *out) {
     return ISDF_OK;
 }
 
-int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms) {
-    if (cspace_ms) *cspace_ms = 0.0;
-    if (!c->fe.built) return ISDF_OK;
+int isdf_frontend_map_bits(isdf_ctx *c) {
     const FeParams F = fe_params(c);
     hipLaunchKernelGGL(fe_map_bits_kernel, dim3(2048), dim3(256), 0, c->stream, F, c->d_occ, c->fe.d_bits);
     HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+
+int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms) {
+    if (cspace_ms) *cspace_ms = 0.0;
+    if (!c->fe.built) return ISDF_OK;
+    { const int rc = isdf_frontend_map_bits(c); if (rc) return rc; }
     c->fe.h_cspace_valid = false;
     if (c->fe.d_cspace) return isdf_frontend_cspace(c, nullptr, cspace_ms);
     return ISDF_OK;

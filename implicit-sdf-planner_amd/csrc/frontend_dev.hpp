@@ -75,6 +75,8 @@ __device__ __forceinline__ void fe_cspace_voxel(const FeParams &F, const uint8_t
 // frontend.hip, for the map update's full path: the whole inflated map again from the ctx's occupancy, the whole configuration space
 // again if there was one (device time of that pass in *cspace_ms), the host copy of the table marked stale
 int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms);
+// its first step alone, for the map shift's incremental path: the whole inflated map again on the ctx's stream (a built front end)
+int isdf_frontend_map_bits(isdf_ctx *c);
 
 // frontend_field.hip, for the map update: the cost-to-go field repaired after voxels closed (isdf_frontend_field_set_repair, mode 1).
 // ..._wanted: mode 1 and a valid field that is a fixed point (not status 2).  ..._begin enqueues the mark over the box lo .. hi

@@ -185,7 +185,8 @@ int isdf::mu_state(isdf_ctx *c, MapUpdateState **out) {
     return ISDF_OK;
 }
 
-int isdf::mu_frontend_box_launch(isdf_ctx *c, MapUpdateState &S, const MuBox &box, const MuBox &grown, bool *patch, size_t *pack_words, long long *cspace_voxels) {
+int isdf::mu_frontend_box_launch(isdf_ctx *c, MapUpdateState &S, const MuBox &box, const MuBox &grown, bool *patch, size_t *pack_words, long long *cspace_voxels,
+                                 size_t pack_offset) {
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     isdf_ctx::FrontEnd &fe = c->fe;
@@ -207,11 +208,11 @@ int isdf::mu_frontend_box_launch(isdf_ctx *c, MapUpdateState &S, const MuBox &bo
     *cspace_voxels = mu_box_voxels(grown);
     if (!fe.h_cspace_valid) return ISDF_OK;
     *pack_words = (size_t)mu_box_voxels(grown) * nw;
-    if ((rc = S.d_pack.reserve(c, *pack_words / 4))) return rc;
-    if ((rc = S.h_pack.reserve(c, *pack_words))) return rc;
+    if ((rc = S.d_pack.reserve(c, (pack_offset + *pack_words) / 4))) return rc;
+    if ((rc = S.h_pack.reserve(c, pack_offset + *pack_words))) return rc;
     const long long np = (long long)(*pack_words / 4);
     hipLaunchKernelGGL(mu_pack_box_kernel, dim3((unsigned)std::min<long long>((np + 255) / 256, 2048)), dim3(256), 0, st, (const uint4 *)fe.d_cspace.get(),
-                       S.d_pack.get(), G.Y, G.Z, (int)(nw / 4), grown);
+                       S.d_pack.get() + pack_offset / 4, G.Y, G.Z, (int)(nw / 4), grown);
     HIPCHK(c, hipGetLastError());
     *patch = true;
     return ISDF_OK;

@@ -29,7 +29,14 @@ struct McEsdfRecord {
     unsigned long long touched, raised;
     unsigned pad[4];
 };
-static_assert(sizeof(McRecord) == 64 && sizeof(McEsdfRecord) == 64 && sizeof(MuRecord) == 64, "each hand-over record is one 64-byte line");
+// the shift's translation stage (map_shift.hip): 64 bytes, zeroed before every shift
+struct MshRecord {
+    unsigned long long counts_left;     // sum of the kept counts of the voxels without a destination
+    unsigned long long occupied_left;   // occupied voxels among them
+    unsigned any_occ;                   // some voxel of the new window is occupied
+    unsigned pad[11];
+};
+static_assert(sizeof(McRecord) == 64 && sizeof(McEsdfRecord) == 64 && sizeof(MuRecord) == 64 && sizeof(MshRecord) == 64, "each hand-over record is one 64-byte line");
 
 }  // namespace isdf
 
@@ -40,6 +47,9 @@ struct MapUpdateState {
     isdf::DevBuf<uint4> d_pack; isdf::PinBuf<uint32_t> h_pack;          // the grown box of the configuration space on its way to the host table
     isdf::DevBuf<int> d_edt_a, d_edt_b;       // map_clear.hip: the slabs of the separable transform over the touched box
     isdf::DevBuf<unsigned> d_free_bits, d_hit_bits;     // map_scan.hip: one bit per voxel, the voxels a scan's rays pass / end in
+    // map_shift.hip: where the translation writes; each then changes places with the ctx's own buffer (one more copy of the counts, the
+    // occupancy and the configuration-space table stays allocated)
+    isdf::DevBuf<unsigned> d_shift_counts, d_shift_cspace; isdf::DevBuf<uint8_t> d_shift_occ;
     hipEvent_t ev_scan[2] = {nullptr, nullptr};          // map_scan.hip: around the ray stage
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};          // [6], [7]: around the field's repair (update) or reopen (clear)
     ~MapUpdateState() {
@@ -59,8 +69,10 @@ void mu_drop_derived(isdf_ctx *c, bool voxels);
 // The front end over the box of the changed voxels, on the ctx's stream: the dwords of the inflated bit map that cover `box`, the
 // configuration-space words of `grown` if there is a table (*cspace_voxels) and, when the A* holds the table on the host, that box
 // packed into S.d_pack (*patch, *pack_words: the caller copies it to S.h_pack and scatters it after its synchronisation).  The
-// kernels recompute from the occupancy: the direction of the change does not show.
-int mu_frontend_box_launch(isdf_ctx *c, MapUpdateState &S, const MuBox &box, const MuBox &grown, bool *patch, size_t *pack_words, long long *cspace_voxels);
+// kernels recompute from the occupancy: the direction of the change does not show.  pack_offset (dwords): where in S.d_pack the box
+// goes - a caller with several boxes (map_shift.hip) reserves S.d_pack and S.h_pack for all of them first, so that nothing grows here.
+int mu_frontend_box_launch(isdf_ctx *c, MapUpdateState &S, const MuBox &box, const MuBox &grown, bool *patch, size_t *pack_words, long long *cspace_voxels,
+                           size_t pack_offset = 0);
 // Everything after the hand-over of a call that occupied (mu_, map_update.hip) or freed (mc_, map_clear.hip) at least one voxel: R is
 // the count stage's record as the host read it, S.d_list the new (cleared) voxels, cap the list's capacity; the counts and the occupancy
 // are the new map's already.  map_scan.hip runs both, the clear's first.  A failure: the caller calls mu_drop_derived.

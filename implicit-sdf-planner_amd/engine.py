@@ -397,6 +397,47 @@ def traj_check_fold_host(a, rows_a, vox_a, b, rows_b, vox_b, lib=None):
     return Engine._traj_check_report(out, pm), rows, vox
 
 
+def _i3(v):
+    return (C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def shift_geometry_host(bmin, bmax, res, dims, shift, lib=None):
+    """isdf_shift_geometry_host: (bmin', bmax') of the window shifted by `shift` voxels.  Raises IsdfError (ISDF_ERR_INVALID_ARG) when
+    isdf_set_pointcloud's ceil((bmax' - bmin') / res) would not give dims again."""
+    lib = lib or capi.load_library()
+    b0, b1 = np.ascontiguousarray(bmin, dtype=np.float64).reshape(3), np.ascontiguousarray(bmax, dtype=np.float64).reshape(3)
+    o0, o1 = np.zeros(3), np.zeros(3)
+    rc = lib.isdf_shift_geometry_host(_p(b0), _p(b1), float(res), _i3(dims), _i3(shift), _p(o0), _p(o1))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, "isdf_shift_geometry_host")
+    return o0, o1
+
+
+def shift_grid_host(grid, shift, lib=None):
+    """isdf_shift_grid_host: out[v] = grid[v + shift], zero where v + shift lies outside.  grid: [X, Y, Z] or [X, Y, Z, m] (one element =
+    the m values of a voxel), any dtype."""
+    lib = lib or capi.load_library()
+    g = np.ascontiguousarray(grid)
+    assert g.ndim in (3, 4)
+    elem = g.itemsize * (g.shape[3] if g.ndim == 4 else 1)
+    out = np.empty_like(g)
+    rc = lib.isdf_shift_grid_host(g.ctypes.data_as(C.c_void_p), elem, _i3(g.shape[:3]), _i3(shift), out.ctypes.data_as(C.c_void_p))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, "isdf_shift_grid_host")
+    return out
+
+
+def shift_bands_host(dims, shift, side, lib=None):
+    """isdf_shift_bands_host: the bands of the configuration space a shift recomputes, int32 [n, 2, 3] = (lo, hi) inclusive, n <= 6."""
+    lib = lib or capi.load_library()
+    boxes = np.zeros((6, 6), dtype=np.int32)
+    n = C.c_int(0)
+    rc = lib.isdf_shift_bands_host(_i3(dims), _i3(shift), int(side), boxes.ctypes.data_as(C.c_void_p), C.byref(n))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(rc, "isdf_shift_bands_host")
+    return boxes[:n.value].reshape(-1, 2, 3).copy()
+
+
 class Engine:
     def __init__(self, cfg, lib=None, devices=None):
         """devices: None = one device (cfg.device); a list = ONE ctx over those devices (isdf_create_multi), used like any other."""
@@ -590,6 +631,36 @@ class Engine:
                                                  pts.shape[0], C.byref(p), C.byref(info)))
         self._watch_refresh_rows()
         return info
+
+    # ---- the map window shifted in place (csrc/map_shift.hip)
+    def _map_shift_params(self, full_fraction=None, force_path=None):
+        p = capi.IsdfMapShiftParams()
+        self.lib.isdf_map_shift_params_default(C.byref(p))
+        if full_fraction is not None:
+            p.full_fraction = float(full_fraction)
+        if force_path is not None:
+            p.force_path = int(force_path)
+        return p
+
+    def shift_map(self, shift, **params):
+        """isdf_shift_map: the window moves by `shift` voxels (new voxel v holds what old voxel v + shift held); every built product is
+        the shifted map's afterwards.  params: full_fraction, force_path.  Returns IsdfMapShiftInfo."""
+        p = self._map_shift_params(**params)
+        info = capi.IsdfMapShiftInfo()
+        self._check(self.lib.isdf_shift_map(self.h, _i3(shift), C.byref(p), C.byref(info)))
+        self._watch_refresh_rows()
+        return info
+
+    def map_follow(self, centre, min_shift=1, **params):
+        """isdf_map_follow: shifts the window so that `centre` (world) falls into its middle voxel, unless that takes fewer than
+        min_shift voxels on every axis.  Returns (shift applied as a tuple, IsdfMapShiftInfo)."""
+        ctr = np.ascontiguousarray(centre, dtype=np.float64).reshape(3)
+        p = self._map_shift_params(**params)
+        info = capi.IsdfMapShiftInfo()
+        s = (C.c_int32 * 3)()
+        self._check(self.lib.isdf_map_follow(self.h, _p(ctr), int(min_shift), C.byref(p), s, C.byref(info)))
+        self._watch_refresh_rows()
+        return tuple(s), info
 
     def map_counts(self):
         """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""

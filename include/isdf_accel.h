@@ -1429,6 +1429,70 @@ long long isdf_scan_sets_host(const double bmin[3], const double bmax[3], double
 long long isdf_scan_ray_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3],
                              const float end[3], int32_t *ijk_out, long long capacity);
 
+/* ---- the map window shifted in place, so that the map can follow the robot -------------------------------------- */
+/* Every call above keeps the box (bmin, bmax, dims) that isdf_set_pointcloud fixed.  isdf_shift_map moves the window by
+ * s = shift_ijk voxels: new voxel v holds what old voxel v + s held, a voxel whose source lies outside the old grid has count 0, and
+ * bmin' = bmin + s * resolution, bmax' = bmax + s * resolution per axis (one fp64 product, one sum, nothing contracted).  If
+ * isdf_set_pointcloud's own ceil((bmax' - bmin') / resolution) does not give the same dims on every axis the call fails with
+ * ISDF_ERR_INVALID_ARG and changes nothing (isdf_shift_geometry_host is this rule).
+ * After the call every product that had been built - kept counts, occupancy, ESDF, inflated bit map, configuration-space table on
+ * the device and in the A*'s host copy - is byte for byte what a fresh ctx holds after isdf_set_pointcloud on a cloud with the
+ * translated counts in the box (bmin', bmax') followed by whichever of isdf_generate_esdf, isdf_frontend_build and
+ * isdf_frontend_cspace had been run.  Counts, occupancy and the table are translated into second buffers that then change places with
+ * the first (one more copy of each stays allocated); the ESDF is transformed whole; of the table only the bands a translation cannot
+ * supply are recomputed (isdf_shift_bands_host) - path 1 - unless their volume exceeds full_fraction of the map, no voxel is
+ * occupied any more, or |s| >= dims on some axis (everything left: the empty map) - path 2, the whole-map kernels, the host copy
+ * marked stale.  s = 0: path 0, nothing is touched.
+ * Voxel indices change their meaning: the grid epoch advances (a report of isdf_traj_check from before the shift is stale for
+ * isdf_points_merge_check), a valid cost-to-go field is dropped (field_dropped), an armed clearance watch (isdf_traj_check_set_watch)
+ * is checked again against the new map and stays armed (watch_rechecked).  The obstacle-point set, lastTstar and a kept swept mesh
+ * are world-space and stay.  A failure after the counts moved drops the ESDF and the front end, as a failing update does.
+ * ISDF_ERR_UNSUPPORTED on a multi-device ctx, ISDF_ERR_STATE without a map or without kept counts (a map from isdf_set_grid).
+ * Nothing is allocated after the first call of a size beyond what isdf_generate_esdf and the watch's re-check allocate.
+ * params may be NULL (defaults), info_out may be NULL.  Not offered: an incremental ESDF, a translated cost-to-go field. */
+#define ISDF_MAP_SHIFT_NONE 0
+#define ISDF_MAP_SHIFT_INCREMENTAL 1
+#define ISDF_MAP_SHIFT_FULL 2
+typedef struct isdf_map_shift_params {
+    double full_fraction;       /* bands above this share of the map: path 2; default 0.5; < 0 or NaN: ISDF_ERR_INVALID_ARG     */
+    int32_t force_path;         /* 0: as decided; 1: path 1 unless everything left; 2: path 2; else ISDF_ERR_INVALID_ARG        */
+    int32_t reserved[5];
+} isdf_map_shift_params;
+typedef struct isdf_map_shift_info {
+    int32_t path;               /* ISDF_MAP_SHIFT_*                                                                              */
+    int32_t shift[3];           /* the shift applied                                                                             */
+    double bmin_new[3];         /* the map's origin after the call                                                               */
+    int64_t voxels_entered;     /* voxels of the new window without a source                                                     */
+    int64_t occupied_left;      /* occupied voxels of the old window without a destination                                       */
+    int64_t counts_left;        /* the sum of their and every other leaving voxel's kept counts                                  */
+    int32_t n_boxes;            /* bands of the configuration space recomputed (path 1 with a table; else 0)                      */
+    int32_t host_table_patched; /* the A*'s host copy was translated and patched in place                                        */
+    int32_t field_dropped, watch_rechecked;
+    int64_t cspace_voxels;      /* configuration-space words recomputed (the bands' volumes; the map on path 2)                  */
+    double translate_ms, esdf_ms, frontend_ms;      /* device time, events on the ctx's stream                                    */
+    double wall_ms;             /* the whole call on the host's clock                                                            */
+} isdf_map_shift_info;
+void isdf_map_shift_params_default(isdf_map_shift_params *p);    /* null-safe */
+void isdf_map_shift_sizes(int sizes_out[2]);                     /* null-safe; sizeof of the two structs above */
+int isdf_shift_map(isdf_ctx *ctx, const int32_t shift_ijk[3], const isdf_map_shift_params *params, isdf_map_shift_info *info_out);
+/* Host arithmetic around isdf_shift_map: s_a = the voxel of centre_xyz (the binning's floor((x - bmin) / resolution), not clamped:
+ * a centre outside the map is fine) minus dims_a / 2.  max |s_a| < min_shift: nothing happens, shift_out = 0, path 0.  Otherwise
+ * isdf_shift_map(s); shift_out (nullable) = s on success, 0 on failure.  A non-finite centre, a negative min_shift or a voxel index
+ * beyond int32: ISDF_ERR_INVALID_ARG. */
+int isdf_map_follow(isdf_ctx *ctx, const double centre_xyz[3], int min_shift, const isdf_map_shift_params *params, int32_t shift_out[3],
+                    isdf_map_shift_info *info_out);
+/* plain host code, no ctx, no device.  The shifted box and the dims guard: ISDF_OK and the new box, or ISDF_ERR_INVALID_ARG (a null
+ * array, resolution <= 0, a dim outside [1, 4096], or the guard; the outputs are then unspecified). */
+int isdf_shift_geometry_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const int32_t shift[3],
+                             double bmin_out[3], double bmax_out[3]);
+/* out[v] = in[v + shift] where v + shift lies in the grid, zero elsewhere: elements of elem_bytes bytes, z fastest.  in == out is
+ * allowed (this is how the A*'s host table is shifted); the arrays must not overlap otherwise. */
+int isdf_shift_grid_host(const void *in, int elem_bytes, const int32_t dims[3], const int32_t shift[3], void *out);
+/* The bands of the configuration space a shift recomputes, side = (kernel_size - 1) / 2 >= 0: per shifted axis the entering slab
+ * grown by side and the side-thick band at the opposite face, over the whole extent of the other axes, clamped, empty ones left out:
+ * boxes_out[i] = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z}, inclusive, *n_boxes_out <= 6.  The boxes may overlap. */
+int isdf_shift_bands_host(const int32_t dims[3], const int32_t shift[3], int side, int32_t boxes_out[6][6], int *n_boxes_out);
+
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
  * the shipped src/plan_manager/map_pcds are "FIELDS x y z / DATA ascii"): xyz_out = up to `capacity` points x 3 floats (may be
