@@ -169,6 +169,21 @@ class IsdfMapScanInfo(C.Structure):
                 ("clear", IsdfMapClearInfo), ("update", IsdfMapUpdateInfo)]
 
 
+class IsdfMapRaycastParams(C.Structure):
+    """isdf_map_raycast_params (include/isdf_accel.h)."""
+    _fields_ = [("test_origin_voxel", C.c_int32), ("per_ray_origin", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class IsdfMapRaycastInfo(C.Structure):
+    """isdf_map_raycast_info (include/isdf_accel.h)."""
+    _fields_ = [("n_rays", C.c_int64), ("n_skipped", C.c_int64), ("n_origin_outside", C.c_int64), ("n_hits", C.c_int64), ("n_clear", C.c_int64),
+                ("steps_total", C.c_int64), ("cast_ms", C.c_double)]
+
+
+RAYCAST_CLEAR, RAYCAST_HIT, RAYCAST_END_OUTSIDE, RAYCAST_ORIGIN_OUTSIDE = 0, 1, 2, 3       # a row's status
+RAYCAST_ROW = 8                                                                           # int32 per ray: status, steps, i, j, k, axis, num, den
+
+
 class IsdfPlanConfig(C.Structure):
     """isdf_plan_config: what a plan needs from the reference's yaml files (include/isdf_accel.h)."""
     _fields_ = [("sweep", IsdfConfig), ("frontend", IsdfFrontendConfig), ("occupancy_resolution", C.c_double),
@@ -331,6 +346,7 @@ EXPORTED_SYMBOLS = [
     "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
     "isdf_map_clear_params_default", "isdf_map_clear_sizes", "isdf_clear_pointcloud", "isdf_clear_voxels", "isdf_clear_esdf_host", "isdf_clear_touched_host",
     "isdf_map_scan_params_default", "isdf_map_scan_sizes", "isdf_integrate_scan", "isdf_scan_sets_host", "isdf_scan_ray_host",
+    "isdf_map_raycast_params_default", "isdf_map_raycast_sizes", "isdf_map_raycast", "isdf_map_raycast_device", "isdf_raycast_host",
     "isdf_map_shift_params_default", "isdf_map_shift_sizes", "isdf_shift_map", "isdf_map_follow", "isdf_shift_geometry_host", "isdf_shift_grid_host",
     "isdf_shift_bands_host",
 ]
@@ -595,6 +611,19 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfMapScanParams), C.sizeof(IsdfMapScanInfo)]:
         raise RuntimeError(f"isdf_map_scan structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfMapScanParams), C.sizeof(IsdfMapScanInfo)]}")
+    rp, ri = C.POINTER(IsdfMapRaycastParams), C.POINTER(IsdfMapRaycastInfo)
+    lib.isdf_map_raycast_params_default.argtypes = [rp]
+    lib.isdf_map_raycast_params_default.restype = None
+    lib.isdf_map_raycast_sizes.argtypes = [ip]
+    lib.isdf_map_raycast_sizes.restype = None
+    lib.isdf_map_raycast.argtypes = [C.c_void_p, dp, C.POINTER(C.c_float), C.c_longlong, rp, C.c_void_p, ri]
+    lib.isdf_map_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, rp, C.c_void_p, ri, C.c_void_p]
+    lib.isdf_raycast_host.argtypes = [C.c_void_p, dp, dp, C.c_double, C.POINTER(C.c_int32), dp, C.POINTER(C.c_float), C.c_longlong, rp, C.c_void_p]
+    lib.isdf_raycast_host.restype = C.c_longlong
+    lib.isdf_map_raycast_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfMapRaycastParams), C.sizeof(IsdfMapRaycastInfo)]:
+        raise RuntimeError(f"isdf_map_raycast structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfMapRaycastParams), C.sizeof(IsdfMapRaycastInfo)]}")
     hp, hi, i3 = C.POINTER(IsdfMapShiftParams), C.POINTER(IsdfMapShiftInfo), C.POINTER(C.c_int32)
     lib.isdf_map_shift_params_default.argtypes = [hp]
     lib.isdf_map_shift_params_default.restype = None

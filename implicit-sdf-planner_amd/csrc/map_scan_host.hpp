@@ -55,15 +55,19 @@ MU_HD void ms_ray_begin(const int qo[3], const int qe[3], MsRay &r) {
 
 MU_HD bool ms_ray_done(const MsRay &r) { return (r.n[0] | r.n[1] | r.n[2]) == 0; }
 
-// one step: r.v becomes the voxel entered.  Only call while !ms_ray_done(r).
-MU_HD void ms_ray_step(MsRay &r) {
+// one step: r.v becomes the voxel entered.  Only call while !ms_ray_done(r).  Returns the axis a of the step; the boundary crossed
+// lies at the fraction (r.m[a] - 2048) / r.D[a] of the segment between the two tick centres (r.m[a] as it is after the call).
+MU_HD int ms_ray_step_axis(MsRay &r) {
     int best = r.n[0] > 0 ? 0 : (r.n[1] > 0 ? 1 : 2);
     for (int b = best + 1; b < 3; b++)
         if (r.n[b] > 0 && (unsigned long long)r.m[b] * r.D[best] < (unsigned long long)r.m[best] * r.D[b]) best = b;
     r.v[best] += r.s[best];
     r.n[best] -= 1;
     r.m[best] += 2048u;
+    return best;
 }
+
+MU_HD void ms_ray_step(MsRay &r) { (void)ms_ray_step_axis(r); }
 
 // ---- host forms
 inline bool ms_geometry_bad(const double bmin[3], const double bmax[3], double res, const int32_t dims[3]) {

@@ -366,6 +366,120 @@ def scan_sets_host(bmin, bmax, res, dims, origin, xyz, hit=None, lib=None):
     return free, hits, int(skipped.value)
 
 
+def _raycast_params(lib, test_origin_voxel, per_ray_origin):
+    p = capi.IsdfMapRaycastParams()
+    lib.isdf_map_raycast_params_default(C.byref(p))
+    p.test_origin_voxel = int(bool(test_origin_voxel)); p.per_ray_origin = int(bool(per_ray_origin))
+    return p
+
+
+def _raycast_origins(origins, n, per_ray_origin):
+    o = np.ascontiguousarray(origins, dtype=np.float64)
+    per_ray = (o.ndim == 2) if per_ray_origin is None else bool(per_ray_origin)
+    return o.reshape((n, 3) if per_ray else (3,)), per_ray
+
+
+def raycast_host(occ, bmin, bmax, res, origins, ends, test_origin_voxel=False, per_ray_origin=None, lib=None):
+    """isdf_raycast_host: the rays origins -> ends (ends n x 3 float32; origins 3 doubles for all rays, or n x 3 - per_ray_origin None:
+    by the array's rank) cast through the occupancy bytes occ [X, Y, Z] in plain host code.  Returns (rows int32 [n, 8] =
+    (status, steps, i, j, k, axis, num, den) per ray, the number of hits).  Raises IsdfError on a negative status (a shared origin outside)."""
+    lib = lib or capi.load_library()
+    o8 = np.ascontiguousarray(occ, dtype=np.uint8)
+    pts = np.ascontiguousarray(ends, dtype=np.float32).reshape(-1, 3)
+    o, per_ray = _raycast_origins(origins, pts.shape[0], per_ray_origin)
+    b0, b1, d, _ = _scan_geometry(bmin, bmax, o8.shape, np.zeros(3))
+    p = _raycast_params(lib, test_origin_voxel, per_ray)
+    rows = np.zeros((pts.shape[0], capi.RAYCAST_ROW), dtype=np.int32)
+    n = lib.isdf_raycast_host(o8.ctypes.data_as(C.c_void_p), _p(b0), _p(b1), float(res), d, _p(o), pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], C.byref(p),
+                              rows.ctypes.data_as(C.c_void_p))
+    if n < 0:
+        raise IsdfError(int(n), "isdf_raycast_host")
+    return rows, int(n)
+
+
+def _raycast_ticks(p, bmin, bmax, res, dims):
+    """the scan's quantisation in numpy: (ticks int64 [n, 3], inside [n]); the ticks of a point outside are 0"""
+    p = np.asarray(p, dtype=np.float64).reshape(-1, 3)
+    b0, b1 = np.asarray(bmin, dtype=np.float64), np.asarray(bmax, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        inside = ((p >= b0) & (p <= b1)).all(axis=1)
+        u = (np.where(inside[:, None], p, b0) - b0) / np.float64(res)
+    q = np.minimum(np.floor(u * 1024.0).astype(np.int64), np.asarray(dims, dtype=np.int64) * 1024 - 1)
+    return q, inside
+
+
+def rows_to_points(rows, origins, ends, geometry):
+    """What a cast's rows say in metres.  geometry = (bmin, bmax, res, dims).  Returns (range float64 [n], point float64 [n, 3]): the point
+    at which the ray entered the voxel its walk ended in - Po + (Pe - Po) * num / den between the two tick centres, taken to world
+    coordinates - and its distance from the origin's tick centre (0 for a walk that ended in its first voxel); NaN for status 2 and 3."""
+    bmin, bmax, res, dims = geometry
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, capi.RAYCAST_ROW)
+    n = rows.shape[0]
+    o = np.asarray(origins, dtype=np.float64)
+    o = np.broadcast_to(o.reshape(-1, 3), (n, 3))
+    qo, _ = _raycast_ticks(o, bmin, bmax, res, dims)
+    qe, _ = _raycast_ticks(np.asarray(ends, dtype=np.float32).astype(np.float64), bmin, bmax, res, dims)
+    Po, Pe = (2 * qo + 1).astype(np.float64), (2 * qe + 1).astype(np.float64)
+    num, den = rows[:, 6].astype(np.float64)[:, None], rows[:, 7].astype(np.float64)[:, None]
+    P = Po + (Pe - Po) * num / den                    # half ticks; |Pe - Po| num < 2^48: the product is exact
+    b0 = np.asarray(bmin, dtype=np.float64)
+    point = b0 + P / 2048.0 * np.float64(res)
+    rng = np.linalg.norm((P - Po) / 2048.0 * np.float64(res), axis=1)
+    bad = rows[:, 0] >= capi.RAYCAST_END_OUTSIDE
+    point[bad] = np.nan; rng[bad] = np.nan
+    return rng, point
+
+
+def scan_from_map(engine_or_occ, origin, ends, res=None, lib=None):
+    """A range sensor simulated on a map: the scan isdf_integrate_scan would have to be given for the map to read back what the sensor
+    saw.  engine_or_occ: an Engine (the casts run on the device; res: the map's resolution when the Engine did not set the map itself)
+    or (occ [X, Y, Z], bmin, bmax, res) (isdf_raycast_host).  The rays
+    origin -> ends (n x 3 float32) are cast; a ray that reaches its end keeps it with hit 0; a ray stopped by an occupied voxel is re-aimed
+    at the middle of its own chord through that voxel (the slab test in tick coordinates in fp64, then world coordinates rounded to
+    float32) and cast again: it is kept, with hit 1, only when the second cast stops at its own end voxel and that voxel is the first
+    cast's.  Every other ray is dropped.  Returns (ends' float32 [m, 3], hit uint8 [m], the number of rays dropped)."""
+    pts = np.ascontiguousarray(ends, dtype=np.float32).reshape(-1, 3)
+    o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+    if isinstance(engine_or_occ, Engine):
+        eng = engine_or_occ
+        occ, bmin, bmax = eng.get_grid(capi.GRID_OCCUPANCY)
+        res = eng._map_res if res is None else float(res)
+        if res is None:
+            raise ValueError("scan_from_map: the Engine's map was not set through set_grid / set_pointcloud; pass res")
+        cast = lambda e: eng.map_raycast(o, e)[0]
+    else:
+        occ, bmin, bmax, res = engine_or_occ
+        cast = lambda e: raycast_host(occ, bmin, bmax, res, o, e, lib=lib)[0]
+    dims = np.asarray(occ).shape
+    rows = cast(pts)
+    clear, hit = rows[:, 0] == capi.RAYCAST_CLEAR, rows[:, 0] == capi.RAYCAST_HIT
+    # the chord of the original ray through the hit voxel, in half ticks: the voxel v spans [2048 v, 2048 (v + 1)]
+    qo, _ = _raycast_ticks(o[None], bmin, bmax, res, dims)
+    qe, _ = _raycast_ticks(pts[hit].astype(np.float64), bmin, bmax, res, dims)
+    Po, Pe = (2 * qo + 1).astype(np.float64), (2 * qe + 1).astype(np.float64)
+    d = Pe - Po
+    lo = 2048.0 * rows[hit, 2:5].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t0, t1 = (lo - Po) / d, (lo + 2048.0 - Po) / d
+    par = d == 0.0                                      # parallel to the slab: the walk is inside it
+    t_in = np.where(par, -np.inf, np.minimum(t0, t1)).max(axis=1)
+    t_out = np.where(par, np.inf, np.maximum(t0, t1)).min(axis=1)
+    t_mid = 0.5 * (np.maximum(t_in, 0.0) + np.minimum(t_out, 1.0))
+    mid = (np.asarray(bmin, dtype=np.float64) + (Po + t_mid[:, None] * d) / 2048.0 * np.float64(res)).astype(np.float32)
+    rows2 = cast(mid)
+    q2, inside2 = _raycast_ticks(mid.astype(np.float64), bmin, bmax, res, dims)
+    own = (rows2[:, 2:5] == (q2 >> 10)).all(axis=1) & inside2
+    keep_hit = (rows2[:, 0] == capi.RAYCAST_HIT) & own & (rows2[:, 2:5] == rows[hit, 2:5]).all(axis=1)
+    out = pts.copy()
+    hit_idx = np.flatnonzero(hit)
+    out[hit_idx] = mid
+    keep = clear.copy()
+    keep[hit_idx[keep_hit]] = True
+    flag = np.zeros(len(pts), dtype=np.uint8)
+    flag[hit_idx[keep_hit]] = 1
+    return np.ascontiguousarray(out[keep]), np.ascontiguousarray(flag[keep]), int(len(pts) - keep.sum())
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -454,6 +568,7 @@ class Engine:
             raise IsdfError(rc, (msg or b"").decode())
         self.h = h
         self._keep = []
+        self._map_res = None            # the resolution set_grid / set_pointcloud gave (scan_from_map: the ABI has no getter for it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -480,6 +595,7 @@ class Engine:
         self._check(self.lib.isdf_set_grid(self.h, vox.ctypes.data_as(C.c_void_p), dt[vox.dtype], vox.shape[0],
                                            vox.shape[1], vox.shape[2], _p(o), None if bm is None else _p(bm),
                                            float(res), kind))
+        self._map_res = float(res)
 
     def set_shape(self, shape):
         self._keep.append(shape)
@@ -533,6 +649,7 @@ class Engine:
         self._check(self.lib.isdf_set_pointcloud(self.h, pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0],
                                                  None if bm0 is None else _p(bm0), None if bm1 is None else _p(bm1),
                                                  float(res), int(sta_threshold), dims))
+        self._map_res = float(res)
         return tuple(dims)
 
     def generate_esdf(self):
@@ -630,6 +747,42 @@ class Engine:
         self._check(self.lib.isdf_integrate_scan(self.h, _p(o), pts.ctypes.data_as(C.POINTER(C.c_float)), None if h is None else h.ctypes.data_as(C.c_void_p),
                                                  pts.shape[0], C.byref(p), C.byref(info)))
         self._watch_refresh_rows()
+        return info
+
+    # ---- rays cast through the map (csrc/map_raycast.hip)
+    def map_raycast(self, origins, ends, test_origin_voxel=False, per_ray_origin=None):
+        """isdf_map_raycast: the rays origins -> ends (ends n x 3 float32; origins 3 doubles for all rays, or n x 3 - per_ray_origin None:
+        by the array's rank) cast through the occupancy on the device, read-only.  Returns (rows int32 [n, 8] = (status, steps, i, j, k,
+        axis, num, den) per ray, IsdfMapRaycastInfo)."""
+        pts = np.ascontiguousarray(ends, dtype=np.float32).reshape(-1, 3)
+        o, per_ray = _raycast_origins(origins, pts.shape[0], per_ray_origin)
+        p = _raycast_params(self.lib, test_origin_voxel, per_ray)
+        rows = np.zeros((pts.shape[0], capi.RAYCAST_ROW), dtype=np.int32)
+        info = capi.IsdfMapRaycastInfo()
+        self._check(self.lib.isdf_map_raycast(self.h, _p(o), pts.ctypes.data_as(C.POINTER(C.c_float)), pts.shape[0], C.byref(p), rows.ctypes.data_as(C.c_void_p),
+                                              C.byref(info)))
+        return rows, info
+
+    def map_raycast_device(self, origins, d_ends, d_rows, test_origin_voxel=False, want_info=True, stream=None):
+        """isdf_map_raycast_device: d_ends (float32 [n, 3]) and d_rows (int32 [n, 8]) are torch tensors on the ctx's device; origins is a
+        host array of 3 doubles (shared) or a float64 [n, 3] tensor on the device (per ray).  The work goes on `stream` (None: torch's
+        current stream).  want_info False: info_out = NULL - nothing is handed over and nothing synchronised; returns None then."""
+        import torch
+        n = int(d_ends.shape[0])
+        per_ray = isinstance(origins, torch.Tensor)
+        if per_ray:
+            assert origins.dtype == torch.float64 and origins.is_contiguous() and tuple(origins.shape) == (n, 3)
+            op = C.c_void_p(origins.data_ptr())
+        else:
+            o = np.ascontiguousarray(origins, dtype=np.float64).reshape(3)
+            op = o.ctypes.data_as(C.c_void_p)
+        assert d_ends.dtype == torch.float32 and d_ends.is_contiguous() and d_rows.dtype == torch.int32 and d_rows.is_contiguous()
+        assert tuple(d_rows.shape) == (n, capi.RAYCAST_ROW)
+        p = _raycast_params(self.lib, test_origin_voxel, per_ray)
+        info = capi.IsdfMapRaycastInfo() if want_info else None
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._check(self.lib.isdf_map_raycast_device(self.h, op, C.c_void_p(d_ends.data_ptr()), n, C.byref(p), C.c_void_p(d_rows.data_ptr()),
+                                                     None if info is None else C.byref(info), C.c_void_p(st)))
         return info
 
     # ---- the map window shifted in place (csrc/map_shift.hip)

@@ -1429,6 +1429,53 @@ long long isdf_scan_sets_host(const double bmin[3], const double bmax[3], double
 long long isdf_scan_ray_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3],
                              const float end[3], int32_t *ijk_out, long long capacity);
 
+/* ---- rays cast through the map: the first occupied voxel per ray, on the device --------------------------------- */
+/* The read-only counterpart of the scan: the same ray, quantised and walked exactly as the section above defines it, testing the
+ * occupancy and stopping at the first occupied voxel.  A cast visits the voxels isdf_integrate_scan would write for the same ray.
+ * Ray i runs from origin o_i (fp64; origins = 3 doubles shared by all rays, or n x 3 with params.per_ray_origin) to end point e_i
+ * (ends = n x 3 floats, widened to fp64 as the scan widens them) and writes one row of eight int32 (32 bytes):
+ *   {status, steps, i, j, k, axis, num, den}
+ * status 3: o_i is outside the map or not finite (per-ray origins only).  status 2: e_i is outside or not finite (the scan's
+ * "skipped").  Otherwise the walk from o_i's voxel - voxel 0, tested only when params.test_origin_voxel != 0 - towards e_i's;
+ * status 1: the first tested voxel whose occupancy byte is not 0 ends the walk; status 0: the walk reaches e_i's voxel without one.
+ * steps: the 0-based index in the walk of the voxel (i, j, k) where it ended - the hit voxel, or e_i's voxel with steps = the sum of
+ * the steps on the three axes.  axis, num, den: where the ray entered that voxel - the axis of the last step taken, that axis's m
+ * before the step and its D, so that Po + (Pe - Po) * num / den (P = 2 q + 1, the tick centres in half ticks) is the crossing point,
+ * which lies on the voxel's face across `axis`; both are below 2^24.  A walk that ended at voxel 0: axis -1, num 0, den 1.  Status 2
+ * and 3 rows: {status, -1, -1, -1, -1, -1, 0, 1}.  Everything in a row is an integer: isdf_raycast_host and the device agree byte
+ * for byte; ranges and points in metres are the caller's arithmetic on the row.
+ * A shared origin outside the map: ISDF_ERR_INVALID_ARG, nothing written.  ISDF_ERR_STATE without an occupancy grid (a map from
+ * isdf_set_grid with ISDF_GRID_OCCUPANCY is served: no kept counts are needed); a multi-device ctx ISDF_ERR_UNSUPPORTED; n = 0 is
+ * legal (every array but a shared origin may then be NULL); params may be NULL (defaults), info_out may be NULL.  The call is
+ * read-only: no map product, epoch, dirty flag, kept field, watch or report changes.  Rays are not clipped to the map: the caller
+ * clips.
+ * isdf_map_raycast stages through grow-only buffers of its own: nothing is allocated after the first call of a size.
+ * isdf_map_raycast_device: d_ends (n x 3 floats) and d_rows_out (n x 8 int32, 16-byte aligned) are device memory, the work is put on
+ * `stream`; d_origins is device memory (n x 3 doubles) with per_ray_origin, and 3 doubles on the HOST without - a shared origin is an
+ * argument of the call, as the scan's is, and is tested before anything is launched.  With info_out == NULL it hands nothing over and
+ * does not synchronise; with info_out it synchronises `stream` once. */
+typedef struct isdf_map_raycast_params {
+    int32_t test_origin_voxel;   /* default 0: a sensor sits in free space, a line of sight may start in an occupied voxel */
+    int32_t per_ray_origin;      /* default 0: origins = 3 doubles for all rays; 1: n x 3                                   */
+    int32_t reserved[2];
+} isdf_map_raycast_params;
+typedef struct isdf_map_raycast_info {
+    int64_t n_rays, n_skipped, n_origin_outside, n_hits, n_clear;      /* given; rows of status 2, 3, 1, 0 */
+    int64_t steps_total;         /* sum of steps over status 0 and 1 */
+    double  cast_ms;             /* device time, events on the ctx's stream (the device form: on `stream`) */
+} isdf_map_raycast_info;
+void isdf_map_raycast_params_default(isdf_map_raycast_params *p);   /* null-safe */
+void isdf_map_raycast_sizes(int sizes_out[2]);                      /* null-safe; sizeof of the two structs above */
+int isdf_map_raycast(isdf_ctx *ctx, const double *origins, const float *ends, long long n, const isdf_map_raycast_params *params,
+                     int32_t *rows_out, isdf_map_raycast_info *info_out);
+int isdf_map_raycast_device(isdf_ctx *ctx, const double *d_origins, const float *d_ends, long long n, const isdf_map_raycast_params *params,
+                            int32_t *d_rows_out, isdf_map_raycast_info *info_out, void *stream);
+/* plain host code, no ctx, no device: the same rows from occupancy bytes (X * Y * Z, z fastest) and the map's geometry (each dim in
+ * [1, 4096]).  Returns n_hits or a negative isdf_status (ISDF_ERR_INVALID_ARG: a null array, a bad geometry, a shared origin outside
+ * the map - nothing written). */
+long long isdf_raycast_host(const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
+                            const double *origins, const float *ends, long long n, const isdf_map_raycast_params *params, int32_t *rows_out);
+
 /* ---- the map window shifted in place, so that the map can follow the robot -------------------------------------- */
 /* Every call above keeps the box (bmin, bmax, dims) that isdf_set_pointcloud fixed.  isdf_shift_map moves the window by
  * s = shift_ijk voxels: new voxel v holds what old voxel v + s held, a voxel whose source lies outside the old grid has count 0, and
