@@ -30,7 +30,7 @@ struct TrajRetimeState;         // traj_retime.hip: scratch of the retiming (lad
 void isdf_traj_retime_release_all(isdf_ctx *c);       // traj_retime.hip: drops it
 struct TrajReallocState;        // traj_realloc.hip: scratch of the per-piece re-allocation (iterate, piece rows, reports, state)
 void isdf_traj_realloc_release_all(isdf_ctx *c);      // traj_realloc.hip: drops it
-struct MapUpdateState;          // map_update.hip: scratch of the in-place map update (input, new-voxel list, hand-over record, table staging)
+struct MapUpdateState;          // map_change.hpp: scratch of the in-place map changes (input, new-voxel list, hand-over record, table staging)
 void isdf_map_update_release_all(isdf_ctx *c);        // map_update.hip: drops it
 struct MapRaycastState;         // map_raycast.hip: staging of the host-pointer ray cast, the counters' record and its pinned copy
 void isdf_map_raycast_release_all(isdf_ctx *c);       // map_raycast.hip: drops it

@@ -1,0 +1,134 @@
+// What the calls that change the map in place share (map_update.hip: voxels become occupied, map_clear.hip: voxels become free,
+// map_scan.hip: both from one range scan, map_shift.hip: the window moves): the grow-only scratch, the typed hand-over records, the
+// lane's "I changed a voxel" step and the host steps every driver goes through - begin, stage, hand-over, map changed, the front-end
+// stage in its two halves, the watch re-check, the ready checks.  The drivers call the steps in their own order; the steps are defined
+// once, in map_change.hip.
+#pragma once
+#include "isdf_ctx.hpp"
+#include "map_update_host.hpp"
+
+namespace isdf {
+
+// A count stage's record (the update's, the clear's, and the scan's two): zeroed, box empty, before every stage
+struct MapListRecord {
+    unsigned n;                         // voxels that changed (may exceed the list's capacity: the full path follows)
+    unsigned esdf0;                     // update: bits of the ESDF's first value before the update: +inf = the map had no occupied voxel
+    int lo[3], hi[3];                   // the dirty box
+    unsigned long long tally;           // update: values that fell (mu_esdf_kernel); clear: points whose voxel's count was 0
+    unsigned pad[6];
+};
+// the clear's ESDF stage
+struct McEsdfRecord {
+    int lo[3], hi[3];                   // the touched box
+    unsigned any_occ, pad0;             // some voxel of the map is still occupied
+    unsigned long long touched, raised;
+    unsigned pad[4];
+};
+// the scan's ray stage
+struct MsRecord {
+    unsigned long long n_skipped, n_hits, n_free, n_hit_voxels;
+    int lo[3], hi[3];                   // the visited box
+    unsigned pad[2];
+};
+// the shift's translation stage
+struct MshRecord {
+    unsigned long long counts_left;     // sum of the kept counts of the voxels without a destination
+    unsigned long long occupied_left;   // occupied voxels among them
+    unsigned any_occ;                   // some voxel of the new window is occupied
+    unsigned pad[11];
+};
+// every record of the family, one 64-byte line each: uploaded empty by map_stage, read back whole by every hand-over
+struct MapRecords { MapListRecord list; McEsdfRecord esdf; MsRecord scan; MshRecord shift; };
+static_assert(sizeof(MapListRecord) == 64 && sizeof(McEsdfRecord) == 64 && sizeof(MsRecord) == 64 && sizeof(MshRecord) == 64, "each hand-over record is one 64-byte line");
+
+inline MapRecords map_records_empty() {
+    MapRecords r{};
+    for (int a = 0; a < 3; a++) { r.list.lo[a] = r.esdf.lo[a] = r.scan.lo[a] = 0x7FFFFFFF; r.list.hi[a] = r.esdf.hi[a] = r.scan.hi[a] = -1; }
+    return r;
+}
+
+// the lane that changed voxel (x, y, z): the voxel goes to the list while there is room, the dirty box widens
+__device__ __forceinline__ void map_list_append(MapListRecord *__restrict__ rec, MuVoxel *__restrict__ list, unsigned cap, int x, int y, int z) {
+    const unsigned pos = atomicAdd(&rec->n, 1u);
+    if (pos < cap) list[pos] = MuVoxel{(unsigned short)x, (unsigned short)y, (unsigned short)z, 0};
+    atomicMin(&rec->lo[0], x); atomicMin(&rec->lo[1], y); atomicMin(&rec->lo[2], z);
+    atomicMax(&rec->hi[0], x); atomicMax(&rec->hi[1], y); atomicMax(&rec->hi[2], z);
+}
+
+}  // namespace isdf
+
+struct MapUpdateState {
+    isdf::DevBuf<void> d_in;                  // the call's points or voxel indices
+    isdf::DevBuf<isdf::MuVoxel> d_list;       // the new (or cleared) voxels, in no defined order
+    isdf::DevBuf<isdf::MapRecords> d_rec; isdf::PinBuf<isdf::MapRecords> h_rec;      // one block each
+    isdf::DevBuf<uint4> d_pack; isdf::PinBuf<uint32_t> h_pack;          // the grown box of the configuration space on its way to the host table
+    isdf::DevBuf<int> d_edt_a, d_edt_b;       // map_clear.hip: the slabs of the separable transform over the touched box
+    isdf::DevBuf<unsigned> d_free_bits, d_hit_bits;     // map_scan.hip: one bit per voxel, the voxels a scan's rays pass / end in
+    // map_shift.hip: where the translation writes; each then changes places with the ctx's own buffer (one more copy of the counts, the
+    // occupancy and the configuration-space table stays allocated)
+    isdf::DevBuf<unsigned> d_shift_counts, d_shift_cspace; isdf::DevBuf<uint8_t> d_shift_occ;
+    hipEvent_t ev_scan[2] = {nullptr, nullptr};          // map_scan.hip: around the ray stage
+    // [0], [1]: a count (translation) stage; [2], [3]: the ESDF stage; [4], [5]: the front-end stage; [6], [7]: the field's repair or reopen
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~MapUpdateState() {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_scan) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+namespace isdf {
+
+// ---- the shared steps (map_change.hip), in the order a driver meets them
+// ready: the three tests every entry point makes before anything moves; op names the operation in the message ("the map update")
+int map_change_ready(isdf_ctx *c, const char *op, const void *in, long long n, bool needs_counts);
+int map_voxels_in_grid(isdf_ctx *c, const int32_t *ijk, long long n);       // ISDF_ERR_INVALID_ARG for an index outside the grid
+// begin: the ctx's device current, its scratch created with every event on first use
+int map_begin(isdf_ctx *c, MapUpdateState **out);
+// list capacity: the most entries a count stage can need, and the cap it is given
+unsigned map_list_cap(long long max_voxels, unsigned long long n_in, unsigned long long n_vox);
+// stage: S.d_in reserved for `in` and `in2` (one behind the other, either may be empty) and S.d_list for list_len entries (0: no list),
+// the records uploaded empty, the input uploaded, ev_begin recorded.  Nothing allocates on a second call of the same size.
+int map_stage(isdf_ctx *c, MapUpdateState &S, const void *in, size_t in_bytes, const void *in2, size_t in2_bytes, size_t list_len, hipEvent_t ev_begin);
+// hand-over: ev_end recorded (null: none), the records to S.h_rec, one synchronisation.  The kernels before it may have run, so a
+// failure leaves "<op> hand-over: ..." in the ctx and drops what was derived from the old map.
+int map_hand_over(isdf_ctx *c, MapUpdateState &S, hipEvent_t ev_end, const char *op, bool voxels);
+inline hipError_t map_records_fetch(MapUpdateState &S, hipStream_t st) { return hipMemcpyAsync(S.h_rec.get(), S.d_rec, sizeof(MapRecords), hipMemcpyDeviceToHost, st); }
+// After a failure past the point where the occupancy moved: what was derived from the old map goes (as isdf_set_pointcloud drops
+// it), the error message stays.  The occupancy and the counts are consistent with each other and stay.
+void mu_drop_derived(isdf_ctx *c, bool voxels);
+// map changed: the voxel forms' counts no longer describe the occupancy, the bit grid is stale, a valid cost-to-go field is dropped
+// (returns 1 then: a driver that repairs it asks isdf_field_*_wanted first)
+int map_changed(isdf_ctx *c, bool voxels);
+// ... and what a refresh over a list decides before its first stage: the dirty box, grown for the front end, which products are
+// refreshed (an ESDF that is switched off is dropped here) and whether a cap of the params is exceeded
+struct MapRefresh { MuBox box, grown; bool do_esdf, do_fe, over; };
+MapRefresh map_refresh_begin(isdf_ctx *c, const MapListRecord &R, unsigned cap, bool voxels, int refresh_esdf, int refresh_frontend, double full_fraction, int *field_dropped);
+// The front-end stage, in two halves around the caller's synchronisation.  _launch: a front end that is switched off (!on) is
+// released; ev[4] (stamp == false: the caller recorded it before work of its own); the whole-map refresh (full) or, per (box, grown)
+// pair, the dwords of the inflated bit map that cover `box`, the configuration-space words of `grown` if there is a table and, when
+// the A* holds the table on the host, that box packed into S.d_pack; ev[5]; the pack buffer on its way to S.h_pack.  The kernels
+// recompute from the occupancy: the direction of the change does not show.  _finish, after the synchronisation: the boxes scattered
+// into the host table, the stage's time.
+struct MapFrontend {
+    int n_boxes; MuBox grown[6];
+    bool patch; size_t pack_total, pack_at[6];
+    int refreshed, cspace_refreshed, host_table_patched; long long cspace_voxels; double ms;
+};
+int map_frontend_launch(isdf_ctx *c, MapUpdateState &S, bool on, bool full, const MuBox *boxes, const MuBox *grown, int n_boxes, MapFrontend &F, bool stamp = true);
+void map_frontend_finish(isdf_ctx *c, MapUpdateState &S, MapFrontend &F);
+template <class Info> inline void map_frontend_report(const MapFrontend &F, Info &info) {       // the update's and the clear's info name these alike
+    info.frontend_refreshed = F.refreshed; info.cspace_refreshed = F.cspace_refreshed; info.host_table_patched = F.host_table_patched;
+    info.cspace_voxels_recomputed = F.cspace_voxels; info.frontend_ms = F.ms;
+}
+// watch re-check: removed or moved voxels cannot be subtracted from the kept report's piece minima, so an armed watch's trajectory is
+// checked against the whole new map again and stays armed.  A failing check drops the report and fails the call.  *rechecked = armed.
+int map_watch_recheck(isdf_ctx *c, bool armed, int32_t *rechecked);
+float mu_event_ms(hipEvent_t a, hipEvent_t b);
+
+// Everything after the hand-over of a call that occupied (mu_, map_update.hip) or freed (mc_, map_clear.hip) at least one voxel: R is
+// the count stage's record as the host read it, S.d_list the new (cleared) voxels, cap the list's capacity; the counts and the occupancy
+// are the new map's already.  map_scan.hip runs both, the clear's first.  A failure: the caller calls mu_drop_derived.
+int mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_update_info &info);
+int mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info);
+
+}  // namespace isdf

@@ -14,14 +14,14 @@
 //                      X x Y x Tz (one lane per column, two sweeps over the occupancy bytes), y pass over X x Ty x Tz, x pass over the
 //                      box with edt_line_kernel<0>'s conversion - the integer d2 is unique, so float(res * sqrt(d2)) is the byte
 //                      isdf_generate_esdf writes.  Scratch: the two slabs, not the map.
-//   front end          map_update.hip's boxed kernels through mu_frontend_box_launch: they recompute from the occupancy.
+//   front end          the shared boxed kernels through map_frontend_launch (map_change.hip): they recompute from the occupancy.
 // A value can only rise, an untouched value stays, and every consumer of the cleared list asks "is there an entry that ...": its
 // order, which the atomics leave undefined, never shows.
 #include "isdf_ctx.hpp"
 #include "frontend_dev.hpp"
 #include "grid_index.hpp"
 #include "map_clear_host.hpp"
-#include "map_update_state.hpp"
+#include "map_change.hpp"
 #include "swept_field.hpp"
 #include <algorithm>
 #include <cmath>
@@ -32,7 +32,7 @@ namespace isdf {
 
 template <bool VOXELS>
 __global__ __launch_bounds__(256) void mc_mark_kernel(const void *__restrict__ in, long long n, DevGrid G, unsigned *__restrict__ counts, unsigned thr,
-                                                      uint8_t *__restrict__ occ, MuVoxel *__restrict__ list, unsigned cap, McRecord *__restrict__ rec) {
+                                                      uint8_t *__restrict__ occ, MuVoxel *__restrict__ list, unsigned cap, MapListRecord *__restrict__ rec) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         int ix, iy, iz;
         bool crossed = false;
@@ -49,19 +49,14 @@ __global__ __launch_bounds__(256) void mc_mark_kernel(const void *__restrict__ i
             const size_t a = ((size_t)ix * G.Y + iy) * G.Z + iz;
             unsigned seen = counts[a];
             for (;;) {
-                if (seen == 0u) { atomicAdd(&rec->ignored, 1ull); break; }
+                if (seen == 0u) { atomicAdd(&rec->tally, 1ull); break; }
                 const unsigned was = atomicCAS(&counts[a], seen, seen - 1u);
                 if (was == seen) { crossed = thr >= 1u && seen == thr; break; }          // thr == 0: every voxel stays occupied
                 seen = was;
             }
             if (crossed) occ[a] = 0;
         }
-        if (crossed) {
-            const unsigned pos = atomicAdd(&rec->n_cleared, 1u);
-            if (pos < cap) list[pos] = MuVoxel{(unsigned short)ix, (unsigned short)iy, (unsigned short)iz, 0};
-            atomicMin(&rec->lo[0], ix); atomicMin(&rec->lo[1], iy); atomicMin(&rec->lo[2], iz);
-            atomicMax(&rec->hi[0], ix); atomicMax(&rec->hi[1], iy); atomicMax(&rec->hi[2], iz);
-        }
+        if (crossed) map_list_append(rec, list, cap, ix, iy, iz);
     }
 }
 
@@ -187,46 +182,32 @@ void empty_boxes(isdf_map_clear_info &info) {
 }  // namespace
 
 // everything after the hand-over of a call that freed at least one voxel
-int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const McRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info) {
+int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info) {
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     const int dims[3] = {G.X, G.Y, G.Z};
     const size_t n_vox = (size_t)G.X * G.Y * G.Z;
     int rc;
-    MuBox box;
-    for (int a = 0; a < 3; a++) { box.lo[a] = info.dirty_lo[a] = R.lo[a]; box.hi[a] = info.dirty_hi[a] = R.hi[a]; }
-    if (voxels) c->d_counts.release();              // the counts no longer describe the occupancy
-    c->bits_dirty = true;
-
-    isdf_ctx::FrontEnd &fe = c->fe;
-    const bool do_esdf = (bool)c->d_esdf && P.refresh_esdf != 0;
-    const bool do_fe = fe.built && P.refresh_frontend != 0;
-    const MuBox grown = mu_box_grow(box, do_fe ? (fe.cfg.kernel_size - 1) / 2 : 0, dims);
-    bool full = (unsigned long long)R.n_cleared > (unsigned long long)cap || (double)mu_box_voxels(grown) > P.full_fraction * (double)n_vox;
     // The cost-to-go field: dropped (mode 0 of isdf_frontend_field_set_reopen; the repair's rule is not proved for opened bits), or
     // lowered in place once the configuration space is the new map's (mode 1).  It is invalid from here until the reopen has gone
     // through: every error path leaves it dropped.
-    const bool reopen = do_fe && isdf_field_reopen_wanted(c);
-    if (fe.field_valid) { fe.field_valid = false; fe.field_reachable = false; info.field_dropped = 1; }
+    const bool reopen = P.refresh_frontend != 0 && isdf_field_reopen_wanted(c);
+    const MapRefresh M = map_refresh_begin(c, R, cap, voxels, P.refresh_esdf, P.refresh_frontend, P.full_fraction, &info.field_dropped);
+    for (int a = 0; a < 3; a++) { info.dirty_lo[a] = M.box.lo[a]; info.dirty_hi[a] = M.box.hi[a]; }
+    bool full = M.over;
 
     // ---- ESDF
-    if (c->d_esdf && !P.refresh_esdf) {
-        c->d_esdf.release();
-        c->grid.esdf = nullptr;
-        c->bricks_stale = true;
-    }
-    McEsdfRecord *const d_er = (McEsdfRecord *)(S.d_rec.get() + 1);
-    const McEsdfRecord *const h_er = (const McEsdfRecord *)(S.h_rec.get() + 1);
+    McEsdfRecord *const d_er = &S.d_rec.get()->esdf;
+    const McEsdfRecord *const h_er = &S.h_rec.get()->esdf;
     HIPCHK(c, hipEventRecord(S.ev[2], st));
-    if (do_esdf) {
+    if (M.do_esdf) {
         MuBox T{{0, 0, 0}, {-1, -1, -1}};
         if (!full) {
             // part one: the touched voxels.  Their box sizes the slabs and decides the path: the second hand-over of the call.
             hipLaunchKernelGGL(mc_touched_kernel, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, st, G, (const float *)c->d_esdf.get(), (const uint8_t *)c->d_occ.get(),
-                               (const MuVoxel *)S.d_list.get(), (int)R.n_cleared, box, d_er);
+                               (const MuVoxel *)S.d_list.get(), (int)R.n, M.box, d_er);
             HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(S.h_rec.get() + 1, S.d_rec.get() + 1, sizeof(McEsdfRecord), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
+            if ((rc = map_hand_over(c, S, nullptr, "map clear", voxels))) return rc;
             for (int a = 0; a < 3; a++) { T.lo[a] = h_er->lo[a]; T.hi[a] = h_er->hi[a]; }
             if (!mu_box_empty(T))
                 for (int a = 0; a < 3; a++)
@@ -251,28 +232,11 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
     info.path = full ? 2 : 1;
     HIPCHK(c, hipEventRecord(S.ev[3], st));
 
-    // ---- front end
-    bool patch = false;
-    size_t pack_words = 0;
-    const size_t nw = 4 * (size_t)((fe.xk * fe.yk + 127) / 128);
-    if (fe.built && !P.refresh_frontend) isdf_frontend_release(c);
-    HIPCHK(c, hipEventRecord(S.ev[4], st));
-    if (do_fe) {
-        info.frontend_refreshed = 1;
-        info.cspace_refreshed = fe.d_cspace ? 1 : 0;
-        if (full) {
-            if ((rc = isdf_frontend_refresh_map(c, nullptr))) return rc;
-            if (fe.d_cspace) info.cspace_voxels_recomputed = (long long)n_vox;
-        } else {
-            long long cs_voxels = 0;
-            if ((rc = mu_frontend_box_launch(c, S, box, grown, &patch, &pack_words, &cs_voxels))) return rc;
-            info.cspace_voxels_recomputed = cs_voxels;
-        }
-    }
-    HIPCHK(c, hipEventRecord(S.ev[5], st));
-    if (patch) HIPCHK(c, hipMemcpyAsync(S.h_pack.get(), S.d_pack, pack_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(S.h_rec.get() + 1, S.d_rec.get() + 1, sizeof(McEsdfRecord), hipMemcpyDeviceToHost, st));
-    const int *const f_lo = full ? nullptr : grown.lo, *const f_hi = full ? nullptr : grown.hi;
+    // ---- front end, the field's reopen around the synchronisation
+    MapFrontend F;
+    if ((rc = map_frontend_launch(c, S, P.refresh_frontend != 0, full, &M.box, &M.grown, 1, F))) return rc;
+    HIPCHK(c, map_records_fetch(S, st));
+    const int *const f_lo = full ? nullptr : M.grown.lo, *const f_hi = full ? nullptr : M.grown.hi;
     if (reopen && (rc = isdf_field_reopen_begin(c, f_lo, f_hi, S.ev[6]))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     if (reopen) {                       // the rounds read one word each; the host table is patched after them
@@ -280,32 +244,11 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
         if ((rc = isdf_field_reopen_end(c, f_lo, f_hi, S.ev[6], S.ev[7], &reopened))) return rc;
         if (reopened) info.field_dropped = 0;
     }
-    if (patch) {
-        mu_scatter_box(fe.h_cspace, dims, nw, grown, S.h_pack.get());
-        info.host_table_patched = 1;
-    }
-    if (do_esdf && !full) info.esdf_voxels_raised = (long long)h_er->raised;
+    map_frontend_finish(c, S, F);
+    map_frontend_report(F, info);
+    if (M.do_esdf && !full) info.esdf_voxels_raised = (long long)h_er->raised;
     info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
-    info.frontend_ms = mu_event_ms(S.ev[4], S.ev[5]);
-    // the kept clearance report (mode 1 of isdf_traj_check_set_watch): removed voxels cannot be subtracted from the piece minima, so the
-    // kept trajectory is checked against the whole new map again.  A failing check drops the report and fails the clear as a whole.
-    if (traj_watch_armed(c)) {
-        const long long folded = c->tck->w.last.updates_folded;
-        isdf_traj_check_info now;
-        if ((rc = traj_check_rerun_kept(c, &now))) {
-            const std::string err = c->err;
-            (void)hipStreamSynchronize(st);
-            traj_check_drop_report(c);
-            c->err = err;
-            return rc;
-        }
-        isdf_traj_watch_info &L = c->tck->w.last;           // (the re-check armed the watch again and cleared this)
-        L.updates_folded = folded + 1;
-        L.path = 2;
-        L.select_ms = now.select_ms; L.field_ms = now.field_ms; L.reduce_ms = now.reduce_ms;
-        info.watch_rechecked = 1;
-    }
-    return ISDF_OK;
+    return map_watch_recheck(c, traj_watch_armed(c), &info.watch_rechecked);
 }
 
 namespace {
@@ -319,70 +262,36 @@ int map_clear(isdf_ctx *c, const void *in, long long n_in, bool voxels, const is
     isdf_map_clear_info info{};
     empty_boxes(info);
     info.n_points = n_in;
-    HIPCHK(c, hipSetDevice(c->device));
     MapUpdateState *Sp;
-    { const int rc0 = mu_state(c, &Sp); if (rc0) return rc0; }
+    int rc = map_begin(c, &Sp);
+    if (rc) return rc;
     MapUpdateState &S = *Sp;
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
-    const size_t n_vox = (size_t)G.X * G.Y * G.Z;
-    int rc;
 
-    // ---- count down, find the cleared voxels: one hand-over record, one synchronisation
-    const size_t in_bytes = (size_t)n_in * 3 * (voxels ? sizeof(int) : sizeof(float));
-    const unsigned cap = (unsigned)std::min<unsigned long long>({(unsigned long long)P.max_cleared_voxels, (unsigned long long)n_in, (unsigned long long)n_vox, 0x7FFFFFFFull});
-    if ((rc = S.d_in.reserve(c, in_bytes))) return rc;
-    if ((rc = S.d_list.reserve(c, std::max<size_t>(cap, 1)))) return rc;
-    if ((rc = S.d_rec.reserve(c, 2))) return rc;
-    if ((rc = S.h_rec.reserve(c, 2))) return rc;
-    {
-        McRecord zero{};
-        McEsdfRecord ezero{};
-        for (int a = 0; a < 3; a++) { zero.lo[a] = ezero.lo[a] = 0x7FFFFFFF; zero.hi[a] = ezero.hi[a] = -1; }
-        std::memcpy(S.h_rec.get(), &zero, sizeof(zero));
-        std::memcpy(S.h_rec.get() + 1, &ezero, sizeof(ezero));
-    }
-    HIPCHK(c, hipMemcpyAsync(S.d_rec, S.h_rec.get(), 2 * sizeof(MuRecord), hipMemcpyHostToDevice, st));
-    if (n_in > 0) HIPCHK(c, hipMemcpyAsync(S.d_in, in, in_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(S.ev[0], st));
+    // ---- count down, find the cleared voxels: one hand-over
+    const unsigned cap = map_list_cap(P.max_cleared_voxels, (unsigned long long)n_in, (unsigned long long)G.X * G.Y * G.Z);
+    if ((rc = map_stage(c, S, in, (size_t)n_in * 3 * (voxels ? sizeof(int) : sizeof(float)), nullptr, 0, std::max<size_t>(cap, 1), S.ev[0]))) return rc;
     if (n_in > 0) {
         const unsigned blocks = (unsigned)std::min<long long>((n_in + 255) / 256, 2048);
+        MapListRecord *const d_rec = &S.d_rec.get()->list;
         if (voxels) hipLaunchKernelGGL(mc_mark_kernel<true>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, (unsigned *)nullptr, 0u, c->d_occ.get(),
-                                       S.d_list.get(), cap, (McRecord *)S.d_rec.get());
+                                       S.d_list.get(), cap, d_rec);
         else hipLaunchKernelGGL(mc_mark_kernel<false>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, c->d_counts.get(), (unsigned)c->counts_thr,
-                                c->d_occ.get(), S.d_list.get(), cap, (McRecord *)S.d_rec.get());
+                                c->d_occ.get(), S.d_list.get(), cap, d_rec);
         HIPCHK(c, hipGetLastError());
     }
-    {
-        hipError_t e = hipEventRecord(S.ev[1], st);
-        if (e == hipSuccess) e = hipMemcpyAsync(S.h_rec.get(), S.d_rec, sizeof(McRecord), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {          // the kernel may have run: the occupancy may have moved
-            c->err = std::string("map clear hand-over: ") + hipGetErrorString(e);
-            mu_drop_derived(c, voxels);
-            return ISDF_ERR_HIP;
-        }
-    }
-    McRecord R;
-    std::memcpy(&R, S.h_rec.get(), sizeof(R));
+    if ((rc = map_hand_over(c, S, S.ev[1], "map clear", voxels))) return rc;           // the kernel may have run: the occupancy may have moved
+    const MapListRecord R = S.h_rec.get()->list;
     info.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
-    info.n_cleared_voxels = R.n_cleared;
-    info.n_points_ignored = (long long)R.ignored;
-    if (R.n_cleared == 0) {             // nothing but the counts changed: every product stays in place, the field and the watch included
-        if (info_out) *info_out = info;
-        return ISDF_OK;
+    info.n_cleared_voxels = R.n;
+    info.n_points_ignored = (long long)R.tally;
+    if (R.n > 0) {                      // (nothing but the counts changed: every product stays in place, the field and the watch included)
+        // from here on the occupancy has moved: a failure must not leave products behind that describe the old map
+        rc = mc_refresh_products(c, S, P, R, cap, voxels, info);
+        if (rc != ISDF_OK) { mu_drop_derived(c, voxels); return rc; }
     }
-    // from here on the occupancy has moved: a failure must not leave products behind that describe the old map
-    rc = mc_refresh_products(c, S, P, R, cap, voxels, info);
-    if (rc != ISDF_OK) { mu_drop_derived(c, voxels); return rc; }
     if (info_out) *info_out = info;
-    return ISDF_OK;
-}
-
-int clear_ready(isdf_ctx *c, const void *in, long long n) {
-    if (n < 0 || (n > 0 && !in)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad clear arguments");
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "clearing the map in place is not offered on a multi-device ctx");
-    if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "clearing the map needs an occupancy grid");
     return ISDF_OK;
 }
 
@@ -397,20 +306,15 @@ bool host_args_bad(const int32_t dims[3], double res, const int32_t *ijk, long l
 
 extern "C" int isdf_clear_pointcloud(isdf_ctx *c, const float *xyz, long long n_points, const isdf_map_clear_params *params, isdf_map_clear_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    const int rc = clear_ready(c, xyz, n_points);
-    if (rc) return rc;
-    if (!c->d_counts) return isdf_fail(c, ISDF_ERR_STATE, "no kept point counts: the map did not come from isdf_set_pointcloud, or isdf_update_voxels / isdf_clear_voxels changed it since");
-    return map_clear(c, xyz, n_points, false, params, info_out);
+    const int rc = map_change_ready(c, "clearing the map", xyz, n_points, true);
+    return rc ? rc : map_clear(c, xyz, n_points, false, params, info_out);
 }
 
 extern "C" int isdf_clear_voxels(isdf_ctx *c, const int32_t *ijk, long long n_voxels, const isdf_map_clear_params *params, isdf_map_clear_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    const int rc = clear_ready(c, ijk, n_voxels);
-    if (rc) return rc;
-    for (long long i = 0; i < n_voxels; i++)
-        if (ijk[3 * i] < 0 || ijk[3 * i] >= c->grid.X || ijk[3 * i + 1] < 0 || ijk[3 * i + 1] >= c->grid.Y || ijk[3 * i + 2] < 0 || ijk[3 * i + 2] >= c->grid.Z)
-            return isdf_fail(c, ISDF_ERR_INVALID_ARG, "a voxel index lies outside the grid");
-    return map_clear(c, ijk, n_voxels, true, params, info_out);
+    int rc = map_change_ready(c, "clearing the map", ijk, n_voxels, false);
+    if (!rc) rc = map_voxels_in_grid(c, ijk, n_voxels);
+    return rc ? rc : map_clear(c, ijk, n_voxels, true, params, info_out);
 }
 
 extern "C" long long isdf_clear_touched_host(const float *esdf_old, const int32_t dims[3], double resolution, const int32_t *cleared_ijk, long long n_cleared,

@@ -7,30 +7,22 @@
 //                    workgroup in LDS and then into the call's record.
 //   ms_apply_kernel  over the visited box, which it reads from that record: one lane per dword of a column's bits.  F = free bit set and
 //                    hit bit clear: the count goes down by miss_weight and not below 0, and the voxel whose count leaves
-//                    [thr, inf) is freed, listed and boxed into an McRecord exactly as mc_mark_kernel's crossing lane does it -
+//                    [thr, inf) is freed, listed and boxed (map_list_append) exactly as mc_mark_kernel's crossing lane does it -
 //                    `ignored` counts what miss_weight single removals would have found at 0.  One lane owns a voxel: no atomics on the
 //                    counts.  Also |F| and the distinct voxels of H.
 //   ms_hits_kernel   one lane per ray again, after the clear's products are in place: the end voxel of a hit ray counts up by one,
-//                    mu_mark_kernel's crossing test and MuRecord.
+//                    mu_mark_kernel's crossing test, into the list record again.
 // Then map_clear.hip's and map_update.hip's own refresh stages, in that order: the call IS isdf_clear_pointcloud of miss_weight
 // centres of every voxel of F followed by isdf_update_pointcloud of the hit end points, and reports what those two calls report.
 #include "isdf_ctx.hpp"
 #include "map_scan_host.hpp"
-#include "map_update_state.hpp"
+#include "map_change.hpp"
 #include "swept_field.hpp"
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 namespace isdf {
-
-// the ray stage's record, the third 64 bytes of the hand-over
-struct MsRecord {
-    unsigned long long n_skipped, n_hits, n_free, n_hit_voxels;
-    int lo[3], hi[3];                   // the visited box
-    unsigned pad[2];
-};
-static_assert(sizeof(MsRecord) == 64, "each hand-over record is one 64-byte line");
 
 struct MsOrigin { int q[3]; };
 
@@ -93,7 +85,7 @@ __global__ __launch_bounds__(256) void ms_trace_kernel(const float *__restrict__
 
 __global__ __launch_bounds__(256) void ms_apply_kernel(DevGrid G, const unsigned *__restrict__ free_bits, const unsigned *__restrict__ hit_bits,
                                                        unsigned *__restrict__ counts, unsigned thr, unsigned miss, uint8_t *__restrict__ occ,
-                                                       MuVoxel *__restrict__ list, unsigned cap, MsRecord *__restrict__ srec, McRecord *__restrict__ rec) {
+                                                       MuVoxel *__restrict__ list, unsigned cap, MsRecord *__restrict__ srec, MapListRecord *__restrict__ rec) {
     const int lo0 = srec->lo[0], lo1 = srec->lo[1], lo2 = srec->lo[2], hi0 = srec->hi[0], hi1 = srec->hi[1], hi2 = srec->hi[2];
     if (hi0 < lo0 || hi1 < lo1 || hi2 < lo2) return;            // no ray was traced
     const int e1 = hi1 - lo1 + 1;
@@ -125,22 +117,18 @@ __global__ __launch_bounds__(256) void ms_apply_kernel(DevGrid G, const unsigned
             if (now != was) counts[a] = now;
             if (thr >= 1u && was >= thr && now < thr) {         // thr == 0: every voxel stays occupied
                 occ[a] = 0;
-                const int z = (int)(a - base);
-                const unsigned pos = atomicAdd(&rec->n_cleared, 1u);
-                if (pos < cap) list[pos] = MuVoxel{(unsigned short)x, (unsigned short)y, (unsigned short)z, 0};
-                atomicMin(&rec->lo[0], x); atomicMin(&rec->lo[1], y); atomicMin(&rec->lo[2], z);
-                atomicMax(&rec->hi[0], x); atomicMax(&rec->hi[1], y); atomicMax(&rec->hi[2], z);
+                map_list_append(rec, list, cap, x, y, (int)(a - base));
             }
         }
     }
     if (n_free) atomicAdd(&srec->n_free, n_free);
     if (n_hitv) atomicAdd(&srec->n_hit_voxels, n_hitv);
-    if (ignored) atomicAdd(&rec->ignored, ignored);
+    if (ignored) atomicAdd(&rec->tally, ignored);
 }
 
 __global__ __launch_bounds__(256) void ms_hits_kernel(const float *__restrict__ xyz, const uint8_t *__restrict__ hit, long long n, DevGrid G,
                                                       unsigned *__restrict__ counts, unsigned thr, uint8_t *__restrict__ occ, const float *__restrict__ esdf,
-                                                      MuVoxel *__restrict__ list, unsigned cap, MuRecord *__restrict__ rec) {
+                                                      MuVoxel *__restrict__ list, unsigned cap, MapListRecord *__restrict__ rec) {
     if (esdf && blockIdx.x == 0 && threadIdx.x == 0) rec->esdf0 = __float_as_uint(esdf[0]);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         int qe[3];
@@ -150,10 +138,7 @@ __global__ __launch_bounds__(256) void ms_hits_kernel(const float *__restrict__ 
         const unsigned old = atomicAdd(&counts[a], 1u);
         if (thr >= 1u && old + 1u == thr) {                     // mu_mark_kernel's crossing: exactly one add sees it
             occ[a] = 1;
-            const unsigned pos = atomicAdd(&rec->n_new, 1u);
-            if (pos < cap) list[pos] = MuVoxel{(unsigned short)ix, (unsigned short)iy, (unsigned short)iz, 0};
-            atomicMin(&rec->lo[0], ix); atomicMin(&rec->lo[1], iy); atomicMin(&rec->lo[2], iz);
-            atomicMax(&rec->hi[0], ix); atomicMax(&rec->hi[1], iy); atomicMax(&rec->hi[2], iz);
+            map_list_append(rec, list, cap, ix, iy, iz);
         }
     }
 }
@@ -184,86 +169,52 @@ void empty_info(isdf_map_scan_info &info) {
     }
 }
 
-// the hand-over of a count stage: the record(s) to the host and one synchronisation.  The kernels before it may have run: a failure
-// here leaves counts and occupancy consistent with each other and drops what was derived from the old map.
-int hand_over(isdf_ctx *c, MapUpdateState &S, hipEvent_t ev_end, int n_records) {
-    hipError_t e = hipEventRecord(ev_end, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(S.h_rec.get(), S.d_rec, (size_t)n_records * sizeof(MuRecord), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) return ISDF_OK;
-    c->err = std::string("scan hand-over: ") + hipGetErrorString(e);
-    mu_drop_derived(c, false);
-    return ISDF_ERR_HIP;
-}
-
 int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8_t *hit, long long n_rays, const isdf_map_scan_params &P, isdf_map_scan_info *info_out) {
     isdf_map_scan_info info{};
     empty_info(info);
     info.n_rays = n_rays;
-    HIPCHK(c, hipSetDevice(c->device));
     MapUpdateState *Sp;
-    { const int rc0 = mu_state(c, &Sp); if (rc0) return rc0; }
+    int rc = map_begin(c, &Sp);
+    if (rc) return rc;
     MapUpdateState &S = *Sp;
-    for (hipEvent_t &e : S.ev_scan) if (!e) HIPCHK(c, hipEventCreate(&e));
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     const unsigned long long n_vox = (unsigned long long)G.X * G.Y * G.Z;
     const size_t n_words = (size_t)((n_vox + 31) / 32);
     const unsigned thr = (unsigned)c->counts_thr, miss = (unsigned)P.miss_weight;
-    int rc;
 
     // ---- scratch: nothing below allocates after the first call of a size.  The lists' capacities as the two calls would choose them,
     // with the number of voxels the rays can visit in place of the number of points (which is known only after the trace).
     const unsigned long long reach = (unsigned long long)n_rays >= n_vox ? n_vox : std::min<unsigned long long>(n_vox, (unsigned long long)n_rays * (unsigned)(G.X + G.Y + G.Z));
-    const unsigned cap_clear = (unsigned)std::min<unsigned long long>({(unsigned long long)P.clear.max_cleared_voxels, reach, 0x7FFFFFFFull});
-    const unsigned long long cap_update_most = std::min<unsigned long long>({(unsigned long long)P.update.max_new_voxels, (unsigned long long)n_rays, n_vox, 0x7FFFFFFFull});
+    const unsigned cap_clear = map_list_cap(P.clear.max_cleared_voxels, reach, n_vox);
+    const unsigned cap_update_most = map_list_cap(P.update.max_new_voxels, (unsigned long long)n_rays, n_vox);
     const size_t xyz_bytes = (size_t)n_rays * 3 * sizeof(float);
-    if ((rc = S.d_in.reserve(c, xyz_bytes + (hit ? (size_t)n_rays : 0)))) return rc;
-    if ((rc = S.d_list.reserve(c, (size_t)std::max<unsigned long long>({cap_clear, cap_update_most, 1ull})))) return rc;
-    if ((rc = S.d_rec.reserve(c, 3))) return rc;
-    if ((rc = S.h_rec.reserve(c, 3))) return rc;
-    if ((rc = S.d_free_bits.reserve(c, n_words))) return rc;
-    if ((rc = S.d_hit_bits.reserve(c, n_words))) return rc;
-    const float *const d_xyz = (const float *)S.d_in.get();
-    const uint8_t *const d_hit = hit ? (const uint8_t *)S.d_in.get() + xyz_bytes : nullptr;
-    McRecord *const d_mc = (McRecord *)S.d_rec.get();
-    MsRecord *const d_ms = (MsRecord *)(S.d_rec.get() + 2);
-    {
-        McRecord zero{};
-        McEsdfRecord ezero{};
-        MsRecord szero{};
-        for (int a = 0; a < 3; a++) { zero.lo[a] = ezero.lo[a] = szero.lo[a] = 0x7FFFFFFF; zero.hi[a] = ezero.hi[a] = szero.hi[a] = -1; }
-        std::memcpy(S.h_rec.get(), &zero, sizeof(zero));
-        std::memcpy(S.h_rec.get() + 1, &ezero, sizeof(ezero));
-        std::memcpy(S.h_rec.get() + 2, &szero, sizeof(szero));
-    }
-    HIPCHK(c, hipMemcpyAsync(S.d_rec, S.h_rec.get(), 3 * sizeof(MuRecord), hipMemcpyHostToDevice, st));
+    if ((rc = S.d_free_bits.reserve(c, n_words)) || (rc = S.d_hit_bits.reserve(c, n_words))) return rc;
     if (n_rays > 0) {
-        HIPCHK(c, hipMemcpyAsync(S.d_in, xyz, xyz_bytes, hipMemcpyHostToDevice, st));
-        if (hit) HIPCHK(c, hipMemcpyAsync((uint8_t *)S.d_in.get() + xyz_bytes, hit, (size_t)n_rays, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(S.d_free_bits, 0, n_words * sizeof(unsigned), st));
         HIPCHK(c, hipMemsetAsync(S.d_hit_bits, 0, n_words * sizeof(unsigned), st));
     }
+    if ((rc = map_stage(c, S, xyz, xyz_bytes, hit, hit ? (size_t)n_rays : 0, std::max<size_t>({cap_clear, cap_update_most, 1u}), S.ev_scan[0]))) return rc;
+    const float *const d_xyz = (const float *)S.d_in.get();
+    const uint8_t *const d_hit = hit ? (const uint8_t *)S.d_in.get() + xyz_bytes : nullptr;
+    MapRecords *const d_rec = S.d_rec.get(), *const h_rec = S.h_rec.get();
     const unsigned ray_blocks = (unsigned)std::min<long long>((n_rays + 255) / 256, 2048);
 
     // ---- the rays, then the frees: one hand-over
-    HIPCHK(c, hipEventRecord(S.ev_scan[0], st));
     if (n_rays > 0) {
-        hipLaunchKernelGGL(ms_trace_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, G, O, S.d_free_bits.get(), S.d_hit_bits.get(), d_ms);
+        hipLaunchKernelGGL(ms_trace_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, G, O, S.d_free_bits.get(), S.d_hit_bits.get(), &d_rec->scan);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(S.ev_scan[1], st));
     HIPCHK(c, hipEventRecord(S.ev[0], st));
     if (n_rays > 0) {
         hipLaunchKernelGGL(ms_apply_kernel, dim3(1024), dim3(256), 0, st, G, (const unsigned *)S.d_free_bits.get(), (const unsigned *)S.d_hit_bits.get(), c->d_counts.get(), thr,
-                           miss, c->d_occ.get(), S.d_list.get(), cap_clear, d_ms, d_mc);
+                           miss, c->d_occ.get(), S.d_list.get(), cap_clear, &d_rec->scan, &d_rec->list);
         HIPCHK(c, hipGetLastError());
     }
-    if ((rc = hand_over(c, S, S.ev[1], 3))) return rc;
-    McRecord R;
-    MsRecord RS;
-    std::memcpy(&R, S.h_rec.get(), sizeof(R));
-    std::memcpy(&RS, S.h_rec.get() + 2, sizeof(RS));
+    if ((rc = map_hand_over(c, S, S.ev[1], "scan", false))) return rc;
+    const MapListRecord R = h_rec->list;
+    const MsRecord RS = h_rec->scan;
     info.trace_ms = mu_event_ms(S.ev_scan[0], S.ev_scan[1]);
     info.n_rays_skipped = (long long)RS.n_skipped;
     info.n_hits = (long long)RS.n_hits;
@@ -273,27 +224,24 @@ int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8
     const unsigned long long n_clear_points = (unsigned long long)miss * RS.n_free;          // what isdf_clear_pointcloud would have been given
     info.clear.n_points = (long long)n_clear_points;
     info.clear.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
-    info.clear.n_cleared_voxels = R.n_cleared;
-    info.clear.n_points_ignored = (long long)R.ignored;
-    if (R.n_cleared > 0) {
+    info.clear.n_cleared_voxels = R.n;
+    info.clear.n_points_ignored = (long long)R.tally;
+    if (R.n > 0) {
         // from here on the occupancy has moved: a failure must not leave products behind that describe the old map
-        const unsigned cap = (unsigned)std::min<unsigned long long>({(unsigned long long)P.clear.max_cleared_voxels, n_clear_points, n_vox, 0x7FFFFFFFull});
-        rc = mc_refresh_products(c, S, P.clear, R, cap, false, info.clear);
+        rc = mc_refresh_products(c, S, P.clear, R, map_list_cap(P.clear.max_cleared_voxels, n_clear_points, n_vox), false, info.clear);
         if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
     }
 
-    // ---- the hits, on the map the clear left
+    // ---- the hits, on the map the clear left: the list record empty again, second hand-over
     info.update.n_points = info.n_hits;
-    const unsigned cap_update = (unsigned)std::min<unsigned long long>({(unsigned long long)P.update.max_new_voxels, RS.n_hits, n_vox, 0x7FFFFFFFull});
-    MuRecord zero{};
-    for (int a = 0; a < 3; a++) { zero.lo[a] = 0x7FFFFFFF; zero.hi[a] = -1; }
-    *S.h_rec.get() = zero;
+    const unsigned cap_update = map_list_cap(P.update.max_new_voxels, RS.n_hits, n_vox);
+    h_rec->list = map_records_empty().list;
     {
-        hipError_t e = hipMemcpyAsync(S.d_rec, S.h_rec.get(), sizeof(MuRecord), hipMemcpyHostToDevice, st);
+        hipError_t e = hipMemcpyAsync(&d_rec->list, &h_rec->list, sizeof(MapListRecord), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipEventRecord(S.ev[0], st);
         if (e == hipSuccess && RS.n_hits > 0) {
             hipLaunchKernelGGL(ms_hits_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, G, c->d_counts.get(), thr, c->d_occ.get(),
-                               (const float *)c->d_esdf.get(), S.d_list.get(), cap_update, S.d_rec.get());
+                               (const float *)c->d_esdf.get(), S.d_list.get(), cap_update, &d_rec->list);
             e = hipGetLastError();
         }
         if (e != hipSuccess) {
@@ -302,11 +250,11 @@ int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8
             return ISDF_ERR_HIP;
         }
     }
-    if ((rc = hand_over(c, S, S.ev[1], 1))) return rc;
-    const MuRecord RU = *S.h_rec.get();
+    if ((rc = map_hand_over(c, S, S.ev[1], "scan", false))) return rc;
+    const MapListRecord RU = h_rec->list;
     info.update.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
-    info.update.n_new_voxels = RU.n_new;
-    if (RU.n_new > 0) {
+    info.update.n_new_voxels = RU.n;
+    if (RU.n > 0) {
         rc = mu_refresh_products(c, S, P.update, RU, cap_update, false, info.update);
         if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
     }
@@ -319,10 +267,9 @@ int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8
 extern "C" int isdf_integrate_scan(isdf_ctx *c, const double origin[3], const float *xyz, const uint8_t *hit, long long n_rays, const isdf_map_scan_params *params,
                                    isdf_map_scan_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    if (!origin || n_rays < 0 || (n_rays > 0 && !xyz)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad scan arguments");
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "integrating a scan in place is not offered on a multi-device ctx");
-    if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "integrating a scan needs an occupancy grid");
-    if (!c->d_counts) return isdf_fail(c, ISDF_ERR_STATE, "no kept point counts: the map did not come from isdf_set_pointcloud, or isdf_update_voxels / isdf_clear_voxels changed it since");
+    if (!origin) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "integrating a scan: null origin");
+    const int rc = map_change_ready(c, "integrating a scan", xyz, n_rays, true);
+    if (rc) return rc;
     isdf_map_scan_params P;
     isdf_map_scan_params_default(&P);
     if (params) P = *params;

@@ -11,11 +11,12 @@
 // Both reduce in the wavefront, then through LDS, and issue one set of global atomics per workgroup into one 64-byte record.  The
 // destination is a second buffer that then changes places with the ctx's own: no overlap of source and destination, no copy back.
 // Everything else is existing code: isdf_generate_esdf on the shifted occupancy, the whole inflated bit map, the boxed
-// configuration-space kernel over the bands (map_shift_host.hpp), the pack / scatter path into the A*'s host copy.
+// configuration-space kernel over the bands (map_shift_host.hpp), the pack / scatter path into the A*'s host copy - the shared steps
+// of map_change.hpp.
 #include "isdf_ctx.hpp"
 #include "frontend_dev.hpp"
 #include "map_shift_host.hpp"
-#include "map_update_state.hpp"
+#include "map_change.hpp"
 #include "swept_field.hpp"
 #include <algorithm>
 #include <chrono>
@@ -117,13 +118,6 @@ namespace {
 
 typedef std::chrono::steady_clock clk;
 
-int shift_ready(isdf_ctx *c) {
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "shifting the map in place is not offered on a multi-device ctx");
-    if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "shifting the map needs an occupancy grid");
-    if (!c->d_counts) return isdf_fail(c, ISDF_ERR_STATE, "no kept point counts: the map did not come from isdf_set_pointcloud, or isdf_update_voxels / isdf_clear_voxels changed it since");
-    return ISDF_OK;
-}
-
 int shift_params(isdf_ctx *c, const isdf_map_shift_params *params, isdf_map_shift_params &P) {
     isdf_map_shift_params_default(&P);
     if (params) P = *params;
@@ -137,10 +131,7 @@ unsigned grid_blocks(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 2
 int shift_refresh(isdf_ctx *c, MapUpdateState &S, bool full, const MuBox *boxes, int n_boxes, bool watch, isdf_map_shift_info &info) {
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
-    const int dims[3] = {G.X, G.Y, G.Z};
-    const size_t n_vox = (size_t)G.X * G.Y * G.Z;
     isdf_ctx::FrontEnd &fe = c->fe;
-    const size_t nw = 4 * (size_t)((fe.xk * fe.yk + 127) / 128);
     int rc;
 
     // ---- ESDF: the whole-map transform on the shifted occupancy
@@ -149,57 +140,22 @@ int shift_refresh(isdf_ctx *c, MapUpdateState &S, bool full, const MuBox *boxes,
     HIPCHK(c, hipEventRecord(S.ev[3], st));
 
     // ---- front end: the inflated map whole; of the (translated) table the bands, or all of it
-    bool patch = false;
-    size_t pack_total = 0, pack_at[6] = {0, 0, 0, 0, 0, 0};
+    MapFrontend F;
     HIPCHK(c, hipEventRecord(S.ev[4], st));
-    if (fe.built && full) {
-        if ((rc = isdf_frontend_refresh_map(c, nullptr))) return rc;
-        if (fe.d_cspace) info.cspace_voxels = (long long)n_vox;
-    } else if (fe.built) {
-        if ((rc = isdf_frontend_map_bits(c))) return rc;
-        if (fe.d_cspace) {
-            info.n_boxes = n_boxes;
-            for (int b = 0; b < n_boxes; b++) {
-                size_t words = 0;
-                long long vox = 0;
-                pack_at[b] = pack_total;
-                if ((rc = mu_frontend_box_launch(c, S, boxes[b], boxes[b], &patch, &words, &vox, pack_total))) return rc;
-                pack_total += words;
-                info.cspace_voxels += vox;
-            }
-        }
-    }
-    HIPCHK(c, hipEventRecord(S.ev[5], st));
-    if (patch) HIPCHK(c, hipMemcpyAsync(S.h_pack.get(), S.d_pack, pack_total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (fe.built && !full && (rc = isdf_frontend_map_bits(c))) return rc;
+    if ((rc = map_frontend_launch(c, S, true, full, boxes, boxes, fe.d_cspace ? n_boxes : 0, F, false))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
-    if (patch) {                        // the A*'s copy: translated in place by the host form's own function, then the bands
+    if (F.patch) {                      // the A*'s copy: translated in place by the host form's own function, then the bands
         const int32_t d32[3] = {G.X, G.Y, G.Z};
-        msh_shift_grid(fe.h_cspace, nw * sizeof(uint32_t), d32, info.shift, fe.h_cspace);
-        for (int b = 0; b < n_boxes; b++) mu_scatter_box(fe.h_cspace, dims, nw, boxes[b], S.h_pack.get() + pack_at[b]);
-        info.host_table_patched = 1;
+        msh_shift_grid(fe.h_cspace, 4 * (size_t)((fe.xk * fe.yk + 127) / 128) * sizeof(uint32_t), d32, info.shift, fe.h_cspace);
     }
+    map_frontend_finish(c, S, F);
+    info.n_boxes = F.n_boxes; info.cspace_voxels = F.cspace_voxels; info.host_table_patched = F.host_table_patched; info.frontend_ms = F.ms;
     info.translate_ms = mu_event_ms(S.ev[0], S.ev[1]);
     info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
-    info.frontend_ms = mu_event_ms(S.ev[4], S.ev[5]);
     // the kept clearance report: the trajectory is in world coordinates, so it is checked against the whole new map again, as the
-    // clear does, and stays armed under the new epoch.  A failing check drops the report and fails the shift as a whole.
-    if (watch) {
-        const long long folded = c->tck->w.last.updates_folded;
-        isdf_traj_check_info now;
-        if ((rc = traj_check_rerun_kept(c, &now))) {
-            const std::string err = c->err;
-            (void)hipStreamSynchronize(st);
-            traj_check_drop_report(c);
-            c->err = err;
-            return rc;
-        }
-        isdf_traj_watch_info &L = c->tck->w.last;
-        L.updates_folded = folded + 1;
-        L.path = 2;
-        L.select_ms = now.select_ms; L.field_ms = now.field_ms; L.reduce_ms = now.reduce_ms;
-        info.watch_rechecked = 1;
-    }
-    return ISDF_OK;
+    // clear does, and stays armed under the new epoch
+    return map_watch_recheck(c, watch, &info.watch_rechecked);
 }
 
 int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, isdf_map_shift_info *info_out) {
@@ -215,15 +171,14 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     double nb0[3], nb1[3];
     if (!msh_shift_geometry(G.bmin, G.bmax, G.res, dims, s, nb0, nb1))
         return isdf_fail(c, ISDF_ERR_INVALID_ARG, "map shift: the shifted box does not give the map's grid dimensions again (isdf_shift_geometry_host)");
-    HIPCHK(c, hipSetDevice(c->device));
     MapUpdateState *Sp;
-    { const int rc0 = mu_state(c, &Sp); if (rc0) return rc0; }
+    int rc = map_begin(c, &Sp);
+    if (rc) return rc;
     MapUpdateState &S = *Sp;
     const hipStream_t st = c->stream;
     isdf_ctx::FrontEnd &fe = c->fe;
     const size_t n_vox = (size_t)G.X * G.Y * G.Z, n_occ = (n_vox + 3) & ~(size_t)3;
     const size_t nw = 4 * (size_t)((fe.xk * fe.yk + 127) / 128);
-    int rc;
 
     // ---- what the host knows before anything runs: the bands, and the path but for an empty map
     MshGeom g{G.X, G.Y, G.Z, 0, 0, 0};
@@ -246,13 +201,10 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     if ((rc = S.d_shift_counts.reserve(c, n_vox)) || (rc = S.d_shift_occ.reserve(c, n_occ))) return rc;
     if (table && (rc = S.d_shift_cspace.reserve(c, n_vox * nw))) return rc;
     if (table && fe.h_cspace_valid && ((rc = S.d_pack.reserve(c, (size_t)band_voxels * nw / 4)) || (rc = S.h_pack.reserve(c, (size_t)band_voxels * nw)))) return rc;
-    if ((rc = S.d_rec.reserve(c, 1)) || (rc = S.h_rec.reserve(c, 1))) return rc;
-    std::memset(S.h_rec.get(), 0, sizeof(MuRecord));
-    HIPCHK(c, hipMemcpyAsync(S.d_rec, S.h_rec.get(), sizeof(MuRecord), hipMemcpyHostToDevice, st));
-    MshRecord *const d_rec = (MshRecord *)S.d_rec.get();
+    if ((rc = map_stage(c, S, nullptr, 0, nullptr, 0, 0, S.ev[0]))) return rc;
+    MshRecord *const d_rec = &S.d_rec.get()->shift;
 
     // ---- translate into the second buffers
-    HIPCHK(c, hipEventRecord(S.ev[0], st));
     hipLaunchKernelGGL((msh_translate_kernel<unsigned, true>), dim3(grid_blocks(n_vox)), dim3(256), 0, st, (const unsigned *)c->d_counts.get(), S.d_shift_counts.get(), g, 1, d_rec);
     hipLaunchKernelGGL(msh_translate_occ_kernel, dim3(grid_blocks(n_occ / 4)), dim3(256), 0, st, (const uint8_t *)c->d_occ.get(), (unsigned *)S.d_shift_occ.get(), g, d_rec);
     if (table)
@@ -269,19 +221,10 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     G.occ = c->d_occ;
     for (int a = 0; a < 3; a++) { G.bmin[a] = info.bmin_new[a] = nb0[a]; G.bmax[a] = nb1[a]; }
     c->grid_epoch++;                    // voxel indices changed their meaning
-    c->bits_dirty = true; c->bricks_stale = true;
-    if (fe.field_valid) { fe.field_valid = false; fe.field_reachable = false; info.field_dropped = 1; }
-    {
-        hipError_t e = hipMemcpyAsync(S.h_rec.get(), S.d_rec, sizeof(MuRecord), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            c->err = std::string("map shift hand-over: ") + hipGetErrorString(e);
-            mu_drop_derived(c, false);
-            return ISDF_ERR_HIP;
-        }
-    }
-    MshRecord R;
-    std::memcpy(&R, S.h_rec.get(), sizeof(R));
+    c->bricks_stale = true;
+    info.field_dropped = map_changed(c, false);
+    if ((rc = map_hand_over(c, S, nullptr, "map shift", false))) return rc;
+    const MshRecord R = S.h_rec.get()->shift;
     info.voxels_entered = msh_voxels_entered(dims, s);
     info.occupied_left = (long long)R.occupied_left;
     info.counts_left = (long long)R.counts_left;
@@ -299,7 +242,7 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
 extern "C" int isdf_shift_map(isdf_ctx *c, const int32_t shift_ijk[3], const isdf_map_shift_params *params, isdf_map_shift_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (!shift_ijk) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null shift");
-    int rc = shift_ready(c);
+    int rc = map_change_ready(c, "shifting the map", nullptr, 0, true);
     if (rc) return rc;
     isdf_map_shift_params P;
     if ((rc = shift_params(c, params, P))) return rc;
@@ -311,7 +254,7 @@ extern "C" int isdf_map_follow(isdf_ctx *c, const double centre_xyz[3], int min_
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (shift_out) shift_out[0] = shift_out[1] = shift_out[2] = 0;
     if (!centre_xyz || min_shift < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "map follow: null centre or negative min_shift");
-    int rc = shift_ready(c);
+    int rc = map_change_ready(c, "shifting the map", nullptr, 0, true);
     if (rc) return rc;
     isdf_map_shift_params P;
     if ((rc = shift_params(c, params, P))) return rc;

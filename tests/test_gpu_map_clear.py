@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import test_gpu_map_update as mu
-from test_gpu_map_update import BMAX, BMIN, DIMS, RES, SIDE, THR, _counts, _engine, _grid_engine, _in_cells, _products, _same
+from test_gpu_map_update import BMAX, BMIN, DIMS, RES, SIDE, THR, _counts, _engine, _grid_engine, _in_cells, _live, _products, _same
 
 pytestmark = pytest.mark.gpu
 
@@ -389,3 +389,19 @@ def test_status_codes(pkg, product_lib):
         with pytest.raises(pkg.IsdfError) as err:
             call()
         assert err.value.code == capi.ISDF_ERR_UNSUPPORTED
+
+
+# ---- nothing is allocated after the first call of a size --------------------------------------------------------------------------
+def test_a_second_clear_of_the_same_size_allocates_nothing(pkg, product_lib):
+    old, removed, _, _, _ = _scene()
+    eng = _engine(pkg, old, host_table=True)
+    assert eng.clear_pointcloud(removed, **INCR).path == 1
+    first = _products(pkg, eng, host_table=True)
+    # the same map again in the same ctx, whose clear scratch stays; then the same clear
+    assert eng.set_pointcloud(old, RES, THR, BMIN, BMAX) == DIMS
+    mu._derive(pkg, eng, host_table=True)
+    before = _live(product_lib)
+    info = eng.clear_pointcloud(removed, **INCR)
+    assert _live(product_lib) == before
+    assert info.path == 1 and info.n_cleared_voxels > 0 and info.host_table_patched == 1
+    _same(_products(pkg, eng, host_table=True), first)

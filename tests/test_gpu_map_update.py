@@ -2,6 +2,7 @@
 build in a second, fresh ctx on the concatenated cloud - never against the update path itself.  Every comparison is == on bytes.
 Shapes: 24 x 20 x 70 voxels at 0.5 m (Z crosses one 64-lane block and is a multiple of neither 32 nor 64), explicit boundaries,
 sta_threshold 2, a few hundred seeded points, a box robot with kernel_size 5 and 3 x 3 attitudes."""
+import ctypes as C
 import functools
 
 import numpy as np
@@ -433,3 +434,25 @@ def test_cspace_of_other_robot_kinds(pkg, product_lib, robot):
     assert fe is None or (want[..., 4:].any() and (want[..., 5] >> 9 == 0).all() and not want[..., 6:].any())      # bits 169 .. 255 stay clear
     assert not np.array_equal(want, _engine(pkg, old, shape=shape, fe=fe).frontend_cspace()[0])                    # (the update had something to change)
     assert np.array_equal(eng.frontend_map_kernel(), fresh.frontend_map_kernel())
+
+
+# ---- 9. nothing is allocated after the first call of a size -----------------------------------------------------------------------
+def _live(lib):
+    out = (C.c_longlong * 2)()
+    lib.isdf_debug_live_bytes(out)
+    return list(out)
+
+
+def test_a_second_update_of_the_same_size_allocates_nothing(pkg, product_lib):
+    old, a, _ = _clouds()
+    eng = _engine(pkg, old, host_table=True)
+    assert eng.update_pointcloud(a, **INCR).path == 1
+    first = _products(pkg, eng, host_table=True)
+    # the same map again in the same ctx, whose update scratch stays; then the same update
+    assert eng.set_pointcloud(old, RES, THR, BMIN, BMAX) == DIMS
+    _derive(pkg, eng, host_table=True)
+    before = _live(product_lib)
+    info = eng.update_pointcloud(a, **INCR)
+    assert _live(product_lib) == before
+    assert info.path == 1 and info.n_new_voxels > 0 and info.host_table_patched == 1
+    _same(_products(pkg, eng, host_table=True), first)
