@@ -78,18 +78,13 @@ int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms);
 // its first step alone, for the map shift's incremental path: the whole inflated map again on the ctx's stream (a built front end)
 int isdf_frontend_map_bits(isdf_ctx *c);
 
-// frontend_field.hip, for the map update: the cost-to-go field repaired after voxels closed (isdf_frontend_field_set_repair, mode 1).
-// ..._wanted: mode 1 and a valid field that is a fixed point (not status 2).  ..._begin enqueues the mark over the box lo .. hi
-// (null: the whole grid), the reset and the first list on the ctx's stream, after the configuration-space refresh; the caller
-// synchronises the stream; ..._end runs the rounds.  *repaired = 0: a bit had opened, the field stays dropped.
-bool isdf_field_repair_wanted(const isdf_ctx *c);
-int isdf_field_repair_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start);
-int isdf_field_repair_end(isdf_ctx *c, hipEvent_t ev_start, hipEvent_t ev_end, int *repaired);
-
-// frontend_field.hip, for the map clear: the field lowered in place after voxels opened (isdf_frontend_field_set_reopen, mode 1).  The
-// same three steps: ..._wanted: mode 1 and a valid field that is a fixed point; ..._begin enqueues the opening mark over the box
-// lo .. hi (null: the whole grid) and the first list; the caller synchronises; ..._end, given the same box, runs the rounds and the counts.
-// *reopened = 0: a bit had closed, the field stays dropped.
-bool isdf_field_reopen_wanted(const isdf_ctx *c);
-int isdf_field_reopen_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start);
-int isdf_field_reopen_end(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *reopened);
+// frontend_field.hip, for the in-place map changes: the cost-to-go field following a change in place - repaired after voxels closed
+// (isdf_frontend_field_set_repair, mode 1) or lowered after voxels opened (isdf_frontend_field_set_reopen, mode 1).
+// ..._wanted: the direction's mode is 1 and the field is valid and a fixed point (not status 2).  ..._begin enqueues the direction's
+// mark over the box lo .. hi (null: the whole grid), closing: the reset, and the first list on the ctx's stream, after the
+// configuration-space refresh; the caller synchronises the stream; ..._end, given the same box, runs the rounds and the counts.
+// *kept = 0: a bit had moved against the direction, the field stays dropped.
+namespace isdf { enum class FfChange { Closing, Opening }; }
+bool isdf_field_change_wanted(const isdf_ctx *c, isdf::FfChange dir);
+int isdf_field_change_begin(isdf_ctx *c, isdf::FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start);
+int isdf_field_change_end(isdf_ctx *c, isdf::FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *kept);

@@ -24,27 +24,29 @@
 // paths, and is flagged by the writer, so it runs again next round with the new value in sight: the fixed point does not depend on which
 // it saw.  Only counts of events (free voxels, bricks seen) go through integer atomics; nothing is decided by their order.
 //   ff_paths_kernel    one lane per start: the steepest walk down the field with the A*'s attitude bookkeeping (below).
-// The field REPAIRED after a map update that closed voxels (occupancy only grows; DESIGN 4.6.2, isdf_frontend_field_set_repair):
-//   ff_repair_mark_kernel   one wavefront per 64 consecutive z of a column of the changed box: the new free ballot against the kept word;
-//                           a closed lane folds its finite old d into tau (an integer atomicMin on the bit pattern: non-negative
-//                           doubles order like their bits) and takes +inf; the new word is written; closed voxels are counted;
-//   ff_repair_reset_kernel  one workgroup per brick: +inf wherever tau <= d < +inf (tau read from device memory), the brick flagged
-//                           when it reset a voxel;
-// then ff_compact_kernel and the rounds of the build.  Every d < tau is kept: the chain of minimising neighbours from such a voxel to
-// the goal passes only voxels with d < tau, none of them closed, and the new graph is a subgraph of the old.  From the kept values
-// every intermediate value is again a real path's length, so the fixed point has the bytes of a build on the new map.
-// The field LOWERED after a map clear that opened voxels (occupancy only shrinks; DESIGN 4.6.3, isdf_frontend_field_set_reopen):
-//   ff_reopen_mark_kernel   the same work layout as ff_repair_mark_kernel, the comparison turned round: the opened bits (new and not
-//                           kept) are counted and kept in a word per wavefront, the new word is written, the brick is flagged, a
-//                           closed bit raises a record word (outside the premise); the lane on the goal voxel, when it opened,
-//                           stores d = 0;
-//   ff_reopen_count_kernel  after the rounds, over the same box: the opened voxels that hold a finite d;
-// between them ff_compact_kernel and the rounds of the build.  Nothing is reset: the old graph is a subgraph of the new, so every old
-// value is a path's length that still exists - an upper bound of the new least fixed point d* -, relaxation keeps it one, and a fixed
-// point >= d* with d[goal] = 0 is d* (in Dijkstra order of d*, v's predecessor u holds d*[u], so d[v] <= fl(d*[u] + w) = d*[v]).
-// A brick without an opened voxel or a lowered halo voxel satisfies its equations as before.
+// The field CHANGED IN PLACE after the map changed in ONE direction (FfChange): voxels only closed (a map update; DESIGN 4.6.2,
+// isdf_frontend_field_set_repair) or only opened (a map clear; DESIGN 4.6.3, isdf_frontend_field_set_reopen).  Both directions are
+// mark, seed, relax: isdf_field_change_begin / _end, one FfRecord.
+//   ff_mark_kernel<dir>     one wavefront per 64 consecutive z of a column of the changed box: the new free ballot against the kept
+//                           word, the new word written, the changed bits counted, a bit that moved against the direction raises
+//                           the record's premise word (the host drops the field).  Closing: a closed lane folds its finite old d
+//                           into tau (an integer atomicMin on the bit pattern: non-negative doubles order like their bits) and
+//                           takes +inf.  Opening: the opened bits are kept in a word per wavefront, the brick is flagged, the lane
+//                           on the goal voxel, when it opened, stores d = 0;
+//   ff_repair_reset_kernel  closing only, one workgroup per brick: +inf wherever tau <= d < +inf (tau read from device memory), the
+//                           brick flagged when it reset a voxel;
+// then ff_compact_kernel and the rounds of the build from the flagged bricks, the count of reached voxels, and
+//   ff_reopen_count_kernel  opening only, over the same box: the opened voxels that hold a finite d.
+// Closing keeps every d < tau: the chain of minimising neighbours from such a voxel to the goal passes only voxels with d < tau, none
+// of them closed, and the new graph is a subgraph of the old.  From the kept values every intermediate value is again a real path's
+// length, so the fixed point has the bytes of a build on the new map.
+// Opening resets nothing: the old graph is a subgraph of the new, so every old value is a path's length that still exists - an upper
+// bound of the new least fixed point d* -, relaxation keeps it one, and a fixed point >= d* with d[goal] = 0 is d* (in Dijkstra order
+// of d*, v's predecessor u holds d*[u], so d[v] <= fl(d*[u] + w) = d*[v]).  A brick without an opened voxel or a lowered halo voxel
+// satisfies its equations as before.
 // Compiled with -ffp-contract=off like frontend.hip (cell indices and cube centres round like the A*'s).
 #include "isdf_ctx.hpp"
+#include "frontend_dev.hpp"
 #include "frontend_field_host.hpp"
 #include <cmath>
 #include <cstring>
@@ -71,6 +73,19 @@ __device__ __forceinline__ void ff_store(double *p, double v) {
     __hip_atomic_store((unsigned long long *)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the free bits of a wavefront whose lanes hold consecutive z of one column: lane's voxel v is free when any attitude bit of its word
+// is set; a lane past the end of the column (valid = false) gives 0
+__device__ __forceinline__ unsigned long long ff_free_ballot(const FfDims &D, const unsigned *__restrict__ cspace, size_t v, bool valid) {
+    bool fr = false;
+    if (valid) {
+        const unsigned *m = cspace + v * D.nw;
+        unsigned any = 0;
+        for (int w = 0; w < D.nw; w++) any |= m[w];
+        fr = any != 0u;
+    }
+    return __ballot(fr);
+}
+
 __global__ __launch_bounds__(256) void ff_init_kernel(FfDims D, const unsigned *__restrict__ cspace, unsigned long long *__restrict__ fm,
                                                        double *__restrict__ d, int *__restrict__ list, unsigned long long *__restrict__ cnt) {
     const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -80,14 +95,10 @@ __global__ __launch_bounds__(256) void ff_init_kernel(FfDims D, const unsigned *
     const int zb = (int)(wv % D.zblocks);
     const long long xy = wv / D.zblocks;
     const int z = (zb << 6) + lane;
-    bool fr = false;
     const long long v = xy * D.Z + z;
+    const unsigned long long bits = ff_free_ballot(D, cspace, (size_t)v, z < D.Z);
     if (z < D.Z) {
-        const unsigned *m = cspace + (size_t)v * D.nw;
-        unsigned any = 0;
-        for (int w = 0; w < D.nw; w++) any |= m[w];
-        fr = any != 0u;
-        const bool is_goal = fr && v == D.goal;
+        const bool is_goal = ((bits >> lane) & 1ull) && v == D.goal;
         d[v] = is_goal ? 0.0 : __longlong_as_double(0x7FF0000000000000ll);
         if (is_goal) {
             const int x = (int)(xy / D.Y), y = (int)(xy % D.Y);
@@ -95,7 +106,6 @@ __global__ __launch_bounds__(256) void ff_init_kernel(FfDims D, const unsigned *
             cnt[FF_CNT_ACTIVE] = 1ull;
         }
     }
-    const unsigned long long bits = __ballot(fr);
     if (lane == 0) {
         fm[wv] = bits;
         if (bits) atomicAdd(cnt + FF_CNT_FREE, (unsigned long long)__popcll(bits));
@@ -222,52 +232,69 @@ __global__ __launch_bounds__(256) void ff_count_kernel(const double *__restrict_
     if ((threadIdx.x & 63) == 0 && k) atomicAdd(cnt + FF_CNT_REACHED, k);
 }
 
-// the repair's record: [tau's bits | closed | closed with a finite d | a bit opened | reset by the threshold | bricks seeded]
-constexpr int FF_REP_TAU = 0, FF_REP_CLOSED = 1, FF_REP_CLOSED_REACHED = 2, FF_REP_OPENED = 3, FF_REP_RESET = 4, FF_REP_SEEDED = 5, FF_REP_WORDS = 8;
 constexpr unsigned long long FF_INF_BITS = 0x7FF0000000000000ull;
 
-// columns x in [x0, x0 + ex), y in [y0, y0 + ey), 64-voxel z blocks zb in [zb0, zb0 + ezb): the changed box, whole columns in z
-__global__ __launch_bounds__(256) void ff_repair_mark_kernel(FfDims D, int x0, int y0, int zb0, int ex, int ey, int ezb, const unsigned *__restrict__ cspace,
-                                                              unsigned long long *__restrict__ fm, double *__restrict__ d, unsigned long long *__restrict__ rep) {
-    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const long long n_wv = (long long)ex * ey * ezb;
-    if (wv >= n_wv) return;
+// The changed box as its kernels take it, whole 64-voxel blocks in z: columns x in [x0, x0 + ex), y in [y0, y0 + ey), blocks zb in
+// [zb0, zb0 + ezb); one wavefront per block of a column.  ff_box_column: this wavefront's index among the box's and its block (false: past
+// the end).
+struct FfBox { int x0, y0, zb0, ex, ey, ezb; };
+struct FfColumn { long long wv; int x, y, zb; };
+__device__ __forceinline__ bool ff_box_column(const FfBox &B, FfColumn &C) {
+    C.wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (C.wv >= (long long)B.ex * B.ey * B.ezb) return false;
+    C.zb = B.zb0 + (int)(C.wv % B.ezb);
+    const long long xy = C.wv / B.ezb;
+    C.y = B.y0 + (int)(xy % B.ey); C.x = B.x0 + (int)(xy / B.ey);
+    return true;
+}
+
+// The mark of either direction.  flags, open: opening only (open[wv]: the opened bits of this wavefront's word, for
+// ff_reopen_count_kernel; written by every wavefront of the box: nothing stale is read).
+template <FfChange DIR>
+__global__ __launch_bounds__(256) void ff_mark_kernel(FfDims D, FfBox B, const unsigned *__restrict__ cspace, unsigned long long *__restrict__ fm, double *__restrict__ d,
+                                                       unsigned *__restrict__ flags, unsigned long long *__restrict__ open, FfRecord *__restrict__ rec) {
+    constexpr bool closing = DIR == FfChange::Closing;
+    FfColumn C;
+    if (!ff_box_column(B, C)) return;
     const int lane = threadIdx.x & 63;
-    const int zb = zb0 + (int)(wv % ezb);
-    const long long xy = wv / ezb;
-    const int y = y0 + (int)(xy % ey), x = x0 + (int)(xy / ey);
-    const int z = (zb << 6) + lane;
-    const size_t col = (size_t)x * D.Y + y;
+    const int z = (C.zb << 6) + lane;
+    const size_t col = (size_t)C.x * D.Y + C.y;
     const size_t v = col * D.Z + z;
-    bool fr = false;
-    if (z < D.Z) {
-        const unsigned *m = cspace + v * D.nw;
-        unsigned any = 0;
-        for (int w = 0; w < D.nw; w++) any |= m[w];
-        fr = any != 0u;
+    const unsigned long long now = ff_free_ballot(D, cspace, v, z < D.Z);
+    const unsigned long long old = fm[col * D.zblocks + C.zb];
+    const unsigned long long changed = closing ? old & ~now : now & ~old, against = closing ? now & ~old : old & ~now;
+    const bool mine = (changed >> lane) & 1ull;            // (a set bit of the kept or of the new word: z < D.Z)
+    unsigned long long hit = 0ull;
+    if (closing) {
+        bool reached = false;
+        if (mine) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(d[v]);
+            reached = bits < FF_INF_BITS;                  // d is never negative and never NaN
+            if (reached) { atomicMin(&rec->tau_bits, bits); d[v] = __longlong_as_double((long long)FF_INF_BITS); }
+        }
+        hit = __ballot(reached);
+    } else {
+        if (mine && (long long)v == D.goal) {
+            d[v] = 0.0;                                    // the goal cell had not been free: the field was all +inf
+            rec->goal_opened = 1ull;
+        }
     }
-    const unsigned long long now = __ballot(fr);
-    const unsigned long long old = fm[col * D.zblocks + zb];
-    const unsigned long long closed = old & ~now;
-    bool reached = false;
-    if ((closed >> lane) & 1ull) {                         // (a set bit of the kept word: z < D.Z)
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(d[v]);
-        reached = bits < FF_INF_BITS;                      // d is never negative and never NaN
-        if (reached) { atomicMin(rep + FF_REP_TAU, bits); d[v] = __longlong_as_double((long long)FF_INF_BITS); }
+    if (lane != 0) return;
+    if (!closing) open[C.wv] = changed;
+    if (now == old) return;
+    fm[col * D.zblocks + C.zb] = now;
+    if (changed) {
+        atomicAdd(&rec->changed, (unsigned long long)__popcll(changed));
+        if (!closing) flags[((C.x / FF_BX) * D.nby + C.y / FF_BY) * D.nbz + C.zb] = 1u;
     }
-    const unsigned long long hit = __ballot(reached);
-    if (lane == 0 && now != old) {
-        fm[col * D.zblocks + zb] = now;
-        if (closed) atomicAdd(rep + FF_REP_CLOSED, (unsigned long long)__popcll(closed));
-        if (hit) atomicAdd(rep + FF_REP_CLOSED_REACHED, (unsigned long long)__popcll(hit));
-        if (now & ~old) rep[FF_REP_OPENED] = 1ull;        // outside the premise: the host drops the field
-    }
+    if (hit) atomicAdd(&rec->changed_reached, (unsigned long long)__popcll(hit));
+    if (against) rec->premise_violated = 1ull;            // outside the premise: the host drops the field
 }
 
 // one workgroup per brick, the lanes on the voxels as in ff_relax_kernel
-__global__ __launch_bounds__(256) void ff_repair_reset_kernel(FfDims D, double *__restrict__ d, unsigned *__restrict__ flags, unsigned long long *__restrict__ rep) {
+__global__ __launch_bounds__(256) void ff_repair_reset_kernel(FfDims D, double *__restrict__ d, unsigned *__restrict__ flags, FfRecord *__restrict__ rec) {
     __shared__ unsigned s_n;
-    const unsigned long long tau = rep[FF_REP_TAU];
+    const unsigned long long tau = rec->tau_bits;
     if (tau >= FF_INF_BITS) return;                        // nothing reached has closed (the same word in every thread)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int b = blockIdx.x;
@@ -289,71 +316,24 @@ __global__ __launch_bounds__(256) void ff_repair_reset_kernel(FfDims D, double *
     __syncthreads();
     if (tid == 0 && s_n) {
         flags[b] = 1u;
-        atomicAdd(rep + FF_REP_RESET, (unsigned long long)s_n);
-        atomicAdd(rep + FF_REP_SEEDED, 1ull);
+        atomicAdd(&rec->reset, (unsigned long long)s_n);
+        atomicAdd(&rec->seeded, 1ull);
     }
 }
 
-// the reopen's record, in the repair's buffer: [opened | a bit closed | the goal cell opened | opened with a finite d afterwards]
-constexpr int FF_ROP_OPENED = 0, FF_ROP_CLOSED = 1, FF_ROP_GOAL = 2, FF_ROP_REACHED = 3;
-
-// The opening direction over the same box as ff_repair_mark_kernel, one wavefront per 64 consecutive z of a column.  open[wv]: the
-// opened bits of this wavefront's word, for ff_reopen_count_kernel (written by every wavefront of the box: nothing stale is read).
-__global__ __launch_bounds__(256) void ff_reopen_mark_kernel(FfDims D, int x0, int y0, int zb0, int ex, int ey, int ezb, const unsigned *__restrict__ cspace,
-                                                              unsigned long long *__restrict__ fm, double *__restrict__ d, unsigned *__restrict__ flags,
-                                                              unsigned long long *__restrict__ open, unsigned long long *__restrict__ rep) {
-    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const long long n_wv = (long long)ex * ey * ezb;
-    if (wv >= n_wv) return;
-    const int lane = threadIdx.x & 63;
-    const int zb = zb0 + (int)(wv % ezb);
-    const long long xy = wv / ezb;
-    const int y = y0 + (int)(xy % ey), x = x0 + (int)(xy / ey);
-    const int z = (zb << 6) + lane;
-    const size_t col = (size_t)x * D.Y + y;
-    const size_t v = col * D.Z + z;
-    bool fr = false;
-    if (z < D.Z) {
-        const unsigned *m = cspace + v * D.nw;
-        unsigned any = 0;
-        for (int w = 0; w < D.nw; w++) any |= m[w];
-        fr = any != 0u;
-    }
-    const unsigned long long now = __ballot(fr);
-    const unsigned long long old = fm[col * D.zblocks + zb];
-    const unsigned long long opened = now & ~old;
-    if (((opened >> lane) & 1ull) && (long long)v == D.goal) {               // (a set bit of the new word: z < D.Z)
-        d[v] = 0.0;                                        // the goal cell had not been free: the field was all +inf
-        rep[FF_ROP_GOAL] = 1ull;
-    }
-    if (lane == 0) {
-        open[wv] = opened;
-        if (now != old) {
-            fm[col * D.zblocks + zb] = now;
-            if (opened) {
-                atomicAdd(rep + FF_ROP_OPENED, (unsigned long long)__popcll(opened));
-                flags[((x / FF_BX) * D.nby + y / FF_BY) * D.nbz + zb] = 1u;
-            }
-            if (old & ~now) rep[FF_ROP_CLOSED] = 1ull;    // outside the premise: the host drops the field
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void ff_reopen_count_kernel(FfDims D, int x0, int y0, int zb0, int ex, int ey, int ezb, const double *__restrict__ d,
-                                                               const unsigned long long *__restrict__ open, unsigned long long *__restrict__ rep) {
-    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (wv >= (long long)ex * ey * ezb) return;
-    const unsigned long long opened = open[wv];
+// after the rounds of the opening direction, over the box of its mark
+__global__ __launch_bounds__(256) void ff_reopen_count_kernel(FfDims D, FfBox B, const double *__restrict__ d, const unsigned long long *__restrict__ open,
+                                                               FfRecord *__restrict__ rec) {
+    FfColumn C;
+    if (!ff_box_column(B, C)) return;
+    const unsigned long long opened = open[C.wv];
     if (!opened) return;                                   // (the same word in every lane of the wavefront)
     const int lane = threadIdx.x & 63;
-    const int zb = zb0 + (int)(wv % ezb);
-    const long long xy = wv / ezb;
-    const int y = y0 + (int)(xy % ey), x = x0 + (int)(xy / ey);
     bool reached = false;
     if ((opened >> lane) & 1ull)                           // (an opened bit: z < D.Z)
-        reached = (unsigned long long)__double_as_longlong(d[((size_t)x * D.Y + y) * D.Z + (zb << 6) + lane]) < FF_INF_BITS;
+        reached = (unsigned long long)__double_as_longlong(d[((size_t)C.x * D.Y + C.y) * D.Z + (C.zb << 6) + lane]) < FF_INF_BITS;
     const unsigned long long hit = __ballot(reached);
-    if (lane == 0 && hit) atomicAdd(rep + FF_ROP_REACHED, (unsigned long long)__popcll(hit));
+    if (lane == 0 && hit) atomicAdd(&rec->opened_reached, (unsigned long long)__popcll(hit));
 }
 
 // GridMap3D::isInMap / getGridIndex as isdf_frontend_astar_search restates them (Gridmap3D.cpp:41-69,135-175)
@@ -467,6 +447,13 @@ int ff_ready(isdf_ctx *c) {
     return ISDF_OK;
 }
 
+int ff_field_ready(isdf_ctx *c) {                          // ... and a field to read
+    const int rdy = ff_ready(c);
+    if (rdy != ISDF_OK) return rdy;
+    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
+    return ISDF_OK;
+}
+
 FfMap ff_map(const isdf_ctx *c) {
     FfMap M{};
     M.X = c->grid.X; M.Y = c->grid.Y; M.Z = c->grid.Z; M.res = c->grid.res;
@@ -494,6 +481,11 @@ FfDims ff_dims(const isdf_ctx *c) {
     D.w1 = std::sqrt(1.0); D.w2 = std::sqrt(2.0); D.w3 = std::sqrt(3.0);
     D.goal = -1ll;
     return D;
+}
+
+long long ff_goal_index(const isdf_ctx *c) {               // FfDims::goal of the field's goal cell (fe.field_goal)
+    const int *g = c->fe.field_goal;
+    return g[0] >= 0 ? ((long long)g[0] * c->grid.Y + g[1]) * c->grid.Z + g[2] : -1ll;
 }
 
 // The rounds, shared by the build and the repair: ff_relax_kernel over the list + ff_compact_kernel, one pinned word read per round,
@@ -563,8 +555,8 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     int gi[3] = {-1, -1, -1};
     const FfMap M = ff_map(c);
     const bool goal_in = ff_cell(M, goal_xyz, gi);                                          // outside the map: reachable = 0, as the A* (:244-249)
-    D.goal = goal_in ? ((long long)gi[0] * G.Y + gi[1]) * G.Z + gi[2] : -1ll;
     fe.field_goal[0] = gi[0]; fe.field_goal[1] = gi[1]; fe.field_goal[2] = gi[2];
+    D.goal = ff_goal_index(c);
     const size_t n_cols = (size_t)G.X * G.Y * D.zblocks;
     if (fe.d_field.reserve(c, n_vox) || fe.d_field_free.reserve(c, n_cols) || fe.d_field_list.reserve(c, (size_t)n_bricks) ||
         fe.d_field_flags.reserve(c, 2 * (size_t)n_bricks) || fe.d_field_cnt.reserve(c, FF_CNT_WORDS) || fe.h_field_cnt.reserve(c, FF_CNT_WORDS))
@@ -627,215 +619,156 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     return ISDF_OK;
 }
 
-// ---- the repair after a map update (called by map_update.hip; the rule and its premise: this file's header) -----------------------
-bool isdf_field_repair_wanted(const isdf_ctx *c) {
+// ---- the field following an in-place change of the map (called by map_change.hip; the rules and their premises: this file's header)
+bool isdf_field_change_wanted(const isdf_ctx *c, FfChange dir) {
     const isdf_ctx::FrontEnd &fe = c->fe;
-    return c->field_repair_mode == 1 && fe.built && fe.field_valid && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
-}
-
-// Enqueues, after the configuration-space refresh on the ctx's stream: the mark kernel over the box lo .. hi (null: the whole grid),
-// the reset kernel, ff_compact_kernel and the record's copy to the host.  The caller synchronises the stream, then calls ..._end.
-int isdf_field_repair_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start) {
-    isdf_ctx::FrontEnd &fe = c->fe;
-    const DevGrid &G = c->grid;
-    FfDims D = ff_dims(c);
-    const int n_bricks = D.nbx * D.nby * D.nbz;
-    if (fe.d_field_rep.reserve(c, FF_REP_WORDS) || fe.h_field_rep.reserve(c, 2 * FF_REP_WORDS)) return ISDF_ERR_HIP;
-    const int x0 = lo ? lo[0] : 0, y0 = lo ? lo[1] : 0, zb0 = lo ? lo[2] >> 6 : 0;
-    const int ex = (hi ? hi[0] : G.X - 1) - x0 + 1, ey = (hi ? hi[1] : G.Y - 1) - y0 + 1, ezb = ((hi ? hi[2] : G.Z - 1) >> 6) - zb0 + 1;
-    if (x0 < 0 || y0 < 0 || zb0 < 0 || ex < 1 || ey < 1 || ezb < 1 || x0 + ex > G.X || y0 + ey > G.Y || zb0 + ezb > D.zblocks)
-        return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field repair's box lies outside the grid");
-    unsigned long long *h = fe.h_field_rep.get();          // [the record as it starts | the record as the kernels left it]
-    for (int i = 0; i < 2 * FF_REP_WORDS; i++) h[i] = 0ull;
-    h[FF_REP_TAU] = FF_INF_BITS;
-    unsigned long long *rep = fe.d_field_rep.get(), *cnt = fe.d_field_cnt.get();
-    unsigned *flags = fe.d_field_flags.get();
-    const hipStream_t st = c->stream;
-    HIPCHK(c, hipEventRecord(ev_start, st));
-    HIPCHK(c, hipMemcpyAsync(rep, h, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
-    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
-    const long long n_wv = (long long)ex * ey * ezb;
-    hipLaunchKernelGGL(ff_repair_mark_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, D, x0, y0, zb0, ex, ey, ezb, fe.d_cspace.get(), fe.d_field_free.get(),
-                       fe.d_field.get(), rep);
-    hipLaunchKernelGGL(ff_repair_reset_kernel, dim3((unsigned)n_bricks), dim3(256), 0, st, D, fe.d_field.get(), flags, rep);
-    hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h + FF_REP_WORDS, rep, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    return ISDF_OK;
-}
-
-// After the stream has been synchronised: the rounds from the seeded bricks, the count of reached voxels.  *repaired = 1: the field is
-// valid again (status 2 when the round bound was hit, as after a build); 0: a bit had opened, the field stays dropped.
-int isdf_field_repair_end(isdf_ctx *c, hipEvent_t ev_start, hipEvent_t ev_end, int *repaired) {
-    isdf_ctx::FrontEnd &fe = c->fe;
-    *repaired = 0;
-    const unsigned long long *rep = fe.h_field_rep.get() + FF_REP_WORDS;
-    if (rep[FF_REP_OPENED]) return ISDF_OK;
-    const DevGrid &G = c->grid;
-    FfDims D = ff_dims(c);
-    const hipStream_t st = c->stream;
-    volatile unsigned long long *h = fe.h_field_cnt.get();
-    const long long n_free = fe.field_free_voxels - (long long)rep[FF_REP_CLOSED];
-    long long bound = n_free;
-    if (fe.field_max_rounds > 0 && fe.field_max_rounds < bound) bound = fe.field_max_rounds;
-    FfRounds R;
-    HIPCHK(c, ff_run_rounds(fe, D, (long long)h[FF_CNT_ACTIVE], bound, st, R));
-    hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)G.X * G.Y * G.Z, fe.d_field_cnt.get());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev_end, st));
-    HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), fe.d_field_cnt.get(), FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev_start, ev_end));
-    const bool goal_in = fe.field_goal[0] >= 0;
-    fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
-    fe.field_status = fe.field_reachable ? R.status : 1;
-    fe.field_free_voxels = n_free;
-    fe.field_reached_voxels = (long long)h[FF_CNT_REACHED];
-    fe.field_valid = true;
-    fe.field_repaired = true;
-    isdf_field_repair_info &I = fe.field_repair;
-    I = isdf_field_repair_info{};
-    I.closed_voxels = (int64_t)rep[FF_REP_CLOSED];
-    I.closed_reached = (int64_t)rep[FF_REP_CLOSED_REACHED];
-    const unsigned long long tau_bits = rep[FF_REP_TAU];
-    std::memcpy(&I.tau, &tau_bits, sizeof(double));
-    I.reset_voxels = (int64_t)(rep[FF_REP_RESET] + rep[FF_REP_CLOSED_REACHED]);
-    I.seeded_bricks = (int32_t)rep[FF_REP_SEEDED];
-    I.rounds = (int32_t)R.rounds;
-    I.brick_visits = R.visits;
-    I.free_voxels = n_free;
-    I.reached_voxels = (int64_t)h[FF_CNT_REACHED];
-    I.reachable = fe.field_reachable ? 1 : 0;
-    I.status = fe.field_status;
-    I.device_ms = ms;
-    *repaired = 1;
-    return ISDF_OK;
-}
-
-// ---- the reopen after a map clear (called by map_clear.hip; the rule and its premise: this file's header) -------------------------
-bool isdf_field_reopen_wanted(const isdf_ctx *c) {
-    const isdf_ctx::FrontEnd &fe = c->fe;
-    return c->field_reopen_mode == 1 && fe.built && fe.field_valid && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
+    const int mode = dir == FfChange::Closing ? c->field_repair_mode : c->field_reopen_mode;
+    return mode == 1 && fe.built && fe.field_valid && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
 }
 
 namespace {
 
-// the changed box as the two reopen kernels take it: whole 64-voxel blocks in z
-struct FfBox { int x0, y0, zb0, ex, ey, ezb; };
-FfBox ff_box(const DevGrid &G, const int lo[3], const int hi[3]) {
-    FfBox B;
+// the box lo .. hi (null: the whole grid) as the box kernels take it, or the error
+int ff_box(isdf_ctx *c, FfChange dir, const int lo[3], const int hi[3], FfBox &B) {
+    const DevGrid &G = c->grid;
     B.x0 = lo ? lo[0] : 0; B.y0 = lo ? lo[1] : 0; B.zb0 = lo ? lo[2] >> 6 : 0;
     B.ex = (hi ? hi[0] : G.X - 1) - B.x0 + 1; B.ey = (hi ? hi[1] : G.Y - 1) - B.y0 + 1; B.ezb = ((hi ? hi[2] : G.Z - 1) >> 6) - B.zb0 + 1;
-    return B;
-}
-
-}  // namespace
-
-// Enqueues, after the configuration-space refresh on the ctx's stream: the opening mark over the box lo .. hi (null: the whole grid),
-// ff_compact_kernel and the record's copy to the host.  The caller synchronises the stream, then calls ..._end with the same box.
-int isdf_field_reopen_begin(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start) {
-    isdf_ctx::FrontEnd &fe = c->fe;
-    const DevGrid &G = c->grid;
-    FfDims D = ff_dims(c);
-    const int n_bricks = D.nbx * D.nby * D.nbz;
-    const size_t n_cols = (size_t)G.X * G.Y * D.zblocks;
-    // the record shares the repair's buffers; the opened words are sized for the whole grid at once: no box of a later clear grows them
-    if (fe.d_field_rep.reserve(c, FF_REP_WORDS) || fe.h_field_rep.reserve(c, 2 * FF_REP_WORDS) || fe.d_field_open.reserve(c, n_cols)) return ISDF_ERR_HIP;
-    const FfBox B = ff_box(G, lo, hi);
-    if (B.x0 < 0 || B.y0 < 0 || B.zb0 < 0 || B.ex < 1 || B.ey < 1 || B.ezb < 1 || B.x0 + B.ex > G.X || B.y0 + B.ey > G.Y || B.zb0 + B.ezb > D.zblocks)
-        return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field reopen's box lies outside the grid");
-    const bool goal_in = fe.field_goal[0] >= 0;
-    D.goal = goal_in ? ((long long)fe.field_goal[0] * G.Y + fe.field_goal[1]) * G.Z + fe.field_goal[2] : -1ll;
-    unsigned long long *h = fe.h_field_rep.get();          // [the record as it starts | the record as the kernels left it]
-    for (int i = 0; i < 2 * FF_REP_WORDS; i++) h[i] = 0ull;
-    unsigned long long *rep = fe.d_field_rep.get(), *cnt = fe.d_field_cnt.get();
-    unsigned *flags = fe.d_field_flags.get();
-    const hipStream_t st = c->stream;
-    HIPCHK(c, hipEventRecord(ev_start, st));
-    HIPCHK(c, hipMemcpyAsync(rep, h, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
-    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
-    const long long n_wv = (long long)B.ex * B.ey * B.ezb;
-    hipLaunchKernelGGL(ff_reopen_mark_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, D, B.x0, B.y0, B.zb0, B.ex, B.ey, B.ezb, fe.d_cspace.get(),
-                       fe.d_field_free.get(), fe.d_field.get(), flags, fe.d_field_open.get(), rep);
-    hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h + FF_REP_WORDS, rep, FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (B.x0 < 0 || B.y0 < 0 || B.zb0 < 0 || B.ex < 1 || B.ey < 1 || B.ezb < 1 || B.x0 + B.ex > G.X || B.y0 + B.ey > G.Y || B.zb0 + B.ezb > (G.Z + FF_BZ - 1) / FF_BZ)
+        return isdf_fail(c, ISDF_ERR_INVALID_ARG, dir == FfChange::Closing ? "the field repair's box lies outside the grid" : "the field reopen's box lies outside the grid");
     return ISDF_OK;
 }
 
-// After the stream has been synchronised: the rounds from the seeded bricks, the counts.  *reopened = 1: the field is valid again
-// (status 2 when the round bound was hit, as after a build); 0: a bit had closed, the field stays dropped.
-int isdf_field_reopen_end(isdf_ctx *c, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *reopened) {
+unsigned ff_box_blocks(const FfBox &B) { return (unsigned)(((long long)B.ex * B.ey * B.ezb + 3) / 4); }      // four wavefronts per workgroup
+
+}  // namespace
+
+// Enqueues, after the configuration-space refresh on the ctx's stream: the direction's mark over the box, closing: the reset,
+// ff_compact_kernel and the record's copy to the host.  The caller synchronises the stream, then calls ..._end with the same box.
+int isdf_field_change_begin(isdf_ctx *c, FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start) {
     isdf_ctx::FrontEnd &fe = c->fe;
-    *reopened = 0;
-    unsigned long long *rep = fe.h_field_rep.get() + FF_REP_WORDS;
-    if (rep[FF_ROP_CLOSED]) return ISDF_OK;
-    const DevGrid &G = c->grid;
+    const bool closing = dir == FfChange::Closing;
     FfDims D = ff_dims(c);
-    const FfBox B = ff_box(G, lo, hi);
+    const int n_bricks = D.nbx * D.nby * D.nbz;
+    if (fe.d_field_rep.reserve(c, 1) || fe.h_field_rep.reserve(c, 2)) return ISDF_ERR_HIP;
+    // the opened words are sized for the whole grid at once: no box of a later clear grows them
+    if (!closing && fe.d_field_open.reserve(c, (size_t)D.X * D.Y * D.zblocks)) return ISDF_ERR_HIP;
+    FfBox B;
+    const int rc = ff_box(c, dir, lo, hi, B);
+    if (rc != ISDF_OK) return rc;
+    if (!closing) D.goal = ff_goal_index(c);
+    FfRecord *h = fe.h_field_rep.get(), *rec = fe.d_field_rep.get();          // h: [the record as it starts | as the kernels left it]
+    h[0] = h[1] = ff_record_empty();
+    unsigned long long *cnt = fe.d_field_cnt.get();
+    unsigned *flags = fe.d_field_flags.get();
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipEventRecord(ev_start, st));
+    HIPCHK(c, hipMemcpyAsync(rec, h, sizeof(FfRecord), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
+    if (closing) {
+        hipLaunchKernelGGL(ff_mark_kernel<FfChange::Closing>, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                           (unsigned *)nullptr, (unsigned long long *)nullptr, rec);
+        hipLaunchKernelGGL(ff_repair_reset_kernel, dim3((unsigned)n_bricks), dim3(256), 0, st, D, fe.d_field.get(), flags, rec);
+    } else
+        hipLaunchKernelGGL(ff_mark_kernel<FfChange::Opening>, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                           flags, fe.d_field_open.get(), rec);
+    hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h + 1, rec, sizeof(FfRecord), hipMemcpyDeviceToHost, st));
+    return ISDF_OK;
+}
+
+// After the stream has been synchronised: the rounds from the seeded bricks, the counts.  *kept = 1: the field is valid again (status
+// 2 when the round bound was hit, as after a build); 0: a bit had moved against the direction, the field stays dropped.
+int isdf_field_change_end(isdf_ctx *c, FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *kept) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    const bool closing = dir == FfChange::Closing;
+    *kept = 0;
+    FfRecord &rec = fe.h_field_rep.get()[1];
+    if (rec.premise_violated) return ISDF_OK;
+    const FfDims D = ff_dims(c);
+    FfBox B;
+    const int rc = ff_box(c, dir, lo, hi, B);
+    if (rc != ISDF_OK) return rc;
     const hipStream_t st = c->stream;
     volatile unsigned long long *h = fe.h_field_cnt.get();
-    const long long n_opened = (long long)rep[FF_ROP_OPENED], n_seeded = (long long)h[FF_CNT_ACTIVE];
-    const bool goal_opened = rep[FF_ROP_GOAL] != 0ull;
-    const long long n_free = fe.field_free_voxels + n_opened;
+    const long long n_seeded = (long long)h[FF_CNT_ACTIVE], reached_before = fe.field_reached_voxels;
+    const long long n_free = fe.field_free_voxels + (closing ? -(long long)rec.changed : (long long)rec.changed);
     long long bound = n_free;
     if (fe.field_max_rounds > 0 && fe.field_max_rounds < bound) bound = fe.field_max_rounds;
     FfRounds R;
-    // a field without a reachable goal whose goal cell did not open is all +inf and stays so: nothing to relax
-    if (fe.field_reached_voxels > 0 || goal_opened) HIPCHK(c, ff_run_rounds(fe, D, n_seeded, bound, st, R));
-    hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)G.X * G.Y * G.Z, fe.d_field_cnt.get());
-    const long long n_wv = (long long)B.ex * B.ey * B.ezb;
-    hipLaunchKernelGGL(ff_reopen_count_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, st, D, B.x0, B.y0, B.zb0, B.ex, B.ey, B.ezb, fe.d_field.get(),
-                       fe.d_field_open.get(), fe.d_field_rep.get());
+    // opening: a field without a reachable goal whose goal cell did not open is all +inf and stays so: nothing to relax
+    if (closing || reached_before > 0 || rec.goal_opened) HIPCHK(c, ff_run_rounds(fe, D, n_seeded, bound, st, R));
+    hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)D.X * D.Y * D.Z, fe.d_field_cnt.get());
+    if (!closing) hipLaunchKernelGGL(ff_reopen_count_kernel, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_field.get(), fe.d_field_open.get(), fe.d_field_rep.get());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev_end, st));
     HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), fe.d_field_cnt.get(), FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(rep, fe.d_field_rep.get(), FF_REP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (!closing) HIPCHK(c, hipMemcpyAsync(&rec, fe.d_field_rep.get(), sizeof(FfRecord), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev_start, ev_end));
-    const bool goal_in = fe.field_goal[0] >= 0;
-    isdf_field_reopen_info &I = fe.field_reopen;
-    I = isdf_field_reopen_info{};
-    I.reached_before = fe.field_reached_voxels;
-    fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
+    fe.field_reachable = fe.field_goal[0] >= 0 && h[FF_CNT_REACHED] > 0;
     fe.field_status = fe.field_reachable ? R.status : 1;
     fe.field_free_voxels = n_free;
     fe.field_reached_voxels = (long long)h[FF_CNT_REACHED];
     fe.field_valid = true;
-    fe.field_reopened = true;
-    I.opened_voxels = n_opened;
-    I.opened_reached = (int64_t)rep[FF_ROP_REACHED];
-    I.reached_voxels = (int64_t)h[FF_CNT_REACHED];
-    I.free_voxels = n_free;
-    I.brick_visits = R.visits;
-    I.seeded_bricks = (int32_t)n_seeded;
-    I.rounds = (int32_t)R.rounds;
-    I.goal_opened = goal_opened ? 1 : 0;
-    I.reachable = fe.field_reachable ? 1 : 0;
-    I.status = fe.field_status;
-    I.device_ms = ms;
-    *reopened = 1;
+    if (closing) {
+        fe.field_repaired = true;
+        isdf_field_repair_info &I = fe.field_repair;
+        I = isdf_field_repair_info{};
+        I.closed_voxels = (int64_t)rec.changed;
+        I.closed_reached = (int64_t)rec.changed_reached;
+        std::memcpy(&I.tau, &rec.tau_bits, sizeof(double));
+        I.reset_voxels = (int64_t)(rec.reset + rec.changed_reached);
+        I.seeded_bricks = (int32_t)rec.seeded;
+        I.rounds = (int32_t)R.rounds; I.brick_visits = R.visits;
+        I.free_voxels = n_free; I.reached_voxels = fe.field_reached_voxels;
+        I.reachable = fe.field_reachable ? 1 : 0; I.status = fe.field_status;
+        I.device_ms = ms;
+    } else {
+        fe.field_reopened = true;
+        isdf_field_reopen_info &I = fe.field_reopen;
+        I = isdf_field_reopen_info{};
+        I.opened_voxels = (int64_t)rec.changed;
+        I.opened_reached = (int64_t)rec.opened_reached;
+        I.reached_before = reached_before;
+        I.seeded_bricks = (int32_t)n_seeded;
+        I.goal_opened = rec.goal_opened ? 1 : 0;
+        I.rounds = (int32_t)R.rounds; I.brick_visits = R.visits;
+        I.free_voxels = n_free; I.reached_voxels = fe.field_reached_voxels;
+        I.reachable = fe.field_reachable ? 1 : 0; I.status = fe.field_status;
+        I.device_ms = ms;
+    }
+    *kept = 1;
     return ISDF_OK;
 }
 
-extern "C" int isdf_frontend_field_set_reopen(isdf_ctx *c, int mode) {
+namespace {
+
+int ff_set_mode(isdf_ctx *c, int mode, int isdf_ctx::*slot, const char *bad_mode) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    if (mode != 0 && mode != 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field's reopen mode is 0 (drop) or 1 (lower in place)");
+    if (mode != 0 && mode != 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, bad_mode);
     if (!c->peers.empty() || c->is_peer || c->rccl_comm) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "cost-to-go field on a multi-device ctx");
-    c->field_reopen_mode = mode;
+    c->*slot = mode;
     return ISDF_OK;
+}
+
+template <class Info> int ff_last_info(isdf_ctx *c, Info *out, bool have, const Info &last, const char *none) {
+    if (!out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
+    if (!have) return isdf_fail(c, ISDF_ERR_STATE, none);
+    *out = last;
+    return ISDF_OK;
+}
+
+}  // namespace
+
+extern "C" int isdf_frontend_field_set_reopen(isdf_ctx *c, int mode) {
+    return ff_set_mode(c, mode, &isdf_ctx::field_reopen_mode, "the field's reopen mode is 0 (drop) or 1 (lower in place)");
 }
 
 extern "C" int isdf_frontend_field_reopen_info(isdf_ctx *c, isdf_field_reopen_info *out) {
-    if (!c) return ISDF_ERR_INVALID_ARG;
-    if (!out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
-    if (!c->fe.field_reopened) return isdf_fail(c, ISDF_ERR_STATE, "no reopen since the last isdf_frontend_field_build");
-    *out = c->fe.field_reopen;
-    return ISDF_OK;
+    return c ? ff_last_info(c, out, c->fe.field_reopened, c->fe.field_reopen, "no reopen since the last isdf_frontend_field_build") : ISDF_ERR_INVALID_ARG;
 }
 
 extern "C" void isdf_frontend_field_reopen_sizes(int sizes_out[1]) {
@@ -843,19 +776,11 @@ extern "C" void isdf_frontend_field_reopen_sizes(int sizes_out[1]) {
 }
 
 extern "C" int isdf_frontend_field_set_repair(isdf_ctx *c, int mode) {
-    if (!c) return ISDF_ERR_INVALID_ARG;
-    if (mode != 0 && mode != 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the field's repair mode is 0 (drop) or 1 (repair)");
-    if (!c->peers.empty() || c->is_peer || c->rccl_comm) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "cost-to-go field on a multi-device ctx");
-    c->field_repair_mode = mode;
-    return ISDF_OK;
+    return ff_set_mode(c, mode, &isdf_ctx::field_repair_mode, "the field's repair mode is 0 (drop) or 1 (repair)");
 }
 
 extern "C" int isdf_frontend_field_repair_info(isdf_ctx *c, isdf_field_repair_info *out) {
-    if (!c) return ISDF_ERR_INVALID_ARG;
-    if (!out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
-    if (!c->fe.field_repaired) return isdf_fail(c, ISDF_ERR_STATE, "no repair since the last isdf_frontend_field_build");
-    *out = c->fe.field_repair;
-    return ISDF_OK;
+    return c ? ff_last_info(c, out, c->fe.field_repaired, c->fe.field_repair, "no repair since the last isdf_frontend_field_build") : ISDF_ERR_INVALID_ARG;
 }
 
 extern "C" void isdf_frontend_field_repair_sizes(int sizes_out[1]) {
@@ -865,9 +790,8 @@ extern "C" void isdf_frontend_field_repair_sizes(int sizes_out[1]) {
 extern "C" int isdf_frontend_field_get(isdf_ctx *c, double *d_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (!d_out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
-    const int rdy = ff_ready(c);
+    const int rdy = ff_field_ready(c);
     if (rdy != ISDF_OK) return rdy;
-    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n_vox = (size_t)c->grid.X * c->grid.Y * c->grid.Z;
     HIPCHK(c, hipMemcpyAsync(d_out, c->fe.d_field.get(), n_vox * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -878,9 +802,8 @@ extern "C" int isdf_frontend_field_get(isdf_ctx *c, double *d_out) {
 extern "C" int isdf_frontend_field_value(isdf_ctx *c, const double *xyz, int n, double *out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (n < 0 || (n > 0 && (!xyz || !out))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad field query");
-    const int rdy = ff_ready(c);
+    const int rdy = ff_field_ready(c);
     if (rdy != ISDF_OK) return rdy;
-    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
     if (n == 0) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<double> buf;                                    // [xyz 3n | values n]
@@ -899,9 +822,8 @@ extern "C" int isdf_frontend_field_paths_device(isdf_ctx *c, const double *d_sta
                                                 double *d_roll_pitch_out, void *stream) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (B < 0 || cap < 1 || (B > 0 && (!d_starts_xyz || !d_n_out || !d_xyz_out || !d_roll_pitch_out))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad field path query");
-    const int rdy = ff_ready(c);
+    const int rdy = ff_field_ready(c);
     if (rdy != ISDF_OK) return rdy;
-    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
     if (B == 0) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     return ff_paths_launch(c, d_starts_xyz, B, cap, d_n_out, d_xyz_out, d_roll_pitch_out, (hipStream_t)stream);
@@ -910,9 +832,8 @@ extern "C" int isdf_frontend_field_paths_device(isdf_ctx *c, const double *d_sta
 extern "C" int isdf_frontend_field_paths(isdf_ctx *c, const double *starts_xyz, int B, int cap, int32_t *n_out, double *xyz_out, double *roll_pitch_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (B < 0 || cap < 1 || (B > 0 && (!starts_xyz || !n_out || !xyz_out || !roll_pitch_out))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad field path query");
-    const int rdy = ff_ready(c);
+    const int rdy = ff_field_ready(c);
     if (rdy != ISDF_OK) return rdy;
-    if (!c->fe.field_valid) return isdf_fail(c, ISDF_ERR_STATE, "isdf_frontend_field_build has not been called");
     if (B == 0) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     // one scoped allocation: [starts 3B | xyz 3 B cap | roll, pitch 2 B cap | n B ints]
@@ -936,58 +857,58 @@ extern "C" int isdf_frontend_field_paths(isdf_ctx *c, const double *starts_xyz, 
     return ISDF_OK;
 }
 
-extern "C" int isdf_frontend_field_host(const uint32_t *free_mask, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_out) {
-    if (!free_mask || !dims || !goal_index || !d_out || n_att < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ISDF_ERR_INVALID_ARG;
+namespace {
+
+// What the host forms share: the argument checks, the goal as ints, the call; run(g, info) fills the direction's own counts of the
+// info and returns whether the goal cell is free.  1 / 0 = that answer, ISDF_ERR_HIP when the host ran out of memory.
+template <class Info, class F> int ff_host_form(const uint32_t *mask, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d, Info *info_out, F run) {
+    if (!mask || !dims || !goal_index || !d || n_att < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ISDF_ERR_INVALID_ARG;
     const int g[3] = {goal_index[0], goal_index[1], goal_index[2]};
     try {
-        return isdf_host::field_dijkstra(free_mask, dims[0], dims[1], dims[2], n_att, g, d_out) ? 1 : 0;
+        Info I{};
+        const bool goal_free = run(g, I);
+        I.reachable = goal_free ? 1 : 0;
+        I.status = goal_free ? 0 : 1;
+        if (info_out) *info_out = I;
+        return goal_free ? 1 : 0;
     } catch (const std::bad_alloc &) {
         return ISDF_ERR_HIP;
     }
+}
+
+}  // namespace
+
+extern "C" int isdf_frontend_field_host(const uint32_t *free_mask, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_out) {
+    return ff_host_form(free_mask, dims, n_att, goal_index, d_out, (isdf_frontend_field_info *)nullptr, [&](const int g[3], isdf_frontend_field_info &) {
+        return isdf_host::field_dijkstra(free_mask, dims[0], dims[1], dims[2], n_att, g, d_out);
+    });
 }
 
 extern "C" int isdf_frontend_field_repair_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_inout,
                                                isdf_field_repair_info *info_out) {
-    if (!free_mask_new || !dims || !goal_index || !d_inout || n_att < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ISDF_ERR_INVALID_ARG;
-    const int g[3] = {goal_index[0], goal_index[1], goal_index[2]};
-    try {
+    return ff_host_form(free_mask_new, dims, n_att, goal_index, d_inout, info_out, [&](const int g[3], isdf_field_repair_info &I) {
         isdf_host::FieldRepairCounts C;
         const bool goal_free = isdf_host::field_repair(free_mask_new, dims[0], dims[1], dims[2], n_att, g, d_inout, &C);
-        if (info_out) {
-            *info_out = isdf_field_repair_info{};
-            info_out->closed_voxels = info_out->closed_reached = C.closed_reached;      // (a closed voxel that had not been reached cannot be told from one that was never free)
-            info_out->tau = C.tau;
-            info_out->reset_voxels = C.reset_voxels;
-            info_out->free_voxels = C.free_voxels;
-            info_out->reached_voxels = C.reached_voxels;
-            info_out->reachable = goal_free ? 1 : 0;
-            info_out->status = goal_free ? 0 : 1;
-        }
-        return goal_free ? 1 : 0;
-    } catch (const std::bad_alloc &) {
-        return ISDF_ERR_HIP;
-    }
+        I.closed_voxels = I.closed_reached = C.closed_reached;      // (a closed voxel that had not been reached cannot be told from one that was never free)
+        I.tau = C.tau;
+        I.reset_voxels = C.reset_voxels;
+        I.free_voxels = C.free_voxels;
+        I.reached_voxels = C.reached_voxels;
+        return goal_free;
+    });
 }
 
 extern "C" int isdf_frontend_field_reopen_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3], double *d_inout,
                                                isdf_field_reopen_info *info_out) {
-    if (!free_mask_new || !dims || !goal_index || !d_inout || n_att < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ISDF_ERR_INVALID_ARG;
-    const int g[3] = {goal_index[0], goal_index[1], goal_index[2]};
-    try {
+    return ff_host_form(free_mask_new, dims, n_att, goal_index, d_inout, info_out, [&](const int g[3], isdf_field_reopen_info &I) {
         isdf_host::FieldReopenCounts C;
         const bool goal_free = isdf_host::field_reopen(free_mask_new, dims[0], dims[1], dims[2], n_att, g, d_inout, &C);
-        if (info_out) {
-            *info_out = isdf_field_reopen_info{};
-            info_out->opened_voxels = info_out->opened_reached = C.newly_reached;       // (an opened voxel that stays +inf cannot be told from a free one that was never reached)
-            info_out->reached_before = C.reached_before;
-            info_out->reached_voxels = C.reached_voxels;
-            info_out->free_voxels = C.free_voxels;
-            info_out->goal_opened = C.goal_opened ? 1 : 0;
-            info_out->reachable = goal_free ? 1 : 0;
-            info_out->status = goal_free ? 0 : 1;
-        }
-        return goal_free ? 1 : 0;
-    } catch (const std::bad_alloc &) {
-        return ISDF_ERR_HIP;
-    }
+        I.opened_voxels = I.opened_reached = C.newly_reached;       // (an opened voxel that stays +inf cannot be told from a free one that was never reached)
+        I.reached_before = C.reached_before;
+        I.reached_voxels = C.reached_voxels;
+        I.free_voxels = C.free_voxels;
+        I.goal_opened = C.goal_opened ? 1 : 0;
+        return goal_free;
+    });
 }
+

@@ -73,16 +73,32 @@ inline void field_relax_heap(const uint32_t *mask, int X, int Y, int Z, size_t n
     }
 }
 
+// the goal's voxel in grid order (z fastest); false: a component lies outside the map = no goal
+inline bool field_goal_voxel(int X, int Y, int Z, const int goal[3], size_t *g) {
+    if (goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z) return false;
+    *g = ((size_t)goal[0] * Y + (size_t)goal[1]) * Z + (size_t)goal[2];
+    return true;
+}
+
+// what the two in-place changes start from: one byte per voxel, free in the mask or not, and their count
+inline std::vector<unsigned char> field_free_bytes(const uint32_t *mask, size_t nw, size_t n, long long *n_free) {
+    std::vector<unsigned char> fr(n);
+    for (size_t v = 0; v < n; v++) {
+        fr[v] = field_voxel_free(mask, nw, v) ? 1 : 0;
+        *n_free += fr[v];
+    }
+    return fr;
+}
+
 // mask: nw = 4 * ceil(n_att / 128) dwords per voxel, grid order (z fastest).  goal: voxel index, any component outside the map = no goal.
 // d_out: X * Y * Z doubles.  Returns true when the goal cell is inside the map and free.
 inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att, const int goal[3], double *d_out) {
     const size_t nw = 4 * (size_t)((n_att + 127) / 128);
-    const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
+    const size_t n = (size_t)X * Y * Z;
     const double inf = std::numeric_limits<double>::infinity();
     for (size_t v = 0; v < n; v++) d_out[v] = inf;
-    if (goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z) return false;
-    const size_t g = (size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2];
-    if (!field_voxel_free(mask, nw, g)) return false;
+    size_t g;
+    if (!field_goal_voxel(X, Y, Z, goal, &g) || !field_voxel_free(mask, nw, g)) return false;
     FieldHeap heap;
     d_out[g] = 0.0;
     heap.push(0.0, g);
@@ -100,16 +116,13 @@ inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att,
 struct FieldRepairCounts { long long closed_reached = 0, reset_voxels = 0, free_voxels = 0, reached_voxels = 0; double tau = 0.0; };
 inline bool field_repair(const uint32_t *mask_new, int X, int Y, int Z, int n_att, const int goal[3], double *d, FieldRepairCounts *counts) {
     const size_t nw = 4 * (size_t)((n_att + 127) / 128);
-    const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
+    const size_t n = (size_t)X * Y * Z;
     const double inf = std::numeric_limits<double>::infinity();
     FieldRepairCounts C;
     C.tau = inf;
-    std::vector<unsigned char> fr(n);
-    for (size_t v = 0; v < n; v++) {
-        fr[v] = field_voxel_free(mask_new, nw, v) ? 1 : 0;
-        C.free_voxels += fr[v];
+    const std::vector<unsigned char> fr = field_free_bytes(mask_new, nw, n, &C.free_voxels);
+    for (size_t v = 0; v < n; v++)
         if (!fr[v] && d[v] < inf) { C.closed_reached++; if (d[v] < C.tau) C.tau = d[v]; }
-    }
     FieldHeap heap;
     for (size_t v = 0; v < n; v++) {
         if (!(d[v] < inf)) continue;
@@ -119,8 +132,8 @@ inline bool field_repair(const uint32_t *mask_new, int X, int Y, int Z, int n_at
     field_relax_heap(mask_new, X, Y, Z, nw, heap, d);
     for (size_t v = 0; v < n; v++) C.reached_voxels += d[v] < inf;
     if (counts) *counts = C;
-    if (goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z) return false;
-    return fr[(size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2]] != 0;
+    size_t g;
+    return field_goal_voxel(X, Y, Z, goal, &g) && fr[g] != 0;
 }
 
 // The field LOWERED after voxels opened (occupancy only shrinks).  d: the field of the same goal on a mask of which
@@ -138,14 +151,10 @@ inline bool field_reopen(const uint32_t *mask_new, int X, int Y, int Z, int n_at
     const size_t n = (size_t)X * Y * Z, YZ = (size_t)Y * Z;
     const double inf = std::numeric_limits<double>::infinity();
     FieldReopenCounts C;
-    std::vector<unsigned char> fr(n);
-    for (size_t v = 0; v < n; v++) {
-        fr[v] = field_voxel_free(mask_new, nw, v) ? 1 : 0;
-        C.free_voxels += fr[v];
-        C.reached_before += d[v] < inf;
-    }
-    const bool goal_in = !(goal[0] < 0 || goal[0] >= X || goal[1] < 0 || goal[1] >= Y || goal[2] < 0 || goal[2] >= Z);
-    const size_t g = goal_in ? (size_t)goal[0] * YZ + (size_t)goal[1] * Z + (size_t)goal[2] : 0;
+    const std::vector<unsigned char> fr = field_free_bytes(mask_new, nw, n, &C.free_voxels);
+    for (size_t v = 0; v < n; v++) C.reached_before += d[v] < inf;
+    size_t g = 0;
+    const bool goal_in = field_goal_voxel(X, Y, Z, goal, &g);
     FieldHeap heap;
     if (goal_in && fr[g] && !(d[g] < inf)) { C.goal_opened = true; d[g] = 0.0; heap.push(0.0, g); }
     for (size_t v = 0; v < n; v++) {

@@ -36,6 +36,24 @@ struct MapRaycastState;         // map_raycast.hip: staging of the host-pointer 
 void isdf_map_raycast_release_all(isdf_ctx *c);       // map_raycast.hip: drops it
 int isdf_traj_check_ready(isdf_ctx *c);               // traj_check.hip: what isdf_traj_check needs of the ctx (shape, occupancy grid), or the error
 
+// frontend_field.hip: the record of one in-place change of the cost-to-go field (voxels closed: the repair; opened: the reopen),
+// one 64-byte line, uploaded empty before the change's kernels and read back after them
+struct FfRecord {
+    unsigned long long tau_bits;            // closing: the least finite d of a closed voxel, as its bits (+inf: none)
+    unsigned long long changed;             // voxels closed / opened
+    unsigned long long changed_reached;     // closing: of them, those that held a finite d
+    unsigned long long premise_violated;    // a bit moved against the direction: the host drops the field
+    unsigned long long reset, seeded;       // closing: voxels reset by the threshold, bricks that reset one
+    unsigned long long goal_opened;         // opening: the goal cell opened
+    unsigned long long opened_reached;      // opening: opened voxels with a finite d after the rounds
+};
+static_assert(sizeof(FfRecord) == 64, "the field change's record is one 64-byte line");
+inline FfRecord ff_record_empty() {
+    FfRecord r{};
+    r.tau_bits = 0x7FF0000000000000ull;
+    return r;
+}
+
 // What the swept-volume kernels need per point set (SweptParams): the optimizer step's (the ctx holds it) or the field query's
 // (SweptMeshState holds its own: the query never shares scratch with the step).  The point arrays grow together.
 struct SweptScratch {
@@ -182,14 +200,15 @@ struct isdf_ctx {
         DevBuf<double> d_field; DevBuf<unsigned long long> d_field_free; DevBuf<int> d_field_list; DevBuf<unsigned> d_field_flags;
         DevBuf<unsigned long long> d_field_cnt; PinBuf<unsigned long long> h_field_cnt;
         bool field_valid = false, field_reachable = false; int field_goal[3] = {-1, -1, -1};
-        // what the repair after a map update needs of the last build: its status and round bound, the count of free voxels; the
-        // repair's record on the device and its pinned copy, the last repair's report (field_repaired: there was one since the build)
-        int field_status = 0, field_max_rounds = 0; long long field_free_voxels = 0;
-        DevBuf<unsigned long long> d_field_rep; PinBuf<unsigned long long> h_field_rep;
+        // what an in-place change (the repair after a map update, the reopen after a clear) needs of the last build: its status and
+        // round bound, the counts of free and of reached voxels as the last build / repair / reopen left them; the change's record on
+        // the device and its pinned copy [as it starts | as the kernels left it]; the opening direction's opened bits of the changed
+        // box, one word per wavefront of the mark kernel
+        int field_status = 0, field_max_rounds = 0; long long field_free_voxels = 0, field_reached_voxels = 0;
+        DevBuf<FfRecord> d_field_rep; PinBuf<FfRecord> h_field_rep;
+        DevBuf<unsigned long long> d_field_open;
+        // the last repair's and the last reopen's report (field_repaired, field_reopened: there was one since the build)
         bool field_repaired = false; isdf_field_repair_info field_repair{};
-        // the reopen after a clear (it shares the repair's record buffers): the opened bits of the changed box, one word per
-        // wavefront of the mark kernel; the voxels reached by the last build / repair / reopen; the last reopen's report
-        DevBuf<unsigned long long> d_field_open; long long field_reached_voxels = 0;
         bool field_reopened = false; isdf_field_reopen_info field_reopen{};
     } fe;
     int field_repair_mode = 0;                  // isdf_frontend_field_set_repair: outlives isdf_frontend_build (fe is reset by it)

@@ -230,6 +230,22 @@ void isdf::map_frontend_finish(isdf_ctx *c, MapUpdateState &S, MapFrontend &F) {
     F.ms = mu_event_ms(S.ev[4], S.ev[5]);
 }
 
+int isdf::map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool follow, bool on, bool full, const MapRefresh &M, MapFrontend &F, int *field_dropped) {
+    const int *const lo = full ? nullptr : M.grown.lo, *const hi = full ? nullptr : M.grown.hi;
+    int rc;
+    if ((rc = map_frontend_launch(c, S, on, full, &M.box, &M.grown, 1, F))) return rc;
+    HIPCHK(c, map_records_fetch(S, c->stream));
+    if (follow && (rc = isdf_field_change_begin(c, dir, lo, hi, S.ev[6]))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (follow) {
+        int kept = 0;
+        if ((rc = isdf_field_change_end(c, dir, lo, hi, S.ev[6], S.ev[7], &kept))) return rc;
+        if (kept) *field_dropped = 0;
+    }
+    map_frontend_finish(c, S, F);
+    return ISDF_OK;
+}
+
 int isdf::map_watch_recheck(isdf_ctx *c, bool armed, int32_t *rechecked) {
     if (!armed) return ISDF_OK;
     const long long folded = c->tck->w.last.updates_folded;

@@ -1,10 +1,12 @@
 // What the calls that change the map in place share (map_update.hip: voxels become occupied, map_clear.hip: voxels become free,
 // map_scan.hip: both from one range scan, map_shift.hip: the window moves): the grow-only scratch, the typed hand-over records, the
 // lane's "I changed a voxel" step and the host steps every driver goes through - begin, stage, hand-over, map changed, the front-end
-// stage in its two halves, the watch re-check, the ready checks.  The drivers call the steps in their own order; the steps are defined
-// once, in map_change.hip.
+// stage in its two halves (the shift) or whole with the cost-to-go field following the change (update, clear and, through them, the
+// scan), the watch re-check, the ready checks.  The drivers call the steps in their own order; the steps are defined once, in
+// map_change.hip.
 #pragma once
 #include "isdf_ctx.hpp"
+#include "frontend_dev.hpp"
 #include "map_update_host.hpp"
 
 namespace isdf {
@@ -68,7 +70,8 @@ struct MapUpdateState {
     // occupancy and the configuration-space table stays allocated)
     isdf::DevBuf<unsigned> d_shift_counts, d_shift_cspace; isdf::DevBuf<uint8_t> d_shift_occ;
     hipEvent_t ev_scan[2] = {nullptr, nullptr};          // map_scan.hip: around the ray stage
-    // [0], [1]: a count (translation) stage; [2], [3]: the ESDF stage; [4], [5]: the front-end stage; [6], [7]: the field's repair or reopen
+    // [0], [1]: a count (translation) stage; [2], [3]: the ESDF stage; [4], [5]: the front-end stage; [6], [7]: the field's in-place
+    // change inside map_frontend_stage, either direction (a scan's two stages use them one after the other)
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     ~MapUpdateState() {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -97,7 +100,7 @@ inline hipError_t map_records_fetch(MapUpdateState &S, hipStream_t st) { return 
 // it), the error message stays.  The occupancy and the counts are consistent with each other and stay.
 void mu_drop_derived(isdf_ctx *c, bool voxels);
 // map changed: the voxel forms' counts no longer describe the occupancy, the bit grid is stale, a valid cost-to-go field is dropped
-// (returns 1 then: a driver that repairs it asks isdf_field_*_wanted first)
+// (returns 1 then: a driver that repairs it asks isdf_field_change_wanted first)
 int map_changed(isdf_ctx *c, bool voxels);
 // ... and what a refresh over a list decides before its first stage: the dirty box, grown for the front end, which products are
 // refreshed (an ESDF that is switched off is dropped here) and whether a cap of the params is exceeded
@@ -116,6 +119,12 @@ struct MapFrontend {
 };
 int map_frontend_launch(isdf_ctx *c, MapUpdateState &S, bool on, bool full, const MuBox *boxes, const MuBox *grown, int n_boxes, MapFrontend &F, bool stamp = true);
 void map_frontend_finish(isdf_ctx *c, MapUpdateState &S, MapFrontend &F);
+// The whole stage of a change in one direction (dir: its voxels closed or opened) with the cost-to-go field following it around the one
+// synchronisation: _launch over (M.box, M.grown) or the full map, the records on their way to S.h_rec, when `follow` (the caller asked
+// isdf_field_change_wanted before map_refresh_begin dropped the field) the field's begin over M.grown; the synchronisation; the
+// field's end - its rounds read one word each -, and only then _finish: the host table is patched after them.  A field that followed:
+// *field_dropped = 0.  F: for map_frontend_report.
+int map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool follow, bool on, bool full, const MapRefresh &M, MapFrontend &F, int *field_dropped);
 template <class Info> inline void map_frontend_report(const MapFrontend &F, Info &info) {       // the update's and the clear's info name these alike
     info.frontend_refreshed = F.refreshed; info.cspace_refreshed = F.cspace_refreshed; info.host_table_patched = F.host_table_patched;
     info.cspace_voxels_recomputed = F.cspace_voxels; info.frontend_ms = F.ms;

@@ -191,7 +191,7 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
     // The cost-to-go field: dropped (mode 0 of isdf_frontend_field_set_reopen; the repair's rule is not proved for opened bits), or
     // lowered in place once the configuration space is the new map's (mode 1).  It is invalid from here until the reopen has gone
     // through: every error path leaves it dropped.
-    const bool reopen = P.refresh_frontend != 0 && isdf_field_reopen_wanted(c);
+    const bool reopen = P.refresh_frontend != 0 && isdf_field_change_wanted(c, FfChange::Opening);
     const MapRefresh M = map_refresh_begin(c, R, cap, voxels, P.refresh_esdf, P.refresh_frontend, P.full_fraction, &info.field_dropped);
     for (int a = 0; a < 3; a++) { info.dirty_lo[a] = M.box.lo[a]; info.dirty_hi[a] = M.box.hi[a]; }
     bool full = M.over;
@@ -234,17 +234,7 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
 
     // ---- front end, the field's reopen around the synchronisation
     MapFrontend F;
-    if ((rc = map_frontend_launch(c, S, P.refresh_frontend != 0, full, &M.box, &M.grown, 1, F))) return rc;
-    HIPCHK(c, map_records_fetch(S, st));
-    const int *const f_lo = full ? nullptr : M.grown.lo, *const f_hi = full ? nullptr : M.grown.hi;
-    if (reopen && (rc = isdf_field_reopen_begin(c, f_lo, f_hi, S.ev[6]))) return rc;
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (reopen) {                       // the rounds read one word each; the host table is patched after them
-        int reopened = 0;
-        if ((rc = isdf_field_reopen_end(c, f_lo, f_hi, S.ev[6], S.ev[7], &reopened))) return rc;
-        if (reopened) info.field_dropped = 0;
-    }
-    map_frontend_finish(c, S, F);
+    if ((rc = map_frontend_stage(c, S, FfChange::Opening, reopen, P.refresh_frontend != 0, full, M, F, &info.field_dropped))) return rc;
     map_frontend_report(F, info);
     if (M.do_esdf && !full) info.esdf_voxels_raised = (long long)h_er->raised;
     info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);

@@ -121,7 +121,7 @@ int isdf::mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_upd
     int rc;
     // The cost-to-go field: dropped (mode 0 of isdf_frontend_field_set_repair), or repaired once the configuration space is the new
     // map's (mode 1).  It is invalid from here until the repair has gone through: every error path leaves it dropped.
-    const bool repair = P.refresh_frontend != 0 && isdf_field_repair_wanted(c);
+    const bool repair = P.refresh_frontend != 0 && isdf_field_change_wanted(c, FfChange::Closing);
     const MapRefresh M = map_refresh_begin(c, R, cap, voxels, P.refresh_esdf, P.refresh_frontend, P.full_fraction, &info.field_dropped);
     for (int a = 0; a < 3; a++) { info.dirty_lo[a] = M.box.lo[a]; info.dirty_hi[a] = M.box.hi[a]; }
     float esdf0;
@@ -148,16 +148,7 @@ int isdf::mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_upd
 
     // ---- front end, the field's repair around the synchronisation
     MapFrontend F;
-    if ((rc = map_frontend_launch(c, S, P.refresh_frontend != 0, full, &M.box, &M.grown, 1, F))) return rc;
-    HIPCHK(c, map_records_fetch(S, st));
-    if (repair && (rc = isdf_field_repair_begin(c, full ? nullptr : M.grown.lo, full ? nullptr : M.grown.hi, S.ev[6]))) return rc;
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (repair) {                       // the rounds read one word each; the host table is patched after them
-        int repaired = 0;
-        if ((rc = isdf_field_repair_end(c, S.ev[6], S.ev[7], &repaired))) return rc;
-        if (repaired) info.field_dropped = 0;
-    }
-    map_frontend_finish(c, S, F);
+    if ((rc = map_frontend_stage(c, S, FfChange::Closing, repair, P.refresh_frontend != 0, full, M, F, &info.field_dropped))) return rc;
     map_frontend_report(F, info);
     info.esdf_voxels_lowered = (long long)S.h_rec.get()->list.tally;
     info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
