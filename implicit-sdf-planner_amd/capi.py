@@ -107,6 +107,19 @@ class IsdfFieldReopenInfo(C.Structure):
                 ("goal_opened", C.c_int32), ("reachable", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32), ("device_ms", C.c_double)]
 
 
+FIELD_SHIFT_DROP, FIELD_SHIFT_CARRY = 0, 1               # isdf_frontend_field_set_shift
+FIELD_SHIFT_GOAL_LEFT = 3                                # isdf_frontend_field_shift_host: the goal cell left the window
+
+
+class IsdfFieldShiftInfo(C.Structure):
+    """isdf_field_shift_info (include/isdf_accel.h)."""
+    _fields_ = [("shift", C.c_int32 * 3), ("goal_new", C.c_int32 * 3), ("left_reached", C.c_int64), ("closed_voxels", C.c_int64),
+                ("closed_reached", C.c_int64), ("tau", C.c_double), ("reset_voxels", C.c_int64), ("opened_voxels", C.c_int64),
+                ("opened_reached", C.c_int64), ("brick_visits", C.c_int64), ("free_voxels", C.c_int64), ("reached_voxels", C.c_int64),
+                ("seeded_bricks_close", C.c_int32), ("rounds_close", C.c_int32), ("seeded_bricks_open", C.c_int32), ("rounds_open", C.c_int32),
+                ("goal_opened", C.c_int32), ("reachable", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32), ("device_ms", C.c_double)]
+
+
 MAP_UPDATE_NONE, MAP_UPDATE_INCREMENTAL, MAP_UPDATE_FULL = 0, 1, 2      # isdf_map_update_info.path
 
 
@@ -343,6 +356,7 @@ EXPORTED_SYMBOLS = [
     "isdf_frontend_field_paths", "isdf_frontend_field_paths_device", "isdf_frontend_field_host", "isdf_frontend_field_release",
     "isdf_frontend_field_set_repair", "isdf_frontend_field_repair_info", "isdf_frontend_field_repair_sizes", "isdf_frontend_field_repair_host",
     "isdf_frontend_field_set_reopen", "isdf_frontend_field_reopen_info", "isdf_frontend_field_reopen_sizes", "isdf_frontend_field_reopen_host",
+    "isdf_frontend_field_set_shift", "isdf_frontend_field_shift_info", "isdf_frontend_field_shift_sizes", "isdf_frontend_field_shift_host",
     "isdf_map_update_params_default", "isdf_map_update_sizes", "isdf_update_pointcloud", "isdf_update_voxels", "isdf_map_counts_get", "isdf_frontend_cspace_get",
     "isdf_map_clear_params_default", "isdf_map_clear_sizes", "isdf_clear_pointcloud", "isdf_clear_voxels", "isdf_clear_esdf_host", "isdf_clear_touched_host",
     "isdf_map_scan_params_default", "isdf_map_scan_sizes", "isdf_integrate_scan", "isdf_scan_sets_host", "isdf_scan_ray_host",
@@ -654,6 +668,14 @@ def load_library(path=None):
     lib.isdf_frontend_field_reopen_sizes(sz)
     if sz[0] != C.sizeof(IsdfFieldReopenInfo):
         raise RuntimeError(f"isdf_field_reopen_info: the library has {sz[0]}, the mirror {C.sizeof(IsdfFieldReopenInfo)}")
+    lib.isdf_frontend_field_set_shift.argtypes = [C.c_void_p, C.c_int]
+    lib.isdf_frontend_field_shift_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldShiftInfo)]
+    lib.isdf_frontend_field_shift_sizes.argtypes = [ip]
+    lib.isdf_frontend_field_shift_sizes.restype = None
+    lib.isdf_frontend_field_shift_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, dp, C.POINTER(IsdfFieldShiftInfo)]
+    lib.isdf_frontend_field_shift_sizes(sz)
+    if sz[0] != C.sizeof(IsdfFieldShiftInfo):
+        raise RuntimeError(f"isdf_field_shift_info: the library has {sz[0]}, the mirror {C.sizeof(IsdfFieldShiftInfo)}")
     if path is None:
         _lib = lib
     return lib

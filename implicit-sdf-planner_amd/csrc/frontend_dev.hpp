@@ -88,3 +88,11 @@ namespace isdf { enum class FfChange { Closing, Opening }; }
 bool isdf_field_change_wanted(const isdf_ctx *c, isdf::FfChange dir);
 int isdf_field_change_begin(isdf_ctx *c, isdf::FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start);
 int isdf_field_change_end(isdf_ctx *c, isdf::FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *kept);
+// ... and carried through a shift of the map window by s, which moves bits both ways (isdf_frontend_field_set_shift, mode 1; DESIGN
+// 4.6.4).  ..._wanted, asked before the shift drops the field: the mode is 1, the field valid and a fixed point, there is a table, the
+// goal cell stays inside the grid and not everything leaves.  ..._begin enqueues the translation and the closing phase's reset after
+// the shift's configuration-space refresh and moves the goal cell; the caller synchronises the stream; ..._end runs the closing
+// phase's rounds, then the opening direction over the box lo .. hi (null: the whole grid).  ev: four events, [0] for ..._begin.
+bool isdf_field_shift_wanted(const isdf_ctx *c, const int32_t s[3]);
+int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start);
+int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], hipEvent_t ev[4]);

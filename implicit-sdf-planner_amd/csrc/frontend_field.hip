@@ -44,6 +44,9 @@
 // bound of the new least fixed point d* -, relaxation keeps it one, and a fixed point >= d* with d[goal] = 0 is d* (in Dijkstra order
 // of d*, v's predecessor u holds d*[u], so d[v] <= fl(d*[u] + w) = d*[v]).  A brick without an opened voxel or a lowered halo voxel
 // satisfies its equations as before.
+// The field CARRIED through a shift of the map window, which moves bits both ways (isdf_frontend_field_set_shift):
+// ff_shift_kernel translates d and the free words into second buffers (fm1 = old & new: a subgraph of both maps), ff_left_kernel
+// takes the leaving voxels' tau; then the closing direction's reset and rounds on fm1, then the opening direction as it is.
 // Compiled with -ffp-contract=off like frontend.hip (cell indices and cube centres round like the A*'s).
 #include "isdf_ctx.hpp"
 #include "frontend_dev.hpp"
@@ -58,7 +61,7 @@ namespace isdf {
 constexpr int FF_BX = 8, FF_BY = 8, FF_BZ = 64;
 constexpr int FF_TX = FF_BX + 2, FF_TY = FF_BY + 2, FF_TZ = FF_BZ + 2;
 constexpr int FF_PER_LANE = FF_BX * FF_BY / 4;             // columns of the brick per wavefront (4 wavefronts)
-constexpr int FF_CNT_ACTIVE = 0, FF_CNT_FREE = 1, FF_CNT_REACHED = 2, FF_CNT_BRICKS = 3, FF_CNT_WORDS = 4;
+constexpr int FF_CNT_ACTIVE = 0, FF_CNT_FREE = 1, FF_CNT_REACHED = 2, FF_CNT_BRICKS = 3, FF_CNT_LEFT = 4, FF_CNT_WORDS = 5;
 
 struct FfDims {
     int X, Y, Z, nbx, nby, nbz, zblocks, nw;
@@ -336,6 +339,77 @@ __global__ __launch_bounds__(256) void ff_reopen_count_kernel(FfDims D, FfBox B,
     if (lane == 0 && hit) atomicAdd(&rec->opened_reached, (unsigned long long)__popcll(hit));
 }
 
+// The field through a shift of the map window, the translation of its first phase.  New voxel v holds old voxel v + s.
+struct FfShift { int s0, s1, s2; };
+
+__device__ __forceinline__ unsigned long long ff_wave_min(unsigned long long v) {          // every lane of the wavefront calls it; lane 0 holds the result
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long u = __shfl_down(v, o);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
+// ff_init_kernel's layout, one wavefront per 64 consecutive z of a DESTINATION column: each lane reads d_old[v + s] (64 consecutive
+// doubles s away) and its old free bit from the source column's word (a z-shift that is no multiple of 64 straddles two), the new free
+// ballot comes from the refreshed table.  fm1 = old & new and d1 go to the second buffers: the source words and values belong to other
+// columns.  A lane whose bit fell folds its finite old d into tau; the counts are reduced in the wavefront, one atomic each.
+__global__ __launch_bounds__(256) void ff_shift_kernel(FfDims D, FfShift S, const unsigned *__restrict__ cspace, const unsigned long long *__restrict__ fm_old,
+                                                        const double *__restrict__ d_old, unsigned long long *__restrict__ fm1, double *__restrict__ d1,
+                                                        FfRecord *__restrict__ rec, unsigned long long *__restrict__ cnt) {
+    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wv >= (long long)D.X * D.Y * D.zblocks) return;
+    const int lane = threadIdx.x & 63;
+    const int zb = (int)(wv % D.zblocks);
+    const long long xy = wv / D.zblocks;
+    const int z = (zb << 6) + lane;
+    const size_t v = (size_t)xy * D.Z + z;
+    const unsigned long long now = ff_free_ballot(D, cspace, v, z < D.Z);
+    const int sx = (int)(xy / D.Y) + S.s0, sy = (int)(xy % D.Y) + S.s1, sz = z + S.s2;
+    unsigned long long bits = FF_INF_BITS;
+    bool was_free = false;
+    if (z < D.Z && sx >= 0 && sx < D.X && sy >= 0 && sy < D.Y && sz >= 0 && sz < D.Z) {
+        const size_t scol = (size_t)sx * D.Y + sy;
+        bits = (unsigned long long)__double_as_longlong(d_old[scol * D.Z + sz]);
+        was_free = (fm_old[scol * D.zblocks + (sz >> 6)] >> (sz & 63)) & 1ull;
+    }
+    const unsigned long long old = __ballot(was_free);
+    const unsigned long long kept = old & now, closed = old & ~now;
+    const bool reached = ((closed >> lane) & 1ull) && bits < FF_INF_BITS;
+    const unsigned long long hit = __ballot(reached);
+    const unsigned long long tau = ff_wave_min(reached ? bits : FF_INF_BITS);
+    // (a finite d_old lies on a voxel that was free: "kept" is "the source exists and the new word is non-zero" wherever it matters)
+    if (z < D.Z) d1[v] = __longlong_as_double((long long)(((kept >> lane) & 1ull) ? bits : FF_INF_BITS));
+    if (lane != 0) return;
+    fm1[wv] = kept;
+    if (kept) atomicAdd(cnt + FF_CNT_FREE, (unsigned long long)__popcll(kept));
+    if (closed) atomicAdd(&rec->changed, (unsigned long long)__popcll(closed));
+    if (hit) {
+        atomicAdd(&rec->changed_reached, (unsigned long long)__popcll(hit));
+        atomicMin(&rec->tau_bits, tau);
+    }
+}
+
+// The leaving voxels - old voxels without a destination - close too: their finite d into tau, their number into the counters.  Over
+// the whole old grid, the index test first: only the leaving slabs' values are read.
+__global__ __launch_bounds__(256) void ff_left_kernel(FfDims D, FfShift S, const double *__restrict__ d_old, FfRecord *__restrict__ rec, unsigned long long *__restrict__ cnt) {
+    const long long n = (long long)D.X * D.Y * D.Z;
+    unsigned long long m = FF_INF_BITS, k = 0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        const long long xy = t / D.Z;
+        const int tx = (int)(xy / D.Y) - S.s0, ty = (int)(xy % D.Y) - S.s1, tz = (int)(t - xy * D.Z) - S.s2;
+        if (tx >= 0 && tx < D.X && ty >= 0 && ty < D.Y && tz >= 0 && tz < D.Z) continue;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(d_old[t]);
+        if (bits < FF_INF_BITS) { k++; m = bits < m ? bits : m; }
+    }
+    m = ff_wave_min(m);
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_down(k, o);
+    if ((threadIdx.x & 63) == 0 && k) {
+        atomicAdd(cnt + FF_CNT_LEFT, k);
+        atomicMin(&rec->tau_bits, m);
+    }
+}
+
 // GridMap3D::isInMap / getGridIndex as isdf_frontend_astar_search restates them (Gridmap3D.cpp:41-69,135-175)
 struct FfMap { int X, Y, Z; double res, bmin[3], bmax[3]; };
 __host__ __device__ inline bool ff_cell(const FfMap &M, const double p[3], int idx[3]) {
@@ -529,7 +603,8 @@ extern "C" int isdf_frontend_field_release(isdf_ctx *c) {
     (void)hipSetDevice(c->device);
     fe.d_field.release(); fe.d_field_free.release(); fe.d_field_list.release(); fe.d_field_flags.release(); fe.d_field_cnt.release();
     fe.h_field_cnt.release(); fe.d_field_rep.release(); fe.h_field_rep.release(); fe.d_field_open.release();
-    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false;
+    fe.d_field_shift.release(); fe.d_field_free_shift.release();
+    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false;
     return ISDF_OK;
 }
 
@@ -545,7 +620,7 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     if (n_vox > (size_t)0x7FFFFFF0) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the field indexes voxels with 31 bits");
     *info_out = isdf_frontend_field_info{};
     HIPCHK(c, hipSetDevice(c->device));
-    fe.field_valid = false; fe.field_repaired = false; fe.field_reopened = false;
+    fe.field_valid = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false;
     if (!fe.d_cspace) {                                    // the table stays on the device: nothing of it comes to the host
         const int rc = isdf_frontend_cspace(c, nullptr, nullptr);
         if (rc != ISDF_OK) return rc;
@@ -607,7 +682,7 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     fe.field_max_rounds = params ? params->max_rounds : 0;
     fe.field_free_voxels = n_free;
     fe.field_reached_voxels = (long long)h[FF_CNT_REACHED];
-    fe.field_repaired = false; fe.field_reopened = false;
+    fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false;
     info_out->reachable = fe.field_reachable ? 1 : 0;
     info_out->status = fe.field_status;
     info_out->rounds = (int32_t)R.rounds;
@@ -744,6 +819,113 @@ int isdf_field_change_end(isdf_ctx *c, FfChange dir, const int lo[3], const int 
     return ISDF_OK;
 }
 
+// ---- the field carried through a shift of the map window (called by map_shift.hip; the rule and its proof: DESIGN 4.6.4)
+bool isdf_field_shift_wanted(const isdf_ctx *c, const int32_t s[3]) {
+    const isdf_ctx::FrontEnd &fe = c->fe;
+    if (c->field_shift_mode != 1 || !fe.built || !fe.field_valid || fe.field_status == 2 || !fe.d_cspace || !fe.d_field) return false;
+    const int dims[3] = {c->grid.X, c->grid.Y, c->grid.Z};
+    for (int a = 0; a < 3; a++) {
+        if (s[a] <= -dims[a] || s[a] >= dims[a]) return false;                              // everything left
+        const long long g = (long long)fe.field_goal[a] - s[a];                              // goal' = goal - s
+        if (fe.field_goal[a] < 0 || g < 0 || g >= dims[a]) return false;
+    }
+    return true;
+}
+
+// Enqueues, after the shift's configuration-space refresh on the ctx's stream: the translation into the second buffers, which then
+// change places with the field's own, the leaving voxels' tau, the closing direction's reset on the translated graph, ff_compact_kernel
+// and the record's and the counters' copies to the host.  The goal cell becomes goal'.  The caller synchronises the stream, then calls
+// ..._end.
+int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    for (int a = 0; a < 3; a++) fe.field_goal[a] -= s[a];
+    FfDims D = ff_dims(c);
+    D.goal = ff_goal_index(c);
+    const int n_bricks = D.nbx * D.nby * D.nbz;
+    const size_t n_vox = (size_t)D.X * D.Y * D.Z, n_cols = (size_t)D.X * D.Y * D.zblocks;
+    if (fe.d_field_shift.reserve(c, n_vox) || fe.d_field_free_shift.reserve(c, n_cols) || fe.d_field_rep.reserve(c, 1) || fe.h_field_rep.reserve(c, 2) ||
+        fe.d_field_cnt.reserve(c, FF_CNT_WORDS) || fe.h_field_cnt.reserve(c, FF_CNT_WORDS))
+        return ISDF_ERR_HIP;
+    FfRecord *h = fe.h_field_rep.get(), *rec = fe.d_field_rep.get();
+    h[0] = h[1] = ff_record_empty();
+    unsigned long long *cnt = fe.d_field_cnt.get();
+    unsigned *flags = fe.d_field_flags.get();
+    const FfShift S{s[0], s[1], s[2]};
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipEventRecord(ev_start, st));
+    HIPCHK(c, hipMemcpyAsync(rec, h, sizeof(FfRecord), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
+    hipLaunchKernelGGL(ff_shift_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, S, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                       fe.d_field_free_shift.get(), fe.d_field_shift.get(), rec, cnt);
+    hipLaunchKernelGGL(ff_left_kernel, dim3(1024), dim3(256), 0, st, D, S, fe.d_field.get(), rec, cnt);
+    fe.d_field.swap(fe.d_field_shift);
+    fe.d_field_free.swap(fe.d_field_free_shift);
+    hipLaunchKernelGGL(ff_repair_reset_kernel, dim3((unsigned)n_bricks), dim3(256), 0, st, D, fe.d_field.get(), flags, rec);
+    hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h + 1, rec, sizeof(FfRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), cnt, FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    return ISDF_OK;
+}
+
+// After the stream has been synchronised: phase 1's rounds on the translated graph and its count, then phase 2 - the opening direction
+// of isdf_field_change_begin / _end over the box lo .. hi (null: the whole grid), which leaves the field valid (status 2 when either
+// phase hit the round bound).  ev: [0] recorded by ..._begin, [1] the end of phase 1, [2], [3] around phase 2.  The last reopen's report
+// is not this call's to change: it is put back.
+int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], hipEvent_t ev[4]) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    FfDims D = ff_dims(c);
+    D.goal = ff_goal_index(c);
+    const FfRecord rec = fe.h_field_rep.get()[1];          // (a copy: phase 2 uses the record again)
+    const hipStream_t st = c->stream;
+    volatile unsigned long long *h = fe.h_field_cnt.get();
+    const long long n_seeded = (long long)h[FF_CNT_ACTIVE], n_free1 = (long long)h[FF_CNT_FREE], n_left = (long long)h[FF_CNT_LEFT];
+    long long bound = n_free1;
+    if (fe.field_max_rounds > 0 && fe.field_max_rounds < bound) bound = fe.field_max_rounds;
+    FfRounds R1;
+    HIPCHK(c, ff_run_rounds(fe, D, n_seeded, bound, st, R1));
+    hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)D.X * D.Y * D.Z, fe.d_field_cnt.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[1], st));
+    HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), fe.d_field_cnt.get(), FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    fe.field_free_voxels = n_free1;                        // what the opening direction starts from: the translated graph's counts
+    fe.field_reached_voxels = (long long)h[FF_CNT_REACHED];
+
+    const bool had_reopen = fe.field_reopened;
+    const isdf_field_reopen_info last_reopen = fe.field_reopen;
+    int kept = 0;
+    int rc = isdf_field_change_begin(c, FfChange::Opening, lo, hi, ev[2]);
+    if (rc == ISDF_OK && hipStreamSynchronize(st) != hipSuccess) rc = isdf_fail(c, ISDF_ERR_HIP, "field carry: the opening mark failed");
+    if (rc == ISDF_OK) rc = isdf_field_change_end(c, FfChange::Opening, lo, hi, ev[2], ev[3], &kept);
+    const isdf_field_reopen_info O = fe.field_reopen;
+    fe.field_reopened = had_reopen; fe.field_reopen = last_reopen;
+    if (rc != ISDF_OK) return rc;
+    // fm1 is a subset of the new free set by construction: a bit against the opening direction is a defect, not a reason to drop
+    if (!kept) return isdf_fail(c, ISDF_ERR_STATE, "field carry: a free bit of the translated graph is not free in the new map");
+    if (R1.status == 2 && fe.field_reachable) fe.field_status = 2;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    fe.field_shifted = true;
+    isdf_field_shift_info &I = fe.field_shift;
+    I = isdf_field_shift_info{};
+    for (int a = 0; a < 3; a++) { I.shift[a] = s[a]; I.goal_new[a] = fe.field_goal[a]; }
+    I.left_reached = n_left;
+    I.closed_voxels = (int64_t)rec.changed;
+    I.closed_reached = (int64_t)rec.changed_reached;
+    std::memcpy(&I.tau, &rec.tau_bits, sizeof(double));
+    I.reset_voxels = (int64_t)(rec.reset + rec.changed_reached);
+    I.seeded_bricks_close = (int32_t)rec.seeded; I.rounds_close = (int32_t)R1.rounds;
+    I.opened_voxels = O.opened_voxels; I.opened_reached = O.opened_reached; I.goal_opened = O.goal_opened;
+    I.seeded_bricks_open = O.seeded_bricks; I.rounds_open = O.rounds;
+    I.brick_visits = R1.visits + O.brick_visits;
+    I.free_voxels = O.free_voxels; I.reached_voxels = O.reached_voxels;
+    I.reachable = fe.field_reachable ? 1 : 0; I.status = fe.field_status;
+    I.device_ms = (double)ms + O.device_ms;
+    return ISDF_OK;
+}
+
 namespace {
 
 int ff_set_mode(isdf_ctx *c, int mode, int isdf_ctx::*slot, const char *bad_mode) {
@@ -773,6 +955,18 @@ extern "C" int isdf_frontend_field_reopen_info(isdf_ctx *c, isdf_field_reopen_in
 
 extern "C" void isdf_frontend_field_reopen_sizes(int sizes_out[1]) {
     if (sizes_out) sizes_out[0] = (int)sizeof(isdf_field_reopen_info);
+}
+
+extern "C" int isdf_frontend_field_set_shift(isdf_ctx *c, int mode) {
+    return ff_set_mode(c, mode, &isdf_ctx::field_shift_mode, "the field's shift mode is 0 (drop) or 1 (carry)");
+}
+
+extern "C" int isdf_frontend_field_shift_info(isdf_ctx *c, isdf_field_shift_info *out) {
+    return c ? ff_last_info(c, out, c->fe.field_shifted, c->fe.field_shift, "no carried shift since the last isdf_frontend_field_build") : ISDF_ERR_INVALID_ARG;
+}
+
+extern "C" void isdf_frontend_field_shift_sizes(int sizes_out[1]) {
+    if (sizes_out) sizes_out[0] = (int)sizeof(isdf_field_shift_info);
 }
 
 extern "C" int isdf_frontend_field_set_repair(isdf_ctx *c, int mode) {
@@ -912,3 +1106,29 @@ extern "C" int isdf_frontend_field_reopen_host(const uint32_t *free_mask_new, co
     });
 }
 
+extern "C" int isdf_frontend_field_shift_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t shift[3], const int32_t goal_index_old[3],
+                                              double *d_inout, isdf_field_shift_info *info_out) {
+    if (!shift) return ISDF_ERR_INVALID_ARG;
+    bool goal_left = false;
+    isdf_field_shift_info I{};
+    const int rc = ff_host_form(free_mask_new, dims, n_att, goal_index_old, d_inout, &I, [&](const int g[3], isdf_field_shift_info &J) {
+        const int s[3] = {shift[0], shift[1], shift[2]};
+        isdf_host::FieldShiftCounts C;
+        const bool goal_free = isdf_host::field_shift(free_mask_new, dims[0], dims[1], dims[2], n_att, s, g, d_inout, &C);
+        goal_left = C.goal_left;
+        for (int a = 0; a < 3; a++) { J.shift[a] = s[a]; J.goal_new[a] = g[a] - s[a]; }
+        J.left_reached = C.left_reached;
+        J.closed_voxels = J.closed_reached = C.close.closed_reached;      // (no old table: as isdf_frontend_field_repair_host)
+        J.tau = C.close.tau;
+        J.reset_voxels = C.close.reset_voxels;
+        J.opened_voxels = J.opened_reached = C.open.newly_reached;        // (as isdf_frontend_field_reopen_host)
+        J.goal_opened = C.open.goal_opened ? 1 : 0;
+        J.free_voxels = C.open.free_voxels;
+        J.reached_voxels = C.open.reached_voxels;
+        return goal_free;
+    });
+    if (rc < 0) return rc;
+    if (goal_left) I.status = ISDF_FIELD_SHIFT_GOAL_LEFT;
+    if (info_out) *info_out = I;
+    return goal_left ? ISDF_FIELD_SHIFT_GOAL_LEFT : rc;
+}

@@ -11,6 +11,7 @@
 // and the grid has at most 801 attitudes: visit_kernels_by_distance (:850-909) pops at most maxdeepth + 1 = 801 attitudes, and only
 // then does its breadth-first order reach every attitude of the grid.
 #pragma once
+#include "map_shift_host.hpp"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -114,12 +115,14 @@ inline bool field_dijkstra(const uint32_t *mask, int X, int Y, int Z, int n_att,
 //   every finite d >= tau becomes +inf, and Dijkstra runs on from the kept voxels as its sources.
 // The result has the bytes of field_dijkstra on mask_new.  Returns true when the goal cell is inside the map and free in mask_new.
 struct FieldRepairCounts { long long closed_reached = 0, reset_voxels = 0, free_voxels = 0, reached_voxels = 0; double tau = 0.0; };
-inline bool field_repair(const uint32_t *mask_new, int X, int Y, int Z, int n_att, const int goal[3], double *d, FieldRepairCounts *counts) {
+// tau_left: the smallest d of reached voxels that are no longer part of d at all (field_shift's leaving voxels); they closed as well.
+inline bool field_repair(const uint32_t *mask_new, int X, int Y, int Z, int n_att, const int goal[3], double *d, FieldRepairCounts *counts,
+                         double tau_left = std::numeric_limits<double>::infinity()) {
     const size_t nw = 4 * (size_t)((n_att + 127) / 128);
     const size_t n = (size_t)X * Y * Z;
     const double inf = std::numeric_limits<double>::infinity();
     FieldRepairCounts C;
-    C.tau = inf;
+    C.tau = tau_left;
     const std::vector<unsigned char> fr = field_free_bytes(mask_new, nw, n, &C.free_voxels);
     for (size_t v = 0; v < n; v++)
         if (!fr[v] && d[v] < inf) { C.closed_reached++; if (d[v] < C.tau) C.tau = d[v]; }
@@ -175,6 +178,58 @@ inline bool field_reopen(const uint32_t *mask_new, int X, int Y, int Z, int n_at
     C.newly_reached = C.reached_voxels - C.reached_before;
     if (counts) *counts = C;
     return goal_in && fr[g] != 0;
+}
+
+// The field CARRIED through a shift of the map window by s (bits move both ways).  d: on entry the field of goal_old on
+// the old table; mask_new: the table after the shift (new voxel v holds old voxel v + s, entering voxels free, the bands at the faces
+// changed either way).  On return d is the field of goal' = goal_old - s on mask_new, the bytes of field_dijkstra.
+//   d1 = d translated by msh_shift_grid's index rule, +inf where there is no source;
+//   tau_left = the smallest finite old d of a voxel without a destination;
+//   phase 1: field_repair with tau_left on mask_new restricted to the voxels with a finite d1 - an overlap voxel that was free and
+//   unreached stays unreached on a subgraph of the old graph, so no old table is needed; its own tau covers the finite d1 whose new
+//   word is 0;
+//   phase 2: field_reopen on mask_new.
+// A goal' outside the map: goal_left, everything +inf, false.  Returns true when the goal cell is inside the map and free in mask_new.
+struct FieldShiftCounts { long long left_reached = 0; bool goal_left = false; FieldRepairCounts close; FieldReopenCounts open; };
+inline bool field_shift(const uint32_t *mask_new, int X, int Y, int Z, int n_att, const int s[3], const int goal_old[3], double *d, FieldShiftCounts *counts) {
+    const size_t nw = 4 * (size_t)((n_att + 127) / 128);
+    const size_t n = (size_t)X * Y * Z;
+    const double inf = std::numeric_limits<double>::infinity();
+    const int32_t dims[3] = {X, Y, Z}, s32[3] = {s[0], s[1], s[2]};
+    const int goal[3] = {goal_old[0] - s[0], goal_old[1] - s[1], goal_old[2] - s[2]};
+    FieldShiftCounts C;
+    size_t g;
+    if (!field_goal_voxel(X, Y, Z, goal_old, &g) || !field_goal_voxel(X, Y, Z, goal, &g)) {
+        for (size_t v = 0; v < n; v++) d[v] = inf;
+        C.goal_left = true;
+        C.close.tau = inf;
+        if (counts) *counts = C;
+        return false;
+    }
+    auto inside = [&](long long x, long long y, long long z) { return x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z; };
+    double tau_left = inf;
+    {
+        size_t v = 0;
+        for (int x = 0; x < X; x++)
+            for (int y = 0; y < Y; y++)
+                for (int z = 0; z < Z; z++, v++)
+                    if (!inside((long long)x - s[0], (long long)y - s[1], (long long)z - s[2]) && d[v] < inf) { C.left_reached++; if (d[v] < tau_left) tau_left = d[v]; }
+    }
+    isdf::msh_shift_grid(d, sizeof(double), dims, s32, d);
+    std::vector<uint32_t> mask1(mask_new, mask_new + n * nw);
+    {
+        size_t v = 0;
+        for (int x = 0; x < X; x++)
+            for (int y = 0; y < Y; y++)
+                for (int z = 0; z < Z; z++, v++) {
+                    if (!inside((long long)x + s[0], (long long)y + s[1], (long long)z + s[2])) d[v] = inf;       // (the grid's zero fill)
+                    if (!(d[v] < inf)) for (size_t w = 0; w < nw; w++) mask1[nw * v + w] = 0u;
+                }
+    }
+    (void)field_repair(mask1.data(), X, Y, Z, n_att, goal, d, &C.close, tau_left);
+    const bool goal_free = field_reopen(mask_new, X, Y, Z, n_att, goal, d, &C.open);
+    if (counts) *counts = C;
+    return goal_free;
 }
 
 }  // namespace isdf_host

@@ -210,9 +210,14 @@ struct isdf_ctx {
         // the last repair's and the last reopen's report (field_repaired, field_reopened: there was one since the build)
         bool field_repaired = false; isdf_field_repair_info field_repair{};
         bool field_reopened = false; isdf_field_reopen_info field_reopen{};
+        // the field carried through a shift of the map window: where the translated d and free bits are written; each
+        // then changes places with d_field / d_field_free (one more copy of both stays allocated); the last carry's report
+        DevBuf<double> d_field_shift; DevBuf<unsigned long long> d_field_free_shift;
+        bool field_shifted = false; isdf_field_shift_info field_shift{};
     } fe;
     int field_repair_mode = 0;                  // isdf_frontend_field_set_repair: outlives isdf_frontend_build (fe is reset by it)
     int field_reopen_mode = 0;                  // isdf_frontend_field_set_reopen: likewise
+    int field_shift_mode = 0;                   // isdf_frontend_field_set_shift: likewise
     int traj_watch_mode = 0;                    // isdf_traj_check_set_watch: outlives the check (the watch itself: TrajCheckState::w)
     struct isdf_xchg *xchg = nullptr;           // peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip)
     isdf_progress_fn progress = nullptr;        // isdf_set_progress: the optimizer drivers' progress / cancel hook

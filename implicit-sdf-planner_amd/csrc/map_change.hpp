@@ -71,8 +71,9 @@ struct MapUpdateState {
     isdf::DevBuf<unsigned> d_shift_counts, d_shift_cspace; isdf::DevBuf<uint8_t> d_shift_occ;
     hipEvent_t ev_scan[2] = {nullptr, nullptr};          // map_scan.hip: around the ray stage
     // [0], [1]: a count (translation) stage; [2], [3]: the ESDF stage; [4], [5]: the front-end stage; [6], [7]: the field's in-place
-    // change inside map_frontend_stage, either direction (a scan's two stages use them one after the other)
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // change inside map_frontend_stage, either direction (a scan's two stages use them one after the other); [6] .. [9]: the field
+    // carried through a shift, its two phases
+    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     ~MapUpdateState() {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_scan) if (e) (void)hipEventDestroy(e);
@@ -100,7 +101,7 @@ inline hipError_t map_records_fetch(MapUpdateState &S, hipStream_t st) { return 
 // it), the error message stays.  The occupancy and the counts are consistent with each other and stay.
 void mu_drop_derived(isdf_ctx *c, bool voxels);
 // map changed: the voxel forms' counts no longer describe the occupancy, the bit grid is stale, a valid cost-to-go field is dropped
-// (returns 1 then: a driver that repairs it asks isdf_field_change_wanted first)
+// (returns 1 then: a driver that repairs it asks isdf_field_change_wanted - the shift: isdf_field_shift_wanted - first)
 int map_changed(isdf_ctx *c, bool voxels);
 // ... and what a refresh over a list decides before its first stage: the dirty box, grown for the front end, which products are
 // refreshed (an ESDF that is switched off is dropped here) and whether a cap of the params is exceeded

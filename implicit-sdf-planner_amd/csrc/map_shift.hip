@@ -12,7 +12,8 @@
 // destination is a second buffer that then changes places with the ctx's own: no overlap of source and destination, no copy back.
 // Everything else is existing code: isdf_generate_esdf on the shifted occupancy, the whole inflated bit map, the boxed
 // configuration-space kernel over the bands (map_shift_host.hpp), the pack / scatter path into the A*'s host copy - the shared steps
-// of map_change.hpp.
+// of map_change.hpp.  A valid cost-to-go field is dropped or, with isdf_frontend_field_set_shift(1), carried after the front-end
+// refresh (frontend_field.hip: isdf_field_shift_wanted / _begin / _end).
 #include "isdf_ctx.hpp"
 #include "frontend_dev.hpp"
 #include "map_shift_host.hpp"
@@ -128,7 +129,8 @@ int shift_params(isdf_ctx *c, const isdf_map_shift_params *params, isdf_map_shif
 unsigned grid_blocks(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 2048); }
 
 // everything after the translated counts and occupancy took the place of the old ones
-int shift_refresh(isdf_ctx *c, MapUpdateState &S, bool full, const MuBox *boxes, int n_boxes, bool watch, isdf_map_shift_info &info) {
+// carry: the cost-to-go field follows the shift (isdf_field_shift_wanted, asked before the field was dropped)
+int shift_refresh(isdf_ctx *c, MapUpdateState &S, bool full, const MuBox *boxes, int n_boxes, bool watch, bool carry, isdf_map_shift_info &info) {
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     isdf_ctx::FrontEnd &fe = c->fe;
@@ -144,7 +146,19 @@ int shift_refresh(isdf_ctx *c, MapUpdateState &S, bool full, const MuBox *boxes,
     HIPCHK(c, hipEventRecord(S.ev[4], st));
     if (fe.built && !full && (rc = isdf_frontend_map_bits(c))) return rc;
     if ((rc = map_frontend_launch(c, S, true, full, boxes, boxes, fe.d_cspace ? n_boxes : 0, F, false))) return rc;
+    if (carry && (rc = isdf_field_shift_begin(c, info.shift, S.ev[6]))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
+    if (carry) {                        // outside the bands the translated word is the new one: the opening mark looks at their hull
+        const bool whole = full || n_boxes == 0;
+        MuBox hull{};
+        for (int b = 0; b < n_boxes && !whole; b++)
+            for (int a = 0; a < 3; a++) {
+                hull.lo[a] = b ? std::min(hull.lo[a], boxes[b].lo[a]) : boxes[b].lo[a];
+                hull.hi[a] = b ? std::max(hull.hi[a], boxes[b].hi[a]) : boxes[b].hi[a];
+            }
+        if ((rc = isdf_field_shift_end(c, info.shift, whole ? nullptr : hull.lo, whole ? nullptr : hull.hi, &S.ev[6]))) return rc;
+        info.field_dropped = 0;
+    }
     if (F.patch) {                      // the A*'s copy: translated in place by the host form's own function, then the bands
         const int32_t d32[3] = {G.X, G.Y, G.Z};
         msh_shift_grid(fe.h_cspace, 4 * (size_t)((fe.xk * fe.yk + 127) / 128) * sizeof(uint32_t), d32, info.shift, fe.h_cspace);
@@ -222,6 +236,7 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     for (int a = 0; a < 3; a++) { G.bmin[a] = info.bmin_new[a] = nb0[a]; G.bmax[a] = nb1[a]; }
     c->grid_epoch++;                    // voxel indices changed their meaning
     c->bricks_stale = true;
+    const bool carry = isdf_field_shift_wanted(c, s);   // (asked before the field is dropped: it stays invalid until the carry has gone through)
     info.field_dropped = map_changed(c, false);
     if ((rc = map_hand_over(c, S, nullptr, "map shift", false))) return rc;
     const MshRecord R = S.h_rec.get()->shift;
@@ -230,7 +245,7 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     info.counts_left = (long long)R.counts_left;
     const bool full = full_known || (P.force_path != 1 && !R.any_occ);
     info.path = full ? ISDF_MAP_SHIFT_FULL : ISDF_MAP_SHIFT_INCREMENTAL;
-    rc = shift_refresh(c, S, full, boxes, n_boxes, watch, info);
+    rc = shift_refresh(c, S, full, boxes, n_boxes, watch, carry, info);
     if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
     info.wall_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     if (info_out) *info_out = info;

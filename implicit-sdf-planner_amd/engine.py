@@ -328,6 +328,31 @@ def frontend_field_reopen_host(free_mask_new, goal_index, n_att, d, lib=None):
     return out, bool(rc), info
 
 
+def frontend_field_shift_host(free_mask_new, shift, goal_index_old, n_att, d, lib=None):
+    """isdf_frontend_field_shift_host: the field `d` of `goal_index_old` (float64 [X, Y, Z], on the table before the shift) carried through
+    a shift of the map window by `shift` in plain host code - d translated (new voxel v holds old voxel v + shift), the leaving and the
+    closed voxels' threshold reset and relaxed on the translated graph, then the opened voxels relaxed on free_mask_new (the table after
+    the shift).  Returns (d_new [X, Y, Z], code, IsdfFieldShiftInfo): code 1 the goal cell goal_index_old - shift is free, 0 it is not,
+    capi.FIELD_SHIFT_GOAL_LEFT it lies outside the grid (all +inf); `d` itself is not changed."""
+    lib = lib or capi.load_library()
+    m = np.ascontiguousarray(free_mask_new, dtype=np.uint32)
+    nw = 4 * ((int(n_att) + 127) // 128)
+    if m.ndim != 4 or m.shape[3] != nw:
+        raise ValueError(f"free_mask_new must be [X, Y, Z, {nw}]")
+    out = np.array(d, dtype=np.float64, order="C")
+    if out.shape != m.shape[:3]:
+        raise ValueError(f"d must be {m.shape[:3]}")
+    dims = np.array(m.shape[:3], dtype=np.int32)
+    s = np.ascontiguousarray(shift, dtype=np.int32).reshape(3)
+    g = np.ascontiguousarray(goal_index_old, dtype=np.int32).reshape(3)
+    info = capi.IsdfFieldShiftInfo()
+    rc = lib.isdf_frontend_field_shift_host(m.ctypes.data_as(C.c_void_p), dims.ctypes.data_as(C.c_void_p), int(n_att), s.ctypes.data_as(C.c_void_p),
+                                            g.ctypes.data_as(C.c_void_p), _p(out), C.byref(info))
+    if rc < 0:
+        raise IsdfError(rc, "isdf_frontend_field_shift_host: bad arguments")
+    return out, int(rc), info
+
+
 def _scan_geometry(bmin, bmax, dims, origin):
     return (np.ascontiguousarray(bmin, dtype=np.float64).reshape(3), np.ascontiguousarray(bmax, dtype=np.float64).reshape(3),
             (C.c_int32 * 3)(*[int(v) for v in dims]), np.ascontiguousarray(origin, dtype=np.float64).reshape(3))
@@ -1007,6 +1032,17 @@ class Engine:
         """isdf_frontend_field_reopen_info: the last reopen's IsdfFieldReopenInfo (ISDF_ERR_STATE: none since the last build)."""
         info = capi.IsdfFieldReopenInfo()
         self._check(self.lib.isdf_frontend_field_reopen_info(self.h, C.byref(info)))
+        return info
+
+    def frontend_field_set_shift(self, mode):
+        """isdf_frontend_field_set_shift: what shift_map / map_follow do with a valid field - 0 (default) drop it, 1 carry it (the
+        values translated, the leaving and the closed voxels' threshold reset and relaxed, then the entering and the opened voxels)."""
+        self._check(self.lib.isdf_frontend_field_set_shift(self.h, int(mode)))
+
+    def frontend_field_shift_info(self):
+        """isdf_frontend_field_shift_info: the last carry's IsdfFieldShiftInfo (ISDF_ERR_STATE: none since the last build)."""
+        info = capi.IsdfFieldShiftInfo()
+        self._check(self.lib.isdf_frontend_field_shift_info(self.h, C.byref(info)))
         return info
 
     def frontend_field_release(self):

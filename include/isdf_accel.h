@@ -1247,6 +1247,71 @@ void isdf_frontend_field_reopen_sizes(int sizes_out[1]);      /* sizeof of the s
 int isdf_frontend_field_reopen_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t goal_index[3],
                                     double *d_inout, isdf_field_reopen_info *info_out);
 
+/* ---- the field carried through a shift of the map window ------------------------------------------------------ */
+/* isdf_shift_map / isdf_map_follow (below) move bits BOTH ways: with s the shift, new voxel v holds old voxel v + s; the voxels of
+ * the leaving slabs vanish, the entering slabs appear free, and the words of the bands at the faces change either way.  The goal
+ * is a cell and moves with the content: goal' = goal - s.  After the shift's configuration-space refresh, in two phases:
+ *   1. translate and close: d1[v] = d_old[v + s] where the source exists and v's new word is non-zero, else +inf;
+ *      fm1[v] = fm_old[v + s] & free_new[v] (0 for an entering voxel).  closed = every leaving voxel and every overlap voxel that
+ *      was free and is not; tau = the least finite old d over them; then 4.6.2's reset (every finite d1 >= tau becomes +inf) and
+ *      relaxation on the graph fm1, from the bricks that hold a reset voxel.
+ *   2. open: 4.6.3 unchanged, fm1 against the new words - the entering slabs are among the opened voxels; d[goal'] = 0 when the
+ *      goal cell opened.
+ * Why the bytes are those of isdf_frontend_field_build towards goal' on a fresh ctx: in old indices G1 = fm_old & free_new is a
+ * subgraph of the old graph, and the closed set is exactly what the old graph has and G1 lacks, so 4.6.2's argument gives the least
+ * fixed point on G1; G1 is a subgraph of the new graph and every kept value is the sum along a path that still exists, so 4.6.3's
+ * argument gives the least fixed point on the new map.  fm1 is a subset of the new free set by construction: phase 2 never sees a
+ * bit against its direction (if it does, the call fails with ISDF_ERR_STATE - a defect, not a drop).
+ * isdf_frontend_field_set_shift: mode 0 (default) - a shift drops a valid field, field_dropped = 1; mode 1 - a shift carries a
+ * valid field, on both of its paths, with and without the A*'s host table, on the ctx's stream after the front-end refresh;
+ * afterwards field_dropped = 0 and isdf_frontend_field_get / _value / _paths[_device] answer as after isdf_frontend_field_build
+ * towards the centre of cell goal' on the new map.  A field without a reachable goal (all +inf) is carried too and becomes reachable
+ * when its goal cell opens.  A phase that hits its round bound (the free voxels of its graph, or the max_rounds of the build) leaves a
+ * valid status-2 field, as the build does.  Also with mode 1 the field is dropped, field_dropped = 1, when it had status 2, when
+ * there is no configuration-space table, when goal' lies outside the grid, when |s_a| >= dims_a on some axis (everything left), or
+ * when a step fails (the shift then fails as a whole and drops every derived product).  s = 0 touches nothing.  One more copy of d
+ * and of the free bits stays allocated (8 B + 1 bit per voxel); nothing is allocated after the first carried shift of a size.
+ * The mode outlives isdf_frontend_build and is independent of isdf_frontend_field_set_repair / _set_reopen.  Other modes:
+ * ISDF_ERR_INVALID_ARG; a multi-device ctx: ISDF_ERR_UNSUPPORTED. */
+int isdf_frontend_field_set_shift(isdf_ctx *ctx, int mode);
+#define ISDF_FIELD_SHIFT_GOAL_LEFT 3   /* isdf_frontend_field_shift_host: status and return value when goal' lies outside the grid */
+typedef struct isdf_field_shift_info {
+    int32_t shift[3];           /* s                                                                                          */
+    int32_t goal_new[3];        /* goal' = goal - s, the field's goal cell after the call                                     */
+    int64_t left_reached;       /* leaving voxels (no destination) that held a finite d                                       */
+    int64_t closed_voxels;      /* overlap voxels whose free bit fell                                                         */
+    int64_t closed_reached;     /* ... that held a finite d                                                                   */
+    double tau;                 /* the least d among left_reached and closed_reached; +inf when there is none                 */
+    int64_t reset_voxels;       /* overlap voxels whose d became +inf in phase 1: closed_reached + the kept voxels with d >= tau */
+    int64_t opened_voxels;      /* voxels free in the new map and not in fm1: the entering free voxels and the opened overlap */
+    int64_t opened_reached;     /* ... that have a finite d afterwards                                                        */
+    int64_t brick_visits;       /* bricks relaxed, over all rounds of both phases                                             */
+    int64_t free_voxels;        /* of the new map                                                                             */
+    int64_t reached_voxels;     /* voxels with a finite d afterwards                                                          */
+    int32_t seeded_bricks_close, rounds_close;      /* phase 1: bricks that reset a voxel, launches of the relaxation         */
+    int32_t seeded_bricks_open, rounds_open;        /* phase 2: bricks that hold an opened voxel, launches of the relaxation  */
+    int32_t goal_opened;        /* 1: the goal cell was among the opened voxels                                               */
+    int32_t reachable, status;  /* as isdf_frontend_field_info; host form: ISDF_FIELD_SHIFT_GOAL_LEFT when goal' is outside   */
+    int32_t reserved;
+    double device_ms;           /* device time of both phases, from the translation to the end of the counts                  */
+} isdf_field_shift_info;
+/* The last carry's report; ISDF_ERR_STATE when there was none since the last isdf_frontend_field_build.  It does not touch
+ * isdf_frontend_field_repair_info / _reopen_info, and a repair or a reopen does not touch it. */
+int isdf_frontend_field_shift_info(isdf_ctx *ctx, isdf_field_shift_info *out);
+void isdf_frontend_field_shift_sizes(int sizes_out[1]);       /* sizeof of the struct above, for mirrors of this header        */
+/* The same rule in plain host code, no ctx and no device.  d_inout: on entry the field of goal_index_old on the OLD table, on
+ * return the field of goal_index_old - shift on free_mask_new (isdf_frontend_field_host's layout, the table after the shift), the
+ * bytes of isdf_frontend_field_host.  d is translated by isdf_shift_grid_host's index rule with +inf where there is no source; tau
+ * is taken over the leaving finite values and over the finite values whose new word is 0; phase 1 is
+ * isdf_frontend_field_repair_host's rule on the table free_mask_new restricted to the voxels with a finite translated d (a voxel
+ * that was free and unreached stays unreached on a subgraph, so no old table is needed), phase 2 isdf_frontend_field_reopen_host's
+ * on free_mask_new.  info_out may be NULL.  No old table is given: closed_voxels = closed_reached, opened_voxels = opened_reached =
+ * the voxels that were +inf after phase 1 and are finite now; the brick and round counts and device_ms stay 0.  Returns 1 (the goal
+ * cell is in the map and free), 0 (in the map, not free: all +inf), ISDF_FIELD_SHIFT_GOAL_LEFT (goal' lies outside the grid: all
+ * +inf, status likewise), or a negative isdf_status. */
+int isdf_frontend_field_shift_host(const uint32_t *free_mask_new, const int32_t dims[3], int n_att, const int32_t shift[3],
+                                   const int32_t goal_index_old[3], double *d_inout, isdf_field_shift_info *info_out);
+
 /* ---- the map updated in place from new sensor points ---------------------------------------------------------- */
 /* isdf_set_pointcloud rebuilds everything from the full cloud.  isdf_update_pointcloud takes only the NEW points (n_points x 3
  * floats, binned as isdf_set_pointcloud bins them: a point outside the box counts for voxel (0,0,0)), adds them to the per-voxel
@@ -1491,12 +1556,12 @@ long long isdf_raycast_host(const uint8_t *occ, const double bmin[3], const doub
  * occupied any more, or |s| >= dims on some axis (everything left: the empty map) - path 2, the whole-map kernels, the host copy
  * marked stale.  s = 0: path 0, nothing is touched.
  * Voxel indices change their meaning: the grid epoch advances (a report of isdf_traj_check from before the shift is stale for
- * isdf_points_merge_check), a valid cost-to-go field is dropped (field_dropped), an armed clearance watch (isdf_traj_check_set_watch)
- * is checked again against the new map and stays armed (watch_rechecked).  The obstacle-point set, lastTstar and a kept swept mesh
+ * isdf_points_merge_check), a valid cost-to-go field is dropped (field_dropped) or, with isdf_frontend_field_set_shift(1), carried
+ * towards the same cell at its new index (field_dropped = 0), an armed clearance watch (isdf_traj_check_set_watch) is checked again against the new map and stays armed (watch_rechecked).  The obstacle-point set, lastTstar and a kept swept mesh
  * are world-space and stay.  A failure after the counts moved drops the ESDF and the front end, as a failing update does.
  * ISDF_ERR_UNSUPPORTED on a multi-device ctx, ISDF_ERR_STATE without a map or without kept counts (a map from isdf_set_grid).
  * Nothing is allocated after the first call of a size beyond what isdf_generate_esdf and the watch's re-check allocate.
- * params may be NULL (defaults), info_out may be NULL.  Not offered: an incremental ESDF, a translated cost-to-go field. */
+ * params may be NULL (defaults), info_out may be NULL.  Not offered: an incremental ESDF. */
 #define ISDF_MAP_SHIFT_NONE 0
 #define ISDF_MAP_SHIFT_INCREMENTAL 1
 #define ISDF_MAP_SHIFT_FULL 2
