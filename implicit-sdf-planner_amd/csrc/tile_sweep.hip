@@ -136,6 +136,10 @@ constexpr int SW_SAMPLES = 4;
 // producer still works (the fused launch below), and nothing has to be cleared between steps.
 constexpr int TL_THREADS = 128;                        // tail: threads per piece (one per sample, K + 1 <= 128 per pass)
 constexpr int TL_GROUPS = TL_THREADS / PARTIAL_STRIDE;     // 6 row groups x 20 columns
+// A tail thread's row of the partial-sum array holds, until the scatter fills it, the values the thread formed before the
+// collision sums arrived (tail_piece): basis rows b0[1..5], b1[2..5], b2[3..5], b3[4..5], jerk, snap.
+constexpr int PK_B0 = 0, PK_B1 = 5, PK_B2 = 9, PK_B3 = 12, PK_JER = 14, PK_SNA = 17;
+static_assert(PK_SNA + 3 <= PARTIAL_STRIDE + 1, "the parked values fit a row of the partial-sum array");
 constexpr unsigned long long SLOT_EMPTY = ~0ull;
 constexpr int SLOT_SPIN_MAX = 1 << 20;                 // bounded wait: a lost producer must not hang the stream
 __device__ __forceinline__ void slot_publish(double *slot, double v) {
@@ -1454,6 +1458,22 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
                 Basis B;
                 poly_basis(j * step, B);
                 vel = ct_beta<1>(c, ld, B.b1); acc3 = ct_beta<2>(c, ld, B.b2); jer0 = ct_beta<3>(c, ld, B.b3);
+                // what only the scatter at the end needs - the basis rows past their structural zeros and constants, jerk and
+                // snap - is formed here, once, and parked in this thread's own row of s_val: the row is idle until the scatter
+                // writes its results into it, so the values cost neither registers across the passes below nor a second
+                // evaluation (and a second fetch of the coefficients) after the collision sums have arrived
+                const d3 sna0 = ct_beta<4>(c, ld, B.b4);
+                double *const park = s_val[tid];
+#pragma unroll
+                for (int r = 1; r < 6; r++) park[PK_B0 + r - 1] = B.b0[r];
+#pragma unroll
+                for (int r = 2; r < 6; r++) park[PK_B1 + r - 2] = B.b1[r];
+#pragma unroll
+                for (int r = 3; r < 6; r++) park[PK_B2 + r - 3] = B.b2[r];
+#pragma unroll
+                for (int r = 4; r < 6; r++) park[PK_B3 + r - 4] = B.b3[r];
+                park[PK_JER] = jer0.x; park[PK_JER + 1] = jer0.y; park[PK_JER + 2] = jer0.z;
+                park[PK_SNA] = sna0.x; park[PK_SNA + 1] = sna0.y; park[PK_SNA + 2] = sna0.z;
             }
             TL_MARK(0);
             double pena = 0.0;
@@ -1517,17 +1537,30 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
             }
             d3 gP, gV, gA, gJ;
             TL_MARK(2);
+            // the parked values come back under the reverse mode (the row index is laundered so that the reads are reads,
+            // not the registers of the stores above kept alive); the basis' structural zeros and constants are written out
+            int prow = tid;
+            asm volatile("" : "+v"(prow));
+            const double *const park = s_val[prow];
+            Basis B;
+            B.b0[0] = 1.0;
+            B.b1[0] = 0.0; B.b1[1] = 1.0;
+            B.b2[0] = 0.0; B.b2[1] = 0.0; B.b2[2] = 2.0;
+            B.b3[0] = 0.0; B.b3[1] = 0.0; B.b3[2] = 0.0; B.b3[3] = 6.0;
+#pragma unroll
+            for (int r = 1; r < 6; r++) B.b0[r] = park[PK_B0 + r - 1];
+#pragma unroll
+            for (int r = 2; r < 6; r++) B.b1[r] = park[PK_B1 + r - 2];
+#pragma unroll
+            for (int r = 3; r < 6; r++) B.b2[r] = park[PK_B2 + r - 3];
+#pragma unroll
+            for (int r = 4; r < 6; r++) B.b3[r] = park[PK_B3 + r - 4];
+            const d3 jer = mk3(park[PK_JER], park[PK_JER + 1], park[PK_JER + 2]), sna = mk3(park[PK_SNA], park[PK_SNA + 1], park[PK_SNA + 2]);
             flat_backward_from(P.flat, vel, acc3, fs, ft, gradPos, gradVel, gradQuat, gradOmg, gP, gV, gA, gJ);
             TL_MARK(3);
             const double node = (j == 0 || j == P.K) ? 0.5 : 1.0;
             const double alpha = j * integral_frac;
-            double *o = s_val[tid];
-            // the basis is formed again here (15 multiplications) instead of living in 60 registers across the passes above
-            double s1 = j * step;
-            asm volatile("" : "+v"(s1));
-            Basis B;
-            poly_basis(s1, B);
-            const d3 jer = ct_beta<3>(c, ld, B.b3), sna = ct_beta<4>(c, ld, B.b4);      // likewise jerk and snap (same bits as above)
+            double *o = s_val[tid];               // (every parked value is in a register by now: the row takes the results)
             const double gPv[3] = {gP.x, gP.y, gP.z}, gVv[3] = {gV.x, gV.y, gV.z}, gAv[3] = {gA.x, gA.y, gA.z}, gJv[3] = {gJ.x, gJ.y, gJ.z};
             // rows below a basis' derivative order meet its structural zeros: those products are skipped (same bits)
 #pragma unroll
