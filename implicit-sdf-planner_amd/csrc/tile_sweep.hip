@@ -140,6 +140,12 @@ constexpr int TL_GROUPS = TL_THREADS / PARTIAL_STRIDE;     // 6 row groups x 20 
 // collision sums arrived (tail_piece): basis rows b0[1..5], b1[2..5], b2[3..5], b3[4..5], jerk, snap.
 constexpr int PK_B0 = 0, PK_B1 = 5, PK_B2 = 9, PK_B3 = 12, PK_JER = 14, PK_SNA = 17;
 static_assert(PK_SNA + 3 <= PARTIAL_STRIDE + 1, "the parked values fit a row of the partial-sum array");
+// The row's spare last double: the sample's cost term, for the early sum of a fused device-resident step (tail_piece).  Nothing
+// else ever writes it: the parked values end below it, the scatter's results and the column sums use columns 0..PARTIAL_STRIDE-1.
+constexpr int PK_COST = PARTIAL_STRIDE;
+static_assert(PK_COST >= PK_SNA + 3 && PK_COST < PARTIAL_STRIDE + 1, "the cost term's column is free and inside the row");
+constexpr int TL_COST_WAVE = TL_THREADS / 64;          // the fused tail's wavefront behind its sample threads: sums the cost terms
+static_assert(TL_COST_WAVE < SW_SAMPLES - 1, "that wavefront is neither a sample thread's nor the one that runs plan_wave");
 constexpr unsigned long long SLOT_EMPTY = ~0ull;
 constexpr int SLOT_SPIN_MAX = 1 << 20;                 // bounded wait: a lost producer must not hang the stream
 __device__ __forceinline__ void slot_publish(double *slot, double v) {
@@ -152,6 +158,18 @@ __device__ __forceinline__ unsigned long long slot_peek(const double *slot) {
 }
 __device__ __forceinline__ void slot_clear(double *slot) {
     __hip_atomic_store((unsigned long long *)slot, SLOT_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the same three for slots in LDS, between wavefronts of one workgroup (the fused tail's cost terms)
+__device__ __forceinline__ void lds_slot_publish(double *slot, double v) {
+    unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+    if (bits == SLOT_EMPTY) bits = 0x7FF8000000000000ull;
+    __hip_atomic_store((unsigned long long *)slot, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ unsigned long long lds_slot_peek(const double *slot) {
+    return __hip_atomic_load((const unsigned long long *)slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void lds_slot_clear(double *slot) {
+    __hip_atomic_store((unsigned long long *)slot, SLOT_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 // the same three for slots other GPUs write or read (boards of the in-kernel exchange: IPC-mapped uncached memory)
 // peers may start their step later than this rank: the wait for a row is bounded by the device wall clock (XFuse::timeout_ticks =
@@ -1432,6 +1450,24 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
             lost = lost || !s_staged;
         }
     }
+    // Order of publication.  A piece's cost is the sum of node * step * pena over its samples, and pena is complete the moment the
+    // collision sums are taken: a fused single-GPU step whose results stay on the device publishes the cost THERE, so that the
+    // hand-over to the collector (an agent-scope store, a polled load, across XCDs) and the collector's sum run under the pieces'
+    // reverse mode, scatter and column sums instead of after them.  Every other step keeps the cost behind the rows: the
+    // separate tail launch has nothing to hide it under, a host-direct step's rows must be released before the cost is visible
+    // (below), and an exchange step's cost travels with its rows to the peers.
+    // The sample threads leave their cost terms in the rows' spare column, each an 8-byte slot that is its own "ready" flag like
+    // the slots in device memory; the wavefront behind them, idle otherwise, empties the column first (one barrier, ahead of all
+    // the work), picks the terms up as they land and adds them in the shape of the late column sums.  The sample threads' work
+    // stays ONE block: cut in two around a barrier at the collision sums, the reverse mode no longer reuses the forward pass's
+    // values but forms them again, the compiler contracts other products into FMAs, and gradT moves in its last bit.
+    const bool early_cost = !EARLY && !XF && P.host_flag == nullptr;
+    if constexpr (!EARLY && !XF) {
+        if (early_cost) {
+            if ((tid >> 6) == TL_COST_WAVE) for (int row = tid & 63; row < TL_THREADS; row += 64) lds_slot_clear(&s_val[row][PK_COST]);
+            __syncthreads();
+        }
+    }
     const PieceIn pin = piece_in(P, b, i);
     const double *c = pin.c;
     const int ld = pin.ld;
@@ -1440,6 +1476,10 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
     double colsum = 0.0;   // threads 0..19: running sum of their output column, samples in ascending order
     unsigned long long tl_c0 = 0, tl_marks = 0;
     if (dbg && tid == 0) { dbg[0] = wall_clock64(); tl_c0 = clock64(); }
+#if ISDF_SWEEP_STATS
+    __shared__ unsigned long long s_tl_pub;     // clock stamp of the wavefront that publishes the cost early, for thread 0's marks
+    if (dbg && tid == 0) __hip_atomic_store(&s_tl_pub, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#endif
 #define TL_MARK(k) do { if (dbg && tid == 0) tl_marks |= (((clock64() - tl_c0) >> 4) & 0xFFFFull) << (16 * (k)); } while (0)
     // (a fused step has K + 1 <= TL_THREADS - sweep_can_fuse - and says so: with a loop the compiler hoists the constants of the
     // penalties' polynomials out of it, runs out of the fused kernels' 168 vector registers and spills them to scratch memory)
@@ -1537,6 +1577,8 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
             }
             d3 gP, gV, gA, gJ;
             TL_MARK(2);
+            // pena is complete: the sample's cost term - the expression of o[19] below - into the row's spare double
+            if constexpr (!EARLY && !XF) if (early_cost) lds_slot_publish(&s_val[tid][PK_COST], ((j == 0 || j == P.K) ? 0.5 : 1.0) * step * pena);
             // the parked values come back under the reverse mode (the row index is laundered so that the reads are reads,
             // not the registers of the stores above kept alive); the basis' structural zeros and constants are written out
             int prow = tid;
@@ -1557,7 +1599,7 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
             for (int r = 4; r < 6; r++) B.b3[r] = park[PK_B3 + r - 4];
             const d3 jer = mk3(park[PK_JER], park[PK_JER + 1], park[PK_JER + 2]), sna = mk3(park[PK_SNA], park[PK_SNA + 1], park[PK_SNA + 2]);
             flat_backward_from(P.flat, vel, acc3, fs, ft, gradPos, gradVel, gradQuat, gradOmg, gP, gV, gA, gJ);
-            TL_MARK(3);
+            if (!early_cost) TL_MARK(3);          // (early cost: mark 3 is the publishing wavefront's)
             const double node = (j == 0 || j == P.K) ? 0.5 : 1.0;
             const double alpha = j * integral_frac;
             double *o = s_val[tid];               // (every parked value is in a register by now: the row takes the results)
@@ -1576,6 +1618,30 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
             o[18] = (dot3(gP, vel) + dot3(gV, acc3) + dot3(gA, jer) + dot3(gJ, sna)) * alpha * node * step + node * integral_frac * pena;
             o[19] = node * step * pena;
         }
+        if constexpr (!EARLY && !XF) {
+            if (early_cost && (tid >> 6) == TL_COST_WAVE) {
+                // The cost, early, in the very shape of the column sums below - TL_GROUPS partial sums over rows g, g + TL_GROUPS,
+                // ... ascending from 0.0, then those in order onto 0.0 - so it has the bits the late sum of column 19 has (which is
+                // still formed, and not stored to the slot).  A term arrives after its thread's own bounded poll, at the latest.
+                const int lane = tid & 63, n = min(TL_THREADS, K1 - j0);
+                // (one lane per row waits for the row's term; the sums then read the column with plain loads, which the compiler
+                // issues together - a lane that polled its group's rows one after the other took 0.7 us over a full column)
+                for (int row = lane; row < n; row += 64)
+                    while (lds_slot_peek(&s_val[row][PK_COST]) == SLOT_EMPTY) __builtin_amdgcn_s_sleep(1);
+                wave_lds_sync();
+                double part = 0.0;
+                if (lane < TL_GROUPS) for (int row = lane; row < n; row += TL_GROUPS) part += s_val[row][PK_COST];
+                double cost = 0.0;
+#pragma unroll
+                for (int g = 0; g < TL_GROUPS; g++) cost += __shfl(part, g);
+                if (lane == 0) {
+                    slot_publish(&P.piece_cost[gp], cost);
+#if ISDF_SWEEP_STATS
+                    if (dbg) __hip_atomic_store(&s_tl_pub, (unsigned long long)clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // mark 3: the cost is on its way
+#endif
+                }
+            }
+        }
         __syncthreads();
         // column sums in two fixed-shape stages: TL_GROUPS partial sums per column (rows g, g + TL_GROUPS, ...), then their sum
         {
@@ -1593,6 +1659,9 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
         }
         __syncthreads();
     }
+#if ISDF_SWEEP_STATS
+    if (dbg && tid == 0 && early_cost) tl_marks |= (((__hip_atomic_load(&s_tl_pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - tl_c0) >> 4) & 0xFFFFull) << 48;
+#endif
     if (dbg && tid == 0) { dbg[2] = tl_marks; dbg[3] = (clock64() - tl_c0) >> 4; }
 #undef TL_MARK
     if (P.host_flag) lost = __syncthreads_or(lost ? 1 : 0) != 0;      // host-direct step: the overflow word must be up before the piece's cost is
@@ -1615,7 +1684,7 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
             if (P.host_flag) { if (lost && P.stats) atomicMax(&P.stats[4], 1ull); __builtin_amdgcn_fence(__ATOMIC_RELEASE, ""); }
             if constexpr (XF) {
                 for (int r = 0; r < P.xf.world; r++) xslot_publish(P.xf.board[r] + (size_t)P.xf.parity * P.xf.parity_stride + (size_t)gp * XF_ROW + 19, colsum);
-            } else slot_publish(&P.piece_cost[gp], colsum);
+            } else if (!early_cost) slot_publish(&P.piece_cost[gp], colsum);      // (early cost: the slot has it since the collision sums were taken)
         }
     }
     }   // mine

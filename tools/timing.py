@@ -70,6 +70,19 @@ def main():
     f = lambda k: ((mk >> (16 * k)) & 0xFFFF) * 16
     print("tail  thread 0 cycles since start: derivatives", pct(f(0)), "| forward+dynamics", pct(f(1)), "| collision terms", pct(f(2)), "| backward", pct(f(3)), "| partials+sums", pct(tl[:, 3] * 16))
     print("tail  block duration us:", pct((tl[:, 1] - tl[:, 0]) / 100.0))
+    # The end of the launch, per tail workgroup.  The last piece's workgroup is the collector: it sums the pieces' costs and writes the
+    # trajectory's.  A piece's cost is published at the end of its column sums (`sums end`: the late order) or, on the fused
+    # device-resident path, by the tail's third wave right after the collision sums were taken (`mark 3`: that wave's stamp; on every
+    # other path mark 3 is thread 0's stamp behind the reverse mode).  Cycles are placed on the wall clock through the sweep's median MHz.
+    mhz = float(np.median(cyc / np.maximum(1, (sc[:, 6] - sc[:, 0]) / 100.0)))
+    at = lambda cycles: us(tl[:, 0]) + cycles / mhz
+    taken, mark3, sums_end, end = at(f(2)), at(f(3)), at(tl[:, 3] * 16), us(tl[:, 1])
+    print("tail  per piece (us): start | sums taken | mark 3 | sums end | end")
+    for p in range(N):
+        print("  piece %3d: %6.2f | %6.2f | %6.2f | %6.2f | %6.2f%s" % (p, us(tl[p, 0]), taken[p], mark3[p], sums_end[p], end[p], "   <- collector" if p == N - 1 else ""))
+    if N > 1:
+        print("launch end: latest sums taken %.2f | latest mark 3 of a non-collector %.2f | latest sums end of a non-collector %.2f | slowest non-collector end %.2f | collector done %.2f"
+              % (taken.max(), mark3[:-1].max(), sums_end[:-1].max(), end[:-1].max(), end[-1]))
 
 
 
