@@ -193,6 +193,37 @@ class IsdfMapRaycastInfo(C.Structure):
                 ("steps_total", C.c_int64), ("cast_ms", C.c_double)]
 
 
+class IsdfDepthCamera(C.Structure):
+    """isdf_depth_camera (include/isdf_accel.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class IsdfDepthRenderParams(C.Structure):
+    """isdf_depth_render_params (include/isdf_accel.h)."""
+    _fields_ = [("splat_m", C.c_double), ("min_depth_m", C.c_double), ("max_splat_px", C.c_int32), ("source", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class IsdfDepthRenderInfo(C.Structure):
+    """isdf_depth_render_info (include/isdf_accel.h)."""
+    _fields_ = [("n_points", C.c_int64), ("n_behind", C.c_int64), ("n_outside", C.c_int64), ("n_near", C.c_int64), ("n_splat_pixels", C.c_int64),
+                ("n_pixels_set", C.c_int64), ("render_ms", C.c_double)]
+
+
+class IsdfDepthRaysParams(C.Structure):
+    """isdf_depth_rays_params (include/isdf_accel.h)."""
+    _fields_ = [("stride_u", C.c_int32), ("stride_v", C.c_int32), ("min_range_m", C.c_double), ("max_range_m", C.c_double), ("no_return_is_free", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class IsdfDepthRaysInfo(C.Structure):
+    """isdf_depth_rays_info (include/isdf_accel.h)."""
+    _fields_ = [("n_pixels", C.c_int64), ("n_no_return", C.c_int64), ("n_below_min", C.c_int64), ("n_truncated", C.c_int64), ("n_clipped", C.c_int64),
+                ("n_hits", C.c_int64), ("rays_ms", C.c_double)]
+
+
+DEPTH_SOURCE_CLOUD, DEPTH_SOURCE_MAP = 0, 1
+DEPTH_I32_MM, DEPTH_U16_MM, DEPTH_F32_M = 0, 1, 2
+DEPTH_EMPTY_MM = 999999
 RAYCAST_CLEAR, RAYCAST_HIT, RAYCAST_END_OUTSIDE, RAYCAST_ORIGIN_OUTSIDE = 0, 1, 2, 3       # a row's status
 RAYCAST_ROW = 8                                                                           # int32 per ray: status, steps, i, j, k, axis, num, den
 
@@ -361,6 +392,9 @@ EXPORTED_SYMBOLS = [
     "isdf_map_clear_params_default", "isdf_map_clear_sizes", "isdf_clear_pointcloud", "isdf_clear_voxels", "isdf_clear_esdf_host", "isdf_clear_touched_host",
     "isdf_map_scan_params_default", "isdf_map_scan_sizes", "isdf_integrate_scan", "isdf_scan_sets_host", "isdf_scan_ray_host",
     "isdf_map_raycast_params_default", "isdf_map_raycast_sizes", "isdf_map_raycast", "isdf_map_raycast_device", "isdf_raycast_host",
+    "isdf_depth_render_params_default", "isdf_depth_render_sizes", "isdf_depth_render", "isdf_depth_render_device", "isdf_depth_render_host",
+    "isdf_depth_rays_params_default", "isdf_depth_rays_sizes", "isdf_depth_rays_rows", "isdf_depth_rays", "isdf_depth_rays_device", "isdf_depth_rays_host",
+    "isdf_integrate_depth",
     "isdf_map_shift_params_default", "isdf_map_shift_sizes", "isdf_shift_map", "isdf_map_follow", "isdf_shift_geometry_host", "isdf_shift_grid_host",
     "isdf_shift_bands_host",
 ]
@@ -638,6 +672,35 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfMapRaycastParams), C.sizeof(IsdfMapRaycastInfo)]:
         raise RuntimeError(f"isdf_map_raycast structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfMapRaycastParams), C.sizeof(IsdfMapRaycastInfo)]}")
+    cp, qp, qi = C.POINTER(IsdfDepthCamera), C.POINTER(IsdfDepthRenderParams), C.POINTER(IsdfDepthRenderInfo)
+    yp, yi = C.POINTER(IsdfDepthRaysParams), C.POINTER(IsdfDepthRaysInfo)
+    lib.isdf_depth_render_params_default.argtypes = [qp]
+    lib.isdf_depth_render_params_default.restype = None
+    lib.isdf_depth_render_sizes.argtypes = [ip]
+    lib.isdf_depth_render_sizes.restype = None
+    lib.isdf_depth_render.argtypes = [C.c_void_p, cp, dp, C.c_void_p, C.c_longlong, qp, C.c_void_p, qi]
+    lib.isdf_depth_render_device.argtypes = [C.c_void_p, cp, dp, C.c_void_p, C.c_longlong, qp, C.c_void_p, qi, C.c_void_p]
+    lib.isdf_depth_render_host.argtypes = [cp, dp, C.c_void_p, C.c_longlong, C.c_void_p, dp, C.c_double, C.POINTER(C.c_int32), qp, C.c_void_p, qi]
+    lib.isdf_depth_rays_params_default.argtypes = [yp]
+    lib.isdf_depth_rays_params_default.restype = None
+    lib.isdf_depth_rays_sizes.argtypes = [ip]
+    lib.isdf_depth_rays_sizes.restype = None
+    lib.isdf_depth_rays_rows.argtypes = [cp, yp]
+    lib.isdf_depth_rays_rows.restype = C.c_longlong
+    lib.isdf_depth_rays.argtypes = [C.c_void_p, cp, dp, C.c_void_p, C.c_int, yp, C.c_void_p, C.c_void_p, yi]
+    lib.isdf_depth_rays_device.argtypes = [C.c_void_p, cp, dp, C.c_void_p, C.c_int, yp, C.c_void_p, C.c_void_p, yi, C.c_void_p]
+    lib.isdf_depth_rays_host.argtypes = [cp, dp, C.c_void_p, C.c_int, yp, dp, dp, C.c_double, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, yi]
+    lib.isdf_depth_rays_host.restype = C.c_longlong
+    lib.isdf_integrate_depth.argtypes = [C.c_void_p, cp, dp, C.c_void_p, C.c_int, yp, sp, yi, si]
+    sz3 = (C.c_int * 3)()
+    lib.isdf_depth_render_sizes(sz3)
+    if list(sz3) != [C.sizeof(IsdfDepthCamera), C.sizeof(IsdfDepthRenderParams), C.sizeof(IsdfDepthRenderInfo)]:
+        raise RuntimeError(f"isdf_depth_render structs: the library has {list(sz3)}, the mirror "
+                           f"{[C.sizeof(IsdfDepthCamera), C.sizeof(IsdfDepthRenderParams), C.sizeof(IsdfDepthRenderInfo)]}")
+    lib.isdf_depth_rays_sizes(sz3)
+    if list(sz3)[:2] != [C.sizeof(IsdfDepthRaysParams), C.sizeof(IsdfDepthRaysInfo)]:
+        raise RuntimeError(f"isdf_depth_rays structs: the library has {list(sz3)[:2]}, the mirror "
+                           f"{[C.sizeof(IsdfDepthRaysParams), C.sizeof(IsdfDepthRaysInfo)]}")
     hp, hi, i3 = C.POINTER(IsdfMapShiftParams), C.POINTER(IsdfMapShiftInfo), C.POINTER(C.c_int32)
     lib.isdf_map_shift_params_default.argtypes = [hp]
     lib.isdf_map_shift_params_default.restype = None

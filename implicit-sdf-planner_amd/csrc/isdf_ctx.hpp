@@ -34,6 +34,8 @@ struct MapUpdateState;          // map_change.hpp: scratch of the in-place map c
 void isdf_map_update_release_all(isdf_ctx *c);        // map_update.hip: drops it
 struct MapRaycastState;         // map_raycast.hip: staging of the host-pointer ray cast, the counters' record and its pinned copy
 void isdf_map_raycast_release_all(isdf_ctx *c);       // map_raycast.hip: drops it
+struct DepthCamState;           // depth_cam.hip: staging of the depth camera's host-pointer forms, the counters' record and its pinned copy
+void isdf_depth_cam_release_all(isdf_ctx *c);         // depth_cam.hip: drops it
 int isdf_traj_check_ready(isdf_ctx *c);               // traj_check.hip: what isdf_traj_check needs of the ctx (shape, occupancy grid), or the error
 
 // frontend_field.hip: the record of one in-place change of the cost-to-go field (voxels closed: the repair; opened: the reopen),
@@ -92,6 +94,7 @@ struct isdf_ctx {
     DevBuf<unsigned> d_counts; int counts_thr = 0;
     MapUpdateState *mup = nullptr;              // isdf_update_pointcloud / isdf_update_voxels: own scratch (grows only)
     MapRaycastState *mrc = nullptr;             // isdf_map_raycast*: own scratch (grows only)
+    DepthCamState *dcm = nullptr;               // isdf_depth_render* / isdf_depth_rays* / isdf_integrate_depth: own scratch (grows only)
     DevBuf<unsigned> d_bits; bool bits_dirty = true;
     bool have_geom = false;
     unsigned long long grid_epoch = 0;          // counts isdf_set_grid / isdf_set_pointcloud: what was derived from voxel indices of an older grid is stale
@@ -245,7 +248,7 @@ struct isdf_ctx {
     DevBuf<double> d_mpart;         // every shard of a multi-device step writes [packed outputs | 8 statistics as doubles] here
     DevBuf<double> d_mstage;        // lead, staged mode: the peers' parts copied next to each other
     // every buffer above frees itself; the states held by pointer are dropped here (isdf_destroy makes the device current)
-    ~isdf_ctx() { isdf_swept_release_all(this); isdf_traj_check_release_all(this); isdf_traj_limits_release_all(this); isdf_traj_retime_release_all(this); isdf_traj_realloc_release_all(this); isdf_map_update_release_all(this); isdf_map_raycast_release_all(this); }
+    ~isdf_ctx() { isdf_swept_release_all(this); isdf_traj_check_release_all(this); isdf_traj_limits_release_all(this); isdf_traj_retime_release_all(this); isdf_traj_realloc_release_all(this); isdf_map_update_release_all(this); isdf_map_raycast_release_all(this); isdf_depth_cam_release_all(this); }
 };
 namespace isdf { struct XFuse; }
 // xchg.hip: fills the in-kernel exchange block of a fused step when isdf_xchg_fuse is on (returns false: not requested;

@@ -97,8 +97,8 @@ int isdf::map_stage(isdf_ctx *c, MapUpdateState &S, const void *in, size_t in_by
     if ((rc = S.d_rec.reserve(c, 1)) || (rc = S.h_rec.reserve(c, 1))) return rc;
     *S.h_rec.get() = map_records_empty();
     HIPCHK(c, hipMemcpyAsync(S.d_rec, S.h_rec.get(), sizeof(MapRecords), hipMemcpyHostToDevice, st));
-    if (in_bytes) HIPCHK(c, hipMemcpyAsync(S.d_in, in, in_bytes, hipMemcpyHostToDevice, st));
-    if (in2_bytes) HIPCHK(c, hipMemcpyAsync((uint8_t *)S.d_in.get() + in_bytes, in2, in2_bytes, hipMemcpyHostToDevice, st));
+    if (in_bytes && in) HIPCHK(c, hipMemcpyAsync(S.d_in, in, in_bytes, hipMemcpyHostToDevice, st));
+    if (in2_bytes && in2) HIPCHK(c, hipMemcpyAsync((uint8_t *)S.d_in.get() + in_bytes, in2, in2_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(ev_begin, st));
     return ISDF_OK;
 }

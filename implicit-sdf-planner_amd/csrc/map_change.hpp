@@ -91,7 +91,8 @@ int map_begin(isdf_ctx *c, MapUpdateState **out);
 // list capacity: the most entries a count stage can need, and the cap it is given
 unsigned map_list_cap(long long max_voxels, unsigned long long n_in, unsigned long long n_vox);
 // stage: S.d_in reserved for `in` and `in2` (one behind the other, either may be empty) and S.d_list for list_len entries (0: no list),
-// the records uploaded empty, the input uploaded, ev_begin recorded.  Nothing allocates on a second call of the same size.
+// the records uploaded empty, the input uploaded (a null `in` / `in2` with bytes: room is kept, nothing is uploaded - the caller fills it
+// on the stream), ev_begin recorded.  Nothing allocates on a second call of the same size.
 int map_stage(isdf_ctx *c, MapUpdateState &S, const void *in, size_t in_bytes, const void *in2, size_t in2_bytes, size_t list_len, hipEvent_t ev_begin);
 // hand-over: ev_end recorded (null: none), the records to S.h_rec, one synchronisation.  The kernels before it may have run, so a
 // failure leaves "<op> hand-over: ..." in the ctx and drops what was derived from the old map.
@@ -140,5 +141,14 @@ float mu_event_ms(hipEvent_t a, hipEvent_t b);
 // are the new map's already.  map_scan.hip runs both, the clear's first.  A failure: the caller calls mu_drop_derived.
 int mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_update_info &info);
 int mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info);
+
+// ---- the scan's stages for callers that bring their rays another way (map_scan.hip; depth_cam.hip's isdf_integrate_depth)
+struct MsOrigin { int q[3]; };              // the sensor's tick
+// produce: writes n_rays end points and n_rays hit bytes into the staged buffers with work on the ctx's stream; it runs after map_stage
+// and before the trace, returns an isdf_status, and must leave the map alone
+typedef int (*MsProduce)(isdf_ctx *c, float *d_xyz, uint8_t *d_hit, void *arg);
+struct MsInput { const float *xyz; const uint8_t *hit; MsProduce produce; void *arg; };     // host arrays (hit nullable), or produce
+int scan_check(isdf_ctx *c, const char *op, const double origin[3], const void *in, long long n, const isdf_map_scan_params *params, isdf_map_scan_params &P, MsOrigin &O);
+int scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long long n_rays, const isdf_map_scan_params &P, isdf_map_scan_info *info_out);
 
 }  // namespace isdf

@@ -24,8 +24,6 @@
 
 namespace isdf {
 
-struct MsOrigin { int q[3]; };
-
 __device__ __forceinline__ bool ms_end_tick(const DevGrid &G, const float *__restrict__ xyz, long long i, int q[3]) {
     const int dims[3] = {G.X, G.Y, G.Z};
     return ms_quantize(G.bmin, G.bmax, G.res, dims, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], q);
@@ -169,7 +167,14 @@ void empty_info(isdf_map_scan_info &info) {
     }
 }
 
-int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8_t *hit, long long n_rays, const isdf_map_scan_params &P, isdf_map_scan_info *info_out) {
+}  // namespace
+
+// The stages behind the staging.  `in` names where the rays come from: the caller's arrays, uploaded by map_stage, or - in.produce - a
+// step that writes them on the ctx's stream straight into the staged buffers (depth_cam.hip: the unprojection of a depth image).
+int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long long n_rays, const isdf_map_scan_params &P, isdf_map_scan_info *info_out) {
+    const float *const xyz = in.xyz;
+    const uint8_t *const hit = in.hit;
+    const bool has_hit = hit || in.produce;
     isdf_map_scan_info info{};
     empty_info(info);
     info.n_rays = n_rays;
@@ -194,9 +199,10 @@ int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8
         HIPCHK(c, hipMemsetAsync(S.d_free_bits, 0, n_words * sizeof(unsigned), st));
         HIPCHK(c, hipMemsetAsync(S.d_hit_bits, 0, n_words * sizeof(unsigned), st));
     }
-    if ((rc = map_stage(c, S, xyz, xyz_bytes, hit, hit ? (size_t)n_rays : 0, std::max<size_t>({cap_clear, cap_update_most, 1u}), S.ev_scan[0]))) return rc;
+    if ((rc = map_stage(c, S, xyz, xyz_bytes, hit, has_hit ? (size_t)n_rays : 0, std::max<size_t>({cap_clear, cap_update_most, 1u}), S.ev_scan[0]))) return rc;
     const float *const d_xyz = (const float *)S.d_in.get();
-    const uint8_t *const d_hit = hit ? (const uint8_t *)S.d_in.get() + xyz_bytes : nullptr;
+    const uint8_t *const d_hit = has_hit ? (const uint8_t *)S.d_in.get() + xyz_bytes : nullptr;
+    if (in.produce && (rc = in.produce(c, (float *)S.d_in.get(), (uint8_t *)S.d_in.get() + xyz_bytes, in.arg))) return rc;          // nothing of the map has moved yet
     MapRecords *const d_rec = S.d_rec.get(), *const h_rec = S.h_rec.get();
     const unsigned ray_blocks = (unsigned)std::min<long long>((n_rays + 255) / 256, 2048);
 
@@ -262,24 +268,28 @@ int integrate_scan(isdf_ctx *c, const MsOrigin &O, const float *xyz, const uint8
     return ISDF_OK;
 }
 
-}  // namespace
-
-extern "C" int isdf_integrate_scan(isdf_ctx *c, const double origin[3], const float *xyz, const uint8_t *hit, long long n_rays, const isdf_map_scan_params *params,
-                                   isdf_map_scan_info *info_out) {
-    if (!c) return ISDF_ERR_INVALID_ARG;
-    if (!origin) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "integrating a scan: null origin");
-    const int rc = map_change_ready(c, "integrating a scan", xyz, n_rays, true);
+// what every entry to the scan checks before anything moves: the ctx (`in`: the caller's rays or image), the parameters, the origin
+int isdf::scan_check(isdf_ctx *c, const char *op, const double origin[3], const void *in, long long n, const isdf_map_scan_params *params, isdf_map_scan_params &P, MsOrigin &O) {
+    const int rc = map_change_ready(c, op, in, n, true);
     if (rc) return rc;
-    isdf_map_scan_params P;
     isdf_map_scan_params_default(&P);
     if (params) P = *params;
     if (P.miss_weight < 0 || P.clear.max_cleared_voxels < 0 || !(P.clear.full_fraction >= 0.0) || P.update.max_new_voxels < 0 || !(P.update.full_fraction >= 0.0))
         return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad scan parameters");
     const DevGrid &G = c->grid;
     const int dims[3] = {G.X, G.Y, G.Z};
-    MsOrigin O;
     if (!ms_quantize(G.bmin, G.bmax, G.res, dims, origin[0], origin[1], origin[2], O.q)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the scan's origin lies outside the map");
-    return integrate_scan(c, O, xyz, hit, n_rays, P, info_out);
+    return ISDF_OK;
+}
+
+extern "C" int isdf_integrate_scan(isdf_ctx *c, const double origin[3], const float *xyz, const uint8_t *hit, long long n_rays, const isdf_map_scan_params *params,
+                                   isdf_map_scan_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!origin) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "integrating a scan: null origin");
+    isdf_map_scan_params P;
+    MsOrigin O;
+    if (int rc = scan_check(c, "integrating a scan", origin, xyz, n_rays, params, P, O)) return rc;
+    return scan_integrate(c, O, MsInput{xyz, hit, nullptr, nullptr}, n_rays, P, info_out);
 }
 
 extern "C" long long isdf_scan_sets_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3], const float *xyz,

@@ -505,6 +505,124 @@ def scan_from_map(engine_or_occ, origin, ends, res=None, lib=None):
     return np.ascontiguousarray(out[keep]), np.ascontiguousarray(flag[keep]), int(len(pts) - keep.sum())
 
 
+def depth_camera(width, height, fx, fy, cx, cy):
+    """isdf_depth_camera"""
+    return capi.IsdfDepthCamera(int(width), int(height), float(fx), float(fy), float(cx), float(cy))
+
+
+def camera_from_yaml(path):
+    """The reference's local_sensing/params/camera.yaml: `key: value` lines with cam_width, cam_height, cam_fx, cam_fy, cam_cx, cam_cy
+    (other keys and # comments are ignored).  Returns an IsdfDepthCamera."""
+    vals = {}
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0]
+            if ":" in line:
+                k, v = line.split(":", 1)
+                vals[k.strip()] = v.strip()
+    missing = [k for k in ("cam_width", "cam_height", "cam_fx", "cam_fy", "cam_cx", "cam_cy") if k not in vals]
+    if missing:
+        raise ValueError(f"{path}: no {', '.join(missing)}")
+    return depth_camera(int(vals["cam_width"]), int(vals["cam_height"]), *(float(vals[k]) for k in ("cam_fx", "cam_fy", "cam_cx", "cam_cy")))
+
+
+def _pose12(cam2world):
+    """cam2world as the ABI takes it: 12 doubles, from a 3 x 4, a 4 x 4 (the last row is dropped) or 12 values"""
+    m = np.asarray(cam2world, dtype=np.float64)
+    if m.shape == (4, 4):
+        m = m[:3]
+    return np.ascontiguousarray(m.reshape(12))
+
+
+def _depth_render_params(lib, splat_m=None, min_depth_m=None, max_splat_px=None, source=None):
+    p = capi.IsdfDepthRenderParams()
+    lib.isdf_depth_render_params_default(C.byref(p))
+    if splat_m is not None:
+        p.splat_m = float(splat_m)
+    if min_depth_m is not None:
+        p.min_depth_m = float(min_depth_m)
+    if max_splat_px is not None:
+        p.max_splat_px = int(max_splat_px)
+    if source is not None:
+        p.source = int(source)
+    return p
+
+
+def _depth_rays_params(lib, stride=None, min_range_m=None, max_range_m=None, no_return_is_free=None):
+    p = capi.IsdfDepthRaysParams()
+    lib.isdf_depth_rays_params_default(C.byref(p))
+    if stride is not None:
+        p.stride_u, p.stride_v = (int(stride), int(stride)) if np.isscalar(stride) else (int(stride[0]), int(stride[1]))
+    if min_range_m is not None:
+        p.min_range_m = float(min_range_m)
+    if max_range_m is not None:
+        p.max_range_m = float(max_range_m)
+    if no_return_is_free is not None:
+        p.no_return_is_free = int(bool(no_return_is_free))
+    return p
+
+
+_DEPTH_DTYPES = {np.dtype(np.int32): capi.DEPTH_I32_MM, np.dtype(np.uint16): capi.DEPTH_U16_MM, np.dtype(np.float32): capi.DEPTH_F32_M}
+
+
+def _depth_image(cam, image):
+    """(contiguous image of the camera's shape, its ISDF_DEPTH_* format by dtype: int32 mm, uint16 mm, float32 m)"""
+    img = np.ascontiguousarray(image)
+    if img.dtype not in _DEPTH_DTYPES:
+        raise ValueError("a depth image is int32 (mm), uint16 (mm) or float32 (m)")
+    return img.reshape(cam.height, cam.width), _DEPTH_DTYPES[img.dtype]
+
+
+def _depth_rows(lib, cam, p):
+    n = lib.isdf_depth_rays_rows(C.byref(cam), C.byref(p))
+    if n < 0:
+        raise IsdfError(int(n), "isdf_depth_rays_rows")
+    return int(n)
+
+
+def depth_render_host(cam, cam2world, xyz=None, occ=None, bmin=None, res=None, lib=None, **params):
+    """isdf_depth_render_host: the depth image (int32 [height, width], millimetres, 999999 = empty) of the cloud xyz (n x 3 float32), or -
+    xyz None - of the centres of the occupied voxels of occ [X, Y, Z] with the map's bmin and res, in plain host code.  params: splat_m,
+    min_depth_m, max_splat_px.  Returns (image, IsdfDepthRenderInfo)."""
+    lib = lib or capi.load_library()
+    pose = _pose12(cam2world)
+    image = np.zeros((cam.height, cam.width), dtype=np.int32)
+    info = capi.IsdfDepthRenderInfo()
+    if xyz is not None:
+        pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        p = _depth_render_params(lib, source=capi.DEPTH_SOURCE_CLOUD, **params)
+        rc = lib.isdf_depth_render_host(C.byref(cam), _p(pose), pts.ctypes.data_as(C.c_void_p), pts.shape[0], None, None, 0.0, None, C.byref(p),
+                                        image.ctypes.data_as(C.c_void_p), C.byref(info))
+    else:
+        o8 = np.ascontiguousarray(occ, dtype=np.uint8)
+        b0 = np.ascontiguousarray(bmin, dtype=np.float64).reshape(3)
+        p = _depth_render_params(lib, source=capi.DEPTH_SOURCE_MAP, **params)
+        rc = lib.isdf_depth_render_host(C.byref(cam), _p(pose), None, 0, o8.ctypes.data_as(C.c_void_p), _p(b0), float(res), (C.c_int32 * 3)(*o8.shape), C.byref(p),
+                                        image.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc != capi.ISDF_OK:
+        raise IsdfError(int(rc), "isdf_depth_render_host")
+    return image, info
+
+
+def depth_rays_host(cam, cam2world, image, bmin, bmax, res, dims, lib=None, **params):
+    """isdf_depth_rays_host: the depth image (int32 mm, uint16 mm or float32 m, by dtype) unprojected, cut to range and clipped to the map
+    (bmin, bmax, res, dims) in plain host code.  params: stride (one number or (u, v)), min_range_m, max_range_m, no_return_is_free.
+    Returns (ends float32 [n, 3] - NaN rows for dropped pixels -, hit uint8 [n], IsdfDepthRaysInfo)."""
+    lib = lib or capi.load_library()
+    pose = _pose12(cam2world)
+    img, fmt = _depth_image(cam, image)
+    p = _depth_rays_params(lib, **params)
+    b0, b1, d, _ = _scan_geometry(bmin, bmax, dims, np.zeros(3))
+    n = _depth_rows(lib, cam, p)
+    ends, hit = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.uint8)
+    info = capi.IsdfDepthRaysInfo()
+    rc = lib.isdf_depth_rays_host(C.byref(cam), _p(pose), img.ctypes.data_as(C.c_void_p), fmt, C.byref(p), _p(b0), _p(b1), float(res), d,
+                                  ends.ctypes.data_as(C.c_void_p), hit.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc < 0:
+        raise IsdfError(int(rc), "isdf_depth_rays_host")
+    return ends, hit, info
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -809,6 +927,78 @@ class Engine:
         self._check(self.lib.isdf_map_raycast_device(self.h, op, C.c_void_p(d_ends.data_ptr()), n, C.byref(p), C.c_void_p(d_rows.data_ptr()),
                                                      None if info is None else C.byref(info), C.c_void_p(st)))
         return info
+
+    # ---- the depth camera (csrc/depth_cam.hip)
+    def depth_render(self, cam, cam2world, xyz=None, **params):
+        """isdf_depth_render: the depth image (int32 [height, width], millimetres, 999999 = empty) of the cloud xyz (n x 3 float32) or -
+        xyz None - of the ctx's own occupied voxels, rendered on the device, read-only.  params: splat_m, min_depth_m, max_splat_px.
+        Returns (image, IsdfDepthRenderInfo)."""
+        pose = _pose12(cam2world)
+        image = np.zeros((cam.height, cam.width), dtype=np.int32)
+        info = capi.IsdfDepthRenderInfo()
+        if xyz is None:
+            p = _depth_render_params(self.lib, source=capi.DEPTH_SOURCE_MAP, **params)
+            pts, n = None, 0
+        else:
+            p = _depth_render_params(self.lib, source=capi.DEPTH_SOURCE_CLOUD, **params)
+            pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+            n = pts.shape[0]
+        self._check(self.lib.isdf_depth_render(self.h, C.byref(cam), _p(pose), None if pts is None else pts.ctypes.data_as(C.c_void_p), n, C.byref(p),
+                                               image.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return image, info
+
+    def depth_render_device(self, cam, cam2world, d_xyz, d_image, want_info=True, stream=None, **params):
+        """isdf_depth_render_device: d_xyz (float32 [n, 3]; None: the ctx's map) and d_image (int32 [height, width]) are torch tensors on
+        the ctx's device; the work goes on `stream` (None: torch's current stream).  want_info False: info_out = NULL - nothing is
+        counted, handed over or synchronised; returns None then."""
+        import torch
+        pose = _pose12(cam2world)
+        assert d_image.dtype == torch.int32 and d_image.is_contiguous() and tuple(d_image.shape) == (cam.height, cam.width)
+        if d_xyz is None:
+            p = _depth_render_params(self.lib, source=capi.DEPTH_SOURCE_MAP, **params)
+            xp, n = None, 0
+        else:
+            assert d_xyz.dtype == torch.float32 and d_xyz.is_contiguous() and d_xyz.shape[1] == 3
+            p = _depth_render_params(self.lib, source=capi.DEPTH_SOURCE_CLOUD, **params)
+            xp, n = C.c_void_p(d_xyz.data_ptr()), int(d_xyz.shape[0])
+        info = capi.IsdfDepthRenderInfo() if want_info else None
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._check(self.lib.isdf_depth_render_device(self.h, C.byref(cam), _p(pose), xp, n, C.byref(p), C.c_void_p(d_image.data_ptr()),
+                                                      None if info is None else C.byref(info), C.c_void_p(st)))
+        return info
+
+    def depth_rays(self, cam, cam2world, image, **params):
+        """isdf_depth_rays: the depth image (int32 mm, uint16 mm or float32 m, by dtype) unprojected on the device, cut to range and clipped
+        to the ctx's map.  params: stride, min_range_m, max_range_m, no_return_is_free.  Returns (ends float32 [n, 3], hit uint8 [n],
+        IsdfDepthRaysInfo) - what integrate_scan takes, the camera's position as the origin."""
+        pose = _pose12(cam2world)
+        img, fmt = _depth_image(cam, image)
+        p = _depth_rays_params(self.lib, **params)
+        n = _depth_rows(self.lib, cam, p)
+        ends, hit = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.uint8)
+        info = capi.IsdfDepthRaysInfo()
+        self._check(self.lib.isdf_depth_rays(self.h, C.byref(cam), _p(pose), img.ctypes.data_as(C.c_void_p), fmt, C.byref(p), ends.ctypes.data_as(C.c_void_p),
+                                             hit.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return ends, hit, info
+
+    def integrate_depth(self, cam, cam2world, image, stride=None, min_range_m=None, max_range_m=None, no_return_is_free=None, miss_weight=None,
+                        max_cleared_voxels=None, max_new_voxels=None, full_fraction=None, refresh_esdf=True, refresh_frontend=True):
+        """isdf_integrate_depth: integrate_scan of the rays depth_rays_host gives for the image, with only the image uploaded.  The first
+        four params are depth_rays', the others integrate_scan's.  Returns (IsdfDepthRaysInfo, IsdfMapScanInfo)."""
+        pose = _pose12(cam2world)
+        img, fmt = _depth_image(cam, image)
+        rp = _depth_rays_params(self.lib, stride=stride, min_range_m=min_range_m, max_range_m=max_range_m, no_return_is_free=no_return_is_free)
+        p = capi.IsdfMapScanParams()
+        self.lib.isdf_map_scan_params_default(C.byref(p))
+        if miss_weight is not None:
+            p.miss_weight = int(miss_weight)
+        p.clear = self._map_clear_params(max_cleared_voxels=max_cleared_voxels, full_fraction=full_fraction, refresh_esdf=refresh_esdf, refresh_frontend=refresh_frontend)
+        p.update = self._map_update_params(max_new_voxels=max_new_voxels, full_fraction=full_fraction, refresh_esdf=refresh_esdf, refresh_frontend=refresh_frontend)
+        dinfo, sinfo = capi.IsdfDepthRaysInfo(), capi.IsdfMapScanInfo()
+        self._check(self.lib.isdf_integrate_depth(self.h, C.byref(cam), _p(pose), img.ctypes.data_as(C.c_void_p), fmt, C.byref(rp), C.byref(p), C.byref(dinfo),
+                                                  C.byref(sinfo)))
+        self._watch_refresh_rows()
+        return dinfo, sinfo
 
     # ---- the map window shifted in place (csrc/map_shift.hip)
     def _map_shift_params(self, full_fraction=None, force_path=None):

@@ -1541,6 +1541,128 @@ int isdf_map_raycast_device(isdf_ctx *ctx, const double *d_origins, const float 
 long long isdf_raycast_host(const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
                             const double *origins, const float *ends, long long n, const isdf_map_raycast_params *params, int32_t *rows_out);
 
+/* ---- the depth camera: a depth image rendered on the device, and one integrated into the map -------------------- */
+/* The sensor of the reference is a simulated depth camera (src/uav_simulator/local_sensing/src/depth_render.cu:2-56, driven by
+ * pcl_render_node.cpp:271-296, unprojected again in render_pcl_world, :224-269; intrinsics in local_sensing/params/camera.yaml).
+ * The camera: width, height in [1, 4096], fx, fy > 0, cx, cy, all finite.  The pose is cam2world: 12 doubles, the rows (R | t) of
+ * the rigid 4x4, row-major, z the optical axis, all finite.  Anything else: ISDF_ERR_INVALID_ARG.
+ *
+ * RENDER.  image = height x width int32 millimetres, row-major, 999999 where nothing reached the pixel (depth_initial).
+ * world2cam = (R^T, -R^T t), formed in fp64 - the translation's row i is -(R_0i t_0 + R_1i t_1 + R_2i t_2), summed left to right -
+ * and rounded to float32 once; fx_f = (float)fx, fy_f = (float)fy as the reference's Parameter holds them; cx, cy stay fp64.  Per point
+ * (x, y, z), float32, nothing contracted into an FMA (depth_render.cu:12-32):
+ *   X = x * w00 + y * w01 + z * w02 + w03, Y and Z likewise from rows 1 and 2, each summed left to right
+ *   not (Z > 0): dropped, n_behind (the reference's Z <= 0; a NaN too).  Z < (float)min_depth_m: dropped, n_near.
+ *   px = (int)((double)(X / Z * fx_f) + cx + 0.5), py = (int)((double)(Y / Z * fy_f) + cy + 0.5): the conversion truncates towards
+ *   zero, so a value in (-1, 0) lands in column (row) 0, as in the reference.  Stated without the conversion's overflow: the point is
+ *   kept when the fp64 value v satisfies -1 < v < width (height), otherwise dropped, n_outside (the centre pixel must be in the image,
+ *   depth_render.cu:23).
+ *   dist_mm = (int)(Z * 1000.0f + 0.5f) in float32 (2^31 or more: INT32_MAX, which changes no pixel)
+ *   r = (int)(splat_m * (double)fx_f / (double)Z + (double)0.5f) - the reference's `0.0573 * para.fx / dist + 0.5f`: double * float /
+ *   float + float, all promoted to double -, 4096 when that is 4096 or more (it then covers any image), then at most max_splat_px
+ *   when that is > 0.
+ *   every pixel (px + j, py + i), -r <= i, j <= r, inside the image takes min(its value, dist_mm).
+ * A minimum over integers does not depend on the order of the atomics: isdf_depth_render_host gives the device's image byte for byte.
+ * ISDF_DEPTH_SOURCE_CLOUD renders xyz (n x 3 floats; n = 0 is legal: every pixel 999999).  ISDF_DEPTH_SOURCE_MAP renders the centres
+ * of the ctx's occupied voxels, bmin + (v + 0.5) * resolution in fp64 rounded to float32, in one pass over the occupancy bytes that
+ * uploads nothing (xyz and n are ignored); ISDF_ERR_STATE without an occupancy grid.
+ * info: n_points (given, or the occupied voxels), n_behind, n_near, n_outside, n_splat_pixels = the sum of the clipped windows' sizes,
+ * n_pixels_set = pixels that are not 999999 at the end, render_ms.  All counts are sums: the host form repeats them (render_ms 0).
+ * The call is read-only, like the ray cast; a multi-device ctx: ISDF_ERR_UNSUPPORTED.  isdf_depth_render stages through grow-only
+ * buffers of its own: nothing is allocated after the first call of a size.  isdf_depth_render_device: d_xyz and d_image_out are device
+ * memory, the work (the clear of the image included) is put on `stream`; with info_out == NULL nothing is counted, handed over or
+ * synchronised, with it `stream` is synchronised once.  params may be NULL (defaults). */
+#define ISDF_DEPTH_SOURCE_CLOUD 0
+#define ISDF_DEPTH_SOURCE_MAP 1
+#define ISDF_DEPTH_EMPTY_MM 999999
+typedef struct isdf_depth_camera {
+    int32_t width, height;
+    double fx, fy, cx, cy;
+} isdf_depth_camera;
+typedef struct isdf_depth_render_params {
+    double splat_m;             /* default 0.0573, the reference's live constant; >= 0                                         */
+    double min_depth_m;         /* default 0; a point nearer than this is dropped; >= 0                                        */
+    int32_t max_splat_px;       /* default 0 = unlimited, as in the reference (at Z = 0.1 m its r is 222: 198 025 pixels from   */
+                                /* one point); otherwise r is clamped to it; < 0: ISDF_ERR_INVALID_ARG                         */
+    int32_t source;             /* ISDF_DEPTH_SOURCE_*                                                                         */
+    int32_t reserved[4];
+} isdf_depth_render_params;
+typedef struct isdf_depth_render_info {
+    int64_t n_points, n_behind, n_outside, n_near, n_splat_pixels, n_pixels_set;
+    double render_ms;           /* device time, events on the ctx's stream (the device form: on `stream`), the clear included   */
+} isdf_depth_render_info;
+void isdf_depth_render_params_default(isdf_depth_render_params *p);     /* null-safe */
+void isdf_depth_render_sizes(int sizes_out[3]);                         /* null-safe; sizeof of the three structs above */
+int isdf_depth_render(isdf_ctx *ctx, const isdf_depth_camera *camera, const double cam2world[12], const float *xyz, long long n,
+                      const isdf_depth_render_params *params, int32_t *image_out, isdf_depth_render_info *info_out);
+int isdf_depth_render_device(isdf_ctx *ctx, const isdf_depth_camera *camera, const double cam2world[12], const float *d_xyz, long long n,
+                             const isdf_depth_render_params *params, int32_t *d_image_out, isdf_depth_render_info *info_out, void *stream);
+/* plain host code, no ctx, no device.  The map source reads occ (X * Y * Z bytes, z fastest), bmin, resolution and dims (each in
+ * [1, 4096]); the cloud source ignores them (they may be NULL).  Returns an isdf_status. */
+int isdf_depth_render_host(const isdf_depth_camera *camera, const double cam2world[12], const float *xyz, long long n, const uint8_t *occ,
+                           const double bmin[3], double resolution, const int32_t dims[3], const isdf_depth_render_params *params,
+                           int32_t *image_out, isdf_depth_render_info *info_out);
+
+/* RAYS.  A depth image turned into the (xyz, hit) arrays isdf_integrate_scan takes, cut to range and clipped to the map, which the
+ * scan asks of its caller.  Formats: ISDF_DEPTH_I32_MM, the render's own output: a value >= 500000 is no return
+ * (pcl_render_node.cpp:293), and so is a value <= 0, which no surface in front of the camera gives; ISDF_DEPTH_U16_MM: 0 is no
+ * return; ISDF_DEPTH_F32_M: 0, a negative or a non-finite value is no return.
+ * The output always has n = ceil(width / stride_u) * ceil(height / stride_v) rows (isdf_depth_rays_rows), ray k = iv * nu + iu for
+ * pixel (u, v) = (iu * stride_u, iv * stride_v): v is the outer index.  A dropped pixel's row is three times the one float32 NaN
+ * 0x7FC00000 with hit 0: the scan skips a non-finite end point, so nothing is compacted and the order is fixed.
+ * Per kept pixel, in fp64, nothing contracted (render_pcl_world, pcl_render_node.cpp:241-246):
+ *   d = mm / 1000.0, or the float widened
+ *   p = ((u - cx) * d / fx, (v - cy) * d / fy, d);  e_a = R_a0 p_0 + R_a1 p_1 + R_a2 p_2 + t_a, summed left to right;  o = t
+ *   range = sqrt(dx * dx + dy * dy + dz * dz) of e - o, summed left to right
+ *   range < min_range_m: dropped (n_below_min).  range > max_range_m: e = o + (e - o) * (max_range_m / range), hit 0 (n_truncated).
+ *   no return (n_no_return): dropped - or, with no_return_is_free, the same with d = 1 and e = o + (e - o) * (max_range_m / range),
+ *   hit 0: a ray of length max_range_m along the pixel's direction, neither the minimum nor n_truncated applies.
+ *   clip: box = [bmin + resolution / 2, bmax - resolution / 2] per axis.  On every axis a where e_a lies outside it
+ *   s_a = (bound_a - o_a) / (e_a - o_a) (0 when e_a == o_a); s = the smallest of them held to [0, 1]; e = o + (e - o) * s, hit 0
+ *   (n_clipped).  e - o is the difference of the e just formed and o.
+ *   the end point is rounded to float32 (a row that is not finite after that is dropped); hit = 1 counts in n_hits.
+ * Only + - * / and sqrt appear, correctly rounded on both sides: isdf_depth_rays_host gives the device's rows byte for byte.
+ * isdf_depth_rays needs the ctx's map geometry only (ISDF_ERR_STATE without a grid; a multi-device ctx: ISDF_ERR_UNSUPPORTED) and is
+ * read-only; it stages through grow-only buffers of its own, as the render does.  A camera outside the map
+ * (the scan's test of its origin): ISDF_ERR_INVALID_ARG, as are a stride < 1, min_range_m < 0, max_range_m <= 0 or NaN, an unknown
+ * format, and no_return_is_free with an infinite max_range_m.  isdf_depth_rays_device: d_image, d_ends_out (n x 3 floats) and
+ * d_hit_out (n bytes) are device memory, the work is put on `stream`; info_out as for the render. */
+#define ISDF_DEPTH_I32_MM 0
+#define ISDF_DEPTH_U16_MM 1
+#define ISDF_DEPTH_F32_M 2
+typedef struct isdf_depth_rays_params {
+    int32_t stride_u, stride_v; /* default 1: every pixel; >= 1                                                                 */
+    double min_range_m;         /* default 0                                                                                   */
+    double max_range_m;         /* default +inf; > 0                                                                           */
+    int32_t no_return_is_free;  /* default 0                                                                                   */
+    int32_t reserved[3];
+} isdf_depth_rays_params;
+typedef struct isdf_depth_rays_info {
+    int64_t n_pixels, n_no_return, n_below_min, n_truncated, n_clipped, n_hits;     /* n_pixels: the rows written */
+    double rays_ms;             /* device time of the unprojection                                                             */
+} isdf_depth_rays_info;
+void isdf_depth_rays_params_default(isdf_depth_rays_params *p);         /* null-safe */
+void isdf_depth_rays_sizes(int sizes_out[2]);                           /* null-safe; sizeof of the two structs above */
+long long isdf_depth_rays_rows(const isdf_depth_camera *camera, const isdf_depth_rays_params *params);     /* n, or ISDF_ERR_INVALID_ARG; params NULL: strides 1 */
+int isdf_depth_rays(isdf_ctx *ctx, const isdf_depth_camera *camera, const double cam2world[12], const void *image, int format,
+                    const isdf_depth_rays_params *params, float *ends_out, uint8_t *hit_out, isdf_depth_rays_info *info_out);
+int isdf_depth_rays_device(isdf_ctx *ctx, const isdf_depth_camera *camera, const double cam2world[12], const void *d_image, int format,
+                           const isdf_depth_rays_params *params, float *d_ends_out, uint8_t *d_hit_out, isdf_depth_rays_info *info_out,
+                           void *stream);
+/* plain host code, no ctx, no device; the map's geometry as isdf_scan_sets_host takes it.  Returns n_hits or a negative isdf_status. */
+long long isdf_depth_rays_host(const isdf_depth_camera *camera, const double cam2world[12], const void *image, int format,
+                               const isdf_depth_rays_params *params, const double bmin[3], const double bmax[3], double resolution,
+                               const int32_t dims[3], float *ends_out, uint8_t *hit_out, isdf_depth_rays_info *info_out);
+/* INTEGRATE.  By definition isdf_integrate_scan(ctx, t, ends, hit, n, scan_params, scan_info_out) with the arrays
+ * isdf_depth_rays_host gives for (camera, cam2world, image, format, rays_params) and the ctx's map: every product and every count of
+ * isdf_map_scan_info but the *_ms is that call's.  Here the image alone is uploaded; the unprojection writes the end points and the hit
+ * bytes on the device straight into the scan's staged input, and the scan's trace, apply and hit stages run as they are (trace_ms
+ * includes the unprojection; depth_info_out->rays_ms is its own time).  The errors are the scan's and the camera's, all before
+ * anything moves.  Both infos may be NULL.  Not offered: an image that is on the device already. */
+int isdf_integrate_depth(isdf_ctx *ctx, const isdf_depth_camera *camera, const double cam2world[12], const void *image, int format,
+                         const isdf_depth_rays_params *rays_params, const isdf_map_scan_params *scan_params,
+                         isdf_depth_rays_info *depth_info_out, isdf_map_scan_info *scan_info_out);
+
 /* ---- the map window shifted in place, so that the map can follow the robot -------------------------------------- */
 /* Every call above keeps the box (bmin, bmax, dims) that isdf_set_pointcloud fixed.  isdf_shift_map moves the window by
  * s = shift_ijk voxels: new voxel v holds what old voxel v + s held, a voxel whose source lies outside the old grid has count 0, and
