@@ -170,6 +170,31 @@ class IsdfMapShiftInfo(C.Structure):
                 ("frontend_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class IsdfMapKnownInfo(C.Structure):
+    """isdf_map_known_info (include/isdf_accel.h)."""
+    _fields_ = [("n_known", C.c_int64), ("n_unknown", C.c_int64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("newly_known", C.c_int64),
+                ("merges", C.c_int64)]
+
+
+class IsdfMapFrontierInfo(C.Structure):
+    """isdf_map_frontier_info (include/isdf_accel.h)."""
+    _fields_ = [("n_frontier", C.c_int64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("kernel_ms", C.c_double)]
+
+
+class IsdfTrajKnownParams(C.Structure):
+    """isdf_traj_known_params (include/isdf_accel.h)."""
+    _fields_ = [("margin", C.c_double), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IsdfTrajKnownInfo(C.Structure):
+    """isdf_traj_known_info (include/isdf_accel.h)."""
+    _fields_ = [("unknown_in_box", C.c_int64), ("candidates", C.c_int64), ("qualified", C.c_int64), ("n_below_margin", C.c_int64),
+                ("n_penetrating", C.c_int64), ("horizon_t", C.c_double), ("horizon_voxel", C.c_int64), ("horizon_value", C.c_double),
+                ("horizon_point", C.c_double * 3), ("horizon_piece", C.c_int32), ("culled", C.c_int32), ("min_clearance", C.c_double),
+                ("min_voxel", C.c_int64), ("duration", C.c_double), ("margin", C.c_double), ("far_r", C.c_double), ("select_ms", C.c_double),
+                ("field_ms", C.c_double), ("reduce_ms", C.c_double)]
+
+
 class IsdfMapScanParams(C.Structure):
     """isdf_map_scan_params (include/isdf_accel.h)."""
     _fields_ = [("miss_weight", C.c_int32), ("reserved", C.c_int32), ("clear", IsdfMapClearParams), ("update", IsdfMapUpdateParams)]
@@ -397,6 +422,9 @@ EXPORTED_SYMBOLS = [
     "isdf_integrate_depth",
     "isdf_map_shift_params_default", "isdf_map_shift_sizes", "isdf_shift_map", "isdf_map_follow", "isdf_shift_geometry_host", "isdf_shift_grid_host",
     "isdf_shift_bands_host",
+    "isdf_map_known_sizes", "isdf_map_known_enable", "isdf_map_known_fill", "isdf_map_known_merge_ms", "isdf_map_known_get", "isdf_map_frontier",
+    "isdf_traj_known_params_default", "isdf_traj_known_horizon", "isdf_traj_known_horizon_device",
+    "isdf_known_merge_host", "isdf_known_shift_host", "isdf_known_fill_host", "isdf_known_frontier_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -715,6 +743,30 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfMapShiftParams), C.sizeof(IsdfMapShiftInfo)]:
         raise RuntimeError(f"isdf_map_shift structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfMapShiftParams), C.sizeof(IsdfMapShiftInfo)]}")
+    ki, fi = C.POINTER(IsdfMapKnownInfo), C.POINTER(IsdfMapFrontierInfo)
+    lib.isdf_map_known_sizes.argtypes = [ip]
+    lib.isdf_map_known_sizes.restype = None
+    lib.isdf_map_known_enable.argtypes = [C.c_void_p, C.c_int]
+    lib.isdf_map_known_fill.argtypes = [C.c_void_p, i3, C.c_int]
+    lib.isdf_map_known_merge_ms.argtypes = [C.c_void_p, C.c_int, dp]
+    lib.isdf_map_known_get.argtypes = [C.c_void_p, C.c_void_p, ki]
+    lib.isdf_map_frontier.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, fi]
+    lib.isdf_known_merge_host.argtypes = [C.c_void_p, i3, C.c_void_p, C.c_void_p]
+    lib.isdf_known_merge_host.restype = C.c_longlong
+    lib.isdf_known_shift_host.argtypes = [C.c_void_p, i3, i3, C.c_void_p]
+    lib.isdf_known_fill_host.argtypes = [C.c_void_p, i3, i3, C.c_int]
+    lib.isdf_known_fill_host.restype = C.c_longlong
+    lib.isdf_known_frontier_host.argtypes = [C.c_void_p, C.c_void_p, i3, C.c_void_p, C.c_void_p, C.c_longlong, fi]
+    hp2, hi2 = C.POINTER(IsdfTrajKnownParams), C.POINTER(IsdfTrajKnownInfo)
+    lib.isdf_traj_known_params_default.argtypes = [hp2]
+    lib.isdf_traj_known_params_default.restype = None
+    lib.isdf_traj_known_horizon.argtypes = [C.c_void_p, C.c_int, dp, dp, hp2, hi2]
+    lib.isdf_traj_known_horizon_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, hp2, hi2, C.c_void_p]
+    sz4 = (C.c_int * 4)()
+    lib.isdf_map_known_sizes(sz4)
+    mirror = [C.sizeof(IsdfMapKnownInfo), C.sizeof(IsdfMapFrontierInfo), C.sizeof(IsdfTrajKnownParams), C.sizeof(IsdfTrajKnownInfo)]
+    if list(sz4) != mirror:
+        raise RuntimeError(f"isdf_map_known structs: the library has {list(sz4)}, the mirror {mirror}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

@@ -56,6 +56,16 @@ inline FfRecord ff_record_empty() {
     return r;
 }
 
+// map_known.hip: the record of one get / fill / frontier call, one 64-byte line, uploaded empty before the kernel and read back after it
+struct MkRecord {
+    unsigned long long n;                   // get: known voxels; frontier: frontier voxels
+    unsigned long long newly;               // fill: bits that went from 0 to 1
+    int lo[3], hi[3];                       // the index box of the counted voxels
+    unsigned pad[6];
+};
+static_assert(sizeof(MkRecord) == 64, "the known grid's record is one 64-byte line");
+int map_known_reset(isdf_ctx *c);           // map_known.hip: the map was replaced - with the mode on, all unknown at the new size
+
 // What the swept-volume kernels need per point set (SweptParams): the optimizer step's (the ctx holds it) or the field query's
 // (SweptMeshState holds its own: the query never shares scratch with the step).  The point arrays grow together.
 struct SweptScratch {
@@ -96,6 +106,24 @@ struct isdf_ctx {
     MapRaycastState *mrc = nullptr;             // isdf_map_raycast*: own scratch (grows only)
     DepthCamState *dcm = nullptr;               // isdf_depth_render* / isdf_depth_rays* / isdf_integrate_depth: own scratch (grows only)
     DevBuf<unsigned> d_bits; bool bits_dirty = true;
+    // the known grid (map_known.hip): one bit per voxel, 1 = some ray has visited it or the caller declared it known.  `on`
+    // outlives maps (isdf_map_known_enable); d_bits holds n_words dwords while `have`; d_shift is where a window shift writes before the
+    // two change places.  Everything else is scratch of isdf_map_known_get / _fill / isdf_map_frontier; all of it grows only.
+    struct Known {
+        bool on = false, have = false;
+        size_t n_words = 0;
+        DevBuf<unsigned> d_bits, d_shift;
+        long long newly = 0, merges = 0;            // isdf_map_known_info's newly_known and merges
+        DevBuf<unsigned> d_front; DevBuf<int> d_cnt, d_base; DevBuf<long long> d_list; DevBuf<void> d_scan_tmp;
+        DevBuf<MkRecord> d_rec; PinBuf<MkRecord> h_rec;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        // isdf_map_known_merge_ms: a developer's pair of events round the merge kernel, recorded only while asked for
+        bool time_merge = false; hipEvent_t ev_merge[2] = {nullptr, nullptr}; double merge_ms = -1.0;
+        ~Known() {
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+            for (hipEvent_t e : ev_merge) if (e) (void)hipEventDestroy(e);
+        }
+    } known;
     bool have_geom = false;
     unsigned long long grid_epoch = 0;          // counts isdf_set_grid / isdf_set_pointcloud: what was derived from voxel indices of an older grid is stale
     // shape

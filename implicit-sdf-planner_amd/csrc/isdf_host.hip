@@ -150,6 +150,7 @@ extern "C" int isdf_set_grid(isdf_ctx *c, const void *vox, int dtype, int nx, in
     c->bricks_stale = true;
     c->grid.occ = c->d_occ;
     c->bits_dirty = true;
+    if (int rc = map_known_reset(c)) return rc;         // a new map: nothing of it has been seen
     ISDF_REPLICATE(c, isdf_set_grid(p_, vox, dtype, nx, ny, nz, origin, bmax, res, kind));
     return ISDF_OK;
 }

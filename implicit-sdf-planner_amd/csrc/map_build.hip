@@ -237,6 +237,7 @@ extern "C" int isdf_set_pointcloud(isdf_ctx *c, const float *xyz, long long n_po
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->grid.esdf = nullptr; c->grid.occ = c->d_occ;
     c->bits_dirty = true;
+    if (int rc = map_known_reset(c)) return rc;         // a new map: nothing of it has been seen
     if (dims_out) { dims_out[0] = (int)dim[0]; dims_out[1] = (int)dim[1]; dims_out[2] = (int)dim[2]; }
     ISDF_REPLICATE(c, isdf_set_pointcloud(p_, xyz, n_points, bmin_opt, bmax_opt, resolution, sta_threshold, nullptr));
     return ISDF_OK;

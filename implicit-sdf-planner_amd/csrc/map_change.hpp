@@ -30,7 +30,7 @@ struct McEsdfRecord {
 struct MsRecord {
     unsigned long long n_skipped, n_hits, n_free, n_hit_voxels;
     int lo[3], hi[3];                   // the visited box
-    unsigned pad[2];
+    unsigned long long newly_known;     // with a known grid (map_known.hip): the bits the scan's merge turned from 0 to 1
 };
 // the shift's translation stage
 struct MshRecord {
@@ -150,5 +150,13 @@ typedef int (*MsProduce)(isdf_ctx *c, float *d_xyz, uint8_t *d_hit, void *arg);
 struct MsInput { const float *xyz; const uint8_t *hit; MsProduce produce; void *arg; };     // host arrays (hit nullable), or produce
 int scan_check(isdf_ctx *c, const char *op, const double origin[3], const void *in, long long n, const isdf_map_scan_params *params, isdf_map_scan_params &P, MsOrigin &O);
 int scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long long n_rays, const isdf_map_scan_params &P, isdf_map_scan_info *info_out);
+
+// ---- the known grid's hooks (map_known.hip), each called only while c->known.have
+// the scan, after its trace: known |= free | hit over the dwords of the visited box of *d_scan, the new bits counted into it
+int map_known_merge_launch(isdf_ctx *c, const unsigned *d_free_bits, const unsigned *d_hit_bits, MsRecord *d_scan);
+void map_known_merged(isdf_ctx *c, const MsRecord &scan);       // ... and after the hand-over that brought the record back
+// the shift, with its translation stage: the grid translated by s (clamped or not) into the second buffer; then the two change places
+int map_known_shift_launch(isdf_ctx *c, const int32_t s[3]);
+void map_known_shift_swap(isdf_ctx *c);
 
 }  // namespace isdf

@@ -212,6 +212,8 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(S.ev_scan[1], st));
+    const bool known = c->known.have && n_rays > 0;         // the visited voxels join the known grid (map_known.hip); off: nothing differs
+    if (known && (rc = map_known_merge_launch(c, S.d_free_bits.get(), S.d_hit_bits.get(), &d_rec->scan))) return rc;
     HIPCHK(c, hipEventRecord(S.ev[0], st));
     if (n_rays > 0) {
         hipLaunchKernelGGL(ms_apply_kernel, dim3(1024), dim3(256), 0, st, G, (const unsigned *)S.d_free_bits.get(), (const unsigned *)S.d_hit_bits.get(), c->d_counts.get(), thr,
@@ -221,6 +223,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     if ((rc = map_hand_over(c, S, S.ev[1], "scan", false))) return rc;
     const MapListRecord R = h_rec->list;
     const MsRecord RS = h_rec->scan;
+    if (known) map_known_merged(c, RS);
     info.trace_ms = mu_event_ms(S.ev_scan[0], S.ev_scan[1]);
     info.n_rays_skipped = (long long)RS.n_skipped;
     info.n_hits = (long long)RS.n_hits;

@@ -225,10 +225,12 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
         hipLaunchKernelGGL((msh_translate_kernel<uint4, false>), dim3(grid_blocks(n_vox * (nw / 4))), dim3(256), 0, st, (const uint4 *)fe.d_cspace.get(),
                            (uint4 *)S.d_shift_cspace.get(), g, (int)(nw / 4), (MshRecord *)nullptr);
     HIPCHK(c, hipGetLastError());
+    if (c->known.have && (rc = map_known_shift_launch(c, s))) return rc;           // the known grid moves with the window (map_known.hip)
     HIPCHK(c, hipEventRecord(S.ev[1], st));
 
     // ---- the new map takes the old one's place.  From here on a failure must not leave products behind that describe the old map.
     const bool watch = traj_watch_armed(c);             // (asked before the epoch moves: a stale watch disarms itself)
+    if (c->known.have) map_known_shift_swap(c);
     c->d_counts.swap(S.d_shift_counts);
     c->d_occ.swap(S.d_shift_occ);
     if (table) fe.d_cspace.swap(S.d_shift_cspace);

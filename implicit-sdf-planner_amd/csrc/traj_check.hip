@@ -20,6 +20,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace {
@@ -59,7 +60,10 @@ __global__ __launch_bounds__(256) void tc_brick_kernel(SelBox B, const double *_
 }
 
 // one wavefront per z-row (x, y) of the box: mask[row][chunk] = the candidates among 64 consecutive voxels, count[row] = their
-// number; stats[0] += occupied voxels of the box, stats[1] += candidates
+// number; stats[0] += occupied voxels of the box, stats[1] += candidates.  KNOWN: `occ` is the known grid's words (map_known.hip) and
+// the per-lane test is "known bit clear" in place of "occupancy byte set" - the known horizon's selection; everything else is shared,
+// and the <false> instance is the check's kernel instruction for instruction.
+template <bool KNOWN>
 __global__ __launch_bounds__(64 * SEL_WAVES) void tc_row_kernel(SelBox B, const uint8_t *__restrict__ occ, const int2 *__restrict__ range,
                                                                 const double *__restrict__ pose, const int *__restrict__ n_coarse,
                                                                 unsigned long long *__restrict__ mask, int *__restrict__ count,
@@ -80,7 +84,11 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void tc_row_kernel(SelBox B, const 
     int n_sel = 0;
     for (int ch = 0; ch < B.n_chunks; ch++) {
         const int z = B.lo[2] + ch * 64 + lane;
-        const bool occupied = z <= B.hi[2] && o[z] != 0;
+        bool occupied;
+        if constexpr (KNOWN) {
+            const size_t a = ((size_t)x * B.Y + y) * B.Z + (size_t)(z <= B.hi[2] ? z : B.hi[2]);
+            occupied = z <= B.hi[2] && !((((const unsigned *)occ)[a >> 5] >> (unsigned)(a & 31)) & 1u);
+        } else occupied = z <= B.hi[2] && o[z] != 0;
         bool sel = occupied;
         if (occupied && B.cull) {
             const int2 r = range[brick_row + (z / BRICK - B.b0[2])];
@@ -232,6 +240,39 @@ __global__ void tc_row_vox_kernel(long long n, const int *__restrict__ flag, con
     row_vox[base[j]] = vox[j];
 }
 
+// ---- the known horizon's reduction (isdf_traj_known_horizon): integer-keyed minima only, so two runs give the same bytes.
+// rec: [0..2] += qualified, below the margin, penetrating; [3] min ordered_key(t*) among the candidates below the margin, [4] the lowest
+// list position (= lowest voxel index: the list ascends) among those that reach it; [5], [6] the same for the value among the qualified
+constexpr int TH_WORDS = 8;
+__global__ __launch_bounds__(256) void th_key_kernel(long long n, const double *__restrict__ val, const double *__restrict__ ts, double margin,
+                                                     unsigned long long *rec) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long q = 0, below = 0, pen = 0;
+    if (j < n) {
+        const double v = val[j];
+        if (v != 1e1) {
+            q = 1; below = v < margin ? 1 : 0; pen = v < 0.0 ? 1 : 0;
+            atomicMin(&rec[5], ordered_key(v));
+            if (below) atomicMin(&rec[3], ordered_key(ts[j]));
+        }
+    }
+    q = wave_sum_u64(q); below = wave_sum_u64(below); pen = wave_sum_u64(pen);
+    if ((threadIdx.x & 63) == 0) {
+        if (q) atomicAdd(&rec[0], q);
+        if (below) atomicAdd(&rec[1], below);
+        if (pen) atomicAdd(&rec[2], pen);
+    }
+}
+__global__ __launch_bounds__(256) void th_pos_kernel(long long n, const double *__restrict__ val, const double *__restrict__ ts, double margin,
+                                                     unsigned long long *rec) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const double v = val[j];
+    if (v == 1e1) return;
+    if (ordered_key(v) == rec[5]) atomicMin(&rec[6], (unsigned long long)j);
+    if (v < margin && ordered_key(ts[j]) == rec[3]) atomicMin(&rec[4], (unsigned long long)j);
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------
 void free_rows(TrajCheckState *s) {
     s->d_rows.release();
@@ -262,19 +303,15 @@ int check_state(isdf_ctx *c, const isdf_traj_check_params *p, double *margin_out
     return ISDF_OK;
 }
 
-// the check on device arrays; hT = the durations on the host.  d_piece_min: N doubles on the device (required).
-int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const int mode, const double margin,
-              isdf_traj_check_info *info, double *d_piece_min, hipStream_t st) {
-    if (!c->tck) c->tck = new TrajCheckState();
-    TrajCheckState *k = c->tck;
-    free_rows(k);
-    SweptMeshState *s;
-    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
-    hipEvent_t ev[4];
-    for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
-    struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
-    HIPCHK(c, hipEventRecord(ev[0], st));
-
+// The select step of the check and of the known horizon: the voxels of `src` that pass the row kernel's test (known == false: occupancy
+// byte set; true: src is the known grid, bit clear) within far_r of a coarse sample, in ascending voxel index, with their centres.
+struct Selection {
+    SelBox B{}; bool empty = true, cull = false; double far_r = 0.0;
+    unsigned long long cnt[2] = {0, 0};         // voxels of the box that pass the test; candidates
+    DevBuf<long long> vox; DevBuf<double> xyz;
+};
+int select_run(isdf_ctx *c, SweptMeshState *s, int N, const double *d_T, const double *d_C, int mode, const uint8_t *src, bool known, const char *op,
+               Selection &L, hipStream_t st) {
     // ---- select: the coarse positions, their box, bricks, rows, scan, emit
     { const int rc = swept_field_coarse_table(c, N, d_T, d_C, mode, st); if (rc) return rc; }
     std::vector<double> pos(3 * (size_t)SWEPT_MAX_COARSE);
@@ -284,20 +321,22 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     HIPCHK(c, hipStreamSynchronize(st));
     const bool mesh = c->shape.kind == ISDF_SHAPE_MESH;
     const double R = mesh ? std::max(c->mesh_rmax, c->shape.bound_radius) : c->shape.bound_radius;
-    const bool cull = R > 0.0 && std::isfinite(R);
+    const bool cull = L.cull = R > 0.0 && std::isfinite(R);
     const double band = 2 * c->cfg.safety_hor + 0.1;
-    const double far_r = cull ? R + band * (mesh ? 1.05 : 1.0) : 0.0;       // the scan's own expression (swept_sweep.hip, scan_body)
+    const double far_r = L.far_r = cull ? R + band * (mesh ? 1.05 : 1.0) : 0.0;       // the scan's own expression (swept_sweep.hip, scan_body)
     const DevGrid &G = c->grid;
-    SelBox B{};
+    SelBox &B = L.B;
+    B = SelBox{};
     B.X = G.X; B.Y = G.Y; B.Z = G.Z; B.res = G.res;
     const int dim[3] = {G.X, G.Y, G.Z};
-    bool empty = n_coarse < 1;
+    bool &empty = L.empty;
+    empty = n_coarse < 1;
     for (int a = 0; a < 3 && !empty; a++) {
         B.bmin[a] = G.bmin[a];
         if (!cull) { B.lo[a] = 0; B.hi[a] = dim[a] - 1; continue; }
         double mn = 1e300, mx = -1e300;
         for (int i = 0; i < n_coarse; i++) { const double v = pos[(size_t)a * SWEPT_MAX_COARSE + i]; mn = std::min(mn, v); mx = std::max(mx, v); }
-        if (!std::isfinite(mn) || !std::isfinite(mx)) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: non-finite trajectory position");
+        if (!std::isfinite(mn) || !std::isfinite(mx)) return fail(c, ISDF_ERR_INVALID_ARG, (std::string(op) + ": non-finite trajectory position").c_str());
         // voxels whose centre (i + 0.5) res + origin can lie within far_r of a sample on this axis, one more on either side for the rounding
         const double l = std::floor((mn - far_r - G.bmin[a]) / G.res - 0.5) - 1.0, h = std::floor((mx + far_r - G.bmin[a]) / G.res - 0.5) + 2.0;
         if (h < 0.0 || l > (double)(dim[a] - 1)) { empty = true; break; }
@@ -307,9 +346,10 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     const double slack = 1.0 + 1e-9;        // the scan compares its own rounding of the same distance: never tighter than it
     const double bdiag = std::sqrt(3.0) * (BRICK / 2) * G.res;        // brick centre to its farthest voxel centre is sqrt(3) 3.5 res
     B.far2 = far_r * far_r * slack; B.bfar2 = (far_r + bdiag) * (far_r + bdiag) * slack;
-    unsigned long long cnt[2] = {0, 0};
-    DevBuf<long long> vox;
-    DevBuf<double> xyz;
+    unsigned long long *const cnt = L.cnt;
+    cnt[0] = cnt[1] = 0;
+    DevBuf<long long> &vox = L.vox;
+    DevBuf<double> &xyz = L.xyz;
     if (!empty) {
         for (int a = 0; a < 3; a++) { B.b0[a] = B.lo[a] / BRICK; B.nb[a] = B.hi[a] / BRICK - B.b0[a] + 1; }
         B.n_chunks = (B.hi[2] - B.lo[2] + 64) / 64;
@@ -325,12 +365,14 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
         HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 2 * sizeof(unsigned long long), st));
         if (cull) hipLaunchKernelGGL(tc_brick_kernel, dim3(std::min<unsigned>(blocks(n_bricks), 4096u)), dim3(256), 0, st, B,
                                      (const double *)s->field.coarse_pose, (const int *)s->field.n_coarse, range.get());
-        hipLaunchKernelGGL(tc_row_kernel, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B, (const uint8_t *)c->d_occ,
-                           (const int2 *)range.get(), (const double *)s->field.coarse_pose, (const int *)s->field.n_coarse, mask.get(), count.get(), d_cnt.get());
+        if (known) hipLaunchKernelGGL(tc_row_kernel<true>, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B, src,
+                                      (const int2 *)range.get(), (const double *)s->field.coarse_pose, (const int *)s->field.n_coarse, mask.get(), count.get(), d_cnt.get());
+        else hipLaunchKernelGGL(tc_row_kernel<false>, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B, src,
+                                (const int2 *)range.get(), (const double *)s->field.coarse_pose, (const int *)s->field.n_coarse, mask.get(), count.get(), d_cnt.get());
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
-        if (cnt[1] > (unsigned long long)INT32_MAX) return fail(c, ISDF_ERR_OVERFLOW, "trajectory check: more than 2^31 candidate voxels");
+        if (cnt[1] > (unsigned long long)INT32_MAX) return fail(c, ISDF_ERR_OVERFLOW, (std::string(op) + ": more than 2^31 candidate voxels").c_str());
         if (cnt[1]) {
             { const int rc = exclusive_sum(c, count.get(), base.get(), n_rows, st); if (rc) return rc; }
             HIPCHK(c, vox.alloc((size_t)cnt[1]));
@@ -341,6 +383,30 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
             HIPCHK(c, hipStreamSynchronize(st));          // (mask / count / base go out of scope here)
         }
     }
+    return ISDF_OK;
+}
+
+// the check on device arrays; hT = the durations on the host.  d_piece_min: N doubles on the device (required).
+int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const int mode, const double margin,
+              isdf_traj_check_info *info, double *d_piece_min, hipStream_t st) {
+    if (!c->tck) c->tck = new TrajCheckState();
+    TrajCheckState *k = c->tck;
+    free_rows(k);
+    SweptMeshState *s;
+    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    hipEvent_t ev[4];
+    for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
+    struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
+    HIPCHK(c, hipEventRecord(ev[0], st));
+
+    Selection L;
+    { const int rc = select_run(c, s, N, d_T, d_C, mode, (const uint8_t *)c->d_occ, false, "trajectory check", L, st); if (rc) return rc; }
+    const bool cull = L.cull, empty = L.empty;
+    const double far_r = L.far_r;
+    const SelBox &B = L.B;
+    const unsigned long long *const cnt = L.cnt;
+    DevBuf<long long> &vox = L.vox;
+    DevBuf<double> &xyz = L.xyz;
     const long long n = (long long)cnt[1];
     HIPCHK(c, hipEventRecord(ev[1], st));
 
@@ -529,4 +595,119 @@ extern "C" int isdf_traj_collide(isdf_ctx *c, int N, const double *T, const doub
     const int rc = isdf_traj_check(c, N, T, coeffs, nullptr, &info, nullptr);
     if (rc) return rc;
     return info.n_penetrating > 0 ? 1 : 0;
+}
+
+// ---- the known horizon of a trajectory: the check's three steps on the UNKNOWN voxels (known bit clear, occupied or not)
+// with the earliest t* below the margin as the reduction.  Own scoped scratch; the kept report, the watch and the V1 state stay.
+namespace {
+
+int horizon_run(isdf_ctx *c, int N, const double *hT, const double *d_T, const double *d_C, int mode, double margin, isdf_traj_known_info *info, hipStream_t st) {
+    SweptMeshState *s;
+    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    hipEvent_t ev[4];
+    for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
+    struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
+    HIPCHK(c, hipEventRecord(ev[0], st));
+    Selection L;
+    { const int rc = select_run(c, s, N, d_T, d_C, mode, (const uint8_t *)c->known.d_bits.get(), true, "known horizon", L, st); if (rc) return rc; }
+    const long long n = (long long)L.cnt[1];
+    HIPCHK(c, hipEventRecord(ev[1], st));
+    DevBuf<double> val, ts;
+    HIPCHK(c, val.alloc((size_t)n)); HIPCHK(c, ts.alloc((size_t)n));
+    { const int rc = swept_field_run(c, N, d_T, d_C, L.xyz.get(), n, mode, val.get(), ts.get(), st); if (rc) return rc; }
+    HIPCHK(c, hipEventRecord(ev[2], st));
+    DevBuf<unsigned long long> d_rec;
+    unsigned long long rec[TH_WORDS] = {0, 0, 0, ~0ull, ~0ull, ~0ull, ~0ull, 0};
+    HIPCHK(c, d_rec.alloc(TH_WORDS));
+    HIPCHK(c, hipMemcpyAsync(d_rec.get(), rec, sizeof(rec), hipMemcpyHostToDevice, st));
+    if (n > 0) {
+        hipLaunchKernelGGL(th_key_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const double *)val.get(), (const double *)ts.get(), margin, d_rec.get());
+        hipLaunchKernelGGL(th_pos_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const double *)val.get(), (const double *)ts.get(), margin, d_rec.get());
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(rec, d_rec.get(), sizeof(rec), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipEventRecord(ev[3], st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    isdf_traj_known_info out{};
+    out.unknown_in_box = (int64_t)L.cnt[0]; out.candidates = n;
+    out.qualified = (int64_t)rec[0]; out.n_below_margin = (int64_t)rec[1]; out.n_penetrating = (int64_t)rec[2];
+    out.horizon_t = -1.0; out.horizon_voxel = -1; out.horizon_value = 1e1; out.horizon_piece = -1;
+    out.min_clearance = 1e1; out.min_voxel = -1;
+    if (rec[1] > 0) {
+        const size_t j = (size_t)rec[4];
+        long long v = -1;
+        HIPCHK(c, hipMemcpyAsync(&out.horizon_t, ts.get() + j, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&out.horizon_value, val.get() + j, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out.horizon_point, L.xyz.get() + 3 * j, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&v, L.vox.get() + j, sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        out.horizon_voxel = v;
+        double t = out.horizon_t;               // locate_piece's rule
+        int idx = 0;
+        while (idx < N && t > hT[idx]) { t -= hT[idx]; idx++; }
+        out.horizon_piece = idx == N ? N - 1 : idx;
+    }
+    if (rec[0] > 0) {
+        const size_t j = (size_t)rec[6];
+        long long v = -1;
+        HIPCHK(c, hipMemcpyAsync(&out.min_clearance, val.get() + j, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&v, L.vox.get() + j, sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        out.min_voxel = v;
+    }
+    for (int i = 0; i < N; i++) out.duration += hT[i];
+    out.culled = L.cull ? 1 : 0; out.margin = margin; out.far_r = L.far_r;
+    float ms[3] = {0.f, 0.f, 0.f};
+    for (int q = 0; q < 3; q++) HIPCHK(c, hipEventElapsedTime(&ms[q], ev[q], ev[q + 1]));
+    out.select_ms = ms[0]; out.field_ms = ms[1]; out.reduce_ms = ms[2];
+    if (info) *info = out;
+    return ISDF_OK;
+}
+
+int horizon_ready(isdf_ctx *c, int N, const void *T, const void *coeffs, const isdf_traj_known_params *p, double *margin) {
+    isdf_traj_check_params q;
+    isdf_traj_check_params_default(&q);
+    if (p) { q.margin = p->margin; q.mode = p->mode; }
+    { const int rc = check_args(c, N, T, coeffs, &q); if (rc) return rc; }
+    if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "known horizon: null ctx");
+    { const int rc = check_state(c, &q, margin); if (rc) return rc; }
+    if (!c->known.have) return fail(c, ISDF_ERR_STATE, "known horizon: no known grid (isdf_map_known_enable, then a map from isdf_set_pointcloud)");
+    return ISDF_OK;
+}
+
+}  // namespace
+
+extern "C" void isdf_traj_known_params_default(isdf_traj_known_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->margin = -1.0;                       // negative: cfg.safety_hor of the ctx
+    p->mode = ISDF_SWEPT_FIELD_PLANNER;
+}
+
+extern "C" int isdf_traj_known_horizon_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const isdf_traj_known_params *p,
+                                              isdf_traj_known_info *info_out, void *stream) {
+    double margin = 0.0;
+    { const int rc = horizon_ready(c, N, d_T, d_coeffs, p, &margin); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<double> hT(N);
+    HIPCHK(c, hipMemcpyAsync(hT.data(), d_T, N * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    { const int rc = swept_check_traj(c, N, hT.data()); if (rc) return rc; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // the known grid is written on the ctx's stream
+    return horizon_run(c, N, hT.data(), d_T, d_coeffs, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, st);
+}
+
+extern "C" int isdf_traj_known_horizon(isdf_ctx *c, int N, const double *T, const double *coeffs, const isdf_traj_known_params *p, isdf_traj_known_info *info_out) {
+    double margin = 0.0;
+    { const int rc = horizon_ready(c, N, T, coeffs, p, &margin); if (rc) return rc; }
+    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
+    for (int q = 0; q < 18 * N; q++) if (!std::isfinite(coeffs[q])) return fail(c, ISDF_ERR_INVALID_ARG, "known horizon: non-finite coefficient");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> traj;                    // own upload: the check's kept trajectory is not touched
+    HIPCHK(c, traj.alloc((size_t)19 * N));
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(traj.get(), T, N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(traj.get() + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
+    return horizon_run(c, N, T, traj.get(), traj.get() + N, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, st);
 }

@@ -391,6 +391,88 @@ def scan_sets_host(bmin, bmax, res, dims, origin, xyz, hit=None, lib=None):
     return free, hits, int(skipped.value)
 
 
+def known_words(dims):
+    """Words of a known grid over dims voxels: ceil(nx ny nz / 32)."""
+    return (int(dims[0]) * int(dims[1]) * int(dims[2]) + 31) // 32
+
+
+def known_pack(mask):
+    """A boolean [X, Y, Z] array as the known grid's words (voxel a = (x * ny + y) * nz + z is bit a & 31 of word a >> 5)."""
+    m = np.ascontiguousarray(mask).astype(bool).reshape(-1)
+    b = np.packbits(m, bitorder="little")
+    out = np.zeros(4 * known_words(np.shape(mask)), dtype=np.uint8)
+    out[:b.size] = b
+    return out.view("<u4").astype(np.uint32)
+
+
+def known_unpack(words, dims):
+    """The words of a known grid as a boolean [X, Y, Z] array."""
+    n = int(dims[0]) * int(dims[1]) * int(dims[2])
+    w = np.ascontiguousarray(words, dtype=np.uint32).astype("<u4").view(np.uint8)
+    return np.unpackbits(w, bitorder="little")[:n].astype(bool).reshape(tuple(int(v) for v in dims))
+
+
+def _known_args(bits, dims):
+    d = (C.c_int32 * 3)(*[int(v) for v in dims])
+    w = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+    if w.size != known_words(dims):
+        raise ValueError(f"a known grid over {tuple(dims)} has {known_words(dims)} words")
+    return w, d
+
+
+def known_merge_host(bits, dims, free, hits, lib=None):
+    """isdf_known_merge_host: (bits | V, bits that went from 0 to 1); free / hits as scan_sets_host returns them (either may be None)."""
+    lib = lib or capi.load_library()
+    w, d = _known_args(bits, dims)
+    out = w.copy()
+    f = None if free is None else np.ascontiguousarray(free, dtype=np.uint8)
+    h = None if hits is None else np.ascontiguousarray(hits, dtype=np.uint32)
+    n = lib.isdf_known_merge_host(out.ctypes.data_as(C.c_void_p), d, None if f is None else f.ctypes.data_as(C.c_void_p),
+                                  None if h is None else h.ctypes.data_as(C.c_void_p))
+    if n < 0:
+        raise IsdfError(int(n), "isdf_known_merge_host")
+    return out, int(n)
+
+
+def known_shift_host(bits, dims, shift, lib=None):
+    """isdf_known_shift_host: the grid translated, K'[v] = K[v + shift] where v + shift lies in the grid, else 0."""
+    lib = lib or capi.load_library()
+    w, d = _known_args(bits, dims)
+    out = np.zeros_like(w)
+    rc = lib.isdf_known_shift_host(w.ctypes.data_as(C.c_void_p), d, _i3(shift), out.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise IsdfError(rc, "isdf_known_shift_host")
+    return out
+
+
+def known_fill_host(bits, dims, box, value, lib=None):
+    """isdf_known_fill_host: (the grid with the inclusive box (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z) - None: all of it - set or cleared,
+    bits that went from 0 to 1).  Raises IsdfError for a box outside the grid or with lo > hi."""
+    lib = lib or capi.load_library()
+    w, d = _known_args(bits, dims)
+    out = w.copy()
+    n = lib.isdf_known_fill_host(out.ctypes.data_as(C.c_void_p), d, None if box is None else (C.c_int32 * 6)(*[int(v) for v in box]), int(value))
+    if n < 0:
+        raise IsdfError(int(n), "isdf_known_fill_host")
+    return out, int(n)
+
+
+def known_frontier_host(bits, occ, capacity=None, lib=None):
+    """isdf_known_frontier_host on occupancy bytes [X, Y, Z]: (frontier words, voxel indices int64 ascending, IsdfMapFrontierInfo).
+    capacity: of the list (default: as many as there are); too short raises IsdfError(ISDF_ERR_OVERFLOW)."""
+    lib = lib or capi.load_library()
+    o = np.ascontiguousarray(occ, dtype=np.uint8)
+    w, d = _known_args(bits, o.shape)
+    out = np.zeros_like(w)
+    info = capi.IsdfMapFrontierInfo()
+    vox = np.zeros(o.size if capacity is None else int(capacity), dtype=np.int64)
+    rc = lib.isdf_known_frontier_host(w.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.c_void_p), d, out.ctypes.data_as(C.c_void_p),
+                                      vox.ctypes.data_as(C.c_void_p), vox.size, C.byref(info))
+    if rc < 0:
+        raise IsdfError(rc, "isdf_known_frontier_host")
+    return out, vox[:int(info.n_frontier)], info
+
+
 def _raycast_params(lib, test_origin_voxel, per_ray_origin):
     p = capi.IsdfMapRaycastParams()
     lib.isdf_map_raycast_params_default(C.byref(p))
@@ -1029,6 +1111,76 @@ class Engine:
         self._check(self.lib.isdf_map_follow(self.h, _p(ctr), int(min_shift), C.byref(p), s, C.byref(info)))
         self._watch_refresh_rows()
         return tuple(s), info
+
+    # ---- observed space: the known grid and the frontier (csrc/map_known.hip)
+    def map_known_enable(self, on=True):
+        """isdf_map_known_enable: the ctx keeps (on) or releases (off) one known bit per voxel of its map; the mode outlives maps."""
+        self._check(self.lib.isdf_map_known_enable(self.h, int(bool(on))))
+
+    def map_known_fill(self, box=None, value=1):
+        """isdf_map_known_fill: the inclusive box (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z) - None: the whole map - declared known (value 1)
+        or unknown (0)."""
+        self._check(self.lib.isdf_map_known_fill(self.h, None if box is None else (C.c_int32 * 6)(*[int(v) for v in box]), int(value)))
+
+    def map_known_merge_ms(self, enable=True):
+        """isdf_map_known_merge_ms: the device time of the last timed merge kernel (-1: none), and whether later merges are timed."""
+        ms = C.c_double(-1.0)
+        self._check(self.lib.isdf_map_known_merge_ms(self.h, int(bool(enable)), C.byref(ms)))
+        return float(ms.value)
+
+    def map_known(self):
+        """isdf_map_known_get: (the grid's uint32 words - known_unpack gives booleans -, IsdfMapKnownInfo)."""
+        out = np.zeros(known_words(self._grid_dims()), dtype=np.uint32)
+        info = capi.IsdfMapKnownInfo()
+        self._check(self.lib.isdf_map_known_get(self.h, out.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return out, info
+
+    def map_frontier(self, capacity=None, want_list=True):
+        """isdf_map_frontier: (frontier words, voxel indices int64 ascending - None when not wanted -, IsdfMapFrontierInfo).  capacity:
+        of the list (default: grown to the number of frontier voxels, which a first short call reports); an explicit one that is too
+        short raises IsdfError(ISDF_ERR_OVERFLOW)."""
+        out = np.zeros(known_words(self._grid_dims()), dtype=np.uint32)
+        info = capi.IsdfMapFrontierInfo()
+        if not want_list:
+            self._check(self.lib.isdf_map_frontier(self.h, out.ctypes.data_as(C.c_void_p), None, 0, C.byref(info)))
+            return out, None, info
+        vox = np.zeros(int(capacity) if capacity is not None else max(getattr(self, "_frontier_cap", 0), 1024), dtype=np.int64)
+        rc = self.lib.isdf_map_frontier(self.h, out.ctypes.data_as(C.c_void_p), vox.ctypes.data_as(C.c_void_p), vox.size, C.byref(info))
+        if rc == capi.ISDF_ERR_OVERFLOW and capacity is None:      # the info is filled: once more with room
+            vox = np.zeros(int(info.n_frontier), dtype=np.int64)
+            rc = self.lib.isdf_map_frontier(self.h, out.ctypes.data_as(C.c_void_p), vox.ctypes.data_as(C.c_void_p), vox.size, C.byref(info))
+        self._check(rc)
+        self._frontier_cap = max(getattr(self, "_frontier_cap", 0), int(info.n_frontier))
+        return out, vox[:int(info.n_frontier)], info
+
+    def _traj_known_params(self, margin, mode):
+        p = capi.IsdfTrajKnownParams()
+        self.lib.isdf_traj_known_params_default(C.byref(p))
+        if margin is not None:
+            p.margin = float(margin)
+        p.mode = int(mode)
+        return p
+
+    @staticmethod
+    def _traj_known_report(info):
+        return {name: (np.array(getattr(info, name)) if name == "horizon_point" else getattr(info, name)) for name, _ in capi.IsdfTrajKnownInfo._fields_}
+
+    def traj_known_horizon(self, T, coeffs_colmajor, margin=None, mode=capi.SWEPT_FIELD_PLANNER):
+        """isdf_traj_known_horizon: the earliest time at which the swept body comes within `margin` of an unknown voxel's centre - a dict of
+        the isdf_traj_known_info fields (horizon_t -1: never).  margin None = cfg.safety_hor."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(-1)
+        p = self._traj_known_params(margin, mode)
+        info = capi.IsdfTrajKnownInfo()
+        self._check(self.lib.isdf_traj_known_horizon(self.h, T.size, _p(T), _p(Cc), C.byref(p), C.byref(info)))
+        return self._traj_known_report(info)
+
+    def traj_known_horizon_device(self, N, d_T, d_coeffs, margin=None, mode=capi.SWEPT_FIELD_PLANNER, stream=0):
+        """The same with the trajectory on the device, on `stream`."""
+        p = self._traj_known_params(margin, mode)
+        info = capi.IsdfTrajKnownInfo()
+        self._check(self.lib.isdf_traj_known_horizon_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), C.byref(p), C.byref(info), C.c_void_p(stream)))
+        return self._traj_known_report(info)
 
     def map_counts(self):
         """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""

@@ -1727,6 +1727,104 @@ int isdf_shift_grid_host(const void *in, int elem_bytes, const int32_t dims[3], 
  * boxes_out[i] = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z}, inclusive, *n_boxes_out <= 6.  The boxes may overlap. */
 int isdf_shift_bands_host(const int32_t dims[3], const int32_t shift[3], int side, int32_t boxes_out[6][6], int *n_boxes_out);
 
+/* ---- observed space in the map: the known grid and the frontier ---------------------------------------------------- */
+/* The map above has two states per voxel, occupied or not; a voxel no ray has ever crossed reads like one a thousand rays have proved
+ * empty, and the slab that enters the window in isdf_shift_map is "free".  The known grid is the third state: ONE BIT per voxel, voxel
+ * a = (x * ny + y) * nz + z is bit a & 31 of uint32 word a >> 5, ceil(nx ny nz / 32) words, the bits beyond the last voxel always 0.
+ * 1 = some ray has visited the voxel or the caller declared it known; 0 = unknown.  The feature is opt-in: with the mode off every
+ * call above runs the launches it ran before, in the same order.
+ * isdf_map_known_enable(ctx, 1): the ctx keeps a known grid K for its map.  If a map with kept counts exists K is allocated now, all
+ * unknown; otherwise when the next isdf_set_pointcloud makes one.  A second enable(1) changes nothing.  enable(0) releases the grid and
+ * its scratch.  The mode outlives maps: isdf_set_pointcloud and isdf_set_grid reset K to all unknown at the new size (after
+ * isdf_set_grid K serves fill, get and frontier; the scan and the shift need kept counts anyway).  A multi-device ctx:
+ * ISDF_ERR_UNSUPPORTED.  The grid, its second buffer and the scratch of fill, get and frontier grow only: those calls, the merge and the
+ * translation allocate nothing on a second call of a size (isdf_debug_live_bytes).  isdf_traj_known_horizon does, as isdf_traj_check does:
+ * its events and candidate buffers are scoped to the call.
+ * Merge: isdf_integrate_scan and isdf_integrate_depth, when K exists, end their ray stage with K' = K u V, V = every voxel visited by
+ * any ray that was not skipped - in terms of isdf_scan_sets_host free_out[v] != 0 or hits_out[v] > 0.  One extra kernel on the ctx's
+ * stream after the trace and before the scan's first hand-over, whose record brings the number of new bits back: no synchronisation of
+ * its own, no second read-back.  miss_weight = 0 still merges; n_rays = 0 merges nothing (and is not counted in `merges`); a call
+ * refused before anything moves leaves K alone.  Every other product of the scan is byte for byte what it is with the mode off.
+ * isdf_update_* and isdf_clear_* leave K alone: a caller's assertion about occupancy is not an observation.
+ * Shift: isdf_shift_map / isdf_map_follow translate K on both paths, K'[v] = K[v + s] where v + s lies in the old grid, else 0 - the
+ * entering slab is unknown; |s_a| >= dims_a on some axis: all unknown; s = 0: untouched.  The translation goes into a second buffer
+ * that changes places with the first, inside the translation stage and under its hand-over.
+ * isdf_map_known_fill: box = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z}, inclusive, or NULL for the whole map; value != 0 sets the bits of the
+ * box, 0 clears them - this is how an a-priori map is declared known.  A box outside the grid or with lo > hi on some axis:
+ * ISDF_ERR_INVALID_ARG, nothing changed.
+ * isdf_map_known_get: bits_out (nullable) = the words of K; info_out (nullable) is computed from K on the device when asked for.
+ * isdf_map_frontier: voxel v is a frontier voxel iff K[v] = 1, its occupancy byte is 0, and some 6-neighbour INSIDE the grid has
+ * K = 0 - the window's faces are not frontiers by themselves.  Computed on demand from the current K and occupancy; nothing is kept.
+ * bits_out (nullable): the frontier in K's layout; vox_out (nullable, capacity entries): the frontier voxels' indices in ASCENDING
+ * order, the same bytes on every run (counts, an exclusive scan, an emit pass: no atomics); a non-null vox_out with capacity <
+ * n_frontier: ISDF_ERR_OVERFLOW with info_out (and bits_out) filled and the list untouched.
+ * Every call but enable: ISDF_ERR_STATE without a known grid; the frontier also without an occupancy grid.
+ * Not offered: a device-pointer form of the frontier; frontiers of the robot's configuration space; unknown space treated as an obstacle. */
+typedef struct isdf_map_known_info {
+    int64_t n_known, n_unknown;     /* bits set; voxels of the grid minus them                                                      */
+    int32_t lo[3], hi[3];           /* index box of the known voxels (lo > hi: none)                                                */
+    int64_t newly_known;            /* voxels the last successful merge or fill turned from 0 to 1                                  */
+    int64_t merges;                 /* scans merged since the grid was last reset                                                   */
+} isdf_map_known_info;
+typedef struct isdf_map_frontier_info {
+    int64_t n_frontier;
+    int32_t lo[3], hi[3];           /* index box of the frontier voxels (lo > hi: none)                                             */
+    double kernel_ms;               /* device time of the frontier kernel, events on the ctx's stream (the host form: 0)            */
+} isdf_map_frontier_info;
+/* The known horizon of a trajectory: the earliest time at which the robot's body comes within the margin of an unseen voxel - how far
+ * a plan may be executed before the map must be looked at again.  isdf_traj_check's three steps with another predicate and
+ * another reduction.  select: the UNKNOWN voxels (K = 0, occupied or not) within far_r of a coarse sample, in ascending voxel index - the
+ * check's row kernel with "known bit clear" in place of "occupancy byte set".  field: the swept-volume query in params.mode at their
+ * centres.  reduce: integer-keyed minima and integer sums only, so two runs give the same bytes.  margin and mode: isdf_traj_check_params'
+ * rules and defaults.  Own scratch: the kept report of isdf_traj_check, an armed watch, the V1 points and lastTstar are untouched; more
+ * than 2^31 candidates ISDF_ERR_OVERFLOW.  No known grid: ISDF_ERR_STATE; every other error as isdf_traj_check's.  The _device form takes
+ * the trajectory on the device, works on `stream` (after the ctx's own stream has drained) and synchronises it before it returns. */
+typedef struct isdf_traj_known_params {
+    double margin;               /* negative (default) = cfg.safety_hor; above 2 safety_hor + 0.1: ISDF_ERR_INVALID_ARG             */
+    int32_t mode;                /* ISDF_SWEPT_FIELD_PLANNER (default) or ISDF_SWEPT_FIELD_CLOSED                                   */
+    int32_t reserved;
+} isdf_traj_known_params;
+typedef struct isdf_traj_known_info {
+    int64_t unknown_in_box;      /* unknown voxels of the selection box (all of the grid if !culled)                                */
+    int64_t candidates;          /* of them, those put through the field query                                                      */
+    int64_t qualified;           /* candidates with a qualifying interval (value != 10)                                             */
+    int64_t n_below_margin;      /* qualified candidates with value < margin                                                        */
+    int64_t n_penetrating;       /* ... with value < 0                                                                              */
+    double horizon_t;            /* the smallest t* among the candidates with value < margin; -1: there are none                    */
+    int64_t horizon_voxel;       /* the lexicographic minimum of (t*, voxel index) (-1: none)                                       */
+    double horizon_value;        /* its value (10: none)                                                                            */
+    double horizon_point[3];     /* its voxel centre                                                                                */
+    int32_t horizon_piece;       /* the piece horizon_t lies in (Trajectory::locatePieceIdx; -1: none)                              */
+    int32_t culled;              /* as isdf_traj_check_info's                                                                       */
+    double min_clearance;        /* smallest value over the unknown candidates (10: nothing qualified), ties to the lowest voxel    */
+    int64_t min_voxel;           /* its voxel index (-1: nothing qualified)                                                         */
+    double duration;             /* the sum of T                                                                                    */
+    double margin, far_r;        /* the margin in force; the selection radius (0 if !culled)                                        */
+    double select_ms, field_ms, reduce_ms;       /* device time of the three steps (events on the stream)                           */
+} isdf_traj_known_info;
+void isdf_traj_known_params_default(isdf_traj_known_params *p);  /* null-safe */
+int isdf_traj_known_horizon(isdf_ctx *ctx, int N, const double *T, const double *coeffs, const isdf_traj_known_params *params,
+                            isdf_traj_known_info *info_out);
+int isdf_traj_known_horizon_device(isdf_ctx *ctx, int N, const double *d_T, const double *d_coeffs, const isdf_traj_known_params *params,
+                                   isdf_traj_known_info *info_out, void *stream);
+void isdf_map_known_sizes(int sizes_out[4]);                     /* null-safe; sizeof of isdf_map_known_info, isdf_map_frontier_info, isdf_traj_known_params, isdf_traj_known_info */
+int isdf_map_known_enable(isdf_ctx *ctx, int on);
+int isdf_map_known_fill(isdf_ctx *ctx, const int32_t *box, int value);
+/* instrument (tools/map_known_bench.py): enable != 0 puts a pair of events round the merge kernel of every later scan; ms_out (nullable)
+ * receives the device time of the last merge so timed, -1 if there is none.  Off by default: no event is recorded then. */
+int isdf_map_known_merge_ms(isdf_ctx *ctx, int enable, double *ms_out);
+int isdf_map_known_get(isdf_ctx *ctx, uint32_t *bits_out, isdf_map_known_info *info_out);
+int isdf_map_frontier(isdf_ctx *ctx, uint32_t *bits_out, int64_t *vox_out, long long capacity, isdf_map_frontier_info *info_out);
+/* plain host code, no ctx, no device; dims = {nx, ny, nz}, each in [1, 4096]; the same arithmetic the kernels run (map_known_host.hpp).
+ * merge: bits |= V from isdf_scan_sets_host's outputs (either nullable); returns the bits that went from 0 to 1.  shift: bits_out =
+ * bits_in translated (the arrays must differ).  fill: as isdf_map_known_fill; returns the bits that went from 0 to 1.  frontier: occ =
+ * nx ny nz occupancy bytes; outputs and ISDF_ERR_OVERFLOW as isdf_map_frontier.  Bad arguments: ISDF_ERR_INVALID_ARG (negative). */
+long long isdf_known_merge_host(uint32_t *bits_inout, const int32_t dims[3], const uint8_t *free_bytes, const uint32_t *hits_u32);
+int isdf_known_shift_host(const uint32_t *bits_in, const int32_t dims[3], const int32_t shift[3], uint32_t *bits_out);
+long long isdf_known_fill_host(uint32_t *bits_inout, const int32_t dims[3], const int32_t *box, int value);
+int isdf_known_frontier_host(const uint32_t *bits, const uint8_t *occ, const int32_t dims[3], uint32_t *bits_out, int64_t *vox_out, long long capacity,
+                             isdf_map_frontier_info *info_out);
+
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
  * the shipped src/plan_manager/map_pcds are "FIELDS x y z / DATA ascii"): xyz_out = up to `capacity` points x 3 floats (may be
