@@ -117,3 +117,41 @@ def assert_mesh_v1_free_running(what, tg, to, gT, gT0, gC, gC0, allow_ties=0):
     assert n_moved <= allow_ties, f"{what}: {moved:.2%} of the points ({n_moved}) end on another t* (max {dt.max():.3e} s)"
     assert_close(gC, gC0, what + " gradC")
     assert_close(gT, gT0, what + " gradT")
+
+
+# ---- every analytic shape kind (tests/test_gpu_sweep_stages.py, test_gpu_shape_plugin.py, test_shape_reference_host.py) --------------
+ALL_KINDS = ["Torus", "Cappedtorus", "CappedCone", "RoundedCone", "WireframeBox", "BendLinear", "TwistBox", "BendBox", "Table", "Trefoil",
+             "SmoothDifference", "SmoothIntersection", "CSG", "Box", "Ball"]
+BODY_OFFSETS = {"ident": (0, 0, 0, 0, 0, 0), "offset": (0.2, -0.1, 0.15, 30, 10, 120)}      # yaml poly_params: the two sweep instantiations
+PLUGIN_POINTS, PLUGIN_BASE = 2000, 40
+MARGIN_MIN = 1e-12          # points with 0 < margin < this may be left out: the decision is not determined in fp64 ...
+LEFT_OUT_MAX = 0.02         # ... but at most this share of a kind's points
+DX_CENTRAL, DX_BOX = 0.000005, 0.01
+
+
+def sdf_floor(pts, params):
+    """16 ulp of (|p| + largest parameter): the rounding floor of an SDF bound."""
+    return 16 * np.spacing(np.linalg.norm(pts, axis=1) + max(abs(v) for v in params))
+
+
+def plugin_case(pkg, name, offset):
+    """(shape struct, points, is_special, high-precision table, kept mask, floor[n]) of one kind and body offset."""
+    import shape_reference as sr
+    sh = pkg.synth.make_shape(name, poly_params=BODY_OFFSETS[offset])
+    params, trans, rot = list(sh.params), list(sh.trans), list(sh.rotate)
+    pts, special = sr.sample_points(name, params, trans, rot, n=PLUGIN_POINTS, n_base=PLUGIN_BASE, seed=sr.KINDS.index(name))
+    tab = sr.reference_table(name, params, trans, rot, pts)
+    m = tab["margin"]
+    kept = ~((m > 0) & (m < MARGIN_MIN))
+    return sh, pts, special, tab, kept, sdf_floor(pts, params)
+
+
+def grad_bound(name, sdf_bound, tab, pts):
+    """Entry-wise bound of the gradient from a bound of the SDF: x 1 / (2 dx) / |quotient| (Box: forward and not normalised, x 1 / dx;
+    Ball: the analytic p / |p|, 16 ulp of 1).  inf where the quotient vanishes (nothing to normalise: the axis of a symmetric shape)."""
+    if name == "Ball":
+        return np.where(np.linalg.norm(pts, axis=1) > 0, 16 * np.finfo(np.float64).eps, np.inf)
+    if name == "Box":
+        return sdf_bound / DX_BOX
+    with np.errstate(divide="ignore"):
+        return np.where(tab["qnorm"] > 0, sdf_bound / (2 * DX_CENTRAL) / tab["qnorm"], np.inf)

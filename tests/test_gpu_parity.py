@@ -214,6 +214,7 @@ def test_every_registered_shape(pkg, orc, product_lib, name):
     eng, o = make_pair(pkg, orc, cfg, shape, esdf=esdf, res=res)
     cost, st = _check(eng, o, T, cm, name)
     assert st[2] > 0
+    assert eng.stats()["grad_pairs"] == st[3], (name, eng.stats(), st)      # the same set of active voxels, by count
 
 
 _ALL_KINDS = ["Torus", "Cappedtorus", "CappedCone", "RoundedCone", "WireframeBox", "BendLinear", "TwistBox", "BendBox", "Table", "Trefoil",
@@ -231,6 +232,7 @@ def test_every_shape_with_identity_body_offset(pkg, orc, product_lib, name):
     eng, o = make_pair(pkg, orc, cfg, shape, esdf=esdf, res=res)
     cost, st = _check(eng, o, T, cm, name + " (identity offset)")
     assert st[2] > 0
+    assert eng.stats()["grad_pairs"] == st[3], (name, eng.stats(), st)      # the same set of active voxels, by count
 
 
 @pytest.mark.parametrize("name", _ALL_KINDS)
@@ -245,8 +247,9 @@ def test_swept_sweep_every_shape_class(pkg, orc, product_lib, name):
         eng, o = make_pair(pkg, orc, cfg, shape, occ=occ, res=res, points=pts)
         tg = np.zeros(len(pts)); to = np.zeros(len(pts))
         c, gT, gC = eng.eval_single(T, cm, tstar=tg)
-        c0, gT0, gC0, _ = o.eval(T, cm, tstar=to)
+        c0, gT0, gC0, st0 = o.eval(T, cm, tstar=to)
         assert abs(c - c0) <= REL_TOL * max(abs(c0), 1e-9), (name, pp)
+        assert eng.stats()["grad_pairs"] == st0[3], (name, pp, eng.stats(), st0)      # the same set of active points, by count
         assert_close(gT, gT0, f"{name} V1 gradT"); assert_close(gC, gC0, f"{name} V1 gradC")
         assert np.max(np.abs(tg - to)) <= 2e-5
 
