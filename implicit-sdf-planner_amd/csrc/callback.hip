@@ -138,8 +138,7 @@ static int cost_function_finish_dev(isdf_ctx *c, double *g, double *cost_out, hi
     const size_t nvar = (size_t)N + 3 * (size_t)(N - 1), rs = cb_res_stride(N);
     if (!c->cb_post_queued) {
         CbDev P{};
-        const int rc = cb_dev_fill(c, N, &P, st);
-        if (rc) return rc;
+        ISDF_TRY(cb_dev_fill(c, N, &P, st));
         if (!bar_usable(c, c->d_cbdev, nvar)) P.x = c->h_cbres.dev();
         launch_cb_post(P, st);
         HIPCHK(c, hipGetLastError());
@@ -263,8 +262,7 @@ extern "C" int isdf_cost_function(isdf_ctx *c, const double *x, double *g, int n
     // would optimise on them without any error - the split form (_launch / all-reduce / _finish) is the one to use
     if (c->world > 1 && c->peers.empty() && !isdf_xchg_fuse_on(c))
         return isdf_fail(c, ISDF_ERR_STATE, "sharded ctx: use isdf_cost_function_launch / _finish around the all-reduce (or switch the in-kernel exchange on)");
-    const int rc = cost_function_launch(c, x, n, c->stream, true);
-    if (rc) return rc;
+    ISDF_TRY(cost_function_launch(c, x, n, c->stream, true));
     return cost_function_finish(c, g, cost_out, c->stream);
 }
 
@@ -274,8 +272,7 @@ extern "C" int isdf_cost_function(isdf_ctx *c, const double *x, double *g, int n
 extern "C" int isdf_cost_function_launch(isdf_ctx *c, const double *x, int n, void *stream, double **d_partial_out, size_t *count_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (!d_partial_out || !count_out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null argument");
-    const int rc = cost_function_launch(c, x, n, (hipStream_t)stream);
-    if (rc) return rc;
+    ISDF_TRY(cost_function_launch(c, x, n, (hipStream_t)stream));
     *d_partial_out = c->d_cb + (size_t)19 * c->minco.N;       // (both MINCO paths keep the sweeps' sums here)
     *count_out = (size_t)c->cb_n_out * isdf_out_stride(c->minco.N);
     return ISDF_OK;

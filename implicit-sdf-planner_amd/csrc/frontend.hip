@@ -367,7 +367,7 @@ int isdf_frontend_map_bits(isdf_ctx *c) {
 int isdf_frontend_refresh_map(isdf_ctx *c, double *cspace_ms) {
     if (cspace_ms) *cspace_ms = 0.0;
     if (!c->fe.built) return ISDF_OK;
-    { const int rc = isdf_frontend_map_bits(c); if (rc) return rc; }
+    ISDF_TRY(isdf_frontend_map_bits(c));
     c->fe.h_cspace_valid = false;
     if (c->fe.d_cspace) return isdf_frontend_cspace(c, nullptr, cspace_ms);
     return ISDF_OK;

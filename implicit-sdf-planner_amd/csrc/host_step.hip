@@ -39,7 +39,7 @@ bool host_rows_wait(isdf_ctx *c, const double *p, size_t n, bool another_area_of
 
 static int direct_reserve(isdf_ctx *c, int nb, int n) {
     const size_t in = (size_t)19 * n * nb, out = isdf_out_stride(n) * nb, need = in + out + (size_t)nb;
-    { const int rc = c->h_dir.reserve(c, need); if (rc) return rc; }      // pinned host memory is device-visible (unified addressing)
+    ISDF_TRY(c->h_dir.reserve(c, need));      // pinned host memory is device-visible (unified addressing)
     c->dir_in = in; c->dir_out = out; c->dir_flags = (size_t)nb;
     return ISDF_OK;
 }

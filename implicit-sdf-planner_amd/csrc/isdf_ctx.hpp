@@ -309,6 +309,13 @@ int isdf_mesh_surface_valid(isdf_ctx *c, const double *d_tri, int nF, double ext
         }                                                                                          \
     } while (0)
 
+// the int-returning twin: a step that failed has recorded its message already, its code is handed on
+#define ISDF_TRY(expr)                                                                             \
+    do {                                                                                           \
+        const int rc_ = (expr);                                                                    \
+        if (rc_) return rc_;                                                                       \
+    } while (0)
+
 int isdf_fail(isdf_ctx *c, int code, const char *msg);      // records the message, returns code
 void isdf_fill_flat(const isdf_config &cfg, isdf::FlatP &f);      // isdf_host.hip: the dynamics constants of a launch
 

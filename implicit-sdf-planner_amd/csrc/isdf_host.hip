@@ -136,14 +136,14 @@ extern "C" int isdf_set_grid(isdf_ctx *c, const void *vox, int dtype, int nx, in
             else for (size_t i = 0; i < n; i++) tmp[i] = (float)((const uint8_t *)vox)[i];
             src = tmp.data();
         }
-        { const int rc = c->d_esdf.renew(c, n); if (rc) return rc; }
+        ISDF_TRY(c->d_esdf.renew(c, n));
         HIPCHK(c, hipMemcpy(c->d_esdf, src, n * sizeof(float), hipMemcpyHostToDevice));
     } else {
         std::vector<uint8_t> tmp(n);
         if (dtype == ISDF_U8) for (size_t i = 0; i < n; i++) tmp[i] = ((const uint8_t *)vox)[i] != 0;
         else if (dtype == ISDF_F32) for (size_t i = 0; i < n; i++) tmp[i] = ((const float *)vox)[i] != 0;
         else for (size_t i = 0; i < n; i++) tmp[i] = ((const double *)vox)[i] != 0;
-        { const int rc = c->d_occ.renew(c, (n + 3) & ~(size_t)3); if (rc) return rc; }
+        ISDF_TRY(c->d_occ.renew(c, (n + 3) & ~(size_t)3));
         HIPCHK(c, hipMemcpy(c->d_occ, tmp.data(), n, hipMemcpyHostToDevice));
     }
     c->grid.esdf = c->d_esdf;
@@ -232,8 +232,7 @@ int isdf_reserve_sweep_buffers(isdf_ctx *c, long long total_pieces) {
         HIPCHK(c, hipDeviceSynchronize());
     }
     if (c->d_piece_cost.capacity() < (size_t)total_pieces) {         // piece-cost slots: created EMPTY like the collision sums' slots
-        const int rc = c->d_piece_cost.reserve(c, (size_t)total_pieces, 0xFF);
-        if (rc) return rc;
+        ISDF_TRY(c->d_piece_cost.reserve(c, (size_t)total_pieces, 0xFF));
         HIPCHK(c, hipDeviceSynchronize());
     }
     return ISDF_OK;
@@ -273,7 +272,7 @@ static int ensure_stage(isdf_ctx *c, size_t total_pieces) {
 // ISDF_DEBUG_TIMING=1 (developer tool): `need` zeroed words for this step's launches; *out stays null when the switch is off
 static int debug_timing_buffer(isdf_ctx *c, size_t need, hipStream_t st, unsigned long long **out) {
     if (!env_is("ISDF_DEBUG_TIMING", '1')) return ISDF_OK;
-    { const int rc = c->d_dbg.reserve(c, need); if (rc) return rc; }
+    ISDF_TRY(c->d_dbg.reserve(c, need));
     HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, need * sizeof(unsigned long long), st));
     c->dbg_used = need;
     *out = c->d_dbg;
@@ -337,7 +336,7 @@ static int v1_step(isdf_ctx *c, const isdf_config &cfg, int n_traj, int N, const
     P.tstar_stage = fixed_tstar ? nullptr : c->v1_tstar_stage;
     c->v1_tstar_stage = nullptr;
     bool regrown;
-    { const int rc = c->v1.reserve(c, (size_t)c->M, true, &regrown); if (rc) return rc; }
+    ISDF_TRY(c->v1.reserve(c, (size_t)c->M, true, &regrown));
     if (regrown) c->scan_order_b = c->scan_order_e = -1;
     c->v1.bind(P);
     // The scan's dispatch order, longest first.  Mesh robots: sorted in this step's prepare kernel from last step's durations.  Analytic
@@ -352,11 +351,11 @@ static int v1_step(isdf_ctx *c, const isdf_config &cfg, int n_traj, int N, const
     const long long order_b = sort_here ? -1 : b, order_e = sort_here ? -1 : e;
     if (scan_lpt) { c->scan_order_b = c->scan_order_e = -1; }
     P.direct_records = fixed_tstar ? 1 : 0;
-    { const int rc = c->d_hist.reserve(c, (size_t)N); if (rc) return rc; }
+    ISDF_TRY(c->d_hist.reserve(c, (size_t)N));
     P.hist = c->d_hist;
     P.stats = c->d_stats;
     P.dbg = nullptr;
-    { const int rc = debug_timing_buffer(c, (size_t)c->M * 7 + (size_t)(N + 1) * 8, st, &P.dbg); if (rc) return rc; }
+    ISDF_TRY(debug_timing_buffer(c, (size_t)c->M * 7 + (size_t)(N + 1) * 8, st, &P.dbg));
     if (fixed_tstar) {               // the minimisers are given (isdf_eval_swept_at_tstar): no search
         launch_swept_fixed(P, d_tstar, st);
         launch_swept_reduce(P, d_out, st);
@@ -365,8 +364,7 @@ static int v1_step(isdf_ctx *c, const isdf_config &cfg, int n_traj, int N, const
     }
     launch_swept_prepare(P, st);
     ProfEvent *ev;
-    const int rc = prof_begin(c, st, &ev);
-    if (rc) return rc;
+    ISDF_TRY(prof_begin(c, st, &ev));
     launch_swept_sweep(P, st, ev ? ev->a : nullptr, ev ? ev->b : nullptr);
     const bool ev2 = ev && c->prof_secondary;
     if (ev2) { HIPCHK(c, hipEventRecord(ev->c, st)); }
@@ -381,7 +379,7 @@ static int v1_step(isdf_ctx *c, const isdf_config &cfg, int n_traj, int N, const
 static int rebuild_bit_grids(isdf_ctx *c, const isdf_config &cfg, SweepParams &P, hipStream_t st) {
     const int zw = (c->grid.Z + 31) / 32, xw = (c->grid.X + 31) / 32, yw = (c->grid.Y + 31) / 32;
     const size_t nwz = (size_t)c->grid.X * c->grid.Y * zw, nwx = (size_t)c->grid.Y * c->grid.Z * xw, nwy = (size_t)c->grid.X * c->grid.Z * yw;
-    { const int rc = c->d_bits.reserve(c, nwz + nwx + nwy); if (rc) return rc; }
+    ISDF_TRY(c->d_bits.reserve(c, nwz + nwx + nwy));
     c->grid.ZW = zw; c->grid.XW = xw; c->grid.YW = yw;
     c->grid.bits = c->d_bits; c->grid.bits_x = c->d_bits + nwz; c->grid.bits_y = c->d_bits + nwz + nwx;
     launch_build_bits(c->grid, cfg.variant == ISDF_V3_ESDF_TILE ? 1 : 0, cfg.occ_thresh, c->d_bits, st);

@@ -418,8 +418,7 @@ extern "C" int isdf_esdf_sample_scattered_device(isdf_ctx *c, const double *d_xy
     if (!c->have_geom || !c->d_esdf) return isdf_fail(c, ISDF_ERR_STATE, "no ESDF grid (isdf_set_grid with ISDF_GRID_ESDF, or isdf_generate_esdf)");
     if (n == 0 || (!d_value && !d_grad)) return ISDF_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const int rc = esdf_bricks_ready(c, (hipStream_t)stream);
-    if (rc) return rc;
+    ISDF_TRY(esdf_bricks_ready(c, (hipStream_t)stream));
     DevGrid G = c->grid;
     const long long blocks = std::min<long long>((n + 255) / 256, 256ll * 64);
     hipLaunchKernelGGL(isdf::esdf_sample_bricked_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, G, (c->grid.Y + 1) / 2, (c->grid.Z + 1) / 2,

@@ -273,8 +273,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
 
 // what every entry to the scan checks before anything moves: the ctx (`in`: the caller's rays or image), the parameters, the origin
 int isdf::scan_check(isdf_ctx *c, const char *op, const double origin[3], const void *in, long long n, const isdf_map_scan_params *params, isdf_map_scan_params &P, MsOrigin &O) {
-    const int rc = map_change_ready(c, op, in, n, true);
-    if (rc) return rc;
+    ISDF_TRY(map_change_ready(c, op, in, n, true));
     isdf_map_scan_params_default(&P);
     if (params) P = *params;
     if (P.miss_weight < 0 || P.clear.max_cleared_voxels < 0 || !(P.clear.full_fraction >= 0.0) || P.update.max_new_voxels < 0 || !(P.update.full_fraction >= 0.0))

@@ -103,7 +103,7 @@ extern "C" int isdf_points_merge_check(isdf_ctx *c, double below, isdf_points_me
         hipEvent_t ev[2];
         for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
         struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 2; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
-        { const int rc = c->d_merge_bits.reserve(c, n_words); if (rc) return rc; }
+        ISDF_TRY(c->d_merge_bits.reserve(c, n_words));
         DevBuf<unsigned> counters;
         HIPCHK(c, counters.alloc(CNT_WORDS));
         HIPCHK(c, mask.alloc(n_waves)); HIPCHK(c, count.alloc(n_waves)); HIPCHK(c, base.alloc(n_waves));
@@ -118,7 +118,7 @@ extern "C" int isdf_points_merge_check(isdf_ctx *c, double below, isdf_points_me
                                (const long long *)k->d_row_vox.get(), (const unsigned *)c->d_merge_bits.get(), below, below < 0.0 ? 1 : 0,
                                mask.get(), count.get(), counters.get());
         HIPCHK(c, hipGetLastError());
-        if (n_rows > 0) { const int rc = exclusive_sum(c, count.get(), base.get(), (long long)n_waves, st); if (rc) return rc; }
+        if (n_rows > 0) ISDF_TRY(exclusive_sum(c, count.get(), base.get(), (long long)n_waves, st));
         HIPCHK(c, hipMemcpyAsync(cnt, counters.get(), sizeof(cnt), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if ((long long)M_before + (long long)cnt[CNT_ADDED] > (long long)INT32_MAX)

@@ -225,8 +225,7 @@ static int mesh_lattice(isdf_ctx *c, int n_faces, const double bb_h[3], DevShape
         if (rcv) return rcv;
     }
     if (lat.want && lat.solid) {
-        const int rc = isdf_mesh_lattice_build(c, &hm, llo, lhi, cells, lat.s_range);
-        if (rc) return rc;
+        ISDF_TRY(isdf_mesh_lattice_build(c, &hm, llo, lhi, cells, lat.s_range));
         if (hm.dl) {
             hm.dl_tau = lat.defect[0]; hm.dl_slack = 1.05f * lat.defect[1] * lat.defect[0];
             HIPCHK(c, hipMemcpy(c->d_mesh, &hm, sizeof(hm), hipMemcpyHostToDevice)); d.filter_f32 = 1;
@@ -238,9 +237,9 @@ static int mesh_lattice(isdf_ctx *c, int n_faces, const double bb_h[3], DevShape
 // the mesh kind: hierarchy and tables, upload, the form of the sweeps, the distance lattice, isdf_mesh_info
 static int install_mesh(isdf_ctx *c, const isdf_shape *s, DevShape &d, const double bb_h[3]) {
     MeshHost m;
-    { const int rc = mesh_host_build(c, s, m); if (rc) return rc; }
+    ISDF_TRY(mesh_host_build(c, s, m));
     DevMesh hm;
-    { const int rc = mesh_upload(c, m, s->n_faces, hm); if (rc) return rc; }
+    ISDF_TRY(mesh_upload(c, m, s->n_faces, hm));
     const int depth = m.depth;
     // Which form the swept-volume sweep takes: the FLAT evaluation for small meshes (<= 64 slots: the reference's 12- to 20-face
     // robots), else one task per workgroup with the quad-cooperative walks (round 6, C5 shape: drone.obj, 52 faces, 1.50 ms against
@@ -261,7 +260,7 @@ static int install_mesh(isdf_ctx *c, const isdf_shape *s, DevShape &d, const dou
     // open surfaces too (next to a boundary the winding number is a fraction), so it alone decides; `closed` is reported.)
     const bool closed = isdf_host::mesh_closed_by_index(s->mesh_faces, s->n_faces, s->n_vertices);
     MeshLattice lat;
-    { const int rc = mesh_lattice(c, s->n_faces, bb_h, d, hm, lat); if (rc) return rc; }
+    ISDF_TRY(mesh_lattice(c, s->n_faces, bb_h, d, hm, lat));
     {   // isdf_mesh_info
         int *mi = c->mesh_info;
         mi[0] = s->n_faces; mi[1] = m.tree.n_nodes(); mi[2] = depth; mi[3] = d.mesh_wg; mi[4] = closed ? 1 : 0; mi[5] = lat.want ? lat.solid : -1;
@@ -282,7 +281,7 @@ extern "C" int isdf_set_shape(isdf_ctx *c, const isdf_shape *s) {
     DevShape d{};
     double bb_c[3], bb_h[3];
     fill_dev_shape(s, d, bb_c, bb_h);
-    if (s->kind == ISDF_SHAPE_MESH) { const int rc = install_mesh(c, s, d, bb_h); if (rc) return rc; }
+    if (s->kind == ISDF_SHAPE_MESH) ISDF_TRY(install_mesh(c, s, d, bb_h));
     if (s->kind != ISDF_SHAPE_MESH) std::memset(c->mesh_info, 0, sizeof(c->mesh_info));
     isdf_frontend_release(c);       // the attitude kernels were voxelised from the previous shape
     c->d_shape_prog.release();
@@ -312,7 +311,7 @@ extern "C" int isdf_set_shape_grid(isdf_ctx *c, const double *cells, int nx, int
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)nx * ny * nz;
     free_mesh(c);
-    { const int rc = c->d_shape_grid.renew(c, n * 4); if (rc) return rc; }
+    ISDF_TRY(c->d_shape_grid.renew(c, n * 4));
     HIPCHK(c, hipMemcpy(c->d_shape_grid, cells, n * 4 * sizeof(double), hipMemcpyHostToDevice));
     DevShape d{};
     d.kind = ISDF_SHAPE_GRID; d.grad_mode = ISDF_GRAD_GRID;

@@ -42,7 +42,7 @@ int swept_field_scratch(isdf_ctx *c, SweptMeshState **out) {
     SweptMeshState *s = c->swm;
     *out = s;
     if (!s->d_stats) HIPCHK(c, s->d_stats.alloc(8));
-    { const int rc = s->h_overflow.reserve(c, 1); if (rc) return rc; }
+    ISDF_TRY(s->h_overflow.reserve(c, 1));
     return s->field.reserve(c, (size_t)FIELD_CHUNK, false);
 }
 
@@ -79,7 +79,7 @@ static SweptParams field_params(isdf_ctx *c, SweptMeshState *s, int N, const dou
 // query's scratch, the doubles swept_field_run builds again for the same trajectory and mode
 int swept_field_coarse_table(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, int mode, hipStream_t st) {
     SweptMeshState *s;
-    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    ISDF_TRY(swept_field_scratch(c, &s));
     SweptParams P = field_params(c, s, N, d_T, d_coeffs);
     P.points = nullptr; P.point_begin = 0; P.point_end = 0; P.M = 0;
     launch_swept_prepare(P, st, mode == ISDF_SWEPT_FIELD_CLOSED);
@@ -91,7 +91,7 @@ int swept_field_coarse_table(isdf_ctx *c, int N, const double *d_T, const double
 int swept_field_launch(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
                        double *d_value, double *d_tstar, hipStream_t st) {
     SweptMeshState *s;
-    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    ISDF_TRY(swept_field_scratch(c, &s));
     if (n <= 0) return ISDF_OK;
     const bool closed = mode == ISDF_SWEPT_FIELD_CLOSED;
     SweptParams P = field_params(c, s, N, d_T, d_coeffs);
@@ -113,7 +113,7 @@ int swept_field_launch(isdf_ctx *c, int N, const double *d_T, const double *d_co
 // the field at n points (device arrays), synchronous on `st` at the end (the overflow word is read back)
 int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
                     double *d_value, double *d_tstar, hipStream_t st) {
-    { const int rc = swept_field_launch(c, N, d_T, d_coeffs, d_xyz, n, mode, d_value, d_tstar, st); if (rc) return rc; }
+    ISDF_TRY(swept_field_launch(c, N, d_T, d_coeffs, d_xyz, n, mode, d_value, d_tstar, st));
     if (n <= 0) return ISDF_OK;
     SweptMeshState *s = c->swm;
     HIPCHK(c, hipMemcpyAsync(s->h_overflow, s->d_stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -394,8 +394,7 @@ int field_nodes(isdf_ctx *c, int N, const double *d_T, const double *d_C, const 
     for (long long b = 0; b < n; b += chunk) {
         const int m = (int)std::min(chunk, n - b);
         hipLaunchKernelGGL(node_xyz_kernel, dim3(blocks(m)), dim3(256), 0, st, L, ids, b, m, xyz.get());
-        const int rc = swept_field_run(c, N, d_T, d_C, xyz.get(), m, mode, val.get(), nullptr, st);
-        if (rc) return rc;
+        ISDF_TRY(swept_field_run(c, N, d_T, d_C, xyz.get(), m, mode, val.get(), nullptr, st));
         hipLaunchKernelGGL(node_scatter_kernel, dim3(blocks(m)), dim3(256), 0, st, ids, b, m, val.get(), f);
     }
     HIPCHK(c, hipGetLastError());
@@ -451,14 +450,14 @@ extern "C" int isdf_swept_sdf_device(isdf_ctx *c, int N, const double *d_T, cons
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (N < 1 || !d_T || !d_coeffs || n < 0 || (n > 0 && (!d_xyz || !d_value_out))) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: bad arguments");
     if (mode != ISDF_SWEPT_FIELD_PLANNER && mode != ISDF_SWEPT_FIELD_CLOSED) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: unknown mode");
-    { const int rc = swept_check_ctx(c); if (rc) return rc; }
+    ISDF_TRY(swept_check_ctx(c));
     HIPCHK(c, hipSetDevice(c->device));
     // the 300 s rule needs the durations on the host
     std::vector<double> hT(N);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(c, hipMemcpyAsync(hT.data(), d_T, N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    { const int rc = swept_check_traj(c, N, hT.data()); if (rc) return rc; }
+    ISDF_TRY(swept_check_traj(c, N, hT.data()));
     return swept_field_run(c, N, d_T, d_coeffs, d_xyz, n, mode, d_value_out, d_tstar_out, st);
 }
 
@@ -467,8 +466,8 @@ extern "C" int isdf_swept_sdf(isdf_ctx *c, int N, const double *T, const double 
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (N < 1 || !T || !coeffs || n < 0 || (n > 0 && (!xyz || !value_out))) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: bad arguments");
     if (mode != ISDF_SWEPT_FIELD_PLANNER && mode != ISDF_SWEPT_FIELD_CLOSED) return fail(c, ISDF_ERR_INVALID_ARG, "swept field: unknown mode");
-    { const int rc = swept_check_ctx(c); if (rc) return rc; }
-    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
+    ISDF_TRY(swept_check_ctx(c));
+    ISDF_TRY(swept_check_traj(c, N, T));
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DevBuf<double> d_in, d_xyz, d_out;
@@ -478,8 +477,7 @@ extern "C" int isdf_swept_sdf(isdf_ctx *c, int N, const double *T, const double 
     HIPCHK(c, hipMemcpyAsync(d_in.get(), T, N * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_in.get() + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
     if (n > 0) HIPCHK(c, hipMemcpyAsync(d_xyz.get(), xyz, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-    const int rc = swept_field_run(c, N, d_in.get(), d_in.get() + N, d_xyz.get(), n, mode, d_out.get(), d_out.get() + n, st);
-    if (rc) return rc;
+    ISDF_TRY(swept_field_run(c, N, d_in.get(), d_in.get() + N, d_xyz.get(), n, mode, d_out.get(), d_out.get() + n, st));
     if (n > 0) {
         HIPCHK(c, hipMemcpyAsync(value_out, d_out.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
         if (tstar_out) HIPCHK(c, hipMemcpyAsync(tstar_out, d_out.get() + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -503,14 +501,14 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
                                      isdf_swept_mesh_info *info_out) {
     // (arguments first: a NULL ctx with bad arguments reports what is wrong with them through isdf_last_error(NULL))
     if (N < 1 || !T || !coeffs) return fail(c, ISDF_ERR_INVALID_ARG, "swept mesh: null trajectory");
-    { const int rc = check_mesh_params(c, p); if (rc) return rc; }
+    ISDF_TRY(check_mesh_params(c, p));
     if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "swept mesh: null ctx");
-    { const int rc = swept_check_ctx(c); if (rc) return rc; }
-    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
+    ISDF_TRY(swept_check_ctx(c));
+    ISDF_TRY(swept_check_traj(c, N, T));
     for (int k = 0; k < 18 * N; k++) if (!std::isfinite(coeffs[k])) return fail(c, ISDF_ERR_INVALID_ARG, "swept mesh: non-finite coefficient");
     HIPCHK(c, hipSetDevice(c->device));
     SweptMeshState *s;
-    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    ISDF_TRY(swept_field_scratch(c, &s));
     free_mesh_result(s);
     hipStream_t st = c->stream;
 
@@ -546,7 +544,7 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     const long long n_cells = (dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1);
 
     // ---- the trajectory on the device
-    { const int rc = s->d_traj.reserve(c, (size_t)19 * N); if (rc) return rc; }
+    ISDF_TRY(s->d_traj.reserve(c, (size_t)19 * N));
     HIPCHK(c, hipMemcpyAsync(s->d_traj, T, N * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(s->d_traj + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
     const double *d_T = s->d_traj, *d_C = s->d_traj + N;
@@ -562,8 +560,7 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     // ---- the field: dense, or coarse lattice + narrow band
     long long coarse_points = 0, fine_points = 0;
     if (p->band == 0) {
-        const int rc = field_nodes(c, N, d_T, d_C, L, nullptr, n_nodes, p->mode, f.get(), st);
-        if (rc) return rc;
+        ISDF_TRY(field_nodes(c, N, d_T, d_C, L, nullptr, n_nodes, p->mode, f.get(), st));
         fine_points = n_nodes;
     } else {
         const int B = p->band;
@@ -572,7 +569,7 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
         DevBuf<int> cids;
         HIPCHK(c, cids.alloc((size_t)n_coarse));
         hipLaunchKernelGGL(coarse_ids_kernel, dim3(blocks(n_coarse)), dim3(256), 0, st, L, Q, cids.get());
-        { const int rc = field_nodes(c, N, d_T, d_C, L, cids.get(), n_coarse, p->mode, f.get(), st); if (rc) return rc; }
+        ISDF_TRY(field_nodes(c, N, d_T, d_C, L, cids.get(), n_coarse, p->mode, f.get(), st));
         coarse_points = n_coarse;
         DevBuf<unsigned char> refine, flag;
         HIPCHK(c, refine.alloc((size_t)n_ccells));
@@ -595,7 +592,7 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
             HIPCHK(c, hipStreamSynchronize(st));
             fine_points = nsel;
         }
-        { const int rc = field_nodes(c, N, d_T, d_C, L, fids.get(), fine_points, p->mode, f.get(), st); if (rc) return rc; }
+        ISDF_TRY(field_nodes(c, N, d_T, d_C, L, fids.get(), fine_points, p->mode, f.get(), st));
     }
     HIPCHK(c, hipEventRecord(ev[1], st));
 
@@ -616,8 +613,8 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     HIPCHK(c, hipStreamSynchronize(st));
     if (cnt[1] > (unsigned long long)INT32_MAX / 3 || cnt[2] > (unsigned long long)INT32_MAX / 3)
         return fail(c, ISDF_ERR_OVERFLOW, "swept mesh: more than 2^31 / 3 vertices or triangles");
-    { const int rc = exclusive_sum(c, tcount.get(), tbase.get(), n_cells, st); if (rc) return rc; }
-    { const int rc = exclusive_sum(c, vcount.get(), vbase.get(), n_nodes, st); if (rc) return rc; }
+    ISDF_TRY(exclusive_sum(c, tcount.get(), tbase.get(), n_cells, st));
+    ISDF_TRY(exclusive_sum(c, vcount.get(), vbase.get(), n_nodes, st));
     HIPCHK(c, s->d_V.alloc((size_t)(cnt[2] ? cnt[2] : 1) * 3));
     HIPCHK(c, s->d_F.alloc((size_t)(cnt[1] ? cnt[1] : 1) * 3));
     hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, (const double *)f.get(), p->iso,

@@ -17,6 +17,7 @@
 //            among the points whose t* lies in it, and the points below the margin compacted in voxel order.  Minima and integer
 //            sums only: the report does not depend on the launch geometry, and two runs give the same bytes.
 #include "swept_field.hpp"
+#include "traj_call.hpp"
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -292,7 +293,7 @@ int check_args(isdf_ctx *c, int N, const void *T, const void *coeffs, const isdf
 }
 // ... and what needs one; margin_out = the margin in force
 int check_state(isdf_ctx *c, const isdf_traj_check_params *p, double *margin_out) {
-    { const int rc = swept_check_ctx(c); if (rc) return rc; }
+    ISDF_TRY(swept_check_ctx(c));
     if (!c->have_geom || !c->d_occ)
         return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: no occupancy grid (isdf_set_grid with ISDF_GRID_OCCUPANCY, or isdf_set_pointcloud)");
     const double band = 2 * c->cfg.safety_hor + 0.1;
@@ -313,7 +314,7 @@ struct Selection {
 int select_run(isdf_ctx *c, SweptMeshState *s, int N, const double *d_T, const double *d_C, int mode, const uint8_t *src, bool known, const char *op,
                Selection &L, hipStream_t st) {
     // ---- select: the coarse positions, their box, bricks, rows, scan, emit
-    { const int rc = swept_field_coarse_table(c, N, d_T, d_C, mode, st); if (rc) return rc; }
+    ISDF_TRY(swept_field_coarse_table(c, N, d_T, d_C, mode, st));
     std::vector<double> pos(3 * (size_t)SWEPT_MAX_COARSE);
     int n_coarse = 0;
     HIPCHK(c, hipMemcpyAsync(pos.data(), s->field.coarse_pose, pos.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -374,7 +375,7 @@ int select_run(isdf_ctx *c, SweptMeshState *s, int N, const double *d_T, const d
         HIPCHK(c, hipStreamSynchronize(st));
         if (cnt[1] > (unsigned long long)INT32_MAX) return fail(c, ISDF_ERR_OVERFLOW, (std::string(op) + ": more than 2^31 candidate voxels").c_str());
         if (cnt[1]) {
-            { const int rc = exclusive_sum(c, count.get(), base.get(), n_rows, st); if (rc) return rc; }
+            ISDF_TRY(exclusive_sum(c, count.get(), base.get(), n_rows, st));
             HIPCHK(c, vox.alloc((size_t)cnt[1]));
             HIPCHK(c, xyz.alloc((size_t)cnt[1] * 3));
             hipLaunchKernelGGL(tc_emit_kernel, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B,
@@ -393,14 +394,14 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     TrajCheckState *k = c->tck;
     free_rows(k);
     SweptMeshState *s;
-    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    ISDF_TRY(swept_field_scratch(c, &s));
     hipEvent_t ev[4];
     for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
     struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
     HIPCHK(c, hipEventRecord(ev[0], st));
 
     Selection L;
-    { const int rc = select_run(c, s, N, d_T, d_C, mode, (const uint8_t *)c->d_occ, false, "trajectory check", L, st); if (rc) return rc; }
+    ISDF_TRY(select_run(c, s, N, d_T, d_C, mode, (const uint8_t *)c->d_occ, false, "trajectory check", L, st));
     const bool cull = L.cull, empty = L.empty;
     const double far_r = L.far_r;
     const SelBox &B = L.B;
@@ -413,7 +414,7 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     // ---- field
     DevBuf<double> val, ts;
     HIPCHK(c, val.alloc((size_t)n)); HIPCHK(c, ts.alloc((size_t)n));
-    { const int rc = swept_field_run(c, N, d_T, d_C, xyz.get(), n, mode, val.get(), ts.get(), st); if (rc) return rc; }
+    ISDF_TRY(swept_field_run(c, N, d_T, d_C, xyz.get(), n, mode, val.get(), ts.get(), st));
     HIPCHK(c, hipEventRecord(ev[2], st));
 
     // ---- reduce
@@ -421,7 +422,7 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     DevBuf<unsigned long long> d_counts;
     DevBuf<double> report;
     HIPCHK(c, d_counts.alloc(3)); HIPCHK(c, report.alloc(REPORT_WORDS));
-    { const int rc = tc_reduce_launch(c, red, n, val.get(), ts.get(), vox.get(), xyz.get(), d_T, N, margin, d_counts.get(), report.get(), d_piece_min, st); if (rc) return rc; }
+    ISDF_TRY(tc_reduce_launch(c, red, n, val.get(), ts.get(), vox.get(), xyz.get(), d_T, N, margin, d_counts.get(), report.get(), d_piece_min, st));
     unsigned long long counts[3];
     double rep[REPORT_WORDS];
     HIPCHK(c, hipMemcpyAsync(counts, d_counts.get(), sizeof(counts), hipMemcpyDeviceToHost, st));
@@ -430,7 +431,7 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
     if (counts[1]) {
         HIPCHK(c, k->d_rows.alloc((size_t)counts[1] * 5));
         HIPCHK(c, k->d_row_vox.alloc((size_t)counts[1]));
-        { const int rc = tc_rows_launch(c, red, n, val.get(), ts.get(), vox.get(), xyz.get(), k->d_rows.get(), k->d_row_vox.get(), st); if (rc) return rc; }
+        ISDF_TRY(tc_rows_launch(c, red, n, val.get(), ts.get(), vox.get(), xyz.get(), k->d_rows.get(), k->d_row_vox.get(), st));
     }
     HIPCHK(c, hipEventRecord(ev[3], st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -460,7 +461,7 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
         // arm: the trajectory, the parameters in force, the report and its piece minima, the selection box (mode 1 of
         // isdf_traj_check_set_watch; the rows and their voxel ids are the kept ones)
         TrajWatchState &w = k->w;
-        { const int rc = w.d_traj.reserve(c, (size_t)20 * N); if (rc) return rc; }
+        ISDF_TRY(w.d_traj.reserve(c, (size_t)20 * N));
         if (d_T != w.d_traj.get()) {            // (a whole-map re-check runs on the kept copy itself)
             HIPCHK(c, hipMemcpyAsync(w.d_traj, d_T, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
             HIPCHK(c, hipMemcpyAsync(w.d_traj + N, d_C, (size_t)18 * N * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -483,10 +484,10 @@ int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const in
 int tc_reduce_launch(isdf_ctx *c, TcReduceScratch &S, long long n, const double *d_val, const double *d_ts, const long long *d_vox, const double *d_xyz,
                      const double *d_T, int N, double margin, unsigned long long *d_counts, double *d_report, double *d_piece_min, hipStream_t st) {
     const int n_part = (int)std::max<long long>(1, blocks(n));
-    { const int rc = S.flag.reserve(c, (size_t)std::max<long long>(n, 1)); if (rc) return rc; }
-    { const int rc = S.fbase.reserve(c, (size_t)std::max<long long>(n, 1)); if (rc) return rc; }
-    { const int rc = S.key.reserve(c, (size_t)N); if (rc) return rc; }
-    { const int rc = S.partial.reserve(c, (size_t)n_part * sizeof(MinRec)); if (rc) return rc; }
+    ISDF_TRY(S.flag.reserve(c, (size_t)std::max<long long>(n, 1)));
+    ISDF_TRY(S.fbase.reserve(c, (size_t)std::max<long long>(n, 1)));
+    ISDF_TRY(S.key.reserve(c, (size_t)N));
+    ISDF_TRY(S.partial.reserve(c, (size_t)n_part * sizeof(MinRec)));
     HIPCHK(c, hipMemsetAsync(d_counts, 0, 3 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(tc_key_fill_kernel, dim3(blocks(N)), dim3(256), 0, st, S.key.get(), N);
     if (n > 0) hipLaunchKernelGGL(tc_reduce_kernel, dim3(n_part), dim3(256), 0, st, n, d_val, d_ts, d_T, N, margin, S.flag.get(), S.key.get(),
@@ -502,7 +503,7 @@ int tc_rows_launch(isdf_ctx *c, TcReduceScratch &S, long long n, const double *d
     if (n <= 0) return ISDF_OK;
     size_t bytes = 0;
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, S.flag.get(), S.fbase.get(), (int)n, st));
-    { const int rc = S.scan_tmp.reserve(c, std::max<size_t>(bytes, 1)); if (rc) return rc; }
+    ISDF_TRY(S.scan_tmp.reserve(c, std::max<size_t>(bytes, 1)));
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S.scan_tmp.get(), bytes, S.flag.get(), S.fbase.get(), (int)n, st));
     hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)S.flag.get(), (const int *)S.fbase.get(), d_xyz, d_val, d_ts, d_rows);
     hipLaunchKernelGGL(tc_row_vox_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)S.flag.get(), (const int *)S.fbase.get(), d_vox, d_row_vox);
@@ -537,16 +538,16 @@ extern "C" void isdf_traj_check_params_default(isdf_traj_check_params *p) {
 
 extern "C" int isdf_traj_check_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const isdf_traj_check_params *p,
                                       isdf_traj_check_info *info_out, double *d_piece_min_out, void *stream) {
-    { const int rc = check_args(c, N, d_T, d_coeffs, p); if (rc) return rc; }
+    ISDF_TRY(check_args(c, N, d_T, d_coeffs, p));
     if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "trajectory check: null ctx");
     double margin = 0.0;
-    { const int rc = check_state(c, p, &margin); if (rc) return rc; }
+    ISDF_TRY(check_state(c, p, &margin));
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     std::vector<double> hT(N);          // the 300 s rule needs the durations on the host
     HIPCHK(c, hipMemcpyAsync(hT.data(), d_T, N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    { const int rc = swept_check_traj(c, N, hT.data()); if (rc) return rc; }
+    ISDF_TRY(swept_check_traj(c, N, hT.data()));
     DevBuf<double> own;
     if (!d_piece_min_out) { HIPCHK(c, own.alloc((size_t)N)); d_piece_min_out = own.get(); }
     return check_run(c, N, d_T, d_coeffs, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, d_piece_min_out, st);
@@ -554,21 +555,20 @@ extern "C" int isdf_traj_check_device(isdf_ctx *c, int N, const double *d_T, con
 
 extern "C" int isdf_traj_check(isdf_ctx *c, int N, const double *T, const double *coeffs, const isdf_traj_check_params *p,
                                isdf_traj_check_info *info_out, double *piece_min_out) {
-    { const int rc = check_args(c, N, T, coeffs, p); if (rc) return rc; }
+    ISDF_TRY(check_args(c, N, T, coeffs, p));
     if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "trajectory check: null ctx");
     double margin = 0.0;
-    { const int rc = check_state(c, p, &margin); if (rc) return rc; }
-    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
+    ISDF_TRY(check_state(c, p, &margin));
+    ISDF_TRY(swept_check_traj(c, N, T));
     for (int q = 0; q < 18 * N; q++) if (!std::isfinite(coeffs[q])) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: non-finite coefficient");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->tck) c->tck = new TrajCheckState();
     TrajCheckState *k = c->tck;
     hipStream_t st = c->stream;
-    { const int rc = k->d_traj.reserve(c, (size_t)20 * N); if (rc) return rc; }     // T | coeffs | per-piece minima
-    HIPCHK(c, hipMemcpyAsync(k->d_traj, T, N * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(k->d_traj + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
+    ISDF_TRY(k->d_traj.reserve(c, (size_t)20 * N));     // T | coeffs | per-piece minima
+    ISDF_TRY(traj_call::upload(c, k->d_traj, (size_t)N, T, coeffs, st));        // (its own 19 N fit: the layout stays)
     double *d_pm = k->d_traj + 19 * (size_t)N;
-    { const int rc = check_run(c, N, k->d_traj, k->d_traj + N, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, d_pm, st); if (rc) return rc; }
+    ISDF_TRY(check_run(c, N, k->d_traj, k->d_traj + N, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, d_pm, st));
     if (piece_min_out) HIPCHK(c, hipMemcpy(piece_min_out, d_pm, N * sizeof(double), hipMemcpyDeviceToHost));
     return ISDF_OK;
 }
@@ -592,8 +592,7 @@ extern "C" int isdf_traj_check_release(isdf_ctx *c) {
 
 extern "C" int isdf_traj_collide(isdf_ctx *c, int N, const double *T, const double *coeffs) {
     isdf_traj_check_info info;
-    const int rc = isdf_traj_check(c, N, T, coeffs, nullptr, &info, nullptr);
-    if (rc) return rc;
+    ISDF_TRY(isdf_traj_check(c, N, T, coeffs, nullptr, &info, nullptr));
     return info.n_penetrating > 0 ? 1 : 0;
 }
 
@@ -603,18 +602,18 @@ namespace {
 
 int horizon_run(isdf_ctx *c, int N, const double *hT, const double *d_T, const double *d_C, int mode, double margin, isdf_traj_known_info *info, hipStream_t st) {
     SweptMeshState *s;
-    { const int rc = swept_field_scratch(c, &s); if (rc) return rc; }
+    ISDF_TRY(swept_field_scratch(c, &s));
     hipEvent_t ev[4];
     for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
     struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
     HIPCHK(c, hipEventRecord(ev[0], st));
     Selection L;
-    { const int rc = select_run(c, s, N, d_T, d_C, mode, (const uint8_t *)c->known.d_bits.get(), true, "known horizon", L, st); if (rc) return rc; }
+    ISDF_TRY(select_run(c, s, N, d_T, d_C, mode, (const uint8_t *)c->known.d_bits.get(), true, "known horizon", L, st));
     const long long n = (long long)L.cnt[1];
     HIPCHK(c, hipEventRecord(ev[1], st));
     DevBuf<double> val, ts;
     HIPCHK(c, val.alloc((size_t)n)); HIPCHK(c, ts.alloc((size_t)n));
-    { const int rc = swept_field_run(c, N, d_T, d_C, L.xyz.get(), n, mode, val.get(), ts.get(), st); if (rc) return rc; }
+    ISDF_TRY(swept_field_run(c, N, d_T, d_C, L.xyz.get(), n, mode, val.get(), ts.get(), st));
     HIPCHK(c, hipEventRecord(ev[2], st));
     DevBuf<unsigned long long> d_rec;
     unsigned long long rec[TH_WORDS] = {0, 0, 0, ~0ull, ~0ull, ~0ull, ~0ull, 0};
@@ -668,9 +667,9 @@ int horizon_ready(isdf_ctx *c, int N, const void *T, const void *coeffs, const i
     isdf_traj_check_params q;
     isdf_traj_check_params_default(&q);
     if (p) { q.margin = p->margin; q.mode = p->mode; }
-    { const int rc = check_args(c, N, T, coeffs, &q); if (rc) return rc; }
+    ISDF_TRY(check_args(c, N, T, coeffs, &q));
     if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "known horizon: null ctx");
-    { const int rc = check_state(c, &q, margin); if (rc) return rc; }
+    ISDF_TRY(check_state(c, &q, margin));
     if (!c->known.have) return fail(c, ISDF_ERR_STATE, "known horizon: no known grid (isdf_map_known_enable, then a map from isdf_set_pointcloud)");
     return ISDF_OK;
 }
@@ -687,21 +686,21 @@ extern "C" void isdf_traj_known_params_default(isdf_traj_known_params *p) {
 extern "C" int isdf_traj_known_horizon_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const isdf_traj_known_params *p,
                                               isdf_traj_known_info *info_out, void *stream) {
     double margin = 0.0;
-    { const int rc = horizon_ready(c, N, d_T, d_coeffs, p, &margin); if (rc) return rc; }
+    ISDF_TRY(horizon_ready(c, N, d_T, d_coeffs, p, &margin));
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     std::vector<double> hT(N);
     HIPCHK(c, hipMemcpyAsync(hT.data(), d_T, N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    { const int rc = swept_check_traj(c, N, hT.data()); if (rc) return rc; }
+    ISDF_TRY(swept_check_traj(c, N, hT.data()));
     HIPCHK(c, hipStreamSynchronize(c->stream));         // the known grid is written on the ctx's stream
     return horizon_run(c, N, hT.data(), d_T, d_coeffs, p ? p->mode : ISDF_SWEPT_FIELD_PLANNER, margin, info_out, st);
 }
 
 extern "C" int isdf_traj_known_horizon(isdf_ctx *c, int N, const double *T, const double *coeffs, const isdf_traj_known_params *p, isdf_traj_known_info *info_out) {
     double margin = 0.0;
-    { const int rc = horizon_ready(c, N, T, coeffs, p, &margin); if (rc) return rc; }
-    { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }
+    ISDF_TRY(horizon_ready(c, N, T, coeffs, p, &margin));
+    ISDF_TRY(swept_check_traj(c, N, T));
     for (int q = 0; q < 18 * N; q++) if (!std::isfinite(coeffs[q])) return fail(c, ISDF_ERR_INVALID_ARG, "known horizon: non-finite coefficient");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<double> traj;                    // own upload: the check's kept trajectory is not touched

@@ -16,21 +16,18 @@
 //            value, then smaller time, then the earlier piece.  A total order, maxima and integer sums only: the report does
 //            not depend on the launch geometry or on the trajectory's place in a batch.
 // Two launches per call whatever B is; the scratch lives in the ctx (TrajLimitsState) and grows only.
-#include "isdf_ctx.hpp"
+#include "traj_call.hpp"
 #include "traj_limits_host.hpp"
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-struct TrajLimitsState {
-    DevBuf<double> d_in;            // host forms: T | coeffs of every trajectory of the call
+struct TrajLimitsState : traj_call::State {     // d_in: T | coeffs of every trajectory of the call; d_out: unused
     DevBuf<double> d_piece;         // [B N][12]
     DevBuf<double> d_info;          // [B][INFO_WORDS]
     DevBuf<double> d_samp;          // sampler, host form: stamps | rows
-    std::vector<double> h_info, h_T;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~TrajLimitsState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    std::vector<double> h_T;
 };
 
 namespace {
@@ -209,19 +206,10 @@ __global__ __launch_bounds__(256) void tl_sample_kernel(FlatP P, TrajView tr, lo
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
+using namespace traj_call;
 
-int check_ctx(isdf_ctx *c, const char *what_null, const char *what_multi) {
-    if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, what_null);
-    if (!c->peers.empty() || c->is_peer || c->rccl_comm) return fail(c, ISDF_ERR_UNSUPPORTED, what_multi);
-    return ISDF_OK;
-}
-int state(isdf_ctx *c, TrajLimitsState **out) {
-    if (!c->tlm) c->tlm = new TrajLimitsState();
-    *out = c->tlm;
-    for (auto &e : c->tlm->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    return ISDF_OK;
-}
+int limits_ctx(isdf_ctx *c) { return check_ctx(c, "trajectory limits: null ctx", "trajectory limits on a multi-device ctx"); }
+int sample_ctx(isdf_ctx *c) { return check_ctx(c, "trajectory sample: null ctx", "trajectory sample on a multi-device ctx"); }
 
 // the two launches of B trajectories on device arrays, nothing else: no event, no copy, no synchronisation
 int limits_launch(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, const isdf_traj_limits_params *p, double *d_piece, double *d_info,
@@ -255,23 +243,18 @@ void limits_unpack(const isdf_config &cfg, const isdf_traj_limits_params *p, con
 }
 
 // the report of B trajectories on device arrays.  d_piece: B N x 12 on the device, or null (the state's own)
-int limits_run(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, const isdf_traj_limits_params *p,
+int limits_run(isdf_ctx *c, TrajLimitsState *k, int B, int N, const double *d_T, const double *d_C, const isdf_traj_limits_params *p,
                isdf_traj_limits_info *infos, double *d_piece, hipStream_t st) {
-    TrajLimitsState *k;
-    { const int rc = state(c, &k); if (rc) return rc; }
-    const size_t pieces = (size_t)B * N;
-    if (!d_piece) { const int rc = k->d_piece.reserve(c, pieces * 12); if (rc) return rc; d_piece = k->d_piece; }
-    { const int rc = k->d_info.reserve(c, (size_t)B * INFO_WORDS); if (rc) return rc; }
+    const size_t words = (size_t)B * INFO_WORDS;
+    if (!d_piece) { ISDF_TRY(k->d_piece.reserve(c, (size_t)B * N * 12)); d_piece = k->d_piece; }
+    ISDF_TRY(k->d_info.reserve(c, words));
     HIPCHK(c, hipEventRecord(k->ev[0], st));
-    { const int rc = limits_launch(c, B, N, d_T, d_C, p, d_piece, k->d_info, st); if (rc) return rc; }
-    HIPCHK(c, hipEventRecord(k->ev[1], st));
-    if (k->h_info.size() < (size_t)B * INFO_WORDS) k->h_info.resize((size_t)B * INFO_WORDS);
-    HIPCHK(c, hipMemcpyAsync(k->h_info.data(), k->d_info, (size_t)B * INFO_WORDS * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    ISDF_TRY(limits_launch(c, B, N, d_T, d_C, p, d_piece, k->d_info, st));
+    double *h_info = k->host_words(words);
     float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    ISDF_TRY(finish(c, k, st, {{h_info, k->d_info, words}}, &ms));
     if (infos) for (int b = 0; b < B; b++) {
-        limits_unpack(c->cfg, p, k->h_info.data() + (size_t)b * INFO_WORDS, infos + b);
+        limits_unpack(c->cfg, p, h_info + (size_t)b * INFO_WORDS, infos + b);
         infos[b].device_ms = ms;
     }
     return ISDF_OK;
@@ -279,9 +262,7 @@ int limits_run(isdf_ctx *c, int B, int N, const double *d_T, const double *d_C, 
 
 int check_trajs(isdf_ctx *c, int B, int N, const double *T, const void *coeffs) {
     if (B < 1 || N < 1 || !T || !coeffs) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory limits: null trajectory");
-    for (long long q = 0; q < (long long)B * N; q++)
-        if (!(T[q] > 0.0) || !std::isfinite(T[q])) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory limits: a duration is not positive and finite");
-    return ISDF_OK;
+    return check_durations(c, (long long)B * N, T, "trajectory limits: a duration is not positive and finite");
 }
 // the durations of a device trajectory onto the host, checked
 int check_device_traj(isdf_ctx *c, TrajLimitsState *k, int N, const double *d_T, hipStream_t st) {
@@ -322,17 +303,13 @@ extern "C" void isdf_traj_limits_sizes(int out[2]) {
 
 extern "C" int isdf_traj_limits_batch(isdf_ctx *c, int B, int N, const double *T, const double *coeffs, const isdf_traj_limits_params *p,
                                       isdf_traj_limits_info *infos_out, double *piece_out) {
-    { const int rc = check_trajs(c, B, N, T, coeffs); if (rc) return rc; }
-    { const int rc = check_ctx(c, "trajectory limits: null ctx", "trajectory limits on a multi-device ctx"); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(check_trajs(c, B, N, T, coeffs));
+    ISDF_TRY(limits_ctx(c));
     TrajLimitsState *k;
-    { const int rc = state(c, &k); if (rc) return rc; }
-    hipStream_t st = c->stream;
+    ISDF_TRY(state_of(c, c->tlm, &k));
     const size_t nT = (size_t)B * N;
-    { const int rc = k->d_in.reserve(c, 19 * nT); if (rc) return rc; }
-    HIPCHK(c, hipMemcpyAsync(k->d_in, T, nT * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(k->d_in + nT, coeffs, 18 * nT * sizeof(double), hipMemcpyHostToDevice, st));
-    { const int rc = limits_run(c, B, N, k->d_in, k->d_in + nT, p, infos_out, nullptr, st); if (rc) return rc; }
+    ISDF_TRY(upload(c, k->d_in, nT, T, coeffs, c->stream));
+    ISDF_TRY(limits_run(c, k, B, N, k->d_in, k->d_in + nT, p, infos_out, nullptr, c->stream));
     if (piece_out) HIPCHK(c, hipMemcpy(piece_out, k->d_piece, 12 * nT * sizeof(double), hipMemcpyDeviceToHost));
     return ISDF_OK;
 }
@@ -345,13 +322,12 @@ extern "C" int isdf_traj_limits(isdf_ctx *c, int N, const double *T, const doubl
 extern "C" int isdf_traj_limits_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const isdf_traj_limits_params *p,
                                        isdf_traj_limits_info *info_out, double *d_piece_out, void *stream) {
     if (N < 1 || !d_T || !d_coeffs) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory limits: null trajectory");
-    { const int rc = check_ctx(c, "trajectory limits: null ctx", "trajectory limits on a multi-device ctx"); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(limits_ctx(c));
     TrajLimitsState *k;
-    { const int rc = state(c, &k); if (rc) return rc; }
+    ISDF_TRY(state_of(c, c->tlm, &k));
     hipStream_t st = (hipStream_t)stream;
-    { const int rc = check_device_traj(c, k, N, d_T, st); if (rc) return rc; }
-    return limits_run(c, 1, N, d_T, d_coeffs, p, info_out, d_piece_out, st);
+    ISDF_TRY(check_device_traj(c, k, N, d_T, st));
+    return limits_run(c, k, 1, N, d_T, d_coeffs, p, info_out, d_piece_out, st);
 }
 
 extern "C" int isdf_traj_limits_host(const isdf_config *cfg, int N, const double *T, const double *coeffs, const isdf_traj_limits_params *p,
@@ -364,12 +340,11 @@ extern "C" int isdf_traj_limits_host(const isdf_config *cfg, int N, const double
 extern "C" int isdf_traj_sample_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, long long n, const double *d_t,
                                        double *d_rows_out, void *stream) {
     if (N < 1 || !d_T || !d_coeffs || n < 0 || (n > 0 && (!d_t || !d_rows_out))) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory sample: null argument");
-    { const int rc = check_ctx(c, "trajectory sample: null ctx", "trajectory sample on a multi-device ctx"); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(sample_ctx(c));
     TrajLimitsState *k;
-    { const int rc = state(c, &k); if (rc) return rc; }
+    ISDF_TRY(state_of(c, c->tlm, &k));
     hipStream_t st = (hipStream_t)stream;
-    { const int rc = check_device_traj(c, k, N, d_T, st); if (rc) return rc; }
+    ISDF_TRY(check_device_traj(c, k, N, d_T, st));
     if (n == 0) return ISDF_OK;
     FlatP P;
     isdf_fill_flat(c->cfg, P);
@@ -383,18 +358,15 @@ extern "C" int isdf_traj_sample_device(isdf_ctx *c, int N, const double *d_T, co
 
 extern "C" int isdf_traj_sample(isdf_ctx *c, int N, const double *T, const double *coeffs, long long n, const double *t, double *rows_out) {
     if (n < 0 || (n > 0 && (!t || !rows_out))) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory sample: null argument");
-    { const int rc = check_trajs(c, 1, N, T, coeffs); if (rc) return rc; }
-    { const int rc = check_ctx(c, "trajectory sample: null ctx", "trajectory sample on a multi-device ctx"); if (rc) return rc; }
+    ISDF_TRY(check_trajs(c, 1, N, T, coeffs));
+    ISDF_TRY(sample_ctx(c));
     if (n == 0) return ISDF_OK;
-    HIPCHK(c, hipSetDevice(c->device));
     TrajLimitsState *k;
-    { const int rc = state(c, &k); if (rc) return rc; }
+    ISDF_TRY(state_of(c, c->tlm, &k));
     hipStream_t st = c->stream;
     const size_t nT = (size_t)N, nn = (size_t)n;
-    { const int rc = k->d_in.reserve(c, 19 * nT); if (rc) return rc; }
-    { const int rc = k->d_samp.reserve(c, (1 + ISDF_TRAJ_SAMPLE_ROW) * nn); if (rc) return rc; }
-    HIPCHK(c, hipMemcpyAsync(k->d_in, T, nT * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(k->d_in + nT, coeffs, 18 * nT * sizeof(double), hipMemcpyHostToDevice, st));
+    ISDF_TRY(k->d_samp.reserve(c, (1 + ISDF_TRAJ_SAMPLE_ROW) * nn));
+    ISDF_TRY(upload(c, k->d_in, nT, T, coeffs, st));
     HIPCHK(c, hipMemcpyAsync(k->d_samp, t, nn * sizeof(double), hipMemcpyHostToDevice, st));
     FlatP P;
     isdf_fill_flat(c->cfg, P);

@@ -15,7 +15,7 @@
 //            so later rounds reproduce its bytes - work that buys the absence of a host decision.  After iterate R the lanes copy the
 //            result's arrays and report words.
 // 4 (R + 1) launches for any B, nothing between them on the host, no atomics; the scratch lives in the ctx and grows only.
-#include "isdf_ctx.hpp"
+#include "traj_call.hpp"
 #include "swept_field.hpp"
 #include "minco_dev_body.hpp"
 #include "traj_realloc_host.hpp"
@@ -30,18 +30,13 @@ constexpr int RES_WORDS = 8 + TW;       // status, rounds, pieces_changed, bindi
 struct RADevState { isdf_host::RAState s; int bad, reserved; };     // bad: a duration of the input is not positive and finite
 }  // namespace
 
-struct TrajReallocState {
-    DevBuf<double> d_in;                // host forms: heads | tails | Q | T of every trajectory of the call
-    DevBuf<double> d_out;               // host forms: the results, T | coeffs
+struct TrajReallocState : traj_call::State {    // d_in: heads | tails | Q | T of every trajectory of the call; d_out: the results, T | coeffs
     DevBuf<double> d_trj;               // the iterate: [B] T | [B] coeffs
     DevBuf<double> d_tnext;             // [B N]
     DevBuf<double> d_piece;             // [B N][12]
     DevBuf<double> d_info;              // [B][TW]
     DevBuf<RADevState> d_state;         // [B]
     DevBuf<double> d_res;               // [B][RES_WORDS]
-    std::vector<double> h_res;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~TrajReallocState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 namespace {
@@ -179,14 +174,8 @@ __global__ __launch_bounds__(64) void ra_update_kernel(const RAUpdate A, const R
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
-
-int state_of(isdf_ctx *c, TrajReallocState **out) {
-    if (!c->tra) c->tra = new TrajReallocState();
-    *out = c->tra;
-    for (auto &e : c->tra->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    return ISDF_OK;
-}
+using namespace traj_call;
+constexpr const char *BAD_DURATION = "trajectory realloc: a duration is not positive and finite";
 
 // what can be said without a ctx
 int check_args(isdf_ctx *c, long long B, int N, const double *head, const double *tail, const double *Q, const double *T,
@@ -202,63 +191,49 @@ int check_args(isdf_ctx *c, long long B, int N, const double *head, const double
         return fail(c, ISDF_ERR_INVALID_ARG, "trajectory realloc: an output overlaps an input or the other output");
     return ISDF_OK;
 }
-int check_durations(isdf_ctx *c, long long n, const double *T) {
-    if (isdf_host::ra_check_durations(n, T)) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory realloc: a duration is not positive and finite");
-    return ISDF_OK;
-}
-int check_ctx(isdf_ctx *c, const isdf_traj_realloc_params &P) {
-    if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "trajectory realloc: null ctx");
-    if (!c->peers.empty() || c->is_peer || c->rccl_comm) return fail(c, ISDF_ERR_UNSUPPORTED, "trajectory realloc on a multi-device ctx");
-    if (P.check) { const int rc = isdf_traj_check_ready(c); if (rc) return rc; }
+int ctx_gate(isdf_ctx *c, const isdf_traj_realloc_params &P) {
+    ISDF_TRY(check_ctx(c, "trajectory realloc: null ctx", "trajectory realloc on a multi-device ctx"));
+    if (P.check) ISDF_TRY(isdf_traj_check_ready(c));
     return ISDF_OK;
 }
 
-// the loop over device arrays: everything queued on st, then ONE synchronisation.  d_T_out / d_C_out: the B results
+// the loop over device arrays: everything queued on st, then ONE synchronisation
 int realloc_run(isdf_ctx *c, TrajReallocState *s, int B, int N, const double *d_head, const double *d_tail, const double *d_Q, const double *d_T,
-                const isdf_traj_realloc_params &P, double *d_T_out, double *d_C_out, double *h_T_out, double *h_C_out, isdf_traj_realloc_info *infos,
-                hipStream_t st) {
+                const isdf_traj_realloc_params &P, const Out &out, isdf_traj_realloc_info *infos, hipStream_t st) {
     const int R = P.rounds;
-    const size_t nT = (size_t)B * N;
-    { const int rc = s->d_trj.reserve(c, 19 * nT); if (rc) return rc; }
-    { const int rc = s->d_tnext.reserve(c, nT); if (rc) return rc; }
-    { const int rc = s->d_piece.reserve(c, 12 * nT); if (rc) return rc; }
-    { const int rc = s->d_info.reserve(c, (size_t)B * TW); if (rc) return rc; }
-    { const int rc = s->d_state.reserve(c, (size_t)B); if (rc) return rc; }
-    { const int rc = s->d_res.reserve(c, (size_t)B * RES_WORDS); if (rc) return rc; }
+    const size_t nT = (size_t)B * N, n_res = (size_t)B * RES_WORDS;
+    ISDF_TRY(s->d_trj.reserve(c, 19 * nT));
+    ISDF_TRY(s->d_tnext.reserve(c, nT));
+    ISDF_TRY(s->d_piece.reserve(c, 12 * nT));
+    ISDF_TRY(s->d_info.reserve(c, (size_t)B * TW));
+    ISDF_TRY(s->d_state.reserve(c, (size_t)B));
+    ISDF_TRY(s->d_res.reserve(c, n_res));
     double *cT = s->d_trj, *cC = s->d_trj + nT;
     RALimits lim;
     isdf_host::tl_limits(&P.limits, c->cfg, lim.limit);
     RASolve S{N, d_head, d_tail, d_Q, d_T, cT, cC};
     RAUpdate U{};
     U.N = N; U.R = R; U.headroom = P.headroom; U.f_max = P.f_max; U.T_in = d_T; U.T_cur = cT; U.C_cur = cC;
-    U.piece = s->d_piece; U.info = s->d_info; U.T_next = s->d_tnext; U.state = s->d_state; U.out_T = d_T_out; U.out_C = d_C_out; U.res = s->d_res;
+    U.piece = s->d_piece; U.info = s->d_info; U.T_next = s->d_tnext; U.state = s->d_state; U.out_T = out.d_T; U.out_C = out.d_C; U.res = s->d_res;
     const bool split = ra_split(N);
     const size_t lds = cbd::cb_lds_doubles(N, false) * sizeof(double);
     HIPCHK(c, hipEventRecord(s->ev[0], st));
     for (int k = 0; k <= R; k++) {
         if (split) hipLaunchKernelGGL(ra_solve_kernel<true>, dim3((unsigned)B), dim3(ra_threads(N)), lds, st, S);
         else hipLaunchKernelGGL(ra_solve_kernel<false>, dim3((unsigned)B), dim3(ra_threads(N)), lds, st, S);
-        { const int rc = isdf_traj_limits_launch(c, B, N, cT, cC, &P.limits, s->d_piece, s->d_info, st); if (rc) return rc; }
+        ISDF_TRY(isdf_traj_limits_launch(c, B, N, cT, cC, &P.limits, s->d_piece, s->d_info, st));
         U.k = k;
         hipLaunchKernelGGL(ra_update_kernel, dim3((unsigned)B), dim3(64), 0, st, U, lim);
         S.T_src = s->d_tnext;
     }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(s->ev[1], st));
-    if (s->h_res.size() < (size_t)B * RES_WORDS) s->h_res.resize((size_t)B * RES_WORDS);
-    HIPCHK(c, hipMemcpyAsync(s->h_res.data(), s->d_res, (size_t)B * RES_WORDS * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (h_T_out) {
-        HIPCHK(c, hipMemcpyAsync(h_T_out, d_T_out, nT * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(h_C_out, d_C_out, 18 * nT * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(c, hipStreamSynchronize(st));
-    for (int b = 0; b < B; b++)
-        if (s->h_res[(size_t)b * RES_WORDS + 7] != 0.0) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory realloc: a duration is not positive and finite");
+    double *h_res = s->host_words(n_res);
     float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+    ISDF_TRY(finish(c, s, st, {{h_res, s->d_res, n_res}, {out.h_T, out.d_T, nT}, {out.h_C, out.d_C, 18 * nT}}, &ms));
+    for (int b = 0; b < B; b++)
+        if (h_res[(size_t)b * RES_WORDS + 7] != 0.0) return fail(c, ISDF_ERR_INVALID_ARG, BAD_DURATION);
     if (infos) for (int b = 0; b < B; b++) {
         isdf_traj_realloc_info *info = infos + b;
-        const double *w = s->h_res.data() + (size_t)b * RES_WORDS;
+        const double *w = h_res + (size_t)b * RES_WORDS;
         std::memset(info, 0, sizeof(*info));
         info->status = (int32_t)w[0]; info->rounds = (int32_t)w[1]; info->pieces_changed = (int32_t)w[2]; info->binding = (int32_t)w[3];
         info->duration_in = w[4]; info->duration_out = w[5]; info->max_factor = w[6];
@@ -271,26 +246,19 @@ int realloc_run(isdf_ctx *c, TrajReallocState *s, int B, int N, const double *d_
 // the host-array forms: inputs up, the loop, results down
 int realloc_host_arrays(isdf_ctx *c, int B, int N, const double *heads, const double *tails, const double *Q, const double *T,
                         const isdf_traj_realloc_params &P, double *T_out, double *C_out, isdf_traj_realloc_info *infos) {
-    HIPCHK(c, hipSetDevice(c->device));
     TrajReallocState *s;
-    { const int rc = state_of(c, &s); if (rc) return rc; }
+    ISDF_TRY(state_of(c, c->tra, &s));
     hipStream_t st = c->stream;
     const size_t b = (size_t)B, nT = b * N, nQ = 3 * b * (size_t)(N - 1);
-    { const int rc = s->d_in.reserve(c, 18 * b + nQ + nT); if (rc) return rc; }
-    { const int rc = s->d_out.reserve(c, 19 * nT); if (rc) return rc; }
+    ISDF_TRY(s->d_in.reserve(c, 18 * b + nQ + nT));
+    ISDF_TRY(s->d_out.reserve(c, 19 * nT));
     double *dh = s->d_in, *dt = dh + 9 * b, *dq = dt + 9 * b, *dT = dq + nQ;
     HIPCHK(c, hipMemcpyAsync(dh, heads, 9 * b * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(dt, tails, 9 * b * sizeof(double), hipMemcpyHostToDevice, st));
     if (nQ) HIPCHK(c, hipMemcpyAsync(dq, Q, nQ * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(dT, T, nT * sizeof(double), hipMemcpyHostToDevice, st));
-    { const int rc = realloc_run(c, s, B, N, dh, dt, dq, dT, P, s->d_out, s->d_out + nT, T_out, C_out, infos, st); if (rc) return rc; }
-    if (P.check) {
-        isdf_traj_check_info chk;
-        const int rc = isdf_traj_check_device(c, N, s->d_out, s->d_out + nT, nullptr, &chk, nullptr, st);
-        if (rc) return rc;
-        if (infos) { infos->check = chk; infos->checked = 1; }
-    }
-    return ISDF_OK;
+    ISDF_TRY(realloc_run(c, s, B, N, dh, dt, dq, dT, P, Out{s->d_out, s->d_out + nT, T_out, C_out}, infos, st));
+    return P.check ? post_check(c, N, s->d_out, s->d_out + nT, infos, st) : ISDF_OK;
 }
 
 }  // namespace
@@ -312,44 +280,34 @@ extern "C" void isdf_traj_realloc_sizes(int out[2]) {
 
 extern "C" int isdf_traj_realloc_batch(isdf_ctx *c, int B, int N, const double *heads, const double *tails, const double *Q, const double *T,
                                        const isdf_traj_realloc_params *p, double *T_out, double *coeffs_out, isdf_traj_realloc_info *infos_out) {
-    { const int rc = check_args(c, B, N, heads, tails, Q, T, p, T_out, coeffs_out, true); if (rc) return rc; }
-    { const int rc = check_durations(c, (long long)B * N, T); if (rc) return rc; }
-    isdf_traj_realloc_params P;
-    if (p) P = *p; else isdf_host::ra_params_default(&P);
-    { const int rc = check_ctx(c, P); if (rc) return rc; }
+    ISDF_TRY(check_args(c, B, N, heads, tails, Q, T, p, T_out, coeffs_out, true));
+    ISDF_TRY(check_durations(c, (long long)B * N, T, BAD_DURATION));
+    const isdf_traj_realloc_params P = resolve(p, isdf_host::ra_params_default);
+    ISDF_TRY(ctx_gate(c, P));
     return realloc_host_arrays(c, B, N, heads, tails, Q, T, P, T_out, coeffs_out, infos_out);
 }
 
 extern "C" int isdf_traj_realloc(isdf_ctx *c, int N, const double *head_pva, const double *tail_pva, const double *Q, const double *T,
                                  const isdf_traj_realloc_params *p, double *T_out, double *coeffs_out, isdf_traj_realloc_info *info_out) {
-    { const int rc = check_args(c, 1, N, head_pva, tail_pva, Q, T, p, T_out, coeffs_out, false); if (rc) return rc; }
-    { const int rc = check_durations(c, N, T); if (rc) return rc; }
-    isdf_traj_realloc_params P;
-    if (p) P = *p; else isdf_host::ra_params_default(&P);
-    { const int rc = check_ctx(c, P); if (rc) return rc; }
-    if (P.check) { const int rc = swept_check_traj(c, N, T); if (rc) return rc; }       // the input must be a trajectory the check takes; the result's total is the check's to judge
+    ISDF_TRY(check_args(c, 1, N, head_pva, tail_pva, Q, T, p, T_out, coeffs_out, false));
+    ISDF_TRY(check_durations(c, N, T, BAD_DURATION));
+    const isdf_traj_realloc_params P = resolve(p, isdf_host::ra_params_default);
+    ISDF_TRY(ctx_gate(c, P));
+    if (P.check) ISDF_TRY(swept_check_traj(c, N, T));       // the input must be a trajectory the check takes; the result's total is the check's to judge
     return realloc_host_arrays(c, 1, N, head_pva, tail_pva, Q, T, P, T_out, coeffs_out, info_out);
 }
 
 extern "C" int isdf_traj_realloc_device(isdf_ctx *c, int N, const double *d_head_pva, const double *d_tail_pva, const double *d_Q, const double *d_T,
                                         const isdf_traj_realloc_params *p, double *d_T_out, double *d_coeffs_out, isdf_traj_realloc_info *info_out,
                                         void *stream) {
-    { const int rc = check_args(c, 1, N, d_head_pva, d_tail_pva, d_Q, d_T, p, d_T_out, d_coeffs_out, false); if (rc) return rc; }
-    isdf_traj_realloc_params P;
-    if (p) P = *p; else isdf_host::ra_params_default(&P);
-    { const int rc = check_ctx(c, P); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(check_args(c, 1, N, d_head_pva, d_tail_pva, d_Q, d_T, p, d_T_out, d_coeffs_out, false));
+    const isdf_traj_realloc_params P = resolve(p, isdf_host::ra_params_default);
+    ISDF_TRY(ctx_gate(c, P));
     TrajReallocState *s;
-    { const int rc = state_of(c, &s); if (rc) return rc; }
+    ISDF_TRY(state_of(c, c->tra, &s));
     hipStream_t st = (hipStream_t)stream;
-    { const int rc = realloc_run(c, s, 1, N, d_head_pva, d_tail_pva, d_Q, d_T, P, d_T_out, d_coeffs_out, nullptr, nullptr, info_out, st); if (rc) return rc; }
-    if (P.check) {
-        isdf_traj_check_info chk;
-        const int rc = isdf_traj_check_device(c, N, d_T_out, d_coeffs_out, nullptr, &chk, nullptr, st);
-        if (rc) return rc;
-        if (info_out) { info_out->check = chk; info_out->checked = 1; }
-    }
-    return ISDF_OK;
+    ISDF_TRY(realloc_run(c, s, 1, N, d_head_pva, d_tail_pva, d_Q, d_T, P, Out{d_T_out, d_coeffs_out, nullptr, nullptr}, info_out, st));
+    return P.check ? post_check(c, N, d_T_out, d_coeffs_out, info_out, st) : ISDF_OK;
 }
 
 extern "C" int isdf_traj_realloc_host(const isdf_config *cfg, int N, const double *head_pva, const double *tail_pva, const double *Q, const double *T,

@@ -12,7 +12,7 @@
 //            the limits, a ballot gives the feasibility mask, tr_advance turns it into the next bracket and the status - every lane
 //            computes the same state, lane 0 stores it.  After the last round the lanes copy the chosen candidate's arrays and report.
 // 1 + 4 rounds launches for any B, nothing between them on the host, no atomics; the scratch lives in the ctx and grows only.
-#include "isdf_ctx.hpp"
+#include "traj_call.hpp"
 #include "swept_field.hpp"
 #include "traj_retime_host.hpp"
 #include <cmath>
@@ -26,18 +26,13 @@ constexpr int RES_WORDS = 8 + TW;       // scale, scale_below, status, rounds, n
 constexpr int ST_WORDS = 2;             // next to a trajectory's TRState: duration_in, 1 if a duration is not positive and finite
 }  // namespace
 
-struct TrajRetimeState {
-    DevBuf<double> d_in;                // host forms: T | coeffs of every trajectory of the call
-    DevBuf<double> d_out;               // host forms: the results, same layout
+struct TrajRetimeState : traj_call::State {     // d_in: T | coeffs of every trajectory of the call; d_out: the results, same layout
     DevBuf<double> d_scaled;            // [B L] T | [B L] coeffs
     DevBuf<double> d_piece;             // [B L N][12]
     DevBuf<double> d_info;              // [B L][TW]
     DevBuf<isdf_host::TRState> d_state; // [B]
     DevBuf<double> d_aux;               // [B][ST_WORDS]
     DevBuf<double> d_res;               // [B][RES_WORDS]
-    std::vector<double> h_res;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~TrajRetimeState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 namespace {
@@ -112,14 +107,8 @@ __global__ __launch_bounds__(64) void tr_pick_kernel(int N, int L, int round, in
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
-
-int state_of(isdf_ctx *c, TrajRetimeState **out) {
-    if (!c->trt) c->trt = new TrajRetimeState();
-    *out = c->trt;
-    for (auto &e : c->trt->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    return ISDF_OK;
-}
+using namespace traj_call;
+constexpr const char *BAD_DURATION = "trajectory retime: a duration is not positive and finite";
 
 // what can be said without a ctx
 int check_args(isdf_ctx *c, long long B, int N, const void *T, const void *coeffs, const isdf_traj_retime_params *p, const void *T_out,
@@ -134,29 +123,23 @@ int check_args(isdf_ctx *c, long long B, int N, const void *T, const void *coeff
         return fail(c, ISDF_ERR_INVALID_ARG, "trajectory retime: B x ladder x N above ISDF_TRAJ_RETIME_MAX_PIECES");
     return ISDF_OK;
 }
-int check_durations(isdf_ctx *c, long long n, const double *T) {
-    for (long long q = 0; q < n; q++)
-        if (!(T[q] > 0.0) || !std::isfinite(T[q])) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory retime: a duration is not positive and finite");
-    return ISDF_OK;
-}
-int check_ctx(isdf_ctx *c, const isdf_traj_retime_params &P) {
-    if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "trajectory retime: null ctx");
-    if (!c->peers.empty() || c->is_peer || c->rccl_comm) return fail(c, ISDF_ERR_UNSUPPORTED, "trajectory retime on a multi-device ctx");
-    if (P.check) { const int rc = isdf_traj_check_ready(c); if (rc) return rc; }
+int ctx_gate(isdf_ctx *c, const isdf_traj_retime_params &P) {
+    ISDF_TRY(check_ctx(c, "trajectory retime: null ctx", "trajectory retime on a multi-device ctx"));
+    if (P.check) ISDF_TRY(isdf_traj_check_ready(c));
     return ISDF_OK;
 }
 
-// the search over device arrays: everything queued on st, then ONE synchronisation.  d_T_out / d_C_out: the B results
-int retime_run(isdf_ctx *c, TrajRetimeState *k, int B, int N, const double *d_T, const double *d_C, const isdf_traj_retime_params &P,
-               double *d_T_out, double *d_C_out, double *h_T_out, double *h_C_out, isdf_traj_retime_info *infos, hipStream_t st) {
+// the search over device arrays: everything queued on st, then ONE synchronisation
+int retime_run(isdf_ctx *c, TrajRetimeState *k, int B, int N, const double *d_T, const double *d_C, const isdf_traj_retime_params &P, const Out &out,
+               isdf_traj_retime_info *infos, hipStream_t st) {
     const int L = P.ladder, R = P.rounds;
-    const size_t cand = (size_t)B * L, nT = cand * N;
-    { const int rc = k->d_scaled.reserve(c, 19 * nT); if (rc) return rc; }
-    { const int rc = k->d_piece.reserve(c, 12 * nT); if (rc) return rc; }
-    { const int rc = k->d_info.reserve(c, cand * TW); if (rc) return rc; }
-    { const int rc = k->d_state.reserve(c, (size_t)B); if (rc) return rc; }
-    { const int rc = k->d_aux.reserve(c, (size_t)B * ST_WORDS); if (rc) return rc; }
-    { const int rc = k->d_res.reserve(c, (size_t)B * RES_WORDS); if (rc) return rc; }
+    const size_t cand = (size_t)B * L, nT = cand * N, n_res = (size_t)B * RES_WORDS, n_aux = (size_t)B * ST_WORDS;
+    ISDF_TRY(k->d_scaled.reserve(c, 19 * nT));
+    ISDF_TRY(k->d_piece.reserve(c, 12 * nT));
+    ISDF_TRY(k->d_info.reserve(c, cand * TW));
+    ISDF_TRY(k->d_state.reserve(c, (size_t)B));
+    ISDF_TRY(k->d_aux.reserve(c, n_aux));
+    ISDF_TRY(k->d_res.reserve(c, n_res));
     double *sT = k->d_scaled, *sC = k->d_scaled + nT;
     TRLimits lim;
     isdf_host::tl_limits(&P.limits, c->cfg, lim.limit);
@@ -166,28 +149,18 @@ int retime_run(isdf_ctx *c, TrajRetimeState *k, int B, int N, const double *d_T,
     for (int round = 0; round < R; round++) {
         hipLaunchKernelGGL(tr_scale_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, B, N, L, d_T, d_C,
                            (const TRState *)k->d_state.get(), sT, sC);
-        { const int rc = isdf_traj_limits_launch(c, (int)cand, N, sT, sC, &P.limits, k->d_piece, k->d_info, st); if (rc) return rc; }
+        ISDF_TRY(isdf_traj_limits_launch(c, (int)cand, N, sT, sC, &P.limits, k->d_piece, k->d_info, st));
         hipLaunchKernelGGL(tr_pick_kernel, dim3((unsigned)B), dim3(64), 0, st, N, L, round, R, lim, (const double *)k->d_info.get(),
-                           (const double *)sT, (const double *)sC, k->d_state.get(), (const double *)k->d_aux.get(), d_T_out, d_C_out, k->d_res.get());
+                           (const double *)sT, (const double *)sC, k->d_state.get(), (const double *)k->d_aux.get(), out.d_T, out.d_C, k->d_res.get());
     }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(k->ev[1], st));
-    if (k->h_res.size() < (size_t)B * (RES_WORDS + ST_WORDS)) k->h_res.resize((size_t)B * (RES_WORDS + ST_WORDS));
-    double *h_aux = k->h_res.data() + (size_t)B * RES_WORDS;
-    HIPCHK(c, hipMemcpyAsync(k->h_res.data(), k->d_res, (size_t)B * RES_WORDS * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(h_aux, k->d_aux, (size_t)B * ST_WORDS * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (h_T_out) {
-        HIPCHK(c, hipMemcpyAsync(h_T_out, d_T_out, (size_t)B * N * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(h_C_out, d_C_out, (size_t)B * 18 * N * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(c, hipStreamSynchronize(st));
-    for (int b = 0; b < B; b++)
-        if (h_aux[(size_t)b * ST_WORDS + 1] != 0.0) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory retime: a duration is not positive and finite");
+    double *h_res = k->host_words(n_res + n_aux), *h_aux = h_res + n_res;
     float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    ISDF_TRY(finish(c, k, st, {{h_res, k->d_res, n_res}, {h_aux, k->d_aux, n_aux}, {out.h_T, out.d_T, (size_t)B * N}, {out.h_C, out.d_C, (size_t)B * 18 * N}}, &ms));
+    for (int b = 0; b < B; b++)
+        if (h_aux[(size_t)b * ST_WORDS + 1] != 0.0) return fail(c, ISDF_ERR_INVALID_ARG, BAD_DURATION);
     if (infos) for (int b = 0; b < B; b++) {
         isdf_traj_retime_info *info = infos + b;
-        const double *w = k->h_res.data() + (size_t)b * RES_WORDS;
+        const double *w = h_res + (size_t)b * RES_WORDS;
         std::memset(info, 0, sizeof(*info));
         info->scale = w[0]; info->scale_below = w[1]; info->status = (int32_t)w[2]; info->rounds = (int32_t)w[3];
         info->candidates = L * info->rounds; info->nonmonotone = (int32_t)w[4]; info->binding = (int32_t)w[5];
@@ -196,6 +169,19 @@ int retime_run(isdf_ctx *c, TrajRetimeState *k, int B, int N, const double *d_T,
         info->device_ms = ms;
     }
     return ISDF_OK;
+}
+
+// the host-array forms: inputs up, the search, results down
+int retime_host_arrays(isdf_ctx *c, int B, int N, const double *T, const double *coeffs, const isdf_traj_retime_params &P, double *T_out,
+                       double *coeffs_out, isdf_traj_retime_info *infos) {
+    TrajRetimeState *k;
+    ISDF_TRY(state_of(c, c->trt, &k));
+    hipStream_t st = c->stream;
+    const size_t nT = (size_t)B * N;
+    ISDF_TRY(k->d_out.reserve(c, 19 * nT));
+    ISDF_TRY(upload(c, k->d_in, nT, T, coeffs, st));
+    ISDF_TRY(retime_run(c, k, B, N, k->d_in, k->d_in + nT, P, Out{k->d_out, k->d_out + nT, T_out, coeffs_out}, infos, st));
+    return P.check ? post_check(c, N, k->d_out, k->d_out + nT, infos, st) : ISDF_OK;
 }
 
 }  // namespace
@@ -217,73 +203,37 @@ extern "C" void isdf_traj_retime_sizes(int out[2]) {
 
 extern "C" int isdf_traj_retime_batch(isdf_ctx *c, int B, int N, const double *T, const double *coeffs, const isdf_traj_retime_params *p,
                                       double *T_out, double *coeffs_out, isdf_traj_retime_info *infos_out) {
-    { const int rc = check_args(c, B, N, T, coeffs, p, T_out, coeffs_out, true); if (rc) return rc; }
-    { const int rc = check_durations(c, (long long)B * N, T); if (rc) return rc; }
-    isdf_traj_retime_params P;
-    if (p) P = *p; else isdf_host::tr_params_default(&P);
-    { const int rc = check_ctx(c, P); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
-    TrajRetimeState *k;
-    { const int rc = state_of(c, &k); if (rc) return rc; }
-    hipStream_t st = c->stream;
-    const size_t nT = (size_t)B * N;
-    { const int rc = k->d_in.reserve(c, 19 * nT); if (rc) return rc; }
-    { const int rc = k->d_out.reserve(c, 19 * nT); if (rc) return rc; }
-    HIPCHK(c, hipMemcpyAsync(k->d_in, T, nT * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(k->d_in + nT, coeffs, 18 * nT * sizeof(double), hipMemcpyHostToDevice, st));
-    return retime_run(c, k, B, N, k->d_in, k->d_in + nT, P, k->d_out, k->d_out + nT, T_out, coeffs_out, infos_out, st);
+    ISDF_TRY(check_args(c, B, N, T, coeffs, p, T_out, coeffs_out, true));
+    ISDF_TRY(check_durations(c, (long long)B * N, T, BAD_DURATION));
+    const isdf_traj_retime_params P = resolve(p, isdf_host::tr_params_default);
+    ISDF_TRY(ctx_gate(c, P));
+    return retime_host_arrays(c, B, N, T, coeffs, P, T_out, coeffs_out, infos_out);
 }
 
 extern "C" int isdf_traj_retime(isdf_ctx *c, int N, const double *T, const double *coeffs, const isdf_traj_retime_params *p,
                                 double *T_out, double *coeffs_out, isdf_traj_retime_info *info_out) {
-    { const int rc = check_args(c, 1, N, T, coeffs, p, T_out, coeffs_out, false); if (rc) return rc; }
-    { const int rc = check_durations(c, N, T); if (rc) return rc; }
-    isdf_traj_retime_params P;
-    if (p) P = *p; else isdf_host::tr_params_default(&P);
-    { const int rc = check_ctx(c, P); if (rc) return rc; }
+    ISDF_TRY(check_args(c, 1, N, T, coeffs, p, T_out, coeffs_out, false));
+    ISDF_TRY(check_durations(c, N, T, BAD_DURATION));
+    const isdf_traj_retime_params P = resolve(p, isdf_host::tr_params_default);
+    ISDF_TRY(ctx_gate(c, P));
     if (P.check) {                                  // the slowest candidate must still be a trajectory the check takes
         std::vector<double> slow((size_t)N);
         for (int i = 0; i < N; i++) slow[(size_t)i] = isdf_host::tr_scale_elem(N, i, T[i], P.s_hi);
-        const int rc = swept_check_traj(c, N, slow.data());
-        if (rc) return rc;
+        ISDF_TRY(swept_check_traj(c, N, slow.data()));
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    TrajRetimeState *k;
-    { const int rc = state_of(c, &k); if (rc) return rc; }
-    hipStream_t st = c->stream;
-    const size_t nT = (size_t)N;
-    { const int rc = k->d_in.reserve(c, 19 * nT); if (rc) return rc; }
-    { const int rc = k->d_out.reserve(c, 19 * nT); if (rc) return rc; }
-    HIPCHK(c, hipMemcpyAsync(k->d_in, T, nT * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(k->d_in + nT, coeffs, 18 * nT * sizeof(double), hipMemcpyHostToDevice, st));
-    { const int rc = retime_run(c, k, 1, N, k->d_in, k->d_in + nT, P, k->d_out, k->d_out + nT, T_out, coeffs_out, info_out, st); if (rc) return rc; }
-    if (P.check) {
-        isdf_traj_check_info chk;
-        const int rc = isdf_traj_check_device(c, N, k->d_out, k->d_out + nT, nullptr, &chk, nullptr, st);
-        if (rc) return rc;
-        if (info_out) { info_out->check = chk; info_out->checked = 1; }
-    }
-    return ISDF_OK;
+    return retime_host_arrays(c, 1, N, T, coeffs, P, T_out, coeffs_out, info_out);
 }
 
 extern "C" int isdf_traj_retime_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const isdf_traj_retime_params *p,
                                        double *d_T_out, double *d_coeffs_out, isdf_traj_retime_info *info_out, void *stream) {
-    { const int rc = check_args(c, 1, N, d_T, d_coeffs, p, d_T_out, d_coeffs_out, false); if (rc) return rc; }
-    isdf_traj_retime_params P;
-    if (p) P = *p; else isdf_host::tr_params_default(&P);
-    { const int rc = check_ctx(c, P); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(check_args(c, 1, N, d_T, d_coeffs, p, d_T_out, d_coeffs_out, false));
+    const isdf_traj_retime_params P = resolve(p, isdf_host::tr_params_default);
+    ISDF_TRY(ctx_gate(c, P));
     TrajRetimeState *k;
-    { const int rc = state_of(c, &k); if (rc) return rc; }
+    ISDF_TRY(state_of(c, c->trt, &k));
     hipStream_t st = (hipStream_t)stream;
-    { const int rc = retime_run(c, k, 1, N, d_T, d_coeffs, P, d_T_out, d_coeffs_out, nullptr, nullptr, info_out, st); if (rc) return rc; }
-    if (P.check) {
-        isdf_traj_check_info chk;
-        const int rc = isdf_traj_check_device(c, N, d_T_out, d_coeffs_out, nullptr, &chk, nullptr, st);
-        if (rc) return rc;
-        if (info_out) { info_out->check = chk; info_out->checked = 1; }
-    }
-    return ISDF_OK;
+    ISDF_TRY(retime_run(c, k, 1, N, d_T, d_coeffs, P, Out{d_T_out, d_coeffs_out, nullptr, nullptr}, info_out, st));
+    return P.check ? post_check(c, N, d_T_out, d_coeffs_out, info_out, st) : ISDF_OK;
 }
 
 extern "C" int isdf_traj_retime_host(const isdf_config *cfg, int N, const double *T, const double *coeffs, const isdf_traj_retime_params *p,

@@ -184,7 +184,7 @@ int fold_full(isdf_ctx *c, TrajCheckState *k, unsigned n_new) {
     const isdf_traj_check_info old = k->w.info;
     const long long folded = k->w.last.updates_folded;
     isdf_traj_check_info now;
-    { const int rc = traj_check_rerun_kept(c, &now); if (rc) return rc; }
+    ISDF_TRY(traj_check_rerun_kept(c, &now));
     isdf_traj_watch_info &L = k->w.last;            // (the re-check armed the watch again and cleared this)
     L.updates_folded = folded + 1;
     L.path = 2;

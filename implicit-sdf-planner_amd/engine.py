@@ -117,6 +117,20 @@ def _traj_arrays(T, coeffs_colmajor):
     return T, Cc
 
 
+def _traj_batch_arrays(T, coeffs_colmajor=None):
+    """B trajectories of N pieces each as T (B x N), Cc (B x 18 N; None when no coefficients are given), B, N."""
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    if T.ndim != 2:
+        raise ValueError("T must be B x N")
+    B, N = T.shape
+    if coeffs_colmajor is None:
+        return T, None, B, N
+    Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(B, -1)
+    if Cc.shape[1] != 18 * N:
+        raise ValueError(f"coefficients: {Cc.shape[1]} doubles per trajectory for {N} pieces (18 per piece)")
+    return T, Cc, B, N
+
+
 def traj_limits_host(cfg, T, coeffs_colmajor, lib=None, **params):
     """isdf_traj_limits_host: the dynamic-limits report in plain host code (no ctx, no device)."""
     lib = lib or capi.load_library()
@@ -1614,13 +1628,7 @@ class Engine:
 
     def traj_limits_batch(self, T, coeffs_colmajor, **params):
         """B trajectories of N pieces each (T: B x N, coefficients: B x 18 N) in one call: a list of B dicts."""
-        T = np.ascontiguousarray(T, dtype=np.float64)
-        if T.ndim != 2:
-            raise ValueError("T must be B x N")
-        B, N = T.shape
-        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(B, -1)
-        if Cc.shape[1] != 18 * N:
-            raise ValueError(f"coefficients: {Cc.shape[1]} doubles per trajectory for {N} pieces (18 per piece)")
+        T, Cc, B, N = _traj_batch_arrays(T, coeffs_colmajor)
         p = traj_limits_params(self.lib, **params)
         infos = (capi.IsdfTrajLimitsInfo * B)()
         piece = np.zeros((B, N, 12))
@@ -1648,6 +1656,10 @@ class Engine:
                                                      C.c_void_p(stream)))
 
     # ---- retiming a trajectory to its dynamic limits (isdf_traj_retime*)
+    def _note_check(self, info):        # a result that went through the clearance check left that check's kept rows in the ctx
+        if info.checked:
+            self._traj_check_rows = int(info.check.n_below_margin)
+
     def traj_retime(self, T, coeffs_colmajor, **params):
         """The smallest uniform slow-down factor of a ladder search at which the limits report is feasible, and the trajectory scaled by
         it: the dict of traj_retime_report.  params: s_lo, s_hi, ladder, rounds, check (True: the result goes through the clearance
@@ -1657,19 +1669,12 @@ class Engine:
         info = capi.IsdfTrajRetimeInfo()
         To, Co = np.zeros_like(T), np.zeros_like(Cc)
         self._check(self.lib.isdf_traj_retime(self.h, T.size, _p(T), _p(Cc), C.byref(p), _p(To), _p(Co), C.byref(info)))
-        if info.checked:
-            self._traj_check_rows = int(info.check.n_below_margin)
+        self._note_check(info)
         return traj_retime_report(info, To, Co)
 
     def traj_retime_batch(self, T, coeffs_colmajor, **params):
         """B trajectories of N pieces each (T: B x N, coefficients: B x 18 N), each with its own brackets and status: a list of B dicts."""
-        T = np.ascontiguousarray(T, dtype=np.float64)
-        if T.ndim != 2:
-            raise ValueError("T must be B x N")
-        B, N = T.shape
-        Cc = np.ascontiguousarray(coeffs_colmajor, dtype=np.float64).reshape(B, -1)
-        if Cc.shape[1] != 18 * N:
-            raise ValueError(f"coefficients: {Cc.shape[1]} doubles per trajectory for {N} pieces (18 per piece)")
+        T, Cc, B, N = _traj_batch_arrays(T, coeffs_colmajor)
         p = traj_retime_params(self.lib, **params)
         infos = (capi.IsdfTrajRetimeInfo * B)()
         To, Co = np.zeros_like(T), np.zeros_like(Cc)
@@ -1682,8 +1687,7 @@ class Engine:
         info = capi.IsdfTrajRetimeInfo()
         self._check(self.lib.isdf_traj_retime_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), C.byref(p), C.c_void_p(d_T_out),
                                                      C.c_void_p(d_coeffs_out), C.byref(info), C.c_void_p(stream)))
-        if info.checked:
-            self._traj_check_rows = int(info.check.n_below_margin)
+        self._note_check(info)
         return traj_retime_report(info)
 
     # ---- re-allocating piece durations to the dynamic limits (isdf_traj_realloc*)
@@ -1696,16 +1700,12 @@ class Engine:
         info = capi.IsdfTrajReallocInfo()
         To, Co = np.zeros_like(T), np.zeros(18 * T.size)
         self._check(self.lib.isdf_traj_realloc(self.h, T.size, _p(h), _p(t), _p(q), _p(T), C.byref(p), _p(To), _p(Co), C.byref(info)))
-        if info.checked:
-            self._traj_check_rows = int(info.check.n_below_margin)
+        self._note_check(info)
         return traj_realloc_report(info, To, Co)
 
     def traj_realloc_batch(self, heads, tails, Q, T, **params):
         """B trajectories of N pieces each (heads, tails: B x 9; Q: B x (N - 1) x 3; T: B x N), each with its own status: a list of B dicts."""
-        T = np.ascontiguousarray(T, dtype=np.float64)
-        if T.ndim != 2:
-            raise ValueError("T must be B x N")
-        B, N = T.shape
+        T, _, B, N = _traj_batch_arrays(T)
         h = np.ascontiguousarray(heads, dtype=np.float64).reshape(B, 9)
         t = np.ascontiguousarray(tails, dtype=np.float64).reshape(B, 9)
         q = np.ascontiguousarray(Q, dtype=np.float64).reshape(B, 3 * (N - 1)) if N > 1 else np.zeros((B, 3))
@@ -1722,8 +1722,7 @@ class Engine:
         info = capi.IsdfTrajReallocInfo()
         self._check(self.lib.isdf_traj_realloc_device(self.h, N, C.c_void_p(d_head), C.c_void_p(d_tail), C.c_void_p(d_Q), C.c_void_p(d_T), C.byref(p),
                                                       C.c_void_p(d_T_out), C.c_void_p(d_coeffs_out), C.byref(info), C.c_void_p(stream)))
-        if info.checked:
-            self._traj_check_rows = int(info.check.n_below_margin)
+        self._note_check(info)
         return traj_realloc_report(info)
 
     def points_merge_check(self, below=None):
