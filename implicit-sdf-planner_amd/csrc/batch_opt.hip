@@ -170,7 +170,7 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
     constexpr int N_SLOTS = 4;          // rounds in flight at most (slots_used of them are used)
     struct Slot {
         PinBuf<double> h_pin; DevBuf<double> d_buf;
-        std::vector<int> active; int group = -1; hipStream_t stream = nullptr; hipEvent_t done = nullptr, sweep_done = nullptr; bool busy = false;
+        std::vector<int> active; int group = -1; hipStream_t stream = nullptr; DevEvents<1> done, sweep_done; bool busy = false;
     } slots[N_SLOTS];
     const size_t in_all = (size_t)n_traj * b.in_per, out_all = (size_t)n_traj * b.ostride;
     // device MINCO: further device regions behind [T | coeffs | sweep out] - x + ends of the round (compacted), junction states,
@@ -183,7 +183,7 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
     auto release = [&] {
         for (Slot &q : slots) {
             q.h_pin.release(); q.d_buf.release();
-            if (q.done) (void)hipEventDestroy(q.done); if (q.sweep_done) (void)hipEventDestroy(q.sweep_done);
+            q.done.release(); q.sweep_done.release();
             if (q.stream) (void)hipStreamDestroy(q.stream);
         }
     };
@@ -191,8 +191,7 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
         // pinned: [T | coeffs of the round | sweep out | overflow word]; device: [T | coeffs | sweep out]
         if (q.h_pin.reserve(c, word_at + 1) != ISDF_OK || q.d_buf.alloc(dev_all) != hipSuccess ||
             hipStreamCreate(&q.stream) != hipSuccess ||
-            hipEventCreateWithFlags(&q.done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&q.sweep_done, hipEventDisableTiming) != hipSuccess) { release(); return isdf_fail(c, ISDF_ERR_HIP, "batch buffers: allocation failed"); }
+            q.done.ready(c, hipEventDisableTiming) != ISDF_OK || q.sweep_done.ready(c, hipEventDisableTiming) != ISDF_OK) { release(); return isdf_fail(c, ISDF_ERR_HIP, "batch buffers: allocation failed"); }
     }
     { int rc0 = isdf_reserve_sweep_buffers(c, (long long)n_traj * N); if (rc0) { release(); return rc0; } }
     (void)hipDeviceSynchronize();
@@ -244,13 +243,13 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
             if (rc == ISDF_OK) isdf::launch_cb_pre(P, q.stream);
             if (rc == ISDF_OK && last_sweep && hipStreamWaitEvent(q.stream, last_sweep, 0) != hipSuccess) rc = ISDF_ERR_HIP;
             if (rc == ISDF_OK) rc = isdf_eval_device(c, na, N, P.T, P.coeffs, q.d_buf + in_all, nullptr, q.stream);
-            if (rc == ISDF_OK && hipEventRecord(q.sweep_done, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
-            last_sweep = q.sweep_done;
+            if (rc == ISDF_OK && hipEventRecord(q.sweep_done[0], q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
+            last_sweep = q.sweep_done[0];
             if (rc == ISDF_OK) isdf::launch_cb_post(P, q.stream);
             if (rc == ISDF_OK && hipGetLastError() != hipSuccess) rc = ISDF_ERR_HIP;
             if (rc == ISDF_OK && hipMemcpyAsync(q.h_pin + pin_res, q.d_buf + off_res, (size_t)na * b.rs * sizeof(double), hipMemcpyDeviceToHost, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
             if (rc == ISDF_OK && hipMemcpyAsync(q.h_pin + word_at, c->d_stats + 4, sizeof(double), hipMemcpyDeviceToHost, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
-            if (rc == ISDF_OK && hipEventRecord(q.done, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
+            if (rc == ISDF_OK && hipEventRecord(q.done[0], q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
             q.busy = true;
             b.rounds_run++;
             b.evals_run += na;
@@ -266,17 +265,17 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
         if (rc == ISDF_OK && hipMemcpyAsync(q.d_buf, q.h_pin, (size_t)na * b.in_per * sizeof(double), hipMemcpyHostToDevice, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
         if (rc == ISDF_OK && last_sweep && hipStreamWaitEvent(q.stream, last_sweep, 0) != hipSuccess) rc = ISDF_ERR_HIP;
         if (rc == ISDF_OK) rc = isdf_eval_device(c, na, N, dT, dC, dO, nullptr, q.stream);
-        if (rc == ISDF_OK && hipEventRecord(q.sweep_done, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
-        last_sweep = q.sweep_done;
+        if (rc == ISDF_OK && hipEventRecord(q.sweep_done[0], q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
+        last_sweep = q.sweep_done[0];
         if (rc == ISDF_OK && hipMemcpyAsync(q.h_pin + in_all, dO, (size_t)na * b.ostride * sizeof(double), hipMemcpyDeviceToHost, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
         if (rc == ISDF_OK && hipMemcpyAsync(q.h_pin + word_at, c->d_stats + 4, sizeof(double), hipMemcpyDeviceToHost, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
-        if (rc == ISDF_OK && hipEventRecord(q.done, q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
+        if (rc == ISDF_OK && hipEventRecord(q.done[0], q.stream) != hipSuccess) rc = ISDF_ERR_HIP;
         q.busy = true;
         b.rounds_run++;
         b.evals_run += na;
     };
     auto deliver = [&](Slot &q) {             // waits for the round, hands the results to its trajectories
-        if (rc == ISDF_OK && hipEventSynchronize(q.done) != hipSuccess) rc = ISDF_ERR_HIP;
+        if (rc == ISDF_OK && hipEventSynchronize(q.done[0]) != hipSuccess) rc = ISDF_ERR_HIP;
         const int na = (int)q.active.size();
         if (rc == ISDF_OK) {
             unsigned long long ovf = 0;
@@ -318,7 +317,7 @@ extern "C" int isdf_optimize_lbfgs_batch(isdf_ctx *c, int n_traj, int N, const d
                 if (b.n_submitted > 0 && b.n_submitted >= std::min(need, free_live)) { take = true; break; }
                 }
                 if (n_busy > 0) {
-                    if (rc != ISDF_OK || hipEventQuery(slots[tail_slot].done) != hipErrorNotReady) break;   // finished (or failed): deliver it - that is where new work comes from
+                    if (rc != ISDF_OK || hipEventQuery(slots[tail_slot].done[0]) != hipErrorNotReady) break;   // finished (or failed): deliver it - that is where new work comes from
                     b.cv_coord.wait_for(lk, std::chrono::microseconds(20));
                     continue;
                 }

@@ -16,7 +16,6 @@
 #include "map_change.hpp"
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 namespace isdf {
 
@@ -159,12 +158,9 @@ struct DepthCamState {
     isdf::DevBuf<void> d_in;                    // a cloud, or a depth image
     isdf::DevBuf<int32_t> d_image;              // the rendered image
     isdf::DevBuf<void> d_rays;                  // end points | hit bytes
-    isdf::DevBuf<isdf::DcRecord> d_rec; isdf::PinBuf<isdf::DcRecord> h_rec;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~DepthCamState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    isdf::RecPair<isdf::DcRecord> rec;
+    isdf::DevEvents<2> ev;
 };
-
-void isdf_depth_cam_release_all(isdf_ctx *c) { delete c->dcm; c->dcm = nullptr; }
 
 using namespace isdf;
 
@@ -228,12 +224,9 @@ int rays_setup(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2worl
 size_t pixel_bytes(int format) { return format == ISDF_DEPTH_U16_MM ? 2 : 4; }
 
 int cam_state(isdf_ctx *c, DepthCamState **out) {
-    if (!c->dcm) { c->dcm = new (std::nothrow) DepthCamState(); if (!c->dcm) return isdf_fail(c, ISDF_ERR_HIP, "out of host memory"); }
-    for (hipEvent_t &e : c->dcm->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (int rc = c->dcm->d_rec.reserve(c, 1)) return rc;
-    if (int rc = c->dcm->h_rec.reserve(c, 1)) return rc;
-    *out = c->dcm;
-    return ISDF_OK;
+    ISDF_TRY(c->dcm.make(c, out));
+    ISDF_TRY((*out)->ev.ready(c));
+    return (*out)->rec.ready(c);
 }
 
 int single_device(isdf_ctx *c, const char *what) {
@@ -254,11 +247,11 @@ int render_check(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2wo
 
 int render_run(isdf_ctx *c, DepthCamState *S, const DcCam &K, const isdf_depth_render_params &P, const float *d_xyz, long long n, int32_t *d_image, bool count, hipStream_t st) {
     if (count) {
-        HIPCHK(c, hipMemsetAsync(S->d_rec, 0, sizeof(DcRecord), st));
+        HIPCHK(c, S->rec.zero(st));
         HIPCHK(c, hipEventRecord(S->ev[0], st));
     }
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)d_image, DC_EMPTY, (size_t)K.width * K.height, st));
-    DcRecord *const rec = count ? S->d_rec.get() : nullptr;
+    DcRecord *const rec = count ? S->rec.dev() : nullptr;
     if (P.source == ISDF_DEPTH_SOURCE_MAP) {
         const DevGrid &G = c->grid;
         DcMap M;
@@ -277,22 +270,16 @@ int render_run(isdf_ctx *c, DepthCamState *S, const DcCam &K, const isdf_depth_r
     }
     if (!count) return ISDF_OK;
     HIPCHK(c, hipEventRecord(S->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(S->h_rec.get(), S->d_rec, sizeof(DcRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, S->rec.fetch(st));
     return ISDF_OK;
 }
 
-double state_ms(const DepthCamState *S) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, S->ev[0], S->ev[1]) == hipSuccess ? ms : 0.0;
-}
-
 void render_info(const DepthCamState *S, isdf_depth_render_info *out) {
-    DcRecord R;
-    std::memcpy(&R, S->h_rec.get(), sizeof(R));
+    const DcRecord R = S->rec.host();
     isdf_depth_render_info info{};
     info.n_points = (int64_t)R.v[0]; info.n_behind = (int64_t)R.v[1]; info.n_outside = (int64_t)R.v[2]; info.n_near = (int64_t)R.v[3];
     info.n_splat_pixels = (int64_t)R.v[4]; info.n_pixels_set = (int64_t)R.v[5];
-    info.render_ms = state_ms(S);
+    info.render_ms = S->ev.ms(0, 1);
     *out = info;
 }
 
@@ -308,26 +295,25 @@ int rays_check(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2worl
 
 int rays_run(isdf_ctx *c, DepthCamState *S, const DcRays &Q, const void *d_image, float *d_ends, uint8_t *d_hit, bool count, hipStream_t st) {
     if (count) {
-        HIPCHK(c, hipMemsetAsync(S->d_rec, 0, sizeof(DcRecord), st));
+        HIPCHK(c, S->rec.zero(st));
         HIPCHK(c, hipEventRecord(S->ev[0], st));
     }
     const long long n = (long long)Q.nu * Q.nv;
     const unsigned blocks = (unsigned)std::min<long long>((n + DC_BLOCK - 1) / DC_BLOCK, 8192);
-    hipLaunchKernelGGL(dc_rays_kernel, dim3(blocks), dim3(DC_BLOCK), 0, st, Q, d_image, d_ends, d_hit, count ? S->d_rec.get() : nullptr);
+    hipLaunchKernelGGL(dc_rays_kernel, dim3(blocks), dim3(DC_BLOCK), 0, st, Q, d_image, d_ends, d_hit, count ? S->rec.dev() : nullptr);
     HIPCHK(c, hipGetLastError());
     if (!count) return ISDF_OK;
     HIPCHK(c, hipEventRecord(S->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(S->h_rec.get(), S->d_rec, sizeof(DcRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, S->rec.fetch(st));
     return ISDF_OK;
 }
 
 void rays_info(const DepthCamState *S, const DcRays &Q, isdf_depth_rays_info *out) {
-    DcRecord R;
-    std::memcpy(&R, S->h_rec.get(), sizeof(R));
+    const DcRecord R = S->rec.host();
     isdf_depth_rays_info info{};
     info.n_pixels = (int64_t)Q.nu * Q.nv;
     info.n_no_return = (int64_t)R.v[1]; info.n_below_min = (int64_t)R.v[2]; info.n_truncated = (int64_t)R.v[3]; info.n_clipped = (int64_t)R.v[4]; info.n_hits = (int64_t)R.v[5];
-    info.rays_ms = state_ms(S);
+    info.rays_ms = S->ev.ms(0, 1);
     *out = info;
 }
 

@@ -1,7 +1,8 @@
 // Owning buffers of the host code (host-only): device memory (DevBuf) and pinned, device-mapped host memory (PinBuf).
 // Both free themselves, neither copies.  As a ctx member a buffer grows only (reserve); as a local it is a scoped temporary
 // that is gone on every return.  Every allocation and every free of the two types goes through mem_take / mem_give, which
-// keep the process-wide count of live bytes behind isdf_debug_live_bytes.
+// keep the process-wide count of live bytes behind isdf_debug_live_bytes.  Events (DevEvents) are owned and counted the same way
+// (event_take / event_give, isdf_debug_live_events); RecPair is a counted call's record: one Rec on the device and its pinned copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -94,5 +95,62 @@ public:
     size_t capacity() const { return cap_; }
     void release() { mem_give(p_, cap_ * sizeof(T), true); p_ = dev_ = nullptr; cap_ = 0; }
     int reserve(isdf_ctx *c, size_t n) { return n <= cap_ ? 0 : grow(c, n); }
+};
+
+inline std::atomic<long long> g_live_events;
+
+inline hipError_t event_take(hipEvent_t *e, unsigned flags) {
+    *e = nullptr;
+    const hipError_t r = hipEventCreateWithFlags(e, flags);
+    if (r != hipSuccess) { *e = nullptr; return r; }
+    g_live_events.fetch_add(1, std::memory_order_relaxed);
+    return hipSuccess;
+}
+inline void event_give(hipEvent_t e) {
+    if (!e) return;
+    (void)hipEventDestroy(e);
+    g_live_events.fetch_sub(1, std::memory_order_relaxed);
+}
+
+// N events: a ctx member keeps them from its first ready() on, a local is gone on every return.
+template <int N> class DevEvents {
+    hipEvent_t e_[N] = {};
+public:
+    DevEvents() = default;
+    DevEvents(const DevEvents &) = delete;
+    DevEvents &operator=(const DevEvents &) = delete;
+    DevEvents(DevEvents &&o) noexcept { for (int k = 0; k < N; k++) std::swap(e_[k], o.e_[k]); }
+    ~DevEvents() { release(); }
+    hipEvent_t operator[](int k) const { return e_[k]; }
+    const hipEvent_t *get() const { return e_; }
+    void release() { for (hipEvent_t &e : e_) { event_give(e); e = nullptr; } }
+    // creates the missing ones
+    int ready(isdf_ctx *c, unsigned flags = hipEventDefault) {
+        for (hipEvent_t &e : e_)
+            if (!e) { const hipError_t r = event_take(&e, flags); if (r != hipSuccess) return isdf_hip_fail(c, "hipEventCreate", r); }
+        return 0;
+    }
+    // device time from event a to event b; 0.0 where HIP refuses (an event never recorded)
+    double ms(int a, int b) const {
+        float v = 0.f;
+        return hipEventElapsedTime(&v, e_[a], e_[b]) == hipSuccess ? (double)v : 0.0;
+    }
+};
+
+// A counted call's record (n Recs where its length depends on the call).  The call empties it on its stream (zero: every byte 0; put:
+// this value, through the pinned copy), its kernels count into dev(), fetch queues the copy back, and after the call's synchronisation
+// host() is the record as the kernels left it.
+template <typename Rec> class RecPair {
+    DevBuf<Rec> d_;
+    PinBuf<Rec> h_;
+    size_t n_ = 1;
+public:
+    int ready(isdf_ctx *c, size_t n = 1) { n_ = n; const int rc = d_.reserve(c, n); return rc ? rc : h_.reserve(c, n); }
+    void release() { d_.release(); h_.release(); }
+    Rec *dev() const { return d_; }
+    Rec &host() const { return *h_.get(); }
+    hipError_t zero(hipStream_t st) { return hipMemsetAsync(d_, 0, n_ * sizeof(Rec), st); }
+    hipError_t put(const Rec &v, hipStream_t st) { host() = v; return hipMemcpyAsync(d_, h_.get(), sizeof(Rec), hipMemcpyHostToDevice, st); }
+    hipError_t fetch(hipStream_t st) { return hipMemcpyAsync(h_.get(), d_, n_ * sizeof(Rec), hipMemcpyDeviceToHost, st); }
 };
 }  // namespace isdf

@@ -323,18 +323,16 @@ extern "C" int isdf_frontend_cspace(isdf_ctx *c, uint32_t *free_mask_out, double
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)F.X * F.Y * F.Z;
     if (!c->fe.d_cspace) HIPCHK(c, c->fe.d_cspace.alloc(n * nw));
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
+    DevEvents<2> ev;
+    ISDF_TRY(ev.ready(c));
     const long long n_wv = (long long)F.X * F.Y * ((F.Z + 63) >> 6);
-    hipExtLaunchKernelGGL(fe_cspace_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, c->stream, e0, e1, 0, F, c->d_occ.get(), c->fe.d_bits.get(),
+    hipExtLaunchKernelGGL(fe_cspace_kernel, dim3((unsigned)((n_wv + 3) / 4)), dim3(256), 0, c->stream, ev[0], ev[1], 0, F, c->d_occ.get(), c->fe.d_bits.get(),
                           (const FeRow *)c->fe.d_row_list.get(), c->fe.d_row_ptr.get(), (uint4 *)c->fe.d_cspace.get());
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && free_mask_out) e = hipMemcpyAsync(free_mask_out, c->fe.d_cspace, n * nw * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (free_mask_out) HIPCHK(c, hipMemcpyAsync(free_mask_out, c->fe.d_cspace, n * nw * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIPCHK(c, e);
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
     if (kernel_ms_out) *kernel_ms_out = ms;
     return ISDF_OK;
 }

@@ -95,4 +95,4 @@ int isdf_field_change_end(isdf_ctx *c, isdf::FfChange dir, const int lo[3], cons
 // phase's rounds, then the opening direction over the box lo .. hi (null: the whole grid).  ev: four events, [0] for ..._begin.
 bool isdf_field_shift_wanted(const isdf_ctx *c, const int32_t s[3]);
 int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start);
-int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], hipEvent_t ev[4]);
+int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], const hipEvent_t ev[4]);

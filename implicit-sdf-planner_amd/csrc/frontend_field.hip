@@ -602,7 +602,7 @@ extern "C" int isdf_frontend_field_release(isdf_ctx *c) {
     isdf_ctx::FrontEnd &fe = c->fe;
     (void)hipSetDevice(c->device);
     fe.d_field.release(); fe.d_field_free.release(); fe.d_field_list.release(); fe.d_field_flags.release(); fe.d_field_cnt.release();
-    fe.h_field_cnt.release(); fe.d_field_rep.release(); fe.h_field_rep.release(); fe.d_field_open.release();
+    fe.h_field_cnt.release(); fe.field_rep.release(); fe.d_field_open.release();
     fe.d_field_shift.release(); fe.d_field_free_shift.release();
     fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false;
     return ISDF_OK;
@@ -640,42 +640,31 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     unsigned long long *cnt = fe.d_field_cnt.get();
     volatile unsigned long long *h = fe.h_field_cnt.get();
     hipStream_t st = c->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    long long n_free = 0;
-    FfRounds R;
+    DevEvents<2> ev;
+    ISDF_TRY(ev.ready(c));
     auto fetch = [&]() {                                   // the counters -> host, one synchronisation
         hipError_t r = hipMemcpyAsync((void *)fe.h_field_cnt.get(), cnt, FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
         return r == hipSuccess ? hipStreamSynchronize(st) : r;
     };
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(ff_init_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
-                           fe.d_field_list.get(), cnt);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = fetch();
-    if (e == hipSuccess) {
-        n_free = (long long)h[FF_CNT_FREE];
-        // Jacobi relaxation fixes at least the voxels with one more edge on their shortest path per round: free voxels bound the rounds
-        long long bound = n_free;
-        if (params && params->max_rounds > 0 && params->max_rounds < bound) bound = params->max_rounds;
-        e = ff_run_rounds(fe, D, (long long)h[FF_CNT_ACTIVE], bound, st, R);
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)n_vox, cnt);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = fetch();
+    HIPCHK(c, hipEventRecord(ev[0], st));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
+    hipLaunchKernelGGL(ff_init_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                       fe.d_field_list.get(), cnt);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, fetch());
+    const long long n_free = (long long)h[FF_CNT_FREE];
+    // Jacobi relaxation fixes at least the voxels with one more edge on their shortest path per round: free voxels bound the rounds
+    long long bound = n_free;
+    if (params && params->max_rounds > 0 && params->max_rounds < bound) bound = params->max_rounds;
+    FfRounds R;
+    HIPCHK(c, ff_run_rounds(fe, D, (long long)h[FF_CNT_ACTIVE], bound, st, R));
+    hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)n_vox, cnt);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[1], st));
+    HIPCHK(c, fetch());
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    HIPCHK(c, e);
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
     fe.field_reachable = goal_in && h[FF_CNT_REACHED] > 0;
     fe.field_valid = true;
     fe.field_status = fe.field_reachable ? R.status : 1;
@@ -724,20 +713,19 @@ int isdf_field_change_begin(isdf_ctx *c, FfChange dir, const int lo[3], const in
     const bool closing = dir == FfChange::Closing;
     FfDims D = ff_dims(c);
     const int n_bricks = D.nbx * D.nby * D.nbz;
-    if (fe.d_field_rep.reserve(c, 1) || fe.h_field_rep.reserve(c, 2)) return ISDF_ERR_HIP;
+    ISDF_TRY(fe.field_rep.ready(c));
     // the opened words are sized for the whole grid at once: no box of a later clear grows them
     if (!closing && fe.d_field_open.reserve(c, (size_t)D.X * D.Y * D.zblocks)) return ISDF_ERR_HIP;
     FfBox B;
     const int rc = ff_box(c, dir, lo, hi, B);
     if (rc != ISDF_OK) return rc;
     if (!closing) D.goal = ff_goal_index(c);
-    FfRecord *h = fe.h_field_rep.get(), *rec = fe.d_field_rep.get();          // h: [the record as it starts | as the kernels left it]
-    h[0] = h[1] = ff_record_empty();
+    FfRecord *rec = fe.field_rep.dev();
     unsigned long long *cnt = fe.d_field_cnt.get();
     unsigned *flags = fe.d_field_flags.get();
     const hipStream_t st = c->stream;
     HIPCHK(c, hipEventRecord(ev_start, st));
-    HIPCHK(c, hipMemcpyAsync(rec, h, sizeof(FfRecord), hipMemcpyHostToDevice, st));
+    HIPCHK(c, fe.field_rep.put(ff_record_empty(), st));
     HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
     if (closing) {
@@ -749,7 +737,7 @@ int isdf_field_change_begin(isdf_ctx *c, FfChange dir, const int lo[3], const in
                            flags, fe.d_field_open.get(), rec);
     hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h + 1, rec, sizeof(FfRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, fe.field_rep.fetch(st));
     return ISDF_OK;
 }
 
@@ -759,7 +747,7 @@ int isdf_field_change_end(isdf_ctx *c, FfChange dir, const int lo[3], const int 
     isdf_ctx::FrontEnd &fe = c->fe;
     const bool closing = dir == FfChange::Closing;
     *kept = 0;
-    FfRecord &rec = fe.h_field_rep.get()[1];
+    const FfRecord &rec = fe.field_rep.host();
     if (rec.premise_violated) return ISDF_OK;
     const FfDims D = ff_dims(c);
     FfBox B;
@@ -775,11 +763,11 @@ int isdf_field_change_end(isdf_ctx *c, FfChange dir, const int lo[3], const int 
     // opening: a field without a reachable goal whose goal cell did not open is all +inf and stays so: nothing to relax
     if (closing || reached_before > 0 || rec.goal_opened) HIPCHK(c, ff_run_rounds(fe, D, n_seeded, bound, st, R));
     hipLaunchKernelGGL(ff_count_kernel, dim3(1024), dim3(256), 0, st, fe.d_field.get(), (long long)D.X * D.Y * D.Z, fe.d_field_cnt.get());
-    if (!closing) hipLaunchKernelGGL(ff_reopen_count_kernel, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_field.get(), fe.d_field_open.get(), fe.d_field_rep.get());
+    if (!closing) hipLaunchKernelGGL(ff_reopen_count_kernel, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_field.get(), fe.d_field_open.get(), fe.field_rep.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev_end, st));
     HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), fe.d_field_cnt.get(), FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (!closing) HIPCHK(c, hipMemcpyAsync(&rec, fe.d_field_rep.get(), sizeof(FfRecord), hipMemcpyDeviceToHost, st));
+    if (!closing) HIPCHK(c, fe.field_rep.fetch(st));
     HIPCHK(c, hipStreamSynchronize(st));
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev_start, ev_end));
@@ -843,17 +831,16 @@ int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start)
     D.goal = ff_goal_index(c);
     const int n_bricks = D.nbx * D.nby * D.nbz;
     const size_t n_vox = (size_t)D.X * D.Y * D.Z, n_cols = (size_t)D.X * D.Y * D.zblocks;
-    if (fe.d_field_shift.reserve(c, n_vox) || fe.d_field_free_shift.reserve(c, n_cols) || fe.d_field_rep.reserve(c, 1) || fe.h_field_rep.reserve(c, 2) ||
+    if (fe.d_field_shift.reserve(c, n_vox) || fe.d_field_free_shift.reserve(c, n_cols) || fe.field_rep.ready(c) ||
         fe.d_field_cnt.reserve(c, FF_CNT_WORDS) || fe.h_field_cnt.reserve(c, FF_CNT_WORDS))
         return ISDF_ERR_HIP;
-    FfRecord *h = fe.h_field_rep.get(), *rec = fe.d_field_rep.get();
-    h[0] = h[1] = ff_record_empty();
+    FfRecord *rec = fe.field_rep.dev();
     unsigned long long *cnt = fe.d_field_cnt.get();
     unsigned *flags = fe.d_field_flags.get();
     const FfShift S{s[0], s[1], s[2]};
     const hipStream_t st = c->stream;
     HIPCHK(c, hipEventRecord(ev_start, st));
-    HIPCHK(c, hipMemcpyAsync(rec, h, sizeof(FfRecord), hipMemcpyHostToDevice, st));
+    HIPCHK(c, fe.field_rep.put(ff_record_empty(), st));
     HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
     hipLaunchKernelGGL(ff_shift_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, S, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
@@ -864,7 +851,7 @@ int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start)
     hipLaunchKernelGGL(ff_repair_reset_kernel, dim3((unsigned)n_bricks), dim3(256), 0, st, D, fe.d_field.get(), flags, rec);
     hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h + 1, rec, sizeof(FfRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, fe.field_rep.fetch(st));
     HIPCHK(c, hipMemcpyAsync((void *)fe.h_field_cnt.get(), cnt, FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     return ISDF_OK;
 }
@@ -873,11 +860,11 @@ int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start)
 // of isdf_field_change_begin / _end over the box lo .. hi (null: the whole grid), which leaves the field valid (status 2 when either
 // phase hit the round bound).  ev: [0] recorded by ..._begin, [1] the end of phase 1, [2], [3] around phase 2.  The last reopen's report
 // is not this call's to change: it is put back.
-int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], hipEvent_t ev[4]) {
+int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], const hipEvent_t ev[4]) {
     isdf_ctx::FrontEnd &fe = c->fe;
     FfDims D = ff_dims(c);
     D.goal = ff_goal_index(c);
-    const FfRecord rec = fe.h_field_rep.get()[1];          // (a copy: phase 2 uses the record again)
+    const FfRecord rec = fe.field_rep.host();            // (a copy: phase 2 uses the record again)
     const hipStream_t st = c->stream;
     volatile unsigned long long *h = fe.h_field_cnt.get();
     const long long n_seeded = (long long)h[FF_CNT_ACTIVE], n_free1 = (long long)h[FF_CNT_FREE], n_left = (long long)h[FF_CNT_LEFT];

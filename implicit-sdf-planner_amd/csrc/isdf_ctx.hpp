@@ -2,6 +2,7 @@
 #pragma once
 #include "isdf_internal.hpp"
 #include "dev_buf.hpp"
+#include "ctx_state.hpp"
 #include "minco_host.hpp"
 #include "midend_host.hpp"
 #include <chrono>
@@ -11,15 +12,12 @@
 
 using namespace isdf;
 
-struct ProfEvent { hipEvent_t a, b, c, d; };   // start/stop of the dominant kernel, start/stop of the one after it
+using ProfEvent = DevEvents<4>;                 // start/stop of the dominant kernel, start/stop of the one after it
 struct isdf_xchg;
 struct SweptMeshState;          // swept_mesh.hip: scratch of the swept-volume field query and the last mesh
 struct TrajCheckState;          // swept_field.hpp: the last clearance check's points below the margin
-void isdf_swept_release_all(isdf_ctx *c);     // swept_mesh.hip: drops the field scratch and the mesh
-void isdf_traj_check_release_all(isdf_ctx *c);        // traj_check.hip: drops the kept clearance report
 void traj_watch_disarm(isdf_ctx *c);                  // traj_watch.hip: the kept report is no longer folded across map updates (a new shape)
 struct TrajLimitsState;         // traj_limits.hip: scratch of the dynamic-limits report and the state sampler
-void isdf_traj_limits_release_all(isdf_ctx *c);       // traj_limits.hip: drops it
 // traj_limits.hip, for callers that hold B trajectories on the device already: the report's two launches on `st` and nothing else (no
 // event, copy or synchronisation; d_piece: B N x 12, d_info: B x ISDF_TL_INFO_WORDS doubles), and a trajectory's words -> its info
 constexpr int ISDF_TL_INFO_WORDS = 4 * ISDF_LIMITS_CHANNELS;     // per channel: value, time, piece, pieces over the limit
@@ -27,15 +25,10 @@ int isdf_traj_limits_launch(isdf_ctx *c, int B, int N, const double *d_T, const 
                             double *d_info, hipStream_t st);
 void isdf_traj_limits_unpack(const isdf_config &cfg, const isdf_traj_limits_params *p, const double *words, isdf_traj_limits_info *info);
 struct TrajRetimeState;         // traj_retime.hip: scratch of the retiming (ladder copies, piece rows, reports, search state)
-void isdf_traj_retime_release_all(isdf_ctx *c);       // traj_retime.hip: drops it
 struct TrajReallocState;        // traj_realloc.hip: scratch of the per-piece re-allocation (iterate, piece rows, reports, state)
-void isdf_traj_realloc_release_all(isdf_ctx *c);      // traj_realloc.hip: drops it
 struct MapUpdateState;          // map_change.hpp: scratch of the in-place map changes (input, new-voxel list, hand-over record, table staging)
-void isdf_map_update_release_all(isdf_ctx *c);        // map_update.hip: drops it
 struct MapRaycastState;         // map_raycast.hip: staging of the host-pointer ray cast, the counters' record and its pinned copy
-void isdf_map_raycast_release_all(isdf_ctx *c);       // map_raycast.hip: drops it
 struct DepthCamState;           // depth_cam.hip: staging of the depth camera's host-pointer forms, the counters' record and its pinned copy
-void isdf_depth_cam_release_all(isdf_ctx *c);         // depth_cam.hip: drops it
 int isdf_traj_check_ready(isdf_ctx *c);               // traj_check.hip: what isdf_traj_check needs of the ctx (shape, occupancy grid), or the error
 
 // frontend_field.hip: the record of one in-place change of the cost-to-go field (voxels closed: the repair; opened: the reopen),
@@ -49,6 +42,7 @@ struct FfRecord {
     unsigned long long goal_opened;         // opening: the goal cell opened
     unsigned long long opened_reached;      // opening: opened voxels with a finite d after the rounds
 };
+static_assert(isdf::LAZY_NO_MEMORY == ISDF_ERR_HIP, "the slot reports a failed new as isdf_create does");
 static_assert(sizeof(FfRecord) == 64, "the field change's record is one 64-byte line");
 inline FfRecord ff_record_empty() {
     FfRecord r{};
@@ -90,11 +84,11 @@ struct isdf_ctx {
     DevBuf<float> d_esdf;
     int mesh_info[16] = {0};                    // isdf_mesh_info: what isdf_set_shape found and decided about the installed mesh
     double mesh_rmax = 0.0;                     // mesh robots: largest body-frame vertex norm (the swept mesh's box margin)
-    SweptMeshState *swm = nullptr;              // isdf_swept_sdf / isdf_swept_mesh_*: own scratch, never the V1 step's
-    TrajCheckState *tck = nullptr;              // isdf_traj_check*: the kept report rows
-    TrajLimitsState *tlm = nullptr;             // isdf_traj_limits* / isdf_traj_sample*: own scratch (grows only)
-    TrajRetimeState *trt = nullptr;             // isdf_traj_retime*: own scratch (grows only)
-    TrajReallocState *tra = nullptr;            // isdf_traj_realloc*: own scratch (grows only)
+    Lazy<SweptMeshState> swm;                   // isdf_swept_sdf / isdf_swept_mesh_*: own scratch, never the V1 step's
+    Lazy<TrajCheckState> tck;                   // isdf_traj_check*: the kept report rows
+    Lazy<TrajLimitsState> tlm;                  // isdf_traj_limits* / isdf_traj_sample*: own scratch (grows only)
+    Lazy<TrajRetimeState> trt;                  // isdf_traj_retime*: own scratch (grows only)
+    Lazy<TrajReallocState> tra;                 // isdf_traj_realloc*: own scratch (grows only)
     const double *v1_tstar_stage = nullptr;     // set by the host-direct V1 step for ONE eval_device_impl call (SweptParams::tstar_stage)
     DevBuf<double> d_esdf_stage;        // isdf_esdf_sample's staging (points | values | gradients): grows only, no allocation per call
     DevBuf<float> d_esdf_bricks; bool bricks_stale = true;     // the ESDF as 2 x 2 x 2-cell bricks with apron, one 128-byte line each (map_build.hip: scattered points)
@@ -102,9 +96,9 @@ struct isdf_ctx {
     // isdf_set_pointcloud's points per voxel and its sta_threshold, kept for isdf_update_pointcloud; gone after isdf_set_grid and after
     // an isdf_update_voxels that occupied a voxel (the counts no longer describe the occupancy)
     DevBuf<unsigned> d_counts; int counts_thr = 0;
-    MapUpdateState *mup = nullptr;              // isdf_update_pointcloud / isdf_update_voxels: own scratch (grows only)
-    MapRaycastState *mrc = nullptr;             // isdf_map_raycast*: own scratch (grows only)
-    DepthCamState *dcm = nullptr;               // isdf_depth_render* / isdf_depth_rays* / isdf_integrate_depth: own scratch (grows only)
+    Lazy<MapUpdateState> mup;                   // isdf_update_pointcloud / isdf_update_voxels: own scratch (grows only)
+    Lazy<MapRaycastState> mrc;                  // isdf_map_raycast*: own scratch (grows only)
+    Lazy<DepthCamState> dcm;                    // isdf_depth_render* / isdf_depth_rays* / isdf_integrate_depth: own scratch (grows only)
     DevBuf<unsigned> d_bits; bool bits_dirty = true;
     // the known grid (map_known.hip): one bit per voxel, 1 = some ray has visited it or the caller declared it known.  `on`
     // outlives maps (isdf_map_known_enable); d_bits holds n_words dwords while `have`; d_shift is where a window shift writes before the
@@ -115,14 +109,9 @@ struct isdf_ctx {
         DevBuf<unsigned> d_bits, d_shift;
         long long newly = 0, merges = 0;            // isdf_map_known_info's newly_known and merges
         DevBuf<unsigned> d_front; DevBuf<int> d_cnt, d_base; DevBuf<long long> d_list; DevBuf<void> d_scan_tmp;
-        DevBuf<MkRecord> d_rec; PinBuf<MkRecord> h_rec;
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        RecPair<MkRecord> rec; DevEvents<2> ev;
         // isdf_map_known_merge_ms: a developer's pair of events round the merge kernel, recorded only while asked for
-        bool time_merge = false; hipEvent_t ev_merge[2] = {nullptr, nullptr}; double merge_ms = -1.0;
-        ~Known() {
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-            for (hipEvent_t e : ev_merge) if (e) (void)hipEventDestroy(e);
-        }
+        bool time_merge = false; DevEvents<2> ev_merge; double merge_ms = -1.0;
     } known;
     bool have_geom = false;
     unsigned long long grid_epoch = 0;          // counts isdf_set_grid / isdf_set_pointcloud: what was derived from voxel indices of an older grid is stale
@@ -233,10 +222,10 @@ struct isdf_ctx {
         bool field_valid = false, field_reachable = false; int field_goal[3] = {-1, -1, -1};
         // what an in-place change (the repair after a map update, the reopen after a clear) needs of the last build: its status and
         // round bound, the counts of free and of reached voxels as the last build / repair / reopen left them; the change's record on
-        // the device and its pinned copy [as it starts | as the kernels left it]; the opening direction's opened bits of the changed
+        // the device and its pinned copy (uploaded empty, read back as the kernels left it); the opening direction's opened bits of the changed
         // box, one word per wavefront of the mark kernel
         int field_status = 0, field_max_rounds = 0; long long field_free_voxels = 0, field_reached_voxels = 0;
-        DevBuf<FfRecord> d_field_rep; PinBuf<FfRecord> h_field_rep;
+        RecPair<FfRecord> field_rep;
         DevBuf<unsigned long long> d_field_open;
         // the last repair's and the last reopen's report (field_repaired, field_reopened: there was one since the build)
         bool field_repaired = false; isdf_field_repair_info field_repair{};
@@ -261,7 +250,7 @@ struct isdf_ctx {
     // reading the peers' buffers over xGMI in rank order, or RCCL's all-reduce) - SURVEY 8(b) "Threading".
     std::vector<isdf_ctx *> peers;
     bool is_peer = false;                       // owned by a lead: not handed to the caller
-    hipEvent_t mev_in = nullptr, mev_done = nullptr;      // lead: inputs ready on the caller's stream / the step's sum has run; peer: shard finished
+    DevEvents<1> mev_in, mev_done;                        // lead: inputs ready on the caller's stream / the step's sum has run; peer: shard finished
     // mesh robots on the tile sweep: the queue of 64-voxel blocks between the scan launch and the exact launch
     DevBuf<unsigned> d_mq_entries, d_mq_count;
     DevBuf<int2> d_mq_items;
@@ -275,8 +264,7 @@ struct isdf_ctx {
     void *rccl_lib = nullptr; void *rccl_comm = nullptr;  // RCCL by dlopen (only when asked for): this device's communicator
     DevBuf<double> d_mpart;         // every shard of a multi-device step writes [packed outputs | 8 statistics as doubles] here
     DevBuf<double> d_mstage;        // lead, staged mode: the peers' parts copied next to each other
-    // every buffer above frees itself; the states held by pointer are dropped here (isdf_destroy makes the device current)
-    ~isdf_ctx() { isdf_swept_release_all(this); isdf_traj_check_release_all(this); isdf_traj_limits_release_all(this); isdf_traj_retime_release_all(this); isdf_traj_realloc_release_all(this); isdf_map_update_release_all(this); isdf_map_raycast_release_all(this); isdf_depth_cam_release_all(this); }
+    // every buffer, event and lazily created state above frees itself (isdf_destroy makes the device current)
 };
 namespace isdf { struct XFuse; }
 // xchg.hip: fills the in-kernel exchange block of a fused step when isdf_xchg_fuse is on (returns false: not requested;

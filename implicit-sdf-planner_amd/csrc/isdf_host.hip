@@ -92,7 +92,7 @@ extern "C" int isdf_destroy(isdf_ctx *c) {
     (void)hipSetDevice(c->device);
     multi_release(c);
     (void)hipDeviceSynchronize();
-    for (auto &p : c->prof_events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); (void)hipEventDestroy(p.c); (void)hipEventDestroy(p.d); }
+    c->prof_events.clear();
     isdf_frontend_release(c);
     isdf_xchg_release(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -198,6 +198,7 @@ extern "C" void isdf_debug_live_bytes(long long out[2]) {
     if (!out) return;
     for (int k = 0; k < 2; k++) out[k] = isdf::g_live_bytes[k].load(std::memory_order_relaxed);
 }
+extern "C" long long isdf_debug_live_events(void) { return isdf::g_live_events.load(std::memory_order_relaxed); }
 
 void isdf_fill_flat(const isdf_config &cfg, FlatP &f) {
     f.mass = cfg.vehicle_mass; f.grav = cfg.grav_acc; f.dh = cfg.horiz_drag; f.dv = cfg.vert_drag;
@@ -210,11 +211,8 @@ static int prof_begin(isdf_ctx *c, hipStream_t st, ProfEvent **ev) {
     if ((c->prof_tick++ % c->prof_every) != 0) return ISDF_OK;
     if (c->prof_used == c->prof_events.size()) {
         ProfEvent p;
-        HIPCHK(c, hipEventCreate(&p.a));
-        HIPCHK(c, hipEventCreate(&p.b));
-        HIPCHK(c, hipEventCreate(&p.c));
-        HIPCHK(c, hipEventCreate(&p.d));
-        c->prof_events.push_back(p);
+        ISDF_TRY(p.ready(c));
+        c->prof_events.push_back(std::move(p));
     }
     *ev = &c->prof_events[c->prof_used++];
     return ISDF_OK;
@@ -365,11 +363,11 @@ static int v1_step(isdf_ctx *c, const isdf_config &cfg, int n_traj, int N, const
     launch_swept_prepare(P, st);
     ProfEvent *ev;
     ISDF_TRY(prof_begin(c, st, &ev));
-    launch_swept_sweep(P, st, ev ? ev->a : nullptr, ev ? ev->b : nullptr);
+    launch_swept_sweep(P, st, ev ? (*ev)[0] : nullptr, ev ? (*ev)[1] : nullptr);
     const bool ev2 = ev && c->prof_secondary;
-    if (ev2) { HIPCHK(c, hipEventRecord(ev->c, st)); }
+    if (ev2) { HIPCHK(c, hipEventRecord((*ev)[2], st)); }
     launch_swept_reduce(P, d_out, st);
-    if (ev2) { HIPCHK(c, hipEventRecord(ev->d, st)); }
+    if (ev2) { HIPCHK(c, hipEventRecord((*ev)[3], st)); }
     HIPCHK(c, hipGetLastError());
     if (scan_lpt) { c->scan_order_b = order_b; c->scan_order_e = order_e; c->scan_order_epoch = c->points_epoch; }
     return ISDF_OK;
@@ -588,8 +586,8 @@ int eval_device_impl(isdf_ctx *c, int n_traj, int N, const double *d_T, const do
         rc = mesh_queue(c, cfg, P, ns_loc);
         if (rc) return rc;
     }
-    launch_sweep(P, st, ev ? ev->a : nullptr, ev ? ev->b : nullptr, fused);
-    if (!fused) launch_tail(P, st, ev2 ? ev->c : nullptr, ev2 ? ev->d : nullptr);
+    launch_sweep(P, st, ev ? (*ev)[0] : nullptr, ev ? (*ev)[1] : nullptr, fused);
+    if (!fused) launch_tail(P, st, ev2 ? (*ev)[2] : nullptr, ev2 ? (*ev)[3] : nullptr);
     HIPCHK(c, hipGetLastError());
     return ISDF_OK;
 }
@@ -658,12 +656,12 @@ extern "C" int isdf_profile_read(isdf_ctx *c, int *n, double *mean_ms) {
     HIPCHK(c, hipSetDevice(c->device));
     double sum = 0.0, sum2 = 0.0;
     for (size_t i = 0; i < c->prof_used; i++) {
-        HIPCHK(c, hipEventSynchronize(c->prof_secondary ? c->prof_events[i].d : c->prof_events[i].b));
+        HIPCHK(c, hipEventSynchronize(c->prof_events[i][c->prof_secondary ? 3 : 1]));
         float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->prof_events[i].a, c->prof_events[i].b));
+        HIPCHK(c, hipEventElapsedTime(&ms, c->prof_events[i][0], c->prof_events[i][1]));
         sum += ms;
         if (c->prof_secondary) {
-            HIPCHK(c, hipEventElapsedTime(&ms, c->prof_events[i].c, c->prof_events[i].d));
+            HIPCHK(c, hipEventElapsedTime(&ms, c->prof_events[i][2], c->prof_events[i][3]));
             sum2 += ms;
         }
     }

@@ -9,7 +9,6 @@
 #include "map_change.hpp"
 #include "swept_field.hpp"
 #include <algorithm>
-#include <new>
 #include <string>
 
 namespace isdf {
@@ -57,8 +56,6 @@ __global__ __launch_bounds__(256) void mu_pack_box_kernel(const uint4 *__restric
 
 using namespace isdf;
 
-void isdf_map_update_release_all(isdf_ctx *c) { delete c->mup; c->mup = nullptr; }
-
 int isdf::map_change_ready(isdf_ctx *c, const char *op, const void *in, long long n, bool needs_counts) {
     const std::string o = op;
     if (n < 0 || (n > 0 && !in)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, (o + ": bad arguments").c_str());
@@ -78,11 +75,9 @@ int isdf::map_voxels_in_grid(isdf_ctx *c, const int32_t *ijk, long long n) {
 
 int isdf::map_begin(isdf_ctx *c, MapUpdateState **out) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->mup) { c->mup = new (std::nothrow) MapUpdateState(); if (!c->mup) return isdf_fail(c, ISDF_ERR_HIP, "out of host memory"); }
-    for (hipEvent_t &e : c->mup->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    for (hipEvent_t &e : c->mup->ev_scan) if (!e) HIPCHK(c, hipEventCreate(&e));
-    *out = c->mup;
-    return ISDF_OK;
+    ISDF_TRY(c->mup.make(c, out));
+    ISDF_TRY((*out)->ev.ready(c));
+    return (*out)->ev_scan.ready(c);
 }
 
 unsigned isdf::map_list_cap(long long max_voxels, unsigned long long n_in, unsigned long long n_vox) {
@@ -94,9 +89,8 @@ int isdf::map_stage(isdf_ctx *c, MapUpdateState &S, const void *in, size_t in_by
     int rc;
     if ((rc = S.d_in.reserve(c, in_bytes + in2_bytes))) return rc;
     if (list_len && (rc = S.d_list.reserve(c, list_len))) return rc;
-    if ((rc = S.d_rec.reserve(c, 1)) || (rc = S.h_rec.reserve(c, 1))) return rc;
-    *S.h_rec.get() = map_records_empty();
-    HIPCHK(c, hipMemcpyAsync(S.d_rec, S.h_rec.get(), sizeof(MapRecords), hipMemcpyHostToDevice, st));
+    if ((rc = S.rec.ready(c))) return rc;
+    HIPCHK(c, S.rec.put(map_records_empty(), st));
     if (in_bytes && in) HIPCHK(c, hipMemcpyAsync(S.d_in, in, in_bytes, hipMemcpyHostToDevice, st));
     if (in2_bytes && in2) HIPCHK(c, hipMemcpyAsync((uint8_t *)S.d_in.get() + in_bytes, in2, in2_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(ev_begin, st));
@@ -105,7 +99,7 @@ int isdf::map_stage(isdf_ctx *c, MapUpdateState &S, const void *in, size_t in_by
 
 int isdf::map_hand_over(isdf_ctx *c, MapUpdateState &S, hipEvent_t ev_end, const char *op, bool voxels) {
     hipError_t e = ev_end ? hipEventRecord(ev_end, c->stream) : hipSuccess;
-    if (e == hipSuccess) e = map_records_fetch(S, c->stream);
+    if (e == hipSuccess) e = S.rec.fetch(c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) return ISDF_OK;
     c->err = std::string(op) + " hand-over: " + hipGetErrorString(e);
@@ -227,14 +221,14 @@ void isdf::map_frontend_finish(isdf_ctx *c, MapUpdateState &S, MapFrontend &F) {
         for (int b = 0; b < F.n_boxes; b++) mu_scatter_box(fe.h_cspace, dims, nw, F.grown[b], S.h_pack.get() + F.pack_at[b]);
         F.host_table_patched = 1;
     }
-    F.ms = mu_event_ms(S.ev[4], S.ev[5]);
+    F.ms = S.ev.ms(4, 5);
 }
 
 int isdf::map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool follow, bool on, bool full, const MapRefresh &M, MapFrontend &F, int *field_dropped) {
     const int *const lo = full ? nullptr : M.grown.lo, *const hi = full ? nullptr : M.grown.hi;
     int rc;
     if ((rc = map_frontend_launch(c, S, on, full, &M.box, &M.grown, 1, F))) return rc;
-    HIPCHK(c, map_records_fetch(S, c->stream));
+    HIPCHK(c, S.rec.fetch(c->stream));
     if (follow && (rc = isdf_field_change_begin(c, dir, lo, hi, S.ev[6]))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (follow) {
@@ -264,9 +258,4 @@ int isdf::map_watch_recheck(isdf_ctx *c, bool armed, int32_t *rechecked) {
     L.select_ms = now.select_ms; L.field_ms = now.field_ms; L.reduce_ms = now.reduce_ms;
     *rechecked = 1;
     return ISDF_OK;
-}
-
-float isdf::mu_event_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
 }

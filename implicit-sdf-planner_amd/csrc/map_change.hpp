@@ -62,22 +62,18 @@ __device__ __forceinline__ void map_list_append(MapListRecord *__restrict__ rec,
 struct MapUpdateState {
     isdf::DevBuf<void> d_in;                  // the call's points or voxel indices
     isdf::DevBuf<isdf::MuVoxel> d_list;       // the new (or cleared) voxels, in no defined order
-    isdf::DevBuf<isdf::MapRecords> d_rec; isdf::PinBuf<isdf::MapRecords> h_rec;      // one block each
+    isdf::RecPair<isdf::MapRecords> rec;
     isdf::DevBuf<uint4> d_pack; isdf::PinBuf<uint32_t> h_pack;          // the grown box of the configuration space on its way to the host table
     isdf::DevBuf<int> d_edt_a, d_edt_b;       // map_clear.hip: the slabs of the separable transform over the touched box
     isdf::DevBuf<unsigned> d_free_bits, d_hit_bits;     // map_scan.hip: one bit per voxel, the voxels a scan's rays pass / end in
     // map_shift.hip: where the translation writes; each then changes places with the ctx's own buffer (one more copy of the counts, the
     // occupancy and the configuration-space table stays allocated)
     isdf::DevBuf<unsigned> d_shift_counts, d_shift_cspace; isdf::DevBuf<uint8_t> d_shift_occ;
-    hipEvent_t ev_scan[2] = {nullptr, nullptr};          // map_scan.hip: around the ray stage
+    isdf::DevEvents<2> ev_scan;                          // map_scan.hip: around the ray stage
     // [0], [1]: a count (translation) stage; [2], [3]: the ESDF stage; [4], [5]: the front-end stage; [6], [7]: the field's in-place
     // change inside map_frontend_stage, either direction (a scan's two stages use them one after the other); [6] .. [9]: the field
     // carried through a shift, its two phases
-    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~MapUpdateState() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_scan) if (e) (void)hipEventDestroy(e);
-    }
+    isdf::DevEvents<10> ev;
 };
 
 namespace isdf {
@@ -94,10 +90,9 @@ unsigned map_list_cap(long long max_voxels, unsigned long long n_in, unsigned lo
 // the records uploaded empty, the input uploaded (a null `in` / `in2` with bytes: room is kept, nothing is uploaded - the caller fills it
 // on the stream), ev_begin recorded.  Nothing allocates on a second call of the same size.
 int map_stage(isdf_ctx *c, MapUpdateState &S, const void *in, size_t in_bytes, const void *in2, size_t in2_bytes, size_t list_len, hipEvent_t ev_begin);
-// hand-over: ev_end recorded (null: none), the records to S.h_rec, one synchronisation.  The kernels before it may have run, so a
+// hand-over: ev_end recorded (null: none), the records to S.rec.host(), one synchronisation.  The kernels before it may have run, so a
 // failure leaves "<op> hand-over: ..." in the ctx and drops what was derived from the old map.
 int map_hand_over(isdf_ctx *c, MapUpdateState &S, hipEvent_t ev_end, const char *op, bool voxels);
-inline hipError_t map_records_fetch(MapUpdateState &S, hipStream_t st) { return hipMemcpyAsync(S.h_rec.get(), S.d_rec, sizeof(MapRecords), hipMemcpyDeviceToHost, st); }
 // After a failure past the point where the occupancy moved: what was derived from the old map goes (as isdf_set_pointcloud drops
 // it), the error message stays.  The occupancy and the counts are consistent with each other and stay.
 void mu_drop_derived(isdf_ctx *c, bool voxels);
@@ -122,7 +117,7 @@ struct MapFrontend {
 int map_frontend_launch(isdf_ctx *c, MapUpdateState &S, bool on, bool full, const MuBox *boxes, const MuBox *grown, int n_boxes, MapFrontend &F, bool stamp = true);
 void map_frontend_finish(isdf_ctx *c, MapUpdateState &S, MapFrontend &F);
 // The whole stage of a change in one direction (dir: its voxels closed or opened) with the cost-to-go field following it around the one
-// synchronisation: _launch over (M.box, M.grown) or the full map, the records on their way to S.h_rec, when `follow` (the caller asked
+// synchronisation: _launch over (M.box, M.grown) or the full map, the records on their way to S.rec.host(), when `follow` (the caller asked
 // isdf_field_change_wanted before map_refresh_begin dropped the field) the field's begin over M.grown; the synchronisation; the
 // field's end - its rounds read one word each -, and only then _finish: the host table is patched after them.  A field that followed:
 // *field_dropped = 0.  F: for map_frontend_report.
@@ -134,7 +129,6 @@ template <class Info> inline void map_frontend_report(const MapFrontend &F, Info
 // watch re-check: removed or moved voxels cannot be subtracted from the kept report's piece minima, so an armed watch's trajectory is
 // checked against the whole new map again and stays armed.  A failing check drops the report and fails the call.  *rechecked = armed.
 int map_watch_recheck(isdf_ctx *c, bool armed, int32_t *rechecked);
-float mu_event_ms(hipEvent_t a, hipEvent_t b);
 
 // Everything after the hand-over of a call that occupied (mu_, map_update.hip) or freed (mc_, map_clear.hip) at least one voxel: R is
 // the count stage's record as the host read it, S.d_list the new (cleared) voxels, cap the list's capacity; the counts and the occupancy

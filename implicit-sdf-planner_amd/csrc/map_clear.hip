@@ -197,8 +197,8 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
     bool full = M.over;
 
     // ---- ESDF
-    McEsdfRecord *const d_er = &S.d_rec.get()->esdf;
-    const McEsdfRecord *const h_er = &S.h_rec.get()->esdf;
+    McEsdfRecord *const d_er = &S.rec.dev()->esdf;
+    const McEsdfRecord *const h_er = &S.rec.host().esdf;
     HIPCHK(c, hipEventRecord(S.ev[2], st));
     if (M.do_esdf) {
         MuBox T{{0, 0, 0}, {-1, -1, -1}};
@@ -237,7 +237,7 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
     if ((rc = map_frontend_stage(c, S, FfChange::Opening, reopen, P.refresh_frontend != 0, full, M, F, &info.field_dropped))) return rc;
     map_frontend_report(F, info);
     if (M.do_esdf && !full) info.esdf_voxels_raised = (long long)h_er->raised;
-    info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
+    info.esdf_ms = S.ev.ms(2, 3);
     return map_watch_recheck(c, traj_watch_armed(c), &info.watch_rechecked);
 }
 
@@ -264,7 +264,7 @@ int map_clear(isdf_ctx *c, const void *in, long long n_in, bool voxels, const is
     if ((rc = map_stage(c, S, in, (size_t)n_in * 3 * (voxels ? sizeof(int) : sizeof(float)), nullptr, 0, std::max<size_t>(cap, 1), S.ev[0]))) return rc;
     if (n_in > 0) {
         const unsigned blocks = (unsigned)std::min<long long>((n_in + 255) / 256, 2048);
-        MapListRecord *const d_rec = &S.d_rec.get()->list;
+        MapListRecord *const d_rec = &S.rec.dev()->list;
         if (voxels) hipLaunchKernelGGL(mc_mark_kernel<true>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, (unsigned *)nullptr, 0u, c->d_occ.get(),
                                        S.d_list.get(), cap, d_rec);
         else hipLaunchKernelGGL(mc_mark_kernel<false>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, c->d_counts.get(), (unsigned)c->counts_thr,
@@ -272,8 +272,8 @@ int map_clear(isdf_ctx *c, const void *in, long long n_in, bool voxels, const is
         HIPCHK(c, hipGetLastError());
     }
     if ((rc = map_hand_over(c, S, S.ev[1], "map clear", voxels))) return rc;           // the kernel may have run: the occupancy may have moved
-    const MapListRecord R = S.h_rec.get()->list;
-    info.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
+    const MapListRecord R = S.rec.host().list;
+    info.count_ms = S.ev.ms(0, 1);
     info.n_cleared_voxels = R.n;
     info.n_points_ignored = (long long)R.tally;
     if (R.n > 0) {                      // (nothing but the counts changed: every product stays in place, the field and the watch included)

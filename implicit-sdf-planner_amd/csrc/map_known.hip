@@ -168,16 +168,14 @@ int known_begin(isdf_ctx *c, const char *op) {
     if (!c->known.have) return isdf_fail(c, ISDF_ERR_STATE, (std::string(op) + ": no known grid (isdf_map_known_enable, then a map from isdf_set_pointcloud)").c_str());
     isdf_ctx::Known &K = c->known;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = K.d_rec.reserve(c, 1)) || (rc = K.h_rec.reserve(c, 1))) return rc;
-    for (hipEvent_t &e : K.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    *K.h_rec.get() = record_empty();
-    HIPCHK(c, hipMemcpyAsync(K.d_rec, K.h_rec.get(), sizeof(MkRecord), hipMemcpyHostToDevice, c->stream));
+    ISDF_TRY(K.rec.ready(c));
+    ISDF_TRY(K.ev.ready(c));
+    HIPCHK(c, K.rec.put(record_empty(), c->stream));
     return ISDF_OK;
 }
 
 int known_fetch(isdf_ctx *c) {
-    HIPCHK(c, hipMemcpyAsync(c->known.h_rec.get(), c->known.d_rec, sizeof(MkRecord), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, c->known.rec.fetch(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ISDF_OK;
 }
@@ -204,7 +202,7 @@ int isdf::map_known_merge_launch(isdf_ctx *c, const unsigned *d_free_bits, const
     const MkGeom g = geom(c);
     isdf_ctx::Known &K = c->known;
     if (K.time_merge) {
-        for (hipEvent_t &e : K.ev_merge) if (!e) HIPCHK(c, hipEventCreate(&e));
+        ISDF_TRY(K.ev_merge.ready(c));
         HIPCHK(c, hipEventRecord(K.ev_merge[0], c->stream));
     }
     hipLaunchKernelGGL(mk_merge_kernel, dim3(1024), dim3(256), 0, c->stream, g, d_free_bits, d_hit_bits, K.d_bits.get(), d_scan);
@@ -216,7 +214,7 @@ int isdf::map_known_merge_launch(isdf_ctx *c, const unsigned *d_free_bits, const
 void isdf::map_known_merged(isdf_ctx *c, const MsRecord &scan) {
     c->known.newly = (long long)scan.newly_known;
     c->known.merges++;
-    if (c->known.time_merge && c->known.ev_merge[1]) c->known.merge_ms = (double)mu_event_ms(c->known.ev_merge[0], c->known.ev_merge[1]);      // (the hand-over has synchronised)
+    if (c->known.time_merge && c->known.ev_merge[1]) c->known.merge_ms = c->known.ev_merge.ms(0, 1);      // (the hand-over has synchronised)
 }
 
 int isdf::map_known_shift_launch(isdf_ctx *c, const int32_t s[3]) {
@@ -274,10 +272,10 @@ extern "C" int isdf_map_known_fill(isdf_ctx *c, const int32_t *box, int value) {
     MuBox B;
     for (int a = 0; a < 3; a++) { B.lo[a] = box[a]; B.hi[a] = box[3 + a]; }
     const long long w0 = (((long long)B.lo[0] * g.Y + B.lo[1]) * g.Z + B.lo[2]) >> 5, w1 = (((long long)B.hi[0] * g.Y + B.hi[1]) * g.Z + B.hi[2]) >> 5;
-    hipLaunchKernelGGL(mk_fill_kernel, dim3(word_blocks(w1 - w0 + 1)), dim3(256), 0, c->stream, g, K.d_bits.get(), B, w0, w1, value ? 1 : 0, K.d_rec.get());
+    hipLaunchKernelGGL(mk_fill_kernel, dim3(word_blocks(w1 - w0 + 1)), dim3(256), 0, c->stream, g, K.d_bits.get(), B, w0, w1, value ? 1 : 0, K.rec.dev());
     HIPCHK(c, hipGetLastError());
     if (int rc = known_fetch(c)) return rc;
-    K.newly = (long long)K.h_rec.get()->newly;
+    K.newly = (long long)K.rec.host().newly;
     return ISDF_OK;
 }
 
@@ -287,13 +285,13 @@ extern "C" int isdf_map_known_get(isdf_ctx *c, uint32_t *bits_out, isdf_map_know
     isdf_ctx::Known &K = c->known;
     const MkGeom g = geom(c);
     if (info_out) {
-        hipLaunchKernelGGL(mk_stats_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, c->stream, g, (const unsigned *)K.d_bits.get(), K.d_rec.get());
+        hipLaunchKernelGGL(mk_stats_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, c->stream, g, (const unsigned *)K.d_bits.get(), K.rec.dev());
         HIPCHK(c, hipGetLastError());
     }
     if (bits_out) HIPCHK(c, hipMemcpyAsync(bits_out, K.d_bits, (size_t)g.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (int rc = known_fetch(c)) return rc;
     if (info_out) {
-        const MkRecord R = *K.h_rec.get();
+        const MkRecord R = K.rec.host();
         isdf_map_known_info info{};
         info.n_known = (int64_t)R.n; info.n_unknown = (int64_t)(g.n_vox - (long long)R.n);
         box_out(R, info.lo, info.hi);
@@ -316,17 +314,17 @@ extern "C" int isdf_map_frontier(isdf_ctx *c, uint32_t *bits_out, int64_t *vox_o
     if ((rc = K.d_front.reserve(c, (size_t)g.n_words)) || (rc = K.d_cnt.reserve(c, (size_t)g.n_words)) || (rc = K.d_base.reserve(c, (size_t)g.n_words))) return rc;
     HIPCHK(c, hipEventRecord(K.ev[0], st));
     hipLaunchKernelGGL(mk_frontier_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, st, g, (const unsigned *)K.d_bits.get(), (const uint8_t *)c->d_occ.get(), K.d_front.get(),
-                       K.d_cnt.get(), K.d_rec.get());
+                       K.d_cnt.get(), K.rec.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(K.ev[1], st));
     if (bits_out) HIPCHK(c, hipMemcpyAsync(bits_out, K.d_front, (size_t)g.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if ((rc = known_fetch(c))) return rc;
-    const MkRecord R = *K.h_rec.get();
+    const MkRecord R = K.rec.host();
     if (info_out) {
         isdf_map_frontier_info info{};
         info.n_frontier = (int64_t)R.n;
         box_out(R, info.lo, info.hi);
-        info.kernel_ms = mu_event_ms(K.ev[0], K.ev[1]);
+        info.kernel_ms = K.ev.ms(0, 1);
         *info_out = info;
     }
     if (!vox_out || R.n == 0) return ISDF_OK;

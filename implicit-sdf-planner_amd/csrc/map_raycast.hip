@@ -11,7 +11,6 @@
 #include "map_raycast_host.hpp"
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 namespace isdf {
 
@@ -70,12 +69,9 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_cast_kernel(const double *__restr
 struct MapRaycastState {
     isdf::DevBuf<void> d_in;                    // origins (3 or n x 3 doubles, 16-byte multiple) | ends
     isdf::DevBuf<int32_t> d_rows;
-    isdf::DevBuf<isdf::MrRecord> d_rec; isdf::PinBuf<isdf::MrRecord> h_rec;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~MapRaycastState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    isdf::RecPair<isdf::MrRecord> rec;
+    isdf::DevEvents<2> ev;
 };
-
-void isdf_map_raycast_release_all(isdf_ctx *c) { delete c->mrc; c->mrc = nullptr; }
 
 using namespace isdf;
 
@@ -92,12 +88,9 @@ extern "C" void isdf_map_raycast_sizes(int sizes_out[2]) {
 namespace {
 
 int raycast_state(isdf_ctx *c, MapRaycastState **out) {
-    if (!c->mrc) { c->mrc = new (std::nothrow) MapRaycastState(); if (!c->mrc) return isdf_fail(c, ISDF_ERR_HIP, "out of host memory"); }
-    for (hipEvent_t &e : c->mrc->ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (int rc = c->mrc->d_rec.reserve(c, 1)) return rc;
-    if (int rc = c->mrc->h_rec.reserve(c, 1)) return rc;
-    *out = c->mrc;
-    return ISDF_OK;
+    ISDF_TRY(c->mrc.make(c, out));
+    ISDF_TRY((*out)->ev.ready(c));
+    return (*out)->rec.ready(c);
 }
 
 // what both forms check of the ctx and of the shared origin; O is filled when the origin is shared
@@ -121,24 +114,23 @@ int raycast_check(isdf_ctx *c, const double *origins, const void *ends, long lon
 int raycast_run(isdf_ctx *c, MapRaycastState *S, const double *d_origins, const float *d_ends, long long n, const isdf_map_raycast_params &P, const MrOrigin &O,
                 int32_t *d_rows, isdf_map_raycast_info *info_out, hipStream_t st) {
     if (info_out) {
-        HIPCHK(c, hipMemsetAsync(S->d_rec, 0, sizeof(MrRecord), st));
+        HIPCHK(c, S->rec.zero(st));
         HIPCHK(c, hipEventRecord(S->ev[0], st));
     }
     if (n > 0) {
         const unsigned blocks = (unsigned)std::min<long long>((n + MR_BLOCK - 1) / MR_BLOCK, 8192);
         hipLaunchKernelGGL(mr_cast_kernel, dim3(blocks), dim3(MR_BLOCK), 0, st, d_origins, d_ends, n, c->grid, O, (const uint8_t *)c->d_occ.get(), (int)P.test_origin_voxel,
-                           d_rows, info_out ? S->d_rec.get() : nullptr);
+                           d_rows, info_out ? S->rec.dev() : nullptr);
         HIPCHK(c, hipGetLastError());
     }
     if (!info_out) return ISDF_OK;
     HIPCHK(c, hipEventRecord(S->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(S->h_rec.get(), S->d_rec, sizeof(MrRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, S->rec.fetch(st));
     return ISDF_OK;
 }
 
 void raycast_info(const MapRaycastState *S, long long n, isdf_map_raycast_info *info_out) {
-    MrRecord R;
-    std::memcpy(&R, S->h_rec.get(), sizeof(R));
+    const MrRecord R = S->rec.host();
     isdf_map_raycast_info info{};
     info.n_rays = n;
     info.n_skipped = (int64_t)R.n_skipped;
@@ -146,8 +138,7 @@ void raycast_info(const MapRaycastState *S, long long n, isdf_map_raycast_info *
     info.n_hits = (int64_t)R.n_hits;
     info.n_clear = (int64_t)R.n_clear;
     info.steps_total = (int64_t)R.steps_total;
-    float ms = 0.f;
-    info.cast_ms = hipEventElapsedTime(&ms, S->ev[0], S->ev[1]) == hipSuccess ? ms : 0.0;
+    info.cast_ms = S->ev.ms(0, 1);
     *info_out = info;
 }
 

@@ -203,7 +203,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     const float *const d_xyz = (const float *)S.d_in.get();
     const uint8_t *const d_hit = has_hit ? (const uint8_t *)S.d_in.get() + xyz_bytes : nullptr;
     if (in.produce && (rc = in.produce(c, (float *)S.d_in.get(), (uint8_t *)S.d_in.get() + xyz_bytes, in.arg))) return rc;          // nothing of the map has moved yet
-    MapRecords *const d_rec = S.d_rec.get(), *const h_rec = S.h_rec.get();
+    MapRecords *const d_rec = S.rec.dev(), *const h_rec = &S.rec.host();
     const unsigned ray_blocks = (unsigned)std::min<long long>((n_rays + 255) / 256, 2048);
 
     // ---- the rays, then the frees: one hand-over
@@ -224,7 +224,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     const MapListRecord R = h_rec->list;
     const MsRecord RS = h_rec->scan;
     if (known) map_known_merged(c, RS);
-    info.trace_ms = mu_event_ms(S.ev_scan[0], S.ev_scan[1]);
+    info.trace_ms = S.ev_scan.ms(0, 1);
     info.n_rays_skipped = (long long)RS.n_skipped;
     info.n_hits = (long long)RS.n_hits;
     info.n_free_voxels = (long long)RS.n_free;
@@ -232,7 +232,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     if (RS.hi[0] >= RS.lo[0]) for (int a = 0; a < 3; a++) { info.ray_lo[a] = RS.lo[a]; info.ray_hi[a] = RS.hi[a]; }
     const unsigned long long n_clear_points = (unsigned long long)miss * RS.n_free;          // what isdf_clear_pointcloud would have been given
     info.clear.n_points = (long long)n_clear_points;
-    info.clear.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
+    info.clear.count_ms = S.ev.ms(0, 1);
     info.clear.n_cleared_voxels = R.n;
     info.clear.n_points_ignored = (long long)R.tally;
     if (R.n > 0) {
@@ -261,7 +261,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     }
     if ((rc = map_hand_over(c, S, S.ev[1], "scan", false))) return rc;
     const MapListRecord RU = h_rec->list;
-    info.update.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
+    info.update.count_ms = S.ev.ms(0, 1);
     info.update.n_new_voxels = RU.n;
     if (RU.n > 0) {
         rc = mu_refresh_products(c, S, P.update, RU, cap_update, false, info.update);

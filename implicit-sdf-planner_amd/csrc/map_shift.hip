@@ -156,7 +156,7 @@ int shift_refresh(isdf_ctx *c, MapUpdateState &S, bool full, const MuBox *boxes,
                 hull.lo[a] = b ? std::min(hull.lo[a], boxes[b].lo[a]) : boxes[b].lo[a];
                 hull.hi[a] = b ? std::max(hull.hi[a], boxes[b].hi[a]) : boxes[b].hi[a];
             }
-        if ((rc = isdf_field_shift_end(c, info.shift, whole ? nullptr : hull.lo, whole ? nullptr : hull.hi, &S.ev[6]))) return rc;
+        if ((rc = isdf_field_shift_end(c, info.shift, whole ? nullptr : hull.lo, whole ? nullptr : hull.hi, S.ev.get() + 6))) return rc;
         info.field_dropped = 0;
     }
     if (F.patch) {                      // the A*'s copy: translated in place by the host form's own function, then the bands
@@ -165,8 +165,8 @@ int shift_refresh(isdf_ctx *c, MapUpdateState &S, bool full, const MuBox *boxes,
     }
     map_frontend_finish(c, S, F);
     info.n_boxes = F.n_boxes; info.cspace_voxels = F.cspace_voxels; info.host_table_patched = F.host_table_patched; info.frontend_ms = F.ms;
-    info.translate_ms = mu_event_ms(S.ev[0], S.ev[1]);
-    info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
+    info.translate_ms = S.ev.ms(0, 1);
+    info.esdf_ms = S.ev.ms(2, 3);
     // the kept clearance report: the trajectory is in world coordinates, so it is checked against the whole new map again, as the
     // clear does, and stays armed under the new epoch
     return map_watch_recheck(c, watch, &info.watch_rechecked);
@@ -216,7 +216,7 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     if (table && (rc = S.d_shift_cspace.reserve(c, n_vox * nw))) return rc;
     if (table && fe.h_cspace_valid && ((rc = S.d_pack.reserve(c, (size_t)band_voxels * nw / 4)) || (rc = S.h_pack.reserve(c, (size_t)band_voxels * nw)))) return rc;
     if ((rc = map_stage(c, S, nullptr, 0, nullptr, 0, 0, S.ev[0]))) return rc;
-    MshRecord *const d_rec = &S.d_rec.get()->shift;
+    MshRecord *const d_rec = &S.rec.dev()->shift;
 
     // ---- translate into the second buffers
     hipLaunchKernelGGL((msh_translate_kernel<unsigned, true>), dim3(grid_blocks(n_vox)), dim3(256), 0, st, (const unsigned *)c->d_counts.get(), S.d_shift_counts.get(), g, 1, d_rec);
@@ -241,7 +241,7 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     const bool carry = isdf_field_shift_wanted(c, s);   // (asked before the field is dropped: it stays invalid until the carry has gone through)
     info.field_dropped = map_changed(c, false);
     if ((rc = map_hand_over(c, S, nullptr, "map shift", false))) return rc;
-    const MshRecord R = S.h_rec.get()->shift;
+    const MshRecord R = S.rec.host().shift;
     info.voxels_entered = msh_voxels_entered(dims, s);
     info.occupied_left = (long long)R.occupied_left;
     info.counts_left = (long long)R.counts_left;

@@ -138,7 +138,7 @@ int isdf::mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_upd
     if (M.do_esdf) {
         if (full) { if ((rc = isdf_generate_esdf(c))) return rc; }
         else {
-            hipLaunchKernelGGL(mu_esdf_kernel, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, st, G, c->d_esdf.get(), S.d_list.get(), (int)R.n, M.box, &S.d_rec.get()->list);
+            hipLaunchKernelGGL(mu_esdf_kernel, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, st, G, c->d_esdf.get(), S.d_list.get(), (int)R.n, M.box, &S.rec.dev()->list);
             HIPCHK(c, hipGetLastError());
         }
         c->bricks_stale = true;
@@ -150,8 +150,8 @@ int isdf::mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_upd
     MapFrontend F;
     if ((rc = map_frontend_stage(c, S, FfChange::Closing, repair, P.refresh_frontend != 0, full, M, F, &info.field_dropped))) return rc;
     map_frontend_report(F, info);
-    info.esdf_voxels_lowered = (long long)S.h_rec.get()->list.tally;
-    info.esdf_ms = mu_event_ms(S.ev[2], S.ev[3]);
+    info.esdf_voxels_lowered = (long long)S.rec.host().list.tally;
+    info.esdf_ms = S.ev.ms(2, 3);
     // the kept clearance report (mode 1 of isdf_traj_check_set_watch): the new voxels folded in, after every product above.  A failing
     // step drops the report and fails the update as a whole, as a failing repair does.
     if (traj_watch_armed(c) && (rc = traj_watch_fold(c, S.d_list.get(), R.n, cap))) return rc;
@@ -181,7 +181,7 @@ int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const i
     if ((rc = map_stage(c, S, in, (size_t)n_in * 3 * (voxels ? sizeof(int) : sizeof(float)), nullptr, 0, std::max<size_t>(cap, 1), S.ev[0]))) return rc;
     if (n_in > 0) {
         const unsigned blocks = (unsigned)std::min<long long>((n_in + 255) / 256, 2048);
-        MapListRecord *const d_rec = &S.d_rec.get()->list;
+        MapListRecord *const d_rec = &S.rec.dev()->list;
         if (voxels) hipLaunchKernelGGL(mu_mark_kernel<true>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, (unsigned *)nullptr, 0u, c->d_occ.get(),
                                        (const float *)c->d_esdf.get(), S.d_list.get(), cap, d_rec);
         else hipLaunchKernelGGL(mu_mark_kernel<false>, dim3(blocks), dim3(256), 0, st, (const void *)S.d_in.get(), n_in, G, c->d_counts.get(), (unsigned)c->counts_thr,
@@ -189,8 +189,8 @@ int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const i
         HIPCHK(c, hipGetLastError());
     }
     if ((rc = map_hand_over(c, S, S.ev[1], "map update", voxels))) return rc;          // the kernel may have run: the occupancy may have advanced
-    const MapListRecord R = S.h_rec.get()->list;
-    info.count_ms = mu_event_ms(S.ev[0], S.ev[1]);
+    const MapListRecord R = S.rec.host().list;
+    info.count_ms = S.ev.ms(0, 1);
     info.n_new_voxels = R.n;
     if (R.n > 0) {                      // (nothing but the counts changed: every product stays in place, the field included)
         // from here on the occupancy has advanced: a failure must not leave products behind that describe the old map

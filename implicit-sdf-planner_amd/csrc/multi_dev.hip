@@ -90,8 +90,7 @@ bool rccl_load() {
 
 void multi_release(isdf_ctx *c) {
     if (c->rccl_comm && g_rccl.CommDestroy) { (void)g_rccl.CommDestroy(c->rccl_comm); c->rccl_comm = nullptr; }
-    if (c->mev_in) { (void)hipEventDestroy(c->mev_in); c->mev_in = nullptr; }
-    if (c->mev_done) { (void)hipEventDestroy(c->mev_done); c->mev_done = nullptr; }
+    c->mev_in.release(); c->mev_done.release();
 }
 
 extern "C" int isdf_create_multi(isdf_ctx **out, const isdf_config *cfg, const int *devices, int n_devices) {
@@ -108,8 +107,8 @@ extern "C" int isdf_create_multi(isdf_ctx **out, const isdf_config *cfg, const i
         if (rc != ISDF_OK) return bail(rc, std::string("device ") + std::to_string(devices[r]) + ": " + isdf_last_error(nullptr));
         all.push_back(q);
         q->rank = r; q->world = n_devices;
-        if (hipSetDevice(q->device) != hipSuccess || hipEventCreateWithFlags(&q->mev_done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&q->mev_in, hipEventDisableTiming) != hipSuccess)
+        if (hipSetDevice(q->device) != hipSuccess || q->mev_done.ready(q, hipEventDisableTiming) != ISDF_OK ||
+            q->mev_in.ready(q, hipEventDisableTiming) != ISDF_OK)
             return bail(ISDF_ERR_HIP, "event creation failed");
     }
     isdf_ctx *lead = all[0];
@@ -175,8 +174,8 @@ int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, const d
     HIPCHK(c, hipSetDevice(c->device));
     // the previous step's sum read the peers' part buffers and this ctx's own: a step issued on ANOTHER caller stream must not
     // overwrite them before that sum has run (the peers' streams follow through mev_in below)
-    if (c->msum_recorded) HIPCHK(c, hipStreamWaitEvent(st, c->mev_done, 0));
-    HIPCHK(c, hipEventRecord(c->mev_in, st));                              // the caller's inputs are ready from here on
+    if (c->msum_recorded) HIPCHK(c, hipStreamWaitEvent(st, c->mev_done[0], 0));
+    HIPCHK(c, hipEventRecord(c->mev_in[0], st));                              // the caller's inputs are ready from here on
     double *lead_ts = swept ? (d_tstar ? d_tstar : c->d_tstar) : nullptr;
     const bool pull = c->multi_pull && c->multi_collective == ISDF_MULTI_PEER_SUM;
     MultiParts parts{};
@@ -189,7 +188,7 @@ int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, const d
         int rc = pull ? ISDF_OK : p->d_in.reserve(p, in_T + in_C);
         if (rc == ISDF_OK) rc = p->d_mpart.reserve(p, count + MULTI_TAIL);
         if (rc) { c->err = p->err; return rc; }
-        HIPCHK(c, hipStreamWaitEvent(p->stream, c->mev_in, 0));
+        HIPCHK(c, hipStreamWaitEvent(p->stream, c->mev_in[0], 0));
         long long pb = 0, pe = 0;
         if (pull) {
             // the shard reads the lead's inputs in place (peer access); lastTstar likewise - every point belongs to ONE shard
@@ -208,7 +207,7 @@ int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, const d
             hipLaunchKernelGGL(multi_tail_kernel, dim3(1), dim3(64), 0, p->stream, p->d_stats, p->d_mpart + count);
             if (swept && pe > pb && lead_ts) HIPCHK(c, hipMemcpyPeerAsync(lead_ts + pb, c->device, p->d_tstar + pb, p->device, (size_t)(pe - pb) * sizeof(double), p->stream));
         }
-        HIPCHK(c, hipEventRecord(p->mev_done, p->stream));
+        HIPCHK(c, hipEventRecord(p->mev_done[0], p->stream));
         parts.p[r] = p->d_mpart;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -222,7 +221,7 @@ int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, const d
     const dim3 grid((unsigned)((count + MULTI_TAIL + 255) / 256)), block(256);
     if (c->multi_collective == ISDF_MULTI_RCCL) {
         // ONE all-reduce of the packed vector per step: every device's part in place, issued from this thread as one group
-        for (int r = 1; r < n; r++) HIPCHK(c, hipStreamWaitEvent(st, c->peers[r - 1]->mev_done, 0));      // (the merged lastTstar)
+        for (int r = 1; r < n; r++) HIPCHK(c, hipStreamWaitEvent(st, c->peers[r - 1]->mev_done[0], 0));      // (the merged lastTstar)
         if (g_rccl.GroupStart() != 0) return isdf_fail(c, ISDF_ERR_HIP, "ncclGroupStart failed");
         for (int r = 0; r < n; r++) {
             isdf_ctx *q = r == 0 ? c : c->peers[r - 1];
@@ -236,7 +235,7 @@ int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, const d
         MultiParts one{}; one.n = 1; one.p[0] = c->d_mpart;
         hipLaunchKernelGGL(multi_sum_kernel, grid, block, 0, st, d_out, one, count, c->d_stats, swept ? 1 : 0, mh_words, c->d_msum_blocks, c->mh_seq);
     } else {
-        for (int r = 1; r < n; r++) HIPCHK(c, hipStreamWaitEvent(st, c->peers[r - 1]->mev_done, 0));
+        for (int r = 1; r < n; r++) HIPCHK(c, hipStreamWaitEvent(st, c->peers[r - 1]->mev_done[0], 0));
         if (c->multi_collective == ISDF_MULTI_STAGED) {
             rc = c->d_mstage.reserve(c, (size_t)(n - 1) * (count + MULTI_TAIL));
             if (rc) return rc;
@@ -251,7 +250,7 @@ int multi_eval_device(isdf_ctx *c, int n_traj, int N, const double *d_T, const d
     HIPCHK(c, hipGetLastError());
     // the next step's peer copies overwrite the peers' inputs: they are ordered behind THIS step's kernels by the peers' own
     // streams; the part buffers behind the lead's "sum done" event (its own mev_done: the lead records no other use of it)
-    HIPCHK(c, hipEventRecord(c->mev_done, st));
+    HIPCHK(c, hipEventRecord(c->mev_done[0], st));
     c->msum_recorded = true;
     return ISDF_OK;
 }

@@ -85,7 +85,7 @@ extern "C" int isdf_points_merge_check(isdf_ctx *c, double below, isdf_points_me
     if (!std::isfinite(below)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "points merge: below must be finite");
     if (!c) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "points merge: null ctx");
     if (!c->peers.empty() || c->is_peer || c->rccl_comm) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "points merge on a multi-device ctx");
-    TrajCheckState *k = c->tck;
+    TrajCheckState *k = c->tck.get();
     if (!k || !k->have) return isdf_fail(c, ISDF_ERR_STATE, "points merge: no kept clearance report (isdf_traj_check)");
     if (k->grid_epoch != c->grid_epoch || !c->have_geom)
         return isdf_fail(c, ISDF_ERR_STATE, "points merge: the kept clearance report is older than the occupancy grid (check again)");
@@ -100,9 +100,8 @@ extern "C" int isdf_points_merge_check(isdf_ctx *c, double below, isdf_points_me
     if (n_rows > 0 || M_before > 0) {
         DevBuf<unsigned long long> mask;
         DevBuf<int> count, base;
-        hipEvent_t ev[2];
-        for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
-        struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 2; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
+        DevEvents<2> ev;
+        ISDF_TRY(ev.ready(c));
         ISDF_TRY(c->d_merge_bits.reserve(c, n_words));
         DevBuf<unsigned> counters;
         HIPCHK(c, counters.alloc(CNT_WORDS));

@@ -81,9 +81,8 @@ struct TrajWatchState {
     DevBuf<double> d_xyz, d_val, d_ts, d_new_rows, d_rows_out;
     DevBuf<void> d_sort_tmp;
     TcReduceScratch red;
-    DevBuf<unsigned long long> d_rec; PinBuf<unsigned long long> h_rec;      // the hand-over record (traj_watch.hip)
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~TrajWatchState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    RecPair<unsigned long long> rec;        // the hand-over record's words (traj_watch.hip)
+    DevEvents<5> ev;
 };
 
 // the last clearance check's violating points (kept like the swept mesh is) and the host form's trajectory upload (traj_check.hip);

@@ -38,9 +38,8 @@ int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg
 }  // namespace
 
 int swept_field_scratch(isdf_ctx *c, SweptMeshState **out) {
-    if (!c->swm) c->swm = new SweptMeshState();
-    SweptMeshState *s = c->swm;
-    *out = s;
+    ISDF_TRY(c->swm.make(c, out));
+    SweptMeshState *s = *out;
     if (!s->d_stats) HIPCHK(c, s->d_stats.alloc(8));
     ISDF_TRY(s->h_overflow.reserve(c, 1));
     return s->field.reserve(c, (size_t)FIELD_CHUNK, false);
@@ -115,7 +114,7 @@ int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeff
                     double *d_value, double *d_tstar, hipStream_t st) {
     ISDF_TRY(swept_field_launch(c, N, d_T, d_coeffs, d_xyz, n, mode, d_value, d_tstar, st));
     if (n <= 0) return ISDF_OK;
-    SweptMeshState *s = c->swm;
+    SweptMeshState *s = c->swm.get();
     HIPCHK(c, hipMemcpyAsync(s->h_overflow, s->d_stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (*s->h_overflow.get()) return fail(c, ISDF_ERR_OVERFLOW, "swept-volume field: a point has more than 32 in-range intervals (results not valid)");
@@ -439,12 +438,6 @@ void traj_aabb(int N, const double *T, const double *C, double lo[3], double hi[
 
 }  // namespace
 
-void isdf_swept_release_all(isdf_ctx *c) {
-    if (!c->swm) return;
-    delete c->swm;
-    c->swm = nullptr;
-}
-
 extern "C" int isdf_swept_sdf_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n,
                                      int mode, double *d_value_out, double *d_tstar_out, void *stream) {
     if (!c) return ISDF_ERR_INVALID_ARG;
@@ -549,9 +542,8 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     HIPCHK(c, hipMemcpyAsync(s->d_traj + N, coeffs, (size_t)18 * N * sizeof(double), hipMemcpyHostToDevice, st));
     const double *d_T = s->d_traj, *d_C = s->d_traj + N;
 
-    hipEvent_t ev[3];
-    for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
-    struct EvFree { hipEvent_t *e; ~EvFree() { for (int k = 0; k < 3; k++) (void)hipEventDestroy(e[k]); } } ev_free{ev};
+    DevEvents<3> ev;
+    ISDF_TRY(ev.ready(c));
     DevBuf<double> f;
     HIPCHK(c, f.alloc((size_t)n_nodes));
     HIPCHK(c, hipMemsetAsync(f.get(), 0xFF, (size_t)n_nodes * sizeof(double), st));      // all-ones = NaN: not evaluated
@@ -646,7 +638,7 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
 extern "C" int isdf_swept_mesh_get(isdf_ctx *c, double *V_out, int capV, int32_t *F_out, int capF) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (!c->swm || !c->swm->have_mesh) return fail(c, ISDF_ERR_STATE, "swept mesh: nothing built (isdf_swept_mesh_build)");
-    SweptMeshState *s = c->swm;
+    SweptMeshState *s = c->swm.get();
     if (capV < s->nV || capF < s->nF) return fail(c, ISDF_ERR_OVERFLOW, "swept mesh: output capacity smaller than the mesh");
     if ((s->nV > 0 && !V_out) || (s->nF > 0 && !F_out)) return fail(c, ISDF_ERR_INVALID_ARG, "swept mesh: null output");
     HIPCHK(c, hipSetDevice(c->device));
@@ -657,7 +649,7 @@ extern "C" int isdf_swept_mesh_get(isdf_ctx *c, double *V_out, int capV, int32_t
 
 extern "C" int isdf_swept_mesh_release(isdf_ctx *c) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    if (c->swm) free_mesh_result(c->swm);
+    if (c->swm) free_mesh_result(c->swm.get());
     return ISDF_OK;
 }
 

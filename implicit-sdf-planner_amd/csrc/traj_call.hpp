@@ -37,21 +37,16 @@ inline int check_durations(isdf_ctx *c, long long n, const double *T, const char
 struct State {
     DevBuf<double> d_in, d_out;         // host forms: the call's inputs / its results (T | coeffs)
     std::vector<double> h_res;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~State() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-    int ready(isdf_ctx *c) {
-        for (auto &e : ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-        return ISDF_OK;
-    }
+    DevEvents<2> ev;
+    int ready(isdf_ctx *c) { return ev.ready(c); }
     double *host_words(size_t n) { if (h_res.size() < n) h_res.resize(n); return h_res.data(); }
 };
 
 // the ctx's device made current, the tool's state (`slot`: the ctx's pointer to it) created on first use, its events ready
-template <typename S> int state_of(isdf_ctx *c, S *&slot, S **out) {
+template <typename S> int state_of(isdf_ctx *c, Lazy<S> &slot, S **out) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!slot) slot = new S();
-    *out = slot;
-    return slot->ready(c);
+    ISDF_TRY(slot.make(c, out));
+    return (*out)->ready(c);
 }
 
 // n trajectories' pieces in all (nT = B N): T | coeffs into buf, which afterwards holds the durations at buf and the coefficients at buf + nT

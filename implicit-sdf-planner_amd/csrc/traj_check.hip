@@ -390,14 +390,13 @@ int select_run(isdf_ctx *c, SweptMeshState *s, int N, const double *d_T, const d
 // the check on device arrays; hT = the durations on the host.  d_piece_min: N doubles on the device (required).
 int check_run(isdf_ctx *c, int N, const double *d_T, const double *d_C, const int mode, const double margin,
               isdf_traj_check_info *info, double *d_piece_min, hipStream_t st) {
-    if (!c->tck) c->tck = new TrajCheckState();
-    TrajCheckState *k = c->tck;
+    TrajCheckState *k;
+    ISDF_TRY(c->tck.make(c, &k));
     free_rows(k);
     SweptMeshState *s;
     ISDF_TRY(swept_field_scratch(c, &s));
-    hipEvent_t ev[4];
-    for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
-    struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
+    DevEvents<4> ev;
+    ISDF_TRY(ev.ready(c));
     HIPCHK(c, hipEventRecord(ev[0], st));
 
     Selection L;
@@ -516,17 +515,11 @@ int traj_check_rerun_kept(isdf_ctx *c, isdf_traj_check_info *info) {
     return check_run(c, w.N, w.d_traj, w.d_traj + w.N, w.mode, w.margin, info, w.d_traj + 19 * (size_t)w.N, c->stream);
 }
 
-void traj_check_drop_report(isdf_ctx *c) { if (c->tck) free_rows(c->tck); }
+void traj_check_drop_report(isdf_ctx *c) { if (c->tck) free_rows(c->tck.get()); }
 
 int isdf_traj_check_ready(isdf_ctx *c) {
     double margin = 0.0;
     return check_state(c, nullptr, &margin);
-}
-
-void isdf_traj_check_release_all(isdf_ctx *c) {
-    if (!c->tck) return;
-    delete c->tck;
-    c->tck = nullptr;
 }
 
 extern "C" void isdf_traj_check_params_default(isdf_traj_check_params *p) {
@@ -562,8 +555,8 @@ extern "C" int isdf_traj_check(isdf_ctx *c, int N, const double *T, const double
     ISDF_TRY(swept_check_traj(c, N, T));
     for (int q = 0; q < 18 * N; q++) if (!std::isfinite(coeffs[q])) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: non-finite coefficient");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->tck) c->tck = new TrajCheckState();
-    TrajCheckState *k = c->tck;
+    TrajCheckState *k;
+    ISDF_TRY(c->tck.make(c, &k));
     hipStream_t st = c->stream;
     ISDF_TRY(k->d_traj.reserve(c, (size_t)20 * N));     // T | coeffs | per-piece minima
     ISDF_TRY(traj_call::upload(c, k->d_traj, (size_t)N, T, coeffs, st));        // (its own 19 N fit: the layout stays)
@@ -576,7 +569,7 @@ extern "C" int isdf_traj_check(isdf_ctx *c, int N, const double *T, const double
 extern "C" int isdf_traj_check_get(isdf_ctx *c, double *rows_out, long long capacity) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (!c->tck || !c->tck->have) return fail(c, ISDF_ERR_STATE, "trajectory check: nothing kept (isdf_traj_check)");
-    TrajCheckState *k = c->tck;
+    TrajCheckState *k = c->tck.get();
     if (capacity < k->n_rows) return fail(c, ISDF_ERR_OVERFLOW, "trajectory check: output capacity smaller than the number of points below the margin");
     if (k->n_rows > 0 && !rows_out) return fail(c, ISDF_ERR_INVALID_ARG, "trajectory check: null output");
     HIPCHK(c, hipSetDevice(c->device));
@@ -586,7 +579,7 @@ extern "C" int isdf_traj_check_get(isdf_ctx *c, double *rows_out, long long capa
 
 extern "C" int isdf_traj_check_release(isdf_ctx *c) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    if (c->tck) free_rows(c->tck);
+    if (c->tck) free_rows(c->tck.get());
     return ISDF_OK;
 }
 
@@ -603,9 +596,8 @@ namespace {
 int horizon_run(isdf_ctx *c, int N, const double *hT, const double *d_T, const double *d_C, int mode, double margin, isdf_traj_known_info *info, hipStream_t st) {
     SweptMeshState *s;
     ISDF_TRY(swept_field_scratch(c, &s));
-    hipEvent_t ev[4];
-    for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
-    struct EvFree { hipEvent_t *e; ~EvFree() { for (int q = 0; q < 4; q++) (void)hipEventDestroy(e[q]); } } ev_free{ev};
+    DevEvents<4> ev;
+    ISDF_TRY(ev.ready(c));
     HIPCHK(c, hipEventRecord(ev[0], st));
     Selection L;
     ISDF_TRY(select_run(c, s, N, d_T, d_C, mode, (const uint8_t *)c->known.d_bits.get(), true, "known horizon", L, st));

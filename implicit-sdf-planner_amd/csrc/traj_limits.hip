@@ -282,12 +282,6 @@ void isdf_traj_limits_unpack(const isdf_config &cfg, const isdf_traj_limits_para
     limits_unpack(cfg, p, words, info);
 }
 
-void isdf_traj_limits_release_all(isdf_ctx *c) {
-    if (!c->tlm) return;
-    delete c->tlm;
-    c->tlm = nullptr;
-}
-
 extern "C" void isdf_traj_limits_params_default(isdf_traj_limits_params *p) {
     if (!p) return;
     std::memset(p, 0, sizeof(*p));

@@ -263,12 +263,6 @@ int realloc_host_arrays(isdf_ctx *c, int B, int N, const double *heads, const do
 
 }  // namespace
 
-void isdf_traj_realloc_release_all(isdf_ctx *c) {
-    if (!c->tra) return;
-    delete c->tra;
-    c->tra = nullptr;
-}
-
 extern "C" void isdf_traj_realloc_params_default(isdf_traj_realloc_params *p) {
     if (p) isdf_host::ra_params_default(p);
 }

@@ -186,12 +186,6 @@ int retime_host_arrays(isdf_ctx *c, int B, int N, const double *T, const double 
 
 }  // namespace
 
-void isdf_traj_retime_release_all(isdf_ctx *c) {
-    if (!c->trt) return;
-    delete c->trt;
-    c->trt = nullptr;
-}
-
 extern "C" void isdf_traj_retime_params_default(isdf_traj_retime_params *p) {
     if (p) isdf_host::tr_params_default(p);
 }

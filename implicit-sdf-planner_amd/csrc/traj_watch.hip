@@ -81,11 +81,6 @@ __global__ __launch_bounds__(256) void tw_merge_rows_kernel(const double *__rest
     vox_out[pos] = id;
 }
 
-float event_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
-}
-
 void last_none(isdf_traj_watch_info &L) {
     L.new_min_clearance = 1e1; L.new_min_tstar = -1.0; L.new_min_voxel = -1; L.new_min_piece = -1;
 }
@@ -99,10 +94,9 @@ int fold_list(isdf_ctx *c, TrajCheckState *k, const MuVoxel *d_list, unsigned n)
     int rc;
     SweptMeshState *s;
     if ((rc = swept_field_scratch(c, &s))) return rc;
-    for (hipEvent_t &e : w.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    const size_t rec_words = (size_t)REC_PIECE + N;
+    if ((rc = w.ev.ready(c))) return rc;
     const long long na = k->n_rows;
-    if ((rc = w.d_rec.reserve(c, rec_words)) || (rc = w.h_rec.reserve(c, rec_words))) return rc;
+    if ((rc = w.rec.ready(c, (size_t)REC_PIECE + N))) return rc;
     if ((rc = w.d_key.reserve(c, n)) || (rc = w.d_vox.reserve(c, n)) || (rc = w.d_xyz.reserve(c, 3 * (size_t)n))) return rc;
     if ((rc = w.d_val.reserve(c, n)) || (rc = w.d_ts.reserve(c, n))) return rc;
     if ((rc = w.d_new_rows.reserve(c, 5 * (size_t)n)) || (rc = w.d_new_row_vox.reserve(c, n))) return rc;
@@ -117,10 +111,10 @@ int fold_list(isdf_ctx *c, TrajCheckState *k, const MuVoxel *d_list, unsigned n)
 
     // ---- select, order
     HIPCHK(c, hipEventRecord(w.ev[0], st));
-    HIPCHK(c, hipMemsetAsync(w.d_rec, 0, rec_words * sizeof(unsigned long long), st));
+    HIPCHK(c, w.rec.zero(st));
     if ((rc = swept_field_coarse_table(c, N, d_T, d_C, w.mode, st))) return rc;        // the arming check's doubles again
     hipLaunchKernelGGL(tw_select_kernel, dim3(blocks(n)), dim3(256), 0, st, B, d_list, n, (const double *)s->field.coarse_pose, (const int *)s->field.n_coarse,
-                       w.d_key.get(), w.d_rec.get() + REC_SEL);
+                       w.d_key.get(), w.rec.dev() + REC_SEL);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipcub::DeviceRadixSort::SortKeys(w.d_sort_tmp.get(), sort_bytes, (const long long *)w.d_key.get(), w.d_vox.get(), (int)n, 0, end_bit, st));
     hipLaunchKernelGGL(tw_xyz_kernel, dim3(blocks(n)), dim3(256), 0, st, B, (const long long *)w.d_vox.get(), n, w.d_xyz.get());
@@ -129,24 +123,24 @@ int fold_list(isdf_ctx *c, TrajCheckState *k, const MuVoxel *d_list, unsigned n)
 
     // ---- field
     if ((rc = swept_field_launch(c, N, d_T, d_C, w.d_xyz, n, w.mode, w.d_val, w.d_ts, st))) return rc;
-    HIPCHK(c, hipMemcpyAsync(w.d_rec.get() + REC_OVERFLOW, s->d_stats.get() + 4, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(w.rec.dev() + REC_OVERFLOW, s->d_stats.get() + 4, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
     HIPCHK(c, hipEventRecord(w.ev[2], st));
 
     // ---- reduce: the update's own report
-    if ((rc = tc_reduce_launch(c, w.red, n, w.d_val, w.d_ts, w.d_vox, w.d_xyz, d_T, N, w.margin, w.d_rec.get() + REC_COUNTS, (double *)(w.d_rec.get() + REC_REPORT),
-                               (double *)(w.d_rec.get() + REC_PIECE), st))) return rc;
+    if ((rc = tc_reduce_launch(c, w.red, n, w.d_val, w.d_ts, w.d_vox, w.d_xyz, d_T, N, w.margin, w.rec.dev() + REC_COUNTS, (double *)(w.rec.dev() + REC_REPORT),
+                               (double *)(w.rec.dev() + REC_PIECE), st))) return rc;
     if ((rc = tc_rows_launch(c, w.red, n, w.d_val, w.d_ts, w.d_vox, w.d_xyz, w.d_new_rows, w.d_new_row_vox, st))) return rc;
     HIPCHK(c, hipEventRecord(w.ev[3], st));
 
     // ---- merge the rows; the one hand-over
     hipLaunchKernelGGL(tw_merge_rows_kernel, dim3(blocks(na + n)), dim3(256), 0, st, (const double *)k->d_rows.get(), (const long long *)k->d_row_vox.get(), na,
-                       (const double *)w.d_new_rows.get(), (const long long *)w.d_new_row_vox.get(), (const unsigned long long *)(w.d_rec.get() + REC_COUNTS),
+                       (const double *)w.d_new_rows.get(), (const long long *)w.d_new_row_vox.get(), (const unsigned long long *)(w.rec.dev() + REC_COUNTS),
                        (long long)n, w.d_rows_out.get(), w.d_row_vox_out.get());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(w.ev[4], st));
-    HIPCHK(c, hipMemcpyAsync(w.h_rec.get(), w.d_rec, rec_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, w.rec.fetch(st));
     HIPCHK(c, hipStreamSynchronize(st));
-    const unsigned long long *R = w.h_rec.get();
+    const unsigned long long *R = &w.rec.host();
     if (R[REC_OVERFLOW]) return isdf_fail(c, ISDF_ERR_OVERFLOW, "clearance watch: a new voxel has more than 32 in-range intervals (the kept report is dropped)");
     if (R[REC_COUNTS + 1] > (unsigned long long)n) return isdf_fail(c, ISDF_ERR_HIP, "clearance watch: inconsistent hand-over record");
 
@@ -174,8 +168,8 @@ int fold_list(isdf_ctx *c, TrajCheckState *k, const MuVoxel *d_list, unsigned n)
     L.new_below_margin = b.n_below_margin; L.new_penetrating = b.n_penetrating;
     L.new_min_clearance = b.min_clearance; L.new_min_tstar = b.min_tstar; L.new_min_voxel = b.min_voxel; L.new_min_piece = b.min_piece;
     L.min_changed = min_changed;
-    L.select_ms = event_ms(w.ev[0], w.ev[1]); L.field_ms = event_ms(w.ev[1], w.ev[2]); L.reduce_ms = event_ms(w.ev[2], w.ev[3]);
-    L.merge_ms = event_ms(w.ev[3], w.ev[4]);
+    L.select_ms = w.ev.ms(0, 1); L.field_ms = w.ev.ms(1, 2); L.reduce_ms = w.ev.ms(2, 3);
+    L.merge_ms = w.ev.ms(3, 4);
     return ISDF_OK;
 }
 
@@ -210,7 +204,7 @@ bool traj_watch_armed(isdf_ctx *c) {
 }
 
 int traj_watch_fold(isdf_ctx *c, const void *d_list, unsigned n_new, unsigned cap) {
-    TrajCheckState *k = c->tck;
+    TrajCheckState *k = c->tck.get();
     if (n_new == 0) return ISDF_OK;
     const int rc = n_new <= cap ? fold_list(c, k, (const MuVoxel *)d_list, n_new) : fold_full(c, k, n_new);
     if (rc != ISDF_OK) {                // never half-merged: the report goes, the message stays

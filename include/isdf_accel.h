@@ -374,6 +374,8 @@ int isdf_host_info(const isdf_ctx *ctx, int64_t info_out[8]);
  * host memory (every ctx, every scratch and temporary; not the exchange's IPC mailbox, not the A* table).  Both return to
  * what they were once every ctx created since has been destroyed. */
 void isdf_debug_live_bytes(long long out[2]);
+/* ... and the HIP events the library holds at this moment, process-wide, under the same rule. */
+long long isdf_debug_live_events(void);
 
 /* Device-resident entry point, asynchronous on `stream` (a hipStream_t passed as void*; NULL = default
  * stream).  All trajectories have N pieces.  d_T: n_traj*N, d_coeffs: n_traj * (6N x 3 col-major),

@@ -1,6 +1,7 @@
-"""Buffer lifetime (csrc/dev_buf.hpp): every device and pinned byte the library takes while a ctx lives is given back when the ctx
-is destroyed.  The figures are isdf_debug_live_bytes - integers the library keeps itself about its own buffers - never the
-device's free memory, which other jobs on a shared card move."""
+"""Buffer, event and state lifetime (csrc/dev_buf.hpp, csrc/ctx_state.hpp): every device and pinned byte and every event the library
+takes while a ctx lives is given back when the ctx is destroyed, and every state a ctx creates on first use goes with it.  The
+figures are isdf_debug_live_bytes and isdf_debug_live_events - integers the library keeps itself about its own buffers and events -
+never the device's free memory, which other jobs on a shared card move."""
 import ctypes as C
 import gc
 
@@ -16,6 +17,11 @@ def _live(lib):
     out = (C.c_longlong * 2)()
     lib.isdf_debug_live_bytes(out)
     return int(out[0]), int(out[1])
+
+
+def _held(lib):
+    """(device bytes, pinned bytes), events"""
+    return _live(lib), int(lib.isdf_debug_live_events())
 
 
 def _ends(pkg, occ, res, N, seed):
@@ -39,6 +45,7 @@ def test_every_byte_comes_back(pkg, product_lib):
     pts = (np.argwhere(occ != 0) + 0.5) * res
     gc.collect()                                            # (engines other tests dropped go now, not in the middle of the count)
     before = _live(lib)
+    events_before = _held(lib)[1]
 
     # ---- V3 ctx, analytic robot: grid + ESDF generation, fused and batch steps, callback, ESDF samples, batch optimizer, front end
     a = pkg.Engine(synth.default_config(capi.V3_ESDF_TILE, kernel_size=9, integral_intervs=16, safety_hor=0.5))
@@ -96,6 +103,47 @@ def test_every_byte_comes_back(pkg, product_lib):
     m.set_shape(cone)
     m.eval_single(T6, C6)
 
-    for e in (m, v, a):
+    assert _held(lib)[1] > events_before, "a living multi-device ctx holds its hand-over events"
+
+    # ---- every state a ctx creates on first use, touched once - and once more, which must take nothing further: the in-place map
+    # changes, the ray cast, the depth camera, the known grid, the trajectory tools, the watch's fold, the cost-to-go field
+    w = pkg.Engine(synth.default_config(capi.V1_SWEPT, safety_hor=0.5))
+    ext = np.array(occ.shape) * res
+    assert tuple(w.set_pointcloud(pts, res, bmin=(0, 0, 0), bmax=ext)) == occ.shape
+    w.set_shape(cone)
+    w.frontend_build(capi.frontend_config(kernel_size=9))
+    w.map_known_enable(True)
+    w.map_known_merge_ms(True)                              # (the merge kernel's own pair of events)
+    free = (np.argwhere(occ == 0) + 0.5) * res
+    few, other = free[[100, 2000, 30000]], free[[500, 9000, 20000]]      # free voxels' centres: `few` for the map changes, `other` for the watch
+    origin = (2.1, 2.2, 2.3)
+    cam = pkg.engine.depth_camera(16, 12, 10.0, 10.0, 8.0, 6.0)
+    pose = np.hstack([np.eye(3), np.array(origin)[:, None]])
+    image, _ = w.depth_render(cam, pose, xyz=pts[:500])
+    head, tail, way, T0 = _ends(pkg, occ, res, 6, 70)
+    head, tail = np.concatenate([head[:, 0], np.zeros(6)]), np.concatenate([tail[:, 0], np.zeros(6)])
+    w.traj_check_set_watch(1)
+
+    def watch_fold():                                       # arms the watch, folds three new voxels, puts the map back (the clear re-checks)
+        w.traj_check(T6, C6, margin=1.0)
+        w.update_pointcloud(other)
+        w.clear_pointcloud(other)
+
+    touches = [("update_pointcloud", lambda: w.update_pointcloud(few)), ("clear_pointcloud", lambda: w.clear_pointcloud(few)),
+               ("integrate_scan", lambda: w.integrate_scan(origin, few)), ("map_raycast", lambda: w.map_raycast(origin, pts[:8])),
+               ("depth_render", lambda: w.depth_render(cam, pose, xyz=pts[:500])), ("depth_rays", lambda: w.depth_rays(cam, pose, image)),
+               ("map_known", w.map_known), ("map_frontier", w.map_frontier),
+               ("traj_limits", lambda: w.traj_limits(T6, C6)), ("traj_retime", lambda: w.traj_retime(T6, C6)),
+               ("traj_realloc", lambda: w.traj_realloc(head, tail, way, T0)), ("watch fold", watch_fold),
+               ("frontend_field_build", lambda: w.frontend_field_build((3.0, 3.0, 3.0))), ("shift_map", lambda: w.shift_map((1, 0, 0)))]
+    events_idle = _held(lib)[1]
+    for what, touch in touches:
+        touch()
+        once = _held(lib)
+        touch()
+        assert _held(lib) == once, f"{what}: a second identical call took bytes or events ((device, pinned), events)"
+    assert _held(lib)[1] > events_idle, "the states keep their events while the ctx lives"
+
+    for e in (w, m, v, a):
         e.close()
-    assert _live(lib) == before, "bytes still held after isdf_destroy (device, pinned)"
+    assert _held(lib) == (before, events_before), "bytes or events still held after isdf_destroy ((device, pinned), events)"
