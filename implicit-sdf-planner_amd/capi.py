@@ -195,6 +195,20 @@ class IsdfTrajKnownInfo(C.Structure):
                 ("field_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+class IsdfViewGainParams(C.Structure):
+    """isdf_view_gain_params (include/isdf_accel.h)."""
+    _fields_ = [("stride_u", C.c_int32), ("stride_v", C.c_int32), ("max_range_m", C.c_double), ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class IsdfViewGainInfo(C.Structure):
+    """isdf_view_gain_info (include/isdf_accel.h)."""
+    _fields_ = [("n_views", C.c_int64), ("n_scored", C.c_int64), ("n_rays_per_view", C.c_int64), ("best_view", C.c_int64), ("best_gain", C.c_int64),
+                ("gain_total", C.c_int64), ("chunks", C.c_int32), ("reserved", C.c_int32), ("gain_ms", C.c_double)]
+
+
+VIEW_GAIN_ROW = 8                       # int64 per view: status, gain, n_rays, n_skipped, n_hits, steps_total, n_rays_unknown, 0
+
+
 class IsdfMapScanParams(C.Structure):
     """isdf_map_scan_params (include/isdf_accel.h)."""
     _fields_ = [("miss_weight", C.c_int32), ("reserved", C.c_int32), ("clear", IsdfMapClearParams), ("update", IsdfMapUpdateParams)]
@@ -425,6 +439,7 @@ EXPORTED_SYMBOLS = [
     "isdf_map_known_sizes", "isdf_map_known_enable", "isdf_map_known_fill", "isdf_map_known_merge_ms", "isdf_map_known_get", "isdf_map_frontier",
     "isdf_traj_known_params_default", "isdf_traj_known_horizon", "isdf_traj_known_horizon_device",
     "isdf_known_merge_host", "isdf_known_shift_host", "isdf_known_fill_host", "isdf_known_frontier_host",
+    "isdf_view_gain_params_default", "isdf_view_gain_sizes", "isdf_view_gain", "isdf_view_gain_device", "isdf_view_gain_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -769,6 +784,19 @@ def load_library(path=None):
     mirror = [C.sizeof(IsdfMapKnownInfo), C.sizeof(IsdfMapFrontierInfo), C.sizeof(IsdfTrajKnownParams), C.sizeof(IsdfTrajKnownInfo)]
     if list(sz4) != mirror:
         raise RuntimeError(f"isdf_map_known structs: the library has {list(sz4)}, the mirror {mirror}")
+    vp, vi = C.POINTER(IsdfViewGainParams), C.POINTER(IsdfViewGainInfo)
+    lib.isdf_view_gain_params_default.argtypes = [vp]
+    lib.isdf_view_gain_params_default.restype = None
+    lib.isdf_view_gain_sizes.argtypes = [ip]
+    lib.isdf_view_gain_sizes.restype = None
+    lib.isdf_view_gain.argtypes = [C.c_void_p, C.POINTER(IsdfDepthCamera), dp, C.c_longlong, vp, C.c_void_p, vi]
+    lib.isdf_view_gain_device.argtypes = [C.c_void_p, C.POINTER(IsdfDepthCamera), C.c_void_p, C.c_longlong, vp, C.c_void_p, vi, C.c_void_p]
+    lib.isdf_view_gain_host.argtypes = [C.c_void_p, C.c_void_p, dp, dp, C.c_double, i3, C.POINTER(IsdfDepthCamera), dp, C.c_longlong, vp, C.c_void_p, vi]
+    lib.isdf_view_gain_host.restype = C.c_longlong
+    lib.isdf_view_gain_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfViewGainParams), C.sizeof(IsdfViewGainInfo)]:
+        raise RuntimeError(f"isdf_view_gain structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfViewGainParams), C.sizeof(IsdfViewGainInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

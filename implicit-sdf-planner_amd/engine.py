@@ -719,6 +719,59 @@ def depth_rays_host(cam, cam2world, image, bmin, bmax, res, dims, lib=None, **pa
     return ends, hit, info
 
 
+def look_at(eye, target, up=(0, 0, 1)):
+    """The cam2world (12 doubles, rows (R | t)) of a camera at `eye` whose optical axis z points at `target`, x to the right and y down;
+    `up` is the world's up (an axis parallel to it takes the world's x, or y, instead)."""
+    eye, target, up = (np.asarray(v, dtype=np.float64).reshape(3) for v in (eye, target, up))
+    z = target - eye
+    z = z / np.linalg.norm(z)
+    for ref in (up, np.array([1.0, 0.0, 0.0]), np.array([0.0, 1.0, 0.0])):
+        x = np.cross(z, ref)
+        if np.linalg.norm(x) > 1e-9:
+            break
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)                  # z forward, x right: y = z x x points down when `up` is up
+    return np.ascontiguousarray(np.column_stack([x, y, z, eye]).reshape(12))
+
+
+def _view_gain_params(lib, stride=None, max_range_m=None, scratch_bytes=None):
+    p = capi.IsdfViewGainParams()
+    lib.isdf_view_gain_params_default(C.byref(p))
+    if stride is not None:
+        p.stride_u, p.stride_v = (int(stride), int(stride)) if np.isscalar(stride) else (int(stride[0]), int(stride[1]))
+    if max_range_m is not None:
+        p.max_range_m = float(max_range_m)
+    if scratch_bytes is not None:
+        p.scratch_bytes = int(scratch_bytes)
+    return p
+
+
+def _view_poses(poses):
+    return np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 12))
+
+
+def view_gain_host(bits, occ, bmin, bmax, res, cam, poses, lib=None, **params):
+    """isdf_view_gain_host: per candidate pose (poses n x 12 doubles, look_at's), the unknown voxels - K = bits, a known grid's words over
+    occ [X, Y, Z] - the depth camera would see through the map (bmin, bmax, res), in plain host code.  params: stride (one number or
+    (u, v)), max_range_m.  Returns (rows int64 [n, 8] = (status, gain, n_rays, n_skipped, n_hits, steps_total, n_rays_unknown, 0),
+    IsdfViewGainInfo - best_view -1: none scored)."""
+    lib = lib or capi.load_library()
+    o8 = np.ascontiguousarray(occ, dtype=np.uint8)
+    w, d = _known_args(bits, o8.shape)
+    b0, b1, _, _ = _scan_geometry(bmin, bmax, o8.shape, np.zeros(3))
+    P = _view_poses(poses)
+    p = _view_gain_params(lib, **params)
+    rows = np.zeros((P.shape[0], capi.VIEW_GAIN_ROW), dtype=np.int64)
+    info = capi.IsdfViewGainInfo()
+    info.n_views = -1                   # a refused call leaves the info alone: that tells its -1 from "no view scored"
+    rc = lib.isdf_view_gain_host(w.ctypes.data_as(C.c_void_p), o8.ctypes.data_as(C.c_void_p), _p(b0), _p(b1), float(res), d, C.byref(cam), _p(P), P.shape[0], C.byref(p),
+                                 rows.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc < 0 and info.n_views < 0:
+        raise IsdfError(int(rc), "isdf_view_gain_host")
+    assert rc == info.best_view
+    return rows, info
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -1195,6 +1248,33 @@ class Engine:
         info = capi.IsdfTrajKnownInfo()
         self._check(self.lib.isdf_traj_known_horizon_device(self.h, N, C.c_void_p(d_T), C.c_void_p(d_coeffs), C.byref(p), C.byref(info), C.c_void_p(stream)))
         return self._traj_known_report(info)
+
+    # ---- the view gain (csrc/view_gain.hip)
+    def view_gain(self, cam, poses, **params):
+        """isdf_view_gain: per candidate pose (poses n x 12 doubles, look_at's), the voxels unknown today that the depth camera would see
+        from there, on the device, read-only.  params: stride (one number or (u, v)), max_range_m, scratch_bytes.  Returns (rows int64
+        [n, 8] = (status, gain, n_rays, n_skipped, n_hits, steps_total, n_rays_unknown, 0), IsdfViewGainInfo)."""
+        P = _view_poses(poses)
+        p = _view_gain_params(self.lib, **params)
+        rows = np.zeros((P.shape[0], capi.VIEW_GAIN_ROW), dtype=np.int64)
+        info = capi.IsdfViewGainInfo()
+        self._check(self.lib.isdf_view_gain(self.h, C.byref(cam), _p(P), P.shape[0], C.byref(p), rows.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return rows, info
+
+    def view_gain_device(self, cam, d_poses, d_rows, want_info=True, stream=None, **params):
+        """isdf_view_gain_device: d_poses (float64 [n, 12]) and d_rows (int64 [n, 8]) are torch tensors on the ctx's device; the work goes
+        on `stream` (None: torch's current stream).  want_info False: info_out = NULL - nothing is handed over and nothing synchronised;
+        returns None then."""
+        import torch
+        n = int(d_poses.shape[0])
+        assert d_poses.dtype == torch.float64 and d_poses.is_contiguous() and tuple(d_poses.shape) == (n, 12)
+        assert d_rows.dtype == torch.int64 and d_rows.is_contiguous() and tuple(d_rows.shape) == (n, capi.VIEW_GAIN_ROW)
+        p = _view_gain_params(self.lib, **params)
+        info = capi.IsdfViewGainInfo() if want_info else None
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        self._check(self.lib.isdf_view_gain_device(self.h, C.byref(cam), C.c_void_p(d_poses.data_ptr()), n, C.byref(p), C.c_void_p(d_rows.data_ptr()),
+                                                   None if info is None else C.byref(info), C.c_void_p(st)))
+        return info
 
     def map_counts(self):
         """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""

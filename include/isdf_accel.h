@@ -1827,6 +1827,72 @@ long long isdf_known_fill_host(uint32_t *bits_inout, const int32_t dims[3], cons
 int isdf_known_frontier_host(const uint32_t *bits, const uint8_t *occ, const int32_t dims[3], uint32_t *bits_out, int64_t *vox_out, long long capacity,
                              isdf_map_frontier_info *info_out);
 
+/* ---- the view gain: the unknown voxels a depth camera would see, per candidate pose ------------------------------- */
+/* What a next-best-view loop maximises: for each of n_views candidate poses, the number of voxels that are unknown today (K = 0) and
+ * that the camera would observe from there, given the map as it stands.  One launch over views x rays; one row per view comes back.
+ * The definition is integers only from a ray's end point on, so isdf_view_gain_host and the device agree byte for byte.
+ * poses: n_views x 12 doubles, each a cam2world as the depth camera takes it (rows (R | t), z the optical axis).  For view j:
+ *   RAYS.  nu = ceil(width / stride_u), nv = ceil(height / stride_v); ray k = iv * nu + iu is pixel (u, v) = (iu stride_u, iv stride_v).
+ *   Its end point and the row order are exactly what isdf_depth_rays_host gives for an image with no return at any pixel with
+ *   no_return_is_free = 1, min_range_m = 0, these strides and max_range_m, and the ctx's map geometry.  In fp64, nothing contracted into
+ *   an FMA: p = ((u - cx) * 1 / fx, (v - cy) * 1 / fy, 1); e = R p + t, each row summed left to right; d = e - t; range = sqrt(d_x^2 +
+ *   d_y^2 + d_z^2); k = max_range_m / range; e_a = t_a + d_a * k, d_a = e_a - t_a.  The clip, with lo = bmin + resolution / 2, hi = bmax -
+ *   resolution / 2: over the axes a with e_a < lo_a (bound = lo_a) or e_a > hi_a (bound = hi_a), s = the smallest of (bound - t_a) / d_a
+ *   (0 where d_a = 0); if there is such an axis, s is held to [0, 1] and e_a = t_a + d_a * s.  Then e is rounded to float32 once.  The
+ *   origin is t.  A ray whose e has a component that is not finite, or whose e (as doubles again) lies outside the map by the scan's test
+ *   (a coordinate < bmin or > bmax), is SKIPPED (n_skipped).
+ *   WALK.  Origin and end are quantised as the scan's rays are (isdf_integrate_scan above: q = floor((p - bmin) / resolution * 1024)
+ *   clamped to dim * 1024 - 1) and walked as isdf_map_raycast walks them with test_origin_voxel = 0: voxel 0 is not tested; the walk ends
+ *   at the first voxel after it whose occupancy byte is not 0, or at the end point's voxel.  V(ray) = every voxel of the walk from voxel 0
+ *   up to and including the one where it ended.  Unknown voxels are transparent - the occupancy byte alone decides: the optimistic gain.
+ *   GAIN.  S_j = the union of V(ray) over the rays that were not skipped: a set per view, not a sum per ray (the voxel at the camera,
+ *   which every ray crosses, counts once).  gain_j = the number of v in S_j with K[v] = 0.
+ * rows_out: n_views x 8 int64, {status, gain, n_rays, n_skipped, n_hits, steps_total, n_rays_unknown, 0}.  status 0: scored.  status 1:
+ * the pose has an entry that is not finite, or its origin lies outside the map by the scan's test - every other word of the row is 0;
+ * never an error of the call, candidates come from anywhere.  n_rays = nu nv; n_hits: walks ended by an occupied voxel; steps_total: the
+ * sum of the walks' step counts as isdf_map_raycast_info counts them; n_rays_unknown: rays whose V holds at least one unknown voxel.
+ * Every word is an integer sum or a set size: nothing depends on the order of the device's atomics.
+ * The call is read-only: K, the occupancy, epochs, a kept field, an armed watch and a kept report are untouched.  The device keeps one
+ * `seen` bit grid in K's layout per view of a chunk: views_per_chunk = scratch_bytes / (4 * words of K) held to [1, n_views]; the chunks
+ * run in turn on the stream, the bytes of the rows do not depend on their size.  The scratch grows only: a second call of a size
+ * allocates nothing.
+ * Errors, all before anything is launched: ISDF_ERR_INVALID_ARG for a bad camera (the depth camera's rule), a stride < 1, a max_range_m
+ * that is not finite or <= 0, scratch_bytes < 0, n_views < 0, a null poses or rows_out with n_views > 0; ISDF_ERR_UNSUPPORTED on a
+ * multi-device ctx; ISDF_ERR_STATE without a known grid or without an occupancy grid.  n_views = 0 is legal; params and info_out may be
+ * NULL.  isdf_view_gain_device: d_poses and d_rows_out are device memory, the work goes on `stream`; with info_out == NULL nothing is
+ * handed over and nothing synchronised, with it `stream` is synchronised once - isdf_map_raycast_device's rule.
+ * Not offered: a pessimistic gain in which unknown voxels block; a range- or angle-weighted gain; candidate generation or clustering of
+ * the frontier; a gain kept incrementally across scans. */
+typedef struct isdf_view_gain_params {
+    int32_t stride_u, stride_v;   /* default 4, 4; >= 1 */
+    double  max_range_m;          /* required: finite, > 0 (default 5.0) */
+    int64_t scratch_bytes;        /* default 64 MiB; >= 0; 0 = one view per chunk */
+    int32_t reserved[4];
+} isdf_view_gain_params;
+
+typedef struct isdf_view_gain_info {
+    int64_t n_views, n_scored, n_rays_per_view;
+    int64_t best_view;            /* lowest index among the largest gains of status-0 rows; -1: none */
+    int64_t best_gain;
+    int64_t gain_total;
+    int32_t chunks, reserved;
+    double  gain_ms;              /* device time, events on the stream */
+} isdf_view_gain_info;
+
+void isdf_view_gain_params_default(isdf_view_gain_params *p);   /* null-safe */
+void isdf_view_gain_sizes(int sizes_out[2]);                    /* null-safe */
+int isdf_view_gain(isdf_ctx *ctx, const isdf_depth_camera *camera, const double *poses, long long n_views, const isdf_view_gain_params *params,
+                   int64_t *rows_out, isdf_view_gain_info *info_out);
+int isdf_view_gain_device(isdf_ctx *ctx, const isdf_depth_camera *camera, const double *d_poses, long long n_views, const isdf_view_gain_params *params,
+                          int64_t *d_rows_out, isdf_view_gain_info *info_out, void *stream);
+/* plain host code, no ctx, no device: bits = K's words, occ = nx ny nz occupancy bytes, the map's geometry as isdf_raycast_host takes it;
+ * scratch_bytes is ignored.  Returns best_view, -1 when no view was scored, or a negative isdf_status (ISDF_ERR_INVALID_ARG: a null
+ * array, a bad geometry, the bad arguments above; rows_out untouched).  info_out (nullable) is filled by a call that was not refused
+ * (chunks 0, gain_ms 0) and left alone by one that was: that tells the two meanings of -1 apart. */
+long long isdf_view_gain_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
+                              const isdf_depth_camera *camera, const double *poses, long long n_views, const isdf_view_gain_params *params, int64_t *rows_out,
+                              isdf_view_gain_info *info_out);
+
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
  * the shipped src/plan_manager/map_pcds are "FIELDS x y z / DATA ascii"): xyz_out = up to `capacity` points x 3 floats (may be
