@@ -141,6 +141,7 @@ __global__ __launch_bounds__(256) void gather_scan_kernel(unsigned *chunk_cnt, i
 __global__ __launch_bounds__(64) void gather_emit_kernel(DevGrid G, const unsigned *__restrict__ marks, size_t n_words,
                                                          const unsigned *__restrict__ chunk_off, double *__restrict__ pts, unsigned cap) {
     // one wave per chunk: words in ascending order -> points sorted by (ix, iy, iz)
+#pragma clang fp contract(off)      // a centre is a rounded product plus the origin (Gridmap3D.cpp:189-193): one FMA differs by an ulp when the origin is not 0
     const size_t base = (size_t)blockIdx.x * GATHER_CHUNK;
     unsigned off = chunk_off[blockIdx.x];
     const int lane = threadIdx.x;
