@@ -409,7 +409,7 @@ EXPORTED_SYMBOLS = [
     "isdf_xchg_create", "isdf_xchg_connect", "isdf_xchg_allreduce", "isdf_xchg_fuse", "isdf_xchg_status", "isdf_xchg_destroy",
     "isdf_xchg_timeout_ms", "isdf_xchg_set_timeout_ms", "isdf_lbfgs_minimize_progress", "isdf_set_progress", "isdf_mesh_info",
     "isdf_swept_sdf", "isdf_swept_sdf_device", "isdf_swept_mesh_params_default", "isdf_swept_mesh_build", "isdf_swept_mesh_get",
-    "isdf_swept_mesh_release", "isdf_write_obj", "isdf_traj_check_params_default", "isdf_traj_check", "isdf_traj_check_device",
+    "isdf_swept_mesh_release", "isdf_lattice_mesh_build", "isdf_write_obj", "isdf_traj_check_params_default", "isdf_traj_check", "isdf_traj_check_device",
     "isdf_traj_check_get", "isdf_traj_check_release", "isdf_traj_collide",
     "isdf_traj_check_set_watch", "isdf_traj_check_watch_info", "isdf_traj_check_watch_sizes", "isdf_traj_check_fold_host",
     "isdf_points_merge_check", "isdf_refine_params_default", "isdf_optimize_lbfgs_checked",
@@ -597,6 +597,7 @@ def load_library(path=None):
     lib.isdf_swept_mesh_build.argtypes = [C.c_void_p, C.c_int, dp, dp, C.POINTER(IsdfSweptMeshParams), C.POINTER(IsdfSweptMeshInfo)]
     lib.isdf_swept_mesh_get.argtypes = [C.c_void_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
     lib.isdf_swept_mesh_release.argtypes = [C.c_void_p]
+    lib.isdf_lattice_mesh_build.argtypes = [C.c_void_p, C.POINTER(C.c_int32), dp, C.c_double, C.c_double, dp, C.POINTER(IsdfSweptMeshInfo)]
     lib.isdf_write_obj.argtypes = [C.c_char_p, dp, C.c_int, C.POINTER(C.c_int32), C.c_int]
     lib.isdf_traj_check_params_default.argtypes = [C.POINTER(IsdfTrajCheckParams)]
     lib.isdf_traj_check_params_default.restype = None

@@ -10,7 +10,7 @@
 // around its main diagonal, the same in every cell, so neighbouring cells agree on every face (crack-free, no ambiguity tables).
 //   narrow band  the field on every B-th node first; a coarse cell is refined when its corners change sign about iso, or when none
 //                of them lies farther than L * sqrt(3) * B * eps from it (a corner that does proves the whole cell's side for an
-//                L-Lipschitz field); the fine nodes of the refined cells are flagged (a gather per node: each once), compacted and
+//                L-Lipschitz field; a corner that reads 10, no interval, counts as 2 safety_hor + 0.1); the fine nodes of the refined cells are flagged (a gather per node: each once), compacted and
 //                evaluated in one batch.
 //   extraction   cells whose eight corners are known: triangles per cell (count, exclusive scan, emit); a vertex per sign-changing
 //                lattice edge (7 per node: +x +y +z +xy +xz +yz +xyz) that lies in such a cell, numbered by ascending global edge
@@ -133,8 +133,10 @@ __device__ __forceinline__ void node_ijk(const Lattice &L, long long id, int &i,
 }
 __device__ __forceinline__ long long node_id(const Lattice &L, int i, int j, int k) { return ((long long)i * L.ny + j) * L.nz + k; }
 
-// xyz of the nodes [first, first + n) of a list (ids) or of the lattice itself (ids == null)
+// xyz of the nodes [first, first + n) of a list (ids) or of the lattice itself (ids == null): origin + i * eps, the product and the
+// sum each rounded on its own (no contraction into an fma)
 __global__ void node_xyz_kernel(Lattice L, const int *ids, long long first, int n, double *xyz) {
+#pragma clang fp contract(off)
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     const long long id = ids ? (long long)ids[first + t] : first + t;
@@ -160,8 +162,9 @@ __global__ void coarse_ids_kernel(Lattice L, Coarse Q, int *ids) {
 }
 // refine[coarse cell] = its corners change sign about iso, or none of them lies farther than thr = L sqrt(3) B eps from it.  A corner
 // c with |f(c) - iso| > thr proves the whole cell: every point of it is within the cell's diagonal of c, so an L-Lipschitz f keeps
-// the side of iso that c is on.
-__global__ void refine_kernel(Lattice L, Coarse Q, const double *f, double iso, double thr, unsigned char *refine) {
+// the side of iso that c is on.  A corner that found no qualifying interval reads the constant 10, which is no distance: all it
+// proves is that the corner is not within the qualification radius unq = 2 safety_hor + 0.1, so it counts as the value unq.
+__global__ void refine_kernel(Lattice L, Coarse Q, const double *f, double iso, double thr, double unq, unsigned char *refine) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int ex = Q.cx - 1, ey = Q.cy - 1, ez = Q.cz - 1;
     if (t >= (long long)ex * ey * ez) return;
@@ -171,7 +174,7 @@ __global__ void refine_kernel(Lattice L, Coarse Q, const double *f, double iso, 
         const double v = f[node_id(L, coarse_coord(ci + (c & 1), Q.B, L.nx), coarse_coord(cj + ((c >> 1) & 1), Q.B, L.ny),
                                    coarse_coord(ck + ((c >> 2) & 1), Q.B, L.nz))];
         if (v < iso) any_in = true; else any_out = true;
-        if (!(fabs(v - iso) <= thr)) far = true;
+        if (!(fabs((v == 1e1 ? unq : v) - iso) <= thr)) far = true;
     }
     refine[t] = (any_in && any_out) || !far ? 1 : 0;
 }
@@ -333,8 +336,10 @@ __global__ void vertex_count_kernel(Lattice L, const double *f, const unsigned c
     if ((threadIdx.x & 63) == 0) { if (v_sum) atomicAdd(&stats[2], v_sum); if (u_sum) atomicAdd(&stats[3], u_sum); }
 }
 
-// vertex positions: linear interpolation of the two node values along the edge, from its lower node
+// vertex positions: linear interpolation of the two node values along the edge, from its lower node - node + t * (d * eps) with
+// t = (iso - f0) / (f1 - f0), every operation rounded on its own (no contraction into an fma)
 __global__ void vertex_emit_kernel(Lattice L, const double *f, double iso, const unsigned char *mask, const int *vbase, double *V) {
+#pragma clang fp contract(off)
     const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= (long long)L.nx * L.ny * L.nz) return;
     const unsigned m = mask[id];
@@ -436,6 +441,39 @@ void traj_aabb(int N, const double *T, const double *C, double lo[3], double hi[
     }
 }
 
+// ---- extraction: count, scan, emit.  The mesh of the field f (device, NaN = node not evaluated) on lattice L into s->d_V / s->d_F,
+// asynchronous on `st` after the counters' read-back; cnt = known cells, triangles, vertices, unqualified edges.  The caller
+// synchronises and then takes the mesh as kept (nV, nF, have_mesh).
+int extract_mesh(isdf_ctx *c, SweptMeshState *s, const Lattice &L, const double *f, double iso, hipStream_t st, unsigned long long cnt[4]) {
+    const long long n_nodes = (long long)L.nx * L.ny * L.nz;
+    const long long n_cells = (long long)(L.nx - 1) * (L.ny - 1) * (L.nz - 1);
+    DevBuf<unsigned char> known, mask;
+    DevBuf<int> tcount, tbase, vcount, vbase;
+    DevBuf<unsigned long long> d_cnt;
+    HIPCHK(c, known.alloc((size_t)n_cells)); HIPCHK(c, tcount.alloc((size_t)n_cells)); HIPCHK(c, tbase.alloc((size_t)n_cells));
+    HIPCHK(c, mask.alloc((size_t)n_nodes)); HIPCHK(c, vcount.alloc((size_t)n_nodes)); HIPCHK(c, vbase.alloc((size_t)n_nodes));
+    HIPCHK(c, d_cnt.alloc(4));
+    HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(cell_count_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, f, iso, known.get(), tcount.get(), d_cnt.get());
+    hipLaunchKernelGGL(vertex_count_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, f, (const unsigned char *)known.get(),
+                       iso, mask.get(), vcount.get(), d_cnt.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (cnt[1] > (unsigned long long)INT32_MAX / 3 || cnt[2] > (unsigned long long)INT32_MAX / 3)
+        return fail(c, ISDF_ERR_OVERFLOW, "swept mesh: more than 2^31 / 3 vertices or triangles");
+    ISDF_TRY(exclusive_sum(c, tcount.get(), tbase.get(), n_cells, st));
+    ISDF_TRY(exclusive_sum(c, vcount.get(), vbase.get(), n_nodes, st));
+    HIPCHK(c, s->d_V.alloc((size_t)(cnt[2] ? cnt[2] : 1) * 3));
+    HIPCHK(c, s->d_F.alloc((size_t)(cnt[1] ? cnt[1] : 1) * 3));
+    hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, f, iso,
+                       (const unsigned char *)mask.get(), (const int *)vbase.get(), s->d_V);
+    hipLaunchKernelGGL(tri_emit_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, f, iso,
+                       (const unsigned char *)known.get(), (const int *)tbase.get(), (const unsigned char *)mask.get(), (const int *)vbase.get(), s->d_F);
+    HIPCHK(c, hipGetLastError());
+    return ISDF_OK;
+}
+
 }  // namespace
 
 extern "C" int isdf_swept_sdf_device(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n,
@@ -534,7 +572,6 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     L.nx = (int)dims[0]; L.ny = (int)dims[1]; L.nz = (int)dims[2];
     L.ox = org[0]; L.oy = org[1]; L.oz = org[2]; L.eps = eps;
     const long long n_nodes = dims[0] * dims[1] * dims[2];
-    const long long n_cells = (dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1);
 
     // ---- the trajectory on the device
     ISDF_TRY(s->d_traj.reserve(c, (size_t)19 * N));
@@ -567,7 +604,8 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
         HIPCHK(c, refine.alloc((size_t)n_ccells));
         HIPCHK(c, flag.alloc((size_t)n_nodes));
         const double thr = p->lipschitz * std::sqrt(3.0) * B * eps;
-        hipLaunchKernelGGL(refine_kernel, dim3(blocks(n_ccells)), dim3(256), 0, st, L, Q, f.get(), p->iso, thr, refine.get());
+        const double unq = 2 * c->cfg.safety_hor + 0.1;
+        hipLaunchKernelGGL(refine_kernel, dim3(blocks(n_ccells)), dim3(256), 0, st, L, Q, f.get(), p->iso, thr, unq, refine.get());
         hipLaunchKernelGGL(flag_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, Q, refine.get(), flag.get());
         DevBuf<int> fids, d_nsel;
         HIPCHK(c, fids.alloc((size_t)n_nodes));
@@ -588,32 +626,8 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
     }
     HIPCHK(c, hipEventRecord(ev[1], st));
 
-    // ---- extraction: count, scan, emit
-    DevBuf<unsigned char> known, mask;
-    DevBuf<int> tcount, tbase, vcount, vbase;
-    DevBuf<unsigned long long> d_cnt;
-    HIPCHK(c, known.alloc((size_t)n_cells)); HIPCHK(c, tcount.alloc((size_t)n_cells)); HIPCHK(c, tbase.alloc((size_t)n_cells));
-    HIPCHK(c, mask.alloc((size_t)n_nodes)); HIPCHK(c, vcount.alloc((size_t)n_nodes)); HIPCHK(c, vbase.alloc((size_t)n_nodes));
-    HIPCHK(c, d_cnt.alloc(4));
-    HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(cell_count_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, (const double *)f.get(), p->iso, known.get(), tcount.get(), d_cnt.get());
-    hipLaunchKernelGGL(vertex_count_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, (const double *)f.get(), (const unsigned char *)known.get(),
-                       p->iso, mask.get(), vcount.get(), d_cnt.get());
-    HIPCHK(c, hipGetLastError());
     unsigned long long cnt[4];
-    HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (cnt[1] > (unsigned long long)INT32_MAX / 3 || cnt[2] > (unsigned long long)INT32_MAX / 3)
-        return fail(c, ISDF_ERR_OVERFLOW, "swept mesh: more than 2^31 / 3 vertices or triangles");
-    ISDF_TRY(exclusive_sum(c, tcount.get(), tbase.get(), n_cells, st));
-    ISDF_TRY(exclusive_sum(c, vcount.get(), vbase.get(), n_nodes, st));
-    HIPCHK(c, s->d_V.alloc((size_t)(cnt[2] ? cnt[2] : 1) * 3));
-    HIPCHK(c, s->d_F.alloc((size_t)(cnt[1] ? cnt[1] : 1) * 3));
-    hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, (const double *)f.get(), p->iso,
-                       (const unsigned char *)mask.get(), (const int *)vbase.get(), s->d_V);
-    hipLaunchKernelGGL(tri_emit_kernel, dim3(blocks(n_cells)), dim3(256), 0, st, L, (const double *)f.get(), p->iso,
-                       (const unsigned char *)known.get(), (const int *)tbase.get(), (const unsigned char *)mask.get(), (const int *)vbase.get(), s->d_F);
-    HIPCHK(c, hipGetLastError());
+    ISDF_TRY(extract_mesh(c, s, L, f.get(), p->iso, st, cnt));
     HIPCHK(c, hipEventRecord(ev[2], st));
     HIPCHK(c, hipStreamSynchronize(st));
     s->nV = (long long)cnt[2]; s->nF = (long long)cnt[1]; s->have_mesh = true;
@@ -631,6 +645,53 @@ extern "C" int isdf_swept_mesh_build(isdf_ctx *c, int N, const double *T, const 
         HIPCHK(c, hipEventElapsedTime(&ms0, ev[0], ev[1]));
         HIPCHK(c, hipEventElapsedTime(&ms1, ev[1], ev[2]));
         info_out->field_ms = ms0; info_out->mesh_ms = ms1;
+    }
+    return ISDF_OK;
+}
+
+extern "C" int isdf_lattice_mesh_build(isdf_ctx *c, const int32_t dims[3], const double origin[3], double eps, double iso, const double *f,
+                                       isdf_swept_mesh_info *info_out) {
+    // (arguments first, as in isdf_swept_mesh_build)
+    if (!dims || !origin || !f) return fail(c, ISDF_ERR_INVALID_ARG, "lattice mesh: null dims, origin or field");
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(c, ISDF_ERR_INVALID_ARG, "lattice mesh: eps must be finite and > 0");
+    if (!std::isfinite(iso)) return fail(c, ISDF_ERR_INVALID_ARG, "lattice mesh: iso must be finite");
+    long long n_nodes = 1;
+    for (int a = 0; a < 3; a++) {
+        if (dims[a] < 2) return fail(c, ISDF_ERR_INVALID_ARG, "lattice mesh: dims must be >= 2 per axis");
+        if (!std::isfinite(origin[a])) return fail(c, ISDF_ERR_INVALID_ARG, "lattice mesh: non-finite origin");
+        n_nodes *= dims[a];
+        if (n_nodes > MESH_MAX_NODES) return fail(c, ISDF_ERR_INVALID_ARG, "lattice mesh: more lattice nodes than the cap of 2^27");
+    }
+    if (!c) return fail(nullptr, ISDF_ERR_INVALID_ARG, "lattice mesh: null ctx");
+    HIPCHK(c, hipSetDevice(c->device));
+    SweptMeshState *s;
+    ISDF_TRY(c->swm.make(c, &s));
+    free_mesh_result(s);
+    hipStream_t st = c->stream;
+    Lattice L{dims[0], dims[1], dims[2], origin[0], origin[1], origin[2], eps};
+
+    DevEvents<2> ev;
+    ISDF_TRY(ev.ready(c));
+    DevBuf<double> d_f;
+    HIPCHK(c, d_f.alloc((size_t)n_nodes));
+    HIPCHK(c, hipMemcpyAsync(d_f.get(), f, (size_t)n_nodes * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(ev[0], st));
+    unsigned long long cnt[4];
+    ISDF_TRY(extract_mesh(c, s, L, d_f.get(), iso, st, cnt));
+    HIPCHK(c, hipEventRecord(ev[1], st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    s->nV = (long long)cnt[2]; s->nF = (long long)cnt[1]; s->have_mesh = true;
+    if (info_out) {
+        std::memset(info_out, 0, sizeof(*info_out));
+        for (int a = 0; a < 3; a++) { info_out->dims[a] = dims[a]; info_out->origin[a] = origin[a]; }
+        info_out->eps = eps;
+        info_out->band_cells = (long long)cnt[0];
+        info_out->n_vertices = s->nV;
+        info_out->n_triangles = s->nF;
+        info_out->unqualified_edges = (long long)cnt[3];
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        info_out->mesh_ms = ms;
     }
     return ISDF_OK;
 }

@@ -1594,12 +1594,27 @@ class Engine:
                 p.bmin[a], p.bmax[a] = float(bbox[0][a]), float(bbox[1][a])
         info = capi.IsdfSweptMeshInfo()
         self._check(self.lib.isdf_swept_mesh_build(self.h, N, _p(T), _p(Cc), C.byref(p), C.byref(info)))
+        return self._kept_mesh(info)
+
+    def _kept_mesh(self, info):
         nV, nF = int(info.n_vertices), int(info.n_triangles)
         V = np.zeros((nV, 3)); F = np.zeros((nF, 3), dtype=np.int32)
         self._check(self.lib.isdf_swept_mesh_get(self.h, _p(V), nV, F.ctypes.data_as(C.POINTER(C.c_int32)), nF))
         d = {name: (list(getattr(info, name)) if name in ("dims", "origin") else getattr(info, name))
              for name, _ in capi.IsdfSweptMeshInfo._fields_ if name != "reserved"}
         return V, F, d
+
+    def lattice_mesh(self, f, origin, eps, iso=0.0):
+        """Marching tetrahedra (the swept mesh's rule) on a caller's lattice field f (nx x ny x nz, NaN = node not evaluated):
+        (V, F, info) as swept_mesh gives them.  Needs no shape, grid or trajectory."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.ndim != 3:
+            raise ValueError("lattice_mesh: f must be a 3-D array")
+        dims = (C.c_int32 * 3)(*f.shape)
+        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        info = capi.IsdfSweptMeshInfo()
+        self._check(self.lib.isdf_lattice_mesh_build(self.h, dims, _p(org), float(eps), float(iso), _p(f), C.byref(info)))
+        return self._kept_mesh(info)
 
     def swept_mesh_release(self):
         self._check(self.lib.isdf_swept_mesh_release(self.h))

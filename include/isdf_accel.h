@@ -428,12 +428,17 @@ int isdf_swept_sdf_device(isdf_ctx *ctx, int N, const double *d_T, const double 
  * diagonal).  Inside is f < iso; a vertex lies on a lattice edge (7 per node: +x +y +z +xy +xz +yz +xyz), placed by linear
  * interpolation; triangles face towards larger f (outwards).  Vertices are numbered by ascending edge id (node * 7 + dir, node
  * = (i * ny + j) * nz + k), triangles come in cell order (z fastest), then tetrahedron order: the output is bitwise
- * reproducible, and the narrow band gives the dense mesh.
+ * reproducible, and the narrow band gives the dense mesh.  Coordinates: node (i, j, k) lies at origin + i * eps per axis, and the
+ * vertex of the edge from node p in direction d (offsets 0 / 1 per axis) at p + t * (d * eps) with t = (iso - f0) / (f1 - f0),
+ * f0 = f(p), f1 = f(p + d) - each operation rounded on its own (no fused multiply-add).  A vertex exists where f0 < iso differs
+ * from f1 < iso and the edge lies in a cell whose eight corners were all evaluated.
  * Box: use_bbox, or the trajectory's positions grown by R + iso + 2 eps (R: bound_radius of the shape; mesh robots: their
  * largest vertex norm; none known: ISDF_ERR_INVALID_ARG), snapped to multiples of eps; more than 2^27 lattice nodes:
  * ISDF_ERR_INVALID_ARG.  Narrow band (band = B > 0): the field on every B-th node, then on the nodes of the coarse cells whose
  * corners change sign about iso or all lie within lipschitz * sqrt(3) * B * eps of it - a corner farther away proves the cell's
- * side of iso (exact for a field with that Lipschitz bound); band = 0 evaluates every node. */
+ * side of iso (exact for a field with that Lipschitz bound; a corner without a qualifying interval, value 10, counts as the
+ * value 2 safety_hor + 0.1 there: that it is not within the qualification radius is all it proves); band = 0 evaluates every
+ * node. */
 typedef struct isdf_swept_mesh_params {
     double eps;          /* lattice spacing (m), > 0 (the reference's yaml eps: 0.05-0.15); default 0.1                */
     double iso;          /* level to extract, >= 0 (0 = the swept volume, > 0 = an inflated one); default 0           */
@@ -464,6 +469,13 @@ int isdf_swept_mesh_build(isdf_ctx *ctx, int N, const double *T, const double *c
 /* copies the last mesh out: V_out capV x 3, F_out capF x 3 (zero based); ISDF_ERR_OVERFLOW (nothing written) if too small */
 int isdf_swept_mesh_get(isdf_ctx *ctx, double *V_out, int capV, int32_t *F_out, int capF);
 int isdf_swept_mesh_release(isdf_ctx *ctx);      /* frees the kept mesh */
+/* marching tetrahedra (the rule of isdf_swept_mesh_build) on a caller's field: f[(i*ny + j)*nz + k], host array, NaN = node not
+ * evaluated (a cell with such a corner is skipped, as in the narrow band).  Needs a ctx only: no shape, grid or trajectory.
+ * dims >= 2 per axis, at most 2^27 nodes, eps finite and > 0, iso finite (negative allowed), no null pointer - else
+ * ISDF_ERR_INVALID_ARG.  Result kept and fetched like the swept mesh (isdf_swept_mesh_get / _release); info: dims, origin, eps,
+ * band_cells, n_vertices, n_triangles, unqualified_edges, mesh_ms; the field counters are 0. */
+int isdf_lattice_mesh_build(isdf_ctx *ctx, const int32_t dims[3], const double origin[3], double eps, double iso,
+                            const double *f, isdf_swept_mesh_info *info_out);
 
 /* ---- trajectory clearance check -------------------------------------------------------------------------------- */
 /* SweptVolumeManager::isTrajCollide (sw_manager.hpp:764: a stub, "currently always returns false"), the verdict generateTraj asks

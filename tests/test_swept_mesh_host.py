@@ -73,6 +73,22 @@ def test_bad_arguments_are_refused_without_a_device(pkg, product_lib):
     q.use_bbox = 1; q.bmin[0] = 1.0; q.bmax[0] = 0.0
     assert L.isdf_swept_mesh_build(None, 2, pT, pC, C.byref(q), None) == capi.ISDF_ERR_INVALID_ARG
     assert b"bbox" in L.isdf_last_error(None)
+    # isdf_lattice_mesh_build: the same order - arguments, then the ctx
+    dims = (C.c_int32 * 3)(3, 4, 5)
+    org = np.zeros(3); f = np.zeros(60)
+    pO, pF = org.ctypes.data_as(dp), f.ctypes.data_as(dp)
+    assert L.isdf_lattice_mesh_build(None, dims, pO, 0.1, 0.0, pF, None) == capi.ISDF_ERR_INVALID_ARG
+    assert b"ctx" in L.isdf_last_error(None)
+    assert L.isdf_lattice_mesh_build(None, dims, pO, 0.1, -0.5, pF, None) == capi.ISDF_ERR_INVALID_ARG
+    assert b"ctx" in L.isdf_last_error(None)                   # a negative iso is allowed here
+    for args, word in (((None, pO, 0.1, 0.0, pF), b"null"), ((dims, None, 0.1, 0.0, pF), b"null"), ((dims, pO, 0.1, 0.0, None), b"null"),
+                       ((dims, pO, 0.0, 0.0, pF), b"eps"), ((dims, pO, -0.1, 0.0, pF), b"eps"), ((dims, pO, float("inf"), 0.0, pF), b"eps"),
+                       ((dims, pO, float("nan"), 0.0, pF), b"eps"), ((dims, pO, 0.1, float("nan"), pF), b"iso"),
+                       ((dims, pO, 0.1, float("inf"), pF), b"iso"), (((C.c_int32 * 3)(3, 1, 5), pO, 0.1, 0.0, pF), b"dims"),
+                       (((C.c_int32 * 3)(3, 4, -5), pO, 0.1, 0.0, pF), b"dims"), (((C.c_int32 * 3)(1024, 1024, 129), pO, 0.1, 0.0, pF), b"cap"),
+                       (((C.c_int32 * 3)(2 ** 30, 2 ** 30, 2 ** 30), pO, 0.1, 0.0, pF), b"cap")):
+        assert L.isdf_lattice_mesh_build(None, *args, None) == capi.ISDF_ERR_INVALID_ARG, word
+        assert word in L.isdf_last_error(None), (word, L.isdf_last_error(None))
 
 
 def test_swept_mesh_struct_layouts_match_header(pkg):
