@@ -206,6 +206,19 @@ class IsdfViewGainInfo(C.Structure):
                 ("gain_total", C.c_int64), ("chunks", C.c_int32), ("reserved", C.c_int32), ("gain_ms", C.c_double)]
 
 
+class IsdfFrontierClusterParams(C.Structure):
+    """isdf_frontier_cluster_params (include/isdf_accel.h)."""
+    _fields_ = [("connectivity", C.c_int32), ("reserved", C.c_int32), ("min_size", C.c_int64)]
+
+
+class IsdfFrontierClusterInfo(C.Structure):
+    """isdf_frontier_cluster_info (include/isdf_accel.h)."""
+    _fields_ = [("n_voxels", C.c_int64), ("n_clusters", C.c_int64), ("n_rows", C.c_int64), ("n_voxels_dropped", C.c_int64), ("largest_size", C.c_int64),
+                ("largest_label", C.c_int64), ("frontier_ms", C.c_double), ("label_ms", C.c_double), ("stats_ms", C.c_double)]
+
+
+# int64 per cluster: label, size, lo xyz, hi xyz, sum xyz, rep_voxel, rep_d2, first_pos, 0, 0
+FRONTIER_CLUSTER_ROW = 16
 VIEW_GAIN_ROW = 8                       # int64 per view: status, gain, n_rays, n_skipped, n_hits, steps_total, n_rays_unknown, 0
 
 
@@ -440,6 +453,7 @@ EXPORTED_SYMBOLS = [
     "isdf_traj_known_params_default", "isdf_traj_known_horizon", "isdf_traj_known_horizon_device",
     "isdf_known_merge_host", "isdf_known_shift_host", "isdf_known_fill_host", "isdf_known_frontier_host",
     "isdf_view_gain_params_default", "isdf_view_gain_sizes", "isdf_view_gain", "isdf_view_gain_device", "isdf_view_gain_host",
+    "isdf_frontier_cluster_params_default", "isdf_frontier_cluster_sizes", "isdf_map_frontier_clusters", "isdf_known_clusters_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -798,6 +812,17 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfViewGainParams), C.sizeof(IsdfViewGainInfo)]:
         raise RuntimeError(f"isdf_view_gain structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfViewGainParams), C.sizeof(IsdfViewGainInfo)]}")
+    cp, ci = C.POINTER(IsdfFrontierClusterParams), C.POINTER(IsdfFrontierClusterInfo)
+    lib.isdf_frontier_cluster_params_default.argtypes = [cp]
+    lib.isdf_frontier_cluster_params_default.restype = None
+    lib.isdf_frontier_cluster_sizes.argtypes = [ip]
+    lib.isdf_frontier_cluster_sizes.restype = None
+    lib.isdf_map_frontier_clusters.argtypes = [C.c_void_p, C.c_void_p, cp, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, ci]
+    lib.isdf_known_clusters_host.argtypes = [C.c_void_p, i3, cp, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, ci]
+    lib.isdf_frontier_cluster_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfFrontierClusterParams), C.sizeof(IsdfFrontierClusterInfo)]:
+        raise RuntimeError(f"isdf_frontier_cluster structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfFrontierClusterParams), C.sizeof(IsdfFrontierClusterInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

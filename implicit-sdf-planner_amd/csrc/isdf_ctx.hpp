@@ -30,6 +30,7 @@ struct MapUpdateState;          // map_change.hpp: scratch of the in-place map c
 struct MapRaycastState;         // map_raycast.hip: staging of the host-pointer ray cast, the counters' record and its pinned copy
 struct DepthCamState;           // depth_cam.hip: staging of the depth camera's host-pointer forms, the counters' record and its pinned copy
 struct ViewGainState;           // view_gain.hip: the view gain's poses, per-view table, rows, seen grids and zero image
+struct FrontierClusterState;    // frontier_cluster.hip: the clusters' union-find, numbering and row scratch, the record and the pinned outputs
 int isdf_traj_check_ready(isdf_ctx *c);               // traj_check.hip: what isdf_traj_check needs of the ctx (shape, occupancy grid), or the error
 
 // frontend_field.hip: the record of one in-place change of the cost-to-go field (voxels closed: the repair; opened: the reopen),
@@ -101,6 +102,7 @@ struct isdf_ctx {
     Lazy<MapRaycastState> mrc;                  // isdf_map_raycast*: own scratch (grows only)
     Lazy<DepthCamState> dcm;                    // isdf_depth_render* / isdf_depth_rays* / isdf_integrate_depth: own scratch (grows only)
     Lazy<ViewGainState> vgn;                    // isdf_view_gain*: own scratch (grows only)
+    Lazy<FrontierClusterState> fcl;             // isdf_map_frontier_clusters: own scratch (grows only)
     DevBuf<unsigned> d_bits; bool bits_dirty = true;
     // the known grid (map_known.hip): one bit per voxel, 1 = some ray has visited it or the caller declared it known.  `on`
     // outlives maps (isdf_map_known_enable); d_bits holds n_words dwords while `have`; d_shift is where a window shift writes before the
@@ -278,6 +280,12 @@ void isdf_xchg_reset_board(isdf_ctx *c);  // xchg.hip: empties this rank's board
 int isdf_reset_result_slots(isdf_ctx *c); // isdf_host.hip: drains the device and empties every self-resetting slot again (after an overflow)
 void isdf_xchg_release(isdf_ctx *c);          // xchg.hip: closes the peer mappings, frees the mailbox (isdf_destroy)
 void isdf_frontend_release(isdf_ctx *c);      // frontend.hip: drops the tables (a new grid or shape)
+namespace isdf {
+// map_known.hip: the frontier stage of isdf_map_frontier and isdf_map_frontier_clusters - the set's words (the frontier, or the caller's
+// set_bits) into known.d_front, their record handed over, and with want_list the scan into known.d_base and the list into known.d_list
+int map_frontier_stage(isdf_ctx *c, const char *op, const uint32_t *set_bits, uint32_t *bits_out, bool want_list, long long capacity, const hipEvent_t *list_ev,
+                       MkRecord *rec_out, bool *counted);
+}
 int isdf_mesh_lattice_build(isdf_ctx *c, isdf::DevMesh *hm, const double lo[3], const double hi[3], int n, float s_range_out[2]);      // shape_eval.hip: the mesh kind's distance lattice (DevMesh::dl)
 int isdf_mesh_surface_valid(isdf_ctx *c, const double *d_tri, int nF, double extent, double tau_limit, int *valid_out, float defect_out[2]);      // shape_eval.hip: exact winding number 0 / 1 on both sides of every face
 

@@ -15,6 +15,8 @@
 //                       +-ny nz, each under its edge mask; the 32 occupancy bytes arrive as two 16-byte loads.  Writes the frontier
 //                       word and its count; the list is the repo's exclusive scan over the counts and mk_emit_kernel - no atomics, so
 //                       the voxels come out ascending on every run.
+//   mk_count_kernel     stands in for the frontier kernel where the set is a caller's (isdf_map_frontier_clusters with bits_in, DESIGN
+//                       4.22): the counts and the record of words that are in d_front already.
 // The reductions go through the wavefront, then LDS, then one set of global atomics per workgroup into one 64-byte record.
 #include "isdf_ctx.hpp"
 #include "map_known_host.hpp"
@@ -129,6 +131,19 @@ __global__ __launch_bounds__(256) void mk_frontier_kernel(MkGeom g, const unsign
             f = mk_frontier_word(known, g.n_words, w, g.X, g.Y, g.Z, g.n_vox, free_mask);
         }
         front[w] = f;
+        cnt[w] = __popc(f);
+        n += __popc(f);
+        mk_word_box(w, f, g.Y, g.Z, g.n_vox, lo, hi);
+    }
+    mk_block_reduce(n, 0ull, lo, hi, &rec->n, nullptr, rec->lo, rec->hi);
+}
+
+// a caller's set in place of the frontier (isdf_map_frontier_clusters with bits_in): the words are in `front` already; their counts and the record
+__global__ __launch_bounds__(256) void mk_count_kernel(MkGeom g, const unsigned *__restrict__ front, int *__restrict__ cnt, MkRecord *rec) {
+    int lo[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, hi[3] = {-1, -1, -1};
+    unsigned long long n = 0;
+    for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < g.n_words; w += (long long)gridDim.x * blockDim.x) {
+        const unsigned f = front[w];
         cnt[w] = __popc(f);
         n += __popc(f);
         mk_word_box(w, f, g.Y, g.Z, g.n_vox, lo, hi);
@@ -301,43 +316,68 @@ extern "C" int isdf_map_known_get(isdf_ctx *c, uint32_t *bits_out, isdf_map_know
     return ISDF_OK;
 }
 
-extern "C" int isdf_map_frontier(isdf_ctx *c, uint32_t *bits_out, int64_t *vox_out, long long capacity, isdf_map_frontier_info *info_out) {
-    if (!c) return ISDF_ERR_INVALID_ARG;
-    if (capacity < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "frontier: negative capacity");
-    if (c->known.have && !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "frontier: no occupancy grid");
-    if (int rc = known_begin(c, "frontier")) return rc;
+// The frontier stage, shared by isdf_map_frontier and isdf_map_frontier_clusters (frontier_cluster.hip): the set's words into d_front with
+// their per-dword counts - the frontier kernel, or with set_bits (host words in K's layout, tail bits clean) the upload and the count
+// kernel -, the record's hand-over, and with want_list the exclusive scan of the counts into d_base and the emit pass into d_list (not
+// synchronised; nothing is launched for an empty set).  *counted: *rec_out is the record (the caller's info can be filled) even where the
+// call then fails.  list_ev (nullable): two events recorded round the scan and the emit pass.
+int isdf::map_frontier_stage(isdf_ctx *c, const char *op, const uint32_t *set_bits, uint32_t *bits_out, bool want_list, long long capacity, const hipEvent_t *list_ev,
+                             MkRecord *rec_out, bool *counted) {
+    *counted = false;
+    const std::string what(op);
+    if (c->known.have && !set_bits && !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, (what + ": no occupancy grid").c_str());
+    if (int rc = known_begin(c, op)) return rc;
     isdf_ctx::Known &K = c->known;
     const MkGeom g = geom(c);
     const hipStream_t st = c->stream;
-    if (g.n_words > (long long)INT_MAX) return isdf_fail(c, ISDF_ERR_OVERFLOW, "frontier: more than 2^31 words");
+    if (g.n_words > (long long)INT_MAX) return isdf_fail(c, ISDF_ERR_OVERFLOW, (what + ": more than 2^31 words").c_str());
     int rc;
     if ((rc = K.d_front.reserve(c, (size_t)g.n_words)) || (rc = K.d_cnt.reserve(c, (size_t)g.n_words)) || (rc = K.d_base.reserve(c, (size_t)g.n_words))) return rc;
+    if (set_bits) HIPCHK(c, hipMemcpyAsync(K.d_front, set_bits, (size_t)g.n_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(K.ev[0], st));
-    hipLaunchKernelGGL(mk_frontier_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, st, g, (const unsigned *)K.d_bits.get(), (const uint8_t *)c->d_occ.get(), K.d_front.get(),
-                       K.d_cnt.get(), K.rec.dev());
+    if (set_bits)
+        hipLaunchKernelGGL(mk_count_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, st, g, (const unsigned *)K.d_front.get(), K.d_cnt.get(), K.rec.dev());
+    else
+        hipLaunchKernelGGL(mk_frontier_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, st, g, (const unsigned *)K.d_bits.get(), (const uint8_t *)c->d_occ.get(), K.d_front.get(),
+                           K.d_cnt.get(), K.rec.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(K.ev[1], st));
     if (bits_out) HIPCHK(c, hipMemcpyAsync(bits_out, K.d_front, (size_t)g.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if ((rc = known_fetch(c))) return rc;
     const MkRecord R = K.rec.host();
-    if (info_out) {
-        isdf_map_frontier_info info{};
-        info.n_frontier = (int64_t)R.n;
-        box_out(R, info.lo, info.hi);
-        info.kernel_ms = K.ev.ms(0, 1);
-        *info_out = info;
-    }
-    if (!vox_out || R.n == 0) return ISDF_OK;
-    if ((unsigned long long)capacity < R.n) return isdf_fail(c, ISDF_ERR_OVERFLOW, "frontier: output capacity smaller than the number of frontier voxels");
-    if (R.n > (unsigned long long)INT_MAX) return isdf_fail(c, ISDF_ERR_OVERFLOW, "frontier: more than 2^31 frontier voxels");
+    *rec_out = R;
+    *counted = true;
+    if (!want_list || R.n == 0) return ISDF_OK;
+    if ((unsigned long long)capacity < R.n) return isdf_fail(c, ISDF_ERR_OVERFLOW, (what + ": output capacity smaller than the number of frontier voxels").c_str());
+    if (R.n > (unsigned long long)INT_MAX) return isdf_fail(c, ISDF_ERR_OVERFLOW, (what + ": more than 2^31 frontier voxels").c_str());
     size_t bytes = 0;
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, K.d_cnt.get(), K.d_base.get(), (int)g.n_words, st));
     if ((rc = K.d_scan_tmp.reserve(c, std::max<size_t>(bytes, 1))) || (rc = K.d_list.reserve(c, (size_t)R.n))) return rc;
+    if (list_ev) HIPCHK(c, hipEventRecord(list_ev[0], st));
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(K.d_scan_tmp.get(), bytes, K.d_cnt.get(), K.d_base.get(), (int)g.n_words, st));
     hipLaunchKernelGGL(mk_emit_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, st, g.n_words, (const unsigned *)K.d_front.get(), (const int *)K.d_base.get(), K.d_list.get());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(vox_out, K.d_list, (size_t)R.n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    if (list_ev) HIPCHK(c, hipEventRecord(list_ev[1], st));
+    return ISDF_OK;
+}
+
+extern "C" int isdf_map_frontier(isdf_ctx *c, uint32_t *bits_out, int64_t *vox_out, long long capacity, isdf_map_frontier_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (capacity < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "frontier: negative capacity");
+    MkRecord R;
+    bool counted = false;
+    const int rc = map_frontier_stage(c, "frontier", nullptr, bits_out, vox_out != nullptr, capacity, nullptr, &R, &counted);
+    if (counted && info_out) {
+        isdf_map_frontier_info info{};
+        info.n_frontier = (int64_t)R.n;
+        box_out(R, info.lo, info.hi);
+        info.kernel_ms = c->known.ev.ms(0, 1);
+        *info_out = info;
+    }
+    if (rc) return rc;
+    if (!vox_out || R.n == 0) return ISDF_OK;
+    HIPCHK(c, hipMemcpyAsync(vox_out, c->known.d_list, (size_t)R.n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return ISDF_OK;
 }
 

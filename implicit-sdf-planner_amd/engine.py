@@ -487,6 +487,53 @@ def known_frontier_host(bits, occ, capacity=None, lib=None):
     return out, vox[:int(info.n_frontier)], info
 
 
+def _cluster_params(lib, connectivity, min_size):
+    p = capi.IsdfFrontierClusterParams()
+    lib.isdf_frontier_cluster_params_default(C.byref(p))
+    p.connectivity, p.min_size = int(connectivity), int(min_size)
+    return p
+
+
+def _cluster_call(call, name):
+    """the sizing call (every output NULL), then the call at exactly the sizes it reported: (vox, labels, rows, info)"""
+    info = capi.IsdfFrontierClusterInfo()
+    rc = call(None, None, 0, None, 0, info)
+    if rc < 0:
+        raise IsdfError(rc, name)
+    n, r = int(info.n_voxels), int(info.n_rows)
+    vox, labels, rows = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros((r, capi.FRONTIER_CLUSTER_ROW), dtype=np.int64)
+    if n:
+        rc = call(vox.ctypes.data_as(C.c_void_p), labels.ctypes.data_as(C.c_void_p), n, rows.ctypes.data_as(C.c_void_p), r, info)
+        if rc < 0:
+            raise IsdfError(rc, name)
+    return vox, labels, rows, info
+
+
+def known_clusters_host(bits, dims, connectivity=26, min_size=1, lib=None):
+    """isdf_known_clusters_host: the connected components (connectivity 6, 18 or 26) of the voxel set `bits`, a bit grid over dims in the
+    known grid's layout (known_pack), in plain host code.  Returns (voxels int64 ascending, labels int32 - the row of each voxel's
+    cluster, -1 where min_size dropped it -, rows int64 [n_rows, 16] = (label, size, lo xyz, hi xyz, sum xyz, rep_voxel, rep_d2,
+    first_pos, 0, 0), IsdfFrontierClusterInfo)."""
+    lib = lib or capi.load_library()
+    w, d = _known_args(bits, dims)
+    p = _cluster_params(lib, connectivity, min_size)
+    return _cluster_call(lambda vox, labels, nv, rows, nr, info: lib.isdf_known_clusters_host(w.ctypes.data_as(C.c_void_p), d, C.byref(p), vox, labels, nv, rows, nr,
+                                                                                              C.byref(info)), "isdf_known_clusters_host")
+
+
+def cluster_points(rows, bmin, resolution, dims):
+    """Of cluster rows (known_clusters_host, Engine.map_frontier_clusters) in a map of dims voxels with lower corner bmin and this
+    resolution, in metres as float64: (the centroids [n, 3], (sum / size + 0.5) * resolution + bmin; the centres of the rep_voxel cells
+    [n, 3] - points of the set itself, which the centroid need not be).  dims: rep_voxel is a voxel index, (x * ny + y) * nz + z."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, capi.FRONTIER_CLUSTER_ROW)
+    b = np.asarray(bmin, dtype=np.float64).reshape(3)
+    ny, nz = int(dims[1]), int(dims[2])
+    centroid = (rows[:, 8:11] / rows[:, 1:2].astype(np.float64) + 0.5) * float(resolution) + b
+    v = rows[:, 11]
+    cells = np.stack([v // (ny * nz), v // nz % ny, v % nz], axis=1)
+    return centroid, (cells + 0.5) * float(resolution) + b
+
+
 def _raycast_params(lib, test_origin_voxel, per_ray_origin):
     p = capi.IsdfMapRaycastParams()
     lib.isdf_map_raycast_params_default(C.byref(p))
@@ -1219,6 +1266,28 @@ class Engine:
         self._check(rc)
         self._frontier_cap = max(getattr(self, "_frontier_cap", 0), int(info.n_frontier))
         return out, vox[:int(info.n_frontier)], info
+
+    def map_frontier_clusters(self, bits=None, connectivity=26, min_size=1):
+        """isdf_map_frontier_clusters: the connected components (connectivity 6, 18 or 26) of the frontier - or of `bits`, any voxel set as
+        a bit grid in the known grid's layout (known_pack) -, on the device, read-only.  Does the sizing call itself.  Returns (voxels
+        int64 ascending - the frontier's list -, labels int32 - the row of each voxel's cluster, -1 where min_size dropped it -, rows int64
+        [n_rows, 16] = (label, size, lo xyz, hi xyz, sum xyz, rep_voxel, rep_d2, first_pos, 0, 0) in ascending label order,
+        IsdfFrontierClusterInfo).  From the frontier to scored goals without the list crossing the bus twice:
+
+            vox, labels, rows, info = eng.map_frontier_clusters(min_size=20)
+            _, bmin, _ = eng.get_grid(capi.GRID_OCCUPANCY)
+            centroids, reps = cluster_points(rows, bmin, res, dims)
+            poses = [look_at(eye, rep) for rep in reps]         # rep: the centre of a frontier voxel, known and free
+            gains, best = eng.view_gain(cam, poses, max_range_m=5.0)
+        """
+        w = None if bits is None else _known_args(bits, self._grid_dims())[0]
+        p = _cluster_params(self.lib, connectivity, min_size)
+        try:
+            return _cluster_call(lambda vox, labels, nv, rows, nr, info: self.lib.isdf_map_frontier_clusters(
+                self.h, None if w is None else w.ctypes.data_as(C.c_void_p), C.byref(p), vox, labels, nv, rows, nr, C.byref(info)), "isdf_map_frontier_clusters")
+        except IsdfError as e:
+            self._check(e.code)
+            raise
 
     def _traj_known_params(self, margin, mode):
         p = capi.IsdfTrajKnownParams()

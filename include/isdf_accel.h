@@ -1873,8 +1873,8 @@ int isdf_known_frontier_host(const uint32_t *bits, const uint8_t *occ, const int
  * multi-device ctx; ISDF_ERR_STATE without a known grid or without an occupancy grid.  n_views = 0 is legal; params and info_out may be
  * NULL.  isdf_view_gain_device: d_poses and d_rows_out are device memory, the work goes on `stream`; with info_out == NULL nothing is
  * handed over and nothing synchronised, with it `stream` is synchronised once - isdf_map_raycast_device's rule.
- * Not offered: a pessimistic gain in which unknown voxels block; a range- or angle-weighted gain; candidate generation or clustering of
- * the frontier; a gain kept incrementally across scans. */
+ * Not offered: a pessimistic gain in which unknown voxels block; a range- or angle-weighted gain; a gain kept incrementally across
+ * scans.  Candidates: isdf_map_frontier_clusters below gives the frontier's clusters and a voxel of each to look at. */
 typedef struct isdf_view_gain_params {
     int32_t stride_u, stride_v;   /* default 4, 4; >= 1 */
     double  max_range_m;          /* required: finite, > 0 (default 5.0) */
@@ -1904,6 +1904,65 @@ int isdf_view_gain_device(isdf_ctx *ctx, const isdf_depth_camera *camera, const 
 long long isdf_view_gain_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
                               const isdf_depth_camera *camera, const double *poses, long long n_views, const isdf_view_gain_params *params, int64_t *rows_out,
                               isdf_view_gain_info *info_out);
+
+/* ---- frontier clusters: connected components of the frontier, their centroids and goal voxels ---------------------- */
+/* The frontier is tens of thousands of voxels; a goal is one of a handful.  isdf_map_frontier_clusters groups a voxel set into its
+ * connected components on the device and returns one small row per component.  Everything but the three times is an integer, and
+ * isdf_known_clusters_host gives the same bytes.
+ *   INPUT SET.  bits_in == NULL: S = the frontier of the current K and occupancy, exactly isdf_map_frontier's.  bits_in != NULL: S = the
+ *   caller's bit grid in K's layout (voxel a = (x * ny + y) * nz + z is bit a & 31 of word a >> 5, ceil(nx ny nz / 32) words); a bit set
+ *   beyond the last voxel: ISDF_ERR_INVALID_ARG.  Any voxel set can be clustered so: the unknown voxels, an occupancy mask.
+ *   NEIGHBOURS.  params.connectivity is 6, 18 or 26 (default 26; anything else ISDF_ERR_INVALID_ARG): voxels p and q are neighbours iff
+ *   q - p lies in {-1, 0, 1}^3, is not 0 and has at most 1, 2 or 3 non-zero entries.  Both lie inside the grid: nothing wraps, and two
+ *   voxels whose bits are adjacent in the stream (the last voxel of a column, the first of the next) are neighbours only by this rule.
+ *   A frontier is a sheet one voxel thick, which 6-connectivity shreds; hence the default.
+ *   CLUSTER.  A connected component of S under that relation.  Its label is its lowest voxel index; the clusters are numbered in
+ *   ascending label order.  params.min_size (default 1; < 1 ISDF_ERR_INVALID_ARG) drops the clusters with fewer voxels from the rows; the
+ *   survivors keep their order and are numbered 0 .. n_rows - 1.
+ *   ROW.  16 int64 per kept cluster: {label, size, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z, sum_x, sum_y, sum_z, rep_voxel, rep_d2, first_pos,
+ *   0, 0}.  lo / hi: the inclusive index box of the members; sum_a: the sum of their indices on axis a; first_pos: the position of
+ *   `label` in vox_out.  The centroid cell is c_a = sum_a / size (C integer division, every term >= 0), the centroid itself sum_a / size
+ *   as a fraction.  rep_voxel is the member p that minimises d2 = |p - c|^2, ties to the lowest voxel index - the minimum over the members
+ *   of the key (d2 << 36) | voxel (a voxel index is below 2^36 and d2 below 2^26 for dims <= 4096, so the key is below 2^62) -, and rep_d2
+ *   its d2: a voxel of S itself (for the frontier: known and free), also where the centroid cell is not one (a ring).
+ *   OUTPUTS.  vox_out (nullable, vox_capacity entries): the voxels of S ascending - for the frontier isdf_map_frontier's list.  labels_out
+ *   (nullable, int32, vox_capacity entries): the row number of vox_out[i]'s cluster, -1 if min_size dropped it.  rows_out (nullable,
+ *   row_capacity rows).  vox_capacity < n_voxels with vox_out or labels_out non-null, or row_capacity < n_rows with rows_out non-null:
+ *   ISDF_ERR_OVERFLOW, info_out filled, every output untouched - a call with all three NULL is the sizing call.  Negative capacities:
+ *   ISDF_ERR_INVALID_ARG.  info_out (nullable): n_voxels = |S|; n_clusters before the filter; n_rows after it; n_voxels_dropped = the
+ *   voxels of the dropped clusters; largest_size and largest_label over ALL clusters, ties to the lowest label (0 and -1: S is empty);
+ *   frontier_ms, label_ms, stats_ms: device time (events on the ctx's stream) of the set's kernel with the list's scan and emit pass,
+ *   of the components (union and flatten), and of numbering, statistics, representatives and rows; 0 in the host form and for an empty S.
+ * The errors are isdf_map_frontier's: no known grid ISDF_ERR_STATE (with bits_in too: the set has the grid's size and uses the known
+ * grid's scratch); no occupancy grid while bits_in is NULL ISDF_ERR_STATE; a multi-device ctx ISDF_ERR_UNSUPPORTED; more than 2^31 words
+ * or voxels of S ISDF_ERR_OVERFLOW.  The call is read-only: K, the occupancy, `merges`, epochs, a kept field, an armed watch and every
+ * kept report are untouched.  Two hand-overs per call: the count of S, which sizes the scratch, and the results.  An empty S launches
+ * nothing past the count and returns zero rows.  The scratch grows only: a second call of a size allocates nothing
+ * (isdf_debug_live_bytes).  Two runs give the same bytes: the components' roots are their lowest positions whatever the order of the
+ * device's atomics, and every statistic is an integer sum, minimum or maximum.
+ * Not offered: a device-pointer form of the outputs; clusters kept incrementally across scans; splitting a large cluster (by its
+ * principal axis, say); the eye position of a candidate view; unknown space treated as an obstacle. */
+typedef struct isdf_frontier_cluster_params {
+    int32_t connectivity;         /* 6, 18 or 26 (default 26) */
+    int32_t reserved;
+    int64_t min_size;             /* default 1; >= 1 */
+} isdf_frontier_cluster_params;
+
+typedef struct isdf_frontier_cluster_info {
+    int64_t n_voxels, n_clusters, n_rows, n_voxels_dropped;
+    int64_t largest_size, largest_label;
+    double  frontier_ms, label_ms, stats_ms;
+} isdf_frontier_cluster_info;
+
+#define ISDF_FRONTIER_CLUSTER_ROW 16
+void isdf_frontier_cluster_params_default(isdf_frontier_cluster_params *p);      /* null-safe */
+void isdf_frontier_cluster_sizes(int sizes_out[2]);                              /* null-safe; sizeof of the params and of the info */
+int isdf_map_frontier_clusters(isdf_ctx *ctx, const uint32_t *bits_in, const isdf_frontier_cluster_params *params, int64_t *vox_out, int32_t *labels_out,
+                               long long vox_capacity, int64_t *rows_out, long long row_capacity, isdf_frontier_cluster_info *info_out);
+/* plain host code, no ctx, no device: set_bits = S's words over dims = {nx, ny, nz}, each in [1, 4096]; outputs, ISDF_ERR_OVERFLOW and
+ * ISDF_ERR_INVALID_ARG (a null set, bad dims, the bad arguments above) as isdf_map_frontier_clusters. */
+int isdf_known_clusters_host(const uint32_t *set_bits, const int32_t dims[3], const isdf_frontier_cluster_params *params, int64_t *vox_out, int32_t *labels_out,
+                             long long vox_capacity, int64_t *rows_out, long long row_capacity, isdf_frontier_cluster_info *info_out);
 
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
