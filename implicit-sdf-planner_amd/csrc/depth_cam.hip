@@ -11,9 +11,10 @@
 // The image is cleared by a 32-bit fill on the same stream.  The counters are summed in the wavefront, through LDS, then one set of
 // atomics per workgroup into the call's 64-byte record; with info_out == NULL the kernels count nothing and nothing is handed over.
 // Built with -ffp-contract=off: the projection and the unprojection are held to their host forms byte for byte.
-#include "isdf_ctx.hpp"
+#include "map_query.hpp"
 #include "depth_cam_host.hpp"
 #include "map_change.hpp"
+#include "dev_block_sum.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -67,24 +68,8 @@ __device__ __forceinline__ void dc_count_drop(int why, unsigned long long cnt[DC
     cnt[1] += why == DC_BEHIND; cnt[2] += why == DC_OUTSIDE; cnt[3] += why == DC_NEAR;
 }
 
-__device__ __forceinline__ void dc_hand_counters(const unsigned long long *cnt, int n, DcRecord *__restrict__ rec, unsigned long long (*s_sum)[DC_COUNTERS]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = 0; k < n; k++) {
-        unsigned long long s = cnt[k];
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if (lane == 0) s_sum[wave][k] = s;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < n) {
-        unsigned long long s = 0;
-        for (int w = 0; w < DC_WAVES; w++) s += s_sum[w][threadIdx.x];
-        if (s) atomicAdd(&rec->v[threadIdx.x], s);
-    }
-}
-
 template <bool COUNT> __global__ __launch_bounds__(DC_BLOCK) void dc_render_cloud_kernel(const float *__restrict__ xyz, long long n, DcCam K, int32_t *__restrict__ image,
                                                                                           DcRecord *__restrict__ rec) {
-    __shared__ unsigned long long s_sum[DC_WAVES][DC_COUNTERS];
     unsigned long long cnt[DC_COUNTERS] = {0, 0, 0, 0, 0, 0};
     const int lane = threadIdx.x & 63;
     // the wavefront's first point: every lane of it takes the same number of turns
@@ -99,13 +84,15 @@ template <bool COUNT> __global__ __launch_bounds__(DC_BLOCK) void dc_render_clou
         }
         dc_splat<COUNT>(drawn, W, image, K.width, cnt);
     }
-    if (COUNT) dc_hand_counters(cnt, DC_COUNTERS, rec, s_sum);
+    if (COUNT) {                // (uniform) every thread of the workgroup is here
+        const unsigned long long s = block_sum<DC_COUNTERS, DC_WAVES>(cnt);
+        if (s) atomicAdd(&rec->v[threadIdx.x], s);          // (s is 0 beyond the counters)
+    }
 }
 
 // occ as dwords (the ctx allocates it in whole dwords): lane t holds voxels 4 t .. 4 t + 3
 template <bool COUNT> __global__ __launch_bounds__(DC_BLOCK) void dc_render_map_kernel(const unsigned *__restrict__ occ4, DcMap M, DcCam K, int32_t *__restrict__ image,
                                                                                         DcRecord *__restrict__ rec) {
-    __shared__ unsigned long long s_sum[DC_WAVES][DC_COUNTERS];
     unsigned long long cnt[DC_COUNTERS] = {0, 0, 0, 0, 0, 0};
     const int lane = threadIdx.x & 63;
     const long long n_words = (M.n_vox + 3) >> 2;
@@ -130,11 +117,13 @@ template <bool COUNT> __global__ __launch_bounds__(DC_BLOCK) void dc_render_map_
             dc_splat<COUNT>(drawn, W, image, K.width, cnt);
         }
     }
-    if (COUNT) dc_hand_counters(cnt, DC_COUNTERS, rec, s_sum);
+    if (COUNT) {                // (uniform) every thread of the workgroup is here
+        const unsigned long long s = block_sum<DC_COUNTERS, DC_WAVES>(cnt);
+        if (s) atomicAdd(&rec->v[threadIdx.x], s);          // (s is 0 beyond the counters)
+    }
 }
 
 __global__ __launch_bounds__(DC_BLOCK) void dc_rays_kernel(DcRays Q, const void *__restrict__ image, float *__restrict__ ends, uint8_t *__restrict__ hit, DcRecord *__restrict__ rec) {
-    __shared__ unsigned long long s_sum[DC_WAVES][DC_COUNTERS];
     unsigned long long cnt[DC_COUNTERS] = {0, 0, 0, 0, 0, 0};
     const long long n = (long long)Q.nu * Q.nv;
     for (long long k = (long long)blockIdx.x * DC_BLOCK + threadIdx.x; k < n; k += (long long)gridDim.x * DC_BLOCK) {
@@ -148,7 +137,8 @@ __global__ __launch_bounds__(DC_BLOCK) void dc_rays_kernel(DcRays Q, const void 
         cnt[4] += (flags & DC_RAY_CLIPPED) != 0; cnt[5] += (flags & DC_RAY_HIT) != 0;
     }
     if (!rec) return;           // (uniform) the caller wants no counters
-    dc_hand_counters(cnt, DC_COUNTERS, rec, s_sum);
+    const unsigned long long s = block_sum<DC_COUNTERS, DC_WAVES>(cnt);
+    if (s) atomicAdd(&rec->v[threadIdx.x], s);
 }
 
 }  // namespace isdf
@@ -160,6 +150,7 @@ struct DepthCamState {
     isdf::DevBuf<void> d_rays;                  // end points | hit bytes
     isdf::RecPair<isdf::DcRecord> rec;
     isdf::DevEvents<2> ev;
+    int ready(isdf_ctx *c) { ISDF_TRY(ev.ready(c)); return rec.ready(c); }
 };
 
 using namespace isdf;
@@ -192,8 +183,7 @@ namespace {
 
 // ---- what the device and the host forms check and set up alike (c may be null: the host forms)
 int render_setup(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2world, const isdf_depth_render_params *params, isdf_depth_render_params &P, DcCam &K) {
-    isdf_depth_render_params_default(&P);
-    if (params) P = *params;
+    P = map_query::resolve(params, isdf_depth_render_params_default);
     if (!cam || dc_camera_bad(cam->width, cam->height, cam->fx, cam->fy, cam->cx, cam->cy, cam2world)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "depth camera: bad intrinsics or pose");
     if (!(P.splat_m >= 0.0) || !(P.splat_m <= 1e300) || !(P.min_depth_m >= 0.0) || !(P.min_depth_m <= 1e30) || P.max_splat_px < 0 ||
         (P.source != ISDF_DEPTH_SOURCE_CLOUD && P.source != ISDF_DEPTH_SOURCE_MAP))
@@ -205,51 +195,32 @@ int render_setup(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2wo
     return ISDF_OK;
 }
 
-int rays_setup(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2world, int format, const isdf_depth_rays_params *params, const double bmin[3], const double bmax[3],
-               double res, const int dims[3], DcRays &Q) {
-    isdf_depth_rays_params P;
-    isdf_depth_rays_params_default(&P);
-    if (params) P = *params;
+int rays_setup(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2world, int format, const isdf_depth_rays_params *params, const MapGeom &M, DcRays &Q) {
+    const isdf_depth_rays_params P = map_query::resolve(params, isdf_depth_rays_params_default);
     if (!cam || dc_camera_bad(cam->width, cam->height, cam->fx, cam->fy, cam->cx, cam->cy, cam2world)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "depth camera: bad intrinsics or pose");
     if (format != ISDF_DEPTH_I32_MM && format != ISDF_DEPTH_U16_MM && format != ISDF_DEPTH_F32_M) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "unknown depth image format");
     if (P.stride_u < 1 || P.stride_v < 1 || !(P.min_range_m >= 0.0) || !(P.max_range_m > 0.0) || (P.no_return_is_free && !(P.max_range_m <= 1.7976931348623157e308)))
         return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad depth ray parameters (no_return_is_free needs a finite max_range_m)");
     int q[3];
-    if (!ms_quantize(bmin, bmax, res, dims, cam2world[3], cam2world[7], cam2world[11], q)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the camera lies outside the map");
+    if (!ms_quantize(M, cam2world[3], cam2world[7], cam2world[11], q)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the camera lies outside the map");
     dc_rays_setup(cam->width, cam->height, cam->fx, cam->fy, cam->cx, cam->cy, cam2world, format, P.stride_u, P.stride_v, P.min_range_m, P.max_range_m,
-                  P.no_return_is_free != 0, bmin, bmax, res, Q);
+                  P.no_return_is_free != 0, M, Q);
     return ISDF_OK;
 }
 
 size_t pixel_bytes(int format) { return format == ISDF_DEPTH_U16_MM ? 2 : 4; }
 
-int cam_state(isdf_ctx *c, DepthCamState **out) {
-    ISDF_TRY(c->dcm.make(c, out));
-    ISDF_TRY((*out)->ev.ready(c));
-    return (*out)->rec.ready(c);
-}
-
-int single_device(isdf_ctx *c, const char *what) {
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, what);
-    return ISDF_OK;
-}
-
 // ---- the render: the clear, the launch and, with counters, the record on its way to the host
 int render_check(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2world, const void *xyz, long long n, const isdf_depth_render_params *params, const void *image,
                  isdf_depth_render_params &P, DcCam &K) {
-    if (int rc = render_setup(c, cam, cam2world, params, P, K)) return rc;
+    ISDF_TRY(render_setup(c, cam, cam2world, params, P, K));
     if (!image || (P.source == ISDF_DEPTH_SOURCE_CLOUD && (n < 0 || (n > 0 && !xyz)))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad depth render arguments");
-    if (int rc = single_device(c, "the depth render is not offered on a multi-device ctx")) return rc;
-    if (P.source == ISDF_DEPTH_SOURCE_MAP && (!c->have_geom || !c->d_occ))
-        return isdf_fail(c, ISDF_ERR_STATE, "rendering the map needs an occupancy grid (isdf_set_grid with ISDF_GRID_OCCUPANCY, or isdf_set_pointcloud)");
-    return ISDF_OK;
+    ISDF_TRY(map_query::single_device(c, "the depth render is not offered on a multi-device ctx"));
+    return P.source == ISDF_DEPTH_SOURCE_MAP ? map_query::has_occupancy(c, "rendering the map") : ISDF_OK;
 }
 
 int render_run(isdf_ctx *c, DepthCamState *S, const DcCam &K, const isdf_depth_render_params &P, const float *d_xyz, long long n, int32_t *d_image, bool count, hipStream_t st) {
-    if (count) {
-        HIPCHK(c, S->rec.zero(st));
-        HIPCHK(c, hipEventRecord(S->ev[0], st));
-    }
+    ISDF_TRY(map_query::count_begin(c, count, S->ev, S->rec, st));
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)d_image, DC_EMPTY, (size_t)K.width * K.height, st));
     DcRecord *const rec = count ? S->rec.dev() : nullptr;
     if (P.source == ISDF_DEPTH_SOURCE_MAP) {
@@ -268,10 +239,7 @@ int render_run(isdf_ctx *c, DepthCamState *S, const DcCam &K, const isdf_depth_r
         else hipLaunchKernelGGL(dc_render_cloud_kernel<false>, dim3(blocks), dim3(DC_BLOCK), 0, st, d_xyz, n, K, d_image, rec);
         HIPCHK(c, hipGetLastError());
     }
-    if (!count) return ISDF_OK;
-    HIPCHK(c, hipEventRecord(S->ev[1], st));
-    HIPCHK(c, S->rec.fetch(st));
-    return ISDF_OK;
+    return map_query::count_end(c, count, S->ev, S->rec, st);
 }
 
 void render_info(const DepthCamState *S, isdf_depth_render_info *out) {
@@ -288,24 +256,16 @@ int rays_check(isdf_ctx *c, const isdf_depth_camera *cam, const double *cam2worl
                const void *hit, DcRays &Q) {
     if (!image || !ends || !hit) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad depth ray arguments");
     if (!c->have_geom) return isdf_fail(c, ISDF_ERR_STATE, "depth rays need a map: its box clips them");
-    const DevGrid &G = c->grid;
-    const int dims[3] = {G.X, G.Y, G.Z};
-    return rays_setup(c, cam, cam2world, format, params, G.bmin, G.bmax, G.res, dims, Q);
+    return rays_setup(c, cam, cam2world, format, params, map_geom(c->grid), Q);
 }
 
 int rays_run(isdf_ctx *c, DepthCamState *S, const DcRays &Q, const void *d_image, float *d_ends, uint8_t *d_hit, bool count, hipStream_t st) {
-    if (count) {
-        HIPCHK(c, S->rec.zero(st));
-        HIPCHK(c, hipEventRecord(S->ev[0], st));
-    }
+    ISDF_TRY(map_query::count_begin(c, count, S->ev, S->rec, st));
     const long long n = (long long)Q.nu * Q.nv;
     const unsigned blocks = (unsigned)std::min<long long>((n + DC_BLOCK - 1) / DC_BLOCK, 8192);
     hipLaunchKernelGGL(dc_rays_kernel, dim3(blocks), dim3(DC_BLOCK), 0, st, Q, d_image, d_ends, d_hit, count ? S->rec.dev() : nullptr);
     HIPCHK(c, hipGetLastError());
-    if (!count) return ISDF_OK;
-    HIPCHK(c, hipEventRecord(S->ev[1], st));
-    HIPCHK(c, S->rec.fetch(st));
-    return ISDF_OK;
+    return map_query::count_end(c, count, S->ev, S->rec, st);
 }
 
 void rays_info(const DepthCamState *S, const DcRays &Q, isdf_depth_rays_info *out) {
@@ -332,17 +292,12 @@ extern "C" int isdf_depth_render_device(isdf_ctx *c, const isdf_depth_camera *ca
     if (!c) return ISDF_ERR_INVALID_ARG;
     isdf_depth_render_params P;
     DcCam K;
-    if (int rc = render_check(c, cam, cam2world, d_xyz, n, params, d_image_out, P, K)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(render_check(c, cam, cam2world, d_xyz, n, params, d_image_out, P, K));
     DepthCamState *S;
-    if (int rc = cam_state(c, &S)) return rc;
+    ISDF_TRY(map_query::state_of(c, c->dcm, &S));
     const hipStream_t st = (hipStream_t)stream;
-    if (int rc = render_run(c, S, K, P, d_xyz, n, d_image_out, info_out != nullptr, st)) return rc;
-    if (info_out) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        render_info(S, info_out);
-    }
-    return ISDF_OK;
+    ISDF_TRY(render_run(c, S, K, P, d_xyz, n, d_image_out, info_out != nullptr, st));
+    return map_query::info_after(c, info_out, st, [&](isdf_depth_render_info *out) { render_info(S, out); });
 }
 
 extern "C" int isdf_depth_render(isdf_ctx *c, const isdf_depth_camera *cam, const double cam2world[12], const float *xyz, long long n, const isdf_depth_render_params *params,
@@ -350,19 +305,18 @@ extern "C" int isdf_depth_render(isdf_ctx *c, const isdf_depth_camera *cam, cons
     if (!c) return ISDF_ERR_INVALID_ARG;
     isdf_depth_render_params P;
     DcCam K;
-    if (int rc = render_check(c, cam, cam2world, xyz, n, params, image_out, P, K)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(render_check(c, cam, cam2world, xyz, n, params, image_out, P, K));
     DepthCamState *S;
-    if (int rc = cam_state(c, &S)) return rc;
+    ISDF_TRY(map_query::state_of(c, c->dcm, &S));
     const hipStream_t st = c->stream;
     const bool cloud = P.source == ISDF_DEPTH_SOURCE_CLOUD;
     const size_t pixels = (size_t)K.width * K.height;
-    if (int rc = S->d_image.reserve(c, pixels)) return rc;
+    ISDF_TRY(S->d_image.reserve(c, pixels));
     if (cloud) {
-        if (int rc = S->d_in.reserve(c, (size_t)n * 3 * sizeof(float))) return rc;
+        ISDF_TRY(S->d_in.reserve(c, (size_t)n * 3 * sizeof(float)));
         if (n > 0) HIPCHK(c, hipMemcpyAsync(S->d_in, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, st));
     }
-    if (int rc = render_run(c, S, K, P, (const float *)S->d_in.get(), cloud ? n : 0, S->d_image.get(), true, st)) return rc;
+    ISDF_TRY(render_run(c, S, K, P, (const float *)S->d_in.get(), cloud ? n : 0, S->d_image.get(), true, st));
     HIPCHK(c, hipMemcpyAsync(image_out, S->d_image, pixels * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (info_out) render_info(S, info_out);
@@ -373,7 +327,7 @@ extern "C" int isdf_depth_render_host(const isdf_depth_camera *cam, const double
                                       double resolution, const int32_t dims[3], const isdf_depth_render_params *params, int32_t *image_out, isdf_depth_render_info *info_out) {
     isdf_depth_render_params P;
     DcCam K;
-    if (int rc = render_setup(nullptr, cam, cam2world, params, P, K)) return rc;
+    ISDF_TRY(render_setup(nullptr, cam, cam2world, params, P, K));
     if (!image_out) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "depth render (host form): bad arguments");
     DcRenderCounts C;
     if (P.source == ISDF_DEPTH_SOURCE_MAP) {
@@ -404,37 +358,31 @@ extern "C" int isdf_depth_rays_device(isdf_ctx *c, const isdf_depth_camera *cam,
                                       const isdf_depth_rays_params *params, float *d_ends_out, uint8_t *d_hit_out, isdf_depth_rays_info *info_out, void *stream) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     DcRays Q;
-    if (int rc = rays_check(c, cam, cam2world, d_image, format, params, d_ends_out, d_hit_out, Q)) return rc;
-    if (int rc = single_device(c, "depth rays on the device are not offered on a multi-device ctx")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(rays_check(c, cam, cam2world, d_image, format, params, d_ends_out, d_hit_out, Q));
+    ISDF_TRY(map_query::single_device(c, "depth rays on the device are not offered on a multi-device ctx"));
     DepthCamState *S;
-    if (int rc = cam_state(c, &S)) return rc;
+    ISDF_TRY(map_query::state_of(c, c->dcm, &S));
     const hipStream_t st = (hipStream_t)stream;
-    if (int rc = rays_run(c, S, Q, d_image, d_ends_out, d_hit_out, info_out != nullptr, st)) return rc;
-    if (info_out) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        rays_info(S, Q, info_out);
-    }
-    return ISDF_OK;
+    ISDF_TRY(rays_run(c, S, Q, d_image, d_ends_out, d_hit_out, info_out != nullptr, st));
+    return map_query::info_after(c, info_out, st, [&](isdf_depth_rays_info *out) { rays_info(S, Q, out); });
 }
 
 extern "C" int isdf_depth_rays(isdf_ctx *c, const isdf_depth_camera *cam, const double cam2world[12], const void *image, int format, const isdf_depth_rays_params *params,
                                float *ends_out, uint8_t *hit_out, isdf_depth_rays_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     DcRays Q;
-    if (int rc = rays_check(c, cam, cam2world, image, format, params, ends_out, hit_out, Q)) return rc;
-    if (int rc = single_device(c, "depth rays on the device are not offered on a multi-device ctx")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(rays_check(c, cam, cam2world, image, format, params, ends_out, hit_out, Q));
+    ISDF_TRY(map_query::single_device(c, "depth rays on the device are not offered on a multi-device ctx"));
     DepthCamState *S;
-    if (int rc = cam_state(c, &S)) return rc;
+    ISDF_TRY(map_query::state_of(c, c->dcm, &S));
     const hipStream_t st = c->stream;
     const size_t n = (size_t)Q.nu * Q.nv, image_bytes = (size_t)Q.width * Q.height * pixel_bytes(format);
-    if (int rc = S->d_in.reserve(c, image_bytes)) return rc;
-    if (int rc = S->d_rays.reserve(c, n * 13)) return rc;
+    ISDF_TRY(S->d_in.reserve(c, image_bytes));
+    ISDF_TRY(S->d_rays.reserve(c, n * 13));
     float *const d_ends = (float *)S->d_rays.get();
     uint8_t *const d_hit = (uint8_t *)S->d_rays.get() + n * 12;
     HIPCHK(c, hipMemcpyAsync(S->d_in, image, image_bytes, hipMemcpyHostToDevice, st));
-    if (int rc = rays_run(c, S, Q, S->d_in.get(), d_ends, d_hit, true, st)) return rc;
+    ISDF_TRY(rays_run(c, S, Q, S->d_in.get(), d_ends, d_hit, true, st));
     HIPCHK(c, hipMemcpyAsync(ends_out, d_ends, n * 12, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(hit_out, d_hit, n, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -447,7 +395,7 @@ extern "C" long long isdf_depth_rays_host(const isdf_depth_camera *cam, const do
                                           isdf_depth_rays_info *info_out) {
     if (ms_geometry_bad(bmin, bmax, resolution, dims) || !image || !ends_out || !hit_out) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "depth rays (host form): bad arguments");
     DcRays Q;
-    if (int rc = rays_setup(nullptr, cam, cam2world, format, params, bmin, bmax, resolution, dims, Q)) return rc;
+    ISDF_TRY(rays_setup(nullptr, cam, cam2world, format, params, map_geom(bmin, bmax, resolution, dims), Q));
     DcRaysCounts C;
     dc_rays_host(Q, image, ends_out, hit_out, C);
     if (info_out) {
@@ -467,20 +415,17 @@ extern "C" int isdf_integrate_depth(isdf_ctx *c, const isdf_depth_camera *cam, c
     const double origin[3] = {cam2world[3], cam2world[7], cam2world[11]};
     isdf_map_scan_params P;
     MsOrigin O;
-    if (int rc = scan_check(c, "integrating a depth image", origin, image, 1, scan_params, P, O)) return rc;
-    const DevGrid &G = c->grid;
-    const int dims[3] = {G.X, G.Y, G.Z};
+    ISDF_TRY(scan_check(c, "integrating a depth image", origin, image, 1, scan_params, P, O));
     DcRays Q;
-    if (int rc = rays_setup(c, cam, cam2world, format, rays_params, G.bmin, G.bmax, G.res, dims, Q)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(rays_setup(c, cam, cam2world, format, rays_params, map_geom(c->grid), Q));
     DepthCamState *S;
-    if (int rc = cam_state(c, &S)) return rc;
+    ISDF_TRY(map_query::state_of(c, c->dcm, &S));
     const size_t image_bytes = (size_t)Q.width * Q.height * pixel_bytes(format);
-    if (int rc = S->d_in.reserve(c, image_bytes)) return rc;
+    ISDF_TRY(S->d_in.reserve(c, image_bytes));
     HIPCHK(c, hipMemcpyAsync(S->d_in, image, image_bytes, hipMemcpyHostToDevice, c->stream));
     DepthProduce D{S, &Q};
     // the scan's first hand-over synchronises the stream: the rays' record is on the host when it returns
-    if (int rc = scan_integrate(c, O, MsInput{nullptr, nullptr, produce_rays, &D}, (long long)Q.nu * Q.nv, P, scan_info_out)) return rc;
+    ISDF_TRY(scan_integrate(c, O, MsInput{nullptr, nullptr, produce_rays, &D}, (long long)Q.nu * Q.nv, P, scan_info_out));
     if (depth_info_out) rays_info(S, Q, depth_info_out);
     return ISDF_OK;
 }

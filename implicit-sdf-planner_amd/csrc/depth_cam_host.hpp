@@ -147,7 +147,7 @@ struct DcRays {
 constexpr int DC_RAY_NO_RETURN = 1, DC_RAY_BELOW_MIN = 2, DC_RAY_TRUNCATED = 4, DC_RAY_CLIPPED = 8, DC_RAY_HIT = 16;
 
 inline void dc_rays_setup(int width, int height, double fx, double fy, double cx, double cy, const double c2w[12], int format, int su, int sv, double min_range,
-                          double max_range, int free_no_return, const double bmin[3], const double bmax[3], double res, DcRays &Q) {
+                          double max_range, int free_no_return, const MapGeom &M, DcRays &Q) {
     Q.width = width; Q.height = height; Q.su = su; Q.sv = sv;
     Q.nu = (width + su - 1) / su; Q.nv = (height + sv - 1) / sv;
     Q.format = format; Q.free_no_return = free_no_return;
@@ -155,8 +155,8 @@ inline void dc_rays_setup(int width, int height, double fx, double fy, double cx
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) Q.R[3 * i + j] = c2w[4 * i + j];
         Q.t[i] = c2w[4 * i + 3];
-        Q.lo[i] = bmin[i] + 0.5 * res;
-        Q.hi[i] = bmax[i] - 0.5 * res;
+        Q.lo[i] = M.bmin[i] + 0.5 * M.res;
+        Q.hi[i] = M.bmax[i] - 0.5 * M.res;
     }
     Q.min_range = min_range; Q.max_range = max_range;
 }

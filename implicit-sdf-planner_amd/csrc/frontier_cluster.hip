@@ -24,7 +24,7 @@
 //   fc_rows_kernel     the rows of the kept clusters as far as the caller's capacity goes; the counts into the record.
 //   fc_labels_kernel   labels[i] = the row of i's cluster or -1.
 // Nothing here writes to the ctx's map, its known grid, its products or its flags.
-#include "isdf_ctx.hpp"
+#include "map_query.hpp"
 #include "frontier_cluster_host.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -245,6 +245,7 @@ struct FrontierClusterState {
     isdf::PinBuf<int64_t> h_vox, h_rows;
     isdf::PinBuf<int32_t> h_labels;
     isdf::DevEvents<4> ev;
+    int ready(isdf_ctx *c) { ISDF_TRY(ev.ready(c)); return rec.ready(c); }
 };
 
 using namespace isdf;
@@ -265,8 +266,7 @@ namespace {
 
 // what the device and the host forms check alike (c may be null: the host form)
 int cluster_setup(isdf_ctx *c, const isdf_frontier_cluster_params *params, long long vox_capacity, long long row_capacity, isdf_frontier_cluster_params &P) {
-    isdf_frontier_cluster_params_default(&P);
-    if (params) P = *params;
+    P = map_query::resolve(params, isdf_frontier_cluster_params_default);
     if (!fc_max_nonzero(P.connectivity)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "frontier clusters: connectivity must be 6, 18 or 26");
     if (P.min_size < 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "frontier clusters: min_size must be at least 1");
     if (vox_capacity < 0 || row_capacity < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "frontier clusters: negative capacity");
@@ -282,16 +282,13 @@ extern "C" int isdf_map_frontier_clusters(isdf_ctx *c, const uint32_t *bits_in, 
     if (!c) return ISDF_ERR_INVALID_ARG;
     isdf_frontier_cluster_params P;
     ISDF_TRY(cluster_setup(c, params, vox_capacity, row_capacity, P));
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "frontier clusters are not offered on a multi-device ctx");
+    ISDF_TRY(map_query::single_device(c, "frontier clusters are not offered on a multi-device ctx"));
     const DevGrid &G = c->grid;
     const int32_t dims[3] = {G.X, G.Y, G.Z};
     const FcGeom g = fc_geom(dims);
     if (bits_in && c->known.have && fc_tail_dirty(bits_in, g)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "frontier clusters: a bit of bits_in beyond the last voxel is set");
-    HIPCHK(c, hipSetDevice(c->device));
     FrontierClusterState *S;
-    ISDF_TRY(c->fcl.make(c, &S));
-    ISDF_TRY(S->ev.ready(c));
-    ISDF_TRY(S->rec.ready(c));
+    ISDF_TRY(map_query::state_of(c, c->fcl, &S));
     const hipStream_t st = c->stream;
     // stage 1 and the first hand-over: |S|
     MkRecord R;

@@ -18,7 +18,7 @@
 //   mk_count_kernel     stands in for the frontier kernel where the set is a caller's (isdf_map_frontier_clusters with bits_in, DESIGN
 //                       4.22): the counts and the record of words that are in d_front already.
 // The reductions go through the wavefront, then LDS, then one set of global atomics per workgroup into one 64-byte record.
-#include "isdf_ctx.hpp"
+#include "map_query.hpp"
 #include "map_known_host.hpp"
 #include "map_change.hpp"
 #include <hipcub/hipcub.hpp>
@@ -178,9 +178,13 @@ MkRecord record_empty() {
     return r;
 }
 
+int has_known(isdf_ctx *c, const char *op) {
+    return map_query::has_known(c, (std::string(op) + ": no known grid (isdf_map_known_enable, then a map from isdf_set_pointcloud)").c_str());
+}
+
 // what every entry point here asks first; the record and its pinned copy exist afterwards, the device record is empty
 int known_begin(isdf_ctx *c, const char *op) {
-    if (!c->known.have) return isdf_fail(c, ISDF_ERR_STATE, (std::string(op) + ": no known grid (isdf_map_known_enable, then a map from isdf_set_pointcloud)").c_str());
+    ISDF_TRY(has_known(c, op));
     isdf_ctx::Known &K = c->known;
     HIPCHK(c, hipSetDevice(c->device));
     ISDF_TRY(K.rec.ready(c));
@@ -206,7 +210,7 @@ int map_known_reset(isdf_ctx *c) {
     K.have = false;                     // (a failure below must not leave a grid of the old size behind a map of the new one)
     if (!K.on || !c->have_geom) return ISDF_OK;
     const MkGeom g = geom(c);
-    if (int rc = K.d_bits.reserve(c, (size_t)g.n_words)) return rc;
+    ISDF_TRY(K.d_bits.reserve(c, (size_t)g.n_words));
     HIPCHK(c, hipMemsetAsync(K.d_bits, 0, (size_t)g.n_words * sizeof(unsigned), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     K.n_words = (size_t)g.n_words; K.have = true; K.newly = 0; K.merges = 0;
@@ -236,7 +240,7 @@ int isdf::map_known_shift_launch(isdf_ctx *c, const int32_t s[3]) {
     isdf_ctx::Known &K = c->known;
     const MkGeom g = geom(c);
     const int32_t dims[3] = {g.X, g.Y, g.Z};
-    if (int rc = K.d_shift.reserve(c, K.n_words)) return rc;
+    ISDF_TRY(K.d_shift.reserve(c, K.n_words));
     hipLaunchKernelGGL(mk_shift_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, c->stream, g, (const unsigned *)K.d_bits.get(), K.d_shift.get(), mk_shift_plan(dims, s));
     HIPCHK(c, hipGetLastError());
     return ISDF_OK;
@@ -252,7 +256,7 @@ extern "C" void isdf_map_known_sizes(int sizes_out[4]) {
 
 extern "C" int isdf_map_known_enable(isdf_ctx *c, int on) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the known grid is not offered on a multi-device ctx");
+    ISDF_TRY(map_query::single_device(c, "the known grid is not offered on a multi-device ctx"));
     isdf_ctx::Known &K = c->known;
     HIPCHK(c, hipSetDevice(c->device));
     if (!on) {
@@ -276,27 +280,27 @@ extern "C" int isdf_map_known_merge_ms(isdf_ctx *c, int enable, double *ms_out) 
 
 extern "C" int isdf_map_known_fill(isdf_ctx *c, const int32_t *box, int value) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    if (!c->known.have) return isdf_fail(c, ISDF_ERR_STATE, "filling the known grid: no known grid (isdf_map_known_enable, then a map from isdf_set_pointcloud)");
+    ISDF_TRY(has_known(c, "filling the known grid"));
     const MkGeom g = geom(c);
     const int32_t dims[3] = {g.X, g.Y, g.Z};
     const int32_t whole[6] = {0, 0, 0, g.X - 1, g.Y - 1, g.Z - 1};
     if (!box) box = whole;
     if (mk_box_bad(dims, box)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "filling the known grid: the box lies outside the grid or has lo > hi");
-    if (int rc = known_begin(c, "filling the known grid")) return rc;
+    ISDF_TRY(known_begin(c, "filling the known grid"));
     isdf_ctx::Known &K = c->known;
     MuBox B;
     for (int a = 0; a < 3; a++) { B.lo[a] = box[a]; B.hi[a] = box[3 + a]; }
     const long long w0 = (((long long)B.lo[0] * g.Y + B.lo[1]) * g.Z + B.lo[2]) >> 5, w1 = (((long long)B.hi[0] * g.Y + B.hi[1]) * g.Z + B.hi[2]) >> 5;
     hipLaunchKernelGGL(mk_fill_kernel, dim3(word_blocks(w1 - w0 + 1)), dim3(256), 0, c->stream, g, K.d_bits.get(), B, w0, w1, value ? 1 : 0, K.rec.dev());
     HIPCHK(c, hipGetLastError());
-    if (int rc = known_fetch(c)) return rc;
+    ISDF_TRY(known_fetch(c));
     K.newly = (long long)K.rec.host().newly;
     return ISDF_OK;
 }
 
 extern "C" int isdf_map_known_get(isdf_ctx *c, uint32_t *bits_out, isdf_map_known_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    if (int rc = known_begin(c, "reading the known grid")) return rc;
+    ISDF_TRY(known_begin(c, "reading the known grid"));
     isdf_ctx::Known &K = c->known;
     const MkGeom g = geom(c);
     if (info_out) {
@@ -304,7 +308,7 @@ extern "C" int isdf_map_known_get(isdf_ctx *c, uint32_t *bits_out, isdf_map_know
         HIPCHK(c, hipGetLastError());
     }
     if (bits_out) HIPCHK(c, hipMemcpyAsync(bits_out, K.d_bits, (size_t)g.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (int rc = known_fetch(c)) return rc;
+    ISDF_TRY(known_fetch(c));
     if (info_out) {
         const MkRecord R = K.rec.host();
         isdf_map_known_info info{};
@@ -326,13 +330,12 @@ int isdf::map_frontier_stage(isdf_ctx *c, const char *op, const uint32_t *set_bi
     *counted = false;
     const std::string what(op);
     if (c->known.have && !set_bits && !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, (what + ": no occupancy grid").c_str());
-    if (int rc = known_begin(c, op)) return rc;
+    ISDF_TRY(known_begin(c, op));
     isdf_ctx::Known &K = c->known;
     const MkGeom g = geom(c);
     const hipStream_t st = c->stream;
     if (g.n_words > (long long)INT_MAX) return isdf_fail(c, ISDF_ERR_OVERFLOW, (what + ": more than 2^31 words").c_str());
-    int rc;
-    if ((rc = K.d_front.reserve(c, (size_t)g.n_words)) || (rc = K.d_cnt.reserve(c, (size_t)g.n_words)) || (rc = K.d_base.reserve(c, (size_t)g.n_words))) return rc;
+    ISDF_TRY(K.d_front.reserve(c, (size_t)g.n_words)); ISDF_TRY(K.d_cnt.reserve(c, (size_t)g.n_words)); ISDF_TRY(K.d_base.reserve(c, (size_t)g.n_words));
     if (set_bits) HIPCHK(c, hipMemcpyAsync(K.d_front, set_bits, (size_t)g.n_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(K.ev[0], st));
     if (set_bits)
@@ -343,7 +346,7 @@ int isdf::map_frontier_stage(isdf_ctx *c, const char *op, const uint32_t *set_bi
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(K.ev[1], st));
     if (bits_out) HIPCHK(c, hipMemcpyAsync(bits_out, K.d_front, (size_t)g.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if ((rc = known_fetch(c))) return rc;
+    ISDF_TRY(known_fetch(c));
     const MkRecord R = K.rec.host();
     *rec_out = R;
     *counted = true;
@@ -352,7 +355,7 @@ int isdf::map_frontier_stage(isdf_ctx *c, const char *op, const uint32_t *set_bi
     if (R.n > (unsigned long long)INT_MAX) return isdf_fail(c, ISDF_ERR_OVERFLOW, (what + ": more than 2^31 frontier voxels").c_str());
     size_t bytes = 0;
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, K.d_cnt.get(), K.d_base.get(), (int)g.n_words, st));
-    if ((rc = K.d_scan_tmp.reserve(c, std::max<size_t>(bytes, 1))) || (rc = K.d_list.reserve(c, (size_t)R.n))) return rc;
+    ISDF_TRY(K.d_scan_tmp.reserve(c, std::max<size_t>(bytes, 1))); ISDF_TRY(K.d_list.reserve(c, (size_t)R.n));
     if (list_ev) HIPCHK(c, hipEventRecord(list_ev[0], st));
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(K.d_scan_tmp.get(), bytes, K.d_cnt.get(), K.d_base.get(), (int)g.n_words, st));
     hipLaunchKernelGGL(mk_emit_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, st, g.n_words, (const unsigned *)K.d_front.get(), (const int *)K.d_base.get(), K.d_list.get());

@@ -7,8 +7,9 @@
 // The lanes of a wavefront finish at different lengths, as the trace's do; a workgroup is two wavefronts so that a short cast still
 // spreads over the compute units and a long ray holds up one other wavefront's slot at most.
 // Nothing here writes to the ctx's map, its products or its flags.
-#include "isdf_ctx.hpp"
+#include "map_query.hpp"
 #include "map_raycast_host.hpp"
+#include "dev_block_sum.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -27,40 +28,24 @@ constexpr int MR_COUNTERS = 5;
 
 struct MrOrigin { int q[3]; };
 
-__device__ __forceinline__ unsigned long long mr_wave_sum(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;                   // lane 0 holds the sum
-}
-
-__global__ __launch_bounds__(MR_BLOCK) void mr_cast_kernel(const double *__restrict__ origins, const float *__restrict__ ends, long long n, DevGrid G, MrOrigin O,
+__global__ __launch_bounds__(MR_BLOCK) void mr_cast_kernel(const double *__restrict__ origins, const float *__restrict__ ends, long long n, MapGeom M, MrOrigin O,
                                                            const uint8_t *__restrict__ occ, int test_origin, int32_t *__restrict__ rows, MrRecord *__restrict__ rec) {
-    __shared__ unsigned long long s_sum[MR_WAVES][MR_COUNTERS];
-    const int dims[3] = {G.X, G.Y, G.Z};
     long long cnt[MR_COUNTERS] = {0, 0, 0, 0, 0};
     for (long long i = (long long)blockIdx.x * MR_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * MR_BLOCK) {
         int qo[3] = {O.q[0], O.q[1], O.q[2]};
         bool ok = true;
-        if (origins) ok = ms_quantize(G.bmin, G.bmax, G.res, dims, origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], qo);
+        if (origins) ok = ms_quantize(M, origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], qo);
         const float end[3] = {ends[3 * i], ends[3 * i + 1], ends[3 * i + 2]};
         int row[MR_ROW];
-        mr_cast_ray(occ, G.bmin, G.bmax, G.res, dims, ok, qo, end, test_origin != 0, row);
+        mr_cast_ray(occ, M, ok, qo, end, test_origin != 0, row);
         mr_count_row(row, cnt[0], cnt[1], cnt[2], cnt[3], cnt[4]);
         int4 *const out = reinterpret_cast<int4 *>(rows + MR_ROW * i);          // 32-byte rows from a 16-byte aligned base
         out[0] = make_int4(row[0], row[1], row[2], row[3]);
         out[1] = make_int4(row[4], row[5], row[6], row[7]);
     }
     if (!rec) return;           // (uniform) the caller wants no counters
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = 0; k < MR_COUNTERS; k++) {
-        const unsigned long long s = mr_wave_sum((unsigned long long)cnt[k]);
-        if (lane == 0) s_sum[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < MR_COUNTERS) {
-        unsigned long long s = 0;
-        for (int w = 0; w < MR_WAVES; w++) s += s_sum[w][threadIdx.x];
-        if (s) atomicAdd(&rec->n_skipped + threadIdx.x, s);            // the five counters lie next to each other
-    }
+    const unsigned long long s = block_sum<MR_COUNTERS, MR_WAVES>(cnt);
+    if (s) atomicAdd(&rec->n_skipped + threadIdx.x, s);            // the five counters lie next to each other; s is 0 beyond them
 }
 
 }  // namespace isdf
@@ -71,6 +56,7 @@ struct MapRaycastState {
     isdf::DevBuf<int32_t> d_rows;
     isdf::RecPair<isdf::MrRecord> rec;
     isdf::DevEvents<2> ev;
+    int ready(isdf_ctx *c) { ISDF_TRY(ev.ready(c)); return rec.ready(c); }
 };
 
 using namespace isdf;
@@ -87,46 +73,30 @@ extern "C" void isdf_map_raycast_sizes(int sizes_out[2]) {
 
 namespace {
 
-int raycast_state(isdf_ctx *c, MapRaycastState **out) {
-    ISDF_TRY(c->mrc.make(c, out));
-    ISDF_TRY((*out)->ev.ready(c));
-    return (*out)->rec.ready(c);
-}
-
 // what both forms check of the ctx and of the shared origin; O is filled when the origin is shared
 int raycast_check(isdf_ctx *c, const double *origins, const void *ends, long long n, const void *rows, const isdf_map_raycast_params *params,
                   isdf_map_raycast_params &P, MrOrigin &O) {
-    isdf_map_raycast_params_default(&P);
-    if (params) P = *params;
+    P = map_query::resolve(params, isdf_map_raycast_params_default);
     if (n < 0 || (!origins && (n > 0 || !P.per_ray_origin)) || (n > 0 && (!ends || !rows))) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad ray cast arguments");
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "casting rays through the map is not offered on a multi-device ctx");
-    if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "casting rays needs an occupancy grid (isdf_set_grid with ISDF_GRID_OCCUPANCY, or isdf_set_pointcloud)");
+    ISDF_TRY(map_query::single_device(c, "casting rays through the map is not offered on a multi-device ctx"));
+    ISDF_TRY(map_query::has_occupancy(c, "casting rays"));
     O = MrOrigin{{0, 0, 0}};
-    if (!P.per_ray_origin) {
-        const DevGrid &G = c->grid;
-        const int dims[3] = {G.X, G.Y, G.Z};
-        if (!ms_quantize(G.bmin, G.bmax, G.res, dims, origins[0], origins[1], origins[2], O.q)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the rays' shared origin lies outside the map");
-    }
+    if (!P.per_ray_origin && !ms_quantize(map_geom(c->grid), origins[0], origins[1], origins[2], O.q))
+        return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the rays' shared origin lies outside the map");
     return ISDF_OK;
 }
 
 // the launch and, with info_out, the one hand-over; d_origins: null for a shared origin (O holds it)
 int raycast_run(isdf_ctx *c, MapRaycastState *S, const double *d_origins, const float *d_ends, long long n, const isdf_map_raycast_params &P, const MrOrigin &O,
-                int32_t *d_rows, isdf_map_raycast_info *info_out, hipStream_t st) {
-    if (info_out) {
-        HIPCHK(c, S->rec.zero(st));
-        HIPCHK(c, hipEventRecord(S->ev[0], st));
-    }
+                int32_t *d_rows, bool count, hipStream_t st) {
+    ISDF_TRY(map_query::count_begin(c, count, S->ev, S->rec, st));
     if (n > 0) {
         const unsigned blocks = (unsigned)std::min<long long>((n + MR_BLOCK - 1) / MR_BLOCK, 8192);
-        hipLaunchKernelGGL(mr_cast_kernel, dim3(blocks), dim3(MR_BLOCK), 0, st, d_origins, d_ends, n, c->grid, O, (const uint8_t *)c->d_occ.get(), (int)P.test_origin_voxel,
-                           d_rows, info_out ? S->rec.dev() : nullptr);
+        hipLaunchKernelGGL(mr_cast_kernel, dim3(blocks), dim3(MR_BLOCK), 0, st, d_origins, d_ends, n, map_geom(c->grid), O, (const uint8_t *)c->d_occ.get(),
+                           (int)P.test_origin_voxel, d_rows, count ? S->rec.dev() : nullptr);
         HIPCHK(c, hipGetLastError());
     }
-    if (!info_out) return ISDF_OK;
-    HIPCHK(c, hipEventRecord(S->ev[1], st));
-    HIPCHK(c, S->rec.fetch(st));
-    return ISDF_OK;
+    return map_query::count_end(c, count, S->ev, S->rec, st);
 }
 
 void raycast_info(const MapRaycastState *S, long long n, isdf_map_raycast_info *info_out) {
@@ -149,18 +119,13 @@ extern "C" int isdf_map_raycast_device(isdf_ctx *c, const double *d_origins, con
     if (!c) return ISDF_ERR_INVALID_ARG;
     isdf_map_raycast_params P;
     MrOrigin O;
-    if (int rc = raycast_check(c, d_origins, d_ends, n, d_rows_out, params, P, O)) return rc;
+    ISDF_TRY(raycast_check(c, d_origins, d_ends, n, d_rows_out, params, P, O));
     if (((uintptr_t)d_rows_out & 15u) != 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the rows of a ray cast must be 16-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
     MapRaycastState *S;
-    if (int rc = raycast_state(c, &S)) return rc;
+    ISDF_TRY(map_query::state_of(c, c->mrc, &S));
     const hipStream_t st = (hipStream_t)stream;
-    if (int rc = raycast_run(c, S, P.per_ray_origin ? d_origins : nullptr, d_ends, n, P, O, d_rows_out, info_out, st)) return rc;
-    if (info_out) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        raycast_info(S, n, info_out);
-    }
-    return ISDF_OK;
+    ISDF_TRY(raycast_run(c, S, P.per_ray_origin ? d_origins : nullptr, d_ends, n, P, O, d_rows_out, info_out != nullptr, st));
+    return map_query::info_after(c, info_out, st, [&](isdf_map_raycast_info *out) { raycast_info(S, n, out); });
 }
 
 extern "C" int isdf_map_raycast(isdf_ctx *c, const double *origins, const float *ends, long long n, const isdf_map_raycast_params *params, int32_t *rows_out,
@@ -168,23 +133,21 @@ extern "C" int isdf_map_raycast(isdf_ctx *c, const double *origins, const float 
     if (!c) return ISDF_ERR_INVALID_ARG;
     isdf_map_raycast_params P;
     MrOrigin O;
-    if (int rc = raycast_check(c, origins, ends, n, rows_out, params, P, O)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+    ISDF_TRY(raycast_check(c, origins, ends, n, rows_out, params, P, O));
     MapRaycastState *S;
-    if (int rc = raycast_state(c, &S)) return rc;
+    ISDF_TRY(map_query::state_of(c, c->mrc, &S));
     const hipStream_t st = c->stream;
     const size_t origin_bytes = P.per_ray_origin ? (((size_t)n * 3 * sizeof(double) + 15) & ~(size_t)15) : 0;
     const size_t end_bytes = (size_t)n * 3 * sizeof(float);
-    if (int rc = S->d_in.reserve(c, origin_bytes + end_bytes)) return rc;
-    if (int rc = S->d_rows.reserve(c, (size_t)n * MR_ROW)) return rc;
+    ISDF_TRY(S->d_in.reserve(c, origin_bytes + end_bytes));
+    ISDF_TRY(S->d_rows.reserve(c, (size_t)n * MR_ROW));
     const double *const d_origins = P.per_ray_origin ? (const double *)S->d_in.get() : nullptr;
     const float *const d_ends = (const float *)((const uint8_t *)S->d_in.get() + origin_bytes);
     if (n > 0) {
         if (P.per_ray_origin) HIPCHK(c, hipMemcpyAsync(S->d_in, origins, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync((uint8_t *)S->d_in.get() + origin_bytes, ends, end_bytes, hipMemcpyHostToDevice, st));
     }
-    isdf_map_raycast_info info{};
-    if (int rc = raycast_run(c, S, d_origins, d_ends, n, P, O, S->d_rows.get(), &info, st)) return rc;
+    ISDF_TRY(raycast_run(c, S, d_origins, d_ends, n, P, O, S->d_rows.get(), true, st));
     if (n > 0) HIPCHK(c, hipMemcpyAsync(rows_out, S->d_rows, (size_t)n * MR_ROW * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (info_out) raycast_info(S, n, info_out);
@@ -193,13 +156,11 @@ extern "C" int isdf_map_raycast(isdf_ctx *c, const double *origins, const float 
 
 extern "C" long long isdf_raycast_host(const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double *origins,
                                        const float *ends, long long n, const isdf_map_raycast_params *params, int32_t *rows_out) {
-    isdf_map_raycast_params P;
-    isdf_map_raycast_params_default(&P);
-    if (params) P = *params;
+    const isdf_map_raycast_params P = map_query::resolve(params, isdf_map_raycast_params_default);
     if (ms_geometry_bad(bmin, bmax, resolution, dims) || !occ || (!origins && (n > 0 || !P.per_ray_origin)) || n < 0 || (n > 0 && (!ends || !rows_out)))
         return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "ray cast (host form): bad arguments");
     MrCounts K;
-    if (!mr_cast_host(occ, bmin, bmax, resolution, dims, origins, P.per_ray_origin != 0, ends, n, P.test_origin_voxel != 0, rows_out, K))
+    if (!mr_cast_host(occ, map_geom(bmin, bmax, resolution, dims), origins, P.per_ray_origin != 0, ends, n, P.test_origin_voxel != 0, rows_out, K))
         return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "ray cast (host form): the shared origin lies outside the map");
     return K.n_hits;
 }

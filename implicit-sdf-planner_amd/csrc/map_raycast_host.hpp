@@ -22,15 +22,15 @@ MU_HD void mr_row_none(int status, int row[MR_ROW]) {
     row[6] = 0; row[7] = 1;
 }
 
-// The walk from tick qo to tick qe over the occupancy bytes (z fastest, dims as the grid's).  Voxel 0 of the walk is tested only when
+// The walk from tick qo to tick qe over the occupancy bytes (z fastest, M.dims as the grid's).  Voxel 0 of the walk is tested only when
 // test_origin is set.  No bounds test: the walk stays in the box of its two end voxels, both of which lie in the grid.
-MU_HD void mr_cast_walk(const uint8_t *occ, const int dims[3], const int qo[3], const int qe[3], bool test_origin, int row[MR_ROW]) {
+MU_HD void mr_cast_walk(const uint8_t *occ, const MapGeom &M, const int qo[3], const int qe[3], bool test_origin, int row[MR_ROW]) {
     MsRay r;
     ms_ray_begin(qo, qe, r);
     int status = MR_CLEAR, steps = 0, axis = -1;
     bool test = test_origin;
     for (;;) {
-        if (test && occ[((size_t)r.v[0] * dims[1] + r.v[1]) * dims[2] + r.v[2]] != 0) { status = MR_HIT; break; }
+        if (test && occ[map_voxel(M, r.v)] != 0) { status = MR_HIT; break; }
         if (ms_ray_done(r)) break;
         axis = ms_ray_step_axis(r);
         steps++;
@@ -47,12 +47,11 @@ MU_HD void mr_cast_walk(const uint8_t *occ, const int dims[3], const int qo[3], 
 }
 
 // one ray: origin_ok / qo from ms_quantize of the origin (the caller's, so that a shared origin is quantised once)
-MU_HD void mr_cast_ray(const uint8_t *occ, const double bmin[3], const double bmax[3], double res, const int dims[3], bool origin_ok, const int qo[3],
-                       const float end[3], bool test_origin, int row[MR_ROW]) {
+MU_HD void mr_cast_ray(const uint8_t *occ, const MapGeom &M, bool origin_ok, const int qo[3], const float end[3], bool test_origin, int row[MR_ROW]) {
     int qe[3];
     if (!origin_ok) { mr_row_none(MR_ORIGIN_OUTSIDE, row); return; }
-    if (!ms_quantize(bmin, bmax, res, dims, (double)end[0], (double)end[1], (double)end[2], qe)) { mr_row_none(MR_END_OUTSIDE, row); return; }
-    mr_cast_walk(occ, dims, qo, qe, test_origin, row);
+    if (!ms_quantize(M, (double)end[0], (double)end[1], (double)end[2], qe)) { mr_row_none(MR_END_OUTSIDE, row); return; }
+    mr_cast_walk(occ, M, qo, qe, test_origin, row);
 }
 
 struct MrCounts { long long n_skipped = 0, n_origin_outside = 0, n_hits = 0, n_clear = 0, steps_total = 0; };
@@ -67,16 +66,16 @@ MU_HD void mr_count_row(const int row[MR_ROW], long long &n_skipped, long long &
 
 // ---- host form: rows_out = n x 8.  origins: 3 doubles for every ray, or n x 3 (per_ray).  false: a shared origin lies outside the
 // map (nothing written).
-inline bool mr_cast_host(const uint8_t *occ, const double bmin[3], const double bmax[3], double res, const int32_t dims[3], const double *origins, bool per_ray,
-                         const float *ends, long long n, bool test_origin, int32_t *rows_out, MrCounts &K) {
+inline bool mr_cast_host(const uint8_t *occ, const MapGeom &M, const double *origins, bool per_ray, const float *ends, long long n, bool test_origin, int32_t *rows_out,
+                         MrCounts &K) {
     K = MrCounts();
     int qo[3] = {0, 0, 0};
     bool ok = true;
-    if (!per_ray && !ms_quantize(bmin, bmax, res, dims, origins[0], origins[1], origins[2], qo)) return false;
+    if (!per_ray && !ms_quantize(M, origins[0], origins[1], origins[2], qo)) return false;
     for (long long i = 0; i < n; i++) {
-        if (per_ray) ok = ms_quantize(bmin, bmax, res, dims, origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], qo);
+        if (per_ray) ok = ms_quantize(M, origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], qo);
         int row[MR_ROW];
-        mr_cast_ray(occ, bmin, bmax, res, dims, ok, qo, ends + 3 * i, test_origin, row);
+        mr_cast_ray(occ, M, ok, qo, ends + 3 * i, test_origin, row);
         mr_count_row(row, K.n_skipped, K.n_origin_outside, K.n_hits, K.n_clear, K.steps_total);
         for (int w = 0; w < MR_ROW; w++) rows_out[MR_ROW * i + w] = row[w];
     }

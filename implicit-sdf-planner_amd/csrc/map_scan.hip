@@ -14,8 +14,7 @@
 //                    mu_mark_kernel's crossing test, into the list record again.
 // Then map_clear.hip's and map_update.hip's own refresh stages, in that order: the call IS isdf_clear_pointcloud of miss_weight
 // centres of every voxel of F followed by isdf_update_pointcloud of the hit end points, and reports what those two calls report.
-#include "isdf_ctx.hpp"
-#include "map_scan_host.hpp"
+#include "map_query.hpp"
 #include "map_change.hpp"
 #include "swept_field.hpp"
 #include <algorithm>
@@ -24,9 +23,8 @@
 
 namespace isdf {
 
-__device__ __forceinline__ bool ms_end_tick(const DevGrid &G, const float *__restrict__ xyz, long long i, int q[3]) {
-    const int dims[3] = {G.X, G.Y, G.Z};
-    return ms_quantize(G.bmin, G.bmax, G.res, dims, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], q);
+__device__ __forceinline__ bool ms_end_tick(const MapGeom &M, const float *__restrict__ xyz, long long i, int q[3]) {
+    return ms_quantize(M, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], q);
 }
 
 __device__ __forceinline__ void ms_set_bit(unsigned *bits, size_t a) {
@@ -35,7 +33,7 @@ __device__ __forceinline__ void ms_set_bit(unsigned *bits, size_t a) {
     if (!(*w & b)) atomicOr(w, b);
 }
 
-__global__ __launch_bounds__(256) void ms_trace_kernel(const float *__restrict__ xyz, const uint8_t *__restrict__ hit, long long n, DevGrid G, MsOrigin O,
+__global__ __launch_bounds__(256) void ms_trace_kernel(const float *__restrict__ xyz, const uint8_t *__restrict__ hit, long long n, MapGeom M, MsOrigin O,
                                                        unsigned *free_bits, unsigned *hit_bits, MsRecord *__restrict__ rec) {
     __shared__ int s_lo[3], s_hi[3];
     __shared__ unsigned s_skipped, s_hits;
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(256) void ms_trace_kernel(const float *__restrict__
     unsigned skipped = 0, hits = 0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         int qe[3];
-        if (!ms_end_tick(G, xyz, i, qe)) { skipped++; continue; }
+        if (!ms_end_tick(M, xyz, i, qe)) { skipped++; continue; }
         const bool is_hit = !hit || hit[i] != 0;
         MsRay r;
         ms_ray_begin(O.q, qe, r);
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(256) void ms_trace_kernel(const float *__restrict__
             hi[a] = max(hi[a], max(r.v[a], ve));
         }
         for (;;) {
-            const size_t a = ((size_t)r.v[0] * G.Y + r.v[1]) * G.Z + r.v[2];           // inside the grid: the walk stays between two voxels of it
+            const size_t a = map_voxel(M, r.v);           // inside the grid: the walk stays between two voxels of it
             const bool last = ms_ray_done(r);
             if (last && is_hit) { ms_set_bit(hit_bits, a); hits++; }
             else ms_set_bit(free_bits, a);
@@ -124,19 +122,19 @@ __global__ __launch_bounds__(256) void ms_apply_kernel(DevGrid G, const unsigned
     if (ignored) atomicAdd(&rec->tally, ignored);
 }
 
-__global__ __launch_bounds__(256) void ms_hits_kernel(const float *__restrict__ xyz, const uint8_t *__restrict__ hit, long long n, DevGrid G,
+__global__ __launch_bounds__(256) void ms_hits_kernel(const float *__restrict__ xyz, const uint8_t *__restrict__ hit, long long n, MapGeom M,
                                                       unsigned *__restrict__ counts, unsigned thr, uint8_t *__restrict__ occ, const float *__restrict__ esdf,
                                                       MuVoxel *__restrict__ list, unsigned cap, MapListRecord *__restrict__ rec) {
     if (esdf && blockIdx.x == 0 && threadIdx.x == 0) rec->esdf0 = __float_as_uint(esdf[0]);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         int qe[3];
-        if ((hit && hit[i] == 0) || !ms_end_tick(G, xyz, i, qe)) continue;
-        const int ix = qe[0] >> MS_TICKS_LOG2, iy = qe[1] >> MS_TICKS_LOG2, iz = qe[2] >> MS_TICKS_LOG2;
-        const size_t a = ((size_t)ix * G.Y + iy) * G.Z + iz;
+        if ((hit && hit[i] == 0) || !ms_end_tick(M, xyz, i, qe)) continue;
+        const int v[3] = {qe[0] >> MS_TICKS_LOG2, qe[1] >> MS_TICKS_LOG2, qe[2] >> MS_TICKS_LOG2};
+        const size_t a = map_voxel(M, v);
         const unsigned old = atomicAdd(&counts[a], 1u);
         if (thr >= 1u && old + 1u == thr) {                     // mu_mark_kernel's crossing: exactly one add sees it
             occ[a] = 1;
-            map_list_append(rec, list, cap, ix, iy, iz);
+            map_list_append(rec, list, cap, v[0], v[1], v[2]);
         }
     }
 }
@@ -184,6 +182,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     MapUpdateState &S = *Sp;
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
+    const MapGeom M = map_geom(G);
     const unsigned long long n_vox = (unsigned long long)G.X * G.Y * G.Z;
     const size_t n_words = (size_t)((n_vox + 31) / 32);
     const unsigned thr = (unsigned)c->counts_thr, miss = (unsigned)P.miss_weight;
@@ -208,7 +207,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
 
     // ---- the rays, then the frees: one hand-over
     if (n_rays > 0) {
-        hipLaunchKernelGGL(ms_trace_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, G, O, S.d_free_bits.get(), S.d_hit_bits.get(), &d_rec->scan);
+        hipLaunchKernelGGL(ms_trace_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, M, O, S.d_free_bits.get(), S.d_hit_bits.get(), &d_rec->scan);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(S.ev_scan[1], st));
@@ -249,7 +248,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
         hipError_t e = hipMemcpyAsync(&d_rec->list, &h_rec->list, sizeof(MapListRecord), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipEventRecord(S.ev[0], st);
         if (e == hipSuccess && RS.n_hits > 0) {
-            hipLaunchKernelGGL(ms_hits_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, G, c->d_counts.get(), thr, c->d_occ.get(),
+            hipLaunchKernelGGL(ms_hits_kernel, dim3(ray_blocks), dim3(256), 0, st, d_xyz, d_hit, n_rays, M, c->d_counts.get(), thr, c->d_occ.get(),
                                (const float *)c->d_esdf.get(), S.d_list.get(), cap_update, &d_rec->list);
             e = hipGetLastError();
         }
@@ -278,9 +277,7 @@ int isdf::scan_check(isdf_ctx *c, const char *op, const double origin[3], const 
     if (params) P = *params;
     if (P.miss_weight < 0 || P.clear.max_cleared_voxels < 0 || !(P.clear.full_fraction >= 0.0) || P.update.max_new_voxels < 0 || !(P.update.full_fraction >= 0.0))
         return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad scan parameters");
-    const DevGrid &G = c->grid;
-    const int dims[3] = {G.X, G.Y, G.Z};
-    if (!ms_quantize(G.bmin, G.bmax, G.res, dims, origin[0], origin[1], origin[2], O.q)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the scan's origin lies outside the map");
+    if (!ms_quantize(map_geom(c->grid), origin[0], origin[1], origin[2], O.q)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the scan's origin lies outside the map");
     return ISDF_OK;
 }
 
@@ -300,7 +297,7 @@ extern "C" long long isdf_scan_sets_host(const double bmin[3], const double bmax
     std::vector<uint8_t> free_set;
     std::vector<uint32_t> hits;
     MsSets S;
-    if (!ms_sets_host(bmin, bmax, resolution, dims, origin, xyz, hit, n_rays, free_set, hits, S)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): the origin lies outside the map");
+    if (!ms_sets_host(map_geom(bmin, bmax, resolution, dims), origin, xyz, hit, n_rays, free_set, hits, S)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): the origin lies outside the map");
     if (free_out) std::memcpy(free_out, free_set.data(), free_set.size());
     if (hits_out) std::memcpy(hits_out, hits.data(), hits.size() * sizeof(uint32_t));
     if (n_skipped_out) *n_skipped_out = S.n_skipped;
@@ -310,6 +307,6 @@ extern "C" long long isdf_scan_sets_host(const double bmin[3], const double bmax
 extern "C" long long isdf_scan_ray_host(const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3], const double origin[3], const float end[3],
                                         int32_t *ijk_out, long long capacity) {
     if (ms_geometry_bad(bmin, bmax, resolution, dims) || !origin || !end || capacity < 0 || (capacity > 0 && !ijk_out)) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): bad arguments");
-    const long long n = ms_ray_host(bmin, bmax, resolution, dims, origin, end, ijk_out, capacity);
+    const long long n = ms_ray_host(map_geom(bmin, bmax, resolution, dims), origin, end, ijk_out, capacity);
     return n < 0 ? isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "scan (host form): the origin lies outside the map") : n;
 }

@@ -19,15 +19,29 @@ namespace isdf {
 
 constexpr int MS_TICKS_LOG2 = 10;           // ticks per voxel: 1024
 
+// The map's metric geometry: the one way it travels through the map's queries and the scan, to kernels (by value) and host forms alike.
+struct MapGeom { double bmin[3], bmax[3], res; int dims[3]; };
+
+// of the host forms' arguments (ms_geometry_bad is their validator); the ctx's: map_query.hpp's map_geom(DevGrid)
+inline MapGeom map_geom(const double bmin[3], const double bmax[3], double res, const int dims[3]) {
+    MapGeom M;
+    for (int a = 0; a < 3; a++) { M.bmin[a] = bmin[a]; M.bmax[a] = bmax[a]; M.dims[a] = dims[a]; }
+    M.res = res;
+    return M;
+}
+
+// the linear index of voxel v (z fastest)
+MU_HD size_t map_voxel(const MapGeom &M, const int v[3]) { return ((size_t)v[0] * M.dims[1] + v[1]) * M.dims[2] + v[2]; }
+
 // false: outside the map by grid_index's test (a coordinate < bmin or > bmax), or not finite; q is untouched then
-MU_HD bool ms_quantize(const double bmin[3], const double bmax[3], double res, const int dims[3], double x, double y, double z, int q[3]) {
+MU_HD bool ms_quantize(const MapGeom &M, double x, double y, double z, int q[3]) {
     const double p[3] = {x, y, z};
     for (int a = 0; a < 3; a++)
-        if (!(p[a] >= bmin[a] && p[a] <= bmax[a])) return false;            // (a NaN fails both comparisons)
+        if (!(p[a] >= M.bmin[a] && p[a] <= M.bmax[a])) return false;            // (a NaN fails both comparisons)
     for (int a = 0; a < 3; a++) {
-        const double u = (p[a] - bmin[a]) / res;
+        const double u = (p[a] - M.bmin[a]) / M.res;
         const double t = floor(u * 1024.0);
-        const long long top = ((long long)dims[a] << MS_TICKS_LOG2) - 1;
+        const long long top = ((long long)M.dims[a] << MS_TICKS_LOG2) - 1;
         q[a] = t >= (double)top ? (int)top : (int)(long long)t;            // 0 <= t: p >= bmin
     }
     return true;
@@ -79,11 +93,10 @@ inline bool ms_geometry_bad(const double bmin[3], const double bmax[3], double r
 
 // the visited voxels of one ray into ijk_out (capacity x 3, nullable when capacity is 0); returns their number, 0: the end point lies
 // outside the map, -1: the origin does
-inline long long ms_ray_host(const double bmin[3], const double bmax[3], double res, const int32_t dims[3], const double origin[3], const float end[3],
-                             int32_t *ijk_out, long long capacity) {
+inline long long ms_ray_host(const MapGeom &M, const double origin[3], const float end[3], int32_t *ijk_out, long long capacity) {
     int qo[3], qe[3];
-    if (!ms_quantize(bmin, bmax, res, dims, origin[0], origin[1], origin[2], qo)) return -1;
-    if (!ms_quantize(bmin, bmax, res, dims, (double)end[0], (double)end[1], (double)end[2], qe)) return 0;
+    if (!ms_quantize(M, origin[0], origin[1], origin[2], qo)) return -1;
+    if (!ms_quantize(M, (double)end[0], (double)end[1], (double)end[2], qe)) return 0;
     MsRay r;
     ms_ray_begin(qo, qe, r);
     long long k = 0;
@@ -103,17 +116,17 @@ struct MsSets {
 
 // The sets of one scan: visited[v] = 1 for every voxel some ray visits, a hit ray's end voxel excepted; hits[v] = the multiplicity of
 // v in H.  F = visited and not in H.  false: the origin lies outside the map.
-inline bool ms_sets_host(const double bmin[3], const double bmax[3], double res, const int32_t dims[3], const double origin[3], const float *xyz,
-                         const uint8_t *hit, long long n_rays, std::vector<uint8_t> &free_set, std::vector<uint32_t> &hits, MsSets &S) {
-    const size_t n_vox = (size_t)dims[0] * dims[1] * dims[2];
+inline bool ms_sets_host(const MapGeom &M, const double origin[3], const float *xyz, const uint8_t *hit, long long n_rays, std::vector<uint8_t> &free_set,
+                         std::vector<uint32_t> &hits, MsSets &S) {
+    const size_t n_vox = (size_t)M.dims[0] * M.dims[1] * M.dims[2];
     free_set.assign(n_vox, 0);
     hits.assign(n_vox, 0);
     S = MsSets();
     for (int a = 0; a < 3; a++) { S.ray.lo[a] = 0x7FFFFFFF; S.ray.hi[a] = -1; }
     int qo[3], qe[3];
-    if (!ms_quantize(bmin, bmax, res, dims, origin[0], origin[1], origin[2], qo)) return false;
+    if (!ms_quantize(M, origin[0], origin[1], origin[2], qo)) return false;
     for (long long i = 0; i < n_rays; i++) {
-        if (!ms_quantize(bmin, bmax, res, dims, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], qe)) { S.n_skipped++; continue; }
+        if (!ms_quantize(M, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], qe)) { S.n_skipped++; continue; }
         const bool is_hit = !hit || hit[i] != 0;
         MsRay r;
         ms_ray_begin(qo, qe, r);
@@ -124,7 +137,7 @@ inline bool ms_sets_host(const double bmin[3], const double bmax[3], double res,
             if (hi > S.ray.hi[a]) S.ray.hi[a] = hi;
         }
         for (;;) {
-            const size_t a = ((size_t)r.v[0] * dims[1] + r.v[1]) * dims[2] + r.v[2];
+            const size_t a = map_voxel(M, r.v);
             const bool last = ms_ray_done(r);
             if (last && is_hit) { hits[a]++; S.n_hits++; }
             else free_set[a] = 1;

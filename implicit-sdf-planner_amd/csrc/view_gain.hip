@@ -11,8 +11,9 @@
 // Every walk has at most 1 + nx + ny + nz voxels and stays in the box of its two end voxels: no bounds test, no read outside the grids.
 // The lanes of a wavefront finish at different lengths, as the cast's do; a workgroup is two wavefronts for the cast's reason.
 // Nothing here writes to the ctx's map, its known grid, its products or its flags.
-#include "isdf_ctx.hpp"
+#include "map_query.hpp"
 #include "view_gain_host.hpp"
+#include "dev_block_sum.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -24,7 +25,7 @@ constexpr int VG_COUNTERS = 5;
 constexpr int VG_SETUP_BLOCK = 64;
 constexpr long long VG_MAX_CHUNK = 65535;       // gridDim.y
 
-__global__ __launch_bounds__(VG_SETUP_BLOCK) void vg_setup_kernel(const double *__restrict__ poses, long long n_views, DcRays base, VgMap M, VgView *__restrict__ views,
+__global__ __launch_bounds__(VG_SETUP_BLOCK) void vg_setup_kernel(const double *__restrict__ poses, long long n_views, DcRays base, MapGeom M, VgView *__restrict__ views,
                                                                   long long *__restrict__ rows) {
     const long long j = (long long)blockIdx.x * VG_SETUP_BLOCK + threadIdx.x;
     if (j >= n_views) return;
@@ -39,16 +40,10 @@ __global__ __launch_bounds__(VG_SETUP_BLOCK) void vg_setup_kernel(const double *
     row[1] = row[3] = row[4] = row[5] = row[6] = row[7] = 0;
 }
 
-__device__ __forceinline__ unsigned long long vg_wave_sum(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;                   // lane 0 holds the sum
-}
-
 // rows: the call's, view0 the chunk's first view; seen: the chunk's grids, n_words each, cleared
-__global__ __launch_bounds__(VG_BLOCK) void vg_gain_kernel(const VgView *__restrict__ views, long long view0, VgMap M, const uint8_t *__restrict__ occ,
+__global__ __launch_bounds__(VG_BLOCK) void vg_gain_kernel(const VgView *__restrict__ views, long long view0, MapGeom M, const uint8_t *__restrict__ occ,
                                                            const unsigned *__restrict__ known, unsigned *seen, long long n_words, const uint16_t *__restrict__ zero_image,
                                                            long long *rows) {
-    __shared__ unsigned long long s_sum[VG_WAVES][VG_COUNTERS];
     const long long j = view0 + blockIdx.y;
     const VgView &V = views[j];
     if (!V.ok) return;          // (uniform)
@@ -70,18 +65,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_gain_kernel(const VgView *__restr
         if (!vg_ray(V, M, zero_image, occ, iu, iv, n_hits, steps_total, n_rays_unknown, visit)) n_skipped++;
     }
     const long long cnt[VG_COUNTERS] = {gain, n_skipped, n_hits, steps_total, n_rays_unknown};
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int q = 0; q < VG_COUNTERS; q++) {
-        const unsigned long long s = vg_wave_sum((unsigned long long)cnt[q]);
-        if (lane == 0) s_sum[wave][q] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < VG_COUNTERS) {
-        unsigned long long s = 0;
-        for (int w = 0; w < VG_WAVES; w++) s += s_sum[w][threadIdx.x];
-        const int word = threadIdx.x == 0 ? 1 : threadIdx.x + 2;          // gain: word 1; the other four: words 3 .. 6
-        if (s) atomicAdd((unsigned long long *)(rows + VG_ROW * j + word), s);
-    }
+    const unsigned long long s = block_sum<VG_COUNTERS, VG_WAVES>(cnt);
+    const int word = threadIdx.x == 0 ? 1 : threadIdx.x + 2;          // gain: word 1; the other four: words 3 .. 6
+    if (s) atomicAdd((unsigned long long *)(rows + VG_ROW * j + word), s);          // (s is 0 beyond the counters)
 }
 
 }  // namespace isdf
@@ -95,6 +81,7 @@ struct ViewGainState {
     isdf::DevBuf<uint16_t> d_zero;
     isdf::PinBuf<int64_t> h_rows;
     isdf::DevEvents<2> ev;
+    int ready(isdf_ctx *c) { return ev.ready(c); }
 };
 
 using namespace isdf;
@@ -115,10 +102,9 @@ extern "C" void isdf_view_gain_sizes(int sizes_out[2]) {
 namespace {
 
 // what the device and the host forms check and set up alike (c may be null: the host form)
-int gain_setup(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, long long n_views, const isdf_view_gain_params *params, const void *rows, const VgMap &M,
+int gain_setup(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, long long n_views, const isdf_view_gain_params *params, const void *rows, const MapGeom &M,
                isdf_view_gain_params &P, DcRays &base) {
-    isdf_view_gain_params_default(&P);
-    if (params) P = *params;
+    P = map_query::resolve(params, isdf_view_gain_params_default);
     const double k[4] = {cam ? cam->fx : 0.0, cam ? cam->fy : 0.0, cam ? cam->cx : 0.0, cam ? cam->cy : 0.0};
     if (!cam || cam->width < 1 || cam->width > DC_MAX_DIM || cam->height < 1 || cam->height > DC_MAX_DIM || !dc_finite(k, 4) || !(cam->fx > 0.0) || !(cam->fy > 0.0))
         return isdf_fail(c, ISDF_ERR_INVALID_ARG, "view gain: bad camera intrinsics");
@@ -129,32 +115,17 @@ int gain_setup(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, lon
     return ISDF_OK;
 }
 
-VgMap gain_map(const double bmin[3], const double bmax[3], double res, const int dims[3]) {
-    VgMap M;
-    for (int a = 0; a < 3; a++) { M.bmin[a] = bmin[a]; M.bmax[a] = bmax[a]; M.dims[a] = dims[a]; }
-    M.res = res;
-    return M;
-}
-
-int gain_check(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, long long n_views, const isdf_view_gain_params *params, const void *rows, VgMap &M,
+int gain_check(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, long long n_views, const isdf_view_gain_params *params, const void *rows, MapGeom &M,
                isdf_view_gain_params &P, DcRays &base) {
-    const DevGrid &G = c->grid;
-    const int dims[3] = {G.X, G.Y, G.Z};
-    M = gain_map(G.bmin, G.bmax, G.res, dims);          // (without a map: zeros, and the state check below refuses)
+    M = map_geom(c->grid);          // (without a map: zeros, and the state check below refuses)
     ISDF_TRY(gain_setup(c, cam, poses, n_views, params, rows, M, P, base));
-    if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the view gain is not offered on a multi-device ctx");
-    if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, "the view gain needs an occupancy grid (isdf_set_grid with ISDF_GRID_OCCUPANCY, or isdf_set_pointcloud)");
-    if (!c->known.have) return isdf_fail(c, ISDF_ERR_STATE, "the view gain needs a known grid (isdf_map_known_enable)");
-    return ISDF_OK;
-}
-
-int gain_state(isdf_ctx *c, ViewGainState **out) {
-    ISDF_TRY(c->vgn.make(c, out));
-    return (*out)->ev.ready(c);
+    ISDF_TRY(map_query::single_device(c, "the view gain is not offered on a multi-device ctx"));
+    ISDF_TRY(map_query::has_occupancy(c, "the view gain"));
+    return map_query::has_known(c, "the view gain needs a known grid (isdf_map_known_enable)");
 }
 
 // the launches on st: the table, then per chunk the clear of its seen grids and the gain kernel; with want_info the rows' pinned copy too
-int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const VgMap &M, const isdf_view_gain_params &P, const double *d_poses, long long n_views,
+int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const MapGeom &M, const isdf_view_gain_params &P, const double *d_poses, long long n_views,
              long long *d_rows, bool want_info, int *chunks_out, hipStream_t st) {
     const long long n_words = (long long)c->known.n_words;
     const long long fit = P.scratch_bytes / (4 * n_words);
@@ -165,10 +136,8 @@ int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const VgMap &M, 
         ISDF_TRY(S->d_seen.reserve(c, (size_t)per_chunk * (size_t)n_words));
         ISDF_TRY(S->d_zero.reserve(c, (size_t)base.width * base.height));
     }
-    if (want_info) {
-        ISDF_TRY(S->h_rows.reserve(c, (size_t)std::max<long long>(n_views, 1) * VG_ROW));
-        HIPCHK(c, hipEventRecord(S->ev[0], st));
-    }
+    if (want_info) ISDF_TRY(S->h_rows.reserve(c, (size_t)std::max<long long>(n_views, 1) * VG_ROW));
+    ISDF_TRY(map_query::count_begin(c, want_info, S->ev, st));
     if (n_views > 0) {
         HIPCHK(c, hipMemsetAsync(S->d_zero, 0, (size_t)base.width * base.height * sizeof(uint16_t), st));
         hipLaunchKernelGGL(vg_setup_kernel, dim3((unsigned)((n_views + VG_SETUP_BLOCK - 1) / VG_SETUP_BLOCK)), dim3(VG_SETUP_BLOCK), 0, st, d_poses, n_views, base, M,
@@ -185,9 +154,8 @@ int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const VgMap &M, 
             ++*chunks_out;
         }
     }
-    if (!want_info) return ISDF_OK;
-    HIPCHK(c, hipEventRecord(S->ev[1], st));
-    if (n_views > 0) HIPCHK(c, hipMemcpyAsync(S->h_rows.get(), d_rows, (size_t)n_views * VG_ROW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ISDF_TRY(map_query::count_end(c, want_info, S->ev, st));
+    if (want_info && n_views > 0) HIPCHK(c, hipMemcpyAsync(S->h_rows.get(), d_rows, (size_t)n_views * VG_ROW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     return ISDF_OK;
 }
 
@@ -205,34 +173,28 @@ void gain_info(const int64_t *rows, long long n_views, const DcRays &base, int c
 extern "C" int isdf_view_gain_device(isdf_ctx *c, const isdf_depth_camera *cam, const double *d_poses, long long n_views, const isdf_view_gain_params *params,
                                      int64_t *d_rows_out, isdf_view_gain_info *info_out, void *stream) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    VgMap M;
+    MapGeom M;
     isdf_view_gain_params P;
     DcRays base;
     ISDF_TRY(gain_check(c, cam, d_poses, n_views, params, d_rows_out, M, P, base));
     if (((uintptr_t)d_rows_out & 7u) != 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "the rows of the view gain must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
     ViewGainState *S;
-    ISDF_TRY(gain_state(c, &S));
+    ISDF_TRY(map_query::state_of(c, c->vgn, &S));
     const hipStream_t st = (hipStream_t)stream;
     int chunks = 0;
     ISDF_TRY(gain_run(c, S, base, M, P, d_poses, n_views, (long long *)d_rows_out, info_out != nullptr, &chunks, st));
-    if (info_out) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        gain_info(S->h_rows.get(), n_views, base, chunks, S->ev.ms(0, 1), info_out);
-    }
-    return ISDF_OK;
+    return map_query::info_after(c, info_out, st, [&](isdf_view_gain_info *out) { gain_info(S->h_rows.get(), n_views, base, chunks, S->ev.ms(0, 1), out); });
 }
 
 extern "C" int isdf_view_gain(isdf_ctx *c, const isdf_depth_camera *cam, const double *poses, long long n_views, const isdf_view_gain_params *params, int64_t *rows_out,
                               isdf_view_gain_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
-    VgMap M;
+    MapGeom M;
     isdf_view_gain_params P;
     DcRays base;
     ISDF_TRY(gain_check(c, cam, poses, n_views, params, rows_out, M, P, base));
-    HIPCHK(c, hipSetDevice(c->device));
     ViewGainState *S;
-    ISDF_TRY(gain_state(c, &S));
+    ISDF_TRY(map_query::state_of(c, c->vgn, &S));
     const hipStream_t st = c->stream;
     ISDF_TRY(S->d_poses.reserve(c, (size_t)n_views * 12));
     ISDF_TRY(S->d_rows.reserve(c, (size_t)n_views * VG_ROW));
@@ -249,7 +211,7 @@ extern "C" long long isdf_view_gain_host(const uint32_t *bits, const uint8_t *oc
                                          const isdf_depth_camera *cam, const double *poses, long long n_views, const isdf_view_gain_params *params, int64_t *rows_out,
                                          isdf_view_gain_info *info_out) {
     if (ms_geometry_bad(bmin, bmax, resolution, dims) || !bits || !occ) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "view gain (host form): bad arguments");
-    const VgMap M = gain_map(bmin, bmax, resolution, dims);
+    const MapGeom M = map_geom(bmin, bmax, resolution, dims);
     isdf_view_gain_params P;
     DcRays base;
     ISDF_TRY(gain_setup(nullptr, cam, poses, n_views, params, rows_out, M, P, base));

@@ -29,8 +29,6 @@ namespace isdf {
 constexpr int VG_ROW = 8;               // int64 per view
 constexpr int VG_SCORED = 0, VG_POSE_OUTSIDE = 1;
 
-struct VgMap { double bmin[3], bmax[3], res; int dims[3]; };
-
 // one view: its rays and its origin's tick
 struct VgView {
     DcRays Q;
@@ -39,12 +37,12 @@ struct VgView {
 };
 
 // what every view of a call shares: dc_rays_setup of the camera with a pose that the views replace
-inline void vg_rays_base(int width, int height, double fx, double fy, double cx, double cy, int su, int sv, double max_range, const VgMap &M, DcRays &Q) {
+inline void vg_rays_base(int width, int height, double fx, double fy, double cx, double cy, int su, int sv, double max_range, const MapGeom &M, DcRays &Q) {
     const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    dc_rays_setup(width, height, fx, fy, cx, cy, eye, DC_FORMAT_U16_MM, su, sv, 0.0, max_range, 1, M.bmin, M.bmax, M.res, Q);
+    dc_rays_setup(width, height, fx, fy, cx, cy, eye, DC_FORMAT_U16_MM, su, sv, 0.0, max_range, 1, M, Q);
 }
 
-MU_HD void vg_view_setup(const DcRays &base, const VgMap &M, const double pose[12], VgView &V) {
+MU_HD void vg_view_setup(const DcRays &base, const MapGeom &M, const double pose[12], VgView &V) {
     V.Q = base;
     bool finite = true;
     for (int i = 0; i < 3; i++) {
@@ -53,7 +51,7 @@ MU_HD void vg_view_setup(const DcRays &base, const VgMap &M, const double pose[1
     }
     for (int i = 0; i < 12; i++) finite = finite && (pose[i] - pose[i] == 0.0);
     V.qo[0] = V.qo[1] = V.qo[2] = 0;
-    V.ok = finite && ms_quantize(M.bmin, M.bmax, M.res, M.dims, pose[3], pose[7], pose[11], V.qo) ? 1 : 0;
+    V.ok = finite && ms_quantize(M, pose[3], pose[7], pose[11], V.qo) ? 1 : 0;
 }
 
 struct VgCounts { long long gain = 0, n_skipped = 0, n_hits = 0, steps_total = 0, n_rays_unknown = 0; };
@@ -61,14 +59,14 @@ struct VgCounts { long long gain = 0, n_skipped = 0, n_hits = 0, steps_total = 0
 // One ray of a scored view.  zero_image: width x height uint16 zeros, the image with no return at any pixel.  visit(a) is called once
 // for every voxel of V(ray), a = (x * ny + y) * nz + z, in the order of the walk, and returns whether K[a] = 0.  false: the ray is skipped.
 template <typename Visit>
-MU_HD bool vg_ray(const VgView &V, const VgMap &M, const void *zero_image, const uint8_t *occ, int iu, int iv, long long &n_hits, long long &steps_total,
+MU_HD bool vg_ray(const VgView &V, const MapGeom &M, const void *zero_image, const uint8_t *occ, int iu, int iv, long long &n_hits, long long &steps_total,
                   long long &n_rays_unknown, Visit &&visit) {
     float e[3];
     uint8_t hit;
     (void)dc_ray(V.Q, zero_image, iu, iv, e, hit);
     int qe[3], row[MR_ROW];
-    if (!ms_quantize(M.bmin, M.bmax, M.res, M.dims, (double)e[0], (double)e[1], (double)e[2], qe)) return false;
-    mr_cast_walk(occ, M.dims, V.qo, qe, false, row);
+    if (!ms_quantize(M, (double)e[0], (double)e[1], (double)e[2], qe)) return false;
+    mr_cast_walk(occ, M, V.qo, qe, false, row);
     n_hits += row[0] == MR_HIT;
     steps_total += row[1];
     // the same walk again, as far as the cast went
@@ -76,7 +74,7 @@ MU_HD bool vg_ray(const VgView &V, const VgMap &M, const void *zero_image, const
     ms_ray_begin(V.qo, qe, r);
     bool unknown = false;
     for (int s = 0;; s++) {
-        if (visit(((size_t)r.v[0] * M.dims[1] + r.v[1]) * M.dims[2] + r.v[2])) unknown = true;
+        if (visit(map_voxel(M, r.v))) unknown = true;
         if (s == row[1]) break;
         ms_ray_step(r);
     }
@@ -85,7 +83,7 @@ MU_HD bool vg_ray(const VgView &V, const VgMap &M, const void *zero_image, const
 }
 
 // ---- host form: rows_out = n_views x 8; seen: a plain bit vector per view, K's layout
-inline void vg_gain_host(const uint32_t *bits, const uint8_t *occ, const VgMap &M, const DcRays &base, const double *poses, long long n_views, int64_t *rows_out) {
+inline void vg_gain_host(const uint32_t *bits, const uint8_t *occ, const MapGeom &M, const DcRays &base, const double *poses, long long n_views, int64_t *rows_out) {
     const long long n_words = mk_words((long long)M.dims[0] * M.dims[1] * M.dims[2]);
     const std::vector<uint16_t> zero((size_t)base.width * base.height, 0);
     std::vector<uint32_t> seen;

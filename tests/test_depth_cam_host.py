@@ -279,7 +279,7 @@ int main() {
     std::vector<int32_t> img(depth, depth + (size_t)K.width * K.height);
     for (int variant = 0; variant < 2; variant++) {
         DcRays Q;
-        dc_rays_setup(K.width, K.height, 12.0, 12.0, 8.3, 5.7, pose, DC_FORMAT_I32_MM, variant ? 2 : 1, variant ? 3 : 1, 0.0, variant ? 6.0 : HUGE_VAL, variant, bmin, bmax, res, Q);
+        dc_rays_setup(K.width, K.height, 12.0, 12.0, 8.3, 5.7, pose, DC_FORMAT_I32_MM, variant ? 2 : 1, variant ? 3 : 1, 0.0, variant ? 6.0 : HUGE_VAL, variant, map_geom(bmin, bmax, res, dims), Q);
         const size_t rows = (size_t)Q.nu * Q.nv;
         std::vector<float> ends(3 * rows, 0.f);
         std::vector<uint8_t> hit(rows, 9);

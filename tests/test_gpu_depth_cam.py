@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import depth_cam_reference as ref
+import test_block_sum_cases as bs
 import test_gpu_map_scan as ms
 import test_gpu_map_update as mu
 from depth_cam_reference import AXIS_POSE, BMAX, BMIN, DIMS, MAP_POSE, RES, SMALL, WIDE
@@ -247,3 +248,25 @@ def test_the_loop_from_poses_alone(pkg, product_lib):
     assert sa != (0, 0, 0)
     mu._same(mu._products(pkg, a), mu._products(pkg, b))
     assert np.array_equal(a.get_grid(pkg.capi.GRID_OCCUPANCY)[1], b.get_grid(pkg.capi.GRID_OCCUPANCY)[1])
+
+
+# ---- 5. the counters at the edges of the block sum: a lane, a wavefront, a workgroup of 256
+@pytest.mark.parametrize("n", bs.DC_SIZES)
+def test_render_counters_equal_the_host_form_at_the_block_sums_edges(pkg, product_lib, n):
+    cloud = bs.dc_cloud()[:n]
+    _, info = _render_both(pkg, product_lib, _bare(pkg), bs.DC_CAM, AXIS_POSE, cloud, **bs.DC_RENDER_PARAMS)
+    print(f"\nn = {n}: {ref.info_counts(info, ref.RENDER_COUNTS)}")
+    assert info.n_points == n and info.n_pixels_set > 0
+
+
+@pytest.mark.parametrize("size", bs.DC_RAYS_IMAGES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_rays_counters_equal_the_host_form_at_the_block_sums_edges(pkg, product_lib, size):
+    eng = _bare(pkg)
+    eng.set_grid(np.zeros(DIMS, dtype=np.uint8), BMIN, RES, pkg.capi.GRID_OCCUPANCY, bmax=BMAX)          # the geometry is all the rays need
+    cam = _cam(pkg, dict(bs.DC_CAM, width=size[0], height=size[1]))
+    image = bs.dc_depth_image(*size)
+    ends, hit, info = eng.depth_rays(cam, MAP_POSE, image, **bs.DC_RAYS_PARAMS)
+    want, want_hit, wi = pkg.engine.depth_rays_host(cam, MAP_POSE, image, BMIN, BMAX, RES, DIMS, lib=product_lib, **bs.DC_RAYS_PARAMS)
+    assert np.array_equal(_bits(ends), _bits(want)) and np.array_equal(hit, want_hit)
+    print(f"\n{size}: {ref.info_counts(info, ref.RAYS_COUNTS)}")
+    assert ref.info_counts(info, ref.RAYS_COUNTS) == ref.info_counts(wi, ref.RAYS_COUNTS) and info.n_pixels == size[0] * size[1]

@@ -9,11 +9,12 @@ import functools
 import numpy as np
 import pytest
 
+import test_block_sum_cases as bs
 import test_gpu_map_update as mu
 from test_gpu_map_clear import N, _same_report
 from test_gpu_map_scan import _scene, _watched
 from test_gpu_map_update import BMAX, BMIN, DIMS, RES, _products, _same
-from test_map_raycast_host import BLOCK_ONLY_A, BLOCK_ONLY_B, NAMED_ENDS, NAMED_ORIGINS, SENSOR, closed_loop_scene
+from test_map_raycast_host import BLOCK_ONLY_A, BLOCK_ONLY_B, FLAT, NAMED_ENDS, NAMED_ORIGINS, SENSOR, closed_loop_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -232,3 +233,18 @@ def test_closed_loop(pkg, product_lib):
     print(f"\n{len(ends)} rays, {dropped} dropped, {hit.sum()} hits; the scan freed {freed.sum()} voxels and occupied {born.sum()}")
     assert freed[BLOCK_ONLY_B].sum() >= 5 and born[BLOCK_ONLY_A].sum() >= 5
     assert info.clear.n_cleared_voxels == freed.sum() and info.update.n_new_voxels == born.sum()
+
+
+# ---- 8. the counters at the edges of the block sum: a lane, a wavefront, a workgroup of 128
+@pytest.mark.parametrize("n", bs.CAST_SIZES)
+def test_counters_equal_the_host_form_at_the_block_sums_edges(pkg, product_lib, n):
+    g = FLAT
+    occ, origins, ends = bs.cast_case()
+    eng = pkg.Engine(pkg.synth.default_config(pkg.capi.V1_SWEPT))
+    eng.set_grid(occ, g.bmin, g.res, pkg.capi.GRID_OCCUPANCY, bmax=g.bmax)
+    want, want_hits = pkg.engine.raycast_host(occ, g.bmin, g.bmax, g.res, origins[:n], ends[:n], per_ray_origin=True, lib=product_lib)
+    rows, info = eng.map_raycast(origins[:n], ends[:n], per_ray_origin=True)
+    assert rows.shape == (n, 8) and rows.tobytes() == want.tobytes()
+    got = {k: int(getattr(info, k)) for k in ("n_rays",) + bs.CAST_COUNTERS}
+    print(f"\nn = {n}: {got}")
+    assert got == bs.cast_counts(want) and info.n_hits == want_hits

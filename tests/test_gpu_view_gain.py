@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import known_reference as kr
+import test_block_sum_cases as bs
 from test_gpu_map_known import RES, _grid_engine, _random_fills
 from test_gpu_map_update import _live
 from test_map_known_host import GRIDS, IDS
@@ -175,3 +176,16 @@ def test_a_known_map_offers_nothing(pkg, product_lib):
     rows, info = _same(pkg, product_lib, eng, cam, poses[::-1], stride=1, max_range_m=40.0)     # reversed: the first two are not scored
     assert rows[:, 0].tolist() == [1, 1, 0, 0, 0, 0] and not rows[:, 1].any() and not rows[:, 6].any()
     assert (info.best_view, info.best_gain, info.gain_total, info.n_scored) == (2, 0, 0, 4)
+
+
+# ---- the counters at the edges of the block sum: a lane, a wavefront, a workgroup of 128; the second view returns before it
+@pytest.mark.parametrize("n_rays", sorted(bs.VG_STRIDES))
+def test_counters_equal_the_host_form_at_the_block_sums_edges(pkg, product_lib, n_rays):
+    eng, _ = _grid_engine(pkg, bs.VG_DIMS)
+    eng.map_known_enable(True)
+    eng.map_known_fill(bs.VG_KNOWN_BOX, 1)
+    cam = pkg.engine.depth_camera(**bs.VG_CAM)
+    rows, info = _same(pkg, product_lib, eng, cam, bs.vg_poses(pkg, bs.VG_DIMS, RES), stride=bs.VG_STRIDES[n_rays], max_range_m=bs.VG_RANGE)
+    print(f"\n{n_rays} rays: {rows[0]}")
+    assert rows[0, 2] == n_rays and rows[0, 1] > 0 and (rows[1] == [1, 0, 0, 0, 0, 0, 0, 0]).all() and info.n_scored == 1
+    assert n_rays == 1 or (rows[0, 1:7] > 0).all()                  # every counter counts (tests/test_block_sum_cases.py, on the same map)

@@ -364,7 +364,7 @@ int main() {
     for (int test_origin = 0; test_origin < 2; test_origin++) {
         std::vector<int32_t> rows((size_t)n * MR_ROW, -7);
         MrCounts K;
-        if (!mr_cast_host(occ.data(), bmin, bmax, res, dims, origins.data(), true, ends.data(), n, test_origin != 0, rows.data(), K)) { std::printf("FAILED: per-ray origins\n"); return 1; }
+        if (!mr_cast_host(occ.data(), map_geom(bmin, bmax, res, dims), origins.data(), true, ends.data(), n, test_origin != 0, rows.data(), K)) { std::printf("FAILED: per-ray origins\n"); return 1; }
         if (K.n_skipped + K.n_origin_outside + K.n_hits + K.n_clear != n) { std::printf("FAILED: counts\n"); return 1; }
         for (long long i = 0; i < n; i++) {
             for (int w = 0; w < MR_ROW; w++) std::printf("%d ", rows[(size_t)i * MR_ROW + w]);
@@ -376,7 +376,7 @@ int main() {
     std::vector<int32_t> rows((size_t)n * MR_ROW, -7);
     MrCounts K;
     const double outside[3] = {bmax[0] + 1.0, bmax[1], bmax[2]};
-    if (mr_cast_host(occ.data(), bmin, bmax, res, dims, outside, false, ends.data(), n, false, rows.data(), K)) { std::printf("FAILED: origin\n"); return 1; }
+    if (mr_cast_host(occ.data(), map_geom(bmin, bmax, res, dims), outside, false, ends.data(), n, false, rows.data(), K)) { std::printf("FAILED: origin\n"); return 1; }
     for (int32_t w : rows) if (w != -7) { std::printf("FAILED: rows written\n"); return 1; }
     std::printf("ok\n");
     return 0;

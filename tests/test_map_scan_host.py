@@ -328,9 +328,9 @@ static const Case cases[] = {
 
 int main() {
     for (const Case &c : cases) {
-        const long long n = ms_ray_host(c.bmin, c.bmax, c.res, c.dims, c.origin, c.end, nullptr, 0);
+        const long long n = ms_ray_host(map_geom(c.bmin, c.bmax, c.res, c.dims), c.origin, c.end, nullptr, 0);
         std::vector<int32_t> ijk((size_t)(n > 0 ? 3 * n : 1), -1);
-        if (n > 0 && ms_ray_host(c.bmin, c.bmax, c.res, c.dims, c.origin, c.end, ijk.data(), n) != n) { std::printf("FAILED: two counts\n"); return 1; }
+        if (n > 0 && ms_ray_host(map_geom(c.bmin, c.bmax, c.res, c.dims), c.origin, c.end, ijk.data(), n) != n) { std::printf("FAILED: two counts\n"); return 1; }
         std::printf("%lld:", n);
         for (long long k = 0; k < n; k++) std::printf(" %d %d %d", ijk[3 * k], ijk[3 * k + 1], ijk[3 * k + 2]);
         std::printf("\n");
@@ -348,15 +348,15 @@ int main() {
         std::vector<uint8_t> free_set;
         std::vector<uint32_t> hits;
         MsSets S;
-        if (!ms_sets_host(g.bmin, g.bmax, g.res, g.dims, g.origin, xyz.data(), hit.data(), (long long)hit.size(), free_set, hits, S)) { std::printf("FAILED: sets\n"); return 1; }
+        if (!ms_sets_host(map_geom(g.bmin, g.bmax, g.res, g.dims), g.origin, xyz.data(), hit.data(), (long long)hit.size(), free_set, hits, S)) { std::printf("FAILED: sets\n"); return 1; }
         long long f = 0, h = 0;
         for (size_t a = 0; a < free_set.size(); a++) { f += free_set[a]; h += hits[a]; if (free_set[a] && hits[a]) { std::printf("FAILED: F and H meet\n"); return 1; } }
         if (f != S.n_free || h != S.n_hits || S.n_skipped + S.n_hits > (long long)hit.size()) { std::printf("FAILED: counts\n"); return 1; }
         for (int a = 0; a < 3; a++) if (S.ray.lo[a] < 0 || S.ray.hi[a] >= g.dims[a]) { std::printf("FAILED: box\n"); return 1; }
         int32_t two[6];
-        if (ms_ray_host(cases[0].bmin, cases[0].bmax, cases[0].res, cases[0].dims, cases[0].origin, cases[0].end, two, 2) < 2) { std::printf("FAILED: capacity\n"); return 1; }
+        if (ms_ray_host(map_geom(cases[0].bmin, cases[0].bmax, cases[0].res, cases[0].dims), cases[0].origin, cases[0].end, two, 2) < 2) { std::printf("FAILED: capacity\n"); return 1; }
         const double outside[3] = {g.bmax[0] + 1.0, g.bmax[1], g.bmax[2]};
-        if (ms_ray_host(g.bmin, g.bmax, g.res, g.dims, outside, g.end, two, 2) != -1) { std::printf("FAILED: origin\n"); return 1; }
+        if (ms_ray_host(map_geom(g.bmin, g.bmax, g.res, g.dims), outside, g.end, two, 2) != -1) { std::printf("FAILED: origin\n"); return 1; }
     }
     std::printf("ok\n");
     return 0;

@@ -214,7 +214,7 @@ int main() {
             if (x % 10 < 6) k[a >> 5] |= 1u << (a & 31);
             occ[a] = (x >> 20) % 5 == 0 ? (uint8_t)(1 + (x >> 30) % 200) : 0;
         }
-        VgMap M;
+        MapGeom M;
         for (int a = 0; a < 3; a++) { M.bmin[a] = 0.0; M.bmax[a] = 0.5 * dims[a]; M.dims[a] = dims[a]; }
         M.res = 0.5;
         for (int s = 1; s <= 3; s += 2) {
