@@ -217,8 +217,24 @@ class IsdfFrontierClusterInfo(C.Structure):
                 ("largest_label", C.c_int64), ("frontier_ms", C.c_double), ("label_ms", C.c_double), ("stats_ms", C.c_double)]
 
 
+class IsdfViewCandidatesParams(C.Structure):
+    """isdf_view_candidates_params (include/isdf_accel.h)."""
+    _fields_ = [("gain", IsdfViewGainParams), ("clearance_voxels", C.c_int32), ("k_best", C.c_int32), ("min_gain", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class IsdfViewCandidatesInfo(C.Structure):
+    """isdf_view_candidates_info (include/isdf_accel.h)."""
+    _fields_ = [("n_targets", C.c_int64), ("n_offsets", C.c_int64), ("n_candidates", C.c_int64), ("n_kept", C.c_int64), ("n_bad", C.c_int64),
+                ("n_occupied", C.c_int64), ("n_unknown", C.c_int64), ("n_close", C.c_int64), ("n_blocked", C.c_int64), ("n_scored", C.c_int64),
+                ("best_target", C.c_int64), ("best_candidate", C.c_int64), ("best_gain", C.c_int64), ("chunks", C.c_int32), ("reserved", C.c_int32),
+                ("filter_ms", C.c_double), ("gain_ms", C.c_double), ("select_ms", C.c_double)]
+
+
 # int64 per cluster: label, size, lo xyz, hi xyz, sum xyz, rep_voxel, rep_d2, first_pos, 0, 0
 FRONTIER_CLUSTER_ROW = 16
+# int64 per candidate view: status, eye_voxel, los_steps, gain, n_hits, steps_total, n_rays_unknown, rank; the statuses in the order of the tests
+VIEW_CANDIDATE_ROW = 8
+VIEW_CAND_KEPT, VIEW_CAND_BAD, VIEW_CAND_OCCUPIED, VIEW_CAND_UNKNOWN, VIEW_CAND_CLOSE, VIEW_CAND_BLOCKED = 0, 1, 2, 3, 4, 5
 VIEW_GAIN_ROW = 8                       # int64 per view: status, gain, n_rays, n_skipped, n_hits, steps_total, n_rays_unknown, 0
 
 
@@ -454,6 +470,7 @@ EXPORTED_SYMBOLS = [
     "isdf_known_merge_host", "isdf_known_shift_host", "isdf_known_fill_host", "isdf_known_frontier_host",
     "isdf_view_gain_params_default", "isdf_view_gain_sizes", "isdf_view_gain", "isdf_view_gain_device", "isdf_view_gain_host",
     "isdf_frontier_cluster_params_default", "isdf_frontier_cluster_sizes", "isdf_map_frontier_clusters", "isdf_known_clusters_host",
+    "isdf_view_candidates_params_default", "isdf_view_candidates_sizes", "isdf_view_candidates", "isdf_view_candidates_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -823,6 +840,19 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfFrontierClusterParams), C.sizeof(IsdfFrontierClusterInfo)]:
         raise RuntimeError(f"isdf_frontier_cluster structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfFrontierClusterParams), C.sizeof(IsdfFrontierClusterInfo)]}")
+    kp, ki = C.POINTER(IsdfViewCandidatesParams), C.POINTER(IsdfViewCandidatesInfo)
+    lib.isdf_view_candidates_params_default.argtypes = [kp]
+    lib.isdf_view_candidates_params_default.restype = None
+    lib.isdf_view_candidates_sizes.argtypes = [ip]
+    lib.isdf_view_candidates_sizes.restype = None
+    lib.isdf_view_candidates.argtypes = [C.c_void_p, C.POINTER(IsdfDepthCamera), C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, kp, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, ki]
+    lib.isdf_view_candidates_host.argtypes = [C.c_void_p, C.c_void_p, dp, dp, C.c_double, i3, C.POINTER(IsdfDepthCamera), C.c_void_p, C.c_longlong, C.c_void_p,
+                                              C.c_longlong, kp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ki]
+    lib.isdf_view_candidates_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfViewCandidatesParams), C.sizeof(IsdfViewCandidatesInfo)]:
+        raise RuntimeError(f"isdf_view_candidates structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfViewCandidatesParams), C.sizeof(IsdfViewCandidatesInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

@@ -11,8 +11,7 @@
 // Every walk has at most 1 + nx + ny + nz voxels and stays in the box of its two end voxels: no bounds test, no read outside the grids.
 // The lanes of a wavefront finish at different lengths, as the cast's do; a workgroup is two wavefronts for the cast's reason.
 // Nothing here writes to the ctx's map, its known grid, its products or its flags.
-#include "map_query.hpp"
-#include "view_gain_host.hpp"
+#include "view_gain_run.hpp"
 #include "dev_block_sum.hpp"
 #include <algorithm>
 #include <cstring>
@@ -72,17 +71,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_gain_kernel(const VgView *__restr
 
 }  // namespace isdf
 
-// the host-pointer form's staging, the per-view table, the chunk's seen grids, the image without a return and the rows' pinned copy
-struct ViewGainState {
-    isdf::DevBuf<double> d_poses;
-    isdf::DevBuf<isdf::VgView> d_views;
-    isdf::DevBuf<long long> d_rows;
-    isdf::DevBuf<unsigned> d_seen;
-    isdf::DevBuf<uint16_t> d_zero;
-    isdf::PinBuf<int64_t> h_rows;
-    isdf::DevEvents<2> ev;
-    int ready(isdf_ctx *c) { return ev.ready(c); }
-};
+// (ViewGainState: view_gain_run.hpp, with the declarations of gain_setup and gain_run - the candidate views score through them)
 
 using namespace isdf;
 
@@ -99,7 +88,7 @@ extern "C" void isdf_view_gain_sizes(int sizes_out[2]) {
     sizes_out[0] = (int)sizeof(isdf_view_gain_params); sizes_out[1] = (int)sizeof(isdf_view_gain_info);
 }
 
-namespace {
+namespace isdf {
 
 // what the device and the host forms check and set up alike (c may be null: the host form)
 int gain_setup(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, long long n_views, const isdf_view_gain_params *params, const void *rows, const MapGeom &M,
@@ -115,6 +104,10 @@ int gain_setup(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, lon
     return ISDF_OK;
 }
 
+}  // namespace isdf
+
+namespace {
+
 int gain_check(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, long long n_views, const isdf_view_gain_params *params, const void *rows, MapGeom &M,
                isdf_view_gain_params &P, DcRays &base) {
     M = map_geom(c->grid);          // (without a map: zeros, and the state check below refuses)
@@ -123,6 +116,10 @@ int gain_check(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, lon
     ISDF_TRY(map_query::has_occupancy(c, "the view gain"));
     return map_query::has_known(c, "the view gain needs a known grid (isdf_map_known_enable)");
 }
+
+}  // namespace
+
+namespace isdf {
 
 // the launches on st: the table, then per chunk the clear of its seen grids and the gain kernel; with want_info the rows' pinned copy too
 int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const MapGeom &M, const isdf_view_gain_params &P, const double *d_poses, long long n_views,
@@ -158,6 +155,10 @@ int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const MapGeom &M
     if (want_info && n_views > 0) HIPCHK(c, hipMemcpyAsync(S->h_rows.get(), d_rows, (size_t)n_views * VG_ROW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     return ISDF_OK;
 }
+
+}  // namespace isdf
+
+namespace {
 
 void gain_info(const int64_t *rows, long long n_views, const DcRays &base, int chunks, double ms, isdf_view_gain_info *out) {
     const VgBest B = vg_best(rows, n_views);

@@ -819,6 +819,66 @@ def view_gain_host(bits, occ, bmin, bmax, res, cam, poses, lib=None, **params):
     return rows, info
 
 
+def view_ring_offsets(radii, n_azimuth, heights):
+    """Eye offsets round a target for view_candidates: for every radius r, azimuth a = 2 pi j / n_azimuth (j = 0 .. n_azimuth - 1) and
+    height h the offset (r cos a, r sin a, h), float64 [len(radii) * n_azimuth * len(heights), 3], radius slowest, height fastest.  The
+    C ABI takes offsets as data and does no trigonometry; this is where the caller's NumPy does it."""
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    h = np.asarray(heights, dtype=np.float64).reshape(-1)
+    a = 2.0 * np.pi * np.arange(int(n_azimuth), dtype=np.float64) / float(n_azimuth)
+    out = np.zeros((r.size, a.size, h.size, 3), dtype=np.float64)
+    out[..., 0] = (r[:, None] * np.cos(a)[None, :])[:, :, None]
+    out[..., 1] = (r[:, None] * np.sin(a)[None, :])[:, :, None]
+    out[..., 2] = h[None, None, :]
+    return np.ascontiguousarray(out.reshape(-1, 3))
+
+
+def _view_cand_params(lib, clearance_voxels=None, k_best=None, min_gain=None, **gain):
+    p = capi.IsdfViewCandidatesParams()
+    lib.isdf_view_candidates_params_default(C.byref(p))
+    p.gain = _view_gain_params(lib, **gain)
+    if clearance_voxels is not None:
+        p.clearance_voxels = int(clearance_voxels)
+    if k_best is not None:
+        p.k_best = int(k_best)
+    if min_gain is not None:
+        p.min_gain = int(min_gain)
+    return p
+
+
+def _view_cand_arrays(targets, offsets, k_best):
+    """(targets [n, 3], offsets [m, 3], and the four outputs sized for them)"""
+    t = np.ascontiguousarray(np.asarray(targets, dtype=np.float64).reshape(-1, 3))
+    o = np.ascontiguousarray(np.asarray(offsets, dtype=np.float64).reshape(-1, 3))
+    n = t.shape[0] * o.shape[0]
+    return (t, o, np.zeros((n, capi.VIEW_CANDIDATE_ROW), dtype=np.int64), np.zeros((n, 12), dtype=np.float64), np.zeros((t.shape[0], 8), dtype=np.int64),
+            np.full((t.shape[0], max(int(k_best), 0)), -1, dtype=np.int64))
+
+
+def view_candidates_host(bits, occ, bmin, bmax, res, cam, targets, offsets, lib=None, **params):
+    """isdf_view_candidates_host: candidate c = i * len(offsets) + k has eye = targets[i] + offsets[k]; each is tested (1 bad, 2 occupied,
+    3 unknown, 4 close, 5 blocked, 0 kept) against K = bits - a known grid's words over occ [X, Y, Z] - and the map (bmin, bmax, res), the
+    kept ones are posed looking at their target, scored by the view gain and ranked per target, in plain host code.  params:
+    clearance_voxels, k_best, min_gain, and the view gain's stride, max_range_m.  Returns (cand int64 [n, 8] = (status, eye_voxel,
+    los_steps, gain, n_hits, steps_total, n_rays_unknown, rank), poses float64 [n, 12], target rows int64 [n_targets, 8] = (n_kept, n_bad,
+    n_occupied, n_unknown, n_close, n_blocked, best_candidate, best_gain), best int64 [n_targets, k_best] padded with -1,
+    IsdfViewCandidatesInfo)."""
+    lib = lib or capi.load_library()
+    o8 = np.ascontiguousarray(occ, dtype=np.uint8)
+    w, d = _known_args(bits, o8.shape)
+    b0, b1, _, _ = _scan_geometry(bmin, bmax, o8.shape, np.zeros(3))
+    p = _view_cand_params(lib, **params)
+    t, o, cand, poses, rows, best = _view_cand_arrays(targets, offsets, p.k_best)
+    info = capi.IsdfViewCandidatesInfo()
+    rc = lib.isdf_view_candidates_host(w.ctypes.data_as(C.c_void_p), o8.ctypes.data_as(C.c_void_p), _p(b0), _p(b1), float(res), d, C.byref(cam),
+                                       t.ctypes.data_as(C.c_void_p), t.shape[0], o.ctypes.data_as(C.c_void_p), o.shape[0], C.byref(p),
+                                       cand.ctypes.data_as(C.c_void_p), poses.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+                                       best.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc < 0:
+        raise IsdfError(int(rc), "isdf_view_candidates_host")
+    return cand, poses, rows, best, info
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -1344,6 +1404,29 @@ class Engine:
         self._check(self.lib.isdf_view_gain_device(self.h, C.byref(cam), C.c_void_p(d_poses.data_ptr()), n, C.byref(p), C.c_void_p(d_rows.data_ptr()),
                                                    None if info is None else C.byref(info), C.c_void_p(st)))
         return info
+
+    # ---- candidate views (csrc/view_cand.hip)
+    def view_candidates(self, cam, targets, offsets, **params):
+        """isdf_view_candidates: eyes targets[i] + offsets[k] (metres; view_ring_offsets builds rings) tested on the device for being a
+        safe, seen place from which the target is visible, the survivors posed, scored by the view gain and ranked per target, read-only.
+        params: clearance_voxels, k_best, min_gain, and the view gain's stride, max_range_m, scratch_bytes.  Returns what
+        view_candidates_host returns: (cand, poses, target_rows, best, IsdfViewCandidatesInfo)."""
+        p = _view_cand_params(self.lib, **params)
+        t, o, cand, poses, rows, best = _view_cand_arrays(targets, offsets, p.k_best)
+        info = capi.IsdfViewCandidatesInfo()
+        self._check(self.lib.isdf_view_candidates(self.h, C.byref(cam), t.ctypes.data_as(C.c_void_p), t.shape[0], o.ctypes.data_as(C.c_void_p), o.shape[0], C.byref(p),
+                                                  cand.ctypes.data_as(C.c_void_p), poses.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+                                                  best.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return cand, poses, rows, best, info
+
+    def next_views(self, cam, offsets, connectivity=26, min_size=1, **params):
+        """One turn of a next-best-view loop: map_frontier_clusters, the centres of the clusters' rep_voxel cells (cluster_points) as
+        targets, view_candidates round them.  Returns (cluster rows, cand, poses, target_rows, best, IsdfViewCandidatesInfo); the best
+        eye overall is poses[info.best_candidate] (-1: no candidate qualified), a goal for frontend_field_build."""
+        _, _, rows, _ = self.map_frontier_clusters(connectivity=connectivity, min_size=min_size)
+        _, bmin, _ = self.get_grid(capi.GRID_OCCUPANCY)
+        _, reps = cluster_points(rows, bmin, self._map_res, self._grid_dims())          # (the resolution set_grid / set_pointcloud gave)
+        return (rows,) + self.view_candidates(cam, reps, offsets, **params)
 
     def map_counts(self):
         """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""

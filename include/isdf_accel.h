@@ -1874,7 +1874,8 @@ int isdf_known_frontier_host(const uint32_t *bits, const uint8_t *occ, const int
  * NULL.  isdf_view_gain_device: d_poses and d_rows_out are device memory, the work goes on `stream`; with info_out == NULL nothing is
  * handed over and nothing synchronised, with it `stream` is synchronised once - isdf_map_raycast_device's rule.
  * Not offered: a pessimistic gain in which unknown voxels block; a range- or angle-weighted gain; a gain kept incrementally across
- * scans.  Candidates: isdf_map_frontier_clusters below gives the frontier's clusters and a voxel of each to look at. */
+ * scans.  Candidates: isdf_map_frontier_clusters below gives the frontier's clusters and a voxel of each to look at, isdf_view_candidates
+ * the eyes round each, posed and scored. */
 typedef struct isdf_view_gain_params {
     int32_t stride_u, stride_v;   /* default 4, 4; >= 1 */
     double  max_range_m;          /* required: finite, > 0 (default 5.0) */
@@ -1941,7 +1942,7 @@ long long isdf_view_gain_host(const uint32_t *bits, const uint8_t *occ, const do
  * (isdf_debug_live_bytes).  Two runs give the same bytes: the components' roots are their lowest positions whatever the order of the
  * device's atomics, and every statistic is an integer sum, minimum or maximum.
  * Not offered: a device-pointer form of the outputs; clusters kept incrementally across scans; splitting a large cluster (by its
- * principal axis, say); the eye position of a candidate view; unknown space treated as an obstacle. */
+ * principal axis, say); unknown space treated as an obstacle.  The eye positions of candidate views: isdf_view_candidates below. */
 typedef struct isdf_frontier_cluster_params {
     int32_t connectivity;         /* 6, 18 or 26 (default 26) */
     int32_t reserved;
@@ -1963,6 +1964,89 @@ int isdf_map_frontier_clusters(isdf_ctx *ctx, const uint32_t *bits_in, const isd
  * ISDF_ERR_INVALID_ARG (a null set, bad dims, the bad arguments above) as isdf_map_frontier_clusters. */
 int isdf_known_clusters_host(const uint32_t *set_bits, const int32_t dims[3], const isdf_frontier_cluster_params *params, int64_t *vox_out, int32_t *labels_out,
                              long long vox_capacity, int64_t *rows_out, long long row_capacity, isdf_frontier_cluster_info *info_out);
+
+/* ---- candidate views: eyes round each target, tested, posed, scored and ranked -------------------------------------- */
+/* The link between isdf_map_frontier_clusters (targets) and isdf_view_gain (scores): for each target a set of eye positions is tested on
+ * the device for being a safe, seen place from which the target is visible, the survivors are posed looking at the target, the view
+ * gain scores them without leaving the device and the best few per target come back.  Everything but the three times is an integer or
+ * an fp64 value of a fixed order of IEEE operations, so isdf_view_candidates_host gives the device's bytes.
+ *   INPUTS.  camera: the depth camera's rule.  targets: n_targets x 3 doubles, metres.  offsets: n_offsets x 3 doubles, metres.
+ *   Candidate c = i * n_offsets + k has eye = target_i + offset_k, one fp64 addition per component.  The ABI does no trigonometry: the
+ *   offsets are data (a ring is engine.view_ring_offsets' business), so no byte depends on a libm.
+ *   STATUS of a candidate: the first test that fails, in this order.
+ *     1 bad.  A component of the target or of the eye is not finite; or the scan's quantisation (isdf_integrate_scan above) refuses the
+ *       target or the eye: a coordinate < bmin or > bmax; or, with d = target - eye, n2 = d_x^2 + d_y^2 + d_z^2 (summed left to right)
+ *       is 0 or not finite.
+ *     2 occupied.  The occupancy byte of the eye's voxel is not 0.
+ *     3 unknown.  K is 0 at the eye's voxel.
+ *     4 close.  Some voxel of the cube of Chebyshev radius clearance_voxels round the eye's voxel, clipped to the grid, is occupied or
+ *       unknown: a safe eye stands in seen, free space.  Radius 0 adds nothing to tests 2 and 3.
+ *     5 blocked.  The walk of isdf_map_raycast with test_origin_voxel = 0 from the eye's tick to the target's tick (both quantised as the
+ *       scan's points are) ends at an occupied voxel that is not the target's own voxel.  A hit at the target's own voxel is visible: a
+ *       target may be a surface voxel.
+ *     0 kept.
+ *   POSE of a kept candidate, fp64, nothing contracted into an FMA, sums left to right in the written order, sqrt and division the IEEE
+ *   ones: n = sqrt(n2); z = d / n; x0 = (z_y, -z_x, 0), h = sqrt(x0_x^2 + x0_y^2); if h <= 1e-9: x0 = (0, z_z, -z_y), h = sqrt(x0_y^2 +
+ *   x0_z^2); x = x0 / h; y = (z_y x_z - z_z x_y, z_z x_x - z_x x_z, z_x x_y - z_y x_x); the pose is rows (x_a, y_a, z_a, eye_a) - what
+ *   engine.look_at(eye, target) with the default up gives, restated so that two implementations round alike.
+ *   GAIN.  The isdf_view_gain row of that pose with params.gain, to the byte.
+ *   SELECTION.  Per target, the kept candidates with gain >= min_gain, ordered by gain descending, ties to the lower k; the first k_best
+ *   of them are the target's best.
+ *   OUTPUTS, all nullable, host memory (the host-pointer form is the only device form).
+ *     cand_out: n_candidates x 8 int64, {status, eye_voxel, los_steps, gain, n_hits, steps_total, n_rays_unknown, rank}.  eye_voxel =
+ *       (x * ny + y) * nz + z, -1 for status 1; los_steps: the step count of test 5's walk, -1 where test 5 was not reached; words 3 - 6:
+ *       the gain row's words 1, 4, 5 and 6, 0 unless the status is 0; rank: the place in the target's best list, -1: not in it.
+ *     poses_out: n_candidates x 12 doubles, all zero unless the status is 0.
+ *     target_out: n_targets x 8 int64, {n_kept, n_bad, n_occupied, n_unknown, n_close, n_blocked, best_candidate, best_gain}; the last two
+ *       are -1 and 0 when no candidate qualified.
+ *     best_out: n_targets x k_best int64 candidate indices, padded with -1.
+ *     info_out: the counts over all candidates; n_scored, the candidates the gain scored (every kept one: a kept eye is finite and
+ *       inside the map); the view gain's chunks (0: nothing kept); best_target, best_candidate and best_gain over all targets, ties to the
+ *       lowest candidate index (-1, -1, 0: none qualified); filter_ms (tests, poses, compaction), gain_ms and select_ms: device time from
+ *       events on the ctx's stream, 0 in the host form and where the stage did not run.
+ *   ERRORS, all before anything is launched, in this order: the view gain's own argument errors for camera and params.gain;
+ *   ISDF_ERR_INVALID_ARG for clearance_voxels outside [0, 8], k_best outside [1, 64], min_gain < 0, a negative n_targets or n_offsets,
+ *   n_offsets > 2^20, n_targets * n_offsets > 2^31 - 1, a null targets or offsets with a positive count; ISDF_ERR_UNSUPPORTED on a
+ *   multi-device ctx; ISDF_ERR_STATE without an occupancy grid, then without a known grid.  Zero targets or zero offsets is legal: nothing
+ *   is launched and no output array is written (info_out is filled: zeros, the three best words -1, -1, 0).
+ * The call is read-only: K, the occupancy, `merges`, epochs, a kept field, an armed watch and every kept report are untouched.  The
+ * scratch (its own and the view gain's) grows only: a second call of a size allocates nothing (isdf_debug_live_bytes).  Two hand-overs
+ * per call: the count of kept candidates, which sizes the gain's launches (the gain is never launched over a rejected candidate, each
+ * view costs a cleared `seen` grid; with nothing kept nothing more is launched), and the results.  Two runs give the same bytes: the
+ * counters are integer sums and the selection is a reduction without atomics.  min_gain is an integer, as every gain is.
+ * Not offered: a device-pointer form; a yaw sweep at a fixed eye; ranking by travel cost (read isdf_frontend_field_value at the best
+ * eyes); eyes tested against the robot's configuration space rather than a voxel cube; a pessimistic or weighted gain; candidates kept
+ * across scans. */
+typedef struct isdf_view_candidates_params {
+    isdf_view_gain_params gain;   /* strides, max_range_m, scratch_bytes: isdf_view_gain's, with its defaults */
+    int32_t clearance_voxels;     /* default 1; in [0, 8] */
+    int32_t k_best;               /* default 3; in [1, 64] */
+    int64_t min_gain;             /* default 1; >= 0 */
+    int32_t reserved[4];
+} isdf_view_candidates_params;
+
+typedef struct isdf_view_candidates_info {
+    int64_t n_targets, n_offsets, n_candidates;
+    int64_t n_kept, n_bad, n_occupied, n_unknown, n_close, n_blocked;
+    int64_t n_scored;
+    int64_t best_target, best_candidate, best_gain;
+    int32_t chunks, reserved;
+    double  filter_ms, gain_ms, select_ms;
+} isdf_view_candidates_info;
+
+#define ISDF_VIEW_CANDIDATE_ROW 8
+void isdf_view_candidates_params_default(isdf_view_candidates_params *p);       /* null-safe */
+void isdf_view_candidates_sizes(int sizes_out[2]);                              /* null-safe; sizeof of the params and of the info */
+int isdf_view_candidates(isdf_ctx *ctx, const isdf_depth_camera *camera, const double *targets, long long n_targets, const double *offsets, long long n_offsets,
+                         const isdf_view_candidates_params *params, int64_t *cand_out, double *poses_out, int64_t *target_out, int64_t *best_out,
+                         isdf_view_candidates_info *info_out);
+/* plain host code, no ctx, no device: bits = K's words, occ = nx ny nz occupancy bytes, the map's geometry as isdf_raycast_host takes it;
+ * gain.scratch_bytes is ignored.  ISDF_OK, or ISDF_ERR_INVALID_ARG (a null bits or occ, a bad geometry, the bad arguments above) with
+ * nothing written. */
+int isdf_view_candidates_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
+                              const isdf_depth_camera *camera, const double *targets, long long n_targets, const double *offsets, long long n_offsets,
+                              const isdf_view_candidates_params *params, int64_t *cand_out, double *poses_out, int64_t *target_out, int64_t *best_out,
+                              isdf_view_candidates_info *info_out);
 
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
