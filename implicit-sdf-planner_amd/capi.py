@@ -230,6 +230,19 @@ class IsdfViewCandidatesInfo(C.Structure):
                 ("filter_ms", C.c_double), ("gain_ms", C.c_double), ("select_ms", C.c_double)]
 
 
+class IsdfViewSelectParams(C.Structure):
+    """isdf_view_select_params (include/isdf_accel.h)."""
+    _fields_ = [("gain", IsdfViewGainParams), ("k_select", C.c_int32), ("reserved0", C.c_int32), ("min_gain", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class IsdfViewSelectInfo(C.Structure):
+    """isdf_view_select_info (include/isdf_accel.h)."""
+    _fields_ = [("n_views", C.c_int64), ("n_scored", C.c_int64), ("n_selected", C.c_int64), ("gain_selected", C.c_int64), ("gain_solo_sum", C.c_int64),
+                ("best_single_gain", C.c_int64), ("list_words", C.c_int64), ("chunks", C.c_int32), ("reserved", C.c_int32), ("gain_ms", C.c_double),
+                ("lists_ms", C.c_double), ("select_ms", C.c_double)]
+
+
+VIEW_SELECT_ROW = 4                     # int64 per round: view, marginal, cumulative, overlap; a round that did not happen: -1, 0, 0, 0
 # int64 per cluster: label, size, lo xyz, hi xyz, sum xyz, rep_voxel, rep_d2, first_pos, 0, 0
 FRONTIER_CLUSTER_ROW = 16
 # int64 per candidate view: status, eye_voxel, los_steps, gain, n_hits, steps_total, n_rays_unknown, rank; the statuses in the order of the tests
@@ -471,6 +484,7 @@ EXPORTED_SYMBOLS = [
     "isdf_view_gain_params_default", "isdf_view_gain_sizes", "isdf_view_gain", "isdf_view_gain_device", "isdf_view_gain_host",
     "isdf_frontier_cluster_params_default", "isdf_frontier_cluster_sizes", "isdf_map_frontier_clusters", "isdf_known_clusters_host",
     "isdf_view_candidates_params_default", "isdf_view_candidates_sizes", "isdf_view_candidates", "isdf_view_candidates_host",
+    "isdf_view_select_params_default", "isdf_view_select_sizes", "isdf_view_select", "isdf_view_select_host",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -853,6 +867,18 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfViewCandidatesParams), C.sizeof(IsdfViewCandidatesInfo)]:
         raise RuntimeError(f"isdf_view_candidates structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfViewCandidatesParams), C.sizeof(IsdfViewCandidatesInfo)]}")
+    sp, si = C.POINTER(IsdfViewSelectParams), C.POINTER(IsdfViewSelectInfo)
+    lib.isdf_view_select_params_default.argtypes = [sp]
+    lib.isdf_view_select_params_default.restype = None
+    lib.isdf_view_select_sizes.argtypes = [ip]
+    lib.isdf_view_select_sizes.restype = None
+    lib.isdf_view_select.argtypes = [C.c_void_p, C.POINTER(IsdfDepthCamera), C.c_void_p, C.c_longlong, sp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, si]
+    lib.isdf_view_select_host.argtypes = [C.c_void_p, C.c_void_p, dp, dp, C.c_double, i3, C.POINTER(IsdfDepthCamera), C.c_void_p, C.c_longlong, sp, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, si]
+    lib.isdf_view_select_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfViewSelectParams), C.sizeof(IsdfViewSelectInfo)]:
+        raise RuntimeError(f"isdf_view_select structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfViewSelectParams), C.sizeof(IsdfViewSelectInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

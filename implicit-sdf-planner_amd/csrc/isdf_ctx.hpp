@@ -32,7 +32,8 @@ struct DepthCamState;           // depth_cam.hip: staging of the depth camera's 
 struct ViewGainState;           // view_gain.hip: the view gain's poses, per-view table, rows, seen grids and zero image
 struct FrontierClusterState;    // frontier_cluster.hip: the clusters' union-find, numbering and row scratch, the record and the pinned outputs
 struct ViewCandState;           // view_cand.hip: the candidate views' rows, poses, dense table, targets' rows, the record and the pinned outputs
-int isdf_traj_check_ready(isdf_ctx *c);               // traj_check.hip: what isdf_traj_check needs of the ctx (shape, occupancy grid), or the error
+struct ViewSelectState;         // view_select.hip: the view selection's rows, per-view lists of set words, marginals, claimed grid, the record and the pinned outputs
+int isdf_traj_check_ready(isdf_ctx *c);             // traj_check.hip: what isdf_traj_check needs of the ctx (shape, occupancy grid), or the error
 
 // frontend_field.hip: the record of one in-place change of the cost-to-go field (voxels closed: the repair; opened: the reopen),
 // one 64-byte line, uploaded empty before the change's kernels and read back after them
@@ -105,6 +106,7 @@ struct isdf_ctx {
     Lazy<ViewGainState> vgn;                    // isdf_view_gain*: own scratch (grows only)
     Lazy<FrontierClusterState> fcl;             // isdf_map_frontier_clusters: own scratch (grows only)
     Lazy<ViewCandState> vcd;                    // isdf_view_candidates: own scratch (grows only); it scores through vgn's
+    Lazy<ViewSelectState> vsl;                  // isdf_view_select: own scratch (grows only); it scores through vgn's
     DevBuf<unsigned> d_bits; bool bits_dirty = true;
     // the known grid (map_known.hip): one bit per voxel, 1 = some ray has visited it or the caller declared it known.  `on`
     // outlives maps (isdf_map_known_enable); d_bits holds n_words dwords while `have`; d_shift is where a window shift writes before the

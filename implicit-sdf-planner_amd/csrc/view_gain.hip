@@ -121,9 +121,10 @@ int gain_check(isdf_ctx *c, const isdf_depth_camera *cam, const void *poses, lon
 
 namespace isdf {
 
-// the launches on st: the table, then per chunk the clear of its seen grids and the gain kernel; with want_info the rows' pinned copy too
+// the launches on st: the table, then per chunk the clear of its seen grids and the gain kernel (and after_chunk, where one is given); with
+// want_info the rows' pinned copy too
 int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const MapGeom &M, const isdf_view_gain_params &P, const double *d_poses, long long n_views,
-             long long *d_rows, bool want_info, int *chunks_out, hipStream_t st) {
+             long long *d_rows, bool want_info, int *chunks_out, hipStream_t st, const GainChunkHook *after_chunk) {
     const long long n_words = (long long)c->known.n_words;
     const long long fit = P.scratch_bytes / (4 * n_words);
     const long long per_chunk = std::max<long long>(1, std::min<long long>(std::min<long long>(fit, n_views), VG_MAX_CHUNK));
@@ -149,6 +150,7 @@ int gain_run(isdf_ctx *c, ViewGainState *S, const DcRays &base, const MapGeom &M
                                (const unsigned *)c->known.d_bits.get(), S->d_seen.get(), n_words, (const uint16_t *)S->d_zero.get(), d_rows);
             HIPCHK(c, hipGetLastError());
             ++*chunks_out;
+            if (after_chunk) ISDF_TRY((*after_chunk)(v0, nv, S->d_seen.get(), n_words));
         }
     }
     ISDF_TRY(map_query::count_end(c, want_info, S->ev, st));

@@ -879,6 +879,45 @@ def view_candidates_host(bits, occ, bmin, bmax, res, cam, targets, offsets, lib=
     return cand, poses, rows, best, info
 
 
+def _view_select_params(lib, k_select=None, min_gain=None, **gain):
+    p = capi.IsdfViewSelectParams()
+    lib.isdf_view_select_params_default(C.byref(p))
+    p.gain = _view_gain_params(lib, **gain)
+    if k_select is not None:
+        p.k_select = int(k_select)
+    if min_gain is not None:
+        p.min_gain = int(min_gain)
+    return p
+
+
+def _view_select_arrays(poses, k_select, dims):
+    """(poses [n, 12] and the four outputs sized for them)"""
+    P = _view_poses(poses)
+    return (P, np.zeros((P.shape[0], capi.VIEW_GAIN_ROW), dtype=np.int64), np.zeros((max(int(k_select), 0), capi.VIEW_SELECT_ROW), dtype=np.int64),
+            np.zeros(P.shape[0], dtype=np.int64), np.zeros(known_words(dims), dtype=np.uint32))
+
+
+def view_select_host(bits, occ, bmin, bmax, res, cam, poses, lib=None, **params):
+    """isdf_view_select_host: the greedy coverage selection of up to k_select of the poses (n x 12 doubles, look_at's) by their joint gain -
+    each round the view that sees the most voxels unknown in K = bits (a known grid's words over occ [X, Y, Z]) that no view picked so far
+    sees - in plain host code.  params: k_select, min_gain, and the view gain's stride, max_range_m.  Returns (rows int64 [n, 8], the view
+    gain's; select int64 [k_select, 4] = (view, marginal, cumulative, overlap), (-1, 0, 0, 0) for a round that did not happen; round int64
+    [n], -1: not picked; claimed uint32 words = K | the picked views' voxels; IsdfViewSelectInfo)."""
+    lib = lib or capi.load_library()
+    o8 = np.ascontiguousarray(occ, dtype=np.uint8)
+    w, d = _known_args(bits, o8.shape)
+    b0, b1, _, _ = _scan_geometry(bmin, bmax, o8.shape, np.zeros(3))
+    p = _view_select_params(lib, **params)
+    P, rows, select, rnd, claimed = _view_select_arrays(poses, p.k_select, o8.shape)
+    info = capi.IsdfViewSelectInfo()
+    rc = lib.isdf_view_select_host(w.ctypes.data_as(C.c_void_p), o8.ctypes.data_as(C.c_void_p), _p(b0), _p(b1), float(res), d, C.byref(cam),
+                                   P.ctypes.data_as(C.c_void_p), P.shape[0], C.byref(p), rows.ctypes.data_as(C.c_void_p), select.ctypes.data_as(C.c_void_p),
+                                   rnd.ctypes.data_as(C.c_void_p), claimed.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc < 0:
+        raise IsdfError(int(rc), "isdf_view_select_host")
+    return rows, select, rnd, claimed, info
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -1427,6 +1466,30 @@ class Engine:
         _, bmin, _ = self.get_grid(capi.GRID_OCCUPANCY)
         _, reps = cluster_points(rows, bmin, self._map_res, self._grid_dims())          # (the resolution set_grid / set_pointcloud gave)
         return (rows,) + self.view_candidates(cam, reps, offsets, **params)
+
+    # ---- the view selection (csrc/view_select.hip)
+    def view_select(self, cam, poses, **params):
+        """isdf_view_select: the greedy coverage selection of up to k_select of the poses by their joint gain, every round on the device,
+        read-only.  params: k_select, min_gain, and the view gain's stride, max_range_m, scratch_bytes.  Returns what view_select_host
+        returns: (rows, select, round, claimed, IsdfViewSelectInfo)."""
+        p = _view_select_params(self.lib, **params)
+        P, rows, select, rnd, claimed = _view_select_arrays(poses, p.k_select, self._grid_dims())
+        info = capi.IsdfViewSelectInfo()
+        self._check(self.lib.isdf_view_select(self.h, C.byref(cam), P.ctypes.data_as(C.c_void_p), P.shape[0], C.byref(p), rows.ctypes.data_as(C.c_void_p),
+                                              select.ctypes.data_as(C.c_void_p), rnd.ctypes.data_as(C.c_void_p), claimed.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return rows, select, rnd, claimed, info
+
+    def next_view_set(self, cam, offsets, k_select=4, select_min_gain=1, connectivity=26, min_size=1, **params):
+        """next_views, then view_select over the poses of all targets' best lists (in the order of the lists): the next k_select places to
+        look, chosen by what they add together rather than each alone.  params go to next_views (clearance_voxels, k_best, min_gain, and
+        the view gain's, which the selection shares); select_min_gain is the selection's min_gain.  Returns (poses float64 [n_selected, 12]
+        in the order picked, their marginal gains int64 [n_selected], their candidate indices int64 [n_selected], IsdfViewSelectInfo)."""
+        _, _, poses, _, best, _ = self.next_views(cam, offsets, connectivity=connectivity, min_size=min_size, **params)
+        listed = best[best >= 0]
+        gain = {k: v for k, v in params.items() if k in ("stride", "max_range_m", "scratch_bytes")}
+        _, select, _, _, info = self.view_select(cam, poses[listed], k_select=k_select, min_gain=select_min_gain, **gain)
+        picked = select[:info.n_selected]
+        return np.ascontiguousarray(poses[listed[picked[:, 0]]]), picked[:, 1].copy(), listed[picked[:, 0]], info
 
     def map_counts(self):
         """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""

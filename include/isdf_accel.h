@@ -2048,6 +2048,73 @@ int isdf_view_candidates_host(const uint32_t *bits, const uint8_t *occ, const do
                               const isdf_view_candidates_params *params, int64_t *cand_out, double *poses_out, int64_t *target_out, int64_t *best_out,
                               isdf_view_candidates_info *info_out);
 
+/* ---- the view selection: k views of a pose list by their joint gain, greedy coverage -------------------------------- */
+/* The gains of isdf_view_gain and isdf_view_candidates are each view's alone and do not add up: the best eyes of one target, and of
+ * neighbouring clusters, look at the same pocket of unknown space.  isdf_view_select picks an ordered set of up to k_select views of a
+ * pose list by the standard greedy coverage rule - the view that sees the most voxels which are unknown today and which no view picked
+ * so far sees, then that view's voxels are claimed - with every round on the device, from sets the gain kernel has built; the rays are
+ * walked once per view, not once per round.  Integers only, so isdf_view_select_host gives the device's bytes.
+ *   SETS.  poses: n_views x 12 doubles, as isdf_view_gain takes them.  A view j whose isdf_view_gain row (with params.gain) has status
+ *   0 is SCORED: S_j is that call's set and U_j = {v in S_j : K[v] = 0}, so |U_j| is the row's gain.  A view of status 1 has an empty U_j
+ *   and is never picked.
+ *   ROUNDS.  C_0 is empty.  In round r = 0 .. k_select - 1: m_j = |U_j \ C_r| for every scored view not picked so far; j* is the lowest
+ *   index among the largest m_j - the largest key ((m_j + 1) << 24) | (2^24 - 1 - j); a marginal is below 2^36 and j below 2^24, so the
+ *   key is below 2^61.  If no such view is left, or m_j* < min_gain, the selection ends with n_selected = r.  Otherwise round r picks j*
+ *   and C_{r+1} = C_r | U_j*.  With min_gain = 0 a view whose marginal is 0 is picked like any other.
+ *   OUTPUTS, all nullable, host memory.
+ *     rows_out: n_views x 8 int64, the isdf_view_gain row of each pose, to the byte.
+ *     select_out: k_select x 4 int64, per round {view, marginal, cumulative, overlap}: marginal = m_j*, cumulative = |C_{r+1}|, overlap =
+ *       the view's own gain - marginal (what earlier picks had claimed of it).  Rounds that did not happen are {-1, 0, 0, 0}.
+ *     round_out: n_views int64, the round in which the view was picked, or -1.
+ *     claimed_out: ceil(nx ny nz / 32) words, K | C_final in K's layout: the known grid the map would have after those views, if nothing
+ *       new turns out to be occupied.
+ *     info_out: n_views; n_scored; n_selected; gain_selected = the last cumulative (0: none); gain_solo_sum = the sum of the picked
+ *       views' own gains, so the double counting shows beside gain_selected; best_single_gain = the largest gain of a scored view;
+ *       list_words = the non-zero words of all U_j (the device's list has one 8-byte entry for each); chunks = the view gain's;
+ *       lists_ms = device time of building the lists (count, scan, fill), select_ms = of the rounds and of claimed_out's kernel, gain_ms
+ *       = the bracket round the view gain's launches less lists_ms (it holds the chunks' hand-overs) - events on the ctx's stream, 0 in
+ *       the host form and with n_views = 0.
+ *   ERRORS, all before anything is launched, in this order: everything isdf_view_gain refuses for camera, params.gain, n_views and a
+ *   null poses, in its order; ISDF_ERR_INVALID_ARG for k_select < 1 or min_gain < 0; ISDF_ERR_INVALID_ARG for n_views > 2^24 (the key's
+ *   room); ISDF_ERR_UNSUPPORTED on a multi-device ctx; ISDF_ERR_STATE without an occupancy grid, then without a known grid.  n_views = 0
+ *   is legal: nothing is launched, select_out is padded, claimed_out = K and the info is filled.
+ * The device keeps no dense set: after each chunk of the view gain, while its `seen` grids are live, every view's non-zero words are
+ * compacted into a segment of {word index, bits} entries of one list; a round streams the segments against the claimed grid.  One
+ * hand-over per chunk (its entry total, which sizes the list), none between the rounds - a `done` flag on the device makes the kernels of
+ * the rounds after the last return at once; at most min(k_select, n_views) rounds are launched -, one at the end.  The call is
+ * read-only: K, the occupancy, `merges`, epochs, a kept field, an armed watch and every kept report are untouched.  The scratch (its own
+ * and the view gain's) grows only and the list keeps its content when it grows: a second call of a size allocates nothing
+ * (isdf_debug_live_bytes).  Two runs give the same bytes: the order of a segment's entries depends on atomics and nothing reads it.
+ * Not offered: a device-pointer form; a travel-cost or otherwise weighted objective; lazy-greedy pruning of the marginals; sets kept
+ * across calls. */
+typedef struct isdf_view_select_params {
+    isdf_view_gain_params gain;   /* strides, max_range_m, scratch_bytes: isdf_view_gain's, with its defaults */
+    int32_t k_select;             /* default 4; >= 1 */
+    int32_t reserved0;
+    int64_t min_gain;             /* default 1; >= 0 */
+    int32_t reserved[4];
+} isdf_view_select_params;
+
+typedef struct isdf_view_select_info {
+    int64_t n_views, n_scored, n_selected;
+    int64_t gain_selected, gain_solo_sum, best_single_gain;
+    int64_t list_words;
+    int32_t chunks, reserved;
+    double  gain_ms, lists_ms, select_ms;
+} isdf_view_select_info;
+
+#define ISDF_VIEW_SELECT_ROW 4
+void isdf_view_select_params_default(isdf_view_select_params *p);       /* null-safe */
+void isdf_view_select_sizes(int sizes_out[2]);                          /* null-safe; sizeof of the params and of the info */
+int isdf_view_select(isdf_ctx *ctx, const isdf_depth_camera *camera, const double *poses, long long n_views, const isdf_view_select_params *params,
+                     int64_t *rows_out, int64_t *select_out, int64_t *round_out, uint32_t *claimed_out, isdf_view_select_info *info_out);
+/* plain host code, no ctx, no device: bits = K's words, occ = nx ny nz occupancy bytes, the map's geometry as isdf_raycast_host takes it;
+ * gain.scratch_bytes is ignored.  ISDF_OK, or ISDF_ERR_INVALID_ARG (a null bits or occ, a bad geometry, the bad arguments above) with
+ * nothing written. */
+int isdf_view_select_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
+                          const isdf_depth_camera *camera, const double *poses, long long n_views, const isdf_view_select_params *params, int64_t *rows_out,
+                          int64_t *select_out, int64_t *round_out, uint32_t *claimed_out, isdf_view_select_info *info_out);
+
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
  * the shipped src/plan_manager/map_pcds are "FIELDS x y z / DATA ascii"): xyz_out = up to `capacity` points x 3 floats (may be
