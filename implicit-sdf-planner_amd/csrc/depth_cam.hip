@@ -14,7 +14,7 @@
 #include "map_query.hpp"
 #include "depth_cam_host.hpp"
 #include "map_change.hpp"
-#include "dev_block_sum.hpp"
+#include "dev_reduce.hpp"
 #include <algorithm>
 #include <cstring>
 

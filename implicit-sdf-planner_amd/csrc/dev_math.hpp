@@ -374,6 +374,7 @@ __device__ __forceinline__ void traj_eval(const TrajView &tr, int piece, double 
     }
 }
 
+// (every lane holds the sum; dev_reduce.hpp's integer wave_sum leaves it in lane 0 only)
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -51,6 +51,7 @@
 #include "isdf_ctx.hpp"
 #include "frontend_dev.hpp"
 #include "frontend_field_host.hpp"
+#include "dev_reduce.hpp"
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(1024) void ff_compact_kernel(unsigned *flags, int *
 __global__ __launch_bounds__(256) void ff_count_kernel(const double *__restrict__ d, long long n, unsigned long long *cnt) {
     unsigned long long k = 0;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) k += d[t] < __longlong_as_double(0x7FF0000000000000ll);
-    for (int s = 32; s > 0; s >>= 1) k += __shfl_down(k, s);
+    k = wave_sum(k);
     if ((threadIdx.x & 63) == 0 && k) atomicAdd(cnt + FF_CNT_REACHED, k);
 }
 
@@ -314,7 +315,7 @@ __global__ __launch_bounds__(256) void ff_repair_reset_kernel(FfDims D, double *
             const unsigned long long bits = (unsigned long long)__double_as_longlong(*p);
             if (bits >= tau && bits < FF_INF_BITS) { *p = __longlong_as_double((long long)FF_INF_BITS); k++; }
         }
-    for (int s = 32; s > 0; s >>= 1) k += __shfl_down(k, s);
+    k = wave_sum(k);
     if (lane == 0 && k) atomicAdd(&s_n, k);
     __syncthreads();
     if (tid == 0 && s_n) {
@@ -341,14 +342,6 @@ __global__ __launch_bounds__(256) void ff_reopen_count_kernel(FfDims D, FfBox B,
 
 // The field through a shift of the map window, the translation of its first phase.  New voxel v holds old voxel v + s.
 struct FfShift { int s0, s1, s2; };
-
-__device__ __forceinline__ unsigned long long ff_wave_min(unsigned long long v) {          // every lane of the wavefront calls it; lane 0 holds the result
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long u = __shfl_down(v, o);
-        v = u < v ? u : v;
-    }
-    return v;
-}
 
 // ff_init_kernel's layout, one wavefront per 64 consecutive z of a DESTINATION column: each lane reads d_old[v + s] (64 consecutive
 // doubles s away) and its old free bit from the source column's word (a z-shift that is no multiple of 64 straddles two), the new free
@@ -377,7 +370,7 @@ __global__ __launch_bounds__(256) void ff_shift_kernel(FfDims D, FfShift S, cons
     const unsigned long long kept = old & now, closed = old & ~now;
     const bool reached = ((closed >> lane) & 1ull) && bits < FF_INF_BITS;
     const unsigned long long hit = __ballot(reached);
-    const unsigned long long tau = ff_wave_min(reached ? bits : FF_INF_BITS);
+    const unsigned long long tau = wave_min(reached ? bits : FF_INF_BITS);
     // (a finite d_old lies on a voxel that was free: "kept" is "the source exists and the new word is non-zero" wherever it matters)
     if (z < D.Z) d1[v] = __longlong_as_double((long long)(((kept >> lane) & 1ull) ? bits : FF_INF_BITS));
     if (lane != 0) return;
@@ -402,8 +395,7 @@ __global__ __launch_bounds__(256) void ff_left_kernel(FfDims D, FfShift S, const
         const unsigned long long bits = (unsigned long long)__double_as_longlong(d_old[t]);
         if (bits < FF_INF_BITS) { k++; m = bits < m ? bits : m; }
     }
-    m = ff_wave_min(m);
-    for (int o = 32; o > 0; o >>= 1) k += __shfl_down(k, o);
+    m = wave_min(m); k = wave_sum(k);
     if ((threadIdx.x & 63) == 0 && k) {
         atomicAdd(cnt + FF_CNT_LEFT, k);
         atomicMin(&rec->tau_bits, m);

@@ -11,7 +11,7 @@
 //                      read with relaxed agent-scope atomic loads: a plain load may be served from a stale line of this CU's L1 - a stale
 //                      parent is still an ancestor, so the result would hold, but the retries would not be bounded by the chip's traffic.
 //   fc_flatten_kernel  root[i] = find(i), and the flag "i is a root".
-//   (hipcub)           exclusive scan of the flags: the cluster number of every root, ascending with the label.
+//   (dev_scan.hpp)     exclusive scan of the flags: the cluster number of every root, ascending with the label.
 //   fc_number_kernel   each root opens its cluster's record: empty sums and box, its position as first_pos.
 //   fc_stats_kernel    size, box and the three sums per cluster, integer atomics only.  The list is z-fastest, so neighbouring lanes
 //                      mostly share a cluster: runs of equal cluster numbers are combined inside the wavefront (a segmented shuffle
@@ -20,13 +20,14 @@
 //                      atomicMin per run.
 //   fc_keep_kernel     keep[c] = size >= min_size (0 beyond the last cluster: the scan below runs over n entries, the host does not
 //                      know the number of clusters yet); the largest cluster and the dropped voxels into the record.
-//   (hipcub)           exclusive scan of keep: the row number of every kept cluster.
+//   (dev_scan.hpp)     exclusive scan of keep: the row number of every kept cluster.
 //   fc_rows_kernel     the rows of the kept clusters as far as the caller's capacity goes; the counts into the record.
 //   fc_labels_kernel   labels[i] = the row of i's cluster or -1.
 // Nothing here writes to the ctx's map, its known grid, its products or its flags.
 #include "map_query.hpp"
 #include "frontier_cluster_host.hpp"
-#include <hipcub/hipcub.hpp>
+#include "dev_reduce.hpp"
+#include "dev_scan.hpp"
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -193,11 +194,7 @@ __global__ __launch_bounds__(FC_BLOCK) void fc_keep_kernel(int n, const int *__r
         if (size) largest = (size << 32) | (0xFFFFFFFFull - (unsigned)c);       // (size < 2^31)
         if (size < min_size) dropped = size;
     }
-    for (int off = 32; off > 0; off >>= 1) {        // every lane of the wavefront is here: one pair of atomics per wavefront
-        const unsigned long long l = __shfl_down(largest, off, 64);
-        largest = l > largest ? l : largest;
-        dropped += __shfl_down(dropped, off, 64);
-    }
+    largest = wave_max(largest); dropped = wave_sum(dropped);       // every lane of the wavefront is here: one pair of atomics per wavefront
     if ((threadIdx.x & 63) == 0) {
         if (largest) atomicMax(&rec->largest, largest);
         if (dropped) atomicAdd(&rec->n_voxels_dropped, dropped);
@@ -240,7 +237,7 @@ struct FrontierClusterState {
     isdf::DevBuf<int> d_parent, d_root, d_flag, d_cnum, d_first, d_keep, d_row_of, d_labels;
     isdf::DevBuf<isdf::FcAcc> d_acc;
     isdf::DevBuf<long long> d_rows;
-    isdf::DevBuf<void> d_scan_tmp;
+    isdf::DevBuf<unsigned char> d_scan_tmp;
     isdf::RecPair<isdf::FcRecord> rec;
     isdf::PinBuf<int64_t> h_vox, h_rows;
     isdf::PinBuf<int32_t> h_labels;
@@ -272,8 +269,6 @@ int cluster_setup(isdf_ctx *c, const isdf_frontier_cluster_params *params, long 
     if (vox_capacity < 0 || row_capacity < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "frontier clusters: negative capacity");
     return ISDF_OK;
 }
-
-unsigned lane_blocks(long long n) { return (unsigned)((n + FC_BLOCK - 1) / FC_BLOCK); }
 
 }  // namespace
 
@@ -309,13 +304,12 @@ extern "C" int isdf_map_frontier_clusters(isdf_ctx *c, const uint32_t *bits_in, 
     ISDF_TRY(S->d_first.reserve(c, un)); ISDF_TRY(S->d_keep.reserve(c, un)); ISDF_TRY(S->d_row_of.reserve(c, un)); ISDF_TRY(S->d_labels.reserve(c, un));
     ISDF_TRY(S->d_acc.reserve(c, un));
     ISDF_TRY(S->d_rows.reserve(c, (size_t)rows_room * FC_ROW));
-    size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, S->d_flag.get(), S->d_cnum.get(), (int)n, st));
-    ISDF_TRY(S->d_scan_tmp.reserve(c, std::max<size_t>(bytes, 1)));
+    size_t bytes;           // of both scans below: n ints into n ints
+    ISDF_TRY(exclusive_sum_reserve(c, S->d_scan_tmp, S->d_flag.get(), S->d_cnum.get(), n, st, &bytes));
     if (vox_out && !vox_short) ISDF_TRY(S->h_vox.reserve(c, un));
     if (labels_out && !vox_short) ISDF_TRY(S->h_labels.reserve(c, un));
     if (rows_room) ISDF_TRY(S->h_rows.reserve(c, (size_t)rows_room * FC_ROW));
-    const unsigned nb = lane_blocks(n);
+    const unsigned nb = blocks(n, FC_BLOCK);
     const int ni = (int)n;
     // stage 2: the components (ev[1], recorded after the emit pass, is its start)
     hipLaunchKernelGGL(fc_init_kernel, dim3(nb), dim3(FC_BLOCK), 0, st, ni, S->d_parent.get());
@@ -326,7 +320,7 @@ extern "C" int isdf_map_frontier_clusters(isdf_ctx *c, const uint32_t *bits_in, 
     HIPCHK(c, hipEventRecord(S->ev[2], st));
     // stage 3: numbering, statistics, representatives, rows
     HIPCHK(c, S->rec.zero(st));
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_scan_tmp.get(), bytes, S->d_flag.get(), S->d_cnum.get(), ni, st));
+    ISDF_TRY(exclusive_sum_run(c, S->d_scan_tmp, bytes, S->d_flag.get(), S->d_cnum.get(), n, st));
     hipLaunchKernelGGL(fc_number_kernel, dim3(nb), dim3(FC_BLOCK), 0, st, ni, (const int *)S->d_flag.get(), (const int *)S->d_cnum.get(), S->d_acc.get(), S->d_first.get());
     hipLaunchKernelGGL(fc_stats_kernel, dim3(nb), dim3(FC_BLOCK), 0, st, g, ni, (const long long *)K.d_list.get(), (const int *)S->d_root.get(), (const int *)S->d_cnum.get(),
                        S->d_acc.get());
@@ -335,7 +329,7 @@ extern "C" int isdf_map_frontier_clusters(isdf_ctx *c, const uint32_t *bits_in, 
     hipLaunchKernelGGL(fc_keep_kernel, dim3(nb), dim3(FC_BLOCK), 0, st, ni, (const int *)S->d_flag.get(), (const int *)S->d_cnum.get(), (const FcAcc *)S->d_acc.get(),
                        (unsigned long long)P.min_size, S->d_keep.get(), S->rec.dev());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_scan_tmp.get(), bytes, S->d_keep.get(), S->d_row_of.get(), ni, st));
+    ISDF_TRY(exclusive_sum_run(c, S->d_scan_tmp, bytes, S->d_keep.get(), S->d_row_of.get(), n, st));
     hipLaunchKernelGGL(fc_rows_kernel, dim3(nb), dim3(FC_BLOCK), 0, st, ni, (const int *)S->d_flag.get(), (const int *)S->d_cnum.get(), (const FcAcc *)S->d_acc.get(),
                        (const int *)S->d_first.get(), (const long long *)K.d_list.get(), (const int *)S->d_keep.get(), (const int *)S->d_row_of.get(),
                        rows_room ? S->d_rows.get() : nullptr, rows_room, S->rec.dev());

@@ -116,7 +116,7 @@ struct isdf_ctx {
         size_t n_words = 0;
         DevBuf<unsigned> d_bits, d_shift;
         long long newly = 0, merges = 0;            // isdf_map_known_info's newly_known and merges
-        DevBuf<unsigned> d_front; DevBuf<int> d_cnt, d_base; DevBuf<long long> d_list; DevBuf<void> d_scan_tmp;
+        DevBuf<unsigned> d_front; DevBuf<int> d_cnt, d_base; DevBuf<long long> d_list; DevBuf<unsigned char> d_scan_tmp;
         RecPair<MkRecord> rec; DevEvents<2> ev;
         // isdf_map_known_merge_ms: a developer's pair of events round the merge kernel, recorded only while asked for
         bool time_merge = false; DevEvents<2> ev_merge; double merge_ms = -1.0;

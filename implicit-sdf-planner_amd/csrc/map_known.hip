@@ -17,11 +17,12 @@
 //                       the voxels come out ascending on every run.
 //   mk_count_kernel     stands in for the frontier kernel where the set is a caller's (isdf_map_frontier_clusters with bits_in, DESIGN
 //                       4.22): the counts and the record of words that are in d_front already.
-// The reductions go through the wavefront, then LDS, then one set of global atomics per workgroup into one 64-byte record.
+// The reductions go through the wavefront, then LDS (dev_reduce.hpp), then one set of global atomics per workgroup into one 64-byte record.
 #include "map_query.hpp"
 #include "map_known_host.hpp"
 #include "map_change.hpp"
-#include <hipcub/hipcub.hpp>
+#include "dev_reduce.hpp"
+#include "dev_scan.hpp"
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -34,29 +35,13 @@ struct MkGeom { int X, Y, Z; long long n_vox, n_words; };
 // called by every thread of a 256-thread workgroup: two sums and a box over the workgroup, then one atomic each where there is something
 __device__ __forceinline__ void mk_block_reduce(unsigned long long n, unsigned long long newly, const int lo[3], const int hi[3], unsigned long long *g_n,
                                                 unsigned long long *g_newly, int *g_lo, int *g_hi) {
-    __shared__ int s_lo[3], s_hi[3];
-    __shared__ unsigned long long s_n[4], s_new[4];
-    if (threadIdx.x < 3) { s_lo[threadIdx.x] = 0x7FFFFFFF; s_hi[threadIdx.x] = -1; }
-    __syncthreads();
-    for (int o = 32; o > 0; o >>= 1) {
-        n += __shfl_down(n, o, 64);
-        newly += __shfl_down(newly, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { s_n[threadIdx.x >> 6] = n; s_new[threadIdx.x >> 6] = newly; }
-    if (g_lo && hi[0] >= 0) {
-        atomicMin(&s_lo[0], lo[0]); atomicMin(&s_lo[1], lo[1]); atomicMin(&s_lo[2], lo[2]);
-        atomicMax(&s_hi[0], hi[0]); atomicMax(&s_hi[1], hi[1]); atomicMax(&s_hi[2], hi[2]);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long a = s_n[0] + s_n[1] + s_n[2] + s_n[3], b = s_new[0] + s_new[1] + s_new[2] + s_new[3];
-        if (g_n && a) atomicAdd(g_n, a);
-        if (g_newly && b) atomicAdd(g_newly, b);
-        if (g_lo && s_hi[0] >= 0) {
-            atomicMin(&g_lo[0], s_lo[0]); atomicMin(&g_lo[1], s_lo[1]); atomicMin(&g_lo[2], s_lo[2]);
-            atomicMax(&g_hi[0], s_hi[0]); atomicMax(&g_hi[1], s_hi[1]); atomicMax(&g_hi[2], s_hi[2]);
-        }
-    }
+    const BoxAcc box = BoxAcc::open();
+    if (g_lo && hi[0] >= 0) box.add(lo, hi);
+    const unsigned long long cnt[2] = {n, newly};
+    const unsigned long long s = block_sum<2, 4>(cnt);      // thread 0: n, thread 1: newly (its barrier lies behind every add)
+    if (threadIdx.x == 0 && g_n && s) atomicAdd(g_n, s);
+    if (threadIdx.x == 1 && g_newly && s) atomicAdd(g_newly, s);
+    if (threadIdx.x == 0 && g_lo) box.flush(g_lo, g_hi);
 }
 
 __global__ __launch_bounds__(256) void mk_merge_kernel(MkGeom g, const unsigned *__restrict__ free_bits, const unsigned *__restrict__ hit_bits,
@@ -164,6 +149,7 @@ using namespace isdf;
 
 namespace {
 
+// workgroups of the grid-stride kernels over n dwords: at most 2048, at least one
 unsigned word_blocks(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 2048)); }
 
 MkGeom geom(const isdf_ctx *c) {
@@ -353,11 +339,10 @@ int isdf::map_frontier_stage(isdf_ctx *c, const char *op, const uint32_t *set_bi
     if (!want_list || R.n == 0) return ISDF_OK;
     if ((unsigned long long)capacity < R.n) return isdf_fail(c, ISDF_ERR_OVERFLOW, (what + ": output capacity smaller than the number of frontier voxels").c_str());
     if (R.n > (unsigned long long)INT_MAX) return isdf_fail(c, ISDF_ERR_OVERFLOW, (what + ": more than 2^31 frontier voxels").c_str());
-    size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, K.d_cnt.get(), K.d_base.get(), (int)g.n_words, st));
-    ISDF_TRY(K.d_scan_tmp.reserve(c, std::max<size_t>(bytes, 1))); ISDF_TRY(K.d_list.reserve(c, (size_t)R.n));
+    size_t bytes;
+    ISDF_TRY(exclusive_sum_reserve(c, K.d_scan_tmp, K.d_cnt.get(), K.d_base.get(), g.n_words, st, &bytes)); ISDF_TRY(K.d_list.reserve(c, (size_t)R.n));
     if (list_ev) HIPCHK(c, hipEventRecord(list_ev[0], st));
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(K.d_scan_tmp.get(), bytes, K.d_cnt.get(), K.d_base.get(), (int)g.n_words, st));
+    ISDF_TRY(exclusive_sum_run(c, K.d_scan_tmp, bytes, K.d_cnt.get(), K.d_base.get(), g.n_words, st));
     hipLaunchKernelGGL(mk_emit_kernel, dim3(word_blocks(g.n_words)), dim3(256), 0, st, g.n_words, (const unsigned *)K.d_front.get(), (const int *)K.d_base.get(), K.d_list.get());
     HIPCHK(c, hipGetLastError());
     if (list_ev) HIPCHK(c, hipEventRecord(list_ev[1], st));

@@ -9,7 +9,7 @@
 // Nothing here writes to the ctx's map, its products or its flags.
 #include "map_query.hpp"
 #include "map_raycast_host.hpp"
-#include "dev_block_sum.hpp"
+#include "dev_reduce.hpp"
 #include <algorithm>
 #include <cstring>
 

@@ -8,7 +8,7 @@
 //   msh_translate_occ_kernel  the occupancy bytes, one lane per destination DWORD (the grid is allocated as whole dwords; a z-row is
 //                             not: the four bytes are placed one by one, a row's end carried).  Counts the occupied voxels that left
 //                             and notes whether any voxel is still occupied.
-// Both reduce in the wavefront, then through LDS, and issue one set of global atomics per workgroup into one 64-byte record.  The
+// Both reduce in the wavefront, then through LDS (dev_reduce.hpp's block_sum), and issue one set of global atomics per workgroup into one 64-byte record.  The
 // destination is a second buffer that then changes places with the ctx's own: no overlap of source and destination, no copy back.
 // Everything else is existing code: isdf_generate_esdf on the shifted occupancy, the whole inflated bit map, the boxed
 // configuration-space kernel over the bands (map_shift_host.hpp), the pack / scatter path into the A*'s host copy - the shared steps
@@ -19,6 +19,7 @@
 #include "map_shift_host.hpp"
 #include "map_change.hpp"
 #include "swept_field.hpp"
+#include "dev_reduce.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -38,22 +39,14 @@ __device__ __forceinline__ bool msh_inside(const MshGeom &g, int x, int y, int z
 
 // called by every thread of a 256-thread workgroup: the two sums and the flag over the workgroup, then one atomic each where not zero
 __device__ __forceinline__ void msh_block_reduce(unsigned long long counts_left, unsigned long long occupied_left, bool any_occ, MshRecord *__restrict__ rec) {
-    __shared__ unsigned long long s_a[4], s_b[4];
     __shared__ unsigned s_f[4];
-    for (int o = 32; o > 0; o >>= 1) {
-        counts_left += __shfl_down(counts_left, o, 64);
-        occupied_left += __shfl_down(occupied_left, o, 64);
-    }
     const bool wave_any = __ballot(any_occ) != 0ull;
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_a[wave] = counts_left; s_b[wave] = occupied_left; s_f[wave] = wave_any ? 1u : 0u; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long a = s_a[0] + s_a[1] + s_a[2] + s_a[3], b = s_b[0] + s_b[1] + s_b[2] + s_b[3];
-        if (a) atomicAdd(&rec->counts_left, a);
-        if (b) atomicAdd(&rec->occupied_left, b);
-        if (s_f[0] | s_f[1] | s_f[2] | s_f[3]) atomicOr(&rec->any_occ, 1u);
-    }
+    if ((threadIdx.x & 63) == 0) s_f[threadIdx.x >> 6] = wave_any ? 1u : 0u;
+    const unsigned long long cnt[2] = {counts_left, occupied_left};
+    const unsigned long long s = block_sum<2, 4>(cnt);      // thread 0: counts, thread 1: occupied (its barrier lies behind the flags' stores)
+    if (threadIdx.x == 0 && s) atomicAdd(&rec->counts_left, s);
+    if (threadIdx.x == 1 && s) atomicAdd(&rec->occupied_left, s);
+    if (threadIdx.x == 0 && (s_f[0] | s_f[1] | s_f[2] | s_f[3])) atomicOr(&rec->any_occ, 1u);
 }
 
 template <typename T, bool COUNTS>

@@ -7,12 +7,14 @@
 //            (cleared on the stream first); a point outside the grid occupies no voxel and is counted.
 //   flag     one thread per kept row of the report: value < below and the bit of its voxel (the check kept the voxel index:
 //            TrajCheckState::d_row_vox) -> one ballot mask and one count per 64 rows.
-//   scan     exclusive sum of the counts (hipCUB).
+//   scan     exclusive sum of the counts (dev_scan.hpp).
 //   append   (x, y, z) of the flagged rows, byte for byte, and lastTstar = 0 behind the old arrays, which move device to device
 //            into the new allocations: old points keep index, bytes and lastTstar; new ones follow in ascending voxel index.
 // The bitmap's content does not depend on the order of the ORs, the counters are integer sums and the rows are in voxel order: no
 // atomic decides a position, and two merges from the same state give the same bytes.  Only four counters come back to the host.
 #include "swept_field.hpp"
+#include "dev_reduce.hpp"
+#include "dev_scan.hpp"
 #include "grid_index.hpp"
 #include <climits>
 #include <cmath>
@@ -21,11 +23,6 @@
 namespace {
 
 enum { CNT_ROWS = 0, CNT_ADDED = 1, CNT_DUP = 2, CNT_OUTSIDE = 3, CNT_WORDS = 4 };
-
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned x) {
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
 
 __global__ __launch_bounds__(256) void pm_mark_kernel(DevGrid G, const double *__restrict__ pts, int M, unsigned *__restrict__ bits,
                                                       unsigned *__restrict__ counters) {
@@ -38,7 +35,7 @@ __global__ __launch_bounds__(256) void pm_mark_kernel(DevGrid G, const double *_
             atomicOr(&bits[v >> 5], 1u << (v & 31));
         } else outside = 1;
     }
-    outside = wave_sum_u32(outside);
+    outside = wave_sum(outside);
     if ((threadIdx.x & 63) == 0 && outside) atomicAdd(&counters[CNT_OUTSIDE], outside);
 }
 
@@ -117,7 +114,8 @@ extern "C" int isdf_points_merge_check(isdf_ctx *c, double below, isdf_points_me
                                (const long long *)k->d_row_vox.get(), (const unsigned *)c->d_merge_bits.get(), below, below < 0.0 ? 1 : 0,
                                mask.get(), count.get(), counters.get());
         HIPCHK(c, hipGetLastError());
-        if (n_rows > 0) ISDF_TRY(exclusive_sum(c, count.get(), base.get(), (long long)n_waves, st));
+        DevBuf<unsigned char> tmp;          // (freed behind the scan)
+        if (n_rows > 0) { ISDF_TRY(exclusive_sum(c, tmp, count.get(), base.get(), (long long)n_waves, st)); tmp.release(); }
         HIPCHK(c, hipMemcpyAsync(cnt, counters.get(), sizeof(cnt), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if ((long long)M_before + (long long)cnt[CNT_ADDED] > (long long)INT32_MAX)

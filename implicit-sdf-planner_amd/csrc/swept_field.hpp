@@ -1,10 +1,9 @@
 // What the users of the swept-volume field query share (swept_mesh.hip: the query and the mesher; traj_check.hip: the clearance
 // check; traj_watch.hip: the check's kept report folded across map updates): the query's scratch, its host-side checks and
-// launches, the small host helpers of the count / scan / emit passes, and the check's selection test, reduction and kept state.
+// launches, and the check's selection test, reduction and kept state.  (The count / scan / emit passes' host helpers: dev_scan.hpp.)
 #pragma once
 #include "isdf_ctx.hpp"
 #include "traj_watch_host.hpp"
-#include <hipcub/hipcub.hpp>
 #include <vector>
 
 constexpr int FIELD_CHUNK = 65536;                        // points per field launch: 65 536 x 1.5 KB of interval slots = 96 MiB
@@ -63,7 +62,8 @@ constexpr int TC_REPORT_WORDS = 7;      // [0] min value [1] its t* [2..4] its p
 struct TcReduceScratch {
     DevBuf<int> flag, fbase;
     DevBuf<unsigned long long> key;
-    DevBuf<void> partial, scan_tmp;
+    DevBuf<void> partial;
+    DevBuf<unsigned char> scan_tmp;
 };
 
 // a watch on the kept report (isdf_traj_check_set_watch, mode 1): what the arming check leaves for the folds, the folded report,
@@ -123,14 +123,3 @@ int swept_field_run(isdf_ctx *c, int N, const double *d_T, const double *d_coeff
 // the same launches without the read-back: the caller fetches the overflow word (SweptMeshState::d_stats[4]) with its own hand-over
 int swept_field_launch(isdf_ctx *c, int N, const double *d_T, const double *d_coeffs, const double *d_xyz, long long n, int mode,
                        double *d_value, double *d_tstar, hipStream_t st);
-
-inline unsigned blocks(long long n, int b = 256) { return (unsigned)((n + b - 1) / b); }
-
-template <typename In, typename Out> int exclusive_sum(isdf_ctx *c, In in, Out out, long long n, hipStream_t st) {
-    size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
-    DevBuf<unsigned char> tmp;
-    HIPCHK(c, tmp.alloc(bytes));
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(tmp.get(), bytes, in, out, (int)n, st));
-    return ISDF_OK;
-}

@@ -19,6 +19,8 @@
 // The reference continues its field along a flood fill (descents of +-0.1 s seeded by a neighbour's t*, sw_manager.hpp:1173-1193):
 // its values depend on the flood order and are deliberately not reproduced - every node here is an independent query.
 #include "swept_field.hpp"
+#include "dev_reduce.hpp"
+#include "dev_scan.hpp"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -263,10 +265,6 @@ __device__ __forceinline__ bool cell_values(const Lattice &L, const double *f, i
     }
     return ok;
 }
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
 
 // per cell: known (all eight corners evaluated) and its number of triangles; stats[0] += known cells, stats[1] += triangles
 __global__ void cell_count_kernel(Lattice L, const double *f, double iso, unsigned char *known, int *tcount, unsigned long long *stats) {
@@ -291,7 +289,7 @@ __global__ void cell_count_kernel(Lattice L, const double *f, double iso, unsign
         tcount[t] = n;
         k_sum = ok; t_sum = (unsigned long long)n;
     }
-    k_sum = wave_sum_u64(k_sum); t_sum = wave_sum_u64(t_sum);
+    k_sum = wave_sum(k_sum); t_sum = wave_sum(t_sum);
     if ((threadIdx.x & 63) == 0) { if (k_sum) atomicAdd(&stats[0], k_sum); if (t_sum) atomicAdd(&stats[1], t_sum); }
 }
 
@@ -332,7 +330,7 @@ __global__ void vertex_count_kernel(Lattice L, const double *f, const unsigned c
         vcount[id] = __popc(m);
         v_sum = __popc(m); u_sum = nu;
     }
-    v_sum = wave_sum_u64(v_sum); u_sum = wave_sum_u64(u_sum);
+    v_sum = wave_sum(v_sum); u_sum = wave_sum(u_sum);
     if ((threadIdx.x & 63) == 0) { if (v_sum) atomicAdd(&stats[2], v_sum); if (u_sum) atomicAdd(&stats[3], u_sum); }
 }
 
@@ -462,8 +460,9 @@ int extract_mesh(isdf_ctx *c, SweptMeshState *s, const Lattice &L, const double 
     HIPCHK(c, hipStreamSynchronize(st));
     if (cnt[1] > (unsigned long long)INT32_MAX / 3 || cnt[2] > (unsigned long long)INT32_MAX / 3)
         return fail(c, ISDF_ERR_OVERFLOW, "swept mesh: more than 2^31 / 3 vertices or triangles");
-    ISDF_TRY(exclusive_sum(c, tcount.get(), tbase.get(), n_cells, st));
-    ISDF_TRY(exclusive_sum(c, vcount.get(), vbase.get(), n_nodes, st));
+    DevBuf<unsigned char> tmp;          // each scan's scratch is its own and is freed behind it
+    ISDF_TRY(exclusive_sum(c, tmp, tcount.get(), tbase.get(), n_cells, st)); tmp.release();
+    ISDF_TRY(exclusive_sum(c, tmp, vcount.get(), vbase.get(), n_nodes, st)); tmp.release();
     HIPCHK(c, s->d_V.alloc((size_t)(cnt[2] ? cnt[2] : 1) * 3));
     HIPCHK(c, s->d_F.alloc((size_t)(cnt[1] ? cnt[1] : 1) * 3));
     hipLaunchKernelGGL(vertex_emit_kernel, dim3(blocks(n_nodes)), dim3(256), 0, st, L, f, iso,

@@ -17,6 +17,8 @@
 //            among the points whose t* lies in it, and the points below the margin compacted in voxel order.  Minima and integer
 //            sums only: the report does not depend on the launch geometry, and two runs give the same bytes.
 #include "swept_field.hpp"
+#include "dev_reduce.hpp"
+#include "dev_scan.hpp"
 #include "traj_call.hpp"
 #include <climits>
 #include <cmath>
@@ -32,11 +34,6 @@ constexpr int SEL_WAVES = 4;             // z-rows per workgroup of the row kern
 int fail(isdf_ctx *c, int code, const char *msg) { return isdf_fail(c, code, msg); }
 
 // (SelBox, voxel_centre, stage_samples and the single-voxel test sample_within: swept_field.hpp - the fold's list kernel shares them)
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
 
 // per brick of the box: the first and last coarse sample within far_r + half-diagonal of its centre (first > last: none)
 __global__ __launch_bounds__(256) void tc_brick_kernel(SelBox B, const double *__restrict__ pose, const int *__restrict__ n_coarse,
@@ -102,7 +99,7 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void tc_row_kernel(SelBox B, const 
         n_sel += __popcll(m);
         n_occ += occupied ? 1ull : 0ull;
     }
-    n_occ = wave_sum_u64(n_occ);
+    n_occ = wave_sum(n_occ);
     if (lane == 0) {
         count[row] = n_sel;
         if (n_occ) atomicAdd(&stats[0], n_occ);
@@ -187,7 +184,7 @@ __global__ __launch_bounds__(256) void tc_reduce_kernel(long long n, const doubl
         }
         flag[j] = (int)below;
     }
-    q = wave_sum_u64(q); below = wave_sum_u64(below); pen = wave_sum_u64(pen);
+    q = wave_sum(q); below = wave_sum(below); pen = wave_sum(pen);
     if ((threadIdx.x & 63) == 0) {
         if (q) atomicAdd(&counts[0], q);
         if (below) atomicAdd(&counts[1], below);
@@ -257,7 +254,7 @@ __global__ __launch_bounds__(256) void th_key_kernel(long long n, const double *
             if (below) atomicMin(&rec[3], ordered_key(ts[j]));
         }
     }
-    q = wave_sum_u64(q); below = wave_sum_u64(below); pen = wave_sum_u64(pen);
+    q = wave_sum(q); below = wave_sum(below); pen = wave_sum(pen);
     if ((threadIdx.x & 63) == 0) {
         if (q) atomicAdd(&rec[0], q);
         if (below) atomicAdd(&rec[1], below);
@@ -375,7 +372,8 @@ int select_run(isdf_ctx *c, SweptMeshState *s, int N, const double *d_T, const d
         HIPCHK(c, hipStreamSynchronize(st));
         if (cnt[1] > (unsigned long long)INT32_MAX) return fail(c, ISDF_ERR_OVERFLOW, (std::string(op) + ": more than 2^31 candidate voxels").c_str());
         if (cnt[1]) {
-            ISDF_TRY(exclusive_sum(c, count.get(), base.get(), n_rows, st));
+            DevBuf<unsigned char> tmp;          // (freed behind the scan)
+            ISDF_TRY(exclusive_sum(c, tmp, count.get(), base.get(), n_rows, st)); tmp.release();
             HIPCHK(c, vox.alloc((size_t)cnt[1]));
             HIPCHK(c, xyz.alloc((size_t)cnt[1] * 3));
             hipLaunchKernelGGL(tc_emit_kernel, dim3(blocks(n_rows, SEL_WAVES)), dim3(64 * SEL_WAVES), 0, st, B,
@@ -500,10 +498,7 @@ int tc_reduce_launch(isdf_ctx *c, TcReduceScratch &S, long long n, const double 
 int tc_rows_launch(isdf_ctx *c, TcReduceScratch &S, long long n, const double *d_val, const double *d_ts, const long long *d_vox, const double *d_xyz,
                    double *d_rows, long long *d_row_vox, hipStream_t st) {
     if (n <= 0) return ISDF_OK;
-    size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, S.flag.get(), S.fbase.get(), (int)n, st));
-    ISDF_TRY(S.scan_tmp.reserve(c, std::max<size_t>(bytes, 1)));
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S.scan_tmp.get(), bytes, S.flag.get(), S.fbase.get(), (int)n, st));
+    ISDF_TRY(exclusive_sum(c, S.scan_tmp, S.flag.get(), S.fbase.get(), n, st));
     hipLaunchKernelGGL(tc_rows_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)S.flag.get(), (const int *)S.fbase.get(), d_xyz, d_val, d_ts, d_rows);
     hipLaunchKernelGGL(tc_row_vox_kernel, dim3(blocks(n)), dim3(256), 0, st, n, (const int *)S.flag.get(), (const int *)S.fbase.get(), d_vox, d_row_vox);
     HIPCHK(c, hipGetLastError());

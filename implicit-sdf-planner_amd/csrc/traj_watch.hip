@@ -17,6 +17,7 @@
 //            and the piece minima on the host from the hand-over record (tw_fold_info, the function isdf_traj_check_fold_host calls).
 // One pinned record and one synchronisation per fold, the field query's overflow word inside the record.
 #include "swept_field.hpp"
+#include "dev_scan.hpp"
 #include "map_update_host.hpp"
 #include <algorithm>
 #include <cmath>

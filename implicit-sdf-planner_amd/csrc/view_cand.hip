@@ -5,19 +5,19 @@
 //                      workgroup per word into the call's record.
 //   vc_tally_kernel    one workgroup per target: its six status counts, best_candidate -1 and best_gain 0 into the target's row, its
 //                      best list padded with -1 - what a call without a kept candidate returns.
-//   (hipcub)           exclusive scan of the flags: the place of every kept candidate in the dense table.
+//   (dev_scan.hpp)     exclusive scan of the flags: the place of every kept candidate in the dense table.
 //   vc_compact_kernel  the kept poses into the dense table, the candidate index of each.
 //   -- the first hand-over: the record.  n_kept sizes the gain's grid and its seen chunks; with zero kept nothing more is launched.
 //   (view_gain.hip)    gain_run on the dense table: vg_setup_kernel, then per chunk the clear and vg_gain_kernel, as isdf_view_gain.
 //   vc_score_kernel    one kept candidate per lane: the gain row's words 1, 4, 5, 6 into the candidate's row.
 //   vc_select_kernel   one workgroup per target, at most k_best rounds: the largest key (gain, then the lower k) below the last round's,
-//                      by a reduction through the wavefronts and LDS - no atomic, so no order to depend on.
+//                      by dev_reduce.hpp's block_max through the wavefronts and LDS - no atomic, so no order to depend on.
 //   -- the second hand-over: the rows, poses, target rows and best lists through their pinned copies.
 // Nothing here writes to the ctx's map, its known grid, its products or its flags; no kernel waits on another workgroup.
 #include "view_gain_run.hpp"
 #include "view_cand_host.hpp"
-#include "dev_block_sum.hpp"
-#include <hipcub/hipcub.hpp>
+#include "dev_reduce.hpp"
+#include "dev_scan.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -95,9 +95,7 @@ __global__ __launch_bounds__(VC_LANE_BLOCK) void vc_score_kernel(long long n_kep
 // cand: word 7 of a ranked candidate is written while other lanes read words 0 and 3 of it - other words
 __global__ __launch_bounds__(VC_SEL_BLOCK) void vc_select_kernel(long long n_offsets, int k_best, long long min_gain, long long *cand, long long *__restrict__ target_rows,
                                                                  long long *__restrict__ best) {
-    __shared__ unsigned long long s_max[VC_SEL_WAVES];
     const long long i = blockIdx.x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned long long prev = ~0ull;
     for (int r = 0; r < k_best; r++) {
         unsigned long long top = 0;
@@ -107,15 +105,7 @@ __global__ __launch_bounds__(VC_SEL_BLOCK) void vc_select_kernel(long long n_off
             const unsigned long long key = vc_key(row[3], k);
             if (key < prev && key > top) top = key;
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long o = __shfl_down(top, off, 64);
-            top = o > top ? o : top;
-        }
-        if (lane == 0) s_max[wave] = top;
-        __syncthreads();
-        top = s_max[0];
-        for (int w = 1; w < VC_SEL_WAVES; w++) top = s_max[w] > top ? s_max[w] : top;
-        __syncthreads();                    // (s_max is written again in the next round)
+        top = block_max<VC_SEL_WAVES>(top);
         if (top == 0) break;                // (uniform: every thread holds the workgroup's maximum)
         if (threadIdx.x == 0) {
             const long long c = i * n_offsets + vc_key_k(top);
@@ -135,7 +125,7 @@ struct ViewCandState {
     isdf::DevBuf<double> d_targets, d_offsets, d_poses, d_dense;
     isdf::DevBuf<long long> d_cand, d_target_rows, d_best, d_gain_rows;
     isdf::DevBuf<int> d_flag, d_pos, d_index;
-    isdf::DevBuf<void> d_scan_tmp;
+    isdf::DevBuf<unsigned char> d_scan_tmp;
     isdf::RecPair<isdf::VcRecord> rec;
     isdf::PinBuf<int64_t> h_cand, h_target_rows, h_best;
     isdf::PinBuf<double> h_poses;
@@ -185,8 +175,6 @@ void cand_info(long long n_targets, long long n_offsets, const VcCounts &N, int 
     *out = info;
 }
 
-unsigned lane_blocks(long long n, int block) { return (unsigned)((n + block - 1) / block); }
-
 }  // namespace
 
 extern "C" int isdf_view_candidates(isdf_ctx *c, const isdf_depth_camera *cam, const double *targets, long long n_targets, const double *offsets, long long n_offsets,
@@ -217,9 +205,8 @@ extern "C" int isdf_view_candidates(isdf_ctx *c, const isdf_depth_camera *cam, c
     ISDF_TRY(S->d_cand.reserve(c, nc * VC_ROW)); ISDF_TRY(S->d_poses.reserve(c, nc * 12)); ISDF_TRY(S->d_dense.reserve(c, nc * 12));
     ISDF_TRY(S->d_flag.reserve(c, nc)); ISDF_TRY(S->d_pos.reserve(c, nc)); ISDF_TRY(S->d_index.reserve(c, nc));
     ISDF_TRY(S->d_target_rows.reserve(c, nt * VC_TARGET_ROW)); ISDF_TRY(S->d_best.reserve(c, nb));
-    size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, S->d_flag.get(), S->d_pos.get(), (int)n_cand, st));
-    ISDF_TRY(S->d_scan_tmp.reserve(c, std::max<size_t>(bytes, 1)));
+    size_t bytes;
+    ISDF_TRY(exclusive_sum_reserve(c, S->d_scan_tmp, S->d_flag.get(), S->d_pos.get(), n_cand, st, &bytes));
     ISDF_TRY(S->h_target_rows.reserve(c, nt * VC_TARGET_ROW));
     if (cand_out) ISDF_TRY(S->h_cand.reserve(c, nc * VC_ROW));
     if (poses_out) ISDF_TRY(S->h_poses.reserve(c, nc * 12));
@@ -229,14 +216,14 @@ extern "C" int isdf_view_candidates(isdf_ctx *c, const isdf_depth_camera *cam, c
     // the filter stage and the first hand-over: the record
     const long long n_words = (long long)c->known.n_words;
     ISDF_TRY(map_query::count_begin(c, true, S->ev_filter, S->rec, st));
-    hipLaunchKernelGGL(vc_filter_kernel, dim3(lane_blocks(n_cand, VC_BLOCK)), dim3(VC_BLOCK), 0, st, (const double *)S->d_targets.get(), (const double *)S->d_offsets.get(),
+    hipLaunchKernelGGL(vc_filter_kernel, dim3(blocks(n_cand, VC_BLOCK)), dim3(VC_BLOCK), 0, st, (const double *)S->d_targets.get(), (const double *)S->d_offsets.get(),
                        n_offsets, n_cand, M, (const uint8_t *)c->d_occ.get(), (const unsigned *)c->known.d_bits.get(), n_words, (int)P.clearance_voxels, S->d_cand.get(),
                        S->d_poses.get(), S->d_flag.get(), S->rec.dev());
     hipLaunchKernelGGL(vc_tally_kernel, dim3((unsigned)n_targets), dim3(VC_SEL_BLOCK), 0, st, n_offsets, (int)P.k_best, (const long long *)S->d_cand.get(),
                        S->d_target_rows.get(), S->d_best.get());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(S->d_scan_tmp.get(), bytes, S->d_flag.get(), S->d_pos.get(), (int)n_cand, st));
-    hipLaunchKernelGGL(vc_compact_kernel, dim3(lane_blocks(n_cand, VC_LANE_BLOCK)), dim3(VC_LANE_BLOCK), 0, st, n_cand, (const int *)S->d_flag.get(),
+    ISDF_TRY(exclusive_sum_run(c, S->d_scan_tmp, bytes, S->d_flag.get(), S->d_pos.get(), n_cand, st));
+    hipLaunchKernelGGL(vc_compact_kernel, dim3(blocks(n_cand, VC_LANE_BLOCK)), dim3(VC_LANE_BLOCK), 0, st, n_cand, (const int *)S->d_flag.get(),
                        (const int *)S->d_pos.get(), (const double *)S->d_poses.get(), S->d_dense.get(), S->d_index.get());
     HIPCHK(c, hipGetLastError());
     ISDF_TRY(map_query::count_end(c, true, S->ev_filter, S->rec, st));
@@ -252,7 +239,7 @@ extern "C" int isdf_view_candidates(isdf_ctx *c, const isdf_depth_camera *cam, c
         ISDF_TRY(gain_run(c, G, base, M, Pg, S->d_dense.get(), n_kept, S->d_gain_rows.get(), false, &chunks, st));
         ISDF_TRY(map_query::count_end(c, true, S->ev_gain, st));
         ISDF_TRY(map_query::count_begin(c, true, S->ev_select, st));
-        hipLaunchKernelGGL(vc_score_kernel, dim3(lane_blocks(n_kept, VC_LANE_BLOCK)), dim3(VC_LANE_BLOCK), 0, st, n_kept, (const int *)S->d_index.get(),
+        hipLaunchKernelGGL(vc_score_kernel, dim3(blocks(n_kept, VC_LANE_BLOCK)), dim3(VC_LANE_BLOCK), 0, st, n_kept, (const int *)S->d_index.get(),
                            (const long long *)S->d_gain_rows.get(), S->d_cand.get());
         hipLaunchKernelGGL(vc_select_kernel, dim3((unsigned)n_targets), dim3(VC_SEL_BLOCK), 0, st, n_offsets, (int)P.k_best, (long long)P.min_gain, S->d_cand.get(),
                            S->d_target_rows.get(), S->d_best.get());

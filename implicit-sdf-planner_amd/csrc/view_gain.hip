@@ -12,7 +12,7 @@
 // The lanes of a wavefront finish at different lengths, as the cast's do; a workgroup is two wavefronts for the cast's reason.
 // Nothing here writes to the ctx's map, its known grid, its products or its flags.
 #include "view_gain_run.hpp"
-#include "dev_block_sum.hpp"
+#include "dev_reduce.hpp"
 #include <algorithm>
 #include <cstring>
 

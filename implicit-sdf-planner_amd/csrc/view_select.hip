@@ -14,7 +14,7 @@
 //   then k rounds, a fixed sequence of launches without a hand-over; once the record's `done` is set the later kernels return at once:
 //   vs_marginal_kernel  grid = (blocks, views): popcount(bits & ~claimed[w]) over the view's segment, block_sum, one 64-bit atomicAdd per
 //                       workgroup into m[j]; a picked or unscored view, and a workgroup past the segment's end, is skipped (uniform).
-//   vs_pick_kernel      one workgroup: the largest vs_key(m[j], j) through the wavefronts and a few LDS words - no atomic, so no order to
+//   vs_pick_kernel      one workgroup: the largest vs_key(m[j], j) by dev_reduce.hpp's block_max (one barrier) - no atomic, so no order to
 //                       depend on; thread 0 writes the round's select row, round[j*], the running sums, or `done`; every m is cleared.
 //   vs_claim_kernel     the winner's segment, read from the record: claimed[w] |= bits.  A word occurs once per view: no atomic.
 //   vs_final_kernel     claimed |= K, where claimed_out is asked for.
@@ -22,7 +22,8 @@
 // Nothing here writes to the ctx's map, its known grid, its products or its flags; no kernel waits on another workgroup.
 #include "view_gain_run.hpp"
 #include "view_select_host.hpp"
-#include "dev_block_sum.hpp"
+#include "dev_reduce.hpp"
+#include "dev_scan.hpp"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -131,9 +132,7 @@ __global__ __launch_bounds__(VS_BLOCK) void vs_marginal_kernel(long long n_views
 
 __global__ __launch_bounds__(VS_BLOCK) void vs_pick_kernel(long long n_views, int r, long long min_gain, const long long *__restrict__ rows, long long *round,
                                                            unsigned long long *m, long long *__restrict__ select, VsCtl *ctl) {
-    __shared__ unsigned long long s_max[VS_WAVES];
-    if (ctl->done) return;          // (uniform: thread 0 writes it after the barriers)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (ctl->done) return;          // (uniform: thread 0 writes it after the barrier)
     unsigned long long top = 0;
     for (long long j = threadIdx.x; j < n_views; j += VS_BLOCK) {
         const unsigned long long mj = m[j];
@@ -142,15 +141,8 @@ __global__ __launch_bounds__(VS_BLOCK) void vs_pick_kernel(long long n_views, in
         const unsigned long long key = vs_key((long long)mj, j);
         top = key > top ? key : top;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_down(top, off, 64);
-        top = o > top ? o : top;
-    }
-    if (lane == 0) s_max[wave] = top;
-    __syncthreads();
+    top = block_max<VS_WAVES, false>(top);          // (called once: no second barrier)
     if (threadIdx.x != 0) return;
-    top = s_max[0];
-    for (int w = 1; w < VS_WAVES; w++) top = s_max[w] > top ? s_max[w] : top;
     if (top == 0 || vs_key_marginal(top) < min_gain) { ctl->done = 1; return; }
     const long long j = vs_key_view(top), marginal = vs_key_marginal(top), gain = rows[VG_ROW * j + 1];
     const long long cumulative = ctl->cumulative + marginal;
@@ -239,7 +231,6 @@ void select_pad(int64_t *select, long long from, long long k_select) {
     }
 }
 
-unsigned lane_blocks(long long n) { return (unsigned)std::max<long long>((n + VS_BLOCK - 1) / VS_BLOCK, 1); }
 // workgroups over n words or entries, each lane sized for a few
 unsigned wide_blocks(long long n) { return (unsigned)std::min<long long>(std::max<long long>((n + VS_BLOCK * VS_PER_LANE - 1) / (VS_BLOCK * VS_PER_LANE), 1), VS_MAX_X); }
 
@@ -301,7 +292,8 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
     HIPCHK(c, hipMemcpyAsync(S->d_poses, poses, nv * 12 * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, S->ctl.zero(st));
     HIPCHK(c, hipMemsetAsync(S->d_claimed, 0, nw * sizeof(unsigned), st));
-    hipLaunchKernelGGL(vs_begin_kernel, dim3(lane_blocks(std::max(n_views, rounds))), dim3(VS_BLOCK), 0, st, n_views, rounds, S->d_count.get(), S->d_m.get(),
+    // (n_views >= 1 here and a known grid has n_words >= 1: blocks() is at least one workgroup at both of its uses below)
+    hipLaunchKernelGGL(vs_begin_kernel, dim3(blocks(std::max(n_views, rounds), VS_BLOCK)), dim3(VS_BLOCK), 0, st, n_views, rounds, S->d_count.get(), S->d_m.get(),
                        S->d_round.get(), S->d_select.get());
     HIPCHK(c, hipGetLastError());
     // the gain, and after every chunk its views' lists
@@ -351,7 +343,7 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
         HIPCHK(c, hipGetLastError());
     }
     if (claimed_out) {
-        hipLaunchKernelGGL(vs_final_kernel, dim3(lane_blocks(n_words)), dim3(VS_BLOCK), 0, st, d_known, S->d_claimed.get(), n_words);
+        hipLaunchKernelGGL(vs_final_kernel, dim3(blocks(n_words, VS_BLOCK)), dim3(VS_BLOCK), 0, st, d_known, S->d_claimed.get(), n_words);
         HIPCHK(c, hipGetLastError());
     }
     ISDF_TRY(map_query::count_end(c, true, S->ev_select, st));

@@ -1,4 +1,4 @@
-"""The inputs on which the device tests hold the queries' counters to the host forms at the edges of dev_block_sum.hpp's block sum - a
+"""The inputs on which the device tests hold the queries' counters to the host forms at the edges of dev_reduce.hpp's block sum - a
 lane, a wavefront, a workgroup - and, here, the proof that the host forms count something in every counter on them: a counter that is 0
 on the host would hold nothing.  Ray cast: tests/test_map_raycast_host.py's 9 x 1 x 13 grid.  Depth camera: a 17 x 13 camera at
 tests/depth_cam_reference.py's poses (and, for the rays, the same intrinsics on images of exactly 1, 255 and 257 pixels, which 17 x 13

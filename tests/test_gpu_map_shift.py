@@ -348,6 +348,27 @@ def test_without_esdf_and_front_end_only_counts_and_occupancy_move(pkg, product_
     _same(_products(pkg, nocs, table="compute"), _products(pkg, _fresh(pkg, _shift(c_old, s), s)))
 
 
+def test_the_counters_where_the_last_wavefront_is_part_filled(pkg, product_lib):
+    """5 x 7 x 67 = 2345 voxels: the counts' kernel runs nine whole workgroups and 41 lanes, the occupancy's (587 dwords) two and 75 lanes,
+    and the leaving voxels of these shifts lie in the first workgroups, in the last lanes, or in all of them"""
+    dims = (5, 7, 67)
+    rng = np.random.default_rng(67)
+    counts = (rng.integers(1, 4, dims) * (rng.uniform(size=dims) < 0.5)).astype(np.uint32)
+    cells = np.argwhere(counts > 0)
+    eng = pkg.Engine(pkg.synth.default_config(pkg.capi.V1_SWEPT))
+    assert eng.set_pointcloud(_in_cells_at(np.zeros(3), cells, counts[tuple(cells.T)].astype(np.int64), rng), RES, THR, np.zeros(3), np.array(dims) * RES) == dims
+    assert np.array_equal(eng.map_counts(), counts)
+    idx = np.stack(np.meshgrid(*[np.arange(n) for n in dims], indexing="ij"), axis=-1)
+    for s in ((-1, 0, 0), (0, 0, 3), (0, -2, 0), (1, 2, -30)):         # (each leaves through a face that still holds points)
+        c_old = eng.map_counts()
+        gone = ((idx - np.array(s) < 0) | (idx - np.array(s) >= np.array(dims))).any(axis=-1)
+        info = eng.shift_map(s, force_path=2)
+        assert np.array_equal(eng.map_counts(), pkg.shift_grid_host(c_old, s, lib=product_lib)), s
+        assert np.array_equal(eng.get_grid(pkg.capi.GRID_OCCUPANCY)[0] != 0, eng.map_counts() >= THR), s
+        assert (info.counts_left, info.occupied_left) == (int(c_old[gone].sum()), int(((c_old >= THR) & gone).sum())), s
+        assert info.counts_left > 0 and info.occupied_left > 0, s
+
+
 # ---- 6. isdf_map_follow ---------------------------------------------------------------------------------------------------------------------
 def test_map_follow(pkg, product_lib):
     capi = pkg.capi

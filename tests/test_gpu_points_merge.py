@@ -240,6 +240,25 @@ def test_arbitrary_points_and_below(pkg, product_lib):
     assert np.array_equal(_bits(eng.get_points()[3 + len(tail):]), _bits(rows[~(rows[:, 3] < below), :3]))
 
 
+def test_points_outside_in_every_wavefront_of_two_workgroups(pkg, product_lib):
+    """the mark kernel's count of the points outside the grid, past one workgroup: 300 points (256 + 44: the second workgroup's only
+    wavefront is part filled), every third one outside, so every wavefront of both workgroups counts some"""
+    occ, esdf, res, T, cm = _world(pkg)
+    eng = _engine(pkg, occ, esdf, res)
+    eng.set_points(np.zeros((0, 3)))
+    eng.traj_check(T, cm, margin=MERGE_MARGIN)
+    rows = eng.traj_check_points()
+    old = np.random.default_rng(300).uniform(0.05, 0.95, (300, 3)) * np.array(occ.shape) * res + np.array(ORIGIN)
+    old[::3, 0] = np.array(ORIGIN)[0] - 1.0 - old[::3, 0]
+    eng.set_points(old)
+    info = eng.points_merge_check()
+    n_rows, tail, n_dup, n_out = _restate(old, rows, occ.shape, res)
+    assert n_out == 100 and n_rows == len(rows) > 0
+    assert (info["M_before"], info["n_rows"], info["n_added"], info["n_duplicate"], info["n_outside"]) == (300, n_rows, len(tail), n_dup, 100)
+    got = eng.get_points()
+    assert np.array_equal(_bits(got[:300]), _bits(old)) and np.array_equal(_bits(got[300:]), _bits(tail))
+
+
 # ---- 6. refusals -----------------------------------------------------------------------------------------------------------
 def test_refusals(pkg, product_lib):
     capi = pkg.capi
