@@ -346,7 +346,33 @@ __device__ __forceinline__ double shape_sdf_rotated(const DevShape &S, d3 pos, c
 
 // getonlyGrad1: central difference dx = 5e-6 (temp -= dx; temp += 2dx), normalised — Shape.hpp:32-57;
 // Box: forward difference dx = 0.01, not normalised — Shape.hpp:2363-2377; Ball: p/|p| — Shape.hpp:622-625.
-template <int KIND, bool IDENT = false>
+// One body per mode; shape_grad picks one at compile time (GMODE = the resolved isdf_grad_mode) or, GMODE = -1, by S.grad_mode.
+template <int KIND, bool IDENT>
+__device__ __forceinline__ d3 shape_grad_box_forward(const DevShape &S, d3 pr) {
+    const double dx = 0.01;
+    const double s0 = shape_sdf<KIND, IDENT>(S, pr);
+    const double gx = shape_sdf<KIND, IDENT>(S, mk3(pr.x + dx, pr.y, pr.z)) - s0;
+    const double gy = shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y + dx, pr.z)) - s0;
+    const double gz = shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y, pr.z + dx)) - s0;
+    return mk3(gx / dx, gy / dx, gz / dx);
+}
+template <int KIND, bool IDENT>
+__device__ __forceinline__ d3 shape_grad_central(const DevShape &S, d3 pr) {
+    const double dx = 0.000005;
+    double lo, hi;
+    lo = pr.x - dx; hi = lo + 2 * dx;
+    const double gx = shape_sdf<KIND, IDENT>(S, mk3(hi, pr.y, pr.z)) - shape_sdf<KIND, IDENT>(S, mk3(lo, pr.y, pr.z));
+    lo = pr.y - dx; hi = lo + 2 * dx;
+    const double gy = shape_sdf<KIND, IDENT>(S, mk3(pr.x, hi, pr.z)) - shape_sdf<KIND, IDENT>(S, mk3(pr.x, lo, pr.z));
+    lo = pr.z - dx; hi = lo + 2 * dx;
+    const double gz = shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y, hi)) - shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y, lo));
+#ifdef ISDF_LEAN_MATH
+    return normalized3_lean(mk3(gx, gy, gz));      // normalising makes the common factor 1 / (2 dx) irrelevant
+#else
+    return normalized3(mk3(gx / (2 * dx), gy / (2 * dx), gz / (2 * dx)));
+#endif
+}
+template <int KIND, bool IDENT = false, int GMODE = -1>
 __device__ __forceinline__ d3 shape_grad(const DevShape &S, d3 pr) {
     if constexpr (KIND == ISDF_SHAPE_MESH) { d3 g; mesh_sdf_grad(S.mesh, pr, g); return g; }
     if constexpr (KIND == ISDF_SHAPE_PROGRAM) {
@@ -368,30 +394,17 @@ __device__ __forceinline__ d3 shape_grad(const DevShape &S, d3 pr) {
         return normalized3(mk3(gx / (2 * dx), gy / (2 * dx), gz / (2 * dx)));
 #endif
     }
-    const int mode = S.grad_mode;   // resolved (never DEFAULT) by the host
-    if (mode == ISDF_GRAD_ANALYTIC_BALL) return normalized3(pr);
-    if constexpr (KIND < 0) if (mode == ISDF_GRAD_GRID) return grid_grad(S, pr);
-    if (mode == ISDF_GRAD_BOX_FORWARD) {
-        const double dx = 0.01;
-        const double s0 = shape_sdf<KIND, IDENT>(S, pr);
-        const double gx = shape_sdf<KIND, IDENT>(S, mk3(pr.x + dx, pr.y, pr.z)) - s0;
-        const double gy = shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y + dx, pr.z)) - s0;
-        const double gz = shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y, pr.z + dx)) - s0;
-        return mk3(gx / dx, gy / dx, gz / dx);
+    if constexpr (GMODE == ISDF_GRAD_ANALYTIC_BALL) return normalized3(pr);
+    else if constexpr (GMODE == ISDF_GRAD_BOX_FORWARD) return shape_grad_box_forward<KIND, IDENT>(S, pr);
+    else if constexpr (GMODE == ISDF_GRAD_CENTRAL) return shape_grad_central<KIND, IDENT>(S, pr);
+    else {
+        static_assert(GMODE == -1, "a compile-time gradient mode is central, box-forward or analytic-ball");
+        const int mode = S.grad_mode;   // resolved (never DEFAULT) by the host
+        if (mode == ISDF_GRAD_ANALYTIC_BALL) return normalized3(pr);
+        if constexpr (KIND < 0) if (mode == ISDF_GRAD_GRID) return grid_grad(S, pr);
+        if (mode == ISDF_GRAD_BOX_FORWARD) return shape_grad_box_forward<KIND, IDENT>(S, pr);
+        return shape_grad_central<KIND, IDENT>(S, pr);
     }
-    const double dx = 0.000005;
-    double lo, hi;
-    lo = pr.x - dx; hi = lo + 2 * dx;
-    const double gx = shape_sdf<KIND, IDENT>(S, mk3(hi, pr.y, pr.z)) - shape_sdf<KIND, IDENT>(S, mk3(lo, pr.y, pr.z));
-    lo = pr.y - dx; hi = lo + 2 * dx;
-    const double gy = shape_sdf<KIND, IDENT>(S, mk3(pr.x, hi, pr.z)) - shape_sdf<KIND, IDENT>(S, mk3(pr.x, lo, pr.z));
-    lo = pr.z - dx; hi = lo + 2 * dx;
-    const double gz = shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y, hi)) - shape_sdf<KIND, IDENT>(S, mk3(pr.x, pr.y, lo));
-#ifdef ISDF_LEAN_MATH
-    return normalized3_lean(mk3(gx, gy, gz));      // normalising makes the common factor 1 / (2 dx) irrelevant
-#else
-    return normalized3(mk3(gx / (2 * dx), gy / (2 * dx), gz / (2 * dx)));
-#endif
 }
 
 } // namespace isdf

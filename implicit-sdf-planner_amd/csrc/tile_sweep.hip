@@ -5,7 +5,8 @@
 //
 // One optimizer step = ONE launch when all its workgroups are resident (one trajectory, a rank's shard, small batches: the
 // tail's workgroups ride behind the sweep's, FUSED), otherwise two (DESIGN.md "integral sweep"):
-//   sweep_kernel<KIND, IDENT, FUSED>  one WORKGROUP per 4 constraint samples, one wavefront per sample:
+//   sweep_kernel<KIND, IDENT, FUSED, GMODE, PLAIN>  one WORKGROUP per 4 constraint samples, one wavefront per sample
+//                   (GMODE, PLAIN: what a fused launch's host-side constants let the compiler leave out - see the kernel):
 //                     (1) poses: one LANE per sample runs the serial fp64 chain (quintic, flatness forward, rotation, the
 //                         tile index box of getPointsInAABB, optional whole-tile cull, the window of tile rows the
 //                         shape's inflated bounding box can reach) and publishes it through LDS;
@@ -196,9 +197,10 @@ __device__ __forceinline__ bool xslot_take(double *slot, double &v, int timeout_
 // ---- inputs of one piece: from the caller's device arrays, or - host-direct step - from the staging buffer the first
 // workgroups of the launch fill from host-mapped memory
 struct PieceIn { const double *c; int ld; double T; };
+template <bool STAGED = true>       // false: the launch is known not to be host-direct (P.host_T null)
 __device__ __forceinline__ PieceIn piece_in(const SweepParams &P, int b, int i) {
     PieceIn r;
-    if (P.host_T) { const double *s = P.stage + ((size_t)b * P.N + i) * 19; r.c = s + 1; r.ld = 6; r.T = s[0]; }
+    if (STAGED && P.host_T) { const double *s = P.stage + ((size_t)b * P.N + i) * 19; r.c = s + 1; r.ld = 6; r.T = s[0]; }
     else { r.c = P.coeffs + (size_t)b * 18 * P.N + 6 * i; r.ld = 6 * P.N; r.T = P.T[(size_t)b * P.N + i]; }
     return r;
 }
@@ -548,19 +550,22 @@ template <bool EARLY, bool XF> __device__ __forceinline__ void tail_piece(const 
 // (tail_piece) - dispatched last, it does the collision-independent part of its samples while the sweep works and picks the
 // collision sums up from their slots as they arrive, so a small step (one trajectory) is one launch without the inter-kernel
 // gap.  Only launches whose workgroups are all resident at 3 per CU use it (launch_sweep); register budget: 3 waves per SIMD.
-template <int KIND, bool IDENT, bool FUSED>
+// GMODE: the shape's resolved gradient mode when the launch site names it (the exact pass then holds that mode's body only), -1:
+// read from P.shape.grad_mode.  PLAIN (fused only, sweep_plain): the launch is device-resident, whole, on one GPU, cull off - the
+// host-direct staging, the whole-tile cull fetch and the exchanging tail are not compiled in.  Same arithmetic in every variant.
+template <int KIND, bool IDENT, bool FUSED, int GMODE = -1, bool PLAIN = false>
 __global__ __launch_bounds__(64 * SW_SAMPLES, FUSED ? 3 : sweep_waves_per_simd(KIND, IDENT)) void sweep_kernel(const SweepParams P) {
     const int n_blocks = FUSED ? P.n_sweep_blocks : (int)gridDim.x;       // sweep workgroups of this launch
     if constexpr (FUSED) {
         __shared__ double s_tail[TL_THREADS][PARTIAL_STRIDE + 1];
         if ((int)blockIdx.x >= n_blocks) {
             if ((P.plan_cls_in || P.plan_lr_in) && !(P.dbg_flags & 2) && (threadIdx.x >> 6) == SW_SAMPLES - 1) plan_wave(P, (int)blockIdx.x - n_blocks, threadIdx.x & 63);       // while the sweep works: the NEXT step's dispatch order
-            if (P.xf.world > 1) tail_piece<false, true>(P, (int)blockIdx.x - n_blocks, s_tail);      // multi-GPU step: exchange inside
+            if (!PLAIN && P.xf.world > 1) tail_piece<false, true>(P, (int)blockIdx.x - n_blocks, s_tail);      // multi-GPU step: exchange inside
             else tail_piece<false, false>(P, (int)blockIdx.x - n_blocks, s_tail);
             return;
         }
     }
-    if constexpr (FUSED) {
+    if constexpr (FUSED && !PLAIN) {
         // host-direct step: the first workgroups bring the inputs in (one PCIe read round trip, instead of a copy command and
         // its completion in front of the launch)
         if (P.host_T && (int)blockIdx.x < (P.n_traj * P.N + STAGE_G - 1) / STAGE_G) stage_in(P, (int)blockIdx.x);
@@ -605,9 +610,9 @@ __global__ __launch_bounds__(64 * SW_SAMPLES, FUSED ? 3 : sweep_waves_per_simd(K
     if (pose_sidx < s_end) {
         const SampleId id = decode_sample(P, pose_sidx);
         bool staged = true;
-        if constexpr (FUSED) if (P.host_T) staged = stage_wait(P, id.b * P.N + id.i);
+        if constexpr (FUSED && !PLAIN) if (P.host_T) staged = stage_wait(P, id.b * P.N + id.i);
         if (!staged && P.stats) atomicMax(&P.stats[4], 1ull);
-        const PieceIn pin = piece_in(P, id.b, id.i);
+        const PieceIn pin = piece_in<!PLAIN>(P, id.b, id.i);
         const double *c = pin.c;
         const int ld = pin.ld;
         const double step = pin.T * P.inv_K;
@@ -626,7 +631,7 @@ __global__ __launch_bounds__(64 * SW_SAMPLES, FUSED ? 3 : sweep_waves_per_simd(K
         int flags = 0;
         if (P.enable_pos) {
             flags = 1;
-            if (P.cull_threshold > 0.0 && esdf_trilinear(G, pos) > P.cull_threshold) flags = 2;
+            if constexpr (!PLAIN) if (P.cull_threshold > 0.0 && esdf_trilinear(G, pos) > P.cull_threshold) flags = 2;
         }
         sp.flags = flags;      // bit 0 is confirmed by the wave that finishes the sample (the tile must exist)
         if ((flags & 1) && P.shape.prune_rows) {
@@ -655,8 +660,8 @@ __global__ __launch_bounds__(64 * SW_SAMPLES, FUSED ? 3 : sweep_waves_per_simd(K
         const long long sx = sample_of_rank((long long)blockIdx.x + (long long)ps * n_blocks);
         if (sx < s_end) {
             const SampleId id = decode_sample(P, sx);
-            if constexpr (FUSED) if (P.host_T) (void)stage_wait(P, id.b * P.N + id.i);      // (a miss is reported by wave 0)
-            const PieceIn pin = piece_in(P, id.b, id.i);
+            if constexpr (FUSED && !PLAIN) if (P.host_T) (void)stage_wait(P, id.b * P.N + id.i);      // (a miss is reported by wave 0)
+            const PieceIn pin = piece_in<!PLAIN>(P, id.b, id.i);
             const double step = pin.T * P.inv_K;
             Basis B;
             poly_basis(id.j * step, B);
@@ -912,7 +917,7 @@ __global__ __launch_bounds__(64 * SW_SAMPLES, FUSED ? 3 : sweep_waves_per_simd(K
                 const int n = min(pend, 64);
                 const unsigned ent = s_list[wave][(pend_head + min(lane, n - 1)) & (SW_LIST_CAP - 1)];
                 bool cand = lane < n;
-                if (use_filter) {
+                if constexpr (!DIRECT) if (use_filter) {
                     const float flx = (float)(ent & 1023u), fly = (float)((ent >> 10) & 1023u), flz = (float)(ent >> 20);
                     const float mx = fmaf(flx, resf, -pvx), my = fmaf(fly, resf, -pvy), mz = fmaf(flz, resf, -pvz);
                     const f3 pr = mkv<float>(Rf[0] * mx + Rf[3] * my + Rf[6] * mz, Rf[1] * mx + Rf[4] * my + Rf[7] * mz,
@@ -1220,7 +1225,7 @@ __global__ __launch_bounds__(64 * SW_SAMPLES, FUSED ? 3 : sweep_waves_per_simd(K
                     d3 g = mk3(0, 0, 0);
                     smoothed_l1_inv(P.safety_hor - shape_sdf<KIND, IDENT>(P.shape, prel), P.mu, P.inv_mu, f, df);
                     if (f > 0.0) {
-                        if constexpr (KIND != ISDF_SHAPE_MESH) g = shape_grad<KIND, IDENT>(P.shape, prel);
+                        if constexpr (KIND != ISDF_SHAPE_MESH) g = shape_grad<KIND, IDENT, GMODE>(P.shape, prel);
                         is_grad = true;
                         v[0] = f;
                         int csb = ls;
@@ -1789,6 +1794,13 @@ bool sweep_can_fuse(const SweepParams &P) {
     return (n_samples + SW_SAMPLES - 1) / SW_SAMPLES + (long long)(P.piece_end - P.piece_begin) <= fused_max_blocks() && (long long)P.n_traj * P.N <= 8 * fused_max_blocks();
 }
 
+// The plain variant of a fused step (sweep_kernel's PLAIN): inputs and outputs in device memory, every piece this rank's own, no
+// exchange inside the launch, whole-tile cull off - what the device-resident step and the L-BFGS callback run.  All from fields
+// the host fills in per launch; anything else takes the general variant.
+static bool sweep_plain(const SweepParams &P) {
+    return !P.host_T && !P.host_flag && P.xf.world <= 1 && !(P.cull_threshold > 0.0) && P.piece_begin == 0 && P.piece_end == P.n_traj * P.N;
+}
+
 static int sweep_target_blocks_mesh() {      // persistent workgroups of mesh_exact_kernel: 5 per CU (96 registers; at 6 the spills cost more than the sixth wavefront brings: 2.43 -> 3.01 ms)
     static int cus = 0;                       // (asked once: the property query costs milliseconds)
     if (cus == 0) {
@@ -1808,7 +1820,15 @@ void launch_sweep(const SweepParams &P0, hipStream_t stream, hipEvent_t ev_start
     const bool ident = P.shape.d.ident != 0;
     if (!fused) hipLaunchKernelGGL(pose_kernel, dim3((unsigned)((n_samples + POSE_THREADS - 1) / POSE_THREADS)), dim3(POSE_THREADS), 0, stream, P);      // the poses of every sample, one thread each
 #define ISDF_LAUNCH_SWEEP(K, I, F) hipExtLaunchKernelGGL((sweep_kernel<K, I, F>), grid, block, 0, stream, ev_start, ev_stop, 0, P)
-#define ISDF_SWEEP_CASE(K) case K: if (fused) ISDF_LAUNCH_SWEEP(K, true, true); else if (ident) ISDF_LAUNCH_SWEEP(K, true, false); else ISDF_LAUNCH_SWEEP(K, false, false); break;
+#define ISDF_LAUNCH_PLAIN(K, GM) hipExtLaunchKernelGGL((sweep_kernel<K, true, true, GM, true>), grid, block, 0, stream, ev_start, ev_stop, 0, P)
+    // The analytic classes' fused step has three instantiations: the plain variant (sweep_plain) with the gradient mode the host
+    // resolved in isdf_set_shape compiled in - central or box-forward -, and the general one (every other launch, any other mode).
+    const bool plain = fused && sweep_plain(P);
+    const int gm = P.shape.grad_mode;
+#define ISDF_SWEEP_CASE(K) case K: \
+        if (plain && gm == ISDF_GRAD_CENTRAL) ISDF_LAUNCH_PLAIN(K, ISDF_GRAD_CENTRAL); \
+        else if (plain && gm == ISDF_GRAD_BOX_FORWARD) ISDF_LAUNCH_PLAIN(K, ISDF_GRAD_BOX_FORWARD); \
+        else if (fused) ISDF_LAUNCH_SWEEP(K, true, true); else if (ident) ISDF_LAUNCH_SWEEP(K, true, false); else ISDF_LAUNCH_SWEEP(K, false, false); break;
     switch (P.shape.kind) {
     // one instantiation per analytic class (sw_manager.hpp:74-123 + Box): each inlines exactly one SDF formula
     ISDF_SWEEP_CASE(ISDF_SHAPE_TORUS) ISDF_SWEEP_CASE(ISDF_SHAPE_CAPPEDTORUS) ISDF_SWEEP_CASE(ISDF_SHAPE_CAPPEDCONE)
@@ -1816,7 +1836,8 @@ void launch_sweep(const SweepParams &P0, hipStream_t stream, hipEvent_t ev_start
     ISDF_SWEEP_CASE(ISDF_SHAPE_TWISTBOX) ISDF_SWEEP_CASE(ISDF_SHAPE_BENDBOX) ISDF_SWEEP_CASE(ISDF_SHAPE_TABLE)
     ISDF_SWEEP_CASE(ISDF_SHAPE_TREFOIL) ISDF_SWEEP_CASE(ISDF_SHAPE_SMOOTHDIFFERENCE) ISDF_SWEEP_CASE(ISDF_SHAPE_SMOOTHINTERSECTION)
     ISDF_SWEEP_CASE(ISDF_SHAPE_CSG) ISDF_SWEEP_CASE(ISDF_SHAPE_BOX)
-    ISDF_SWEEP_CASE(ISDF_SHAPE_PROGRAM)      // the interpreter (dev_shape_program.hpp): fused / identity offset / general like a class
+    // the interpreter (dev_shape_program.hpp): fused / identity offset / general like a class, one fused instantiation
+    case ISDF_SHAPE_PROGRAM: if (fused) ISDF_LAUNCH_SWEEP(ISDF_SHAPE_PROGRAM, true, true); else if (ident) ISDF_LAUNCH_SWEEP(ISDF_SHAPE_PROGRAM, true, false); else ISDF_LAUNCH_SWEEP(ISDF_SHAPE_PROGRAM, false, false); break;
     case ISDF_SHAPE_MESH:
         if (P.mq_items) {      // scan launch -> queue -> exact launch -> per-sample sums (the events span the three)
             hipExtLaunchKernelGGL((sweep_kernel<ISDF_SHAPE_MESH, false, false>), grid, block, 0, stream, ev_start, nullptr, 0, P);
@@ -1827,6 +1848,7 @@ void launch_sweep(const SweepParams &P0, hipStream_t stream, hipEvent_t ev_start
     default: if (fused) ISDF_LAUNCH_SWEEP(-1, true, true); else if (ident) ISDF_LAUNCH_SWEEP(-1, true, false); else ISDF_LAUNCH_SWEEP(-1, false, false); break;      // Ball (and anything new)
     }
 #undef ISDF_SWEEP_CASE
+#undef ISDF_LAUNCH_PLAIN
 #undef ISDF_LAUNCH_SWEEP
 }
 
