@@ -242,6 +242,16 @@ class IsdfViewSelectInfo(C.Structure):
                 ("lists_ms", C.c_double), ("select_ms", C.c_double)]
 
 
+class IsdfKnownErodeParams(C.Structure):
+    """isdf_known_erode_params (include/isdf_accel.h)."""
+    _fields_ = [("radius", C.c_int32), ("border", C.c_int32)]
+
+
+class IsdfKnownErodeInfo(C.Structure):
+    """isdf_known_erode_info (include/isdf_accel.h)."""
+    _fields_ = [("radius_used", C.c_int32), ("border", C.c_int32), ("known_voxels", C.c_int64), ("eroded_voxels", C.c_int64), ("erode_ms", C.c_double)]
+
+
 VIEW_SELECT_ROW = 4                     # int64 per round: view, marginal, cumulative, overlap; a round that did not happen: -1, 0, 0, 0
 # int64 per cluster: label, size, lo xyz, hi xyz, sum xyz, rep_voxel, rep_d2, first_pos, 0, 0
 FRONTIER_CLUSTER_ROW = 16
@@ -485,6 +495,8 @@ EXPORTED_SYMBOLS = [
     "isdf_frontier_cluster_params_default", "isdf_frontier_cluster_sizes", "isdf_map_frontier_clusters", "isdf_known_clusters_host",
     "isdf_view_candidates_params_default", "isdf_view_candidates_sizes", "isdf_view_candidates", "isdf_view_candidates_host",
     "isdf_view_select_params_default", "isdf_view_select_sizes", "isdf_view_select", "isdf_view_select_host",
+    "isdf_known_erode_params_default", "isdf_known_erode_sizes", "isdf_map_known_erode", "isdf_known_erode_host", "isdf_frontend_field_build_known",
+    "isdf_frontend_field_known_info",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -879,6 +891,19 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfViewSelectParams), C.sizeof(IsdfViewSelectInfo)]:
         raise RuntimeError(f"isdf_view_select structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfViewSelectParams), C.sizeof(IsdfViewSelectInfo)]}")
+    ep, ei = C.POINTER(IsdfKnownErodeParams), C.POINTER(IsdfKnownErodeInfo)
+    lib.isdf_known_erode_params_default.argtypes = [ep]
+    lib.isdf_known_erode_params_default.restype = None
+    lib.isdf_known_erode_sizes.argtypes = [ip]
+    lib.isdf_known_erode_sizes.restype = None
+    lib.isdf_map_known_erode.argtypes = [C.c_void_p, ep, C.c_void_p, ei]
+    lib.isdf_known_erode_host.argtypes = [C.c_void_p, i3, C.c_int, C.c_int, C.c_void_p]
+    lib.isdf_frontend_field_build_known.argtypes = [C.c_void_p, dp, ep, C.POINTER(IsdfFrontendFieldParams), C.POINTER(IsdfFrontendFieldInfo), ei]
+    lib.isdf_frontend_field_known_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.isdf_known_erode_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfKnownErodeParams), C.sizeof(IsdfKnownErodeInfo)]:
+        raise RuntimeError(f"isdf_known_erode structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfKnownErodeParams), C.sizeof(IsdfKnownErodeInfo)]}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

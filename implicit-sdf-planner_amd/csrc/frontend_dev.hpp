@@ -93,6 +93,10 @@ int isdf_field_change_end(isdf_ctx *c, isdf::FfChange dir, const int lo[3], cons
 // goal cell stays inside the grid and not everything leaves.  ..._begin enqueues the translation and the closing phase's reset after
 // the shift's configuration-space refresh and moves the goal cell; the caller synchronises the stream; ..._end runs the closing
 // phase's rounds, then the opening direction over the box lo .. hi (null: the whole grid).  ev: four events, [0] for ..._begin.
+// A field gated by the eroded known grid (isdf_frontend_field_build_known) follows nothing: both ..._wanted refuse it, and
+// whatever can change K or the map calls isdf_field_known_changed first, which drops it (1: a field was dropped; an ungated field is
+// not touched).
+int isdf_field_known_changed(isdf_ctx *c);
 bool isdf_field_shift_wanted(const isdf_ctx *c, const int32_t s[3]);
 int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start);
 int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], const hipEvent_t ev[4]);

@@ -11,6 +11,8 @@
 // order that reaches a fixed point reaches the same BYTES - those of frontend_field_host.hpp's Dijkstra.
 //   ff_init_kernel     one wavefront per 64 consecutive z: the free bits of the column (one ballot -> one 64-bit word), d = +inf, d[goal] = 0,
 //                      the goal's brick as the first active list, the count of free voxels;
+//   ff_init_known_kernel  the same for isdf_frontend_field_build_known: the ballot ANDed with the eroded known grid's bits of
+//                      the column, so that the free words carry "free and seen" and nothing after it knows of the gate;
 //   ff_relax_kernel    one workgroup per ACTIVE brick of 8 x 8 x 64 voxels (z fastest, 64 consecutive z per wavefront as in
 //                      fe_cspace_kernel): the brick and its one-voxel halo of d in LDS (10 x 10 x 66 doubles, 52.8 KB: three workgroups per
 //                      CU; a wavefront's 64 lanes read 64 consecutive doubles, which ds_read_b64 serves without bank conflicts), the
@@ -51,6 +53,8 @@
 #include "isdf_ctx.hpp"
 #include "frontend_dev.hpp"
 #include "frontend_field_host.hpp"
+#include "map_known_host.hpp"
+#include "map_query.hpp"
 #include "dev_reduce.hpp"
 #include <cmath>
 #include <cstring>
@@ -101,6 +105,39 @@ __global__ __launch_bounds__(256) void ff_init_kernel(FfDims D, const unsigned *
     const int z = (zb << 6) + lane;
     const long long v = xy * D.Z + z;
     const unsigned long long bits = ff_free_ballot(D, cspace, (size_t)v, z < D.Z);
+    if (z < D.Z) {
+        const bool is_goal = ((bits >> lane) & 1ull) && v == D.goal;
+        d[v] = is_goal ? 0.0 : __longlong_as_double(0x7FF0000000000000ll);
+        if (is_goal) {
+            const int x = (int)(xy / D.Y), y = (int)(xy % D.Y);
+            list[0] = ((x / FF_BX) * D.nby + y / FF_BY) * D.nbz + zb;
+            cnt[FF_CNT_ACTIVE] = 1ull;
+        }
+    }
+    if (lane == 0) {
+        fm[wv] = bits;
+        if (bits) atomicAdd(cnt + FF_CNT_FREE, (unsigned long long)__popcll(bits));
+    }
+}
+
+// ff_init_kernel for the field gated by the eroded known grid (isdf_frontend_field_build_known), a second kernel so that the
+// plain build's keeps its code to the instruction: the column's free ballot is ANDed with the 64 bits of `gate` that start at the
+// wavefront's first voxel - the grid is one stream of bits in voxel order (map_known_host.hpp), so they are two funnel-shifted dwords,
+// the same in every lane; bits past the column's end belong to the next column and meet a ballot that is 0 there.  The field's own fm
+// words then carry free & E, and nothing downstream knows of the gate.
+__global__ __launch_bounds__(256) void ff_init_known_kernel(FfDims D, const unsigned *__restrict__ cspace, unsigned long long *__restrict__ fm,
+                                                             double *__restrict__ d, int *__restrict__ list, unsigned long long *__restrict__ cnt,
+                                                             const unsigned *__restrict__ gate, long long gate_words) {
+    const long long wv = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long n_wv = (long long)D.X * D.Y * D.zblocks;
+    if (wv >= n_wv) return;
+    const int lane = threadIdx.x & 63;
+    const int zb = (int)(wv % D.zblocks);
+    const long long xy = wv / D.zblocks;
+    const int z = (zb << 6) + lane;
+    const long long a0 = xy * D.Z + (zb << 6), v = a0 + lane;
+    const unsigned long long seen = (unsigned long long)mk_bits_at(gate, gate_words, a0) | ((unsigned long long)mk_bits_at(gate, gate_words, a0 + 32) << 32);
+    const unsigned long long bits = ff_free_ballot(D, cspace, (size_t)v, z < D.Z) & seen;
     if (z < D.Z) {
         const bool is_goal = ((bits >> lane) & 1ull) && v == D.goal;
         d[v] = is_goal ? 0.0 : __longlong_as_double(0x7FF0000000000000ll);
@@ -596,23 +633,38 @@ extern "C" int isdf_frontend_field_release(isdf_ctx *c) {
     fe.d_field.release(); fe.d_field_free.release(); fe.d_field_list.release(); fe.d_field_flags.release(); fe.d_field_cnt.release();
     fe.h_field_cnt.release(); fe.field_rep.release(); fe.d_field_open.release();
     fe.d_field_shift.release(); fe.d_field_free_shift.release();
-    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false;
+    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false; fe.field_gated = false;
     return ISDF_OK;
 }
 
-extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], const isdf_frontend_field_params *params, isdf_frontend_field_info *info_out) {
-    if (!c) return ISDF_ERR_INVALID_ARG;
+namespace {
+
+// what both builds refuse, in this order, before anything is launched; erode: the gated build's parameters (null: the plain build)
+int ff_build_check(isdf_ctx *c, const double goal_xyz[3], const isdf_known_erode_params *erode, const isdf_frontend_field_params *params,
+                   const isdf_frontend_field_info *info_out) {
     if (!goal_xyz || !info_out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null goal / info");
     if (params && params->max_rounds < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "negative max_rounds");
+    if (erode) ISDF_TRY(known_erode_check(c, *erode));
     const int rdy = ff_ready(c);
     if (rdy != ISDF_OK) return rdy;
+    if (erode) ISDF_TRY(map_query::has_known(c, "the gated field needs a known grid (isdf_map_known_enable, then a map from isdf_set_pointcloud)"));
+    if ((size_t)c->grid.X * c->grid.Y * c->grid.Z > (size_t)0x7FFFFFF0) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the field indexes voxels with 31 bits");
+    return ISDF_OK;
+}
+
+// The build of either kind, behind ff_build_check.  erode: the gated build - the erosion's passes are queued first, on the same
+// stream, and ff_init_known_kernel reads their result; the build's first hand-over brings the erosion's record back with it.
+int ff_build(isdf_ctx *c, const double goal_xyz[3], const isdf_known_erode_params *erode, const isdf_frontend_field_params *params, isdf_frontend_field_info *info_out,
+             isdf_known_erode_info *gate_out) {
     isdf_ctx::FrontEnd &fe = c->fe;
     const DevGrid &G = c->grid;
     const size_t n_vox = (size_t)G.X * G.Y * G.Z;
-    if (n_vox > (size_t)0x7FFFFFF0) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, "the field indexes voxels with 31 bits");
     *info_out = isdf_frontend_field_info{};
     HIPCHK(c, hipSetDevice(c->device));
-    fe.field_valid = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false;
+    fe.field_valid = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false; fe.field_gated = false;
+    int gate_r = 0;
+    const unsigned *d_gate = nullptr;
+    if (erode) ISDF_TRY(known_erode_radius(c, *erode, &gate_r));
     if (!fe.d_cspace) {                                    // the table stays on the device: nothing of it comes to the host
         const int rc = isdf_frontend_cspace(c, nullptr, nullptr);
         if (rc != ISDF_OK) return rc;
@@ -638,13 +690,19 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
         hipError_t r = hipMemcpyAsync((void *)fe.h_field_cnt.get(), cnt, FF_CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
         return r == hipSuccess ? hipStreamSynchronize(st) : r;
     };
+    if (erode) ISDF_TRY(known_erode_launch(c, gate_r, erode->border, &d_gate));       // (outside the build's own bracket: erode_ms is its time)
     HIPCHK(c, hipEventRecord(ev[0], st));
     HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
-    hipLaunchKernelGGL(ff_init_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
-                       fe.d_field_list.get(), cnt);
+    if (erode)
+        hipLaunchKernelGGL(ff_init_known_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                           fe.d_field_list.get(), cnt, d_gate, (long long)c->known.n_words);
+    else
+        hipLaunchKernelGGL(ff_init_kernel, dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, st, D, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                           fe.d_field_list.get(), cnt);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, fetch());
+    if (erode && gate_out) known_erode_report(c, gate_r, erode->border, gate_out);
     const long long n_free = (long long)h[FF_CNT_FREE];
     // Jacobi relaxation fixes at least the voxels with one more edge on their shortest path per round: free voxels bound the rounds
     long long bound = n_free;
@@ -672,14 +730,49 @@ extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], 
     info_out->free_voxels = n_free;
     info_out->reached_voxels = (long long)h[FF_CNT_REACHED];
     info_out->device_ms = ms;
+    if (erode) { fe.field_gated = true; fe.field_gate_radius = gate_r; fe.field_gate_border = erode->border; }
     return ISDF_OK;
+}
+
+}  // namespace
+
+extern "C" int isdf_frontend_field_build(isdf_ctx *c, const double goal_xyz[3], const isdf_frontend_field_params *params, isdf_frontend_field_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    ISDF_TRY(ff_build_check(c, goal_xyz, nullptr, params, info_out));
+    return ff_build(c, goal_xyz, nullptr, params, info_out, nullptr);
+}
+
+extern "C" int isdf_frontend_field_build_known(isdf_ctx *c, const double goal_xyz[3], const isdf_known_erode_params *erode, const isdf_frontend_field_params *params,
+                                               isdf_frontend_field_info *info_out, isdf_known_erode_info *gate_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    const isdf_known_erode_params P = map_query::resolve(erode, isdf_known_erode_params_default);
+    ISDF_TRY(ff_build_check(c, goal_xyz, &P, params, info_out));
+    return ff_build(c, goal_xyz, &P, params, info_out, gate_out);
+}
+
+extern "C" int isdf_frontend_field_known_info(isdf_ctx *c, int32_t out[4]) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    if (!out) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null output");
+    const isdf_ctx::FrontEnd &fe = c->fe;
+    const bool gated = fe.field_valid && fe.field_gated;
+    out[0] = gated ? 1 : 0; out[1] = gated ? fe.field_gate_radius : 0; out[2] = gated ? fe.field_gate_border : 0; out[3] = 0;
+    return ISDF_OK;
+}
+
+// Whatever can change K or the map calls this first: a gated field describes the K of its build and is dropped, whatever the repair,
+// reopen and shift modes say (an ungated field is not touched).  1: a field was dropped.
+int isdf_field_known_changed(isdf_ctx *c) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    if (!fe.field_valid || !fe.field_gated) return 0;
+    fe.field_valid = false; fe.field_reachable = false; fe.field_gated = false;
+    return 1;
 }
 
 // ---- the field following an in-place change of the map (called by map_change.hip; the rules and their premises: this file's header)
 bool isdf_field_change_wanted(const isdf_ctx *c, FfChange dir) {
     const isdf_ctx::FrontEnd &fe = c->fe;
     const int mode = dir == FfChange::Closing ? c->field_repair_mode : c->field_reopen_mode;
-    return mode == 1 && fe.built && fe.field_valid && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
+    return mode == 1 && fe.built && fe.field_valid && !fe.field_gated && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
 }
 
 namespace {
@@ -802,7 +895,7 @@ int isdf_field_change_end(isdf_ctx *c, FfChange dir, const int lo[3], const int 
 // ---- the field carried through a shift of the map window (called by map_shift.hip; the rule and its proof: DESIGN 4.6.4)
 bool isdf_field_shift_wanted(const isdf_ctx *c, const int32_t s[3]) {
     const isdf_ctx::FrontEnd &fe = c->fe;
-    if (c->field_shift_mode != 1 || !fe.built || !fe.field_valid || fe.field_status == 2 || !fe.d_cspace || !fe.d_field) return false;
+    if (c->field_shift_mode != 1 || !fe.built || !fe.field_valid || fe.field_gated || fe.field_status == 2 || !fe.d_cspace || !fe.d_field) return false;
     const int dims[3] = {c->grid.X, c->grid.Y, c->grid.Z};
     for (int a = 0; a < 3; a++) {
         if (s[a] <= -dims[a] || s[a] >= dims[a]) return false;                              // everything left

@@ -64,6 +64,18 @@ struct MkRecord {
 static_assert(sizeof(MkRecord) == 64, "the known grid's record is one 64-byte line");
 int map_known_reset(isdf_ctx *c);           // map_known.hip: the map was replaced - with the mode on, all unknown at the new size
 
+// known_erode.hip, for isdf_map_known_erode and the gated cost-to-go field: ..._check: the parameters' ranges;
+// ..._radius: radius -1 resolved to the front end's footprint (ISDF_ERR_STATE without one); ..._launch: the passes, bracketed by the
+// state's events and followed by the record's copy, on the ctx's stream - *d_E: the eroded grid's words, which stay until the next
+// launch; ..._report: after a synchronisation of the stream, the info of the last launch.
+struct KnownErodeState;
+namespace isdf {
+int known_erode_check(isdf_ctx *c, const isdf_known_erode_params &P);
+int known_erode_radius(isdf_ctx *c, const isdf_known_erode_params &P, int *radius);
+int known_erode_launch(isdf_ctx *c, int radius, int border, const unsigned **d_E);
+void known_erode_report(isdf_ctx *c, int radius, int border, isdf_known_erode_info *out);
+}
+
 // What the swept-volume kernels need per point set (SweptParams): the optimizer step's (the ctx holds it) or the field query's
 // (SweptMeshState holds its own: the query never shares scratch with the step).  The point arrays grow together.
 struct SweptScratch {
@@ -107,6 +119,7 @@ struct isdf_ctx {
     Lazy<FrontierClusterState> fcl;             // isdf_map_frontier_clusters: own scratch (grows only)
     Lazy<ViewCandState> vcd;                    // isdf_view_candidates: own scratch (grows only); it scores through vgn's
     Lazy<ViewSelectState> vsl;                  // isdf_view_select: own scratch (grows only); it scores through vgn's
+    Lazy<KnownErodeState> ker;                  // isdf_map_known_erode / isdf_frontend_field_build_known: own scratch (grows only)
     DevBuf<unsigned> d_bits; bool bits_dirty = true;
     // the known grid (map_known.hip): one bit per voxel, 1 = some ray has visited it or the caller declared it known.  `on`
     // outlives maps (isdf_map_known_enable); d_bits holds n_words dwords while `have`; d_shift is where a window shift writes before the
@@ -242,10 +255,14 @@ struct isdf_ctx {
         // then changes places with d_field / d_field_free (one more copy of both stays allocated); the last carry's report
         DevBuf<double> d_field_shift; DevBuf<unsigned long long> d_field_free_shift;
         bool field_shifted = false; isdf_field_shift_info field_shift{};
+        // the field gated by the eroded known grid (isdf_frontend_field_build_known): its free words carry free & E, so
+        // whatever can change K or the map drops it (isdf_field_known_changed)
+        bool field_gated = false; int field_gate_radius = 0, field_gate_border = 0;
     } fe;
     int field_repair_mode = 0;                  // isdf_frontend_field_set_repair: outlives isdf_frontend_build (fe is reset by it)
     int field_reopen_mode = 0;                  // isdf_frontend_field_set_reopen: likewise
     int field_shift_mode = 0;                   // isdf_frontend_field_set_shift: likewise
+    bool gate_dropped = false;                  // map_change_ready dropped a gated field: the in-place change under way reports field_dropped = 1
     int traj_watch_mode = 0;                    // isdf_traj_check_set_watch: outlives the check (the watch itself: TrajCheckState::w)
     struct isdf_xchg *xchg = nullptr;           // peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip)
     isdf_progress_fn progress = nullptr;        // isdf_set_progress: the optimizer drivers' progress / cancel hook

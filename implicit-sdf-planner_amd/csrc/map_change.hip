@@ -63,6 +63,9 @@ int isdf::map_change_ready(isdf_ctx *c, const char *op, const void *in, long lon
     if (!c->have_geom || !c->d_occ) return isdf_fail(c, ISDF_ERR_STATE, (o + " needs an occupancy grid").c_str());
     if (needs_counts && !c->d_counts)
         return isdf_fail(c, ISDF_ERR_STATE, (o + ": no kept point counts (the map did not come from isdf_set_pointcloud, or isdf_update_voxels / isdf_clear_voxels changed it since)").c_str());
+    // a field gated by the eroded known grid describes the K and the map of its build: it goes here, also where the call then finds
+    // nothing to change, and whatever the repair, reopen and shift modes say
+    c->gate_dropped = isdf_field_known_changed(c) != 0;
     return ISDF_OK;
 }
 
@@ -120,7 +123,7 @@ int isdf::map_changed(isdf_ctx *c, bool voxels) {
     if (voxels) c->d_counts.release();
     c->bits_dirty = true;
     isdf_ctx::FrontEnd &fe = c->fe;
-    if (!fe.field_valid) return 0;
+    if (!fe.field_valid) return c->gate_dropped ? 1 : 0;          // (a gated field went in map_change_ready)
     fe.field_valid = false; fe.field_reachable = false;
     return 1;
 }

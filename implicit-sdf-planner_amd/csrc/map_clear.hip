@@ -252,6 +252,7 @@ int map_clear(isdf_ctx *c, const void *in, long long n_in, bool voxels, const is
     isdf_map_clear_info info{};
     empty_boxes(info);
     info.n_points = n_in;
+    info.field_dropped = c->gate_dropped ? 1 : 0;      // (a gated field went in map_change_ready, whatever this frame changes)
     MapUpdateState *Sp;
     int rc = map_begin(c, &Sp);
     if (rc) return rc;

@@ -21,6 +21,7 @@
 #include "map_query.hpp"
 #include "map_known_host.hpp"
 #include "map_change.hpp"
+#include "frontend_dev.hpp"
 #include "dev_reduce.hpp"
 #include "dev_scan.hpp"
 #include <algorithm>
@@ -245,10 +246,12 @@ extern "C" int isdf_map_known_enable(isdf_ctx *c, int on) {
     ISDF_TRY(map_query::single_device(c, "the known grid is not offered on a multi-device ctx"));
     isdf_ctx::Known &K = c->known;
     HIPCHK(c, hipSetDevice(c->device));
+    (void)isdf_field_known_changed(c);          // a field gated by K's erosion goes with either answer
     if (!on) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         K.on = K.have = false; K.n_words = 0; K.newly = K.merges = 0;
         K.d_bits.release(); K.d_shift.release(); K.d_front.release(); K.d_cnt.release(); K.d_base.release(); K.d_list.release(); K.d_scan_tmp.release();
+        c->ker.reset();                         // the erosion's scratch grids
         return ISDF_OK;
     }
     if (K.on) return ISDF_OK;           // (a grid that exists stays as it is)
@@ -273,6 +276,7 @@ extern "C" int isdf_map_known_fill(isdf_ctx *c, const int32_t *box, int value) {
     if (!box) box = whole;
     if (mk_box_bad(dims, box)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "filling the known grid: the box lies outside the grid or has lo > hi");
     ISDF_TRY(known_begin(c, "filling the known grid"));
+    (void)isdf_field_known_changed(c);          // K changes: a field gated by its erosion is dropped
     isdf_ctx::Known &K = c->known;
     MuBox B;
     for (int a = 0; a < 3; a++) { B.lo[a] = box[a]; B.hi[a] = box[3 + a]; }

@@ -176,6 +176,7 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     isdf_map_scan_info info{};
     empty_info(info);
     info.n_rays = n_rays;
+    info.clear.field_dropped = info.update.field_dropped = c->gate_dropped ? 1 : 0;       // (a gated field went in map_change_ready, whatever the rays change)
     MapUpdateState *Sp;
     int rc = map_begin(c, &Sp);
     if (rc) return rc;

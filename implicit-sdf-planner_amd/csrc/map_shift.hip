@@ -171,6 +171,7 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
     DevGrid &G = c->grid;
     const int32_t dims[3] = {G.X, G.Y, G.Z};
     for (int a = 0; a < 3; a++) { info.shift[a] = s[a]; info.bmin_new[a] = G.bmin[a]; }
+    info.field_dropped = c->gate_dropped ? 1 : 0;       // (a gated field went in map_change_ready, also where nothing moves)
     if (s[0] == 0 && s[1] == 0 && s[2] == 0) {          // nothing is touched, the epoch included
         if (info_out) *info_out = info;
         return ISDF_OK;

@@ -169,6 +169,7 @@ int map_update(isdf_ctx *c, const void *in, long long n_in, bool voxels, const i
     isdf_map_update_info info{};
     for (int a = 0; a < 3; a++) { info.dirty_lo[a] = 0; info.dirty_hi[a] = -1; }
     info.n_points = n_in;
+    info.field_dropped = c->gate_dropped ? 1 : 0;      // (a gated field went in map_change_ready, whatever this frame changes)
     MapUpdateState *Sp;
     int rc = map_begin(c, &Sp);
     if (rc) return rc;

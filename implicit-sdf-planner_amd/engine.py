@@ -459,6 +459,18 @@ def known_shift_host(bits, dims, shift, lib=None):
     return out
 
 
+def known_erode_host(bits, dims, radius, border=0, lib=None):
+    """isdf_known_erode_host: the eroded known grid's words - voxel v is set when every voxel of the cube of 2 radius + 1 a side round v is
+    known, a voxel outside the grid counting as `border`."""
+    lib = lib or capi.load_library()
+    w, d = _known_args(bits, dims)
+    out = np.zeros_like(w)
+    rc = lib.isdf_known_erode_host(w.ctypes.data_as(C.c_void_p), d, int(radius), int(border), out.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise IsdfError(rc, "isdf_known_erode_host")
+    return out
+
+
 def known_fill_host(bits, dims, box, value, lib=None):
     """isdf_known_fill_host: (the grid with the inclusive box (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z) - None: all of it - set or cleared,
     bits that went from 0 to 1).  Raises IsdfError for a box outside the grid or with lo > hi."""
@@ -1348,6 +1360,16 @@ class Engine:
         self._check(self.lib.isdf_map_known_get(self.h, out.ctypes.data_as(C.c_void_p), C.byref(info)))
         return out, info
 
+    def known_erode(self, radius=-1, border=0, want_bits=True):
+        """isdf_map_known_erode: (the eroded known grid's uint32 words - None when not wanted -, IsdfKnownErodeInfo).  Voxel v is set when
+        the whole cube of 2 radius + 1 voxels a side round it is known; radius -1: the front end's (kernel_size - 1) / 2; border: what
+        the grid's outside counts as (0 unseen, 1 seen).  Read-only."""
+        out = np.zeros(known_words(self._grid_dims()), dtype=np.uint32) if want_bits else None
+        p = capi.IsdfKnownErodeParams(int(radius), int(border))
+        info = capi.IsdfKnownErodeInfo()
+        self._check(self.lib.isdf_map_known_erode(self.h, C.byref(p), None if out is None else out.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return out, info
+
     def map_frontier(self, capacity=None, want_list=True):
         """isdf_map_frontier: (frontier words, voxel indices int64 ascending - None when not wanted -, IsdfMapFrontierInfo).  capacity:
         of the list (default: grown to the number of frontier voxels, which a first short call reports); an explicit one that is too
@@ -1483,7 +1505,9 @@ class Engine:
         """next_views, then view_select over the poses of all targets' best lists (in the order of the lists): the next k_select places to
         look, chosen by what they add together rather than each alone.  params go to next_views (clearance_voxels, k_best, min_gain, and
         the view gain's, which the selection shares); select_min_gain is the selection's min_gain.  Returns (poses float64 [n_selected, 12]
-        in the order picked, their marginal gains int64 [n_selected], their candidate indices int64 [n_selected], IsdfViewSelectInfo)."""
+        in the order picked, their marginal gains int64 [n_selected], their candidate indices int64 [n_selected], IsdfViewSelectInfo).
+        The loop's last link is frontend_field_build_known towards a picked pose's eye (poses[i, 3::4]): the cost-to-go field through
+        observed space only, off which frontend_field_paths reads the way there."""
         _, _, poses, _, best, _ = self.next_views(cam, offsets, connectivity=connectivity, min_size=min_size, **params)
         listed = best[best >= 0]
         gain = {k: v for k, v in params.items() if k in ("stride", "max_range_m", "scratch_bytes")}
@@ -1635,6 +1659,26 @@ class Engine:
         info = capi.IsdfFrontendFieldInfo()
         self._check(self.lib.isdf_frontend_field_build(self.h, _p(g), C.byref(p), C.byref(info)))
         return info
+
+    def frontend_field_build_known(self, goal, radius=-1, border=0, max_rounds=0):
+        """isdf_frontend_field_build_known: the field of the cell of `goal` through observed space only - a voxel is free when the
+        configuration-space table says so AND the whole cube of 2 radius + 1 voxels round it is known (known_erode's radius and border).
+        Returns (IsdfFrontendFieldInfo, IsdfKnownErodeInfo).  The robot's own cell is usually unseen: declare a box round it known first
+        (map_known_fill); the paths never need a free start cell.  Whatever changes the known grid or the map drops a gated field."""
+        g = np.ascontiguousarray(goal, dtype=np.float64).reshape(3)
+        p = capi.IsdfFrontendFieldParams()
+        self.lib.isdf_frontend_field_params_default(C.byref(p))
+        p.max_rounds = int(max_rounds)
+        e = capi.IsdfKnownErodeParams(int(radius), int(border))
+        info, gate = capi.IsdfFrontendFieldInfo(), capi.IsdfKnownErodeInfo()
+        self._check(self.lib.isdf_frontend_field_build_known(self.h, _p(g), C.byref(e), C.byref(p), C.byref(info), C.byref(gate)))
+        return info, gate
+
+    def frontend_field_known_info(self):
+        """isdf_frontend_field_known_info: (gated, radius_used, border) of the live field; zeros for an ungated field or none."""
+        out = (C.c_int32 * 4)()
+        self._check(self.lib.isdf_frontend_field_known_info(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def frontend_field(self, xyz=None):
         """The whole field, float64 [X, Y, Z] (cells; +inf where a voxel is not free or cannot reach the goal), or, with `xyz`

@@ -2115,6 +2115,69 @@ int isdf_view_select_host(const uint32_t *bits, const uint8_t *occ, const double
                           const isdf_depth_camera *camera, const double *poses, long long n_views, const isdf_view_select_params *params, int64_t *rows_out,
                           int64_t *select_out, int64_t *round_out, uint32_t *claimed_out, isdf_view_select_info *info_out);
 
+/* ---- planning through observed space only: the eroded known grid and the field gated by it ------------------------ */
+/* The configuration-space table knows "occupied" and "not occupied": a voxel behind a wall no sensor has looked behind is free to it,
+ * and isdf_frontend_field_build plans through it.  The eroded known grid says, for every voxel, whether the whole cube of voxels a robot
+ * centred there can touch has been observed; the gated build closes every voxel for which it has not.  Integers only.
+ *   DEFINITION.  K is the known grid above: voxel a = (x * ny + y) * nz + z is bit a & 31 of word a >> 5, ceil(nx ny nz / 32) words, the
+ *   tail bits 0.  For a radius r >= 0 and border in {0, 1}
+ *     E[v] = 1  iff  for every u with max(|ux - vx|, |uy - vy|, |uz - vz|) <= r:
+ *                    (u inside the grid and K[u] = 1)  or  (u outside the grid and border = 1)
+ *   in K's layout, tail bits 0.  r = 0: E = K.  border = 0: the grid's outside counts as unseen - right for a window that follows the
+ *   robot; border = 1: it counts as seen - right for a fixed world box.  A radius of the largest dimension or more gives, with border = 0,
+ *   all 0, and with border = 1 all 1 when K is all 1 and all 0 otherwise.
+ *   radius = -1 (the default) means (kernel_size - 1) / 2 of the last isdf_frontend_build, the footprint the configuration-space pass
+ *   reads; ISDF_ERR_STATE without a front end.  Otherwise 0 <= radius <= 64.
+ * isdf_map_known_erode: E of the ctx's K on the device - three one-axis passes over the bit stream, 2 r + 1 reads per dword and pass, not
+ * (2 r + 1)^3 per voxel.  bits_out (nullable): E's words; info_out (nullable): radius_used, border, known_voxels = |K|, eroded_voxels = |E|,
+ * erode_ms = device time of the passes.  ERRORS, all before anything is launched, in this order: a null ctx (ISDF_ERR_INVALID_ARG); a
+ * border other than 0 or 1, then a radius outside -1 .. 64 (ISDF_ERR_INVALID_ARG); a multi-device ctx (ISDF_ERR_UNSUPPORTED); no known
+ * grid (ISDF_ERR_STATE); radius -1 without a front end (ISDF_ERR_STATE).  The call is read-only: K, the occupancy, a kept field, an armed
+ * watch, every kept report and the epochs are untouched; its scratch (two bit grids) grows only, so a second call of a size allocates
+ * nothing (isdf_debug_live_bytes), and two calls give the same bytes.
+ * isdf_known_erode_host: plain host code, no ctx, no device, the same bytes.  bits_out must not be bits.  ISDF_ERR_INVALID_ARG, with
+ * nothing written, in this order: null or aliased grids; bad dims (each 1 .. 4096); a border other than 0 or 1; a radius outside 0 .. 64.
+ *   THE GATED FIELD.  isdf_frontend_field_build_known is isdf_frontend_field_build over
+ *     free'[v] = (any attitude bit of table[v]) && E[v],
+ *   E eroded in the same call from the K of that moment: d is the least fixed point above over free', its bytes those of
+ *   isdf_frontend_field_host on table'[v] = E[v] ? table[v] : 0.  A goal cell with E = 0 gives reachable = 0 and status = 1, as an
+ *   occupied goal does.  info_out->free_voxels counts free'; gate_out (nullable) is the erosion's info.  Afterwards
+ *   isdf_frontend_field_get / _value / _paths[_device] work on the gated field as on any other: a path steps on voxels with E = 1 only,
+ *   its start cell excepted, which need not be free.  ERRORS, all before anything is launched, in this order: a null ctx; a null goal or
+ *   info; a negative max_rounds; a border other than 0 or 1, then a radius outside -1 .. 64 (all ISDF_ERR_INVALID_ARG); a multi-device ctx
+ *   (ISDF_ERR_UNSUPPORTED); no front end (ISDF_ERR_STATE); no known grid (ISDF_ERR_STATE); more than 2^31 - 16 voxels
+ *   (ISDF_ERR_UNSUPPORTED).  isdf_frontend_field_build itself launches what it always launched.
+ *   isdf_frontend_field_known_info: out = {gated, radius_used, border, 0} of the live field; zeros for an ungated field or none.
+ *   THE ROBOT'S OWN CELL is usually unseen - no ray starts inside the robot -, so E is 0 round it and no gated path could leave it.  A
+ *   caller declares a box round the robot known first (isdf_map_known_fill), as it does for the frontier; the paths never need a free
+ *   start cell.
+ *   DROPPED, NOT CARRIED.  A gated field describes the K of its build.  Everything that can change K or the map drops it - field_valid
+ *   goes false and the getters answer "isdf_frontend_field_build has not been called" -: isdf_update_pointcloud / _voxels,
+ *   isdf_clear_pointcloud / _voxels, isdf_integrate_scan / _depth (also when no occupancy changed), isdf_shift_map, isdf_map_follow (also
+ *   when it does not move), once the call's own state checks have passed; isdf_map_known_fill, isdf_map_known_enable and
+ *   isdf_frontend_build.  The repair, reopen and shift modes do not apply to it: nothing of them runs and their _info calls report none.
+ *   An ungated field behaves in all of these exactly as before.
+ * Not offered: the A* (isdf_frontend_astar_search) over the gated table; a gate for isdf_traj_check (isdf_traj_known_horizon reports the
+ * first unknown voxel a trajectory comes near); a gated field repaired, reopened or carried through map changes. */
+typedef struct isdf_known_erode_params {
+    int32_t radius;               /* default -1: the front end's (kernel_size - 1) / 2; else 0 .. 64 */
+    int32_t border;               /* default 0: the outside counts as unseen; 1: as seen */
+} isdf_known_erode_params;
+
+typedef struct isdf_known_erode_info {
+    int32_t radius_used, border;
+    int64_t known_voxels, eroded_voxels;
+    double  erode_ms;
+} isdf_known_erode_info;
+
+void isdf_known_erode_params_default(isdf_known_erode_params *p);       /* null-safe */
+void isdf_known_erode_sizes(int sizes_out[2]);                          /* null-safe; sizeof of the params and of the info */
+int isdf_map_known_erode(isdf_ctx *ctx, const isdf_known_erode_params *params, uint32_t *bits_out, isdf_known_erode_info *info_out);
+int isdf_known_erode_host(const uint32_t *bits, const int32_t dims[3], int radius, int border, uint32_t *bits_out);
+int isdf_frontend_field_build_known(isdf_ctx *ctx, const double goal_xyz[3], const isdf_known_erode_params *erode, const isdf_frontend_field_params *params,
+                                    isdf_frontend_field_info *info_out, isdf_known_erode_info *gate_out);
+int isdf_frontend_field_known_info(isdf_ctx *ctx, int32_t out[4]);
+
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
  * the shipped src/plan_manager/map_pcds are "FIELDS x y z / DATA ascii"): xyz_out = up to `capacity` points x 3 floats (may be
