@@ -100,6 +100,16 @@ class IsdfFieldRepairInfo(C.Structure):
 FIELD_REOPEN_DROP, FIELD_REOPEN_LOWER = 0, 1             # isdf_frontend_field_set_reopen
 
 
+FIELD_KNOWN_FOLLOW_DROP, FIELD_KNOWN_FOLLOW_FOLLOW = 0, 1    # isdf_frontend_field_set_known_follow
+
+
+class IsdfFieldFollowInfo(C.Structure):
+    """isdf_field_follow_info (include/isdf_accel.h)."""
+    _fields_ = [("opening", C.c_int32), ("closing", C.c_int32), ("radius_used", C.c_int32), ("border", C.c_int32), ("known_voxels", C.c_int64),
+                ("eroded_voxels", C.c_int64), ("opened_voxels", C.c_int64), ("closed_voxels", C.c_int64), ("free_voxels", C.c_int64),
+                ("reached_voxels", C.c_int64), ("reachable", C.c_int32), ("status", C.c_int32), ("erode_ms", C.c_double), ("device_ms", C.c_double)]
+
+
 class IsdfFieldReopenInfo(C.Structure):
     """isdf_field_reopen_info (include/isdf_accel.h)."""
     _fields_ = [("opened_voxels", C.c_int64), ("opened_reached", C.c_int64), ("reached_before", C.c_int64), ("reached_voxels", C.c_int64),
@@ -497,6 +507,7 @@ EXPORTED_SYMBOLS = [
     "isdf_view_select_params_default", "isdf_view_select_sizes", "isdf_view_select", "isdf_view_select_host",
     "isdf_known_erode_params_default", "isdf_known_erode_sizes", "isdf_map_known_erode", "isdf_known_erode_host", "isdf_frontend_field_build_known",
     "isdf_frontend_field_known_info",
+    "isdf_frontend_field_set_known_follow", "isdf_frontend_field_follow_info", "isdf_frontend_field_follow_sizes",
 ]
 
 HOST_PATH_COPY, HOST_PATH_DIRECT_MAPPED, HOST_PATH_DIRECT_BAR, HOST_PATH_DEVICE_CALLBACK = 0, 1, 2, 3
@@ -904,6 +915,13 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfKnownErodeParams), C.sizeof(IsdfKnownErodeInfo)]:
         raise RuntimeError(f"isdf_known_erode structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfKnownErodeParams), C.sizeof(IsdfKnownErodeInfo)]}")
+    lib.isdf_frontend_field_set_known_follow.argtypes = [C.c_void_p, C.c_int]
+    lib.isdf_frontend_field_follow_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldFollowInfo)]
+    lib.isdf_frontend_field_follow_sizes.argtypes = [ip]
+    lib.isdf_frontend_field_follow_sizes.restype = None
+    lib.isdf_frontend_field_follow_sizes(sz)
+    if sz[0] != C.sizeof(IsdfFieldFollowInfo):
+        raise RuntimeError(f"isdf_field_follow_info: the library has {sz[0]}, the mirror {C.sizeof(IsdfFieldFollowInfo)}")
     lib.isdf_frontend_field_set_repair.argtypes = [C.c_void_p, C.c_int]
     lib.isdf_frontend_field_repair_info.argtypes = [C.c_void_p, C.POINTER(IsdfFieldRepairInfo)]
     lib.isdf_frontend_field_repair_sizes.argtypes = [ip]

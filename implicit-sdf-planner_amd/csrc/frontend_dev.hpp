@@ -93,10 +93,21 @@ int isdf_field_change_end(isdf_ctx *c, isdf::FfChange dir, const int lo[3], cons
 // goal cell stays inside the grid and not everything leaves.  ..._begin enqueues the translation and the closing phase's reset after
 // the shift's configuration-space refresh and moves the goal cell; the caller synchronises the stream; ..._end runs the closing
 // phase's rounds, then the opening direction over the box lo .. hi (null: the whole grid).  ev: four events, [0] for ..._begin.
-// A field gated by the eroded known grid (isdf_frontend_field_build_known) follows nothing: both ..._wanted refuse it, and
-// whatever can change K or the map calls isdf_field_known_changed first, which drops it (1: a field was dropped; an ungated field is
-// not touched).
+// A field gated by the eroded known grid (isdf_frontend_field_build_known) is never carried through a shift, and with
+// follow mode 0 (isdf_frontend_field_set_known_follow) it follows nothing: whatever can change K or the map calls
+// isdf_field_known_changed first, which drops it (1: a field was dropped; an ungated field is not touched).  With follow mode 1
+//  that call keeps a gated field that is valid, a fixed point and has its table - isdf_field_follow_wanted - and the
+// calling driver must run the stages or drop the field itself (isdf_field_gate_drop: the unconditional drop, which the shift and
+// isdf_map_known_enable call): isdf_field_change_wanted then answers for a gated field by the follow mode alone, in both directions,
+// and isdf_field_change_begin re-erodes K at the field's own (radius, border) and marks with ballot(table) & E.
+// isdf_field_follow_stage: one stage on its own - begin, the synchronisation, end -, for a change of K without a table refresh; a
+// failure or a bit against the direction drops the field (*kept = 0).  isdf_field_follow_call: a new public call begins - the next
+// followed stage starts a new isdf_field_follow_info.
 int isdf_field_known_changed(isdf_ctx *c);
+int isdf_field_gate_drop(isdf_ctx *c);
+bool isdf_field_follow_wanted(const isdf_ctx *c);
+void isdf_field_follow_call(isdf_ctx *c);
+int isdf_field_follow_stage(isdf_ctx *c, isdf::FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *kept);
 bool isdf_field_shift_wanted(const isdf_ctx *c, const int32_t s[3]);
 int isdf_field_shift_begin(isdf_ctx *c, const int32_t s[3], hipEvent_t ev_start);
 int isdf_field_shift_end(isdf_ctx *c, const int32_t s[3], const int lo[3], const int hi[3], const hipEvent_t ev[4]);

@@ -37,6 +37,8 @@
 //                           on the goal voxel, when it opened, stores d = 0;
 //   ff_repair_reset_kernel  closing only, one workgroup per brick: +inf wherever tau <= d < +inf (tau read from device memory), the
 //                           brick flagged when it reset a voxel;
+//   ff_mark_known_kernel<dir>  the mark for a gated field that follows the change (isdf_frontend_field_set_known_follow):
+//                           the new ballot ANDed with the freshly eroded known grid's bits of the column, as ff_init_known_kernel reads them;
 // then ff_compact_kernel and the rounds of the build from the flagged bricks, the count of reached voxels, and
 //   ff_reopen_count_kernel  opening only, over the same box: the opened voxels that hold a finite d.
 // Closing keeps every d < tau: the chain of minimising neighbours from such a voxel to the goal passes only voxels with d < tau, none
@@ -317,6 +319,54 @@ __global__ __launch_bounds__(256) void ff_mark_kernel(FfDims D, FfBox B, const u
     } else {
         if (mine && (long long)v == D.goal) {
             d[v] = 0.0;                                    // the goal cell had not been free: the field was all +inf
+            rec->goal_opened = 1ull;
+        }
+    }
+    if (lane != 0) return;
+    if (!closing) open[C.wv] = changed;
+    if (now == old) return;
+    fm[col * D.zblocks + C.zb] = now;
+    if (changed) {
+        atomicAdd(&rec->changed, (unsigned long long)__popcll(changed));
+        if (!closing) flags[((C.x / FF_BX) * D.nby + C.y / FF_BY) * D.nbz + C.zb] = 1u;
+    }
+    if (hit) atomicAdd(&rec->changed_reached, (unsigned long long)__popcll(hit));
+    if (against) rec->premise_violated = 1ull;            // outside the premise: the host drops the field
+}
+
+// ff_mark_kernel for a gated field that follows the change (isdf_frontend_field_set_known_follow), a second kernel for
+// ff_init_known_kernel's reason: the new word is the column's free ballot ANDed with the 64 bits of the freshly eroded grid that start
+// at the wavefront's first voxel, read as that kernel reads them.  The kept word carries free & E_old, so the comparison is between the
+// gated sets, and a bit of either the table or E that moved against the direction raises the premise word.
+template <FfChange DIR>
+__global__ __launch_bounds__(256) void ff_mark_known_kernel(FfDims D, FfBox B, const unsigned *__restrict__ cspace, unsigned long long *__restrict__ fm, double *__restrict__ d,
+                                                             unsigned *__restrict__ flags, unsigned long long *__restrict__ open, FfRecord *__restrict__ rec,
+                                                             const unsigned *__restrict__ gate, long long gate_words) {
+    constexpr bool closing = DIR == FfChange::Closing;
+    FfColumn C;
+    if (!ff_box_column(B, C)) return;
+    const int lane = threadIdx.x & 63;
+    const int z = (C.zb << 6) + lane;
+    const size_t col = (size_t)C.x * D.Y + C.y;
+    const long long a0 = (long long)col * D.Z + (C.zb << 6);
+    const size_t v = (size_t)a0 + lane;
+    const unsigned long long seen = (unsigned long long)mk_bits_at(gate, gate_words, a0) | ((unsigned long long)mk_bits_at(gate, gate_words, a0 + 32) << 32);
+    const unsigned long long now = ff_free_ballot(D, cspace, v, z < D.Z) & seen;
+    const unsigned long long old = fm[col * D.zblocks + C.zb];
+    const unsigned long long changed = closing ? old & ~now : now & ~old, against = closing ? now & ~old : old & ~now;
+    const bool mine = (changed >> lane) & 1ull;            // (a set bit of the kept or of the new word: z < D.Z)
+    unsigned long long hit = 0ull;
+    if (closing) {
+        bool reached = false;
+        if (mine) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(d[v]);
+            reached = bits < FF_INF_BITS;
+            if (reached) { atomicMin(&rec->tau_bits, bits); d[v] = __longlong_as_double((long long)FF_INF_BITS); }
+        }
+        hit = __ballot(reached);
+    } else {
+        if (mine && (long long)v == D.goal) {
+            d[v] = 0.0;                                    // the goal cell had been closed by the table or by the gate: the field was all +inf
             rec->goal_opened = 1ull;
         }
     }
@@ -633,7 +683,7 @@ extern "C" int isdf_frontend_field_release(isdf_ctx *c) {
     fe.d_field.release(); fe.d_field_free.release(); fe.d_field_list.release(); fe.d_field_flags.release(); fe.d_field_cnt.release();
     fe.h_field_cnt.release(); fe.field_rep.release(); fe.d_field_open.release();
     fe.d_field_shift.release(); fe.d_field_free_shift.release();
-    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false; fe.field_gated = false;
+    fe.field_valid = false; fe.field_reachable = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false; fe.field_gated = false; fe.field_followed = false;
     return ISDF_OK;
 }
 
@@ -661,7 +711,7 @@ int ff_build(isdf_ctx *c, const double goal_xyz[3], const isdf_known_erode_param
     const size_t n_vox = (size_t)G.X * G.Y * G.Z;
     *info_out = isdf_frontend_field_info{};
     HIPCHK(c, hipSetDevice(c->device));
-    fe.field_valid = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false; fe.field_gated = false;
+    fe.field_valid = false; fe.field_repaired = false; fe.field_reopened = false; fe.field_shifted = false; fe.field_gated = false; fe.field_followed = false;
     int gate_r = 0;
     const unsigned *d_gate = nullptr;
     if (erode) ISDF_TRY(known_erode_radius(c, *erode, &gate_r));
@@ -761,18 +811,36 @@ extern "C" int isdf_frontend_field_known_info(isdf_ctx *c, int32_t out[4]) {
 
 // Whatever can change K or the map calls this first: a gated field describes the K of its build and is dropped, whatever the repair,
 // reopen and shift modes say (an ungated field is not touched).  1: a field was dropped.
+// With follow mode 1 (isdf_frontend_field_set_known_follow) a gated field that can follow is kept: the calling driver
+// runs the stages or drops it (isdf_field_gate_drop).
 int isdf_field_known_changed(isdf_ctx *c) {
-    isdf_ctx::FrontEnd &fe = c->fe;
-    if (!fe.field_valid || !fe.field_gated) return 0;
-    fe.field_valid = false; fe.field_reachable = false; fe.field_gated = false;
-    return 1;
+    if (isdf_field_follow_wanted(c)) return 0;
+    return isdf_field_gate_drop(c);
 }
 
+int isdf_field_gate_drop(isdf_ctx *c) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    if (!fe.field_gated) return 0;
+    const bool was_valid = fe.field_valid;
+    if (fe.field_followed) fe.field_repaired = fe.field_reopened = false;          // (the stages' reports go with the field they describe)
+    fe.field_valid = false; fe.field_reachable = false; fe.field_gated = false; fe.field_followed = false;
+    return was_valid ? 1 : 0;
+}
+
+bool isdf_field_follow_wanted(const isdf_ctx *c) {
+    const isdf_ctx::FrontEnd &fe = c->fe;
+    return c->field_known_follow_mode == 1 && fe.built && fe.field_valid && fe.field_gated && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
+}
+
+void isdf_field_follow_call(isdf_ctx *c) { c->fe.follow_fresh = true; }
+
 // ---- the field following an in-place change of the map (called by map_change.hip; the rules and their premises: this file's header)
+// A gated field is governed by the follow mode alone, in both directions; an ungated one by the direction's own mode.
 bool isdf_field_change_wanted(const isdf_ctx *c, FfChange dir) {
     const isdf_ctx::FrontEnd &fe = c->fe;
+    if (fe.field_gated) return isdf_field_follow_wanted(c);
     const int mode = dir == FfChange::Closing ? c->field_repair_mode : c->field_reopen_mode;
-    return mode == 1 && fe.built && fe.field_valid && !fe.field_gated && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
+    return mode == 1 && fe.built && fe.field_valid && fe.field_status != 2 && (bool)fe.d_cspace && (bool)fe.d_field;
 }
 
 namespace {
@@ -809,15 +877,31 @@ int isdf_field_change_begin(isdf_ctx *c, FfChange dir, const int lo[3], const in
     unsigned long long *cnt = fe.d_field_cnt.get();
     unsigned *flags = fe.d_field_flags.get();
     const hipStream_t st = c->stream;
+    // a gated field: K eroded again at the field's own radius and border, queued with no synchronisation of its own and outside the
+    // stage's bracket (erode_ms is its time); its record comes back with the stage's hand-over
+    const bool gated = fe.field_gated;
+    const unsigned *d_gate = nullptr;
+    if (gated) {
+        ISDF_TRY(map_query::has_known(c, "the gated field's follow needs the known grid"));
+        ISDF_TRY(known_erode_launch(c, fe.field_gate_radius, fe.field_gate_border, &d_gate));
+    }
+    const long long gate_words = (long long)c->known.n_words;
     HIPCHK(c, hipEventRecord(ev_start, st));
     HIPCHK(c, fe.field_rep.put(ff_record_empty(), st));
     HIPCHK(c, hipMemsetAsync(cnt, 0, FF_CNT_WORDS * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(flags, 0, 2 * (size_t)n_bricks * sizeof(unsigned), st));
     if (closing) {
-        hipLaunchKernelGGL(ff_mark_kernel<FfChange::Closing>, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
-                           (unsigned *)nullptr, (unsigned long long *)nullptr, rec);
+        if (gated)
+            hipLaunchKernelGGL(ff_mark_known_kernel<FfChange::Closing>, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_cspace.get(), fe.d_field_free.get(),
+                               fe.d_field.get(), (unsigned *)nullptr, (unsigned long long *)nullptr, rec, d_gate, gate_words);
+        else
+            hipLaunchKernelGGL(ff_mark_kernel<FfChange::Closing>, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                               (unsigned *)nullptr, (unsigned long long *)nullptr, rec);
         hipLaunchKernelGGL(ff_repair_reset_kernel, dim3((unsigned)n_bricks), dim3(256), 0, st, D, fe.d_field.get(), flags, rec);
-    } else
+    } else if (gated)
+        hipLaunchKernelGGL(ff_mark_known_kernel<FfChange::Opening>, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
+                           flags, fe.d_field_open.get(), rec, d_gate, gate_words);
+    else
         hipLaunchKernelGGL(ff_mark_kernel<FfChange::Opening>, dim3(ff_box_blocks(B)), dim3(256), 0, st, D, B, fe.d_cspace.get(), fe.d_field_free.get(), fe.d_field.get(),
                            flags, fe.d_field_open.get(), rec);
     hipLaunchKernelGGL(ff_compact_kernel, dim3(1), dim3(1024), 0, st, flags, fe.d_field_list.get(), cnt, fe.h_field_cnt.dev(), n_bricks);
@@ -888,8 +972,42 @@ int isdf_field_change_end(isdf_ctx *c, FfChange dir, const int lo[3], const int 
         I.reachable = fe.field_reachable ? 1 : 0; I.status = fe.field_status;
         I.device_ms = ms;
     }
+    if (fe.field_gated) {                                  // the followed call's report: this stage added to it
+        isdf_known_erode_info E;
+        known_erode_report(c, fe.field_gate_radius, fe.field_gate_border, &E);              // (the stage's hand-over brought the record back)
+        isdf_field_follow_info &I = fe.field_follow;
+        if (fe.follow_fresh || !fe.field_followed) I = isdf_field_follow_info{};
+        fe.follow_fresh = false; fe.field_followed = true;
+        if (closing) { I.closing++; I.closed_voxels += (int64_t)rec.changed; }
+        else { I.opening++; I.opened_voxels += (int64_t)rec.changed; }
+        I.radius_used = E.radius_used; I.border = E.border;
+        I.known_voxels = E.known_voxels; I.eroded_voxels = E.eroded_voxels;
+        I.free_voxels = n_free; I.reached_voxels = fe.field_reached_voxels;
+        I.reachable = fe.field_reachable ? 1 : 0; I.status = fe.field_status;
+        I.erode_ms += E.erode_ms; I.device_ms += ms;
+    }
     *kept = 1;
     return ISDF_OK;
+}
+
+// One stage on its own, for a change of K without a table refresh (isdf_map_known_fill): the field is invalid from here until the
+// stage has gone through; a failure or a bit against the direction leaves it dropped.
+int isdf_field_follow_stage(isdf_ctx *c, FfChange dir, const int lo[3], const int hi[3], hipEvent_t ev_start, hipEvent_t ev_end, int *kept) {
+    isdf_ctx::FrontEnd &fe = c->fe;
+    *kept = 0;
+    fe.field_valid = false; fe.field_reachable = false;
+    int rc = isdf_field_change_begin(c, dir, lo, hi, ev_start);
+    if (rc == ISDF_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = isdf_fail(c, ISDF_ERR_HIP, "the gated field's follow: the mark failed");
+    if (rc == ISDF_OK) rc = isdf_field_change_end(c, dir, lo, hi, ev_start, ev_end, kept);
+    if (rc != ISDF_OK || !*kept) {
+        const std::string err = c->err;
+        (void)hipStreamSynchronize(c->stream);
+        fe.field_valid = false;
+        (void)isdf_field_gate_drop(c);
+        c->err = err;
+        *kept = 0;
+    }
+    return rc;
 }
 
 // ---- the field carried through a shift of the map window (called by map_shift.hip; the rule and its proof: DESIGN 4.6.4)
@@ -1039,6 +1157,19 @@ extern "C" int isdf_frontend_field_shift_info(isdf_ctx *c, isdf_field_shift_info
 
 extern "C" void isdf_frontend_field_shift_sizes(int sizes_out[1]) {
     if (sizes_out) sizes_out[0] = (int)sizeof(isdf_field_shift_info);
+}
+
+extern "C" int isdf_frontend_field_set_known_follow(isdf_ctx *c, int mode) {
+    return ff_set_mode(c, mode, &isdf_ctx::field_known_follow_mode, "the gated field's follow mode is 0 (drop) or 1 (follow in place)");
+}
+
+extern "C" int isdf_frontend_field_follow_info(isdf_ctx *c, isdf_field_follow_info *out) {
+    return c ? ff_last_info(c, out, c->fe.field_valid && c->fe.field_gated && c->fe.field_followed, c->fe.field_follow, "no followed change since the last isdf_frontend_field_build_known")
+             : ISDF_ERR_INVALID_ARG;
+}
+
+extern "C" void isdf_frontend_field_follow_sizes(int sizes_out[1]) {
+    if (sizes_out) sizes_out[0] = (int)sizeof(isdf_field_follow_info);
 }
 
 extern "C" int isdf_frontend_field_set_repair(isdf_ctx *c, int mode) {

@@ -59,7 +59,8 @@ struct MkRecord {
     unsigned long long n;                   // get: known voxels; frontier: frontier voxels
     unsigned long long newly;               // fill: bits that went from 0 to 1
     int lo[3], hi[3];                       // the index box of the counted voxels
-    unsigned pad[6];
+    unsigned long long gone;                // fill: bits that went from 1 to 0
+    unsigned pad[4];
 };
 static_assert(sizeof(MkRecord) == 64, "the known grid's record is one 64-byte line");
 int map_known_reset(isdf_ctx *c);           // map_known.hip: the map was replaced - with the mode on, all unknown at the new size
@@ -258,10 +259,14 @@ struct isdf_ctx {
         // the field gated by the eroded known grid (isdf_frontend_field_build_known): its free words carry free & E, so
         // whatever can change K or the map drops it (isdf_field_known_changed)
         bool field_gated = false; int field_gate_radius = 0, field_gate_border = 0;
+        // ... unless it follows the change (isdf_frontend_field_set_known_follow): the report of the last followed call, which
+        // its stages add to (follow_fresh: the next stage starts a new report), and the last stage's erosion info
+        bool field_followed = false, follow_fresh = true; isdf_field_follow_info field_follow{};
     } fe;
     int field_repair_mode = 0;                  // isdf_frontend_field_set_repair: outlives isdf_frontend_build (fe is reset by it)
     int field_reopen_mode = 0;                  // isdf_frontend_field_set_reopen: likewise
     int field_shift_mode = 0;                   // isdf_frontend_field_set_shift: likewise
+    int field_known_follow_mode = 0;            // isdf_frontend_field_set_known_follow: likewise
     bool gate_dropped = false;                  // map_change_ready dropped a gated field: the in-place change under way reports field_dropped = 1
     int traj_watch_mode = 0;                    // isdf_traj_check_set_watch: outlives the check (the watch itself: TrajCheckState::w)
     struct isdf_xchg *xchg = nullptr;           // peer-to-peer exchange of the multi-GPU path (csrc/xchg.hip)

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void mu_pack_box_kernel(const uint4 *__restric
 
 using namespace isdf;
 
-int isdf::map_change_ready(isdf_ctx *c, const char *op, const void *in, long long n, bool needs_counts) {
+int isdf::map_change_ready(isdf_ctx *c, const char *op, const void *in, long long n, bool needs_counts, bool may_follow) {
     const std::string o = op;
     if (n < 0 || (n > 0 && !in)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, (o + ": bad arguments").c_str());
     if (!c->peers.empty() || c->is_peer) return isdf_fail(c, ISDF_ERR_UNSUPPORTED, (o + " is not offered on a multi-device ctx").c_str());
@@ -64,8 +64,10 @@ int isdf::map_change_ready(isdf_ctx *c, const char *op, const void *in, long lon
     if (needs_counts && !c->d_counts)
         return isdf_fail(c, ISDF_ERR_STATE, (o + ": no kept point counts (the map did not come from isdf_set_pointcloud, or isdf_update_voxels / isdf_clear_voxels changed it since)").c_str());
     // a field gated by the eroded known grid describes the K and the map of its build: it goes here, also where the call then finds
-    // nothing to change, and whatever the repair, reopen and shift modes say
-    c->gate_dropped = isdf_field_known_changed(c) != 0;
+    // nothing to change, and whatever the repair, reopen and shift modes say - unless it follows the change (DESIGN 4.27:
+    // may_follow and isdf_frontend_field_set_known_follow(1)); the driver then runs the stages or drops it
+    c->gate_dropped = (may_follow ? isdf_field_known_changed(c) : isdf_field_gate_drop(c)) != 0;
+    isdf_field_follow_call(c);
     return ISDF_OK;
 }
 
@@ -227,8 +229,10 @@ void isdf::map_frontend_finish(isdf_ctx *c, MapUpdateState &S, MapFrontend &F) {
     F.ms = S.ev.ms(4, 5);
 }
 
-int isdf::map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool follow, bool on, bool full, const MapRefresh &M, MapFrontend &F, int *field_dropped) {
-    const int *const lo = full ? nullptr : M.grown.lo, *const hi = full ? nullptr : M.grown.hi;
+int isdf::map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool follow, bool on, bool full, const MapRefresh &M, MapFrontend &F, int *field_dropped,
+                             const MuBox *field_more) {
+    const MuBox fbox = field_more ? mu_box_union(M.grown, *field_more) : M.grown;     // the field's box: where the table or (field_more) the gate can have moved
+    const int *const lo = full ? nullptr : fbox.lo, *const hi = full ? nullptr : fbox.hi;
     int rc;
     if ((rc = map_frontend_launch(c, S, on, full, &M.box, &M.grown, 1, F))) return rc;
     HIPCHK(c, S.rec.fetch(c->stream));
@@ -238,6 +242,7 @@ int isdf::map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool 
         int kept = 0;
         if ((rc = isdf_field_change_end(c, dir, lo, hi, S.ev[6], S.ev[7], &kept))) return rc;
         if (kept) *field_dropped = 0;
+        else (void)isdf_field_gate_drop(c);               // (a gated field that met a bit against the direction: its gate goes with it)
     }
     map_frontend_finish(c, S, F);
     return ISDF_OK;

@@ -80,7 +80,8 @@ namespace isdf {
 
 // ---- the shared steps (map_change.hip), in the order a driver meets them
 // ready: the three tests every entry point makes before anything moves; op names the operation in the message ("the map update")
-int map_change_ready(isdf_ctx *c, const char *op, const void *in, long long n, bool needs_counts);
+// may_follow = false (the shift): a gated cost-to-go field is dropped whatever isdf_frontend_field_set_known_follow says
+int map_change_ready(isdf_ctx *c, const char *op, const void *in, long long n, bool needs_counts, bool may_follow = true);
 int map_voxels_in_grid(isdf_ctx *c, const int32_t *ijk, long long n);       // ISDF_ERR_INVALID_ARG for an index outside the grid
 // begin: the ctx's device current, its scratch created with every event on first use
 int map_begin(isdf_ctx *c, MapUpdateState **out);
@@ -120,8 +121,10 @@ void map_frontend_finish(isdf_ctx *c, MapUpdateState &S, MapFrontend &F);
 // synchronisation: _launch over (M.box, M.grown) or the full map, the records on their way to S.rec.host(), when `follow` (the caller asked
 // isdf_field_change_wanted before map_refresh_begin dropped the field) the field's begin over M.grown; the synchronisation; the
 // field's end - its rounds read one word each -, and only then _finish: the host table is patched after them.  A field that followed:
-// *field_dropped = 0.  F: for map_frontend_report.
-int map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool follow, bool on, bool full, const MapRefresh &M, MapFrontend &F, int *field_dropped);
+// *field_dropped = 0.  F: for map_frontend_report.  field_more (nullable): a second box the field's stage covers with M.grown - where a
+// scan's new known voxels can have moved a gated field's gate.
+int map_frontend_stage(isdf_ctx *c, MapUpdateState &S, FfChange dir, bool follow, bool on, bool full, const MapRefresh &M, MapFrontend &F, int *field_dropped,
+                       const MuBox *field_more = nullptr);
 template <class Info> inline void map_frontend_report(const MapFrontend &F, Info &info) {       // the update's and the clear's info name these alike
     info.frontend_refreshed = F.refreshed; info.cspace_refreshed = F.cspace_refreshed; info.host_table_patched = F.host_table_patched;
     info.cspace_voxels_recomputed = F.cspace_voxels; info.frontend_ms = F.ms;
@@ -134,7 +137,8 @@ int map_watch_recheck(isdf_ctx *c, bool armed, int32_t *rechecked);
 // the count stage's record as the host read it, S.d_list the new (cleared) voxels, cap the list's capacity; the counts and the occupancy
 // are the new map's already.  map_scan.hip runs both, the clear's first.  A failure: the caller calls mu_drop_derived.
 int mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_update_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_update_info &info);
-int mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info);
+int mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info,
+                        const MuBox *field_more = nullptr);      // field_more: map_frontend_stage's
 
 // ---- the scan's stages for callers that bring their rays another way (map_scan.hip; depth_cam.hip's isdf_integrate_depth)
 struct MsOrigin { int q[3]; };              // the sensor's tick

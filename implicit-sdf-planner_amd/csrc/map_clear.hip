@@ -182,7 +182,8 @@ void empty_boxes(isdf_map_clear_info &info) {
 }  // namespace
 
 // everything after the hand-over of a call that freed at least one voxel
-int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info) {
+int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_clear_params &P, const MapListRecord &R, unsigned cap, bool voxels, isdf_map_clear_info &info,
+                              const MuBox *field_more) {
     const hipStream_t st = c->stream;
     const DevGrid &G = c->grid;
     const int dims[3] = {G.X, G.Y, G.Z};
@@ -193,6 +194,7 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
     // through: every error path leaves it dropped.
     const bool reopen = P.refresh_frontend != 0 && isdf_field_change_wanted(c, FfChange::Opening);
     const MapRefresh M = map_refresh_begin(c, R, cap, voxels, P.refresh_esdf, P.refresh_frontend, P.full_fraction, &info.field_dropped);
+    if (!reopen) (void)isdf_field_gate_drop(c);          // (a gated field that does not follow: its gate and its follow report go with it)
     for (int a = 0; a < 3; a++) { info.dirty_lo[a] = M.box.lo[a]; info.dirty_hi[a] = M.box.hi[a]; }
     bool full = M.over;
 
@@ -234,7 +236,7 @@ int isdf::mc_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_cle
 
     // ---- front end, the field's reopen around the synchronisation
     MapFrontend F;
-    if ((rc = map_frontend_stage(c, S, FfChange::Opening, reopen, P.refresh_frontend != 0, full, M, F, &info.field_dropped))) return rc;
+    if ((rc = map_frontend_stage(c, S, FfChange::Opening, reopen, P.refresh_frontend != 0, full, M, F, &info.field_dropped, field_more))) return rc;
     map_frontend_report(F, info);
     if (M.do_esdf && !full) info.esdf_voxels_raised = (long long)h_er->raised;
     info.esdf_ms = S.ev.ms(2, 3);

@@ -75,15 +75,16 @@ __global__ __launch_bounds__(256) void mk_shift_kernel(MkGeom g, const unsigned 
 }
 
 __global__ __launch_bounds__(256) void mk_fill_kernel(MkGeom g, unsigned *__restrict__ known, MuBox box, long long w0, long long w1, int value, MkRecord *rec) {
-    unsigned long long newly = 0;
+    unsigned long long newly = 0, gone = 0;
     for (long long w = w0 + (long long)blockIdx.x * blockDim.x + threadIdx.x; w <= w1; w += (long long)gridDim.x * blockDim.x) {
         const unsigned m = mk_box_mask(w, g.Y, g.Z, g.n_vox, box.lo, box.hi);
         if (!m) continue;
         const unsigned old = known[w], now = value ? old | m : old & ~m;
         if (now != old) known[w] = now;
         newly += __popc(now & ~old);
+        gone += __popc(old & ~now);
     }
-    mk_block_reduce(0ull, newly, nullptr, nullptr, nullptr, &rec->newly, nullptr, nullptr);
+    mk_block_reduce(gone, newly, nullptr, nullptr, &rec->gone, &rec->newly, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(256) void mk_stats_kernel(MkGeom g, const unsigned *__restrict__ known, MkRecord *rec) {
@@ -246,7 +247,7 @@ extern "C" int isdf_map_known_enable(isdf_ctx *c, int on) {
     ISDF_TRY(map_query::single_device(c, "the known grid is not offered on a multi-device ctx"));
     isdf_ctx::Known &K = c->known;
     HIPCHK(c, hipSetDevice(c->device));
-    (void)isdf_field_known_changed(c);          // a field gated by K's erosion goes with either answer
+    (void)isdf_field_gate_drop(c);              // a field gated by K's erosion goes with either answer, whatever its follow mode
     if (!on) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         K.on = K.have = false; K.n_words = 0; K.newly = K.merges = 0;
@@ -276,15 +277,27 @@ extern "C" int isdf_map_known_fill(isdf_ctx *c, const int32_t *box, int value) {
     if (!box) box = whole;
     if (mk_box_bad(dims, box)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "filling the known grid: the box lies outside the grid or has lo > hi");
     ISDF_TRY(known_begin(c, "filling the known grid"));
-    (void)isdf_field_known_changed(c);          // K changes: a field gated by its erosion is dropped
+    // K changes: a field gated by its erosion is dropped, or - isdf_frontend_field_set_known_follow(1), DESIGN 4.27 - kept
+    // for the stage below: a set box can only grow E (opening), a cleared one only shrink it (closing), inside the box grown by the radius
+    const bool follow = isdf_field_follow_wanted(c);
+    (void)isdf_field_known_changed(c);
+    isdf_field_follow_call(c);
     isdf_ctx::Known &K = c->known;
     MuBox B;
     for (int a = 0; a < 3; a++) { B.lo[a] = box[a]; B.hi[a] = box[3 + a]; }
     const long long w0 = (((long long)B.lo[0] * g.Y + B.lo[1]) * g.Z + B.lo[2]) >> 5, w1 = (((long long)B.hi[0] * g.Y + B.hi[1]) * g.Z + B.hi[2]) >> 5;
     hipLaunchKernelGGL(mk_fill_kernel, dim3(word_blocks(w1 - w0 + 1)), dim3(256), 0, c->stream, g, K.d_bits.get(), B, w0, w1, value ? 1 : 0, K.rec.dev());
-    HIPCHK(c, hipGetLastError());
-    ISDF_TRY(known_fetch(c));
+    int rc = hipGetLastError() == hipSuccess ? known_fetch(c) : isdf_fail(c, ISDF_ERR_HIP, "filling the known grid: the launch failed");
+    if (rc != ISDF_OK) {                        // the kernel may have run: K may have moved
+        if (follow) { const std::string err = c->err; (void)isdf_field_gate_drop(c); c->err = err; }
+        return rc;
+    }
     K.newly = (long long)K.rec.host().newly;
+    if (follow && (value ? K.rec.host().newly : K.rec.host().gone) > 0) {
+        const MuBox grown = mu_box_grow(B, c->fe.field_gate_radius, dims);
+        int kept = 0;
+        ISDF_TRY(isdf_field_follow_stage(c, value ? FfChange::Opening : FfChange::Closing, grown.lo, grown.hi, K.ev[0], K.ev[1], &kept));
+    }
     return ISDF_OK;
 }
 

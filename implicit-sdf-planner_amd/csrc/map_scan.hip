@@ -177,6 +177,9 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     empty_info(info);
     info.n_rays = n_rays;
     info.clear.field_dropped = info.update.field_dropped = c->gate_dropped ? 1 : 0;       // (a gated field went in map_change_ready, whatever the rays change)
+    // ... unless it follows the change: one opening stage once K has grown and the clear's table refresh is done, over the
+    // clear's grown box and the rays' box grown by the gate's radius - where E can have grown -, then the update's closing stage
+    const bool follow = isdf_field_follow_wanted(c);
     MapUpdateState *Sp;
     int rc = map_begin(c, &Sp);
     if (rc) return rc;
@@ -213,12 +216,21 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     }
     HIPCHK(c, hipEventRecord(S.ev_scan[1], st));
     const bool known = c->known.have && n_rays > 0;         // the visited voxels join the known grid (map_known.hip); off: nothing differs
-    if (known && (rc = map_known_merge_launch(c, S.d_free_bits.get(), S.d_hit_bits.get(), &d_rec->scan))) return rc;
-    HIPCHK(c, hipEventRecord(S.ev[0], st));
-    if (n_rays > 0) {
-        hipLaunchKernelGGL(ms_apply_kernel, dim3(1024), dim3(256), 0, st, G, (const unsigned *)S.d_free_bits.get(), (const unsigned *)S.d_hit_bits.get(), c->d_counts.get(), thr,
-                           miss, c->d_occ.get(), S.d_list.get(), cap_clear, &d_rec->scan, &d_rec->list);
-        HIPCHK(c, hipGetLastError());
+    // from the merge's launch on K may have moved: a failure before the hand-over (which drops every product itself) takes a field
+    // that follows along - it is never left valid over a K it does not describe
+    rc = [&]() -> int {
+        if (known) ISDF_TRY(map_known_merge_launch(c, S.d_free_bits.get(), S.d_hit_bits.get(), &d_rec->scan));
+        HIPCHK(c, hipEventRecord(S.ev[0], st));
+        if (n_rays > 0) {
+            hipLaunchKernelGGL(ms_apply_kernel, dim3(1024), dim3(256), 0, st, G, (const unsigned *)S.d_free_bits.get(), (const unsigned *)S.d_hit_bits.get(), c->d_counts.get(),
+                               thr, miss, c->d_occ.get(), S.d_list.get(), cap_clear, &d_rec->scan, &d_rec->list);
+            HIPCHK(c, hipGetLastError());
+        }
+        return ISDF_OK;
+    }();
+    if (rc != ISDF_OK) {
+        if (follow) (void)isdf_field_gate_drop(c);
+        return rc;
     }
     if ((rc = map_hand_over(c, S, S.ev[1], "scan", false))) return rc;
     const MapListRecord R = h_rec->list;
@@ -235,10 +247,29 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     info.clear.count_ms = S.ev.ms(0, 1);
     info.clear.n_cleared_voxels = R.n;
     info.clear.n_points_ignored = (long long)R.tally;
+    const bool k_grew = follow && known && RS.newly_known > 0;
+    MuBox kbox{{0, 0, 0}, {-1, -1, -1}};
+    if (k_grew) {
+        const int dims[3] = {G.X, G.Y, G.Z};
+        MuBox rays;
+        for (int a = 0; a < 3; a++) { rays.lo[a] = RS.lo[a]; rays.hi[a] = RS.hi[a]; }
+        kbox = mu_box_grow(rays, c->fe.field_gate_radius, dims);
+    }
+    bool k_open = false;                // the opening stage on its own: K grew, no voxel was cleared
     if (R.n > 0) {
         // from here on the occupancy has moved: a failure must not leave products behind that describe the old map
-        rc = mc_refresh_products(c, S, P.clear, R, map_list_cap(P.clear.max_cleared_voxels, n_clear_points, n_vox), false, info.clear);
+        rc = mc_refresh_products(c, S, P.clear, R, map_list_cap(P.clear.max_cleared_voxels, n_clear_points, n_vox), false, info.clear, k_grew ? &kbox : nullptr);
         if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
+    } else if (k_grew) {
+        // K has moved: the field is invalid until the stage has gone through.  Its mark is queued here and the hits' hand-over below is its
+        // synchronisation: no hand-over is added.  The mark reads the table, which the hits stage does not touch.
+        c->fe.field_valid = false; c->fe.field_reachable = false;
+        if (P.clear.refresh_frontend == 0) (void)isdf_field_gate_drop(c);
+        else {
+            k_open = true;
+            rc = isdf_field_change_begin(c, FfChange::Opening, kbox.lo, kbox.hi, S.ev[6]);
+            if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
+        }
     }
 
     // ---- the hits, on the map the clear left: the list record empty again, second hand-over
@@ -261,6 +292,16 @@ int isdf::scan_integrate(isdf_ctx *c, const MsOrigin &O, const MsInput &in, long
     }
     if ((rc = map_hand_over(c, S, S.ev[1], "scan", false))) return rc;
     const MapListRecord RU = h_rec->list;
+    if (k_open) {
+        int kept = 0;
+        rc = isdf_field_change_end(c, FfChange::Opening, kbox.lo, kbox.hi, S.ev[6], S.ev[7], &kept);
+        if (rc != ISDF_OK) { mu_drop_derived(c, false); return rc; }
+        if (!kept) (void)isdf_field_gate_drop(c);
+    }
+    if (follow && !c->fe.field_valid) {                     // the opening stage lost the field: every stage after it says so
+        c->gate_dropped = true;
+        info.clear.field_dropped = info.update.field_dropped = 1;
+    }
     info.update.count_ms = S.ev.ms(0, 1);
     info.update.n_new_voxels = RU.n;
     if (RU.n > 0) {

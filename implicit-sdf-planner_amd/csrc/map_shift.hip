@@ -253,7 +253,7 @@ int shift_map(isdf_ctx *c, const int32_t s[3], const isdf_map_shift_params &P, i
 extern "C" int isdf_shift_map(isdf_ctx *c, const int32_t shift_ijk[3], const isdf_map_shift_params *params, isdf_map_shift_info *info_out) {
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (!shift_ijk) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "null shift");
-    int rc = map_change_ready(c, "shifting the map", nullptr, 0, true);
+    int rc = map_change_ready(c, "shifting the map", nullptr, 0, true, false);
     if (rc) return rc;
     isdf_map_shift_params P;
     if ((rc = shift_params(c, params, P))) return rc;
@@ -265,7 +265,7 @@ extern "C" int isdf_map_follow(isdf_ctx *c, const double centre_xyz[3], int min_
     if (!c) return ISDF_ERR_INVALID_ARG;
     if (shift_out) shift_out[0] = shift_out[1] = shift_out[2] = 0;
     if (!centre_xyz || min_shift < 0) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "map follow: null centre or negative min_shift");
-    int rc = map_change_ready(c, "shifting the map", nullptr, 0, true);
+    int rc = map_change_ready(c, "shifting the map", nullptr, 0, true, false);
     if (rc) return rc;
     isdf_map_shift_params P;
     if ((rc = shift_params(c, params, P))) return rc;

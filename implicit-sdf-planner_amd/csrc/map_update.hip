@@ -123,6 +123,7 @@ int isdf::mu_refresh_products(isdf_ctx *c, MapUpdateState &S, const isdf_map_upd
     // map's (mode 1).  It is invalid from here until the repair has gone through: every error path leaves it dropped.
     const bool repair = P.refresh_frontend != 0 && isdf_field_change_wanted(c, FfChange::Closing);
     const MapRefresh M = map_refresh_begin(c, R, cap, voxels, P.refresh_esdf, P.refresh_frontend, P.full_fraction, &info.field_dropped);
+    if (!repair) (void)isdf_field_gate_drop(c);          // (a gated field that does not follow: its gate and its follow report go with it)
     for (int a = 0; a < 3; a++) { info.dirty_lo[a] = M.box.lo[a]; info.dirty_hi[a] = M.box.hi[a]; }
     float esdf0;
     std::memcpy(&esdf0, &R.esdf0, sizeof(float));

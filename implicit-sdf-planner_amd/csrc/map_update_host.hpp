@@ -35,6 +35,15 @@ inline MuBox mu_box_grow(const MuBox &b, int side, const int dims[3]) {
     return g;
 }
 
+// the smallest box that holds both (an empty one adds nothing)
+inline MuBox mu_box_union(const MuBox &a, const MuBox &b) {
+    if (mu_box_empty(a)) return b;
+    if (mu_box_empty(b)) return a;
+    MuBox u;
+    for (int k = 0; k < 3; k++) { u.lo[k] = a.lo[k] < b.lo[k] ? a.lo[k] : b.lo[k]; u.hi[k] = a.hi[k] > b.hi[k] ? a.hi[k] : b.hi[k]; }
+    return u;
+}
+
 // squared distance, in voxels, from voxel (x, y, z) to the nearest voxel of the box (0 inside)
 MU_HD long long mu_box_dist2(int x, int y, int z, const int lo[3], const int hi[3]) {
     const int p[3] = {x, y, z};

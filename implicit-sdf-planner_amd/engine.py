@@ -1680,6 +1680,17 @@ class Engine:
         self._check(self.lib.isdf_frontend_field_known_info(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def frontend_field_set_known_follow(self, mode):
+        """isdf_frontend_field_set_known_follow: what updates, clears, scans, depth images and known-grid fills do with a valid GATED field -
+        0 (default) drop it, 1 follow the change in place (the mark against ballot(table) & E of the K of that moment)."""
+        self._check(self.lib.isdf_frontend_field_set_known_follow(self.h, int(mode)))
+
+    def frontend_field_follow_info(self):
+        """isdf_frontend_field_follow_info: the last followed call's IsdfFieldFollowInfo (ISDF_ERR_STATE: none since the last build)."""
+        info = capi.IsdfFieldFollowInfo()
+        self._check(self.lib.isdf_frontend_field_follow_info(self.h, C.byref(info)))
+        return info
+
     def frontend_field(self, xyz=None):
         """The whole field, float64 [X, Y, Z] (cells; +inf where a voxel is not free or cannot reach the goal), or, with `xyz`
         (n, 3) world points, the values at their cells (+inf outside the map)."""

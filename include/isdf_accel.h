@@ -2156,9 +2156,10 @@ int isdf_view_select_host(const uint32_t *bits, const uint8_t *occ, const double
  *   isdf_clear_pointcloud / _voxels, isdf_integrate_scan / _depth (also when no occupancy changed), isdf_shift_map, isdf_map_follow (also
  *   when it does not move), once the call's own state checks have passed; isdf_map_known_fill, isdf_map_known_enable and
  *   isdf_frontend_build.  The repair, reopen and shift modes do not apply to it: nothing of them runs and their _info calls report none.
- *   An ungated field behaves in all of these exactly as before.
+ *   An ungated field behaves in all of these exactly as before.  This is mode 0 of isdf_frontend_field_set_known_follow, the default;
+ *   with mode 1 a gated field follows updates, clears, scans and fills in place (below).
  * Not offered: the A* (isdf_frontend_astar_search) over the gated table; a gate for isdf_traj_check (isdf_traj_known_horizon reports the
- * first unknown voxel a trajectory comes near); a gated field repaired, reopened or carried through map changes. */
+ * first unknown voxel a trajectory comes near); a gated field carried through a shift of the map window. */
 typedef struct isdf_known_erode_params {
     int32_t radius;               /* default -1: the front end's (kernel_size - 1) / 2; else 0 .. 64 */
     int32_t border;               /* default 0: the outside counts as unseen; 1: as seen */
@@ -2177,6 +2178,45 @@ int isdf_known_erode_host(const uint32_t *bits, const int32_t dims[3], int radiu
 int isdf_frontend_field_build_known(isdf_ctx *ctx, const double goal_xyz[3], const isdf_known_erode_params *erode, const isdf_frontend_field_params *params,
                                     isdf_frontend_field_info *info_out, isdf_known_erode_info *gate_out);
 int isdf_frontend_field_known_info(isdf_ctx *ctx, int32_t out[4]);
+
+/* ---- the gated field kept across scans, updates, clears and fills ------------------------------------------------- */
+/* The gated field's free set is free'[v] = (any attitude bit of table[v]) && E[v].  Every in-place change moves it in ONE direction
+ * per stage: an update closes table bits with K fixed (closing); a clear opens them with K fixed (opening); isdf_map_known_fill(box, 1)
+ * grows K, so E grows (opening), and (box, 0) shrinks both (closing), with E changed only inside the box grown by the gate's radius; a
+ * scan ORs bits into K and opens table bits (one opening stage), then closes table bits with E fixed (one closing stage).  Each stage
+ * is the mark / seed / relax of isdf_frontend_field_set_repair / _set_reopen with the mark taken against ballot(table) & E_new, E_new
+ * eroded from the K of that moment at the radius and border of the build; the result has the bytes of isdf_frontend_field_build_known
+ * on the new map and K, by the proofs of those two rules.
+ * isdf_frontend_field_set_known_follow: mode 0 (default) - a gated field is dropped as described under DROPPED, NOT CARRIED above, to
+ * every byte and status code; mode 1 - a gated field that is valid, has status 0 or 1 and whose table is on the device FOLLOWS
+ *   isdf_update_pointcloud / _voxels   the closing stage over the dirty box grown by the footprint;
+ *   isdf_clear_pointcloud / _voxels    the opening stage over it;
+ *   isdf_integrate_scan / _depth       one opening stage after the clear's table refresh, over the union of the clear's grown box (if a
+ *                                      voxel was cleared) and the rays' box grown by the gate's radius - also when nothing was cleared
+ *                                      but a voxel became known -, then the update's closing stage.  No ray, or nothing newly known,
+ *                                      cleared or occupied: the field is untouched, field_dropped = 0 and no stage is reported;
+ *   isdf_map_known_fill                value 1: opening, value 0: closing, over the box grown by the gate's radius; no stage when no
+ *                                      bit of K changed,
+ * whatever the repair, reopen and shift modes say; an ungated field is governed by those three exactly as before.  field_dropped of
+ * each call's info is 0 where the field followed.  STILL DROPPED in mode 1: by isdf_shift_map and isdf_map_follow, isdf_map_known_enable
+ * and isdf_frontend_build; by a change with refresh_frontend = 0; a field of status 2; a stage that finds a bit moved against its
+ * direction; and whenever a step fails after the map has moved.  The mode outlives isdf_frontend_build.  Other modes:
+ * ISDF_ERR_INVALID_ARG; a multi-device ctx: ISDF_ERR_UNSUPPORTED.
+ * isdf_frontend_field_follow_info: the last followed call's report - its stages added up, the state after the last of them;
+ * ISDF_ERR_STATE when no call was followed since the last build, or the field has been dropped since.  isdf_frontend_field_repair_info / _reopen_info report the closing /
+ * the opening stage that ran, as for an ungated field; isdf_frontend_field_known_info keeps answering (1, radius, border). */
+typedef struct isdf_field_follow_info {
+    int32_t opening, closing;                 /* stages of that direction that ran in the call                                       */
+    int32_t radius_used, border;              /* the gate's, as at the build                                                          */
+    int64_t known_voxels, eroded_voxels;      /* |K| and |E| after the change                                                         */
+    int64_t opened_voxels, closed_voxels;     /* bits of free' that rose / fell                                                       */
+    int64_t free_voxels, reached_voxels;      /* |free'| and the voxels with a finite d after the change                              */
+    int32_t reachable, status;                /* as isdf_frontend_field_info                                                          */
+    double erode_ms, device_ms;               /* device time of the erosions / of the stages (mark to counts), summed                 */
+} isdf_field_follow_info;
+int isdf_frontend_field_set_known_follow(isdf_ctx *ctx, int mode);
+int isdf_frontend_field_follow_info(isdf_ctx *ctx, isdf_field_follow_info *out);
+void isdf_frontend_field_follow_sizes(int sizes_out[1]);      /* sizeof of the struct above, for mirrors of this header              */
 
 /* ---- the reference's own input files (host side; no device needed) ---------------------------------------------------- */
 /* ASCII .pcd global map as pcl::io::loadPCDFile<pcl::PointXYZ> reads it (src/map_manager/src/globalmap_gene.cpp:433-460;
