@@ -252,6 +252,17 @@ class IsdfViewSelectInfo(C.Structure):
                 ("lists_ms", C.c_double), ("select_ms", C.c_double)]
 
 
+class IsdfViewSelectRoutedParams(C.Structure):
+    """isdf_view_select_routed_params (include/isdf_accel.h)."""
+    _fields_ = [("select", IsdfViewSelectParams), ("cost0", C.c_double), ("max_cost", C.c_double), ("path_cap", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class IsdfViewSelectRoutedInfo(C.Structure):
+    """isdf_view_select_routed_info (include/isdf_accel.h)."""
+    _fields_ = [("select", IsdfViewSelectInfo), ("n_eligible", C.c_int64), ("n_unreachable", C.c_int64), ("n_over_budget", C.c_int64),
+                ("cost_selected", C.c_double), ("cost_source", C.c_int32), ("reserved", C.c_int32), ("cost_ms", C.c_double), ("paths_ms", C.c_double)]
+
+
 class IsdfKnownErodeParams(C.Structure):
     """isdf_known_erode_params (include/isdf_accel.h)."""
     _fields_ = [("radius", C.c_int32), ("border", C.c_int32)]
@@ -505,6 +516,7 @@ EXPORTED_SYMBOLS = [
     "isdf_frontier_cluster_params_default", "isdf_frontier_cluster_sizes", "isdf_map_frontier_clusters", "isdf_known_clusters_host",
     "isdf_view_candidates_params_default", "isdf_view_candidates_sizes", "isdf_view_candidates", "isdf_view_candidates_host",
     "isdf_view_select_params_default", "isdf_view_select_sizes", "isdf_view_select", "isdf_view_select_host",
+    "isdf_view_select_routed_params_default", "isdf_view_select_routed_sizes", "isdf_view_select_routed", "isdf_view_select_routed_host",
     "isdf_known_erode_params_default", "isdf_known_erode_sizes", "isdf_map_known_erode", "isdf_known_erode_host", "isdf_frontend_field_build_known",
     "isdf_frontend_field_known_info",
     "isdf_frontend_field_set_known_follow", "isdf_frontend_field_follow_info", "isdf_frontend_field_follow_sizes",
@@ -902,6 +914,19 @@ def load_library(path=None):
     if list(sz) != [C.sizeof(IsdfViewSelectParams), C.sizeof(IsdfViewSelectInfo)]:
         raise RuntimeError(f"isdf_view_select structs: the library has {list(sz)}, the mirror "
                            f"{[C.sizeof(IsdfViewSelectParams), C.sizeof(IsdfViewSelectInfo)]}")
+    rp, ri = C.POINTER(IsdfViewSelectRoutedParams), C.POINTER(IsdfViewSelectRoutedInfo)
+    lib.isdf_view_select_routed_params_default.argtypes = [rp]
+    lib.isdf_view_select_routed_params_default.restype = None
+    lib.isdf_view_select_routed_sizes.argtypes = [ip]
+    lib.isdf_view_select_routed_sizes.restype = None
+    lib.isdf_view_select_routed.argtypes = [C.c_void_p, C.POINTER(IsdfDepthCamera), C.c_void_p, C.c_longlong, C.c_void_p, rp, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ri]
+    lib.isdf_view_select_routed_host.argtypes = [C.c_void_p, C.c_void_p, dp, dp, C.c_double, i3, C.POINTER(IsdfDepthCamera), C.c_void_p, C.c_longlong, C.c_void_p, rp,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ri]
+    lib.isdf_view_select_routed_sizes(sz)
+    if list(sz) != [C.sizeof(IsdfViewSelectRoutedParams), C.sizeof(IsdfViewSelectRoutedInfo)]:
+        raise RuntimeError(f"isdf_view_select_routed structs: the library has {list(sz)}, the mirror "
+                           f"{[C.sizeof(IsdfViewSelectRoutedParams), C.sizeof(IsdfViewSelectRoutedInfo)]}")
     ep, ei = C.POINTER(IsdfKnownErodeParams), C.POINTER(IsdfKnownErodeInfo)
     lib.isdf_known_erode_params_default.argtypes = [ep]
     lib.isdf_known_erode_params_default.restype = None

@@ -103,6 +103,9 @@ int isdf_field_change_end(isdf_ctx *c, isdf::FfChange dir, const int lo[3], cons
 // isdf_field_follow_stage: one stage on its own - begin, the synchronisation, end -, for a change of K without a table refresh; a
 // failure or a bit against the direction drops the field (*kept = 0).  isdf_field_follow_call: a new public call begins - the next
 // followed stage starts a new isdf_field_follow_info.
+// isdf_field_read_ready: what the field's getters answer before they read - ISDF_OK with a valid field (gated or not), else the
+// status and the sentence of isdf_frontend_field_value; for a query elsewhere that reads c->fe.d_field (view_select.hip).
+int isdf_field_read_ready(isdf_ctx *c);
 int isdf_field_known_changed(isdf_ctx *c);
 int isdf_field_gate_drop(isdf_ctx *c);
 bool isdf_field_follow_wanted(const isdf_ctx *c);

@@ -54,6 +54,7 @@
 // Compiled with -ffp-contract=off like frontend.hip (cell indices and cube centres round like the A*'s).
 #include "isdf_ctx.hpp"
 #include "frontend_dev.hpp"
+#include "field_cell.hpp"
 #include "frontend_field_host.hpp"
 #include "map_known_host.hpp"
 #include "map_query.hpp"
@@ -489,22 +490,6 @@ __global__ __launch_bounds__(256) void ff_left_kernel(FfDims D, FfShift S, const
     }
 }
 
-// GridMap3D::isInMap / getGridIndex as isdf_frontend_astar_search restates them (Gridmap3D.cpp:41-69,135-175)
-struct FfMap { int X, Y, Z; double res, bmin[3], bmax[3]; };
-__host__ __device__ inline bool ff_cell(const FfMap &M, const double p[3], int idx[3]) {
-    for (int a = 0; a < 3; a++) if (p[a] < M.bmin[a]) return false;
-    for (int a = 0; a < 3; a++) if (p[a] > M.bmax[a]) return false;
-    const int dims[3] = {M.X, M.Y, M.Z};
-    for (int a = 0; a < 3; a++) {
-        const double dd = p[a] - M.bmin[a];
-        int i = (int)floor(dd / M.res);
-        if (i < 0) i = 0;
-        if (i >= dims[a]) i = dims[a] - 1;
-        idx[a] = i;
-    }
-    return true;
-}
-
 __global__ __launch_bounds__(256) void ff_value_kernel(FfMap M, const double *__restrict__ d, const double *__restrict__ xyz, int n, double *__restrict__ out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
@@ -607,13 +592,6 @@ int ff_field_ready(isdf_ctx *c) {                          // ... and a field to
     return ISDF_OK;
 }
 
-FfMap ff_map(const isdf_ctx *c) {
-    FfMap M{};
-    M.X = c->grid.X; M.Y = c->grid.Y; M.Z = c->grid.Z; M.res = c->grid.res;
-    for (int a = 0; a < 3; a++) { M.bmin[a] = c->grid.bmin[a]; M.bmax[a] = c->grid.bmax[a]; }
-    return M;
-}
-
 FfWalk ff_walk(const isdf_ctx *c) {
     const isdf_ctx::FrontEnd &fe = c->fe;
     FfWalk W{};
@@ -670,6 +648,8 @@ int ff_paths_launch(isdf_ctx *c, const double *d_starts, int B, int cap, int *d_
 }
 
 }  // namespace
+
+int isdf_field_read_ready(isdf_ctx *c) { return ff_field_ready(c); }
 
 extern "C" void isdf_frontend_field_params_default(isdf_frontend_field_params *out) {
     if (!out) return;

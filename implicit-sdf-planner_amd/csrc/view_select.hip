@@ -19,13 +19,27 @@
 //   vs_claim_kernel     the winner's segment, read from the record: claimed[w] |= bits.  A word occurs once per view: no atomic.
 //   vs_final_kernel     claimed |= K, where claimed_out is asked for.
 //   -- the last hand-over: the record and the outputs asked for, through their pinned copies.
-// Nothing here writes to the ctx's map, its known grid, its products or its flags; no kernel waits on another workgroup.
+// The routed selection: isdf_view_select_routed, the same sets and lists, the rounds by utility = marginal gain per travel cost.
+//   vs_cost_kernel         one lane per view, after the gain: c_j = the ctx's cost-to-go field at the cell of the view's eye (field_cell.hpp's
+//                          ff_cell, the field's own rule), or the caller's staged array; the scored views that are eligible, unreachable and
+//                          over the budget, block_sum, one atomicAdd per counter and workgroup.
+//   vs_marginal_kernel<true>  as above, and a view whose cost is not finite or above the budget is skipped (uniform).
+//   vs_pick_util_kernel    one workgroup instead of vs_pick_kernel: every lane keeps the best of its views - the largest u = m / (cost0 + c),
+//                          among equals the lowest j -, then block_max over the bit pattern of u plus one (u >= 0: the pattern orders as the
+//                          value does, 0 stays "none") and block_max over VS_MAX_VIEWS - j among the lanes that hold the top.  No atomic.
+//   vs_claim_kernel        unchanged.
+//   vs_gather_eyes_kernel  with path_cap >= 1: the picked views' eyes as starts, a start outside the map for a round that did not happen;
+//   (frontend_field.hip)   then isdf_frontend_field_paths_device on the same stream - no hand-over between the rounds and the paths.
+// Nothing here writes to the ctx's map, its known grid, its field, its products or its flags; no kernel waits on another workgroup.
 #include "view_gain_run.hpp"
 #include "view_select_host.hpp"
+#include "frontend_dev.hpp"
+#include "field_cell.hpp"
 #include "dev_reduce.hpp"
 #include "dev_scan.hpp"
 #include <algorithm>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 namespace isdf {
@@ -46,8 +60,11 @@ struct VsCtl {
     long long done;                         // the stop rule has ended the selection
     long long winner;                       // the last round's view
     long long n_selected, cumulative, solo_sum;
-    long long pad;
+    double cost_selected;                   // the routed selection: the picked views' costs, added in pick order (zeroed as +0.0)
 };
+
+// the routed selection's counts over the scored views, zeroed before the cost kernel
+struct VsCostRec { unsigned long long n_eligible, n_unreachable, n_over_budget, pad; };
 static_assert(sizeof(VsCtl) == 64, "the selection's record is one 64-byte line");
 
 __global__ __launch_bounds__(VS_BLOCK) void vs_begin_kernel(long long n_views, long long rounds, unsigned long long *__restrict__ count, unsigned long long *__restrict__ m,
@@ -109,13 +126,16 @@ __global__ __launch_bounds__(VS_BLOCK) void vs_fill_kernel(const unsigned *__res
     }
 }
 
+// ROUTED: cost is the per-view travel cost and a view that is not eligible by it is skipped; else cost is null and never read
+template <bool ROUTED>
 __global__ __launch_bounds__(VS_BLOCK) void vs_marginal_kernel(long long n_views, const long long *__restrict__ rows, const long long *__restrict__ round,
                                                                const unsigned long long *__restrict__ start, const unsigned long long *__restrict__ count,
                                                                const VsEntry *__restrict__ list, const unsigned *__restrict__ claimed, unsigned long long *m,
-                                                               const VsCtl *__restrict__ ctl) {
+                                                               const VsCtl *__restrict__ ctl, const double *__restrict__ cost, double max_cost) {
     if (ctl->done) return;          // (uniform)
     for (long long j = blockIdx.y; j < n_views; j += gridDim.y) {
         if (rows[VG_ROW * j] != VG_SCORED || round[j] >= 0) continue;           // (uniform)
+        if (ROUTED && !vs_cost_eligible(cost[j], max_cost)) continue;           // (uniform)
         const unsigned long long n = count[j];
         if ((unsigned long long)blockIdx.x * VS_BLOCK >= n) continue;           // (uniform)
         const VsEntry *const seg = list + start[j];
@@ -152,6 +172,70 @@ __global__ __launch_bounds__(VS_BLOCK) void vs_pick_kernel(long long n_views, in
     ctl->winner = j; ctl->n_selected = r + 1; ctl->cumulative = cumulative; ctl->solo_sum += gain;
 }
 
+// One lane per view.  staged null: c_j from the field d (the map's X Y Z doubles) at the eye's cell, +inf outside the map - what
+// ff_value_kernel answers for the eye; else the caller's array.  rows are the gain's: the counts are over the scored views.
+__global__ __launch_bounds__(VS_BLOCK) void vs_cost_kernel(long long n_views, FfMap M, const double *__restrict__ d, const double *__restrict__ poses,
+                                                           const double *__restrict__ staged, const long long *__restrict__ rows, double max_cost,
+                                                           double *__restrict__ cost, VsCostRec *rec) {
+    const long long j = (long long)blockIdx.x * VS_BLOCK + threadIdx.x;
+    long long cnt[3] = {0, 0, 0};
+    if (j < n_views) {
+        double cj;
+        if (staged) cj = staged[j];
+        else {
+            const double p[3] = {poses[12 * j + 3], poses[12 * j + 7], poses[12 * j + 11]};
+            int cell[3];
+            cj = ff_cell(M, p, cell) ? d[((size_t)cell[0] * M.Y + cell[1]) * M.Z + cell[2]] : __longlong_as_double(0x7FF0000000000000ll);
+        }
+        cost[j] = cj;
+        if (rows[VG_ROW * j] == VG_SCORED) cnt[!vs_cost_finite(cj) ? 1 : !(cj <= max_cost) ? 2 : 0] = 1;
+    }
+    const unsigned long long s = block_sum<3, VS_WAVES>(cnt);
+    if (threadIdx.x < 3 && s) atomicAdd(&rec->n_eligible + threadIdx.x, s);         // (the record's first three words, in the order of cnt)
+}
+
+__global__ __launch_bounds__(VS_BLOCK) void vs_pick_util_kernel(long long n_views, int r, long long min_gain, double cost0, double max_cost,
+                                                                const long long *__restrict__ rows, const double *__restrict__ cost, long long *round,
+                                                                unsigned long long *m, long long *__restrict__ select, double *__restrict__ util, VsCtl *ctl) {
+    if (ctl->done) return;          // (uniform: thread 0 writes it after a barrier)
+    __shared__ unsigned long long s_marginal;
+    unsigned long long key = 0, best_m = 0;
+    long long best_j = 0;
+    for (long long j = threadIdx.x; j < n_views; j += VS_BLOCK) {
+        const unsigned long long mj = m[j];
+        m[j] = 0;                   // for the next round
+        if (rows[VG_ROW * j] != VG_SCORED || round[j] >= 0 || !vs_cost_eligible(cost[j], max_cost) || (long long)mj < min_gain) continue;
+        const unsigned long long k = (unsigned long long)__double_as_longlong(vs_utility((long long)mj, cost0, cost[j])) + 1ull;
+        if (k > key) { key = k; best_m = mj; best_j = j; }          // (j rises in a lane: among equals the lowest stays)
+    }
+    const unsigned long long top = block_max<VS_WAVES, true>(key);
+    if (top == 0) {                 // (uniform: every thread holds the top)
+        if (threadIdx.x == 0) ctl->done = 1;
+        return;
+    }
+    const long long j = VS_MAX_VIEWS - (long long)block_max<VS_WAVES, false>(key == top ? (unsigned long long)(VS_MAX_VIEWS - best_j) : 0ull);
+    if (key == top && best_j == j) s_marginal = best_m;             // (one lane: a view belongs to one lane)
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const long long marginal = (long long)s_marginal, gain = rows[VG_ROW * j + 1];
+    const long long cumulative = ctl->cumulative + marginal;
+    const double c = cost[j];
+    long long *const s = select + (long long)VS_ROW * r;
+    s[0] = j; s[1] = marginal; s[2] = cumulative; s[3] = gain - marginal;
+    util[2 * r] = c; util[2 * r + 1] = __longlong_as_double((long long)(top - 1ull));
+    round[j] = r;
+    ctl->winner = j; ctl->n_selected = r + 1; ctl->cumulative = cumulative; ctl->solo_sum += gain; ctl->cost_selected += c;
+}
+
+// starts: rounds x 3, the eye of round r's view, or a point outside every map for a round that did not happen (its path has n = 0)
+__global__ __launch_bounds__(VS_BLOCK) void vs_gather_eyes_kernel(long long rounds, const long long *__restrict__ select, const double *__restrict__ poses,
+                                                                  double *__restrict__ starts) {
+    const long long r = (long long)blockIdx.x * VS_BLOCK + threadIdx.x;
+    if (r >= rounds) return;
+    const long long j = select[VS_ROW * r];
+    for (int a = 0; a < 3; a++) starts[3 * r + a] = j >= 0 ? poses[12 * j + 3 + 4 * a] : __longlong_as_double((long long)0xFFF0000000000000ull);
+}
+
 __global__ __launch_bounds__(VS_BLOCK) void vs_claim_kernel(const unsigned long long *__restrict__ start, const unsigned long long *__restrict__ count,
                                                             const VsEntry *__restrict__ list, unsigned *claimed, const VsCtl *__restrict__ ctl) {
     if (ctl->done) return;          // (uniform)
@@ -183,8 +267,16 @@ struct ViewSelectState {
     isdf::PinBuf<int64_t> h_rows, h_select, h_round;
     isdf::PinBuf<uint32_t> h_claimed;
     isdf::DevEvents<2> ev_gain, ev_lists, ev_fill, ev_select;
+    // the routed selection's: the staged and the per-view costs, the rounds' {cost, utility}, the picked eyes and their paths
+    isdf::DevBuf<double> d_cost_in, d_cost, d_util, d_starts, d_path_xyz, d_path_rp;
+    isdf::DevBuf<int32_t> d_path_n;
+    isdf::RecPair<isdf::VsCostRec> cost_rec;
+    isdf::PinBuf<double> h_cost, h_util, h_path_xyz, h_path_rp;
+    isdf::PinBuf<int32_t> h_path_n;
+    isdf::DevEvents<2> ev_cost, ev_paths;
     int ready(isdf_ctx *c) {
         ISDF_TRY(ev_gain.ready(c)); ISDF_TRY(ev_lists.ready(c)); ISDF_TRY(ev_fill.ready(c)); ISDF_TRY(ev_select.ready(c));
+        ISDF_TRY(ev_cost.ready(c)); ISDF_TRY(ev_paths.ready(c)); ISDF_TRY(cost_rec.ready(c));
         return ctl.ready(c);
     }
 };
@@ -202,6 +294,19 @@ extern "C" void isdf_view_select_params_default(isdf_view_select_params *p) {
 extern "C" void isdf_view_select_sizes(int sizes_out[2]) {
     if (!sizes_out) return;
     sizes_out[0] = (int)sizeof(isdf_view_select_params); sizes_out[1] = (int)sizeof(isdf_view_select_info);
+}
+
+extern "C" void isdf_view_select_routed_params_default(isdf_view_select_routed_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    isdf_view_select_params_default(&p->select);
+    p->cost0 = 1.0;
+    p->max_cost = std::numeric_limits<double>::infinity();
+}
+
+extern "C" void isdf_view_select_routed_sizes(int sizes_out[2]) {
+    if (!sizes_out) return;
+    sizes_out[0] = (int)sizeof(isdf_view_select_routed_params); sizes_out[1] = (int)sizeof(isdf_view_select_routed_info);
 }
 
 namespace {
@@ -231,6 +336,44 @@ void select_pad(int64_t *select, long long from, long long k_select) {
     }
 }
 
+// the routed call's additions to the selection's arguments (null: isdf_view_select)
+struct VsRoute {
+    const double *cost;             // the caller's array, or null: the ctx's field
+    double cost0, max_cost;
+    int path_cap;                   // 0: no paths
+    double *cost_out, *util_out;
+    int32_t *path_n_out;
+    double *path_xyz_out, *path_rp_out;
+    isdf_view_select_routed_info *info_out;
+};
+
+// the routed form's own argument rules, after the selection's (c may be null: the host form, which has no paths)
+int route_check(isdf_ctx *c, const isdf_view_select_routed_params &P, const double *cost, long long n_views) {
+    if (P.select.min_gain < 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "routed view select: min_gain >= 1 (with a utility a view that adds nothing is never picked)");
+    if (!(P.cost0 > 0.0) || !vs_cost_finite(P.cost0) || !(P.max_cost >= 0.0) || P.path_cap < 0)
+        return isdf_fail(c, ISDF_ERR_INVALID_ARG, "bad routed view select parameters (cost0 finite and > 0, max_cost >= 0, path_cap >= 0)");
+    if (cost && P.path_cap >= 1) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "routed view select: paths are read off the ctx's field, not with a cost array");
+    if (cost)
+        for (long long j = 0; j < n_views; j++)
+            if (!(cost[j] >= 0.0)) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "routed view select: a cost is negative or not a number");
+    return ISDF_OK;
+}
+
+void route_info(const VsRouteCounts &R, int source, double cost_ms, double paths_ms, isdf_view_select_routed_info *out) {
+    out->n_eligible = R.n_eligible; out->n_unreachable = R.n_unreachable; out->n_over_budget = R.n_over_budget;
+    out->cost_selected = R.cost_selected; out->cost_source = source; out->reserved = 0; out->cost_ms = cost_ms; out->paths_ms = paths_ms;
+}
+
+// what a round that did not happen leaves in the routed outputs, from round `from` on
+void route_pad(const VsRoute &R, long long from, long long k_select) {
+    const size_t cap = (size_t)R.path_cap, n = (size_t)(k_select - from);
+    if (R.util_out) std::memset(R.util_out + 2 * from, 0, n * 2 * sizeof(double));
+    if (cap == 0) return;
+    if (R.path_n_out) std::memset(R.path_n_out + from, 0, n * sizeof(int32_t));
+    if (R.path_xyz_out) std::memset(R.path_xyz_out + (size_t)from * cap * 3, 0, n * cap * 3 * sizeof(double));
+    if (R.path_rp_out) std::memset(R.path_rp_out + (size_t)from * cap * 2, 0, n * cap * 2 * sizeof(double));
+}
+
 // workgroups over n words or entries, each lane sized for a few
 unsigned wide_blocks(long long n) { return (unsigned)std::min<long long>(std::max<long long>((n + VS_BLOCK * VS_PER_LANE - 1) / (VS_BLOCK * VS_PER_LANE), 1), VS_MAX_X); }
 
@@ -247,12 +390,10 @@ int list_reserve(isdf_ctx *c, ViewSelectState *S, size_t need, size_t used, hipS
     return ISDF_OK;         // (the smaller one goes here)
 }
 
-}  // namespace
-
-extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const double *poses, long long n_views, const isdf_view_select_params *params, int64_t *rows_out,
-                                int64_t *select_out, int64_t *round_out, uint32_t *claimed_out, isdf_view_select_info *info_out) {
-    if (!c) return ISDF_ERR_INVALID_ARG;
-    const isdf_view_select_params P = map_query::resolve(params, isdf_view_select_params_default);
+// The body of both entries.  route null: isdf_view_select, which launches what it always launched; else PR are the routed call's
+// parameters (P = PR->select) and the cost kernel, the routed marginal and pick kernels and the paths join in.
+int select_run(isdf_ctx *c, const isdf_depth_camera *cam, const double *poses, long long n_views, const isdf_view_select_params &P, const VsRoute *route,
+               const isdf_view_select_routed_params *PR, int64_t *rows_out, int64_t *select_out, int64_t *round_out, uint32_t *claimed_out, isdf_view_select_info *info_out) {
     const MapGeom M = map_geom(c->grid);            // (without a map: zeros, and the state check below refuses)
     isdf_view_gain_params Pg;
     DcRays base;
@@ -260,6 +401,11 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
     ISDF_TRY(map_query::single_device(c, "the view selection is not offered on a multi-device ctx"));
     ISDF_TRY(map_query::has_occupancy(c, "the view selection"));
     ISDF_TRY(map_query::has_known(c, "the view selection needs a known grid (isdf_map_known_enable)"));
+    if (route) {
+        ISDF_TRY(route_check(c, *PR, route->cost, n_views));
+        if (!route->cost) ISDF_TRY(isdf_field_read_ready(c));
+    }
+    const bool paths = route && route->path_cap >= 1;
     ViewSelectState *S;
     ViewGainState *G;
     ISDF_TRY(map_query::state_of(c, c->vsl, &S));
@@ -278,6 +424,10 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
         }
         if (select_out) select_pad(select_out, 0, P.k_select);
         if (info_out) select_info(0, N, 0, 0.0, 0.0, 0.0, info_out);
+        if (route) {
+            route_pad(*route, 0, P.k_select);
+            if (route->info_out) route_info(VsRouteCounts(), route->cost ? 1 : 0, 0.0, 0.0, route->info_out);
+        }
         return ISDF_OK;
     }
     const long long rounds = std::min<long long>(P.k_select, n_views);          // a view is picked once: no later round can pick
@@ -289,8 +439,28 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
     if (want_rows) ISDF_TRY(S->h_rows.reserve(c, nv * VG_ROW));
     if (select_out) ISDF_TRY(S->h_select.reserve(c, (size_t)rounds * VS_ROW));
     if (round_out) ISDF_TRY(S->h_round.reserve(c, nv));
+    const size_t nr = (size_t)rounds, cap = route ? (size_t)route->path_cap : 0;
+    if (route) {
+        if (route->cost) ISDF_TRY(S->d_cost_in.reserve(c, nv));
+        ISDF_TRY(S->d_cost.reserve(c, nv)); ISDF_TRY(S->d_util.reserve(c, nr * 2));
+        if (route->cost_out) ISDF_TRY(S->h_cost.reserve(c, nv));
+        if (route->util_out) ISDF_TRY(S->h_util.reserve(c, nr * 2));
+    }
+    if (paths) {
+        if (nr * cap > (size_t)0x7FFFFFFF) return isdf_fail(c, ISDF_ERR_INVALID_ARG, "routed view select: rounds x path_cap above 2^31 - 1");
+        ISDF_TRY(S->d_starts.reserve(c, nr * 3)); ISDF_TRY(S->d_path_n.reserve(c, nr));
+        ISDF_TRY(S->d_path_xyz.reserve(c, nr * cap * 3)); ISDF_TRY(S->d_path_rp.reserve(c, nr * cap * 2));
+        if (route->path_n_out) ISDF_TRY(S->h_path_n.reserve(c, nr));
+        if (route->path_xyz_out) ISDF_TRY(S->h_path_xyz.reserve(c, nr * cap * 3));
+        if (route->path_rp_out) ISDF_TRY(S->h_path_rp.reserve(c, nr * cap * 2));
+    }
     HIPCHK(c, hipMemcpyAsync(S->d_poses, poses, nv * 12 * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(c, S->ctl.zero(st));
+    if (route) {
+        if (route->cost) HIPCHK(c, hipMemcpyAsync(S->d_cost_in, route->cost, nv * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(c, S->cost_rec.zero(st));
+        HIPCHK(c, hipMemsetAsync(S->d_util, 0, nr * 2 * sizeof(double), st));            // (a round that did not happen: {0, 0})
+    }
     HIPCHK(c, hipMemsetAsync(S->d_claimed, 0, nw * sizeof(unsigned), st));
     // (n_views >= 1 here and a known grid has n_words >= 1: blocks() is at least one workgroup at both of its uses below)
     hipLaunchKernelGGL(vs_begin_kernel, dim3(blocks(std::max(n_views, rounds), VS_BLOCK)), dim3(VS_BLOCK), 0, st, n_views, rounds, S->d_count.get(), S->d_m.get(),
@@ -327,17 +497,36 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
     ISDF_TRY(map_query::count_begin(c, true, S->ev_gain, st));
     ISDF_TRY(gain_run(c, G, base, M, Pg, S->d_poses.get(), n_views, S->d_rows.get(), false, &chunks, st, &lists));
     ISDF_TRY(map_query::count_end(c, true, S->ev_gain, st));
+    if (route) {                    // the costs, once the rows are the gain's
+        ISDF_TRY(map_query::count_begin(c, true, S->ev_cost, st));
+        hipLaunchKernelGGL(vs_cost_kernel, dim3(blocks(n_views, VS_BLOCK)), dim3(VS_BLOCK), 0, st, n_views, ff_map(c), (const double *)c->fe.d_field.get(),
+                           (const double *)S->d_poses.get(), route->cost ? (const double *)S->d_cost_in.get() : (const double *)nullptr, (const long long *)S->d_rows.get(),
+                           route->max_cost, S->d_cost.get(), S->cost_rec.dev());
+        HIPCHK(c, hipGetLastError());
+        ISDF_TRY(map_query::count_end(c, true, S->ev_cost, st));
+    }
     // the rounds: a fixed sequence, no hand-over between them
     ISDF_TRY(list_reserve(c, S, 1, 0, st));             // (no entry at all: the kernels still take a pointer)
     const unsigned seg_bx = wide_blocks((long long)std::min<unsigned long long>(longest_chunk, (unsigned long long)n_words));          // a segment has at most n_words entries
     const unsigned view_by = (unsigned)std::min<long long>(n_views, VS_MAX_Y);
     ISDF_TRY(map_query::count_begin(c, true, S->ev_select, st));
     for (long long r = 0; r < rounds; r++) {
-        hipLaunchKernelGGL(vs_marginal_kernel, dim3(seg_bx, view_by), dim3(VS_BLOCK), 0, st, n_views, (const long long *)S->d_rows.get(), (const long long *)S->d_round.get(),
-                           (const unsigned long long *)S->d_start.get(), (const unsigned long long *)S->d_count.get(), (const VsEntry *)S->d_list.get(),
-                           (const unsigned *)S->d_claimed.get(), S->d_m.get(), (const VsCtl *)S->ctl.dev());
-        hipLaunchKernelGGL(vs_pick_kernel, dim3(1), dim3(VS_BLOCK), 0, st, n_views, (int)r, (long long)P.min_gain, (const long long *)S->d_rows.get(), S->d_round.get(),
-                           S->d_m.get(), S->d_select.get(), S->ctl.dev());
+        if (route) {
+            hipLaunchKernelGGL(vs_marginal_kernel<true>, dim3(seg_bx, view_by), dim3(VS_BLOCK), 0, st, n_views, (const long long *)S->d_rows.get(),
+                               (const long long *)S->d_round.get(), (const unsigned long long *)S->d_start.get(), (const unsigned long long *)S->d_count.get(),
+                               (const VsEntry *)S->d_list.get(), (const unsigned *)S->d_claimed.get(), S->d_m.get(), (const VsCtl *)S->ctl.dev(),
+                               (const double *)S->d_cost.get(), route->max_cost);
+            hipLaunchKernelGGL(vs_pick_util_kernel, dim3(1), dim3(VS_BLOCK), 0, st, n_views, (int)r, (long long)P.min_gain, route->cost0, route->max_cost,
+                               (const long long *)S->d_rows.get(), (const double *)S->d_cost.get(), S->d_round.get(), S->d_m.get(), S->d_select.get(), S->d_util.get(),
+                               S->ctl.dev());
+        } else {
+            hipLaunchKernelGGL(vs_marginal_kernel<false>, dim3(seg_bx, view_by), dim3(VS_BLOCK), 0, st, n_views, (const long long *)S->d_rows.get(),
+                               (const long long *)S->d_round.get(), (const unsigned long long *)S->d_start.get(), (const unsigned long long *)S->d_count.get(),
+                               (const VsEntry *)S->d_list.get(), (const unsigned *)S->d_claimed.get(), S->d_m.get(), (const VsCtl *)S->ctl.dev(),
+                               (const double *)nullptr, 0.0);
+            hipLaunchKernelGGL(vs_pick_kernel, dim3(1), dim3(VS_BLOCK), 0, st, n_views, (int)r, (long long)P.min_gain, (const long long *)S->d_rows.get(), S->d_round.get(),
+                               S->d_m.get(), S->d_select.get(), S->ctl.dev());
+        }
         hipLaunchKernelGGL(vs_claim_kernel, dim3(seg_bx), dim3(VS_BLOCK), 0, st, (const unsigned long long *)S->d_start.get(), (const unsigned long long *)S->d_count.get(),
                            (const VsEntry *)S->d_list.get(), S->d_claimed.get(), (const VsCtl *)S->ctl.dev());
         HIPCHK(c, hipGetLastError());
@@ -347,8 +536,26 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
         HIPCHK(c, hipGetLastError());
     }
     ISDF_TRY(map_query::count_end(c, true, S->ev_select, st));
+    if (paths) {                    // the ways to the picked eyes, behind the rounds on the same stream; rows come back whole: zero past a path's end
+        ISDF_TRY(map_query::count_begin(c, true, S->ev_paths, st));
+        HIPCHK(c, hipMemsetAsync(S->d_path_xyz, 0, nr * cap * 3 * sizeof(double), st));
+        HIPCHK(c, hipMemsetAsync(S->d_path_rp, 0, nr * cap * 2 * sizeof(double), st));
+        hipLaunchKernelGGL(vs_gather_eyes_kernel, dim3(blocks(rounds, VS_BLOCK)), dim3(VS_BLOCK), 0, st, rounds, (const long long *)S->d_select.get(),
+                           (const double *)S->d_poses.get(), S->d_starts.get());
+        HIPCHK(c, hipGetLastError());
+        ISDF_TRY(isdf_frontend_field_paths_device(c, S->d_starts.get(), (int)rounds, route->path_cap, S->d_path_n.get(), S->d_path_xyz.get(), S->d_path_rp.get(), (void *)st));
+        ISDF_TRY(map_query::count_end(c, true, S->ev_paths, st));
+    }
     // the last hand-over: the record and the outputs asked for, through the pinned copies
     HIPCHK(c, S->ctl.fetch(st));
+    if (route) {
+        HIPCHK(c, S->cost_rec.fetch(st));
+        if (route->cost_out) HIPCHK(c, hipMemcpyAsync(S->h_cost.get(), S->d_cost, nv * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (route->util_out) HIPCHK(c, hipMemcpyAsync(S->h_util.get(), S->d_util, nr * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (paths && route->path_n_out) HIPCHK(c, hipMemcpyAsync(S->h_path_n.get(), S->d_path_n, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (paths && route->path_xyz_out) HIPCHK(c, hipMemcpyAsync(S->h_path_xyz.get(), S->d_path_xyz, nr * cap * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (paths && route->path_rp_out) HIPCHK(c, hipMemcpyAsync(S->h_path_rp.get(), S->d_path_rp, nr * cap * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
     if (want_rows) HIPCHK(c, hipMemcpyAsync(S->h_rows.get(), S->d_rows, nv * VG_ROW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (select_out) HIPCHK(c, hipMemcpyAsync(S->h_select.get(), S->d_select, (size_t)rounds * VS_ROW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (round_out) HIPCHK(c, hipMemcpyAsync(S->h_round.get(), S->d_round, nv * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -368,7 +575,42 @@ extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const
         N.n_selected = R.n_selected; N.gain_selected = R.cumulative; N.gain_solo_sum = R.solo_sum; N.list_words = (long long)R.base;
         select_info(n_views, N, chunks, std::max(S->ev_gain.ms(0, 1) - lists_ms, 0.0), lists_ms, S->ev_select.ms(0, 1), info_out);
     }
+    if (route) {
+        if (route->cost_out) std::memcpy(route->cost_out, S->h_cost.get(), nv * sizeof(double));
+        if (route->util_out) std::memcpy(route->util_out, S->h_util.get(), nr * 2 * sizeof(double));
+        if (paths && route->path_n_out) std::memcpy(route->path_n_out, S->h_path_n.get(), nr * sizeof(int32_t));
+        if (paths && route->path_xyz_out) std::memcpy(route->path_xyz_out, S->h_path_xyz.get(), nr * cap * 3 * sizeof(double));
+        if (paths && route->path_rp_out) std::memcpy(route->path_rp_out, S->h_path_rp.get(), nr * cap * 2 * sizeof(double));
+        route_pad(*route, rounds, P.k_select);
+        if (route->info_out) {
+            const VsCostRec &K = S->cost_rec.host();
+            VsRouteCounts R;
+            R.n_eligible = (long long)K.n_eligible; R.n_unreachable = (long long)K.n_unreachable; R.n_over_budget = (long long)K.n_over_budget;
+            R.cost_selected = S->ctl.host().cost_selected;
+            route_info(R, route->cost ? 1 : 0, S->ev_cost.ms(0, 1), paths ? S->ev_paths.ms(0, 1) : 0.0, route->info_out);
+        }
+    }
     return ISDF_OK;
+}
+
+}  // namespace
+
+extern "C" int isdf_view_select(isdf_ctx *c, const isdf_depth_camera *cam, const double *poses, long long n_views, const isdf_view_select_params *params, int64_t *rows_out,
+                                int64_t *select_out, int64_t *round_out, uint32_t *claimed_out, isdf_view_select_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    const isdf_view_select_params P = map_query::resolve(params, isdf_view_select_params_default);
+    return select_run(c, cam, poses, n_views, P, nullptr, nullptr, rows_out, select_out, round_out, claimed_out, info_out);
+}
+
+extern "C" int isdf_view_select_routed(isdf_ctx *c, const isdf_depth_camera *cam, const double *poses, long long n_views, const double *cost,
+                                       const isdf_view_select_routed_params *params, int64_t *rows_out, int64_t *select_out, int64_t *round_out, uint32_t *claimed_out,
+                                       double *cost_out, double *util_out, int32_t *path_n_out, double *path_xyz_out, double *path_rp_out,
+                                       isdf_view_select_routed_info *info_out) {
+    if (!c) return ISDF_ERR_INVALID_ARG;
+    const isdf_view_select_routed_params P = map_query::resolve(params, isdf_view_select_routed_params_default);
+    const VsRoute route{cost, P.cost0, P.max_cost, P.path_cap, cost_out, util_out, path_n_out, path_xyz_out, path_rp_out, info_out};
+    // (the info's rows: the selection's words are filled through the same pointer the plain entry takes)
+    return select_run(c, cam, poses, n_views, P.select, &route, &P, rows_out, select_out, round_out, claimed_out, info_out ? &info_out->select : nullptr);
 }
 
 extern "C" int isdf_view_select_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
@@ -387,5 +629,35 @@ extern "C" int isdf_view_select_host(const uint32_t *bits, const uint8_t *occ, c
     vs_select_host(bits, occ, M, base, poses, n_views, P.k_select, P.min_gain, rows_out ? rows_out : rows.data(), select_out ? select_out : select.data(),
                    round_out ? round_out : round.data(), claimed_out ? claimed_out : claimed.data(), N);
     if (info_out) select_info(n_views, N, 0, 0.0, 0.0, 0.0, info_out);
+    return ISDF_OK;
+}
+
+extern "C" int isdf_view_select_routed_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
+                                            const isdf_depth_camera *cam, const double *poses, long long n_views, const double *cost,
+                                            const isdf_view_select_routed_params *params, int64_t *rows_out, int64_t *select_out, int64_t *round_out, uint32_t *claimed_out,
+                                            double *cost_out, double *util_out, isdf_view_select_routed_info *info_out) {
+    if (ms_geometry_bad(bmin, bmax, resolution, dims) || !bits || !occ) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "routed view select (host form): bad arguments");
+    const MapGeom M = map_geom(bmin, bmax, resolution, dims);
+    const isdf_view_select_routed_params P = map_query::resolve(params, isdf_view_select_routed_params_default);
+    isdf_view_gain_params Pg;
+    DcRays base;
+    ISDF_TRY(select_setup(nullptr, cam, poses, n_views, P.select, M, Pg, base));
+    ISDF_TRY(route_check(nullptr, P, cost, n_views));
+    if (P.path_cap != 0) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "routed view select (host form): no paths (path_cap = 0)");
+    if (n_views > 0 && !cost) return isdf_fail(nullptr, ISDF_ERR_INVALID_ARG, "routed view select (host form): a cost array is required");
+    const size_t nw = (size_t)mk_words(mk_voxels(dims)), nv = (size_t)n_views, k = (size_t)P.select.k_select;
+    std::vector<int64_t> rows(rows_out ? 0 : nv * VG_ROW), select(select_out ? 0 : k * VS_ROW), round(round_out ? 0 : nv);
+    std::vector<uint32_t> claimed(claimed_out ? 0 : nw);
+    std::vector<double> util(util_out ? 0 : k * 2);
+    VsCounts N;
+    VsRouteCounts R;
+    vs_select_routed_host(bits, occ, M, base, poses, n_views, P.select.k_select, P.select.min_gain, cost, P.cost0, P.max_cost, rows_out ? rows_out : rows.data(),
+                          select_out ? select_out : select.data(), round_out ? round_out : round.data(), claimed_out ? claimed_out : claimed.data(),
+                          util_out ? util_out : util.data(), N, R);
+    if (cost_out && nv) std::memcpy(cost_out, cost, nv * sizeof(double));
+    if (info_out) {
+        select_info(n_views, N, 0, 0.0, 0.0, 0.0, &info_out->select);
+        route_info(R, 1, 0.0, 0.0, info_out);
+    }
     return ISDF_OK;
 }

@@ -39,14 +39,13 @@ inline void vs_counts_of_rows(const int64_t *rows, long long n_views, VsCounts &
     N.n_scored = B.n_scored; N.best_single_gain = B.best_gain;
 }
 
-// ---- host form: rows n_views x 8, select k_select x 4, round n_views, claimed n_words; all are written
-inline void vs_select_host(const uint32_t *bits, const uint8_t *occ, const MapGeom &M, const DcRays &base, const double *poses, long long n_views, int k_select,
-                           long long min_gain, int64_t *rows, int64_t *select, int64_t *round, uint32_t *claimed, VsCounts &N) {
+// the sets: rows and round are written, U[j] is empty for a view that is not scored; N.list_words and the counts of the rows
+inline void vs_sets_host(const uint32_t *bits, const uint8_t *occ, const MapGeom &M, const DcRays &base, const double *poses, long long n_views, int64_t *rows, int64_t *round,
+                         std::vector<std::vector<uint32_t>> &U, VsCounts &N) {
     const long long n_words = mk_words((long long)M.dims[0] * M.dims[1] * M.dims[2]);
     const std::vector<uint16_t> zero((size_t)base.width * base.height, 0);
     N = VsCounts();
-    // the sets: U[j] is empty for a view that is not scored
-    std::vector<std::vector<uint32_t>> U((size_t)n_views);
+    U.assign((size_t)n_views, std::vector<uint32_t>());
     for (long long j = 0; j < n_views; j++) {
         int64_t *const row = rows + VG_ROW * j;
         for (int w = 0; w < VG_ROW; w++) row[w] = 0;
@@ -71,32 +70,100 @@ inline void vs_select_host(const uint32_t *bits, const uint8_t *occ, const MapGe
         for (long long w = 0; w < n_words; w++) N.list_words += u[(size_t)w] != 0u;
     }
     vs_counts_of_rows(rows, n_views, N);
-    // the rounds
+}
+
+inline void vs_rounds_begin(long long n_words, int k_select, int64_t *select, uint32_t *claimed) {
     for (long long w = 0; w < n_words; w++) claimed[w] = 0u;
     for (int r = 0; r < k_select; r++) {
         int64_t *const s = select + (long long)VS_ROW * r;
         s[0] = -1; s[1] = s[2] = s[3] = 0;
     }
+}
+
+// round r has picked view j with marginal m: its voxels are claimed, the counts and the outputs move on
+inline void vs_round_take(int r, long long j, long long m, long long n_words, const std::vector<uint32_t> &u, const int64_t *rows, int64_t *select, int64_t *round,
+                          uint32_t *claimed, VsCounts &N) {
+    for (long long w = 0; w < n_words; w++) claimed[w] |= u[(size_t)w];
+    N.gain_selected += m;
+    N.gain_solo_sum += rows[VG_ROW * j + 1];
+    N.n_selected = r + 1;
+    round[j] = r;
+    int64_t *const s = select + (long long)VS_ROW * r;
+    s[0] = j; s[1] = m; s[2] = N.gain_selected; s[3] = rows[VG_ROW * j + 1] - m;
+}
+
+inline long long vs_marginal_host(const std::vector<uint32_t> &u, const uint32_t *claimed, long long n_words) {
+    long long m = 0;
+    for (long long w = 0; w < n_words; w++) m += vs_popcount(u[(size_t)w] & ~claimed[w]);
+    return m;
+}
+
+// ---- host form: rows n_views x 8, select k_select x 4, round n_views, claimed n_words; all are written
+inline void vs_select_host(const uint32_t *bits, const uint8_t *occ, const MapGeom &M, const DcRays &base, const double *poses, long long n_views, int k_select,
+                           long long min_gain, int64_t *rows, int64_t *select, int64_t *round, uint32_t *claimed, VsCounts &N) {
+    const long long n_words = mk_words((long long)M.dims[0] * M.dims[1] * M.dims[2]);
+    std::vector<std::vector<uint32_t>> U;
+    vs_sets_host(bits, occ, M, base, poses, n_views, rows, round, U, N);
+    // the rounds
+    vs_rounds_begin(n_words, k_select, select, claimed);
     for (int r = 0; r < k_select; r++) {
         unsigned long long top = 0;
         for (long long j = 0; j < n_views; j++) {
             if (rows[VG_ROW * j] != VG_SCORED || round[j] >= 0) continue;
-            const std::vector<uint32_t> &u = U[(size_t)j];
-            long long m = 0;
-            for (long long w = 0; w < n_words; w++) m += vs_popcount(u[(size_t)w] & ~claimed[w]);
-            const unsigned long long key = vs_key(m, j);
+            const unsigned long long key = vs_key(vs_marginal_host(U[(size_t)j], claimed, n_words), j);
             if (key > top) top = key;
         }
         if (top == 0 || vs_key_marginal(top) < min_gain) break;
-        const long long j = vs_key_view(top), m = vs_key_marginal(top);
-        const std::vector<uint32_t> &u = U[(size_t)j];
-        for (long long w = 0; w < n_words; w++) claimed[w] |= u[(size_t)w];
-        N.gain_selected += m;
-        N.gain_solo_sum += rows[VG_ROW * j + 1];
-        N.n_selected = r + 1;
-        round[j] = r;
-        int64_t *const s = select + (long long)VS_ROW * r;
-        s[0] = j; s[1] = m; s[2] = N.gain_selected; s[3] = rows[VG_ROW * j + 1] - m;
+        const long long j = vs_key_view(top);
+        vs_round_take(r, j, vs_key_marginal(top), n_words, U[(size_t)j], rows, select, round, claimed, N);
+    }
+    for (long long w = 0; w < n_words; w++) claimed[w] |= bits[w];
+}
+
+// ---- the routed selection: greedy coverage by utility = marginal gain per travel cost.  cost: n_views doubles, each
+// non-negative or +inf (the caller has checked that).  A view is eligible when it is scored, not picked so far, its cost finite and
+// <= max_cost; round r: among the eligible views with m_j >= min_gain (min_gain >= 1), u_j = (double)m_j / (cost0 + c_j) - one addition,
+// one division, fp64 - and j* the lowest index among the largest u_j.  util k_select x 2: {c_j*, u_j*}, {0, 0} for a round that did not
+// happen.
+struct VsRouteCounts { long long n_eligible = 0, n_unreachable = 0, n_over_budget = 0; double cost_selected = 0.0; };
+
+MU_HD bool vs_cost_finite(double c) { return c - c == 0.0; }           // (not a NaN, not an infinity)
+MU_HD bool vs_cost_eligible(double c, double max_cost) { return vs_cost_finite(c) && c <= max_cost; }
+MU_HD double vs_utility(long long m, double cost0, double c) { return (double)m / (cost0 + c); }
+
+inline void vs_route_counts(const int64_t *rows, const double *cost, long long n_views, double max_cost, VsRouteCounts &R) {
+    R = VsRouteCounts();
+    for (long long j = 0; j < n_views; j++) {
+        if (rows[VG_ROW * j] != VG_SCORED) continue;
+        if (!vs_cost_finite(cost[j])) R.n_unreachable++;
+        else if (!(cost[j] <= max_cost)) R.n_over_budget++;
+        else R.n_eligible++;
+    }
+}
+
+inline void vs_select_routed_host(const uint32_t *bits, const uint8_t *occ, const MapGeom &M, const DcRays &base, const double *poses, long long n_views, int k_select,
+                                  long long min_gain, const double *cost, double cost0, double max_cost, int64_t *rows, int64_t *select, int64_t *round,
+                                  uint32_t *claimed, double *util, VsCounts &N, VsRouteCounts &R) {
+    const long long n_words = mk_words((long long)M.dims[0] * M.dims[1] * M.dims[2]);
+    std::vector<std::vector<uint32_t>> U;
+    vs_sets_host(bits, occ, M, base, poses, n_views, rows, round, U, N);
+    vs_route_counts(rows, cost, n_views, max_cost, R);
+    vs_rounds_begin(n_words, k_select, select, claimed);
+    for (int r = 0; r < k_select; r++) util[2 * r] = util[2 * r + 1] = 0.0;
+    for (int r = 0; r < k_select; r++) {
+        long long best = -1, best_m = 0;
+        double best_u = 0.0;
+        for (long long j = 0; j < n_views; j++) {
+            if (rows[VG_ROW * j] != VG_SCORED || round[j] >= 0 || !vs_cost_eligible(cost[j], max_cost)) continue;
+            const long long m = vs_marginal_host(U[(size_t)j], claimed, n_words);
+            if (m < min_gain) continue;
+            const double u = vs_utility(m, cost0, cost[j]);
+            if (best < 0 || u > best_u) { best = j; best_m = m; best_u = u; }
+        }
+        if (best < 0) break;
+        vs_round_take(r, best, best_m, n_words, U[(size_t)best], rows, select, round, claimed, N);
+        util[2 * r] = cost[best]; util[2 * r + 1] = best_u;
+        R.cost_selected += cost[best];
     }
     for (long long w = 0; w < n_words; w++) claimed[w] |= bits[w];
 }

@@ -930,6 +930,53 @@ def view_select_host(bits, occ, bmin, bmax, res, cam, poses, lib=None, **params)
     return rows, select, rnd, claimed, info
 
 
+def _view_route_params(lib, cost0=None, max_cost=None, path_cap=None, **select):
+    p = capi.IsdfViewSelectRoutedParams()
+    lib.isdf_view_select_routed_params_default(C.byref(p))
+    p.select = _view_select_params(lib, **select)
+    if cost0 is not None:
+        p.cost0 = float(cost0)
+    if max_cost is not None:
+        p.max_cost = float(max_cost)
+    if path_cap is not None:
+        p.path_cap = int(path_cap)
+    return p
+
+
+def _view_route_cost(cost, n):
+    """the caller's cost array as n doubles, or None"""
+    if cost is None:
+        return None
+    c = np.ascontiguousarray(cost, dtype=np.float64).reshape(-1)
+    if c.size != n:
+        raise ValueError(f"cost must hold one value per pose ({n}), not {c.size}")
+    return c
+
+
+def view_select_routed_host(bits, occ, bmin, bmax, res, cam, poses, cost, lib=None, **params):
+    """isdf_view_select_routed_host: view_select_host by utility - each round the view with the largest marginal gain per travel cost, m /
+    (cost0 + cost[j]), among the scored views whose cost is finite and <= max_cost - in plain host code.  cost: one non-negative double
+    or +inf per pose, in cells (frontend_field_host gives a field to read it from).  params: cost0, max_cost, and view_select_host's
+    (min_gain >= 1).  Returns (rows, select, round, claimed, cost float64 [n], util float64 [k_select, 2] = (cost, utility) of each
+    round's view, (0, 0) for a round that did not happen, IsdfViewSelectRoutedInfo)."""
+    lib = lib or capi.load_library()
+    o8 = np.ascontiguousarray(occ, dtype=np.uint8)
+    w, d = _known_args(bits, o8.shape)
+    b0, b1, _, _ = _scan_geometry(bmin, bmax, o8.shape, np.zeros(3))
+    p = _view_route_params(lib, **params)
+    P, rows, select, rnd, claimed = _view_select_arrays(poses, p.select.k_select, o8.shape)
+    c = _view_route_cost(cost, P.shape[0])
+    cost_out, util = np.zeros(P.shape[0]), np.zeros((max(int(p.select.k_select), 0), 2))
+    info = capi.IsdfViewSelectRoutedInfo()
+    rc = lib.isdf_view_select_routed_host(w.ctypes.data_as(C.c_void_p), o8.ctypes.data_as(C.c_void_p), _p(b0), _p(b1), float(res), d, C.byref(cam),
+                                          P.ctypes.data_as(C.c_void_p), P.shape[0], None if c is None else c.ctypes.data_as(C.c_void_p), C.byref(p),
+                                          rows.ctypes.data_as(C.c_void_p), select.ctypes.data_as(C.c_void_p), rnd.ctypes.data_as(C.c_void_p),
+                                          claimed.ctypes.data_as(C.c_void_p), cost_out.ctypes.data_as(C.c_void_p), util.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc < 0:
+        raise IsdfError(int(rc), "isdf_view_select_routed_host")
+    return rows, select, rnd, claimed, cost_out, util, info
+
+
 def _traj_check_info_from(d):
     info = capi.IsdfTrajCheckInfo()
     for name, _ in capi.IsdfTrajCheckInfo._fields_:
@@ -1514,6 +1561,52 @@ class Engine:
         _, select, _, _, info = self.view_select(cam, poses[listed], k_select=k_select, min_gain=select_min_gain, **gain)
         picked = select[:info.n_selected]
         return np.ascontiguousarray(poses[listed[picked[:, 0]]]), picked[:, 1].copy(), listed[picked[:, 0]], info
+
+    def view_select_routed(self, cam, poses, cost=None, **params):
+        """isdf_view_select_routed: view_select by utility = marginal gain per travel cost.  cost None: the travel cost of a view is the
+        ctx's valid cost-to-go field at its eye - build the field TOWARDS THE ROBOT first (frontend_field_build[_known]) -, an eye the
+        field does not reach is never picked; else one non-negative double or +inf per pose.  params: cost0, max_cost, path_cap, and
+        view_select's (min_gain >= 1).  Returns (rows, select, round, claimed, cost float64 [n], util float64 [k_select, 2], paths,
+        IsdfViewSelectRoutedInfo); paths is None with path_cap 0, else (n int32 [k_select], xyz [k_select, path_cap, 3], roll/pitch
+        [k_select, path_cap, 2]) as frontend_field_paths gives them for the picked eyes in pick order: each walks from the eye to the
+        robot's cell, with the attitudes of walking that way."""
+        p = _view_route_params(self.lib, **params)
+        k = max(int(p.select.k_select), 0)
+        P, rows, select, rnd, claimed = _view_select_arrays(poses, k, self._grid_dims())
+        c = _view_route_cost(cost, P.shape[0])
+        cost_out, util = np.zeros(P.shape[0]), np.zeros((k, 2))
+        cap = max(int(p.path_cap), 0)
+        paths = (np.zeros(k, dtype=np.int32), np.zeros((k, cap, 3)), np.zeros((k, cap, 2))) if cap else None
+        info = capi.IsdfViewSelectRoutedInfo()
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)          # noqa: E731
+        self._check(self.lib.isdf_view_select_routed(self.h, C.byref(cam), ptr(P), P.shape[0], ptr(c), C.byref(p), ptr(rows), ptr(select), ptr(rnd), ptr(claimed),
+                                                     ptr(cost_out), ptr(util), *([ptr(a) for a in paths] if paths else [None] * 3), C.byref(info)))
+        return rows, select, rnd, claimed, cost_out, util, paths, info
+
+    def next_view_set_routed(self, cam, offsets, robot_xyz, known=True, radius=-1, border=0, k_select=4, select_min_gain=1, cost0=1.0, max_cost=np.inf,
+                             path_cap=256, connectivity=26, min_size=1, **params):
+        """next_view_set with the robot in it: next_views, then the cost-to-go field towards robot_xyz (frontend_field_build_known with
+        radius and border when `known`, else frontend_field_build; it replaces the ctx's field), then view_select_routed over the poses
+        of all targets' best lists.  Returns (poses float64 [n_selected, 12] in the order picked, their marginal gains int64
+        [n_selected], their travel costs float64 [n_selected] in cells, paths: a list of n_selected arrays [n, 3] running robot -> eye
+        (a walk of more than path_cap nodes keeps the path_cap nearest the eye and so no longer starts at the robot), their candidate
+        indices int64 [n_selected], IsdfViewSelectRoutedInfo).  Every returned view is one the field reaches."""
+        _, _, poses, _, best, _ = self.next_views(cam, offsets, connectivity=connectivity, min_size=min_size, **params)
+        listed = best[best >= 0]
+        if known:
+            self.frontend_field_build_known(robot_xyz, radius, border)
+        else:
+            self.frontend_field_build(robot_xyz)
+        gain = {k: v for k, v in params.items() if k in ("stride", "max_range_m", "scratch_bytes")}
+        _, select, _, _, _, util, paths, info = self.view_select_routed(cam, poses[listed], k_select=k_select, min_gain=select_min_gain, cost0=cost0, max_cost=max_cost,
+                                                                        path_cap=path_cap, **gain)
+        n_sel = info.select.n_selected
+        picked = select[:n_sel]
+        n, xyz, _ = paths
+        cap = xyz.shape[1]
+        # (a walk longer than path_cap is cut at its far end, the robot's)
+        ways = [np.ascontiguousarray(xyz[r, :min(int(n[r]), cap)][::-1]) for r in range(n_sel)]
+        return np.ascontiguousarray(poses[listed[picked[:, 0]]]), picked[:, 1].copy(), util[:n_sel, 0].copy(), ways, listed[picked[:, 0]], info
 
     def map_counts(self):
         """The per-voxel point counts set_pointcloud keeps, uint32 [X, Y, Z]."""

@@ -2014,7 +2014,7 @@ int isdf_known_clusters_host(const uint32_t *set_bits, const int32_t dims[3], co
  * per call: the count of kept candidates, which sizes the gain's launches (the gain is never launched over a rejected candidate, each
  * view costs a cleared `seen` grid; with nothing kept nothing more is launched), and the results.  Two runs give the same bytes: the
  * counters are integer sums and the selection is a reduction without atomics.  min_gain is an integer, as every gain is.
- * Not offered: a device-pointer form; a yaw sweep at a fixed eye; ranking by travel cost (read isdf_frontend_field_value at the best
+ * Not offered: a device-pointer form; a yaw sweep at a fixed eye; ranking by travel cost (isdf_view_select_routed does that over the best
  * eyes); eyes tested against the robot's configuration space rather than a voxel cube; a pessimistic or weighted gain; candidates kept
  * across scans. */
 typedef struct isdf_view_candidates_params {
@@ -2085,8 +2085,8 @@ int isdf_view_candidates_host(const uint32_t *bits, const uint8_t *occ, const do
  * read-only: K, the occupancy, `merges`, epochs, a kept field, an armed watch and every kept report are untouched.  The scratch (its own
  * and the view gain's) grows only and the list keeps its content when it grows: a second call of a size allocates nothing
  * (isdf_debug_live_bytes).  Two runs give the same bytes: the order of a segment's entries depends on atomics and nothing reads it.
- * Not offered: a device-pointer form; a travel-cost or otherwise weighted objective; lazy-greedy pruning of the marginals; sets kept
- * across calls. */
+ * Not offered: a device-pointer form; a weighted objective other than isdf_view_select_routed's gain per travel cost (below); lazy-greedy
+ * pruning of the marginals; sets kept across calls. */
 typedef struct isdf_view_select_params {
     isdf_view_gain_params gain;   /* strides, max_range_m, scratch_bytes: isdf_view_gain's, with its defaults */
     int32_t k_select;             /* default 4; >= 1 */
@@ -2114,6 +2114,76 @@ int isdf_view_select(isdf_ctx *ctx, const isdf_depth_camera *camera, const doubl
 int isdf_view_select_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
                           const isdf_depth_camera *camera, const double *poses, long long n_views, const isdf_view_select_params *params, int64_t *rows_out,
                           int64_t *select_out, int64_t *round_out, uint32_t *claimed_out, isdf_view_select_info *info_out);
+
+/* ---- the routed view selection: greedy coverage by marginal gain per travel cost ----------------------------------- */
+/* isdf_view_select does not know where the robot is: a view across the map with a few more unknown voxels beats one two metres away,
+ * and a view whose eye the robot cannot reach is picked like any other (isdf_view_candidates tests an eye against the occupancy and a
+ * voxel cube, not against the configuration space, so a gated field's d can be +inf at an eye that passed).  isdf_view_select_routed
+ * is that selection by UTILITY = marginal gain per travel cost, the cost read on the device from the ctx's valid cost-to-go field at
+ * each view's eye, and the ways to the picked views read off the same field in the same stream.  The caller builds the field TOWARDS THE
+ * ROBOT'S CELL first (isdf_frontend_field_build or _build_known): the graph is symmetric, so d[eye] is the cost of going there.
+ *   The sets U_j, the rows, the claimed grid and its layout, and the meaning of select_out and round_out are isdf_view_select's.
+ *   COST.  c_j is a non-negative double or +inf, in the field's unit, CELLS.  With cost == NULL, c_j is the ctx's field at the cell of
+ *   the eye (poses[12 j + 3], [12 j + 7], [12 j + 11]) - to the byte what isdf_frontend_field_value answers for that point, +inf for an
+ *   eye outside the map.  With cost != NULL, c_j = cost[j], a host array of n_views doubles; no field is needed then.
+ *   ELIGIBLE.  A view is eligible when it is scored (row status 0), not picked so far, c_j is finite and c_j <= max_cost.
+ *   ROUND r.  m_j = |U_j \ C_r| for every eligible view.  Among the eligible views with m_j >= min_gain, u_j = (double)m_j / (cost0 +
+ *   c_j): one IEEE addition, then one IEEE division, in fp64 (m_j < 2^36: the conversion is exact).  j* is the lowest index among the
+ *   largest u_j.  If there is no such view the selection ends with n_selected = r; otherwise round r picks j* and C_{r+1} = C_r | U_j*.
+ *   OUTPUTS, all nullable, host memory.
+ *     rows_out, select_out (the same four int64 per round), round_out, claimed_out: as isdf_view_select gives them.
+ *     cost_out: n_views doubles, c_j of every view, scored or not.
+ *     util_out: k_select x 2 doubles, {c_j*, u_j*} per round; {0, 0} for a round that did not happen.
+ *     with path_cap >= 1 (cost == NULL only), for the picked views in pick order: path_n_out k_select int32, path_xyz_out k_select x
+ *       path_cap x 3 doubles, path_rp_out k_select x path_cap x 2 doubles - exactly what isdf_frontend_field_paths gives with the picked
+ *       eyes as starts and cap = path_cap.  The walk goes FROM THE EYE TO THE ROBOT'S CELL (the field's goal), and the attitudes are those
+ *       of walking that way; a caller that drives robot -> eye reverses the rows.  Rounds that did not happen: n = 0 and zeros.
+ *     info_out: select = isdf_view_select_info's words; n_eligible = the eligible views at round 0; n_unreachable = the scored views
+ *       whose c is not finite; n_over_budget = the scored views with a finite c > max_cost; cost_selected = the sum of the picked c_j in
+ *       pick order; cost_source = 0 (field) or 1 (array); cost_ms, paths_ms = device time of the cost kernel and of the path launches
+ *       (events on the ctx's stream; 0 in the host form and where the stage did not run).
+ *   ERRORS, all before anything is launched, in this order: everything isdf_view_select refuses, in its order; ISDF_ERR_INVALID_ARG for
+ *   min_gain < 1 (with a utility 0 is "none", and a view that adds nothing is not worth a trip), cost0 <= 0 or not finite, a NaN or
+ *   negative max_cost, path_cap < 0, path_cap >= 1 together with a cost array, a cost array holding a NaN or a negative value; with
+ *   cost == NULL what the field's getters answer: ISDF_ERR_STATE without a front end or without a valid field (a dropped field is no
+ *   field).  n_views = 0 is legal: nothing is launched, the outputs are padded, claimed_out = K.
+ * On the device: one lane per view reads c_j through the field's own cell rule; the marginal kernel skips ineligible views; the pick is
+ * two integer reductions without atomics (the bit pattern of u, which orders as u does for u >= 0, then the lowest index among the
+ * equals); the picked eyes are gathered on the device as starts for the path kernel, which follows the rounds with no hand-over and
+ * rides the final copy.  The call is read-only, as the selection is: the field, K, the epochs, a kept report and an armed watch are
+ * untouched; a gated and an ungated field are both accepted.  The scratch grows only: a second call of a size allocates nothing
+ * (isdf_debug_live_bytes).  isdf_view_select itself launches what it always launched.
+ * isdf_view_select_routed_host: plain host code, the same bytes; cost is required (isdf_frontend_field_host gives a field to read it
+ * from), there are no paths, cost_source = 1.
+ * Not offered: a tour whose cost is counted from the previous pick (it needs a field per round); other utilities (linear, exponential);
+ * a device-pointer form. */
+typedef struct isdf_view_select_routed_params {
+    isdf_view_select_params select;   /* isdf_view_select's, with its defaults; min_gain >= 1 here */
+    double  cost0;                    /* default 1.0; finite, > 0: the cost of standing still, in cells */
+    double  max_cost;                 /* default +inf: no budget; >= 0 */
+    int32_t path_cap;                 /* default 0: no paths; else the rows per path */
+    int32_t reserved[5];
+} isdf_view_select_routed_params;
+
+typedef struct isdf_view_select_routed_info {
+    isdf_view_select_info select;
+    int64_t n_eligible, n_unreachable, n_over_budget;
+    double  cost_selected;
+    int32_t cost_source, reserved;
+    double  cost_ms, paths_ms;
+} isdf_view_select_routed_info;
+
+void isdf_view_select_routed_params_default(isdf_view_select_routed_params *p);     /* null-safe */
+void isdf_view_select_routed_sizes(int sizes_out[2]);                               /* null-safe; sizeof of the params and of the info */
+int isdf_view_select_routed(isdf_ctx *ctx, const isdf_depth_camera *camera, const double *poses, long long n_views, const double *cost,
+                            const isdf_view_select_routed_params *params, int64_t *rows_out, int64_t *select_out, int64_t *round_out, uint32_t *claimed_out,
+                            double *cost_out, double *util_out, int32_t *path_n_out, double *path_xyz_out, double *path_rp_out,
+                            isdf_view_select_routed_info *info_out);
+/* ISDF_OK, or ISDF_ERR_INVALID_ARG (a null bits, occ or cost, a bad geometry, the bad arguments above) with nothing written. */
+int isdf_view_select_routed_host(const uint32_t *bits, const uint8_t *occ, const double bmin[3], const double bmax[3], double resolution, const int32_t dims[3],
+                                 const isdf_depth_camera *camera, const double *poses, long long n_views, const double *cost,
+                                 const isdf_view_select_routed_params *params, int64_t *rows_out, int64_t *select_out, int64_t *round_out, uint32_t *claimed_out,
+                                 double *cost_out, double *util_out, isdf_view_select_routed_info *info_out);
 
 /* ---- planning through observed space only: the eroded known grid and the field gated by it ------------------------ */
 /* The configuration-space table knows "occupied" and "not occupied": a voxel behind a wall no sensor has looked behind is free to it,
